@@ -4,6 +4,7 @@
     python bench.py --gpus 1 --steps 200 --warmup 20
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR    (+ what the last timed step computed, as DIR/*.npy)
 
 Headline workload (BASELINE.json configs[2], the configuration the metric is quoted on): REALRobot2020-R2J3-v0, 4096 envs
 per GPU, 3 objects, 128x128 top-down RGB + depth rendered every step; one "step" = one env.step() of every env in the
@@ -173,6 +174,36 @@ def heavy_counts(env, nat):
     """Envs the last step solved / rendered on the side streams (RR_F_ENV_CLASS: 1 heavy, 2 very heavy)."""
     cls = env.host(nat.F_ENV_CLASS)
     return {"heavy": int((cls == 1).sum()), "very_heavy": int((cls == 2).sum())}
+
+
+DUMP_BYTES = 64 * 10 ** 6          # --dump-outputs: at most this much in all, half for the low-dimensional arrays, half for images
+DUMP_IMAGE_ENVS = 64                # ... images of at most this many envs
+
+
+def dump_outputs(out_dir, env, nat, n_local, w, h, render):
+    """--dump-outputs: the observations the last timed step gave its caller (float32 .npy files under out_dir): joints [n, 9],
+    touch [n, 4] and object poses [n, objects, 7] of every env (of a seeded sample of envs when they would not fit), and when the
+    step rendered, RGB [m, h, w, 3] and depth [m, h, w] of a seeded sample of m envs; the env indices are `env_ids` and
+    `image_env_ids` (float64).  The samples depend on the arguments only, so two builds can be compared file for file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(0)
+    low = {'joints': env.host(nat.F_JOINTS), 'touch': env.host(nat.F_TOUCH), 'object_poses': env.host(nat.F_OBJ_POSE)}
+    per_env = sum(a[0].size for a in low.values()) * 4 + 8
+    n_low = min(n_local, (DUMP_BYTES // 2) // per_env)
+    ids = np.arange(n_local) if n_low == n_local else np.sort(rng.choice(n_local, n_low, replace=False))
+    out = {name: a[ids].astype(np.float32) for name, a in low.items()}
+    out['env_ids'] = ids.astype(np.float64)
+    if render:
+        n_img = min(n_local, DUMP_IMAGE_ENVS, (DUMP_BYTES // 2) // (w * h * 4 * 4 + 8))
+        img_ids = np.sort(rng.choice(n_local, n_img, replace=False))
+        out['rgb'] = env.host(nat.F_RGB)[img_ids].astype(np.float32)
+        out['depth'] = env.host(nat.F_DEPTH)[img_ids].astype(np.float32)
+        out['image_env_ids'] = img_ids.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return sorted(out)
 
 
 def load_profile(name, cfg):
@@ -412,6 +443,9 @@ def main():
                          '(images) or as per-step records of the changed pixels applied to persistent copies (images-delta)')
     ap.add_argument('--stub-env', action='store_true',
                     help='plumbing test on CPU (gloo): a stub replaces the simulator; the printed line is marked as such')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the observations of the last timed step as DIR/<name>.npy (float32; '
+                         'images of a fixed, seeded sample of envs) so that two builds can be compared output for output')
     args = ap.parse_args()
     if args.image:
         global W, H
@@ -554,6 +588,9 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
     assert (env.host(nat.F_ERRFLAGS) == 0).all(), "an env reported a non-finite state"
+    if args.dump_outputs and rank == 0:
+        # (before the timing pass below steps the envs further; rank 0's envs)
+        dump_outputs(args.dump_outputs, env, nat, n_local, W, H, render)
     timed_steps = [args.presettle + args.warmup, args.presettle + args.warmup + args.steps]
     if stub:
         if rank == 0:

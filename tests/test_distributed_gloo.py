@@ -177,6 +177,36 @@ def test_bench_plumbing_four_ranks_gather_images_and_plan_check():
     assert out2["config"]["gathered_bytes_per_step_per_rank"] == 24 * (9 + 4 + 21) * 4 + 4 * (1 * 12 + 8)
 
 
+def test_bench_dump_outputs_stub_env(tmp_path):
+    """`bench.py --dump-outputs DIR` on CPU (--stub-env, one rank): the last timed step's observations as float32 / float64 .npy
+    files, at most 64 MB in all (at 320x240 the images of a seeded sample of envs only), the same files from two runs with the
+    same arguments, and a result line whose `steps` / `ms_per_step` describe the timed region."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k in range(2):
+        out_dir = tmp_path / ('d%d' % k)
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '7', '--warmup', '2', '--presettle', '3',
+               '--envs-per-gpu', '100', '--image', '320x240', '--stub-env', '--dump-outputs', str(out_dir)]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300,
+                           env=dict(os.environ, OMP_NUM_THREADS='1'), cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith('{')][0])
+        assert out["steps"] == 7 and out["timed_steps"] == [5, 12] and out["ms_per_step"] > 0
+        runs.append({p.stem: np.load(str(p)) for p in sorted(out_dir.glob('*.npy'))})
+    a, b = runs
+    assert sorted(a) == ['depth', 'env_ids', 'image_env_ids', 'joints', 'object_poses', 'rgb', 'touch']
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 * 10 ** 6
+    assert a['joints'].shape == (100, 9) and a['touch'].shape == (100, 4) and a['object_poses'].shape == (100, 3, 7)
+    m = len(a['image_env_ids'])
+    assert 0 < m < 100 and a['rgb'].shape == (m, 240, 320, 3) and a['depth'].shape == (m, 240, 320)
+    assert np.array_equal(a['env_ids'], np.arange(100)) and np.any(a['joints'] != 0)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+
+
 def test_plan_check_names_every_violation():
     """bench.check_plan: what makes `bench.py --gpus N` exit non-zero before the first step."""
     import importlib.util

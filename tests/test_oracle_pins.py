@@ -351,9 +351,10 @@ def test_collision_hull_reduction_error():
     """Bullet collides the full convex hull of every OBJ; the compiled model keeps <= 192 vertices (an inner
     approximation) and <= 192 facet planes (an outer approximation) per shape.  The deviation of either from the full hull,
     recorded by tools/compile_model.py in the blob, must stay below 1 mm for every shape (0.3 mm for the shapes the task
-    touches: objects, gripper, fingers, skins, table, shelf).  Where the reference's OBJ files are present (the build
-    container) the numbers are re-measured independently: support functions of the full hull, of the vertex subset and
-    (by linear programming) of the plane subset along 120 random directions."""
+    touches: objects, gripper, fingers, skins, table, shelf).  For the three objects the numbers are re-measured
+    independently against the full hull vertex sets of the reference's OBJ files (tests/golden/full_hulls.npz, written by
+    tools/compile_model.py with RR_FULL_HULLS_OUT): support functions of the full hull, of the vertex subset and (by linear
+    programming) of the plane subset along 120 random directions."""
     import os
     from real_robots_amd.model import load_model
     m = load_model()
@@ -366,24 +367,18 @@ def test_collision_hull_reduction_error():
     task = [s for s in range(ns) if s not in arm]
     assert dev[task].max() < 3.1e-4, dev[task].max()
     assert nv.max() <= 192 and nf.max() <= 192 and int(m['dims'][8]) == 192 and int(m['dims'][9]) == 192
-    ref = '/root/reference/real_robots/data/kuka_gripper_description/meshes'
-    if not os.path.isdir(ref):
-        return
     from scipy.optimize import linprog
-    from scipy.spatial import ConvexHull
     rng = np.random.default_rng(0)
     D = rng.normal(size=(120, 3))
     D /= np.linalg.norm(D, axis=1, keepdims=True)
-
-    def obj_points(name, scale):
-        pts = [[float(x) for x in line.split()[1:4]] for line in open(os.path.join(ref, name)) if line.startswith('v ')]
-        return np.array(pts) * np.array(scale)
+    hulls = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'full_hulls.npz'))
+    names = [str(n) for n in hulls['names']]
+    assert len(names) == ns
 
     # objects: the OBJ is used unscaled in the object frame (cube.urdf, tomato.urdf, mustard.urdf)
-    for s, (fn, scale) in zip(range(ns - 3, ns), (('cube.obj', (1, 1, 1)), ('tomato.obj', (1, 1, 1)), ('mustard.obj', (1, 1, 1)))):
-        pts = obj_points(fn, scale)
-        hv = pts[ConvexHull(pts).vertices]
-        full = (hv @ D.T).max(0)
+    for s, fn in zip(range(ns - 3, ns), ('cube', 'tomato', 'mustard')):
+        assert names[s] == fn
+        full = (hulls['hull_%d' % s].astype(np.float64) @ D.T).max(0)
         sub = (m['shape_verts'][s][:nv[s]] @ D.T).max(0)
         assert (full - sub).max() < 1.0e-3 and (full - sub).min() > -1e-6, (fn, (full - sub).max())
         pl = m['shape_planes'][s][:nf[s]].astype(np.float64)
