@@ -247,7 +247,7 @@ int rr_step_plan_masked(rr_env *env, const uint8_t *idle_mask_host, int32_t rend
  * milliseconds and launch counts per kernel since the last call and resets them.
  * kernel ids: 0 prep (state part: forward kinematics, object terms, joint-space dynamics), 1 collide, 2 solve (command part --
  * rate limit, clipping, motor targets -- then rows, Gauss-Seidel, integration), 3 render_setup, 4 raster, 5 image set-up outside
- * the two render kernels (the full static copy of the first frame; the separate restore pass with RR_SEPARATE_RESTORE), 6 shade.
+ * the two render kernels (the full static copy of the first frame, and of every frame with RR_FULL_COPY), 6 shade.
  * When the step would run its heavy envs on the side stream, the timed step runs the same launches one
  * after the other: 2 / 3 / 4 / 6 then hold what the main stream runs (the light envs), 7 the solve and 8 the render
  * (set-up + raster + shade) of the heavy envs, which run beside them in an untimed step.  0 and 1 are the LOOK-AHEAD of the

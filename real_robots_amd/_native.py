@@ -19,8 +19,8 @@ RR_ABI_VERSION = 6
  F_ENV_CLASS, F_PREP) = range(13)
 PREP_FLOATS = 378          # RR_F_PREP: frames 165, M^-1 121, qd* 11, object terms 81 -- in this order (realrobot.hip S_*)
 NUM_KERNELS = 9
-# id 5 = image set-up outside the two render kernels: the full static copy of the first frame (and the earlier schemes
-# RR_FULL_COPY / RR_SEPARATE_RESTORE); it does not run in steady state
+# id 5 = image set-up outside the two render kernels: the full static copy of the first frame (and of every frame with the
+# earlier scheme RR_FULL_COPY); it does not run in steady state
 KERNEL_NAMES = ('k_prep', 'k_collide', 'k_solve', 'k_render_setup', 'k_raster', 'k_image_setup', 'k_shade',
                 'k_solve_heavy', 'render_heavy')      # 7, 8: the heavy envs' solve / render (side streams in an untimed step);
                                                       # k_prep / k_collide = the look-ahead of the next step

@@ -21,7 +21,7 @@
 //                                    meshlet clusters, fragment list out (winners + pixels vacated since the last frame)
 //   k_shade         deferred shading of the fragment lists; vacated / occluded pixels go back to the static layer
 //                                    (the images persist in HBM: k_static_copy, the full copy, only runs for the first
-//                                    frame; k_restore is the separate-pass variant kept for RR_SEPARATE_RESTORE)
+//                                    frame)
 //   k_render_list / k_raster_list  the same three stages for the envs of a heavy list (side streams): one list-walking
 //                                    launch for a short list, list-walking visibility + the grid kernels for a long one
 // The arithmetic restates what the reference delegates to pybullet.stepSimulation / getCameraImage
@@ -73,7 +73,7 @@ struct BodyParams {   // passed by value as kernel argument -> scalar loads, uni
 };
 
 struct SimParams {
-    int N, nobj, iters, npairs, ablate, small_area, os_cap, edge_contacts, heavy_min, heavy2_min, coop_build;
+    int N, nobj, iters, npairs, ablate, os_cap, edge_contacts, heavy2_min;
     float warmstart;   // Bullet's m_warmstartingFactor (0.85); 0: cold start every step   // os_cap: object-vs-static contacts per env with rows in LDS (<= OS_CAP)
     float dt, gravity, erp, margin, kp, kd, max_impulse, lin_damp, ang_damp, rest_thresh;
 };
@@ -96,10 +96,9 @@ struct ShapeData {    // global memory, read uniformly
 struct RenderModel {
     int ni, nt, W, H, tile_h, ntiles, first_dynamic_tri;
     int tile_w, ntx;         // raster tiles are tile_w x tile_h pixels, ntx of them across: full-width strips up to 128 columns, 64 x 64 squares above (rr_create)
-    int in_otype[MAXINST], in_oidx[MAXINST], in_uid[MAXINST], in_tex[MAXINST], in_cull[MAXINST];
+    int in_otype[MAXINST], in_oidx[MAXINST], in_uid[MAXINST], in_tex[MAXINST];
     int tile_xbits;          // bits of a column within a tile (2^tile_xbits >= tile_w); a row within a tile then fits 14 - tile_xbits bits (tile_w * tile_h <= 4096)
     unsigned w_magic;        // ceil(2^32 / tile_w): row of a pixel-in-tile index = __umulhi(index, w_magic), exact for index < 2^20 and tile_w <= 1024
-    int any_cull;            // some in_cull is set (RR_CULL): the window loop looks the flag of its instance up only then
     float in_color[MAXINST][3];
     int tex_off[16], tex_w[16], tex_h[16];
     int link_body[NLINK_MAX];
@@ -440,7 +439,7 @@ __device__ __forceinline__ void dispatch_order_class(int x, int N, int ntiles, i
 // The translation unit is kept in parts (one library, one compilation: the kernels share structs, device math and macros):
 #include "rr_prep.inc"    // k_prep: the state part of a step (forward kinematics, object terms, joint-space dynamics)
 #include "rr_collide.inc"    // k_collide: the collision pass (contact lists, warm-start matching, env classes)
-#include "rr_solve.inc"    // k_solve / k_solve_light / k_solve_light_ow: command part, row build, projected Gauss-Seidel, integration
+#include "rr_solve.inc"    // k_solve / k_solve_rs / k_solve_light_ow: command part, row build, projected Gauss-Seidel, integration
 #include "rr_state.inc"    // reset / state io / observation kernels, render set-up
 #include "rr_ik.inc"    // inverse kinematics and macro plans (K8)
 #include "rr_render.inc"    // rasteriser: k_raster, k_shade, the list-walking render kernels

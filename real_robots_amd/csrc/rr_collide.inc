@@ -30,7 +30,7 @@ __device__ __forceinline__ Xf load_xf(const ShapeData *S, int s, const float *sc
 __device__ unsigned long long g_sprof[16];
 #define SPROF(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); sp_acc[i] += (unsigned)(now_ - sp_t0); sp_t0 = now_; } while (0)   /* cheap phase clock: s_memtime into per-wave accumulators, flushed once (SBLK_END); RR_ABLATE = block << 16 | 0x4000: one block only */
 #define SPROF_INIT unsigned long long sp_t0 = __builtin_readcyclecounter(); unsigned sp_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define SPROF_FLUSH do { if ((threadIdx.x & 63) == 0 && (threadIdx.x >> 6) == ((OW && LIGHT_OW_THREADS == 384) ? 1 : 0) && (!(P.ablate & 0x4000) || (int)blockIdx.x == (P.ablate >> 16))) { _Pragma("unroll") for (int i_ = 0; i_ < 12; i_++) atomicAdd(&g_sprof[i_], (unsigned long long)sp_acc[i_]); } } while (0)
+#define SPROF_FLUSH do { if ((threadIdx.x & 63) == 0 && (threadIdx.x >> 6) == ((!GEN && LIGHT_OW_THREADS == 384) ? 1 : 0) && (!(P.ablate & 0x4000) || (int)blockIdx.x == (P.ablate >> 16))) { _Pragma("unroll") for (int i_ = 0; i_ < 12; i_++) atomicAdd(&g_sprof[i_], (unsigned long long)sp_acc[i_]); } } while (0)
 // per solver workgroup: {total cycles, cycles up to the end of the row build, cycles of the PGS loop, -, then per env
 // nc | generic contacts << 8 | leading object-vs-static contacts << 16 | last F-list length << 24}
 __device__ unsigned g_sblk[4096 * 8];
@@ -706,12 +706,12 @@ __device__ __forceinline__ void collide_env(const SimParams &P, const DevPtrs &D
     }
     CPROF_END;
     if (tid == 0) {
-        // "heavy": more generic contacts than P.heavy_min (an env with a few generic rows lengthens its wave's chain by a
-        // quarter, an arm pressed on the table fourfold -- only the latter are worth the side stream when many envs have some)
+        // "heavy": any generic contact (an env with a few generic rows lengthens its wave's chain by a quarter, an arm pressed on
+        // the table fourfold; thresholds of 3 / 6 / 10 generic contacts were measured slower at every horizon but the longest)
         // generic contacts = all but the object-vs-static ones the solver's object lanes take: up to KOS = 4 per object and
         // P.os_cap in all, in list order (those pairs come first) -- the row builder's rule, so that a "light" env has none
         ngen = nct - min(P.os_cap, min(oscnt0, 4) + min(oscnt1, 4) + min(oscnt2, 4));
-        const bool heavy = ngen > P.heavy_min;
+        const bool heavy = ngen > 0;
         D.ccount_next[env] = nct;
         // (the very heavy list is capped at VH_MAX entries -- its solve is launched with one wave per entry; beyond that an env is
         // just "heavy": classes are scheduling, never a result)

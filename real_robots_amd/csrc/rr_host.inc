@@ -61,17 +61,15 @@ struct rr_env {
     float *score_out; unsigned char *score_mask;                               // lazily allocated (rr_evaluate_goals)
     std::vector<void *> allocs;
     bool timing;
-    bool full_copy, sep_restore;   // RR_FULL_COPY / RR_SEPARATE_RESTORE at create: the two earlier image-update schemes (tests, A/B)
+    bool full_copy;                // RR_FULL_COPY at create: the earlier image-update scheme, the static layer copied into every image before each frame (tests)
     int split_max_pct;             // the heavy / light split is used while at most this share of the solver groups is heavy (RR_SPLIT_MAX_PCT)
     int *h_hcount;                 // pinned host copy of D.hcount[0] (device-mapped: written by k_prep_a of the following step)
     bool prep_scalar;              // RR_PREP_SCALAR=1: the thread-per-env preparation kernels instead of k_prep16 (A/B, tests)
-    bool light_ow;                 // k_solve_light_ow available and wanted (RR_NO_OBJECT_WAVE=1: k_solve_light; A/B, tests)
     bool split_heavy;              // heavy solver groups + their render on the side stream (RR_NO_SPLIT=1 turns it off: A/B, tests)
     bool images_valid;       // every env's image holds its previous frame (static layer + the pixels of its fragment list)
     hipEvent_t ev[2 * RR_NUM_KERNELS];
     hipStream_t aux;         // side stream: the HBM-bound static-layer copy runs beside the VALU-bound physics / visibility kernels
     hipEvent_t ev_fork, ev_join, ev_dyn, ev_join2, ev_vsolved, ev_hsolved, ev_rast;
-    bool la_after_raster;          // placement 1: the look-ahead waits for the light envs' visibility pass (RR_LA_AFTER_RASTER=0: for the solves only)
     hipStream_t aux2;              // the very heavy envs' solve + render (RR_HEAVY2_MIN)
     std::vector<hipStream_t> unused_streams;   // RR_SKIP_QUEUES: created only to take hardware queue ids
     // Look-ahead (DESIGN.md 5.2): the state part of step t+1 (k_prep_ab, k_collide) runs on the side streams behind the render
@@ -83,8 +81,6 @@ struct rr_env {
     // cost-ordered dispatch of k_raster (RR_NO_RASTER_ORDER=1: env-major grid)
     unsigned *item_perm;           // [8 * ceil(N / 8) * ntiles] the order, written by the extra workgroups of k_shade
     bool ord_valid, ord_pending;   // item_perm holds an order; a k_raster has left costs that the next k_shade launch turns into one
-    bool ext_events;               // events bound to the launches they follow (LAUNCH_EV); RR_NO_EXT_EVENTS: recorded by markers
-    bool no_fused_setup;           // RR_NO_FUSED_SETUP: separate k_render_setup launches instead of the solve kernels' tails
     bool collide_ordered;          // RR_COLLIDE_ORDER=0: k_collide in env order (default: by falling duration of the env's last collision pass)
     void *obs_host;                // rr_map_observations: mapped pinned block {joints [N][9], touch [N][4], poses [N][nobj][7], timestep [N], errflags [N]} or nullptr
     ObsMirror obs_dev;             // its device-visible addresses
@@ -263,19 +259,17 @@ static ImageOut env_images(const rr_env *e) {
     return o;
 }
 
-// (Re)builds the shared static layer for the current camera: background everywhere, then -- unless disabled with
-// RR_NO_STATIC_LAYER -- the never-moving instances (table, shelf, robot base; the eye camera is fixed, env.py:136-141,
-// 253-255) are rasterised and shaded once; their visibility keys seed every env's frame.
+// (Re)builds the shared static layer for the current camera: background everywhere, then the never-moving instances (table,
+// shelf, robot base; the eye camera is fixed, env.py:136-141, 253-255) are rasterised and shaded once; their visibility keys
+// seed every env's frame.
 static int build_static_layer(rr_env *e) {
     hipLaunchKernelGGL(k_background, dim3(64), dim3(256), 0, e->stream, e->RM_dev, e->D);
-    if (e->D.static_vis_out) {
-        ImageOut so;
-        so.rgb = e->D.static_rgb; so.depth = e->D.static_depth; so.mask = e->D.static_mask; so.env_stride = 0;
-        e->D.static_vis = nullptr;
-        hipLaunchKernelGGL(k_render_setup, dim3((e->P.N * MAXINST + 63) / 64), dim3(64), 0, e->stream, e->B, e->P, e->RM_dev, e->D, 0);
-        hipLaunchKernelGGL(k_raster, dim3(1, e->RM.ntiles), dim3(RASTER_THREADS), 0, e->stream, e->P, e->RM_dev, e->D, e->n_inst_used, 1, 0, 0, 0);
-        hipLaunchKernelGGL(k_shade, dim3(1, e->RM.ntiles, SHADE_SPLIT), dim3(SHADE_THREADS), 0, e->stream, e->RM_dev, e->D, so, 0, 0, 0, 0, (unsigned *)nullptr);
-    }
+    ImageOut so;
+    so.rgb = e->D.static_rgb; so.depth = e->D.static_depth; so.mask = e->D.static_mask; so.env_stride = 0;
+    e->D.static_vis = nullptr;
+    hipLaunchKernelGGL(k_render_setup, dim3((e->P.N * MAXINST + 63) / 64), dim3(64), 0, e->stream, e->B, e->P, e->RM_dev, e->D, 0);
+    hipLaunchKernelGGL(k_raster, dim3(1, e->RM.ntiles), dim3(RASTER_THREADS), 0, e->stream, e->P, e->RM_dev, e->D, e->n_inst_used, 1, 0, 0, 0);
+    hipLaunchKernelGGL(k_shade, dim3(1, e->RM.ntiles, SHADE_SPLIT), dim3(SHADE_THREADS), 0, e->stream, e->RM_dev, e->D, so, 0, 0, 0, 0, (unsigned *)nullptr);
     // the pass above used env 0's fragment list; from here on the lists describe what differs from the static layer
     if (hipMemsetAsync(e->D.frag_count, 0, (size_t)e->P.N * e->RM.ntiles * sizeof(unsigned), e->stream) != hipSuccess ||
         hipStreamSynchronize(e->stream) != hipSuccess) return fail(RR_EDEVICE, "static layer pass failed");
@@ -323,19 +317,15 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
     e->timing = false; e->step_err = hipSuccess; e->step_err_what = nullptr;
     memset(e->pin_buf, 0, sizeof e->pin_buf); memset(e->pin_ev, 0, sizeof e->pin_ev); memset(e->pin_used, 0, sizeof e->pin_used); e->pin_next = 0; e->pin_bytes = 0;
     e->full_copy = getenv("RR_FULL_COPY") != nullptr;
-    e->sep_restore = getenv("RR_SEPARATE_RESTORE") != nullptr;
     e->split_heavy = getenv("RR_NO_SPLIT") == nullptr;
     e->lookahead = getenv("RR_NO_LOOKAHEAD") == nullptr;
     e->item_perm = nullptr; e->ord_valid = e->ord_pending = false;
-    e->no_fused_setup = getenv("RR_NO_FUSED_SETUP") != nullptr;
-    e->la_after_raster = !(getenv("RR_LA_AFTER_RASTER") && atoi(getenv("RR_LA_AFTER_RASTER")) == 0);
     e->prep_scalar = getenv("RR_PREP_SCALAR") && atoi(getenv("RR_PREP_SCALAR")) != 0;
-    e->ext_events = getenv("RR_NO_EXT_EVENTS") == nullptr;
     e->collide_ordered = !(getenv("RR_COLLIDE_ORDER") && atoi(getenv("RR_COLLIDE_ORDER")) == 0);
     e->force_hcount[0] = e->force_hcount[1] = -1;
     e->run_ahead = getenv("RR_RUN_AHEAD") ? std::max(0, std::min(atoi(getenv("RR_RUN_AHEAD")), RUN_AHEAD_MAX)) : 8;
     e->step_no = 0;
-    e->coop_all = !(getenv("RR_COOP_ALL") && atoi(getenv("RR_COOP_ALL")) == 0) && getenv("RR_NO_COOP") == nullptr;
+    e->coop_all = !(getenv("RR_COOP_ALL") && atoi(getenv("RR_COOP_ALL")) == 0);
     e->obs_host = nullptr; memset(&e->obs_dev, 0, sizeof e->obs_dev);
     e->img_host[0] = e->img_host[1] = e->img_host[2] = nullptr;
     e->img_sel = 7;
@@ -397,13 +387,10 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
     if (cfg->solver_flags & RR_SOLVER_NO_RATE_LIMIT)      // env.py:314-321 skipped: +-inf never clips (fminf / fmaxf of the command part)
         for (int k = 0; k < 9; k++) B.act_maxdiff[k] = INFINITY;
     P.ablate = getenv("RR_ABLATE") ? atoi(getenv("RR_ABLATE")) : 0;
-    P.small_area = std::min(64, getenv("RR_SMALL_AREA") ? atoi(getenv("RR_SMALL_AREA")) : SMALL_AREA);      // (<= 64: a record's box width has 6 bits)
-    // RR_SOLVER_POOL (tests): LDS floats for object-vs-static rows, 60 per contact; contacts beyond it take the generic (slot layout) path
-    P.heavy_min = getenv("RR_HEAVY_MIN") ? atoi(getenv("RR_HEAVY_MIN")) : 0;
     P.heavy2_min = getenv("RR_HEAVY2_MIN") ? atoi(getenv("RR_HEAVY2_MIN")) : 16;      // generic contacts above which an env is "very heavy" (1000: never; A/B 6..30: 13-16 best)
     P.warmstart = getenv("RR_NO_WARMSTART") ? 0.0f : upstream(cfg->warmstart, 0.85f);       // (the variable: diagnostics, cold start every step)
-    P.coop_build = getenv("RR_NO_COOP") ? 0 : 1;                  // (A/B, tests: very heavy envs four to a wave like the heavy ones)
     P.edge_contacts = getenv("RR_NO_EDGE_CONTACTS") ? 0 : 1;       // (diagnostics: vertex candidates only)
+    // RR_SOLVER_POOL (tests): LDS floats for object-vs-static rows, 60 per contact; contacts beyond it take the generic (slot layout) path
     P.os_cap = getenv("RR_SOLVER_POOL") ? std::max(0, std::min(atoi(getenv("RR_SOLVER_POOL")) / 60, (int)OS_CAP)) : OS_CAP;
     P.lin_damp = upstream(cfg->lin_damping, 0.04f); P.ang_damp = upstream(cfg->ang_damping, 0.04f); P.rest_thresh = 0.2f;
     e->epb = cfg->envs_per_block > 0 ? cfg->envs_per_block : 64;
@@ -476,9 +463,6 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
     NEED(ip = b.i32("inst_owner", ni * 4));
     for (int i = 0; i < ni; i++) { RM.in_otype[i] = ip[4 * i]; RM.in_oidx[i] = ip[4 * i + 1]; RM.in_uid[i] = ip[4 * i + 2]; RM.in_tex[i] = ip[4 * i + 3]; }
     NEED(f = b.f32("inst_color", ni * 3)); memcpy(RM.in_color, f, (size_t)ni * 12);
-    // Back-face culling of closed meshes is opt-in (RR_CULL=1): it is invisible unless the near plane cuts through a
-    // mesh (then TinyRenderer shows the inside faces), so the default keeps exact parity with the two-sided oracle.
-    if (getenv("RR_CULL")) { NEED(ip = b.i32("inst_cull", ni)); memcpy(RM.in_cull, ip, (size_t)ni * 4); for (int i = 0; i < ni; i++) RM.any_cull |= ip[i] != 0; }
     NEED(ip = b.i32("tex_info", ntex * 3));
     for (int t = 0; t < ntex; t++) { RM.tex_off[t] = ip[3 * t]; RM.tex_w[t] = ip[3 * t + 1]; RM.tex_h[t] = ip[3 * t + 2]; }
     {   // a one-texel texture (the arm's colours: tools/compile_model.py stores uniform images as 1 x 1) travels with the instance
@@ -612,17 +596,16 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
         }
     }
     for (int i = 0; i < 2 * RR_NUM_KERNELS; i++) hipEventCreate(&e->ev[i]);
-    if (!getenv("RR_NO_AUX_STREAM")) {
+    {
         // fork / join events order two streams of the same device: no timing, no system-scope fence (the cache writeback
         // and invalidation a default event performs when it is recorded costs ~6 us on the stream that records it)
-        const unsigned evf = getenv("RR_EVENT_FLAGS") ? (unsigned)strtoul(getenv("RR_EVENT_FLAGS"), nullptr, 0) : (hipEventDisableTiming | hipEventDisableSystemFence);
+        const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
         // the side stream carries the step's longest chain (the heavy envs' solve, then their render): with a higher
-        // priority its few workgroups are dispatched ahead of the main stream's render when both are ready (RR_AUX_PRIORITY=0: same)
+        // priority its few workgroups are dispatched ahead of the main stream's render when both are ready
         int prio_lo = 0, prio_hi = 0;
         hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        const int prio = getenv("RR_AUX_PRIORITY") && atoi(getenv("RR_AUX_PRIORITY")) == 0 ? prio_lo : prio_hi;
         // (a runtime without stream priorities: plain non-blocking streams)
-        auto side_stream = [&](hipStream_t *st) { return hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio) == hipSuccess || hipStreamCreateWithFlags(st, hipStreamNonBlocking) == hipSuccess; };
+        auto side_stream = [&](hipStream_t *st) { return hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio_hi) == hipSuccess || hipStreamCreateWithFlags(st, hipStreamNonBlocking) == hipSuccess; };
         // Which hardware queue a stream gets follows from the streams the PROCESS has created before it, and the step is very
         // sensitive to it: with one unused stream created in front of `aux` (or of `aux2`) the headline step takes 0.89 ms instead of
         // 0.585, with one in front of each 0.585 again (round 6, NOTEBOOK.md B; tools/ubench/queue_probe.hip shows 50-70 us of extra
@@ -664,27 +647,19 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
         if (!getenv("RR_NO_RASTER_ORDER") && (long long)N * RM.ntiles >= 2048 && (long long)N * RM.ntiles <= (1 << 20) && N < (1 << 24)) {
             if ((r = dev_alloc(e, &e->D.item_cost, (size_t)N * RM.ntiles)) != RR_OK || (r = dev_alloc(e, &e->D.item_bin, (size_t)N * RM.ntiles)) != RR_OK || (r = dev_alloc(e, &e->item_perm, (size_t)8 * ((N + 7) / 8) * RM.ntiles)) != RR_OK) { rr_destroy(e); *out = nullptr; return r; }
         }
-        if (!getenv("RR_NO_STATIC_LAYER")) {
-            unsigned long long *sv = nullptr;
-            if ((r = dev_alloc(e, &sv, spx)) != RR_OK) { rr_destroy(e); *out = nullptr; return r; }
-            e->D.static_vis_out = sv;
-        }
+        if ((r = dev_alloc(e, &e->D.static_vis_out, spx)) != RR_OK) { rr_destroy(e); *out = nullptr; return r; }
         e->field_ptr[RR_F_FRAG_COUNT] = e->D.frag_count;
         if ((r = build_static_layer(e)) != RR_OK) { rr_destroy(e); *out = nullptr; return r; }
     }
-    // the 256-thread form of k_solve (heavy solver groups, four per workgroup) asks for 158 KiB of dynamic LDS: only the
-    // heavy / light split launches it, and a device that cannot grant it runs without the split (same results, one launch)
-    if (e->split_heavy && (hipFuncSetAttribute((const void *)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * SGRP * LF_TOTAL * sizeof(float))) != hipSuccess ||
-                           hipFuncSetAttribute((const void *)k_solve_rs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * SGRP * LF_TOTAL * sizeof(float))) != hipSuccess)) {
+    // the 256-thread form of k_solve (heavy solver groups, four per workgroup) and the light envs' solve with an object wave (five
+    // waves, sixteen envs) ask for 158 KiB of dynamic LDS: only the heavy / light split launches them, and a device that cannot grant
+    // it runs without the split (same results, one launch)
+    const int lds_split = (int)(4 * SGRP * LF_TOTAL * sizeof(float));
+    if (e->split_heavy && (hipFuncSetAttribute((const void *)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, lds_split) != hipSuccess ||
+                           hipFuncSetAttribute((const void *)k_solve_rs, hipFuncAttributeMaxDynamicSharedMemorySize, lds_split) != hipSuccess ||
+                           hipFuncSetAttribute((const void *)k_solve_light_ow, hipFuncAttributeMaxDynamicSharedMemorySize, lds_split) != hipSuccess)) {
         (void)hipGetLastError();
         e->split_heavy = false;
-    }
-    // the light envs' solve with an object wave (five waves, sixteen envs and the same 158 KiB per workgroup); without the
-    // attribute (or with RR_NO_OBJECT_WAVE) the one-group-per-env form in 64-thread workgroups -- same results
-    e->light_ow = e->split_heavy && !getenv("RR_NO_OBJECT_WAVE");
-    if (e->light_ow && hipFuncSetAttribute((const void *)k_solve_light_ow, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * SGRP * LF_TOTAL * sizeof(float))) != hipSuccess) {
-        (void)hipGetLastError();
-        e->light_ow = false;
     }
     if (hipGetLastError() != hipSuccess) { rr_destroy(e); *out = nullptr; return fail(RR_EDEVICE, "rr_create: device error during set-up"); }
     return RR_OK;
@@ -775,11 +750,10 @@ int rr_set_object_poses(rr_env *e, const float *poses_host, const uint8_t *env_m
 }
 
 static bool g_debug_sync = getenv("RR_DEBUG_SYNC") != nullptr;
-static int g_skip = getenv("RR_SKIP") ? atoi(getenv("RR_SKIP")) : 0;
 #define TIMED(id, launch)                                                   \
     do {                                                                    \
         if (e->timing) hipEventRecord(e->ev[2 * (id)], e->stream);          \
-        if (!((g_skip >> (id)) & 1)) launch;                                \
+        launch;                                                             \
         if (g_debug_sync) { hipError_t e__ = hipStreamSynchronize(e->stream); fprintf(stderr, "[rr] kernel %d done: %s\n", (id), hipGetErrorString(e__)); } \
         if (e->timing) {                                                    \
             hipEventRecord(e->ev[2 * (id) + 1], e->stream);                 \
@@ -802,10 +776,6 @@ static int ensure_images(rr_env *e, DevPtrs &D) {
         if (!e->images_valid) HIPCHK(hipMemsetAsync(e->D.frag_count, 0, (size_t)N * e->RM.ntiles * sizeof(unsigned), e->stream));
         e->images_valid = true;
         return 0;           // the lists are empty: nothing to restore
-    }
-    if (e->sep_restore) {
-        TIMED(5, hipLaunchKernelGGL(k_restore, dim3(N, e->RM.ntiles), dim3(RESTORE_THREADS), 0, e->stream, e->RM_dev, D, io, 1));
-        return 0;
     }
     return 1;
 }
@@ -936,7 +906,7 @@ static void launch_solve_class(rr_env *e, int sel, hipStream_t st, const RenderM
     // -- unless the heavy list is long too (macro actions: 1 500+ heavy envs, packed, beside 380 very heavy ones: 3.82 -> 3.76 M in the coop form)
     const bool h_long_ = (long long)lagged_count(e, 0, 0) * e->RM.ntiles > RENDER_LIST_WGS;
     // (beside_raster false: a step without camera -- no visibility pass for the one-env-per-wave form's LDS regions to crowd out)
-    const bool coop = e->P.coop_build && lagged <= (sel == 3 && (!h_long_ || !beside_raster) ? COOP_MAX_VH : COOP_MAX);
+    const bool coop = lagged <= (sel == 3 && (!h_long_ || !beside_raster) ? COOP_MAX_VH : COOP_MAX);
     // (fused_rm: the step draws -- the kernel also sets up the render instances of its envs, as the light solve does)
     if (fused_rm) {
         if (coop) LAUNCH_EV(done, k_solve_rs, dim3((N + 3) / 4), dim3(256), lds64, st, e->B, e->P, e->D, sel, 1, fused_rm);
@@ -949,12 +919,9 @@ static void launch_solve_class(rr_env *e, int sel, hipStream_t st, const RenderM
 // the start of a step whose look-ahead is missing or stale, or at the end of a step that has a single class.
 static void state_part_all(rr_env *e, bool overlap) {
     if (overlap) {
-        const bool bind = e->ext_events;
-        launch_prep_a(e, 0, 1, e->stream, bind ? e->ev_fork : nullptr);
-        if (!bind) HIPQ(hipEventRecord(e->ev_fork, e->stream));
+        launch_prep_a(e, 0, 1, e->stream, e->ev_fork);
         HIPQ(hipStreamWaitEvent(e->aux, e->ev_fork, 0));
-        launch_prep_b(e, 0, e->aux, bind ? e->ev_dyn : nullptr);
-        if (!bind) HIPQ(hipEventRecord(e->ev_dyn, e->aux));
+        launch_prep_b(e, 0, e->aux, e->ev_dyn);
         launch_collide(e, 0, e->stream);
         HIPQ(hipStreamWaitEvent(e->stream, e->ev_dyn, 0));
     } else {
@@ -994,19 +961,17 @@ static int pin_acquire(rr_env *e, char **slot, int *idx) {
 #define NORENDER_SPLIT_VH_MIN 64   // a step without camera runs its classes side by side from this many (lagged) very heavy envs on (step_single)
 
 static void launch_light_solve(rr_env *e, const RenderModel *fused_rm, hipStream_t st, hipEvent_t done = nullptr) {
-    const int N = e->P.N;
     const size_t lds64 = (size_t)SGRP * LF_TOTAL * sizeof(float);
-    if (e->light_ow) LAUNCH_EV(done, k_solve_light_ow, dim3((N + 15) / 16), dim3(LIGHT_OW_THREADS), 4 * lds64, st, e->B, e->P, e->D, fused_rm);
-    else LAUNCH_EV(done, k_solve_light, dim3((N + SGRP - 1) / SGRP), dim3(SGRP * 16), lds64, st, e->B, e->P, e->D, fused_rm);
+    LAUNCH_EV(done, k_solve_light_ow, dim3((e->P.N + 15) / 16), dim3(LIGHT_OW_THREADS), 4 * lds64, st, e->B, e->P, e->D, fused_rm);
 }
 
 // The same launches as step_split(), one after the other on the main stream, each under its timer -- 2 / 3 / 4 / 6 what the main
 // stream runs in an untimed step (the light envs), 7 / 8 what the side streams run beside it, 0 / 1 the look-ahead of the next step.
-static int step_split_timed(rr_env *e, const DevPtrs &D, int restore, const RenderModel *fused_rm, bool ahead, int render_mode) {
-    TIMED(2, launch_light_solve(e, fused_rm, e->stream));
-    TIMED(7, { launch_solve_class(e, 2, e->stream, fused_rm); launch_solve_class(e, 3, e->stream, fused_rm); });
-    launch_render(e, D, restore, 1, e->stream, true, fused_rm != nullptr);
-    TIMED(8, { launch_render(e, D, restore, 2, e->stream, false, fused_rm != nullptr); launch_render(e, D, restore, 3, e->stream, false, fused_rm != nullptr); });
+static int step_split_timed(rr_env *e, const DevPtrs &D, int restore, bool ahead, int render_mode) {
+    TIMED(2, launch_light_solve(e, e->RM_dev, e->stream));
+    TIMED(7, { launch_solve_class(e, 2, e->stream, e->RM_dev); launch_solve_class(e, 3, e->stream, e->RM_dev); });
+    launch_render(e, D, restore, 1, e->stream, true, true);
+    TIMED(8, { launch_render(e, D, restore, 2, e->stream, false, true); launch_render(e, D, restore, 3, e->stream, false, true); });
     if (ahead) {
         TIMED(0, launch_prep_ab(e, 0, e->stream));
         TIMED(1, launch_collide(e, 0, e->stream));
@@ -1019,7 +984,8 @@ static int step_split_timed(rr_env *e, const DevPtrs &D, int restore, const Rend
 // long as its longest Gauss-Seidel chain).  Main stream: light solve -> visibility -> shading of the light envs; heavy stream:
 // heavy solve -> their render (-> the very heavy envs' render); very heavy stream: their solve (-> look-ahead).  Where the
 // look-ahead and the very heavy envs' render go was settled by measurement (DESIGN.md 5.2, NOTEBOOK.md B).
-static int step_split(rr_env *e, const DevPtrs &D, int restore, const RenderModel *fused_rm, bool ahead, int render_mode) {
+// The solve kernels set up the render instances of their envs themselves.
+static int step_split(rr_env *e, const DevPtrs &D, int restore, bool ahead, int render_mode) {
     // (a long heavy list is rendered by three launches, the longest chain of the step: the very heavy envs' render then goes to the
     // tail of the main stream, which is done with the shading by then)
     const bool h_long = (long long)lagged_count(e, 0, 0) * e->RM.ntiles > RENDER_LIST_WGS;
@@ -1030,37 +996,29 @@ static int step_split(rr_env *e, const DevPtrs &D, int restore, const RenderMode
     const bool la_side = ahead && !la_on_vh;
     const bool vh_render_on_main = la_on_vh && h_long;
     // (the events that say "this class is solved" / "the collision pass is done" complete with those launches: LAUNCH_EV)
-    const bool ext_ev = e->ext_events, bind = ext_ev && ahead;
-    bool join2_bound = false;
     HIPQ(hipEventRecord(e->ev_fork, e->stream));
     HIPQ(hipStreamWaitEvent(e->aux, e->ev_fork, 0));
-    launch_solve_class(e, 2, e->aux, fused_rm, bind ? e->ev_hsolved : nullptr);
-    if (ahead && !bind) HIPQ(hipEventRecord(e->ev_hsolved, e->aux));
+    launch_solve_class(e, 2, e->aux, e->RM_dev, ahead ? e->ev_hsolved : nullptr);
     // (ev_join: the heavy stream's last launch -- the heavy lists' render, or the very heavy envs' behind it, or placement 2's collision pass)
     const bool vh_render_on_aux = la_on_vh && !vh_render_on_main;
-    const hipEvent_t join_ev = ext_ev && !la_side ? e->ev_join : nullptr;
-    launch_render(e, D, restore, 2, e->aux, false, fused_rm != nullptr, vh_render_on_aux ? nullptr : join_ev);
+    const hipEvent_t join_ev = la_side ? nullptr : e->ev_join;
+    launch_render(e, D, restore, 2, e->aux, false, true, vh_render_on_aux ? nullptr : join_ev);
     HIPQ(hipStreamWaitEvent(e->aux2, e->ev_fork, 0));
-    launch_solve_class(e, 3, e->aux2, fused_rm, bind ? e->ev_vsolved : nullptr);
-    if (ahead && !bind) HIPQ(hipEventRecord(e->ev_vsolved, e->aux2));
+    launch_solve_class(e, 3, e->aux2, e->RM_dev, ahead ? e->ev_vsolved : nullptr);
     if (vh_render_on_aux) {
         HIPQ(hipStreamWaitEvent(e->aux, e->ev_vsolved, 0));
-        launch_render(e, D, restore, 3, e->aux, false, fused_rm != nullptr, join_ev);
-    } else if (!la_on_vh) launch_render(e, D, restore, 3, e->aux2, false, fused_rm != nullptr);
-    if (!la_side && !join_ev) HIPQ(hipEventRecord(e->ev_join, e->aux));
-    launch_light_solve(e, fused_rm, e->stream, bind ? e->ev_dyn : nullptr);
-    if (ahead && !bind) HIPQ(hipEventRecord(e->ev_dyn, e->stream));            // the light envs' solve
+        launch_render(e, D, restore, 3, e->aux, false, true, join_ev);
+    } else if (!la_on_vh) launch_render(e, D, restore, 3, e->aux2, false, true);
+    launch_light_solve(e, e->RM_dev, e->stream, ahead ? e->ev_dyn : nullptr);
     // (the thread-per-env k_prep_ab needed a whole free SIMD for each of its 64 waves and sat in its queue until the visibility
     // pass' grid was exhausted -- which kept the collision pass, 39 KB of LDS per workgroup, out of the visibility pass' way;
-    // k_prep_ab16 gets onto the machine at once, so the look-ahead is HELD behind the light envs' visibility pass by an event:
-    // RR_LA_AFTER_RASTER=0 lets it go as soon as the solves are done)
-    const bool la_after_raster = la_on_vh && e->la_after_raster && !e->prep_scalar;
+    // k_prep_ab16 gets onto the machine at once, so the look-ahead is HELD behind the light envs' visibility pass by an event)
+    const bool la_after_raster = la_on_vh && !e->prep_scalar;
     if (la_on_vh && !la_after_raster) {
         HIPQ(hipStreamWaitEvent(e->aux2, e->ev_dyn, 0));
         HIPQ(hipStreamWaitEvent(e->aux2, e->ev_hsolved, 0));
         launch_prep_ab(e, 0, e->aux2);
-        launch_collide(e, 0, e->aux2, ext_ev ? e->ev_join2 : nullptr);
-        join2_bound = ext_ev;
+        launch_collide(e, 0, e->aux2, e->ev_join2);
     } else if (la_side) {
         // the heavy stream is done with its envs' render long before the very heavy envs' is: the kinematics half of the preparation
         // (69 VGPRs: it gets onto the machine beside the renders) and the collision pass go there once every solve is done, the
@@ -1068,32 +1026,27 @@ static int step_split(rr_env *e, const DevPtrs &D, int restore, const RenderMode
         HIPQ(hipStreamWaitEvent(e->aux, e->ev_dyn, 0));
         HIPQ(hipStreamWaitEvent(e->aux, e->ev_vsolved, 0));
         launch_prep_a(e, 0, 0, e->aux);
-        launch_collide(e, 0, e->aux, ext_ev ? e->ev_join : nullptr);
-        if (!ext_ev) HIPQ(hipEventRecord(e->ev_join, e->aux));
+        launch_collide(e, 0, e->aux, e->ev_join);
         HIPQ(hipStreamWaitEvent(e->aux2, e->ev_dyn, 0));
         HIPQ(hipStreamWaitEvent(e->aux2, e->ev_hsolved, 0));
-        launch_prep_b(e, 0, e->aux2, ext_ev ? e->ev_join2 : nullptr);
-        join2_bound = ext_ev;
+        launch_prep_b(e, 0, e->aux2, e->ev_join2);
     }
     if (la_after_raster) {
         const ImageOut io = env_images(e);
-        if (!fused_rm) hipLaunchKernelGGL(k_render_setup, dim3((e->P.N * MAXINST + 63) / 64), dim3(64), 0, e->stream, e->B, e->P, e->RM_dev, D, 1);
         launch_raster(e, D, restore, 1, e->stream);
         HIPQ(hipEventRecord(e->ev_rast, e->stream));
         HIPQ(hipStreamWaitEvent(e->aux2, e->ev_rast, 0));          // (behind the light solve too: same stream)
         HIPQ(hipStreamWaitEvent(e->aux2, e->ev_hsolved, 0));
         launch_prep_ab(e, 0, e->aux2);
-        launch_collide(e, 0, e->aux2, ext_ev ? e->ev_join2 : nullptr);
-        join2_bound = ext_ev;
-        if (!join2_bound) HIPQ(hipEventRecord(e->ev_join2, e->aux2));
+        launch_collide(e, 0, e->aux2, e->ev_join2);
         launch_shade(e, D, io, 1, e->stream);
     } else {
-        if (!join2_bound) HIPQ(hipEventRecord(e->ev_join2, e->aux2));
-        launch_render(e, D, restore, 1, e->stream, false, fused_rm != nullptr);
+        if (!ahead) HIPQ(hipEventRecord(e->ev_join2, e->aux2));     // (with the look-ahead its last launch completes ev_join2)
+        launch_render(e, D, restore, 1, e->stream, false, true);
     }
     if (vh_render_on_main) {
         HIPQ(hipStreamWaitEvent(e->stream, e->ev_vsolved, 0));
-        launch_render(e, D, restore, 3, e->stream, false, fused_rm != nullptr);
+        launch_render(e, D, restore, 3, e->stream, false, true);
     }
     if (ahead) e->la_valid = true;
     HIPQ(hipStreamWaitEvent(e->stream, e->ev_join, 0));
@@ -1106,12 +1059,12 @@ static int step_split(rr_env *e, const DevPtrs &D, int restore, const RenderMode
 static int step_single(rr_env *e, bool overlap, bool ahead, int render_mode) {
     const int N = e->P.N;
     const size_t lds64 = (size_t)SGRP * LF_TOTAL * sizeof(float);
-    const bool small_n = N <= SMALL_N_MAX && e->split_heavy && e->aux && !e->timing && !g_skip;
+    const bool small_n = N <= SMALL_N_MAX && e->split_heavy && !e->timing;
     if (small_n && N == 1) {
         launch_light_solve(e, nullptr, e->stream);
         launch_solve_class(e, 2, e->stream);
         launch_solve_class(e, 3, e->stream);
-    } else if (!render_mode && N > COOP_ALL_MAX && e->split_heavy && e->aux && !e->timing && !g_skip && lagged_count(e, 1, 0) >= NORENDER_SPLIT_VH_MIN) {
+    } else if (!render_mode && N > COOP_ALL_MAX && e->split_heavy && !e->timing && lagged_count(e, 1, 0) >= NORENDER_SPLIT_VH_MIN) {
         // Placement 3b: a step without camera whose very heavy list is long (macro actions without the retina: 368 of 4 096 envs).  In the
         // one launch for everybody those envs are solved four to a wave, sixteen lanes building the rows of an env at the contact cap; side
         // by side on the three streams they get a wave each -- 0.765 -> 0.711 ms per step on the macro workload.  With a handful of
@@ -1139,8 +1092,7 @@ static int step_single(rr_env *e, bool overlap, bool ahead, int render_mode) {
         HIPQ(hipEventRecord(e->ev_fork, e->stream));
         HIPQ(hipStreamWaitEvent(e->aux, e->ev_fork, 0));
         launch_prep_ab(e, 0, e->aux);
-        launch_collide(e, 0, e->aux, e->ext_events ? e->ev_join : nullptr);
-        if (!e->ext_events) HIPQ(hipEventRecord(e->ev_join, e->aux));
+        launch_collide(e, 0, e->aux, e->ev_join);
     }
     if (render_mode) rc = do_render(e, render_mode == 2);
     if (la_beside) {
@@ -1176,7 +1128,7 @@ int rr_step(rr_env *e, const float *joint_cmd, int32_t cmd_on_device, int32_t re
         HIPCHK(hipMemcpyAsync(e->D.render_flags, pin + (size_t)N * 36, N, hipMemcpyHostToDevice, e->stream));
     }
     if (pin_idx >= 0) { HIPCHK(hipEventRecord(e->pin_ev[pin_idx], e->stream)); e->pin_used[pin_idx] = true; }
-    const bool overlap = e->aux && !e->timing && !g_skip;      // side streams in use (timing leg / diagnostics: everything on the main stream)
+    const bool overlap = !e->timing;      // side streams in use (timing leg: everything on the main stream)
     // ---- bounded run-ahead (a batch: a handful of envs is waited for every step by its caller anyway)
     const unsigned ahead_period = (unsigned)std::max(1, e->run_ahead / 2);
     const bool bounded = e->run_ahead > 0 && N > SMALL_N_MAX && e->step_no % ahead_period == 0;      // (a marker step)
@@ -1197,13 +1149,11 @@ int rr_step(rr_env *e, const float *joint_cmd, int32_t cmd_on_device, int32_t re
     const bool ahead = e->lookahead;            // this step ends with the state part of the next one
     // (a step without camera runs all envs in one launch: its classes side by side measured 0.525 instead of 0.452 ms on config 2;
     // ONE env -- the gym facade -- renders in its chain on the main stream too: the split has nothing to overlap there)
-    if (e->aux && !g_skip && render_mode && e->split_heavy && !mostly_heavy && !(N == 1 && !e->timing)) {
+    if (render_mode && e->split_heavy && !mostly_heavy && !(N == 1 && !e->timing)) {
         DevPtrs D = e->D;
         if (render_mode != 2) D.render_flags = nullptr;
         const int restore = ensure_images(e, D);
-        // (the solve kernels set up the render instances of their envs themselves; RR_NO_FUSED_SETUP: separate k_render_setup launches)
-        const RenderModel *fused_rm = e->no_fused_setup ? nullptr : e->RM_dev;
-        const int rc = e->timing ? step_split_timed(e, D, restore, fused_rm, ahead, render_mode) : step_split(e, D, restore, fused_rm, ahead, render_mode);
+        const int rc = e->timing ? step_split_timed(e, D, restore, ahead, render_mode) : step_split(e, D, restore, ahead, render_mode);
         if (rc != RR_OK) return rc;
         HIPCHK(hipGetLastError());
         if (bounded) HIPCHK(hipEventRecord(e->ahead_ev[ahead_slot], e->stream));

@@ -28,6 +28,7 @@ static_assert(RASTER_INST <= MAXINST && MAXWIN <= 512, "clip queue entries: wind
 #define INLINE_PIX 2     // sample points of a small triangle walked by its own lane; the rest is redistributed over the wave
 #endif
 #define SMALL_AREA 64    // bbox area (sample points) up to which a triangle takes the per-lane + redistribution path (A/B: 16 0.60, 32 0.54, 64 0.53, 128 0.54 ms)
+static_assert(SMALL_AREA <= 64, "a raster record's box width has 6 bits");
 
 struct STri { float sx[3], sy[3], sz[3], w[3]; };
 
@@ -463,7 +464,7 @@ __device__ __forceinline__ void raster_tile(const SimParams &P, const RenderMode
     }
     __syncthreads();
     WGM(3);
-    // Every wave takes 64 consecutive triangles per window.  A triangle whose clipped bounding box holds <= small_area
+    // Every wave takes 64 consecutive triangles per window.  A triangle whose clipped bounding box holds <= SMALL_AREA
     // sample points is rasterised by its own lane; bigger ones are handed to the whole wave (ballot, v_readlane broadcast
     // of the projected triangle, 64 sample points per step in 8x8 blocks) so that one large triangle does not make 63
     // lanes wait.
@@ -551,8 +552,6 @@ __device__ __forceinline__ void raster_tile(const SimParams &P, const RenderMode
             const float ymin = fminf(s.sy[0], fminf(s.sy[1], s.sy[2])), ymax = fmaxf(s.sy[0], fmaxf(s.sy[1], s.sy[2]));
             bool on = live && !(xmax < txlo || ymax < ty0 || xmin > txhi || ymin > ty1);
             const TriEdge te = tri_edge(s);
-            // back faces of closed, consistently wound meshes can never win the depth test (opt-in, RR_CULL; wave-uniform per window)
-            if (RM.any_cull && RM.in_cull[inst]) on = on && !(PDIFF(s.sx[1] - s.sx[0], s.sy[2] - s.sy[0], s.sx[2] - s.sx[0], s.sy[1] - s.sy[0]) <= 0.0f);
             x0 = (int)ceilf(__builtin_amdgcn_fmed3f(xmin, txlo, txhi)); x1 = (int)floorf(__builtin_amdgcn_fmed3f(xmax, txlo, txhi));
             y0 = (int)ceilf(__builtin_amdgcn_fmed3f(ymin, ty0, ty1)); y1 = (int)floorf(__builtin_amdgcn_fmed3f(ymax, ty0, ty1));
             on = on && !(x1 < x0 || y1 < y0) && te.ok;
@@ -562,7 +561,7 @@ __device__ __forceinline__ void raster_tile(const SimParams &P, const RenderMode
         }
         PH(2);                                      // bounding box, set-up
         if (ABL(1)) continue;
-        const bool big = live && area > P.small_area;
+        const bool big = live && area > SMALL_AREA;
 #ifdef RR_RASTER_STATS
         {
             const unsigned long long lm = __ballot(live), bm = __ballot(big);
@@ -950,47 +949,7 @@ __global__ void __launch_bounds__(COPY_THREADS) k_static_copy(const RenderModel 
     }
 }
 
-// Background fill of the shared static images (before the static layer is shaded, and when there is no static layer).
-// Incremental image update: an env's image in HBM still holds its previous frame, and only the pixels of that frame's
-// fragment list differ from the static layer.  Putting the static values back at exactly those pixels (before k_raster
-// overwrites the list) leaves the same image as a full copy of the static layer -- ~1 000 pixels instead of 16 384 per env.
-#define RESTORE_THREADS 256
-__global__ void __launch_bounds__(RESTORE_THREADS) k_restore(const RenderModel *RMp, DevPtrs D, ImageOut out, int use_flags) {
-    const RenderModel &RM = *RMp;
-    const int env = blockIdx.x, tile = blockIdx.y;
-    if (use_flags && D.render_flags && !D.render_flags[env]) return;
-    const unsigned n = D.frag_count[(size_t)env * RM.ntiles + tile];          // still the previous frame's count
-    const uint2 *lst = D.frag_list + ((size_t)env * RM.ntiles + tile) * TILE_PIX;
-    const int tyi_ = tile / RM.ntx, row0_ = tyi_ * RM.tile_h, tx0_ = (tile - tyi_ * RM.ntx) * RM.tile_w;
-    const size_t ebase = (size_t)env * out.env_stride;
-    // (pixel-in-tile index -> pixel of the image)
-#define RESTORE_GP(PI) ((size_t)(row0_ + (int)__umulhi((unsigned)(PI), RM.w_magic)) * RM.W + (size_t)(tx0_ + (int)(PI) - (int)__umulhi((unsigned)(PI), RM.w_magic) * RM.tile_w))
-    // four fragments per thread and trip, every load of the trip issued before the first store (the kernel is a chain of
-    // dependent round trips: list entry -> static pixel -> store)
-    for (unsigned i0 = 0; i0 < n; i0 += 4 * RESTORE_THREADS) {
-        unsigned pi[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) { const unsigned i = i0 + k * RESTORE_THREADS + threadIdx.x; pi[k] = i < n ? lst[i].y >> 18 : 0xffffffffu; }
-        unsigned char r[4][3]; float d[4]; int m[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const size_t so = RESTORE_GP(pi[k] != 0xffffffffu ? pi[k] : 0u);
-            r[k][0] = D.static_rgb[so * 3]; r[k][1] = D.static_rgb[so * 3 + 1]; r[k][2] = D.static_rgb[so * 3 + 2];
-            d[k] = D.static_depth[so];
-            m[k] = out.mask ? D.static_mask[so] : 0;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (pi[k] == 0xffffffffu) continue;
-            const size_t o = ebase + RESTORE_GP(pi[k]);
-            out.rgb[o * 3] = r[k][0]; out.rgb[o * 3 + 1] = r[k][1]; out.rgb[o * 3 + 2] = r[k][2];
-            out.depth[o] = d[k];
-            if (out.mask) out.mask[o] = m[k];
-        }
-    }
-#undef RESTORE_GP
-}
-
+// Background fill of the shared static images (before the static layer is shaded).
 __global__ void k_background(const RenderModel *RMp, DevPtrs D) {
     const int npx = RMp->W * RMp->H;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += gridDim.x * blockDim.x) {
@@ -1050,7 +1009,7 @@ __device__ __forceinline__ void shade_block(const RenderModel &RM, const DevPtrs
         // where it does not, and where the previous frame's fragment has gone, the pixel goes back to the static layer
         // (the image persists in HBM from frame to frame, do_render)
         if (t == (int)FRAG_VACATED || (sv && !((((unsigned long long)f.x << 32) | (unsigned)t) < sv[gp]))) {
-            // (vacated entries only exist in env frames; with RR_NO_STATIC_LAYER the static buffers hold the background)
+            // (vacated entries only exist in env frames)
 #if defined(RR_SHADE_PROBE) && (RR_SHADE_PROBE & 128)
             continue;       // (probe: what does the put-back path cost?)
 #endif

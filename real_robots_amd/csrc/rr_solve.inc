@@ -1,5 +1,5 @@
 // rr_solve.inc -- part of realrobot.hip (included there, in this order; not a stand-alone translation unit).
-// k_solve / k_solve_light / k_solve_light_ow: command part, row build, projected Gauss-Seidel, integration
+// k_solve / k_solve_rs / k_solve_light_ow: command part, row build, projected Gauss-Seidel, integration
 // ---------------------------------------------------------------------------------------------- k_solve
 __device__ __forceinline__ void plane_space(v3 n, v3 &p, v3 &q) {   // btPlaneSpace1
     if (fabsf(n.z) > 0.70710678118654752440f) {
@@ -315,7 +315,7 @@ __device__ __forceinline__ void instance_setup(const BodyParams &B, const SimPar
 // queue -- folds away at compile time and the sweep of motors, limits and object-lane rows runs without the register
 // spills (v_accvgpr_read: a third of the torsional steps' instructions) the full kernel needs.  Same source, same
 // arithmetic: results do not depend on which form solved an env (split-equivalence tests, bitwise).
-// OW ("object wave", light form only): workgroups of five waves solve sixteen envs -- waves 0..3 are the envs' 16-lane groups
+// The light form runs with an object wave: workgroups of five waves solve sixteen envs -- waves 0..3 are the envs' 16-lane groups
 // (command part, row build, the robot's rows, joint integration), wave 4 runs the object chains of all sixteen envs, one LANE per
 // (env, object) (light_object_wave below).  In a light env the robot's rows and each object's rows are separate problems;
 // with the object rows on lanes 11..13 of every group 62 % of a sweep's instructions ran with 3 of 16 lanes live.
@@ -329,9 +329,8 @@ __device__ void light_object_wave(const BodyParams &B, const SimParams &P, const
 // RSETUP: the kernel also sets up the render instances of its envs (RMp).  A template parameter, not just a null pointer: with the
 // set-up code in its tail the generic kernel's sweep loop comes out 3 % slower (register allocation), which a step without camera --
 // config 2 -- must not pay.
-template <bool GEN, bool OW = false, bool RSETUP = !GEN>
+template <bool GEN, bool RSETUP = !GEN>
 __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams &P, const DevPtrs &D, int sel, int coop_launch, const RenderModel *RMp = nullptr) {
-    static_assert(!(GEN && OW), "the object wave belongs to the light form");
     const int N = P.N;
     if (sel <= 1 && blockIdx.x == 0 && threadIdx.x == 0) {
         // (once per step, by the launch every step has: the bookkeeping of the contact frame this step's look-ahead will fill;
@@ -345,15 +344,15 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
     // waves share one (together as many issue slots as the object wave).  Object wave 53 -> 37 us (scratch/sprof_light.py), the
     // kernel 56.7 -> 54.3 us, the step 0.691 -> 0.685 ms.  (LIGHT_OW_THREADS 320: J J J J O, the object wave shares with a group wave.)
     int jwave = 0;
-    if (OW) {
+    if (!GEN) {
         const int wv = threadIdx.x >> 6;
         if (wv == 0) { light_object_wave(B, P, D, RMp); return; }
         if (wv == 4) { __syncthreads(); return; }
         jwave = wv < 4 ? wv - 1 : 3;
     }
-    const int grp = OW ? 4 * jwave + ((threadIdx.x >> 4) & 3) : threadIdx.x >> 4, l = threadIdx.x & 15;
+    const int grp = !GEN ? 4 * jwave + ((threadIdx.x >> 4) & 3) : threadIdx.x >> 4, l = threadIdx.x & 15;
 #else
-    if (OW && (threadIdx.x >> 6) == 4) { light_object_wave(B, P, D, RMp); return; }
+    if (!GEN && (threadIdx.x >> 6) == 4) { light_object_wave(B, P, D, RMp); return; }
     const int grp = threadIdx.x >> 4, l = threadIdx.x & 15;
 #endif
     const int unit = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);   // the wave's index in the launch
@@ -364,12 +363,12 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
     // arithmetic per row whichever group builds it: results do not depend on the mode (tested bitwise).
     const bool coop = GEN && coop_launch && (sel >= 2 || sel == 0);    // (sel 0: every env its own wave -- batches of at most one wave per SIMD, rr_step)
     const int cg = coop ? (grp & 3) : 0;                              // this group's place among the builders of its env
-    int env_raw = OW ? 16 * (int)blockIdx.x + grp : (coop ? unit : 4 * unit + (grp & 3));
+    int env_raw = !GEN ? 16 * (int)blockIdx.x + grp : (coop ? unit : 4 * unit + (grp & 3));
     bool mine = true;                                                 // this 16-lane group has an env to solve in this launch
     if (sel == 2) { mine = env_raw < *D.hcount; env_raw = mine ? D.hlist[env_raw] : N; }
     else if (sel == 3) { mine = env_raw < *D.hcount2; env_raw = mine ? D.hlist2[env_raw] : N; }
     else if (sel == 1) mine = env_raw < N && D.hgflag[env_raw] == 0;
-    if (!OW && __ballot(mine) == 0ull) return;                        // (wave-uniform; OW: every wave goes to the workgroup's barrier)
+    if (GEN && __ballot(mine) == 0ull) return;                        // (wave-uniform; the light form: every wave goes to the workgroup's barrier)
     int env = env_raw < N ? env_raw : N - 1;                          // groups without an env run along as no-ops
     float *state = D.state, *scratch = D.scratch;
     const int lj = l < NB ? l : 0;               // joint owned by this lane (lanes >= 11 alias joint 0, masked)
@@ -560,7 +559,7 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
                 os_row_pair(k, k == 0 ? n : (k == 1 ? t1 : t2), x, oA, dist, rest, spin, roll, lam0, dt, P.erp, P.rest_thresh,
                             L_OSL + (3 * ci + k) * 12, L_OST + (3 * ci + k) * 8);
         }
-        if (OW) {
+        if (!GEN) {
             // what the object wave needs besides the rows and the objects' data (L_OBJ): who steps, whose contacts, orientations
             if (l == 0) {
                 *(int *)&LD(L_GSC + OW_FLAGS) = ((mine && env_raw < N) ? 1 : 0) | (dead ? 2 : 0);
@@ -1042,7 +1041,7 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
     // then the register rows add theirs (b2.w of a normal row = its inherited impulse; absent rows are all-zero)
     if (ng_max > 0) { OBJ_SLOTS(FROM_SLOT) }
 #pragma unroll
-    for (int i = 0; i < (OW ? 0 : KOS); i++) {
+    for (int i = 0; i < (GEN ? KOS : 0); i++) {
         const float l0_ = os_l0[i], sm_ = l0_ * inv_mass;
         os_ln[i] = l0_;
         V01 = pk_fma(P2(os_n0[i].x, os_n0[i].y), P2(sm_, sm_), V01);
@@ -1167,7 +1166,7 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
         if (simple) {
             SWEEP_MOTORS
             LIMIT_STEP(0) LIMIT_STEP(1)
-            if (!OW) {
+            if (GEN) {
                 OSN_STEP(0) OSN_STEP(1) OSN_STEP(2) OSN_STEP(3)
                 OSF_STEP(0) OSF_STEP(1) OSF_STEP(2) OSF_STEP(3)
                 OST_STEP(0) OST_STEP(1) OST_STEP(2) OST_STEP(3)
@@ -1179,7 +1178,7 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
         LIMIT_STEP(0) LIMIT_STEP(1)
         LIMIT_LOOP
         SPROF(7);
-        if (OW) continue;                         // (the object chains are the object wave's)
+        if (!GEN) continue;                         // (the object chains are the object wave's)
 #pragma unroll 1
         for (int pass = 0; pass < 3; pass++) {    // all normals, then all lateral frictions, then all torsional frictions
             // ---- the generic sweep of this pass: its first blocks are requested before the object lanes' own work
@@ -1285,7 +1284,7 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
     SPROF_FLUSH;
     // normal impulses of the register-resident contact rows go back to their LDS slots (contact forces below)
 #pragma unroll
-    for (int i = 0; i < (OW ? 0 : KOS); i++) {
+    for (int i = 0; i < (GEN ? KOS : 0); i++) {
         const int c = (os_cs >> (8 * i)) & 255;
         if (c != 255) LD(L_OSL + (3 * c) * 12 + 11) = os_ln[i];
     }
@@ -1300,7 +1299,7 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
     float q_fin = q_l;                 // joint angle / object pose after this step: what the render instances are set up from
     float o_fin[7] = {0, 0, 0, 0, 0, 0, 1};
     if (dead) {
-        if (!OW && lt >= NB && lt - NB < P.nobj) {
+        if (GEN && lt >= NB && lt - NB < P.nobj) {
 #pragma unroll
             for (int k = 0; k < 3; k++) o_fin[k] = STT(ST_OPOS + 3 * (lt - NB) + k);
 #pragma unroll
@@ -1322,7 +1321,7 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
         else if (lt == 7) D.joints[(size_t)env * 9 + 7] = qn;
         else if (lt == 8) D.joints[(size_t)env * 9 + 8] = -qn;
     }
-    if (!OW && lt >= NB && lt - NB < P.nobj) {
+    if (GEN && lt >= NB && lt - NB < P.nobj) {
         // (position, orientation and unconstrained velocities are the registers of the stage-in: no load at the tail of the chain)
         const int i = lt - NB;
         float v[3], w[3], pn[3];
@@ -1374,7 +1373,7 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
     if (!finite) atomicOr(&D.errflags[env], 1u);
     // ---- touch sensors (robot.py:152-163) + contact forces: lane c takes contacts c, c + 16, c + 32; the four maxima go round
     // the group (a maximum does not depend on the order it is taken in)
-    if (OW) {
+    if (!GEN) {
         // (a light env has no contact of the robot: the touch sensors read zero; the contact forces are the object wave's)
         if (l < 4) D.touch[(size_t)env * 4 + l] = 0.0f;
         if (l == 0) D.timestep[env] += 1;
@@ -1414,7 +1413,7 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
     if (RSETUP) {
         if (!setup) return;
         const RenderModel &RM = *RMp;
-        if (!OW && lt >= NB && lt < NB + NOBJ) {
+        if (GEN && lt >= NB && lt < NB + NOBJ) {
 #pragma unroll
             for (int k = 0; k < 7; k++) LD(L_OBJ + 20 * (lt - NB) + k) = o_fin[k];
         }
@@ -1428,7 +1427,7 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
 #pragma unroll 1
         for (int i = lt; i < RM.ni; i += 16) {
             const int ot = RM.in_otype[i], oi = RM.in_oidx[i];
-            if (OW && ot == 2) continue;          // (an object's instances are set up by the object wave, from what it integrated)
+            if (!GEN && ot == 2) continue;          // (an object's instances are set up by the object wave, from what it integrated)
             float op7[7];
             const int ob = ot == 2 ? min(max(oi, 0), NOBJ - 1) : 0;
 #pragma unroll
@@ -1437,7 +1436,7 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
         }
     }
 }
-// Wave 4 of a k_solve_light workgroup (solve_body<false, true>): the object chains of the workgroup's sixteen envs, lane 3 e + o =
+// The object wave of a k_solve_light_ow workgroup (solve_body<false>): the object chains of the workgroup's sixteen envs, lane 3 e + o =
 // object o of env e.  Everything it needs was staged in LDS by the env's group before the workgroup's barrier: the objects'
 // data (L_OBJ), the rows of the contacts (L_OSL / L_OST, coefficients), flags, contact masks and orientations (OW_*).  Same
 // row steps, same order within a chain, same integration as the object lanes of the one-kernel form: same bits.
@@ -1639,13 +1638,11 @@ __device__ __forceinline__ void light_object_wave(const BodyParams &B, const Sim
 }
 __global__ void __launch_bounds__(256) k_solve(BodyParams B, SimParams P, DevPtrs D, int sel, int coop_launch) { solve_body<true>(B, P, D, sel, coop_launch); }
 // ... and with the render set-up of its envs in its tail (the heavy classes of a step that draws)
-__global__ void __launch_bounds__(256) k_solve_rs(BodyParams B, SimParams P, DevPtrs D, int sel, int coop_launch, const RenderModel *RMp) { solve_body<true, false, true>(B, P, D, sel, coop_launch, RMp); }
-// the light envs of a split step (sel 1), 64-thread workgroups
+__global__ void __launch_bounds__(256) k_solve_rs(BodyParams B, SimParams P, DevPtrs D, int sel, int coop_launch, const RenderModel *RMp) { solve_body<true, true>(B, P, D, sel, coop_launch, RMp); }
+// the light envs of a split step (sel 1), in workgroups for sixteen envs with one wave running the object chains; the bookkeeping
+// of solve_body's first lines is thread 0's whatever its wave's role
 // (RMp: the render model when the step draws -- the kernel then sets up the render instances of its envs; else nullptr)
-__global__ void __launch_bounds__(64) k_solve_light(BodyParams B, SimParams P, DevPtrs D, const RenderModel *RMp) { solve_body<false>(B, P, D, 1, 0, RMp); }
-// ... in workgroups for sixteen envs with one wave running the object chains (OW); the bookkeeping of solve_body's first lines
-// is thread 0's whatever its wave's role
-__global__ void __launch_bounds__(LIGHT_OW_THREADS) k_solve_light_ow(BodyParams B, SimParams P, DevPtrs D, const RenderModel *RMp) { solve_body<false, true>(B, P, D, 1, 0, RMp); }
+__global__ void __launch_bounds__(LIGHT_OW_THREADS) k_solve_light_ow(BodyParams B, SimParams P, DevPtrs D, const RenderModel *RMp) { solve_body<false>(B, P, D, 1, 0, RMp); }
 
 // obs pack without stepping (after reset / set_state)
 __global__ void k_obs(SimParams P, DevPtrs D) {

@@ -7,6 +7,5 @@ import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['r
 }
 for lib in scratch/variants/old.so real_robots_amd/csrc/librealrobot_hip.so; do
   export RR_LIB=$PWD/$lib
-  run "$lib coop"
-  RR_NO_COOP=1 run "$lib NO_COOP"
+  run "$lib"
 done

@@ -1,4 +1,4 @@
-"""Phase cycle stamps of k_solve_light on the bench workload (development; needs `make -C real_robots_amd/csrc stats`).
+"""Phase cycle stamps of k_solve_light_ow on the bench workload (development; needs `make -C real_robots_amd/csrc stats`).
 One workgroup (= one wave = four envs) at a time: RR_ABLATE = block << 16 | 0x4000; blocks >= 300 have no counterpart in the
 coop launches of the heavy classes (their lists are shorter than 1200), so the stamps are the light kernel's alone."""
 import ctypes

@@ -226,15 +226,16 @@ def test_edited_eye_camera_reaches_the_retina():
     e.close()
 
 
-def test_object_wave_form_of_the_light_solve_is_bitwise_equivalent(monkeypatch):
+def test_object_wave_light_solve_is_bitwise_the_inline_step(monkeypatch):
     """k_solve_light_ow (workgroups of five waves for sixteen envs: four waves of 16-lane env groups for the command part, the row
     build and the robot's rows, the fifth wave one lane per (env, object) for the object chains, integration and the objects'
-    render instances) against k_solve_light (RR_NO_OBJECT_WAVE=1: everything of an env on its 16-lane group): states, joints,
-    touch sensors, object poses, contact forces, images bitwise equal over 200 steps of full-range commands with resets, a
-    teleport and a rejected (non-finite) command in between, at an env count that is not a multiple of 16 and with 1..3 objects."""
+    render instances) in the default step against the in-line step (RR_NO_SPLIT=1 RR_NO_LOOKAHEAD=1: one k_solve for all envs,
+    everything of an env on its 16-lane group): states, joints, touch sensors, object poses, contact forces, images bitwise
+    equal over 200 steps of full-range commands with resets, a teleport and a rejected (non-finite) command in between, at an
+    env count that is not a multiple of 16 and with 1..3 objects."""
     for n_obj, N in ((3, 130), (2, 49), (1, 16)):
         a = BatchedREALRobotEnv(N, objects=n_obj, width=64, height=64)
-        b = _make(monkeypatch, {'RR_NO_OBJECT_WAVE': '1'}, N, objects=n_obj, width=64, height=64)
+        b = _make(monkeypatch, {'RR_NO_SPLIT': '1', 'RR_NO_LOOKAHEAD': '1'}, N, objects=n_obj, width=64, height=64)
         rng = np.random.default_rng(7 + n_obj)
         ids = list(range(N))
         for t in range(200):
