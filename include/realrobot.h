@@ -23,11 +23,13 @@
 extern "C" {
 #endif
 
-#define RR_ABI_VERSION 6   /* 3: RR_F_CONTACT_COUNT, RR_F_ENV_CLASS, rr_checkpoint_*, rr_evaluate_goals; 4: rr_map_observations, rr_map_images,
+#define RR_ABI_VERSION 7   /* 3: RR_F_CONTACT_COUNT, RR_F_ENV_CLASS, rr_checkpoint_*, rr_evaluate_goals; 4: rr_map_observations, rr_map_images,
                               rr_sync_observations, rr_device_microbench; checkpoint blobs carry the step parameters (version 2 header);
                               5: rr_select_image_mirror; 6: rr_config carries the motor / solver constants the reference leaves to
                               pybullet's defaults (motor_kp .. solver_flags, in the place of reserved[7]: same struct size); checkpoint
-                              header version 3 carries them too; RR_F_PREP; rr_pack_image_delta, rr_apply_image_delta */
+                              header version 3 carries them too; RR_F_PREP; rr_pack_image_delta, rr_apply_image_delta;
+                              7: rr_set_object_dynamics, rr_get_object_dynamics (per-env mass, inertia and contact materials of the
+                              objects); checkpoint header version 4 carries them */
 
 enum {
     RR_OK = 0,
@@ -129,6 +131,20 @@ int rr_set_object_poses(rr_env *env, const float *poses_host, const uint8_t *env
  * tests/test_actions.py:95-98 parks the objects on the shelf that way). Defaults: the poses of the model blob. */
 int rr_set_object_home(rr_env *env, int32_t env_index, int32_t obj, const float *pose7);
 
+/* Per-env dynamics of the free objects: f32 [N, n_obj, 8] host, one row per (env, object) =
+ *   {mass, ixx, iyy, izz (principal inertia, object frame), lateral friction, restitution, rolling friction, spinning friction}.
+ * Replaces pybullet.changeDynamics(uid, -1, mass=, localInertiaDiagonal=, lateralFriction=, restitution=, rollingFriction=,
+ * spinningFriction=) of an object for the envs whose mask byte is non-zero (NULL: all envs; the rows of the other envs are not read).
+ * Mass and inertias must be finite and > 0, the four materials finite and >= 0: on any violation the call returns RR_EINVAL and
+ * changes no env.  Defaults: the values of the model blob.  The values are part of the env, not of its state: they outlive rr_reset,
+ * rr_set_state and rr_set_object_pose(s), and checkpoints carry them.  An object's materials apply to all of its collision shapes; a
+ * contact between two shapes gets the materials combined by Bullet's rule (products of friction and restitution, r_a mu_b + r_b mu_a
+ * at most 10 for rolling / spinning -- rr_get_contacts shows the combined friction); the table and the robot keep the blob's values.
+ * Synchronous (the source is host memory). */
+int rr_set_object_dynamics(rr_env *env, const float *dyn_host, const uint8_t *env_mask_host);
+/* Replaces pybullet.getDynamicsInfo(uid, -1) of the objects: every env's rows, same layout, f32 [N, n_obj, 8] host. */
+int rr_get_object_dynamics(rr_env *env, float *dyn_out_host);
+
 /* Replaces one REALRobotEnv.step_joints() (env.py:326-356) for all N envs:
  *   limitActionByJoint (env.py:314-321), control_objects_limits (env.py:257-264), Kuka.apply_action
  *   (robot.py:188-201), scene.global_step() -> stepSimulation (env.py:340), calc_state/get_touch_sensors
@@ -169,9 +185,9 @@ int rr_copy_to_host(rr_env *env, int32_t field, void *dst, size_t bytes);
 int rr_set_state(rr_env *env, const float *state_host);
 /* Checkpoint = everything a restore needs to continue BIT FOR BIT where the save left off: the state (with the motor targets),
  * the contact history of the warm start (contact list + normal forces of the last solved step -- Bullet's persistent manifolds
- * with their cached impulses, which pybullet.saveState / restoreState carry too), episode clocks, error flags, touch sensors and
- * the per-env object home poses.  Opaque host blob of rr_checkpoint_bytes() bytes, valid for env handles of the same num_envs /
- * n_objects.  (Macro plans in flight are host-side policy state and not part of it.)  save + restore + step == step, tested. */
+ * with their cached impulses, which pybullet.saveState / restoreState carry too), episode clocks, error flags, touch sensors,
+ * the per-env object home poses and the per-env object dynamics (rr_set_object_dynamics).  Opaque host blob of
+ * rr_checkpoint_bytes() bytes, valid for env handles of the same num_envs / n_objects.  (Macro plans in flight are host-side policy state and not part of it.)  save + restore + step == step, tested. */
 int rr_checkpoint_bytes(rr_env *env, size_t *bytes);
 int rr_checkpoint_save(rr_env *env, void *dst_host, size_t bytes);
 int rr_checkpoint_restore(rr_env *env, const void *src_host, size_t bytes);

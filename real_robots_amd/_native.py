@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get('RR_LIB', os.path.join(_HERE, 'csrc', 'librealrobot_hi
 BLOB_GZ = os.environ.get('RR_MODEL', os.path.join(_HERE, 'data', 'realrobot_model.bin.gz'))      # (RR_MODEL: another compiled model, A/B)
 LINK_NAMES = open(os.path.join(_HERE, 'data', 'realrobot_model_links.txt')).read().split()
 
-RR_ABI_VERSION = 6
+RR_ABI_VERSION = 7
 (F_JOINTS, F_TOUCH, F_OBJ_POSE, F_RGB, F_DEPTH, F_MASK, F_TIMESTEP, F_ERRFLAGS, F_STATE, F_FRAG_COUNT, F_CONTACT_COUNT,
  F_ENV_CLASS, F_PREP) = range(13)
 PREP_FLOATS = 378          # RR_F_PREP: frames 165, M^-1 121, qd* 11, object terms 81 -- in this order (realrobot.hip S_*)
@@ -31,7 +31,9 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_set_timing', 'rr_get_timing', 'rr_last_error', 'rr_abi_version', 'rr_ik', 'rr_plan_macro', 'rr_get_plan',
            'rr_step_plan', 'rr_set_camera', 'rr_set_object_poses', 'rr_step_plan_masked', 'rr_checkpoint_bytes',
            'rr_checkpoint_save', 'rr_checkpoint_restore', 'rr_evaluate_goals', 'rr_device_microbench', 'rr_map_observations', 'rr_map_images', 'rr_sync_observations', 'rr_select_image_mirror',
-           'rr_pack_image_delta', 'rr_apply_image_delta')
+           'rr_pack_image_delta', 'rr_apply_image_delta', 'rr_set_object_dynamics', 'rr_get_object_dynamics')
+# rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
+DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 
 
 class Config(C.Structure):
@@ -135,6 +137,8 @@ def load_library():
     L.rr_select_image_mirror.argtypes = [vp, C.c_int32]
     L.rr_pack_image_delta.argtypes = [vp, vp, vp, C.c_uint32]
     L.rr_apply_image_delta.argtypes = [vp, vp, i32, C.c_uint32, C.c_size_t, vp, vp, vp]
+    L.rr_set_object_dynamics.argtypes = [vp, vp, vp]
+    L.rr_get_object_dynamics.argtypes = [vp, vp]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]

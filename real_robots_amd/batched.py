@@ -46,6 +46,7 @@ class BatchedREALRobotEnv:
         p_, n_ = C.c_void_p(), C.c_size_t()                  # the tile count is the library's choice: ask for it
         nat.check(self.L.rr_get_buffer(self.h, nat.F_FRAG_COUNT, C.byref(p_), C.byref(n_)))
         self._shapes[nat.F_FRAG_COUNT] = ((self.N, max(1, n_.value // (4 * self.N))), np.uint32)
+        self._dyn_default = self._dynamics_raw()           # a fresh handle holds the model's object dynamics
 
     def map_images(self, mask=True):
         """Pinned host copies of the images that every rendered step refreshes (rr_map_images; a handful of envs only): numpy views
@@ -174,7 +175,8 @@ class BatchedREALRobotEnv:
 
     def checkpoint(self):
         """Opaque snapshot (numpy uint8 array) of everything a later `restore` needs to continue bit for bit: state with motor
-        targets, contact history of the warm start, episode clocks, error flags, touch sensors, object home poses."""
+        targets, contact history of the warm start, episode clocks, error flags, touch sensors, object home poses and object
+        dynamics."""
         n = C.c_size_t()
         nat.check(self.L.rr_checkpoint_bytes(self.h, C.byref(n)))
         buf = np.empty(n.value, np.uint8)
@@ -200,6 +202,68 @@ class BatchedREALRobotEnv:
             m = np.ascontiguousarray(env_mask, dtype=np.uint8)
             assert m.shape == (self.N,)
         nat.check(self.L.rr_set_object_poses(self.h, p.ctypes.data, m.ctypes.data if m is not None else None))
+
+    # ------------------------------------------------------------------ object dynamics (changeDynamics / getDynamicsInfo)
+    def _dynamics_raw(self):
+        out = np.empty((self.N, self.n_objects, 8), np.float32)
+        nat.check(self.L.rr_get_object_dynamics(self.h, out.ctypes.data))
+        return out
+
+    @staticmethod
+    def _dynamics_dict(raw):
+        return {'mass': raw[..., 0].copy(), 'inertia': raw[..., 1:4].copy(), 'friction': raw[..., 4].copy(),
+                'restitution': raw[..., 5].copy(), 'rolling': raw[..., 6].copy(), 'spinning': raw[..., 7].copy()}
+
+    def object_dynamics(self):
+        """Every env's object dynamics: dict of float32 arrays mass [N, n_objects], inertia [N, n_objects, 3] (principal moments,
+        object frame), friction (lateral), restitution, rolling, spinning [N, n_objects]."""
+        return self._dynamics_dict(self._dynamics_raw())
+
+    def default_object_dynamics(self):
+        """The model's values (what a fresh handle has), same layout as `object_dynamics()`."""
+        return self._dynamics_dict(self._dyn_default)
+
+    def set_object_dynamics(self, mass=None, inertia=None, friction=None, restitution=None, rolling=None, spinning=None,
+                            env_mask=None):
+        """pybullet's changeDynamics for the objects of a batch (rr_set_object_dynamics).  Every argument broadcasts to
+        [N, n_objects] (`inertia`: [N, n_objects, 3], the principal moments in the object frame); None keeps the current value.
+        env_mask (uint8 / bool [N], None: all envs) selects the envs that change.  Mass and inertia must be finite and > 0,
+        friction, restitution, rolling and spinning friction finite and >= 0; anything else raises ValueError before the library
+        is called, and nothing changes.
+        `mass` without `inertia` scales the current inertia by the ratio of the masses (uniform density): a choice of this
+        project -- what pybullet does with the inertia on a mass-only changeDynamics cannot be checked here.
+        The values outlive reset(), `state = ...` and teleports, and checkpoints carry them."""
+        N, k = self.N, self.n_objects
+        cur = self._dynamics_raw()
+        new = cur.astype(np.float64)
+
+        def arg(v, name, shape, positive):
+            try:
+                a = np.broadcast_to(np.asarray(v, dtype=np.float64), shape)
+            except (ValueError, TypeError):
+                raise ValueError("%s: cannot broadcast an array of shape %s to %s" % (name, np.shape(v), shape))
+            if not np.isfinite(a).all() or ((a <= 0).any() if positive else (a < 0).any()):
+                raise ValueError("%s must be finite and %s" % (name, "> 0" if positive else ">= 0"))
+            return a
+        if mass is not None:
+            new[..., 0] = arg(mass, 'mass', (N, k), True)
+            if inertia is None:
+                new[..., 1:4] = cur[..., 1:4] * (new[..., 0] / cur[..., 0])[..., None]
+        if inertia is not None:
+            new[..., 1:4] = arg(inertia, 'inertia', (N, k, 3), True)
+        for col, (name, v) in enumerate((('friction', friction), ('restitution', restitution), ('rolling', rolling),
+                                         ('spinning', spinning)), start=4):
+            if v is not None:
+                new[..., col] = arg(v, name, (N, k), False)
+        new = new.astype(np.float32)
+        if not np.isfinite(new).all() or (new[..., :4] <= 0).any():     # (an inertia scaled out of float32's range)
+            raise ValueError("mass and inertia must be finite and > 0 in float32")
+        m = None
+        if env_mask is not None:
+            m = np.ascontiguousarray(env_mask).astype(np.uint8)
+            if m.shape != (N,):
+                raise ValueError("env_mask must have shape (%d,)" % N)
+        nat.check(self.L.rr_set_object_dynamics(self.h, new.ctypes.data, m.ctypes.data if m is not None else None))
 
     def set_object_home(self, env, obj, pose7):
         """Pose object `obj` of env `env` (None: every env) returns to on reset / when it leaves the table

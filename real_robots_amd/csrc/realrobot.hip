@@ -90,7 +90,7 @@ struct ShapeData {    // global memory, read uniformly
     float edges[MAXSHAPES][EMAXC][12];    // long sharp hull edges: p0, p1 - p0, the two facet normals (owner frame)
     int pair_a[MAXPAIRS], pair_b[MAXPAIRS];
     int pair_meta[MAXPAIRS][4];      // {bodyA, bodyB, link of shape a, 0}: body = -1 static, 0..15 robot body, 16+i object i
-    float pair_mat[MAXPAIRS][4];     // {friction, restitution} products of the two shapes, combined {rolling, spinning} friction
+    float pair_mat[MAXPAIRS][4];     // the blob's materials of every pair (pair_materials): the defaults of DevPtrs::pair_mat, host side only
 };
 
 struct RenderModel {
@@ -158,6 +158,9 @@ struct DevPtrs {
     unsigned *errflags;// [N]
     const float *body_tab; // [NB][16] per-body constants of k_prep16's body lanes (BT_*: com, inertia, mass, joint damping, axis)
     float *obj_home;   // [NOBJ*7][N] per-env pose an object is put back to by reset / the out-of-bounds rule (robot.py:19-24, mutable there)
+    const float *obj_dyn;   // [NOBJ*4][N] per-env {mass, ixx, iyy, izz} of object i in rows 4 i .. 4 i + 3 (rr_set_object_dynamics; defaults: the blob's)
+    const float4 *pair_mat;   // [N][npairs] per-env contact materials of every collision pair {friction, restitution, rolling, spinning}, combined
+                              // on the host (pair_materials in rr_host.inc) from the shapes' values and the env's object dynamics
     float4 *grows;     // [N * GP_RECS][16] generic solver rows in the slot layout, as canonical normal rows and as the blocks the sweeps stream (GP_*)
     float *cmd;        // [N][9]
     const float *cmd_in; // [N][9] the command buffer of this step: cmd, or the caller's device buffer (read in place)

@@ -633,7 +633,7 @@ __device__ __forceinline__ void collide_env(const SimParams &P, const DevPtrs &D
                 float4 *rec = D.clist_next + ((size_t)env * MAXC + (ok_ & 255) + r) * 3;
                 rec[0] = make_float4(a.x, a.y, a.z, b.x);
                 rec[1] = make_float4(b.y, b.z, a.w, __int_as_float(meta | (pair << 24)));      // (bits 24..30: the pair, for the next step's matching)
-                rec[2] = *(const float4 *)S->pair_mat[pair];
+                rec[2] = D.pair_mat[(size_t)env * P.npairs + pair];       // (the env's own materials: rr_set_object_dynamics)
                 // warm start (oracle warm_start_match()): the previous contact of the same bodies nearest to this one within the
                 // margin, unless another new contact of those bodies is nearer to it (or as near and earlier in the list).
                 // Pairs with the same bodies -- a moving shape against the statics -- are at most three consecutive ones, so

@@ -110,7 +110,24 @@ struct rr_env {
     // the host until the copy is done; from these slots it is asynchronous, and a slot is reused only after the event
     // recorded behind its copy has completed
     char *pin_buf[4]; hipEvent_t pin_ev[4]; bool pin_used[4]; int pin_next; size_t pin_bytes;
+    // per-env object dynamics (rr_set_object_dynamics): host copies every upload of D.obj_dyn / D.pair_mat is made from
+    std::vector<float> dyn;        // [N][nobj][8] {mass, ixx, iyy, izz, lateral friction, restitution, rolling, spinning}
+    std::vector<float> pair_host;  // [N][npairs][4] the env's combined contact materials (pair_materials)
+    std::vector<float> shape_mat;  // [ns][4] the blob's {friction, restitution, rolling, spinning} of every collision shape
+    std::vector<int> shape_obj;    // [ns] the free object a shape belongs to, -1 for the table / shelf / robot
+    std::vector<int> pair_shapes;  // [npairs][2] shapes a, b of every collision pair
 };
+
+// The combining rule of the contact materials of two shapes (btManifoldResult::calculateCombinedFriction / Restitution /
+// RollingFriction / SpinningFriction, SURVEY A.1.6): products of friction and restitution, r_a mu_b + r_b mu_a at most 10 for
+// rolling and spinning.  The one place that knows it: the blob's table (rr_create) and every env's (rr_set_object_dynamics).
+// Host arithmetic on purpose: the device would contract the sums into fused multiply-adds of other last bits.
+static void pair_materials(const float *a, const float *b, float *out) {
+    out[0] = a[0] * b[0]; out[1] = a[1] * b[1];
+    out[2] = std::min(a[2] * b[0] + b[2] * a[0], 10.0f);
+    out[3] = std::min(a[3] * b[0] + b[3] * a[0], 10.0f);
+}
+static int upload_dynamics(rr_env *e);
 
 // The lagged host copy of the heavy (which 0) / very heavy (which 1) list length: written to mapped pinned memory by a recent
 // step's kernels, read here without any synchronisation -- it only ever selects a launch shape or a placement, never a result
@@ -431,11 +448,24 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
         S.pair_meta[k][0] = S.otype[sa] == 0 ? -1 : (S.otype[sa] == 1 ? S.oidx[sa] : 16 + S.oidx[sa]);
         S.pair_meta[k][1] = S.otype[sb] == 0 ? -1 : (S.otype[sb] == 1 ? S.oidx[sb] : 16 + S.oidx[sb]);
         S.pair_meta[k][2] = S.link[sa]; S.pair_meta[k][3] = 0;
-        S.pair_mat[k][0] = S.fric[sa] * S.fric[sb]; S.pair_mat[k][1] = S.rest[sa] * S.rest[sb];
-        // btManifoldResult::calculateCombinedRollingFriction / SpinningFriction: r_a mu_b + r_b mu_a, at most 10 (SURVEY A.1.6)
-        S.pair_mat[k][2] = std::min(S.roll[sa] * S.fric[sb] + S.roll[sb] * S.fric[sa], 10.0f);
-        S.pair_mat[k][3] = std::min(S.spin[sa] * S.fric[sb] + S.spin[sb] * S.fric[sa], 10.0f);
+        const float ma[4] = {S.fric[sa], S.rest[sa], S.roll[sa], S.spin[sa]}, mb[4] = {S.fric[sb], S.rest[sb], S.roll[sb], S.spin[sb]};
+        pair_materials(ma, mb, S.pair_mat[k]);
+        e->pair_shapes.push_back(sa); e->pair_shapes.push_back(sb);
     }
+    for (int s = 0; s < ns; s++) {
+        e->shape_mat.insert(e->shape_mat.end(), {S.fric[s], S.rest[s], S.roll[s], S.spin[s]});
+        e->shape_obj.push_back(S.otype[s] == 2 && S.oidx[s] >= 0 && S.oidx[s] < P.nobj ? S.oidx[s] : -1);
+    }
+    // the default dynamics of every env: the blob's mass and inertia of an object, the materials of its first collision shape
+    // (the model has one per object), and the blob's pair table
+    e->dyn.assign((size_t)N * P.nobj * 8, 0.0f);
+    for (int i = 0; i < P.nobj; i++) {
+        float row[8] = {B.obj_mass[i], B.obj_inertia[i][0], B.obj_inertia[i][1], B.obj_inertia[i][2], 0.0f, 0.0f, 0.0f, 0.0f};
+        for (int s = ns - 1; s >= 0; s--) if (e->shape_obj[s] == i) memcpy(row + 4, &e->shape_mat[4 * s], 16);
+        for (int n = 0; n < N; n++) memcpy(&e->dyn[((size_t)n * P.nobj + i) * 8], row, 32);
+    }
+    e->pair_host.resize((size_t)N * np * 4);
+    for (int n = 0; n < N; n++) memcpy(&e->pair_host[(size_t)n * np * 4], S.pair_mat, (size_t)np * 16);
 
     // k_collide's warm-start matching looks for the previous contacts of the same bodies (bodyA, bodyB, linkA) among the
     // pairs pair-2 .. pair+2 only: pairs with equal keys must form runs of at most three consecutive pairs (one collision shape
@@ -524,6 +554,12 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
     ALLOC(D.timestep, (size_t)N);
     ALLOC(D.errflags, (size_t)N);
     ALLOC(D.obj_home, (size_t)NOBJ * 7 * N);
+    {
+        float *od_ = nullptr; float4 *pm_ = nullptr;
+        ALLOC(od_, (size_t)NOBJ * 4 * N); ALLOC(pm_, (size_t)N * np);
+        D.obj_dyn = od_; D.pair_mat = pm_;
+        if ((rc = upload_dynamics(e)) != RR_OK) { rr_destroy(e); return rc; }
+    }
     ALLOC(D.grows, (size_t)N * GP_RECS * 16);        // (zeroed: the dummy block / contact records stay all zero)
     ALLOC(D.cmd, (size_t)N * 9);
     ALLOC(D.joints, (size_t)N * 9);
@@ -710,6 +746,62 @@ int rr_set_object_home(rr_env *e, int32_t env_index, int32_t obj, const float *p
         }
     }
     HIPCHK(hipStreamSynchronize(e->stream));   // pose7 is host memory
+    return RR_OK;
+}
+
+// The device tables of the per-env object dynamics from the host copies: D.obj_dyn ({mass, inertia} of every object, SoA; objects
+// the handle does not simulate keep the blob's values) and D.pair_mat (every env's combined materials).  Synchronous.
+static int upload_dynamics(rr_env *e) {
+    const size_t N = e->P.N;
+    const int no = e->P.nobj;
+    std::vector<float> od((size_t)NOBJ * 4 * N);
+    for (int i = 0; i < NOBJ; i++)
+        for (int k = 0; k < 4; k++)
+            for (size_t n = 0; n < N; n++)
+                od[(size_t)(4 * i + k) * N + n] = i < no ? e->dyn[(n * no + i) * 8 + k] : (k == 0 ? e->B.obj_mass[i] : e->B.obj_inertia[i][k - 1]);
+    HIPCHK(hipSetDevice(e->cfg.device));
+    e->la_valid = false;          // the look-ahead's object terms and contact list were made with the old values
+    HIPCHK(hipMemcpyAsync((void *)e->D.obj_dyn, od.data(), od.size() * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync((void *)e->D.pair_mat, e->pair_host.data(), e->pair_host.size() * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));   // the sources are host memory
+    return RR_OK;
+}
+
+// changeDynamics / getDynamicsInfo of the free objects, per env (rows {mass, ixx, iyy, izz, lateral friction, restitution, rolling,
+// spinning}).  The rows of the masked envs are checked first and the call changes nothing unless all of them are valid; an object's
+// materials apply to all of its collision shapes, the pair materials of the env are combined again on the host (pair_materials).
+int rr_set_object_dynamics(rr_env *e, const float *dyn_host, const uint8_t *env_mask_host) {
+    if (!e || !dyn_host) return fail(RR_EINVAL, "null argument");
+    const int N = e->P.N, no = e->P.nobj;
+    for (int n = 0; n < N; n++) {
+        if (env_mask_host && !env_mask_host[n]) continue;
+        for (int i = 0; i < no; i++) {
+            const float *r = dyn_host + ((size_t)n * no + i) * 8;
+            for (int k = 0; k < 8; k++)
+                if (!std::isfinite(r[k]) || (k < 4 ? !(r[k] > 0.0f) : !(r[k] >= 0.0f)))
+                    return fail(RR_EINVAL, "rr_set_object_dynamics: env " + std::to_string(n) + " object " + std::to_string(i) +
+                                               (k < 4 ? ": mass and inertia must be finite and > 0" : ": friction, restitution, rolling and spinning friction must be finite and >= 0"));
+        }
+    }
+    const int np = e->P.npairs;
+    for (int n = 0; n < N; n++) {
+        if (env_mask_host && !env_mask_host[n]) continue;
+        memcpy(&e->dyn[(size_t)n * no * 8], dyn_host + (size_t)n * no * 8, (size_t)no * 32);
+        for (int k = 0; k < np; k++) {
+            float m[2][4];
+            for (int j = 0; j < 2; j++) {
+                const int s = e->pair_shapes[2 * k + j], o = e->shape_obj[s];
+                memcpy(m[j], o >= 0 ? &e->dyn[((size_t)n * no + o) * 8 + 4] : &e->shape_mat[4 * s], 16);
+            }
+            pair_materials(m[0], m[1], &e->pair_host[((size_t)n * np + k) * 4]);
+        }
+    }
+    return upload_dynamics(e);
+}
+
+int rr_get_object_dynamics(rr_env *e, float *dyn_out_host) {
+    if (!e || !dyn_out_host) return fail(RR_EINVAL, "null argument");
+    memcpy(dyn_out_host, e->dyn.data(), e->dyn.size() * 4);
     return RR_OK;
 }
 
@@ -1230,8 +1322,9 @@ int rr_set_state(rr_env *e, const float *state_host) {
 
 // ---- checkpoint: everything a later restore needs to continue bit for bit ----------------------------------------------------
 // {header, state slab [72][N] (incl. motor targets), contact count [N], contact list [N][48][3] float4, normal forces [N][48],
-//  timestep [N], errflags [N], touch [N][4], object home poses [21][N]}: the 61-float state of RR_F_STATE plus the contact
-// history of the warm start (Bullet: the persistent manifolds with their cached impulses) and the episode clocks.
+//  timestep [N], errflags [N], touch [N][4], object home poses [21][N], object dynamics [N][nobj][8], pair materials
+//  [N][npairs][4]}: the 61-float state of RR_F_STATE plus the contact history of the warm start (Bullet: the persistent manifolds
+// with their cached impulses), the episode clocks and the per-env object data.
 // The header also carries every parameter the continuation depends on: a blob restored into a handle that steps differently
 // (other dt / ERP / margin / sweeps / warm-start factor / motor gains and force / damping / rate-limit switch / object-lane
 // capacity / inertia source / edge contacts) is rejected
@@ -1241,7 +1334,7 @@ struct CkptHeader { char magic[8]; int32_t version, N, nobj, iters; float dt, er
 static CkptHeader ckpt_header(const rr_env *e) {
     CkptHeader hd;
     memset(&hd, 0, sizeof hd);
-    memcpy(hd.magic, "RRCKPT03", 8); hd.version = 3; hd.N = e->P.N; hd.nobj = e->P.nobj; hd.iters = e->P.iters;
+    memcpy(hd.magic, "RRCKPT04", 8); hd.version = 4; hd.N = e->P.N; hd.nobj = e->P.nobj; hd.iters = e->P.iters;
     hd.dt = e->P.dt; hd.erp = e->P.erp; hd.margin = e->P.margin; hd.warmstart = e->P.warmstart;
     hd.os_cap = e->P.os_cap; hd.edge_contacts = e->P.edge_contacts; hd.urdf_inertia = e->cfg.use_urdf_inertia;
     hd.no_rate_limit = (e->cfg.solver_flags & RR_SOLVER_NO_RATE_LIMIT) ? 1 : 0;
@@ -1251,7 +1344,7 @@ static CkptHeader ckpt_header(const rr_env *e) {
 }
 static size_t ckpt_bytes(const rr_env *e) {
     const size_t N = e->P.N;
-    return sizeof(CkptHeader) + 4 * (ST_TOTAL * N + N + N * MAXC * 12 + N * MAXC + N + N + N * 4 + NOBJ * 7 * N);
+    return sizeof(CkptHeader) + 4 * (ST_TOTAL * N + N + N * MAXC * 12 + N * MAXC + N + N + N * 4 + NOBJ * 7 * N) + 4 * (e->dyn.size() + e->pair_host.size());
 }
 int rr_checkpoint_bytes(rr_env *e, size_t *bytes) {
     if (!e || !bytes) return fail(RR_EINVAL, "null argument");
@@ -1269,7 +1362,13 @@ static int ckpt_copy(rr_env *e, char *host, bool save) {
         else HIPCHK(hipMemcpyAsync(p.dev, h, p.bytes, hipMemcpyHostToDevice, e->stream));
         h += p.bytes;
     }
-    return RR_OK;
+    // the object dynamics: from the host copies (a restore uploads them again)
+    for (std::vector<float> *v : {&e->dyn, &e->pair_host}) {
+        if (save) memcpy(h, v->data(), v->size() * 4);
+        else memcpy(v->data(), h, v->size() * 4);
+        h += v->size() * 4;
+    }
+    return save ? RR_OK : upload_dynamics(e);
 }
 int rr_checkpoint_save(rr_env *e, void *dst_host, size_t bytes) {
     if (!e || !dst_host) return fail(RR_EINVAL, "null argument");

@@ -18,12 +18,14 @@ __device__ __forceinline__ bool object_out_of_bounds(float x, float z, float tab
 // the out-of-bounds rule (env.py:257-264) sends home is taken at its home pose, at rest (the solve kernel writes that pose into the
 // state when the step starts).  One function for every form of the preparation (a thread per env, sixteen lanes per env): the same
 // expressions, hence the same bits.
-// (ixx, iyy, izz: the object's principal inertias, B.obj_inertia[i] -- handed in so that a lane-varying i needs no indexed read of the kernel arguments)
+// (the object's principal inertias: the env's own, D.obj_dyn -- rr_set_object_dynamics)
 // Contraction-free: the two callers (a loop over the objects on one thread; one object per lane) otherwise get different fused
 // multiply-adds out of the same source -- a loop-invariant product hoisted here, fused there -- and the forms of a step must agree bit for bit.
 #pragma clang fp contract(off)
-__device__ __forceinline__ void object_terms(const BodyParams &B, const SimParams &P, const DevPtrs &D, int env, int i, float ixx, float iyy, float izz, bool store = true) {
+__device__ __forceinline__ void object_terms(const BodyParams &B, const SimParams &P, const DevPtrs &D, int env, int i, bool store = true) {
     const int N = P.N;
+    const float *od = D.obj_dyn + env;
+    const float ixx = od[(4 * i + 1) * N], iyy = od[(4 * i + 2) * N], izz = od[(4 * i + 3) * N];
     const float *state = D.state;
     float *scratch = D.scratch;
     float px = STT(ST_OPOS + 3 * i), py = STT(ST_OPOS + 3 * i + 1), pz = STT(ST_OPOS + 3 * i + 2);
@@ -228,7 +230,7 @@ __device__ __forceinline__ void prep_body(const BodyParams &B, const SimParams &
     if (PHASE == 2) return;
     // ---- objects: rotation, inverse inertia, unconstrained velocities -- of the pose that counts: an object the out-of-bounds
     // rule (env.py:257-264) sends home is taken at its home pose, at rest (the solve kernel writes that pose into the state when the step starts)
-    for (int i = 0; i < P.nobj; i++) object_terms(B, P, D, env, i, B.obj_inertia[i][0], B.obj_inertia[i][1], B.obj_inertia[i][2]);
+    for (int i = 0; i < P.nobj; i++) object_terms(B, P, D, env, i);
 }
 // One thread per env of the class `sel` (pick_env); the launches cover N work items whatever the class (a heavy list's length
 // is known on the device only; work items past its end exit at once).
@@ -330,9 +332,7 @@ __device__ __forceinline__ void prep16_objects(const BodyParams &B, const SimPar
     const int o = t % 3;
     const int env = pick_env(D, sel, (int)blockIdx.x * P16_ENVS + t / 3, P.N);
     if (env < 0 || o >= P.nobj || (D.errflags[env] & 1u)) return;
-    object_terms(B, P, D, env, o, o == 0 ? B.obj_inertia[0][0] : (o == 1 ? B.obj_inertia[1][0] : B.obj_inertia[2][0]),
-                 o == 0 ? B.obj_inertia[0][1] : (o == 1 ? B.obj_inertia[1][1] : B.obj_inertia[2][1]),
-                 o == 0 ? B.obj_inertia[0][2] : (o == 1 ? B.obj_inertia[1][2] : B.obj_inertia[2][2]));
+    object_terms(B, P, D, env, o);
 }
 
 template <int PHASE>       // 0: everything (k_prep_ab16: wave 0 the robots, wave 1 the objects); 1: frames + objects (k_prep_a16); 2: joint-space dynamics only (k_prep_b16)

@@ -424,7 +424,7 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
     for (int kk = 0; kk < 9; kk++) myobj.Iinv.m[kk] = SCR(S_OIINV + 9 * ob_l + kk);
     myobj.vs = mk(SCR(S_OVS + 3 * ob_l), SCR(S_OVS + 3 * ob_l + 1), SCR(S_OVS + 3 * ob_l + 2));
     myobj.ws = mk(SCR(S_OWS + 3 * ob_l), SCR(S_OWS + 3 * ob_l + 1), SCR(S_OWS + 3 * ob_l + 2));
-    myobj.imass = 1.0f / (ob_l == 0 ? B.obj_mass[0] : (ob_l == 1 ? B.obj_mass[1] : B.obj_mass[2]));
+    myobj.imass = 1.0f / D.obj_dyn[(size_t)(4 * ob_l) * N + env];          // (the env's own mass: rr_set_object_dynamics)
     // ---- the command part of the step -- everything that needs the action: limitActionByJoint (env.py:314-321), the clipping
     // and gripper coupling of Kuka.apply_action (robot.py:188-201) -> the motor target of this lane's joint; a non-finite
     // command flags the env (robot.py:189 asserts) and the env does not step.  It also APPLIES the out-of-bounds rule
@@ -854,7 +854,9 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
     // (dv, dw) of object lane-11 on lanes 11..13
     float dq = wsA, vb = wsB;          // (warm start: the inherited impulses of the generic normal rows are already applied)
     v2f V01 = P2(0.0f, 0.0f), V23 = P2(0.0f, 0.0f), V45 = P2(0.0f, 0.0f);      // (dv.xy) (dv.z dw.x) (dw.yz), REG_ROW_STEP
-    const float inv_mass = lo_ >= 0 ? 1.0f / B.obj_mass[lo_ >= 0 ? lo_ : 0] : 0.0f;
+    // (1 / mass of the lane's object as its L_OBJ record holds it -- the word the light object wave reads too; an LDS read
+    // instead of a register held from the stage-in.  Lanes of objects the handle does not simulate have no rows to step.)
+    const float inv_mass = lo_ >= 0 ? LD(L_OBJ + 20 * (lo_ >= 0 ? lo_ : 0) + 3) : 0.0f;
     const float max_imp = P.max_impulse;
     const float m_rhs = l < NB ? LD(L_MOT + 3 * lj) : 0.0f, m_dinv = l < NB ? LD(L_MOT + 3 * lj + 1) : 0.0f;
     float m_lam = 0.0f, m_c = m_rhs, m_keep = 0.0f;      // m_c = lambda + rhs of this lane's motor row (brought up to date once per sweep, SWEEP_MOTORS)

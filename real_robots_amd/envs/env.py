@@ -99,7 +99,8 @@ class EyeCamera:
 
 class _BulletShim:
     """`env._p`: the handful of pybullet client calls that callers of the reference use on the env (videomaker.py:84,124,
-    generate_goals.py:105), answered from the batched backend.  Anything else raises AttributeError -- there is no Bullet here."""
+    generate_goals.py:105) and changeDynamics / getDynamicsInfo of the objects, answered from the batched backend.  Anything else
+    raises AttributeError -- there is no Bullet here."""
 
     def __init__(self, env):
         self._env = env
@@ -127,6 +128,48 @@ class _BulletShim:
 
     def stepSimulation(self):
         self._env._backend().step(None)
+
+    # changeDynamics keyword -> BatchedREALRobotEnv.set_object_dynamics argument
+    _DYNAMICS_KW = {'mass': 'mass', 'localInertiaDiagonal': 'inertia', 'lateralFriction': 'friction', 'restitution': 'restitution',
+                    'rollingFriction': 'rolling', 'spinningFriction': 'spinning'}
+
+    def _object_index(self, call, body_uid, link_index):
+        n = self._env._n_objects
+        if not 2 <= int(body_uid) < 2 + n:
+            raise NotImplementedError("%s: body %r -- only the objects (unique ids 2..%d) are supported" % (call, body_uid, 1 + n))
+        if int(link_index) != -1:
+            raise NotImplementedError("%s: link %r -- the objects have only their base (linkIndex -1)" % (call, link_index))
+        return int(body_uid) - 2
+
+    def changeDynamics(self, bodyUniqueId, linkIndex, **kwargs):
+        """pybullet.changeDynamics for the objects (body unique ids 2.., linkIndex -1): mass, localInertiaDiagonal,
+        lateralFriction, restitution, rollingFriction, spinningFriction (BatchedREALRobotEnv.set_object_dynamics: a mass without
+        localInertiaDiagonal scales the inertia by the mass ratio).  Any other keyword, body or link raises NotImplementedError."""
+        o = self._object_index('changeDynamics', bodyUniqueId, linkIndex)
+        other = sorted(k for k in kwargs if k not in self._DYNAMICS_KW)
+        if other:
+            raise NotImplementedError("changeDynamics: unsupported keyword(s) %s (supported: %s)" % (', '.join(other), ', '.join(self._DYNAMICS_KW)))
+        be = self._env._backend()
+        cur = be.object_dynamics()
+        args = {}
+        for kw, v in kwargs.items():
+            field = self._DYNAMICS_KW[kw]
+            a = cur[field].astype(np.float64)
+            a[0, o] = v
+            args[field] = a
+        be.set_object_dynamics(**args)
+
+    def getDynamicsInfo(self, bodyUniqueId, linkIndex):
+        """pybullet.getDynamicsInfo for the objects, in pybullet's layout: (mass, lateral friction, local inertia diagonal, local
+        inertial position, local inertial orientation, restitution, rolling friction, spinning friction, contact damping, contact
+        stiffness, body type, collision margin).  Without a counterpart here, with Bullet's defaults: the inertial frame (0, 0, 0) /
+        (0, 0, 0, 1) (the objects' URDFs put it at the origin), contact damping and stiffness -1.0 (not set), body type 1 (rigid
+        body) and the collision margin 0.04 (Bullet's CONVEX_DISTANCE_MARGIN)."""
+        o = self._object_index('getDynamicsInfo', bodyUniqueId, linkIndex)
+        d = self._env._backend().object_dynamics()
+        return (float(d['mass'][0, o]), float(d['friction'][0, o]), tuple(float(x) for x in d['inertia'][0, o]),
+                (0.0, 0.0, 0.0), (0.0, 0.0, 0.0, 1.0), float(d['restitution'][0, o]), float(d['rolling'][0, o]),
+                float(d['spinning'][0, o]), -1.0, -1.0, 1, 0.04)
 
 
 class REALRobotEnv:

@@ -11,6 +11,13 @@ observation of the finished episode is in `infos["final_obs"]` (an object array:
 env, None elsewhere; `infos["_final_obs"]` is the mask of the envs it applies to) -- every action acts on the episode its observation came from, no action is dropped.
 Observations are batched numpy arrays; with `device_obs=True` the image / low-dim entries are the library's device
 buffers instead (DLPack / __cuda_array_interface__, zero copy into torch on ROCm).
+Domain randomisation of the object dynamics: `dynamics_randomization={'mass': (0.5, 2.0), 'friction': (0.5, 1.5)}` draws, for every
+env and object, a multiplier of the model's value uniformly from (low, high) per field (fields: mass, inertia, friction,
+restitution, rolling, spinning; inertia takes one multiplier for its three moments, and follows the mass multiplier when only the
+mass is randomised -- uniform density).  reset(seed=...) draws every env's values from numpy.random.default_rng(seed); the
+same-step autoreset draws again for the truncated envs only.  The values in force are returned under `infos["object_dynamics"]`
+(a dict of arrays like BatchedREALRobotEnv.object_dynamics(): every env after reset(); after an autoreset
+`infos["_object_dynamics"]` masks the envs that drew new ones).
 """
 import numpy as np
 
@@ -39,7 +46,7 @@ def _batch_dict_space(space, n):
 
 class REALRobotVectorEnv(_Base):
     def __init__(self, num_envs, objects=3, additional_obs=False, eye_width=320, eye_height=240, device=0,
-                 max_episode_steps=int(15e6), render_every_step=True, device_obs=False, solver=None):
+                 max_episode_steps=int(15e6), render_every_step=True, device_obs=False, solver=None, dynamics_randomization=None):
         self.num_envs = int(num_envs)
         self._robot = Kuka(additional_obs, objects, eye_width, eye_height, env=None)
         self.single_action_space = spaces.Dict({"joint_command": self._robot.action_space, "render": spaces.MultiBinary(1)})
@@ -58,6 +65,36 @@ class REALRobotVectorEnv(_Base):
         # host-side episode clocks (no device read-back per step): the batched env behind this adapter is private to it, every
         # path that resets an env goes through reset() / step() below and resets its clock with it
         self._steps = np.zeros(self.num_envs, np.int64)
+        self._dyn_rand = None
+        if dynamics_randomization:
+            self._dyn_rand = {}
+            for k, r in dynamics_randomization.items():
+                if k not in self.DYNAMICS_FIELDS:
+                    raise ValueError("dynamics_randomization: unknown field %r (known: %s)" % (k, ', '.join(self.DYNAMICS_FIELDS)))
+                lo, hi = (float(x) for x in r)
+                if not (np.isfinite(lo) and np.isfinite(hi) and 0 <= lo <= hi) or (k in ('mass', 'inertia') and lo <= 0):
+                    raise ValueError("dynamics_randomization[%r]: need finite 0 <= low <= high (low > 0 for mass / inertia)" % k)
+                self._dyn_rand[k] = (lo, hi)
+            self._dyn_default = self._be.default_object_dynamics()
+        self._dyn_rng = np.random.default_rng()
+
+    DYNAMICS_FIELDS = ('mass', 'inertia', 'friction', 'restitution', 'rolling', 'spinning')
+
+    def _draw_dynamics(self, mask):
+        """Draws new multipliers for the envs in `mask` (bool [N]) and applies them; returns the values in force."""
+        n, k = int(mask.sum()), self._be.n_objects
+        mult = {f: self._dyn_rng.uniform(*self._dyn_rand[f], size=(n, k)) for f in self.DYNAMICS_FIELDS if f in self._dyn_rand}
+        if 'inertia' not in mult and 'mass' in mult:
+            mult['inertia'] = mult['mass']
+        args = {}
+        cur = self._be.object_dynamics()
+        for f, m in mult.items():
+            v = cur[f].astype(np.float64)
+            d = self._dyn_default[f][mask].astype(np.float64)
+            v[mask] = d * (m[..., None] if f == 'inertia' else m)
+            args[f] = v
+        self._be.set_object_dynamics(env_mask=mask.astype(np.uint8), **args)
+        return self._be.object_dynamics()
 
     # ------------------------------------------------------------------ observations
     def _obs(self, rendered):
@@ -73,11 +110,16 @@ class REALRobotVectorEnv(_Base):
         return obs
 
     def reset(self, *, seed=None, options=None):
+        infos = {}
+        if seed is not None:
+            self._dyn_rng = np.random.default_rng(seed)
+        if self._dyn_rand:
+            infos["object_dynamics"] = self._draw_dynamics(np.ones(self.num_envs, bool))
         self._be.reset()
         self._steps[:] = 0
         if self.render_every_step:
             self._be.render()
-        return self._obs(self.render_every_step), {}
+        return self._obs(self.render_every_step), infos
 
     def step(self, actions):
         """actions: float array [N, 9] of joint commands (or a dict with "joint_command" [N, 9] and optional "render")."""
@@ -102,6 +144,9 @@ class REALRobotVectorEnv(_Base):
                     fin[i]["object_positions"] = op[i]
             infos["final_obs"] = fin
             infos["_final_obs"] = truncated.copy()
+            if self._dyn_rand:
+                infos["object_dynamics"] = self._draw_dynamics(truncated)
+                infos["_object_dynamics"] = truncated.copy()
             self._be.reset(truncated.astype(np.uint8))
             self._steps[truncated] = 0
             if render:
