@@ -5,6 +5,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR    (+ what the last timed step computed, as DIR/*.npy)
+    python bench.py --gpus 1 --steps K --warmup W --full                (+ roofline, secondary workloads, cpu_baseline)
 
 Headline workload (BASELINE.json configs[2], the configuration the metric is quoted on): REALRobot2020-R2J3-v0, 4096 envs
 per GPU, 3 objects, 128x128 top-down RGB + depth rendered every step; one "step" = one env.step() of every env in the
@@ -12,7 +13,12 @@ batch.  Joint commands: README-style resample-and-hold `action_space.sample()` o
 (robot.py:58-67), keyed by global env id, resident in HBM before the timed region.
 Weak scaling by default (every rank owns --envs-per-gpu envs; `--scaling strong` splits a fixed total over the ranks);
 no collective on the stepping path; `--gather lowdim|images` adds the optional policy-side observation all-gather
-(RCCL).  Rank 0 prints ONE JSON line.  Extra objects in that line:
+(RCCL).  Rank 0 prints ONE JSON line.  Beside the headline it always carries
+  timed_steps / heavy_envs   which steps of the workload the timed region covered and how many envs were heavy / very heavy
+                (solved and rendered on the side streams, DESIGN.md 5.1) at its start and end: full-range random commands
+                press more and more arms onto the table, so the rate depends on the window
+A plain run does only what the headline needs: set-up, presettle + warm-up, the timed steps, --dump-outputs, the line.
+`--full` adds what takes runs of its own (without it `roofline` is null and the other two are absent):
   roofline      per-kernel HIP-event durations (library stream; the launches of a step one after the other: k_solve, k_raster
                 ... are what the main stream runs for the light envs, k_solve_heavy / render_heavy what the side stream runs
                 beside them for the few heavy ones) and, for the unit that dominates the step's critical path, ALGORITHMIC
@@ -22,9 +28,6 @@ no collective on the stepping path; `--gather lowdim|images` adds the optional p
                 `roofline.valu` prices the dominant kernel against the VALU issue rate a sample-test-like instruction mix reaches
                 in this run on the same device (rr_device_microbench kind 2), which is what actually bounds it; the sweep over
                 instruction kinds and occupancies behind that choice is profiles/r04_valu_issue.txt.
-  timed_steps / heavy_envs   which steps of the workload the timed region covered and how many envs were heavy / very heavy
-                (solved and rendered on the side streams, DESIGN.md 5.1) at its start and end: full-range random commands
-                press more and more arms onto the table, so the rate depends on the window
   secondary     (N=1 only) the same library on the other workloads a reader needs to judge the headline: the LATE window
                 (steps 2000-2200, SURVEY 8(d) config 3's horizon), half-range commands (round 1's headline), macro-action
                 pushing and a batched evaluate() (BASELINE config 5), BASELINE config 2 (1024 envs, 1 object, no render),
@@ -357,6 +360,108 @@ def secondary_workloads(torch, np, nat, BatchedREALRobotEnv, device, steps):
     return out
 
 
+def roofline_leg(args, env, nat, n_local, n_obj, render, step_fn, elapsed, device):
+    """--full: per-kernel HIP-event durations over steps of step_fn right behind the timed region (every kernel alone on the
+    library's stream) and the unit that dominates the step's critical path against the HBM and VALU peaks, with the device
+    micro-benchmarks of this run and the committed PMC profiles of the same configuration."""
+    nprof = min(20, args.steps)
+    kernels, algo, frags = kernel_table(env, nat, n_local, n_obj, W, H, render, step_fn, nprof)
+    # the dominant kernel = the largest share of the step's critical path: the main stream's launches (the side stream's
+    # solve + render of the few heavy envs end before the main stream's render does, profiles/README.md)
+    dom_kernel = max((k for k in kernels if k not in SIDE_STREAM_KERNELS), key=lambda k: kernels[k]["avg_ms"])
+    dom = dom_kernel
+    if render:
+        # the image is produced by two kernels (visibility; deferred shading incl. putting vacated pixels back to the
+        # static layer): the stage as a whole is what SURVEY 8(d)'s image bytes belong to
+        members = [k for k in RENDER_KERNELS if k in kernels]
+        rms = sum(kernels[k]["avg_ms"] for k in members) + (kernels['render_heavy']["avg_ms"] if 'render_heavy' in kernels else 0.0)
+        kernels['render_stage'] = {"avg_ms": round(rms, 4), "launches": kernels['k_raster']["launches"], "members": members,
+                                   "algorithmic_GBs": round(algo['_image'] * n_local / (rms * 1e-3) / 1e9, 2),
+                                   "list_entries_per_env": round(frags, 1)}
+        algo['render_stage'] = algo['_image']
+        if dom_kernel in RENDER_KERNELS:
+            dom = 'render_stage'      # the image is the unit SURVEY 8(d) prices; its kernels are reported together
+    run_cfg = {"envs": n_local, "objects": n_obj, "width": W, "height": H, "render": bool(render),
+               "command_scale": args.command_scale, "solver_iters": args.solver_iters}
+    traffic, traffic_src = None, None
+    prof, why = load_profile('traffic_latest.json', run_cfg)
+    if prof is not None:
+        traffic = prof.get(dom)
+        traffic_src = "profiles/traffic_latest.json (%s): rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of this configuration, not of this run" % prof.get('source', '?')
+    else:
+        traffic_src = "null: " + why
+    # what this box achieves, measured in this run by the library (rr_device_microbench): HBM copy / triad bandwidth and the VALU
+    # issue rate of a sample-test-like mix at the raster kernel's occupancy (SURVEY 8(d): "measure achievable ... in the same run")
+    ubench, ubench_err = None, None
+    try:
+        ubench = nat.device_microbench(device)
+    except Exception as ex:            # the headline must not depend on it
+        ubench_err = repr(ex)
+    # `frac` is priced against a FIXED ceiling (256 CUs x 4 SIMDs x 2.4 GHz, one wave64 VALU instruction per 2 cycles on a
+    # SIMD-32 = 1228.8 G wave-instr/s); the rate a sample-test-like instruction mix reaches in this run is reported beside it
+    # (`reference_mix_rate`): it depends on the mix and on the clocks and is no ceiling
+    valu_peak = VALU_PEAK_WAVE_INSTR
+    mix_rate = ubench['valu_mix_G_wave_instr_s'] if ubench else None
+    valu = None
+    sq, why_sq = load_profile('sq_latest.json', run_cfg)
+    if sq is not None and dom_kernel in sq.get('valu_wave_instr_per_launch', {}):
+        wi = float(sq['valu_wave_instr_per_launch'][dom_kernel])
+        dur = kernels[dom_kernel]["avg_ms"] * 1e-3
+        valu = {"kernel": dom_kernel, "wave_instr_per_launch": round(wi), "wave_instr_per_env_step": round(wi / n_local, 1),
+                "achieved": round(wi / dur / 1e9, 2), "peak": round(valu_peak / 1e9, 1), "unit": "G wave64-instr/s",
+                "frac": round(wi / dur / valu_peak, 4),
+                "peak_is": "fixed: 256 CUs x 4 SIMDs x 2.4 GHz / 2 cycles per wave64 instruction (SIMD-32)",
+                "reference_mix_rate": mix_rate, "frac_of_reference_mix": (round(wi / dur / (mix_rate * 1e9), 4) if mix_rate else None),
+                "reference_mix_is": ("measured in this run: rr_device_microbench kind 2, a sample-test-like mix (sub, mul, fma, cmp, cndmask) at "
+                                     "eight waves per SIMD on every SIMD" if ubench else "not measured (%s)" % ubench_err) +
+                                    "; the sweep over instruction kinds and 1..8 waves per SIMD is profiles/r04_valu_issue.txt: single-kind "
+                                    "streams saturate at 505-553 G, the mix at 806-975 G",
+                "source": "SQ_INSTS_VALU of profiles/sq_latest.json (%s, same configuration) / this run's HIP-event duration" % sq.get('source', '?')}
+    else:
+        valu = {"kernel": dom_kernel, "frac": None, "note": "null: " + (why_sq or "kernel not in the profile")}
+    ach = kernels[dom]["algorithmic_GBs"]
+    # what the counters say bounds the dominant kernel: VALU issue when its issue fraction exceeds its HBM fraction (it does,
+    # tenfold); the HBM figures stay the contract's accounting (achieved / peak / frac)
+    traffic_lo = prof.get('lower_bound', {}).get(dom) if prof is not None else None
+    dom_ms = kernels[dom]["avg_ms"]
+    traffic_frac = round(traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 6) if traffic else None
+    bound = "valu" if (valu.get("frac") or 0.0) > max(ach / HBM_PEAK_GBS, traffic_frac or 0.0) else "hbm"
+    roofline = {"bound": bound, "kernel": dom if dom != 'render_stage' else "+".join(kernels['render_stage']['members']),
+                "dominant_single_kernel": dom_kernel,
+                "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 6),
+                "hbm_achievable_GBs": ({"copy": ubench['hbm_copy_GBs'], "triad": ubench['hbm_triad_GBs'],
+                                        "frac_of_copy": round(ach / ubench['hbm_copy_GBs'], 6),
+                                        "note": "device copy / triad of 256 MiB arrays measured in this run (rr_device_microbench); "
+                                                "`peak` stays the 8 TB/s spec figure the contract prescribes"}
+                                       if ubench else {"error": ubench_err}),
+                "achieved_is": "ALGORITHMIC bytes per launch / HIP-event duration (full images, although a frame rewrites only "
+                               "the pixels that changed) -- the contract's accounting, not a measured HBM rate; `traffic` is the measured one",
+                "traffic": traffic, "traffic_lower_bound": traffic_lo, "achieved_traffic_frac": traffic_frac,
+                "traffic_note": "HBM bytes of the unit per step from PMC counters; `traffic` applies the guide's x2 FETCH_SIZE correction "
+                                "(calibrated for 16-B-per-lane coalesced reads only) to every read, `traffic_lower_bound` to none: "
+                                "the unit's reads are mostly scattered 8/16-byte records, so the truth lies between; "
+                                "achieved_traffic_frac = traffic / duration / 8 TB/s",
+                "traffic_source": traffic_src,
+                "algorithmic_bytes_per_launch": round(algo[dom] * n_local),
+                "whole_step_algorithmic_GBs": round((algo['_state'] + (W * H * 7 if render else 0)) * n_local * args.steps / elapsed / 1e9, 2),
+                "bound_note": "`bound` comes from the counters: the dominant kernel's VALU issue fraction (roofline.valu) against its HBM "
+                              "fractions. achieved / peak / frac stay in the contract's HBM terms (algorithmic bytes): at 116 KB and "
+                              "~0.3 M instructions per env-step the path is instruction-issue / latency bound (DESIGN.md 5): k_raster's "
+                              "own VALU stream alone issues at 780-810 G wave-instr/s, with its 26.8 M LDS instructions per launch (2-6 "
+                              "CU-cycles each) at 350-700 G -- VALU issue and LDS instruction issue load the CU about equally "
+                              "(profiles/r04_raster_stream_issue.txt, r04_valu_lds_issue.txt), and 0.86 of the workgroup slots are busy "
+                              "(profiles/r04_raster_wg_timeline.txt)",
+                "valu": valu,
+                "kernels": kernels,
+                "timing_note": "per-kernel durations: HIP events on the library's stream, the launches of a step one after the "
+                               "other (no side-stream overlap), %d steps of the same workload right after the timed region; "
+                               "k_solve / k_render_setup / k_raster / k_shade = the main stream's launches (light envs), "
+                               "k_solve_heavy / render_heavy = the side streams' (heavy envs); k_prep / k_collide = the look-ahead "
+                               "of the next step, which an untimed step runs under the render; render_stage = the image of every "
+                               "env = k_raster + k_shade + render_heavy; rocprofv3 --stats of the overlapped run is under profiles/" % nprof}
+    return roofline
+
+
 def check_plan(rows, world, total, distinct_devices=True):
     """rows[r] = [1, device ordinal, first env id, end env id, rank] as gathered from rank r.  Returns None when the plan holds,
     else the reason: wrong rank count, a rank out of place, two ranks on one device, env-id blocks that do not tile [0, total)."""
@@ -434,8 +539,11 @@ def main():
                          '(objects landed on the table, arms moving, contacts active)')
     ap.add_argument('--image', default=None, help='WxH of the rendered observation (development A/B; the headline config is 128x128)')
     ap.add_argument('--no-render', action='store_true', help='dynamics-only variant (not the headline metric)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the secondary workloads (profiling runs)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: the per-kernel timing pass and roofline, the secondary '
+                         'workloads and the CPU baseline (a plain run prints "roofline": null)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the secondary workloads (profiling runs)')
     ap.add_argument('--scaling', choices=('weak', 'strong'), default='weak',
                     help='weak: --envs-per-gpu envs on every rank; strong: --envs-per-gpu envs in total, split over the ranks')
     ap.add_argument('--gather', nargs='?', const='lowdim', default='none', choices=('none', 'lowdim', 'images', 'images-delta'),
@@ -460,7 +568,7 @@ def main():
         args.gpus = world
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub_env:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub_env:
         cpu = cpu_baseline()             # before this process touches the GPU
 
     import numpy as np
@@ -609,109 +717,16 @@ def main():
             dist.destroy_process_group()
         return
 
-    # per-kernel device time (HIP events on the library's stream), separate pass right behind the timed region
-    nprof = min(20, args.steps)
-    base_t = args.presettle + args.warmup + args.steps
-    views_saved, views = views, None              # the timing pass measures the kernels, not the gather
-    kernels, algo, frags = kernel_table(env, nat, n_local, n_obj, W, H, render, lambda t: one_step(base_t + t), nprof)
-    views = views_saved
-    # the dominant kernel = the largest share of the step's critical path: the main stream's launches (the side stream's
-    # solve + render of the few heavy envs end before the main stream's render does, profiles/README.md)
-    dom_kernel = max((k for k in kernels if k not in SIDE_STREAM_KERNELS), key=lambda k: kernels[k]["avg_ms"])
-    dom = dom_kernel
-    if render:
-        # the image is produced by two kernels (visibility; deferred shading incl. putting vacated pixels back to the
-        # static layer): the stage as a whole is what SURVEY 8(d)'s image bytes belong to
-        members = [k for k in RENDER_KERNELS if k in kernels]
-        rms = sum(kernels[k]["avg_ms"] for k in members) + (kernels['render_heavy']["avg_ms"] if 'render_heavy' in kernels else 0.0)
-        kernels['render_stage'] = {"avg_ms": round(rms, 4), "launches": kernels['k_raster']["launches"], "members": members,
-                                   "algorithmic_GBs": round(algo['_image'] * n_local / (rms * 1e-3) / 1e9, 2),
-                                   "list_entries_per_env": round(frags, 1)}
-        algo['render_stage'] = algo['_image']
-        if dom_kernel in RENDER_KERNELS:
-            dom = 'render_stage'      # the image is the unit SURVEY 8(d) prices; its kernels are reported together
-    run_cfg = {"envs": n_local, "objects": n_obj, "width": W, "height": H, "render": bool(render),
-               "command_scale": args.command_scale, "solver_iters": args.solver_iters}
-    traffic, traffic_src = None, None
-    prof, why = load_profile('traffic_latest.json', run_cfg)
-    if prof is not None:
-        traffic = prof.get(dom)
-        traffic_src = "profiles/traffic_latest.json (%s): rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of this configuration, not of this run" % prof.get('source', '?')
-    else:
-        traffic_src = "null: " + why
-    # what this box achieves, measured in this run by the library (rr_device_microbench): HBM copy / triad bandwidth and the VALU
-    # issue rate of a sample-test-like mix at the raster kernel's occupancy ("measure achievable ... in the same run")
-    ubench, ubench_err = None, None
-    try:
-        ubench = nat.device_microbench(local_rank)
-    except Exception as ex:            # the headline must not depend on it
-        ubench_err = repr(ex)
-    # `frac` is priced against a FIXED ceiling (256 CUs x 4 SIMDs x 2.4 GHz, one wave64 VALU instruction per 2 cycles on a
-    # SIMD-32 = 1228.8 G wave-instr/s); the rate a sample-test-like instruction mix reaches in this run is reported beside it
-    # (`reference_mix_rate`): it depends on the mix and on the clocks and is no ceiling
-    valu_peak = VALU_PEAK_WAVE_INSTR
-    mix_rate = ubench['valu_mix_G_wave_instr_s'] if ubench else None
-    valu = None
-    sq, why_sq = load_profile('sq_latest.json', run_cfg)
-    if sq is not None and dom_kernel in sq.get('valu_wave_instr_per_launch', {}):
-        wi = float(sq['valu_wave_instr_per_launch'][dom_kernel])
-        dur = kernels[dom_kernel]["avg_ms"] * 1e-3
-        valu = {"kernel": dom_kernel, "wave_instr_per_launch": round(wi), "wave_instr_per_env_step": round(wi / n_local, 1),
-                "achieved": round(wi / dur / 1e9, 2), "peak": round(valu_peak / 1e9, 1), "unit": "G wave64-instr/s",
-                "frac": round(wi / dur / valu_peak, 4),
-                "peak_is": "fixed: 256 CUs x 4 SIMDs x 2.4 GHz / 2 cycles per wave64 instruction (SIMD-32)",
-                "reference_mix_rate": mix_rate, "frac_of_reference_mix": (round(wi / dur / (mix_rate * 1e9), 4) if mix_rate else None),
-                "reference_mix_is": ("measured in this run: rr_device_microbench kind 2, a sample-test-like mix (sub, mul, fma, cmp, cndmask) at "
-                                     "eight waves per SIMD on every SIMD" if ubench else "not measured (%s)" % ubench_err) +
-                                    "; the sweep over instruction kinds and 1..8 waves per SIMD is profiles/r04_valu_issue.txt: single-kind "
-                                    "streams saturate at 505-553 G, the mix at 806-975 G",
-                "source": "SQ_INSTS_VALU of profiles/sq_latest.json (%s, same configuration) / this run's HIP-event duration" % sq.get('source', '?')}
-    else:
-        valu = {"kernel": dom_kernel, "frac": None, "note": "null: " + (why_sq or "kernel not in the profile")}
-    ach = kernels[dom]["algorithmic_GBs"]
-    # what the counters say bounds the dominant kernel: VALU issue when its issue fraction exceeds its HBM fraction (it does,
-    # tenfold); the HBM figures stay the contract's accounting (achieved / peak / frac)
-    traffic_lo = prof.get('lower_bound', {}).get(dom) if prof is not None else None
-    dom_ms = kernels[dom]["avg_ms"]
-    traffic_frac = round(traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 6) if traffic else None
-    bound = "valu" if (valu.get("frac") or 0.0) > max(ach / HBM_PEAK_GBS, traffic_frac or 0.0) else "hbm"
-    roofline = {"bound": bound, "kernel": dom if dom != 'render_stage' else "+".join(kernels['render_stage']['members']),
-                "dominant_single_kernel": dom_kernel,
-                "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 6),
-                "hbm_achievable_GBs": ({"copy": ubench['hbm_copy_GBs'], "triad": ubench['hbm_triad_GBs'],
-                                        "frac_of_copy": round(ach / ubench['hbm_copy_GBs'], 6),
-                                        "note": "device copy / triad of 256 MiB arrays measured in this run (rr_device_microbench); "
-                                                "`peak` stays the 8 TB/s spec figure the contract prescribes"}
-                                       if ubench else {"error": ubench_err}),
-                "achieved_is": "ALGORITHMIC bytes per launch / HIP-event duration (full images, although a frame rewrites only "
-                               "the pixels that changed) -- the contract's accounting, not a measured HBM rate; `traffic` is the measured one",
-                "traffic": traffic, "traffic_lower_bound": traffic_lo, "achieved_traffic_frac": traffic_frac,
-                "traffic_note": "HBM bytes of the unit per step from PMC counters; `traffic` applies the guide's x2 FETCH_SIZE correction "
-                                "(calibrated for 16-B-per-lane coalesced reads only) to every read, `traffic_lower_bound` to none: "
-                                "the unit's reads are mostly scattered 8/16-byte records, so the truth lies between; "
-                                "achieved_traffic_frac = traffic / duration / 8 TB/s",
-                "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": round(algo[dom] * n_local),
-                "whole_step_algorithmic_GBs": round((algo['_state'] + (W * H * 7 if render else 0)) * n_local * args.steps / elapsed / 1e9, 2),
-                "bound_note": "`bound` comes from the counters: the dominant kernel's VALU issue fraction (roofline.valu) against its HBM "
-                              "fractions. achieved / peak / frac stay in the contract's HBM terms (algorithmic bytes): at 116 KB and "
-                              "~0.3 M instructions per env-step the path is instruction-issue / latency bound (DESIGN.md 5): k_raster's "
-                              "own VALU stream alone issues at 780-810 G wave-instr/s, with its 26.8 M LDS instructions per launch (2-6 "
-                              "CU-cycles each) at 350-700 G -- VALU issue and LDS instruction issue load the CU about equally "
-                              "(profiles/r04_raster_stream_issue.txt, r04_valu_lds_issue.txt), and 0.86 of the workgroup slots are busy "
-                              "(profiles/r04_raster_wg_timeline.txt)",
-                "valu": valu,
-                "kernels": kernels,
-                "timing_note": "per-kernel durations: HIP events on the library's stream, the launches of a step one after the "
-                               "other (no side-stream overlap), %d steps of the same workload right after the timed region; "
-                               "k_solve / k_render_setup / k_raster / k_shade = the main stream's launches (light envs), "
-                               "k_solve_heavy / render_heavy = the side streams' (heavy envs); k_prep / k_collide = the look-ahead "
-                               "of the next step, which an untimed step runs under the render; render_stage = the image of every "
-                               "env = k_raster + k_shade + render_heavy; rocprofv3 --stats of the overlapped run is under profiles/" % nprof}
+    roofline = None
+    if args.full:
+        # per-kernel device time (HIP events on the library's stream), separate pass right behind the timed region
+        base_t = args.presettle + args.warmup + args.steps
+        views = None              # the timing pass measures the kernels, not the gather
+        roofline = roofline_leg(args, env, nat, n_local, n_obj, render, lambda t: one_step(base_t + t), elapsed, local_rank)
     env.close()
 
     secondary = None
-    if rank == 0 and world == 1 and not args.no_secondary and render and n_local == ENVS_PER_GPU:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and render and n_local == ENVS_PER_GPU:
         secondary = secondary_workloads(torch, np, nat, BatchedREALRobotEnv, local_rank, min(args.steps, 100))
 
     if rank == 0:

@@ -5,9 +5,9 @@
 # configuration so that bench.py only attaches them to runs of that configuration.  Usage: tools/profile_round.sh [tag]
 TAG=${1:-r06}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/round; mkdir -p $O
-cd $R && python bench.py --steps 200 --warmup 20 > $O/${TAG}_bench.json 2> $O/bench.err; tail -c 600 $O/${TAG}_bench.json
+cd $R && python bench.py --full --steps 200 --warmup 20 > $O/${TAG}_bench.json 2> $O/bench.err; tail -c 600 $O/${TAG}_bench.json
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline --no-secondary"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-secondary"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- $B --steps 100 --warmup 10 > $O/stats_bench.log 2>&1
 cp $O/stats/run_kernel_stats.csv $O/${TAG}_kernel_stats.csv; head -12 $O/${TAG}_kernel_stats.csv
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -o run -- $B --steps 20 --warmup 5 > $O/pmc_fetch.log 2>&1
