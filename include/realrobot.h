@@ -78,7 +78,7 @@ typedef struct rr_config {
     int32_t num_envs;       /* N envs on this device */
     int32_t n_objects;      /* 1..3: cube, tomato, mustard      robot.py:49-50 */
     int32_t width, height;  /* eye camera; reference default 320x240 (robot.py:30-31).  width: a multiple of 4 in [4, 1024], height in
-                               [1, 1024], at most 255 raster tiles of 4096 pixels (1024 x 1020 fits, 1024 x 1024 does not): RR_EINVAL otherwise */
+                               [1, 1024], at most 255 raster tiles of 4096 pixels (1024 x 960 fits, 1024 x 961 does not): RR_EINVAL otherwise */
     int32_t device;         /* HIP device ordinal */
     int32_t solver_iters;   /* PGS iterations; <=0 -> 50        SURVEY A.1.2 */
     int32_t envs_per_block; /* physics kernels: envs (threads) per workgroup; <=0 -> default */
@@ -167,7 +167,8 @@ int rr_render(rr_env *env);
 /* Replaces the camera of this env handle (row-major 4x4 OpenGL view and projection matrices, host). The default is the
  * reference's eye camera; the facade uses a second env handle with EnvCamera's matrices for render('rgb_array')
  * (computeViewMatrixFromYawPitchRoll / computeProjectionMatrixFOV, env.py:480-499).  Both pointers NULL: back to the default
- * eye camera (eye (0.01, 0, 1.2) -> table position, up (0, 0, 1), fov 80, near 0.1, far 100; env.py:136-141, 253-255, 548-551). */
+ * eye camera (eye (0.01, 0, 1.2) -> table position, up (0, 0, 1), fov 80, near 0.1, far 100; env.py:136-141, 253-255, 548-551).
+ * Does not render: every env keeps its last frame until it is rendered again, and that frame is the first one of the new camera. */
 int rr_set_camera(rr_env *env, const float *view16, const float *proj16);
 
 /* Device pointer + size of an observation/state buffer (valid until rr_destroy). */
@@ -219,7 +220,7 @@ int rr_sync_observations(rr_env *env);
  * { env * H * W + row * W + col, r | g << 8 | b << 16, depth bits }, the pixel's NEW value -- at offsets_dev[item] + i, where
  * offsets_dev (u32 [N * tiles], device) is the exclusive prefix sum of RR_F_FRAG_COUNT made by the caller; records beyond
  * `capacity` are dropped.  On the library's stream.  After a frame that rewrote whole images (the first render of a handle,
- * rr_set_camera) the lists do not describe the change: ship the slabs then.
+ * the first render of an env after rr_set_camera) the lists do not describe the change: ship the slabs then.
  * rr_apply_image_delta is the receiving side, with no env handle: `world` blocks of `capacity` records of which the first
  * totals_dev[r] are valid, applied to persistent images of world * pixels_per_rank pixels (rank r's records address its block);
  * enqueued on `stream` (a hipStream_t or NULL) of the current device. */

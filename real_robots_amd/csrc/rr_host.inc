@@ -67,6 +67,8 @@ struct rr_env {
     bool prep_scalar;              // RR_PREP_SCALAR=1: the thread-per-env preparation kernels instead of k_prep16 (A/B, tests)
     bool split_heavy;              // heavy solver groups + their render on the side stream (RR_NO_SPLIT=1 turns it off: A/B, tests)
     bool images_valid;       // every env's image holds its previous frame (static layer + the pixels of its fragment list)
+    unsigned char *stale_dev;  // [N] device: the env's image predates the current static layer (rr_set_camera after its last frame)
+    bool stale_any;          // some env may be stale: every render checks (cleared by a render of all envs)
     hipEvent_t ev[2 * RR_NUM_KERNELS];
     hipStream_t aux;         // side stream: the HBM-bound static-layer copy runs beside the VALU-bound physics / visibility kernels
     hipEvent_t ev_fork, ev_join, ev_dyn, ev_join2, ev_vsolved, ev_hsolved, ev_rast;
@@ -291,7 +293,14 @@ static int build_static_layer(rr_env *e) {
     if (hipMemsetAsync(e->D.frag_count, 0, (size_t)e->P.N * e->RM.ntiles * sizeof(unsigned), e->stream) != hipSuccess ||
         hipStreamSynchronize(e->stream) != hipSuccess) return fail(RR_EDEVICE, "static layer pass failed");
     e->D.static_vis = e->D.static_vis_out;
-    e->images_valid = false;         // the next render starts from a full copy of the new static layer
+    // Before the first frame of a handle every image starts from a full copy of the static layer.  Later (rr_set_camera) an
+    // env's image is its last frame, which a step that does not render it must leave alone: each env takes the full copy of the
+    // new layer at its own next render instead.
+    if (e->images_valid) {
+        if (hipMemsetAsync(e->stale_dev, 1, (size_t)e->P.N, e->stream) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess)
+            return fail(RR_EDEVICE, "static layer pass failed");
+        e->stale_any = true;
+    }
     return RR_OK;
 }
 
@@ -312,7 +321,7 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
         if (getenv("RR_TILE_W")) { const int t_ = atoi(getenv("RR_TILE_W")); if (t_ >= 4 && t_ <= cfg->width && t_ <= TILE_PIX) tw_ = t_; }
         int th_ = TILE_PIX / tw_; if (th_ > cfg->height) th_ = cfg->height;
         const int nt_ = ((cfg->width + tw_ - 1) / tw_) * ((cfg->height + th_ - 1) / th_);
-        if (nt_ > 255) return fail(RR_EINVAL, "rr_create: image too large: more than 255 raster tiles of 4096 pixels (e.g. 1024 x 1020 fits, 1024 x 1024 does not)");
+        if (nt_ > 255) return fail(RR_EINVAL, "rr_create: image too large: more than 255 raster tiles of 4096 pixels (e.g. 1024 x 960 fits, 1024 x 961 does not)");
     }
     Blob b;
     if (!b.init(model_blob, blob_bytes)) return fail(RR_EMODEL, "rr_create: bad model blob header");
@@ -567,6 +576,7 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
     ALLOC(D.objpose, (size_t)N * P.nobj * 7);
     ALLOC(D.inst_xf, (size_t)N * MAXINST * 32);
     ALLOC(D.render_flags, (size_t)N);
+    ALLOC(e->stale_dev, (size_t)N);
     const size_t npx = (size_t)N * RM.W * RM.H;
     ALLOC(D.rgb, npx * 3);
     ALLOC(D.depth, npx);
@@ -856,18 +866,30 @@ static bool g_debug_sync = getenv("RR_DEBUG_SYNC") != nullptr;
         }                                                                   \
     } while (0)
 
-// Image set-up that precedes the first frame after create / a new static layer: full copy of the static layer (all envs).
+// Image set-up that precedes a frame: the first frame of a handle starts every image (all envs) from a full copy of the static
+// layer; after a new static layer (rr_set_camera) each env rendered in this frame whose image predates it takes the full copy.
 static int ensure_images(rr_env *e, DevPtrs &D) {
     const int N = e->P.N;
     const ImageOut io = env_images(e);
+    const int copy_blocks = std::min(16, (e->RM.W * e->RM.H / 4 + COPY_THREADS - 1) / COPY_THREADS);
     if (!e->images_valid || e->full_copy) {
-        const int copy_blocks = std::min(16, (e->RM.W * e->RM.H / 4 + COPY_THREADS - 1) / COPY_THREADS);
         DevPtrs Dall = D;
         if (!e->images_valid) Dall.render_flags = nullptr;      // first frame: every env, flagged or not -- all images become valid
-        TIMED(5, hipLaunchKernelGGL(k_static_copy, dim3(copy_blocks, std::min(N, 65535)), dim3(COPY_THREADS), 0, e->stream, e->RM_dev, Dall, io, 1, N));
+        TIMED(5, hipLaunchKernelGGL(k_static_copy, dim3(copy_blocks, std::min(N, 65535)), dim3(COPY_THREADS), 0, e->stream, e->RM_dev, Dall, io, 1, N,
+                                    (const unsigned char *)nullptr));
         if (!e->images_valid) HIPCHK(hipMemsetAsync(e->D.frag_count, 0, (size_t)N * e->RM.ntiles * sizeof(unsigned), e->stream));
+        if (!e->images_valid || !D.render_flags) {       // (every image now holds the current static layer)
+            if (e->stale_any) HIPCHK(hipMemsetAsync(e->stale_dev, 0, (size_t)N, e->stream));
+            e->stale_any = false;
+        }
         e->images_valid = true;
         return 0;           // the lists are empty: nothing to restore
+    }
+    if (e->stale_any) {
+        TIMED(5, hipLaunchKernelGGL(k_static_copy, dim3(copy_blocks, std::min(N, 65535)), dim3(COPY_THREADS), 0, e->stream, e->RM_dev, D, io, 1, N,
+                                    (const unsigned char *)e->stale_dev));
+        hipLaunchKernelGGL(k_stale_clear, dim3((N + 255) / 256), dim3(256), 0, e->stream, e->RM_dev, D, N, e->stale_dev);
+        if (!D.render_flags) e->stale_any = false;      // a frame of every env: none is stale any more
     }
     return 1;
 }

@@ -931,11 +931,14 @@ __global__ void __launch_bounds__(RASTER_THREADS) __attribute__((amdgpu_waves_pe
 
 // Copies the static layer (or the background when there is none) into the images of every rendered env: 4 pixels per
 // thread (W % 4 == 0 enforced at create).  Pure streaming: reads hit L2, writes are the obs bytes of SURVEY 8(d).
+// stale != nullptr: only the rendered envs whose byte is set (images that predate the current static layer, rr_set_camera).
 #define COPY_THREADS 256
-__global__ void __launch_bounds__(COPY_THREADS) k_static_copy(const RenderModel *RMp, DevPtrs D, ImageOut out, int use_flags, int N) {
+__global__ void __launch_bounds__(COPY_THREADS) k_static_copy(const RenderModel *RMp, DevPtrs D, ImageOut out, int use_flags, int N,
+                                                              const unsigned char *stale) {
     const int ngroups = (RMp->W * RMp->H) >> 2;
     for (int env = blockIdx.y; env < N; env += gridDim.y) {
     if (use_flags && D.render_flags && !D.render_flags[env]) continue;
+    if (stale && !stale[env]) continue;
     const size_t base = (size_t)env * out.env_stride;
     for (int g = blockIdx.x * COPY_THREADS + threadIdx.x; g < ngroups; g += gridDim.x * COPY_THREADS) {
         const unsigned *srgb = (const unsigned *)(D.static_rgb) + (size_t)3 * g;
@@ -947,6 +950,16 @@ __global__ void __launch_bounds__(COPY_THREADS) k_static_copy(const RenderModel 
         if (out.mask) *(int4 *)(out.mask + base + (size_t)4 * g) = *(const int4 *)(D.static_mask + (size_t)4 * g);
     }
     }
+}
+
+// Behind k_static_copy(stale): the rendered stale envs hold the full static layer now -- empty fragment lists (nothing to
+// restore), no longer stale.  One thread per env.
+__global__ void k_stale_clear(const RenderModel *RMp, DevPtrs D, int N, unsigned char *stale) {
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env >= N || !stale[env] || (D.render_flags && !D.render_flags[env])) return;
+    const int nt = RMp->ntiles;
+    for (int t = 0; t < nt; t++) D.frag_count[(size_t)env * nt + t] = 0u;
+    stale[env] = 0;
 }
 
 // Background fill of the shared static images (before the static layer is shaded).

@@ -85,8 +85,13 @@ def test_robot_object_contact_parity_and_touch_sensors():
     env.close()
 
 
-@pytest.mark.parametrize("W,H", [(128, 128), (320, 240), (256, 256), (64, 48)])
+@pytest.mark.parametrize("W,H", [(128, 128), (320, 240), (256, 256), (64, 48), (4, 1), (4, 1024), (132, 97), (128, 33), (1024, 960)])
 def test_raster_parity(W, H):
+    """Mask identical, RGB within 1 grey level, depth within 1e-6 at every pixel.  At 1024 x 960 (box coordinate 1023) the frame
+    puts samples of the table top within 2e-5 texel of a texel boundary, where the device's shading (not contraction-free) and
+    the oracle's may fetch neighbouring texels: there, and only there, at most 4 pixels per frame may differ by more, and each
+    of them must lie within EPS_TEXEL of a texel boundary by the float64 ray caster (tests/numpy_camera.py; measured: 2 per
+    frame, 7e-6 and 2e-5 texel)."""
     N = 4
     env = BatchedREALRobotEnv(N, objects=3, width=W, height=H)
     o = Oracle(3, W, H)
@@ -104,7 +109,14 @@ def test_raster_parity(W, H):
         # coverage math is evaluated without FMA contraction on both sides -> the images agree exactly
         same = (m == msk[i])
         assert same.all()
-        assert np.abs(r.astype(int) - rgb[i].astype(int)).max() <= 1
+        bad = np.argwhere(np.abs(r.astype(int) - rgb[i].astype(int)).max(-1) > 1)
+        if W * H >= 1024 * 960 and 0 < len(bad) <= 4:
+            from tests import numpy_camera as nc
+            rows = sorted(set(bad[:, 0].tolist()))
+            h = nc.render(st[i].astype(np.float64), 3, W, H, rows=rows)
+            assert all(h['texel'][rows.index(y), x] < nc.EPS_TEXEL for y, x in bad), (i, bad)
+            bad = bad[:0]
+        assert len(bad) == 0, (i, bad[:8])
         assert np.abs(d - dep[i]).max() < 1e-6
         assert set(np.unique(msk[i]).tolist()) <= {-1, 0, 1, 2, 3, 4}
     env.close()

@@ -79,6 +79,43 @@ def test_create_rejects_bad_arguments_and_fails_loudly_without_gpu():
             env.reset()
 
 
+def test_create_image_size_limit_matches_the_tile_rule(monkeypatch):
+    """rr_create checks the image size before it looks for a device: a size the tile rule accepts gets past the checks
+    (RR_EDEVICE without a GPU, a handle with one), a rejected one returns RR_EINVAL.  Tiles of 4096 pixels, 64 wide above a
+    width of 128, at most 255 of them: 1024 x 960 is 16 x 15 = 240 tiles, 1024 x 961 and 1024 x 1020 are 16 x 16 = 256;
+    1020 x 64 is 16 tiles, and 255 strips 4 wide under RR_TILE_W=4 -- exactly the last index before the sentinel.  The
+    example sizes of the header's rr_config comment are the ones this rule accepts and rejects."""
+    L = nat.load_library()
+    blob = nat.model_blob()
+
+    def create(W, H):
+        cfg = nat.Config()
+        cfg.abi_version, cfg.num_envs, cfg.n_objects, cfg.width, cfg.height = nat.RR_ABI_VERSION, 1, 1, W, H
+        h = C.c_void_p()
+        rc = L.rr_create(C.byref(cfg), blob, len(blob), None, C.byref(h))
+        if rc == 0:
+            L.rr_destroy(h)
+        assert rc in (0, -1, -2), rc
+        return rc != -1, L.rr_last_error()
+
+    monkeypatch.delenv('RR_TILE_W', raising=False)
+    assert create(1024, 960)[0]
+    ok, err = create(1024, 961)
+    assert not ok and b'255 raster tiles' in err
+    assert not create(1024, 1020)[0]
+    assert create(1020, 64)[0]
+    monkeypatch.setenv('RR_TILE_W', '4')
+    assert create(1020, 64)[0]                    # 255 tiles
+    assert not create(1024, 64)[0]                # 256 tiles
+    monkeypatch.delenv('RR_TILE_W')
+    hdr = open(os.path.join(os.path.dirname(__file__), '..', 'include', 'realrobot.h')).read()
+    fits, fails = re.search(r'\((\d+) x (\d+) fits, (\d+) x (\d+) does not\)', hdr).groups()[:2], \
+        re.search(r'\((\d+) x (\d+) fits, (\d+) x (\d+) does not\)', hdr).groups()[2:]
+    assert create(*map(int, fits))[0] and not create(*map(int, fails))[0]
+    src = open(os.path.join(os.path.dirname(__file__), '..', 'real_robots_amd', 'csrc', 'rr_host.inc')).read()
+    assert re.search(r'e\.g\. (\d+) x (\d+) fits, (\d+) x (\d+) does not', src).groups() == fits + fails
+
+
 def test_solver_dict_reaches_the_config_struct():
     """ABI 6: the constants the reference leaves to pybullet's defaults travel in rr_config (same 80 bytes as ABI 5's reserved
     words); 0 = default, an explicit zero is passed as the header's "literal zero" (negative)."""

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle.oracle import Oracle, LINK_NAMES
+from tests import numpy_camera as nc
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = json.load(open(os.path.join(HERE, 'golden', 'fk_golden.json')))
@@ -260,20 +261,15 @@ def test_table_top_coverage_and_depth_match_analytic_ray_casting():
     """Known answer for the camera + rasteriser conventions (SURVEY 8c "raster of a single axis-aligned box"): the top
     face of the table (an axis-aligned rectangle at z = 0.279403) is ray-cast analytically in float64 with the OpenGL
     look-at / perspective matrices of env.py:136-141,253-255,518,548-551, the sample-point convention ndc_x = 2 col / W - 1,
-    ndc_y = 2 (H - 1 - row) / H - 1, and GL depth 0.5 z_ndc + 0.5.  Every pixel whose ray meets the rectangle's plane
+    ndc_y = 2 (H - 1 - row) / H - 1, and GL depth 0.5 z_ndc + 0.5 (the matrices are tests/numpy_camera.py's, built from the
+    camera frame and glFrustum).  Every pixel whose ray meets the rectangle's plane
     inside the strip -0.15 < x < 0.05 (clear of robot, shelf and the parked cube) must be table (mask 1) exactly when
     the hit lies inside the rectangle's y range, with the analytic depth to 1e-6."""
     W = H = 128
     o = Oracle(1, W, H)
     o.set_object_pose(0, [0.2, 0.0, 0.45, 0, 0, 0, 1])          # cube parked on the shelf side, outside the strip
     rgb, depth, mask = o.render()
-    eye, tgt, up = np.array([0.01, 0.0, 1.2]), np.array([0.0, 0.0, 0.08]), np.array([0.0, 0.0, 1.0])
-    f = (tgt - eye) / np.linalg.norm(tgt - eye)
-    s = np.cross(f, up); s /= np.linalg.norm(s)
-    u = np.cross(s, f)
-    V = np.eye(4); V[0, :3], V[1, :3], V[2, :3] = s, u, -f; V[:3, 3] = -V[:3, :3] @ eye
-    n, fa, t = 0.1, 100.0, 1.0 / np.tan(np.radians(80.0) / 2)
-    Pm = np.array([[t / (W / H), 0, 0, 0], [0, t, 0, 0], [0, 0, (n + fa) / (n - fa), 2 * n * fa / (n - fa)], [0, 0, -1, 0]])
+    V, Pm = nc.eye_camera(W, H)                                  # the float64 ray caster's eye camera (tests/numpy_camera.py)
     inv = np.linalg.inv(Pm @ V)
     z_top, ylo, yhi = 0.279403, -0.505576, 0.495054
     checked = 0
