@@ -170,6 +170,15 @@ int rr_render(rr_env *env);
  * eye camera (eye (0.01, 0, 1.2) -> table position, up (0, 0, 1), fov 80, near 0.1, far 100; env.py:136-141, 253-255, 548-551).
  * Does not render: every env keeps its last frame until it is rendered again, and that frame is the first one of the new camera. */
 int rr_set_camera(rr_env *env, const float *view16, const float *proj16);
+/* Per-env cameras (additive in ABI 7): the envs whose mask byte is non-zero (NULL: all) get their own row-major 4x4 OpenGL view and
+ * projection (views16 / projs16: f32 [N][16] host, rows of unmasked envs not read) -- the conventions and limits of rr_set_camera:
+ * any view, a perspective projection whose near plane is 0.1 (geometry nearer than w = 0.1 is clipped).  A null or non-finite
+ * matrix of a masked env returns RR_EINVAL and changes no env.  The envs outside the mask are not touched (camera, image, fragment
+ * lists).  Does not render: a masked env keeps its last frame until its own next render, the first frame of its new camera.
+ * The first call allocates a static layer per env (19 bytes per pixel per env: 1.27 GB at 4096 envs of 128 x 128); rr_set_camera
+ * returns the handle to one camera for all envs.  Cameras are settings of the handle, not env state: rr_reset, rr_set_state,
+ * rr_set_object_pose(s) and rr_checkpoint_restore keep them, checkpoints do not carry them.  Synchronous. */
+int rr_set_env_cameras(rr_env *env, const float *views16, const float *projs16, const uint8_t *env_mask_host);
 
 /* Device pointer + size of an observation/state buffer (valid until rr_destroy). */
 int rr_get_buffer(rr_env *env, int32_t field, void **dev_ptr, size_t *bytes);

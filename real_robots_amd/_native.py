@@ -31,7 +31,8 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_set_timing', 'rr_get_timing', 'rr_last_error', 'rr_abi_version', 'rr_ik', 'rr_plan_macro', 'rr_get_plan',
            'rr_step_plan', 'rr_set_camera', 'rr_set_object_poses', 'rr_step_plan_masked', 'rr_checkpoint_bytes',
            'rr_checkpoint_save', 'rr_checkpoint_restore', 'rr_evaluate_goals', 'rr_device_microbench', 'rr_map_observations', 'rr_map_images', 'rr_sync_observations', 'rr_select_image_mirror',
-           'rr_pack_image_delta', 'rr_apply_image_delta', 'rr_set_object_dynamics', 'rr_get_object_dynamics')
+           'rr_pack_image_delta', 'rr_apply_image_delta', 'rr_set_object_dynamics', 'rr_get_object_dynamics',
+           'rr_set_env_cameras')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 
@@ -127,6 +128,7 @@ def load_library():
     L.rr_get_plan.argtypes = [vp, i32, vp]
     L.rr_step_plan.argtypes = [vp, i32, vp]
     L.rr_set_camera.argtypes = [vp, vp, vp]
+    L.rr_set_env_cameras.argtypes = [vp, vp, vp, vp]
     L.rr_set_object_poses.argtypes = [vp, vp, vp]
     L.rr_step_plan_masked.argtypes = [vp, vp, i32, vp]
     L.rr_evaluate_goals.argtypes = [vp, vp, vp, vp]

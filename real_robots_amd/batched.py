@@ -370,6 +370,29 @@ class BatchedREALRobotEnv:
         p = np.ascontiguousarray(proj, dtype=np.float32).reshape(16)
         nat.check(self.L.rr_set_camera(self.h, v.ctypes.data, p.ctypes.data))
 
+    def set_env_cameras(self, views, projs, env_mask=None):
+        """Per-env cameras (rr_set_env_cameras): row-major 4x4 OpenGL view / projection matrices, [N, 4, 4] or [4, 4] for every
+        env, for the envs of env_mask (uint8 / bool [N], None: all); the other envs keep theirs.  Same conventions and limits as
+        set_camera.  Does not render: a masked env keeps its last frame until its next render.  A non-finite matrix of a masked
+        env raises and changes nothing; set_camera puts every env back on one camera.  The cameras outlive reset(),
+        `state = ...`, teleports and restore().  A sharded batch gathers full image slabs after this call, as after set_camera."""
+        N = self.N
+
+        def arg(m, name):
+            a = np.asarray(m, dtype=np.float32)
+            if a.shape == (4, 4):
+                a = np.broadcast_to(a, (N, 4, 4))
+            if a.shape != (N, 4, 4):
+                raise ValueError("%s must have shape (%d, 4, 4) or (4, 4), not %s" % (name, N, a.shape))
+            return np.ascontiguousarray(a)
+        v, p = arg(views, 'views'), arg(projs, 'projs')
+        m = None
+        if env_mask is not None:
+            m = np.ascontiguousarray(env_mask).astype(np.uint8)
+            if m.shape != (N,):
+                raise ValueError("env_mask must have shape (%d,)" % N)
+        nat.check(self.L.rr_set_env_cameras(self.h, v.ctypes.data, p.ctypes.data, m.ctypes.data if m is not None else None))
+
     def set_timing(self, on):
         nat.check(self.L.rr_set_timing(self.h, int(on)))
 

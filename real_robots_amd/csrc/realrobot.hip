@@ -109,6 +109,11 @@ struct RenderModel {
     float tile_plane[256][8];  // per raster tile: NDC y of its first / last sample row and |xyz| of those two planes {ndc_a, nrm_a, ndc_b, nrm_b}, then the same for its first / last sample column
                              // (host side, frustum_plane_norms: two square roots and twenty multiply-adds per WAVE of the visibility pass otherwise)
 };
+// An env's own camera record (DevPtrs::env_cam): the three camera fields of RenderModel for that env, tile_plane cut to its ntiles rows.
+#define CAM_VP 0
+#define CAM_PN 16
+#define CAM_TP 21
+__host__ __device__ __forceinline__ int cam_floats(int ntiles) { return CAM_TP + 8 * ntiles; }
 
 // scratch slots (floats per env), one record per env [N][S_TOTAL]
 enum {
@@ -180,7 +185,9 @@ struct DevPtrs {
     const ShapeData *shapes;
     const unsigned long long *static_vis;   // [H*W] visibility keys of the never-moving instances (or nullptr)
     unsigned long long *static_vis_out;
-    unsigned char *static_rgb; float *static_depth; int *static_mask;   // [H*W] shaded static layer (shared by all envs)
+    unsigned char *static_rgb; float *static_depth; int *static_mask;   // [H*W] shaded static layer (shared by all envs), or [N][H*W] with per-env cameras
+    size_t static_stride;   // pixels between the static layers of two envs: 0 (one layer for all envs) or H*W (per-env cameras)
+    const float *env_cam;   // [N][cam_floats(ntiles)] per-env cameras {VP, plane_norm, tile_plane} (rr_set_env_cameras); nullptr: RenderModel's for all envs
     uint2 *frag_list;       // [N*ntiles][TILE_PIX] pixels won by moving triangles: {depth bits, pixel-in-tile << 18 | triangle}
     unsigned *frag_count;   // [N*ntiles]
     // dispatch order of k_raster's workgroups (dispatch_order_class): the (env, tile) items by falling cost of the previous frame

@@ -118,6 +118,13 @@ struct rr_env {
     std::vector<float> shape_mat;  // [ns][4] the blob's {friction, restitution, rolling, spinning} of every collision shape
     std::vector<int> shape_obj;    // [ns] the free object a shape belongs to, -1 for the table / shelf / robot
     std::vector<int> pair_shapes;  // [npairs][2] shapes a, b of every collision pair
+    // per-env cameras (rr_set_env_cameras): allocated by its first call; D.env_cam / D.static_* point at them while the handle is in
+    // per-env mode, at the shared layer below otherwise (rr_set_camera)
+    std::vector<float> cam_host;   // [N][cam_floats(ntiles)] host copy of every env's record
+    float *cam_dev;                // [N][cam_floats(ntiles)]
+    int *cam_sel;                  // [N] class array of the rebuild launches: 0 the envs whose layer is rebuilt (sel 1 selects them), 1 the others
+    unsigned long long *env_static_vis; unsigned char *env_static_rgb; float *env_static_depth; int *env_static_mask;   // [N][H*W]
+    unsigned long long *shared_static_vis; unsigned char *shared_static_rgb; float *shared_static_depth; int *shared_static_mask;   // [H*W]
 };
 
 // The combining rule of the contact materials of two shapes (btManifoldResult::calculateCombinedFriction / Restitution /
@@ -170,6 +177,16 @@ static int dev_alloc(rr_env *e, T **p, size_t count, bool zero = true) {
     return RR_OK;
 }
 
+// VP = proj * view (row-major 4x4): the one product of a camera's matrices (rr_set_camera, rr_set_env_cameras, the default eye)
+static void camera_vp(const float *view16, const float *proj16, float *VP) {
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            float a = 0;
+            for (int k = 0; k < 4; k++) a += proj16[4 * i + k] * view16[4 * k + j];
+            VP[4 * i + j] = a;
+        }
+}
+
 static void look_at_persp(float *VP, const float *table_pos, int W, int H) {
     float eye[3] = {0.01f, 0.0f, 1.2f};                       // env.py:136
     float tgt[3] = {table_pos[0], table_pos[1], table_pos[2]};  // env.py:253-255 (table position)
@@ -190,23 +207,19 @@ static void look_at_persp(float *VP, const float *table_pos, int W, int H) {
     float yscale = 1.0f / tanf(fov * 3.14159265358979323846f / 360.0f);
     float xscale = yscale / aspect;
     float Pm[16] = {xscale, 0, 0, 0, 0, yscale, 0, 0, 0, 0, (nearv + farv) / (nearv - farv), 2 * nearv * farv / (nearv - farv), 0, 0, -1, 0};
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++) {
-            float a = 0;
-            for (int k = 0; k < 4; k++) a += Pm[4 * i + k] * V[4 * k + j];
-            VP[4 * i + j] = a;
-        }
+    camera_vp(V, Pm, VP);
 }
 
-static void frustum_plane_norms(RenderModel &RM) {
-    const float *V = RM.VP;
+// The frustum planes' norms and the tiles' planes (RenderModel::plane_norm, tile_plane) of the camera VP, for RM's raster tiles:
+// the handle's camera (rr_set_camera) and every env's record (rr_set_env_cameras) come from this one function.
+static void frustum_plane_norms(const RenderModel &RM, const float *V, float *plane_norm, float (*tile_plane)[8]) {
     const float sg[4] = {1, -1, 1, -1};
     const int row[4] = {0, 0, 1, 1};
     for (int k = 0; k < 4; k++) {
         float a = V[12] + sg[k] * V[4 * row[k]], b = V[13] + sg[k] * V[4 * row[k] + 1], c = V[14] + sg[k] * V[4 * row[k] + 2];
-        RM.plane_norm[k] = sqrtf(a * a + b * b + c * c);
+        plane_norm[k] = sqrtf(a * a + b * b + c * c);
     }
-    RM.plane_norm[4] = sqrtf(V[12] * V[12] + V[13] * V[13] + V[14] * V[14]);
+    plane_norm[4] = sqrtf(V[12] * V[12] + V[13] * V[13] + V[14] * V[14]);
     // the two tile-boundary planes of every raster tile (conservative cull of a cluster against the tile's sample rows)
     for (int tile = 0; tile < RM.ntiles && tile < 256; tile++) {
         const int tyi = tile / RM.ntx, tx0 = (tile - tyi * RM.ntx) * RM.tile_w, cols = std::min(RM.tile_w, RM.W - tx0);
@@ -215,11 +228,11 @@ static void frustum_plane_norms(RenderModel &RM) {
         for (int k = 0; k < 2; k++) {
             const float ndc = 2.0f * (k ? ty1 : ty0) / (float)RM.H - 1.0f;
             const float a = V[4] - ndc * V[12], b = V[5] - ndc * V[13], c = V[6] - ndc * V[14];
-            RM.tile_plane[tile][2 * k] = ndc; RM.tile_plane[tile][2 * k + 1] = sqrtf(a * a + b * b + c * c);
+            tile_plane[tile][2 * k] = ndc; tile_plane[tile][2 * k + 1] = sqrtf(a * a + b * b + c * c);
             // (sample column px sits at NDC x = 2 px / W - 1: the viewport maps (x + 1) W / 2)
             const float ndx = 2.0f * (float)(k ? tx0 + cols - 1 : tx0) / (float)RM.W - 1.0f;
             const float ax = V[0] - ndx * V[12], bx = V[1] - ndx * V[13], cx = V[2] - ndx * V[14];
-            RM.tile_plane[tile][4 + 2 * k] = ndx; RM.tile_plane[tile][5 + 2 * k] = sqrtf(ax * ax + bx * bx + cx * cx);
+            tile_plane[tile][4 + 2 * k] = ndx; tile_plane[tile][5 + 2 * k] = sqrtf(ax * ax + bx * bx + cx * cx);
         }
     }
 }
@@ -282,7 +295,7 @@ static ImageOut env_images(const rr_env *e) {
 // shelf, robot base; the eye camera is fixed, env.py:136-141, 253-255) are rasterised and shaded once; their visibility keys
 // seed every env's frame.
 static int build_static_layer(rr_env *e) {
-    hipLaunchKernelGGL(k_background, dim3(64), dim3(256), 0, e->stream, e->RM_dev, e->D);
+    hipLaunchKernelGGL(k_background, dim3(64), dim3(256), 0, e->stream, e->RM_dev, e->D, 1, (const unsigned char *)nullptr);
     ImageOut so;
     so.rgb = e->D.static_rgb; so.depth = e->D.static_depth; so.mask = e->D.static_mask; so.env_stride = 0;
     e->D.static_vis = nullptr;
@@ -526,7 +539,7 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
     }
     memcpy(e->table_pos, table_pos, sizeof e->table_pos);
     look_at_persp(RM.VP, table_pos, RM.W, RM.H);
-    frustum_plane_norms(RM);
+    frustum_plane_norms(RM, RM.VP, RM.plane_norm, RM.tile_plane);
     e->n_inst_used = ni - (NOBJ - P.nobj);
 
     // device allocations
@@ -695,6 +708,8 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
         }
         if ((r = dev_alloc(e, &e->D.static_vis_out, spx)) != RR_OK) { rr_destroy(e); *out = nullptr; return r; }
         e->field_ptr[RR_F_FRAG_COUNT] = e->D.frag_count;
+        e->shared_static_vis = e->D.static_vis_out; e->shared_static_rgb = e->D.static_rgb;
+        e->shared_static_depth = e->D.static_depth; e->shared_static_mask = e->D.static_mask;
         if ((r = build_static_layer(e)) != RR_OK) { rr_destroy(e); *out = nullptr; return r; }
     }
     // the 256-thread form of k_solve (heavy solver groups, four per workgroup) and the light envs' solve with an object wave (five
@@ -1715,18 +1730,93 @@ int rr_set_camera(rr_env *e, const float *view16, const float *proj16) {
     if (!e || (!view16) != (!proj16)) return fail(RR_EINVAL, "rr_set_camera: null argument (both matrices, or neither for the default eye)");
     HIPCHK(hipSetDevice(e->cfg.device));
     HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->D.env_cam) {          // per-env cameras end: every env shares the handle's camera and static layer again
+        e->D.env_cam = nullptr; e->D.static_stride = 0;
+        e->D.static_vis = e->D.static_vis_out = e->shared_static_vis; e->D.static_rgb = e->shared_static_rgb;
+        e->D.static_depth = e->shared_static_depth; e->D.static_mask = e->shared_static_mask;
+    }
     if (!view16) look_at_persp(e->RM.VP, e->table_pos, e->RM.W, e->RM.H);       // back to the reference's eye camera (env.py:136-141, 253-255)
-    else
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++) {
-            float a = 0;
-            for (int k = 0; k < 4; k++) a += proj16[4 * i + k] * view16[4 * k + j];
-            e->RM.VP[4 * i + j] = a;
-        }
-    frustum_plane_norms(e->RM);
+    else camera_vp(view16, proj16, e->RM.VP);
+    frustum_plane_norms(e->RM, e->RM.VP, e->RM.plane_norm, e->RM.tile_plane);
     HIPCHK(hipMemcpy(e->RM_dev, &e->RM, sizeof e->RM, hipMemcpyHostToDevice));
     int rc = build_static_layer(e);
     if (rc != RR_OK) return rc;
+    return RR_OK;
+}
+
+// Per-env cameras.  The first call allocates a camera record and a static layer per env; entering per-env mode starts every env
+// from the handle's camera and a copy of its static layer.  The masked envs then get their record (camera_vp and
+// frustum_plane_norms, as rr_set_camera) and their layer is rebuilt by the launches of build_static_layer over a grid of all
+// envs, of which only the masked ones stay (class array cam_sel, sel 1): background, instance set-up, pass-1 visibility with the
+// env's own fragment list as scratch, shading into its layer.  Their lists are emptied and, once images exist, they become stale
+// (a full copy of their own layer at their next render).  The other envs are not touched.
+int rr_set_env_cameras(rr_env *e, const float *views16, const float *projs16, const uint8_t *env_mask_host) {
+    if (!e || !views16 || !projs16) return fail(RR_EINVAL, "rr_set_env_cameras: null argument");
+    const int N = e->P.N;
+    for (int i = 0; i < N; i++) {
+        if (env_mask_host && !env_mask_host[i]) continue;
+        for (int k = 0; k < 16; k++)
+            if (!std::isfinite(views16[16 * (size_t)i + k]) || !std::isfinite(projs16[16 * (size_t)i + k]))
+                return fail(RR_EINVAL, "rr_set_env_cameras: non-finite matrix of env " + std::to_string(i) + " (no env changed)");
+    }
+    HIPCHK(hipSetDevice(e->cfg.device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const RenderModel &RM = e->RM;
+    const int CF = cam_floats(RM.ntiles);
+    const size_t px = (size_t)RM.W * RM.H;
+    int rc;
+    if (!e->cam_dev) {
+        if ((rc = dev_alloc(e, &e->cam_dev, (size_t)N * CF)) != RR_OK || (rc = dev_alloc(e, &e->cam_sel, (size_t)N)) != RR_OK ||
+            (rc = dev_alloc(e, &e->env_static_vis, (size_t)N * px, false)) != RR_OK || (rc = dev_alloc(e, &e->env_static_rgb, (size_t)N * px * 3, false)) != RR_OK ||
+            (rc = dev_alloc(e, &e->env_static_depth, (size_t)N * px, false)) != RR_OK || (rc = dev_alloc(e, &e->env_static_mask, (size_t)N * px, false)) != RR_OK) {
+            e->cam_dev = nullptr;          // (what was allocated stays on the handle's list until rr_destroy; a later call allocates again)
+            return rc;
+        }
+        e->cam_host.assign((size_t)N * CF, 0.0f);
+    }
+    const dim3 copy_grid(std::min(16, (int)((px / 4 + COPY_THREADS - 1) / COPY_THREADS)), std::min(N, 65535));
+    if (!e->D.env_cam) {          // entering per-env mode: every env has the handle's camera and static layer
+        for (int i = 0; i < N; i++) {
+            float *rec = e->cam_host.data() + (size_t)i * CF;
+            memcpy(rec + CAM_VP, RM.VP, sizeof RM.VP);
+            memcpy(rec + CAM_PN, RM.plane_norm, sizeof RM.plane_norm);
+            memcpy(rec + CAM_TP, RM.tile_plane, sizeof(float) * 8 * RM.ntiles);
+        }
+        ImageOut layers;
+        layers.rgb = e->env_static_rgb; layers.depth = e->env_static_depth; layers.mask = e->env_static_mask; layers.env_stride = px;
+        hipLaunchKernelGGL(k_static_copy, copy_grid, dim3(COPY_THREADS), 0, e->stream, e->RM_dev, e->D, layers, 0, N, (const unsigned char *)nullptr);
+        hipLaunchKernelGGL(k_static_vis_spread, copy_grid, dim3(COPY_THREADS), 0, e->stream, (const unsigned long long *)e->shared_static_vis, e->env_static_vis, px, N);
+        HIPCHK(hipGetLastError());
+        e->D.env_cam = e->cam_dev; e->D.static_stride = px;
+        e->D.static_vis = e->D.static_vis_out = e->env_static_vis; e->D.static_rgb = e->env_static_rgb;
+        e->D.static_depth = e->env_static_depth; e->D.static_mask = e->env_static_mask;
+    }
+    std::vector<int> sel(N, 1);
+    std::vector<uint8_t> mask(N, 0);
+    for (int i = 0; i < N; i++) {
+        if (env_mask_host && !env_mask_host[i]) continue;
+        sel[i] = 0; mask[i] = 1;
+        float *rec = e->cam_host.data() + (size_t)i * CF;
+        camera_vp(views16 + 16 * (size_t)i, projs16 + 16 * (size_t)i, rec + CAM_VP);
+        frustum_plane_norms(RM, rec + CAM_VP, rec + CAM_PN, (float (*)[8])(rec + CAM_TP));
+    }
+    HIPCHK(hipMemcpyAsync(e->cam_dev, e->cam_host.data(), sizeof(float) * N * CF, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->cam_sel, sel.data(), sizeof(int) * N, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->mask_dev, mask.data(), N, hipMemcpyHostToDevice, e->stream));
+    // the rebuild: build_static_layer's launches with the masked envs selected
+    DevPtrs Db = e->D;
+    Db.static_vis = nullptr; Db.hgflag = e->cam_sel;
+    ImageOut layers;
+    layers.rgb = Db.static_rgb; layers.depth = Db.static_depth; layers.mask = Db.static_mask; layers.env_stride = px;
+    hipLaunchKernelGGL(k_background, copy_grid, dim3(256), 0, e->stream, e->RM_dev, Db, N, (const unsigned char *)e->mask_dev);
+    hipLaunchKernelGGL(k_render_setup, dim3((N * MAXINST + 63) / 64), dim3(64), 0, e->stream, e->B, e->P, e->RM_dev, Db, 1);
+    hipLaunchKernelGGL(k_raster, dim3(N, RM.ntiles), dim3(RASTER_THREADS), 0, e->stream, e->P, e->RM_dev, Db, e->n_inst_used, 1, 0, 0, 1);
+    hipLaunchKernelGGL(k_shade, dim3(N, RM.ntiles, SHADE_SPLIT), dim3(SHADE_THREADS), 0, e->stream, e->RM_dev, Db, layers, 0, 0, 1, 0, (unsigned *)nullptr);
+    hipLaunchKernelGGL(k_camera_changed, dim3((N + 255) / 256), dim3(256), 0, e->stream, e->RM_dev, e->D, N, (const unsigned char *)e->mask_dev,
+                       e->images_valid ? e->stale_dev : (unsigned char *)nullptr);
+    HIPCHK(hipGetLastError());
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return fail(RR_EDEVICE, "rr_set_env_cameras: static layer pass failed");
+    if (e->images_valid) e->stale_any = true;
     return RR_OK;
 }
 

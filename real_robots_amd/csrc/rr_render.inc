@@ -355,13 +355,14 @@ extern "C" int rr_debug_raster_wgmarks(unsigned long long *out /*[65536][8]*/) {
 
 // The cluster cull of raster_tile: clip-space centre of the cluster's bounding sphere against the five
 // frustum planes, then against the planes of a tile's first / last sample row and column (RM.tile_plane), radius enlarged -- conservative.
+// pn / tp: the camera's plane_norm and the tile's row of tile_plane (RenderModel's, or the env's record with per-env cameras).
 struct ClusterClip { float cx, cy, cw, r; };
-__device__ __forceinline__ bool cluster_outside_frustum(const RenderModel &RM, const float *m, const float4 cs, ClusterClip &c) {
+__device__ __forceinline__ bool cluster_outside_frustum(const float *pn /*RM.plane_norm*/, const float *m, const float4 cs, ClusterClip &c) {
     c.cx = m[0] * cs.x + m[1] * cs.y + m[2] * cs.z + m[3]; c.cy = m[4] * cs.x + m[5] * cs.y + m[6] * cs.z + m[7];
     c.cw = m[12] * cs.x + m[13] * cs.y + m[14] * cs.z + m[15];
     c.r = cs.w * 1.001f + 1e-4f;
-    return (c.cw + c.cx) < -c.r * RM.plane_norm[0] || (c.cw - c.cx) < -c.r * RM.plane_norm[1] || (c.cw + c.cy) < -c.r * RM.plane_norm[2] ||
-           (c.cw - c.cy) < -c.r * RM.plane_norm[3] || (c.cw - 0.1f) < -c.r * RM.plane_norm[4];
+    return (c.cw + c.cx) < -c.r * pn[0] || (c.cw - c.cx) < -c.r * pn[1] || (c.cw + c.cy) < -c.r * pn[2] ||
+           (c.cw - c.cy) < -c.r * pn[3] || (c.cw - 0.1f) < -c.r * pn[4];
 }
 __device__ __forceinline__ bool cluster_outside_tile(const ClusterClip &c, const float *tp /*RM.tile_plane[tile]*/, bool tiled, bool xtiled) {
     return (tiled && ((tp[0] * c.cw - c.cy) > c.r * tp[1] * 1.001f + 1e-4f * c.cw || (c.cy - tp[2] * c.cw) > c.r * tp[3] * 1.001f + 1e-4f * c.cw)) ||
@@ -453,12 +454,18 @@ __device__ __forceinline__ void raster_tile(const SimParams &P, const RenderMode
     }
     static_assert(MAXWIN <= NT_, "one cluster per thread in the cull");
     if (cull_mine) {
+        // the cull's camera planes: the handle's, or this env's record (env and tile are uniform in the workgroup: scalar loads)
+        const float *cam_pn = RM.plane_norm, *cam_tp = RM.tile_plane[tile];
+        if (D.env_cam) {
+            const float *cam = D.env_cam + (size_t)__builtin_amdgcn_readfirstlane(env) * cam_floats(RM.ntiles);
+            cam_pn = cam + CAM_PN; cam_tp = cam + CAM_TP + 8 * __builtin_amdgcn_readfirstlane(tile);
+        }
         const int wi = tid;
         int inst = cull_inst;
         float4 cs = cull_cs;
         asm("" : "+v"(inst), "+v"(cs.x), "+v"(cs.y), "+v"(cs.z), "+v"(cs.w));      // (nothing computed from them ahead of the barrier: the wait for the two loads stays down here)
         ClusterClip cc;
-        const bool out = cluster_outside_frustum(RM, mvp[inst], cs, cc) || cluster_outside_tile(cc, RM.tile_plane[tile], tiled, xtiled);
+        const bool out = cluster_outside_frustum(cam_pn, mvp[inst], cs, cc) || cluster_outside_tile(cc, cam_tp, tiled, xtiled);
         RSTAT(0, 1);                                // windows
         if (!out && inst < n_inst_used) wlist[atomicAdd(&wcount, 1u)] = (unsigned short)wi;
     }
@@ -816,8 +823,8 @@ __device__ __forceinline__ void raster_tile(const SimParams &P, const RenderMode
         atomicAdd(&g_rstats[14], (unsigned long long)(__builtin_readcyclecounter() - t_exit_)); atomicAdd(&g_rstats[15], (unsigned long long)(t_exit_ - t_loop0_));
     }
 #endif
-    if (pass == 1) {   // publish the static layer's keys
-        unsigned long long *sv = D.static_vis_out + (size_t)row0 * W + tx0i;
+    if (pass == 1) {   // publish the static layer's keys: the shared layer is built as env 0, an env's own layer (per-env cameras) as that env
+        unsigned long long *sv = D.static_vis_out + (size_t)env * W * H + (size_t)row0 * W + tx0i;
         for (int i = tid; i < npix; i += NT_) { const int lr = i / TW, lx = i - lr * TW; if (lx < cols) sv[(size_t)lr * W + lx] = vis[i]; }
     }
     // ---- compaction: pixels owned by a triangle rasterised in this pass go to the fragment list of this (env, tile)
@@ -939,15 +946,15 @@ __global__ void __launch_bounds__(COPY_THREADS) k_static_copy(const RenderModel 
     for (int env = blockIdx.y; env < N; env += gridDim.y) {
     if (use_flags && D.render_flags && !D.render_flags[env]) continue;
     if (stale && !stale[env]) continue;
-    const size_t base = (size_t)env * out.env_stride;
+    const size_t base = (size_t)env * out.env_stride, sbase = D.static_stride * env;      // (sbase: the env's own layer, per-env cameras)
     for (int g = blockIdx.x * COPY_THREADS + threadIdx.x; g < ngroups; g += gridDim.x * COPY_THREADS) {
-        const unsigned *srgb = (const unsigned *)(D.static_rgb) + (size_t)3 * g;
+        const unsigned *srgb = (const unsigned *)(D.static_rgb + 3 * sbase) + (size_t)3 * g;      // (3 H W is a multiple of 4: W % 4 == 0)
         const unsigned r0 = srgb[0], r1 = srgb[1], r2 = srgb[2];
-        const float4 dv = *(const float4 *)(D.static_depth + (size_t)4 * g);
+        const float4 dv = *(const float4 *)(D.static_depth + sbase + (size_t)4 * g);
         unsigned *rgbp = (unsigned *)(out.rgb + (base + (size_t)4 * g) * 3);
         rgbp[0] = r0; rgbp[1] = r1; rgbp[2] = r2;
         *(float4 *)(out.depth + base + (size_t)4 * g) = dv;
-        if (out.mask) *(int4 *)(out.mask + base + (size_t)4 * g) = *(const int4 *)(D.static_mask + (size_t)4 * g);
+        if (out.mask) *(int4 *)(out.mask + base + (size_t)4 * g) = *(const int4 *)(D.static_mask + sbase + (size_t)4 * g);
     }
     }
 }
@@ -962,13 +969,36 @@ __global__ void k_stale_clear(const RenderModel *RMp, DevPtrs D, int N, unsigned
     stale[env] = 0;
 }
 
-// Background fill of the shared static images (before the static layer is shaded).
-__global__ void k_background(const RenderModel *RMp, DevPtrs D) {
+// Background fill of the static images (before the static layer is shaded): the shared layer (N = 1), or the layers of the
+// envs whose mask byte is set (per-env cameras; mask == nullptr: all N).
+__global__ void k_background(const RenderModel *RMp, DevPtrs D, int N, const unsigned char *mask) {
     const int npx = RMp->W * RMp->H;
+    for (int env = blockIdx.y; env < N; env += gridDim.y) {
+    if (mask && !mask[env]) continue;
+    unsigned char *rgb = D.static_rgb + 3 * D.static_stride * env;
+    float *depth = D.static_depth + D.static_stride * env;
+    int *msk = D.static_mask + D.static_stride * env;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += gridDim.x * blockDim.x) {
-        D.static_rgb[3 * i] = 255; D.static_rgb[3 * i + 1] = 255; D.static_rgb[3 * i + 2] = 255;
-        D.static_depth[i] = 1.0f; D.static_mask[i] = -1;
+        rgb[3 * i] = 255; rgb[3 * i + 1] = 255; rgb[3 * i + 2] = 255;
+        depth[i] = 1.0f; msk[i] = -1;
     }
+    }
+}
+
+// Per-env cameras: the visibility keys of the shared static layer into every env's layer (the images go by k_static_copy).
+__global__ void k_static_vis_spread(const unsigned long long *src, unsigned long long *dst, size_t npx, int N) {
+    for (int env = blockIdx.y; env < N; env += gridDim.y)
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += (size_t)gridDim.x * blockDim.x) dst[(size_t)env * npx + i] = src[i];
+}
+
+// Per-env cameras, behind the rebuild of the static layers of the envs whose mask byte is set: their fragment lists (scratch
+// of the rebuild) are empty, and -- stale != nullptr -- their images predate their new layer (a full copy at their next render).
+__global__ void k_camera_changed(const RenderModel *RMp, DevPtrs D, int N, const unsigned char *mask, unsigned char *stale) {
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env >= N || !mask[env]) return;
+    const int nt = RMp->ntiles;
+    for (int t = 0; t < nt; t++) D.frag_count[(size_t)env * nt + t] = 0u;
+    if (stale) stale[env] = 1;
 }
 
 // Deferred shading of the fragment lists, one lane per listed pixel.  Every (env, tile) list is dealt out in
@@ -1008,7 +1038,8 @@ __device__ __forceinline__ void shade_block(const RenderModel &RM, const DevPtrs
     const uint2 *lst = D.frag_list + ((size_t)env * RM.ntiles + tile) * TILE_PIX;
     const int tyi = tile / RM.ntx, row0 = tyi * RM.tile_h, tx0i = (tile - tyi * RM.ntx) * RM.tile_w;
     const size_t ebase = (size_t)env * out.env_stride;
-    const unsigned long long *sv = D.static_vis;                 // null while the static layer itself is built
+    const size_t sbase = D.static_stride * env;                  // the env's own static layer (per-env cameras), else 0
+    const unsigned long long *sv = D.static_vis ? D.static_vis + sbase : nullptr;     // null while the static layer itself is built
     for (unsigned i = z * NTHREADS + threadIdx.x; i < n; i += nz * NTHREADS) {
         const uint2 f = lst[i];
 #ifdef RR_RASTER_STATS
@@ -1026,7 +1057,7 @@ __device__ __forceinline__ void shade_block(const RenderModel &RM, const DevPtrs
 #if defined(RR_SHADE_PROBE) && (RR_SHADE_PROBE & 128)
             continue;       // (probe: what does the put-back path cost?)
 #endif
-            const size_t so = gp, o = ebase + gp;
+            const size_t so = sbase + gp, o = ebase + gp;
             out.rgb[o * 3] = D.static_rgb[so * 3]; out.rgb[o * 3 + 1] = D.static_rgb[so * 3 + 1]; out.rgb[o * 3 + 2] = D.static_rgb[so * 3 + 2];
             out.depth[o] = D.static_depth[so];
             if (out.mask) out.mask[o] = D.static_mask[so];

@@ -233,6 +233,20 @@ __device__ __forceinline__ void os_row_pair(int k, v3 dir, v3 x, const ObjData &
 }
 
 // ---------------------------------------------------------------------------------------------- render setup
+// mvp = VP [R p; 0 1] of one render instance: the one 4x4 product of the camera with a model matrix (instance_setup_core)
+__device__ __forceinline__ void instance_mvp(const float *VP, const m3 &R, const v3 &p, float (&mvp)[16]) {
+#pragma clang fp contract(off)
+    const float xf[12] = {R.m[0], R.m[1], R.m[2], R.m[3], R.m[4], R.m[5], R.m[6], R.m[7], R.m[8], p.x, p.y, p.z};
+#pragma unroll
+    for (int e = 0; e < 16; e++) {
+        const int r = e >> 2, c = e & 3;
+        float a = 0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) a += VP[4 * r + k] * (c < 3 ? xf[3 * k + c] : xf[9 + k]);
+        a += VP[4 * r + 3] * (c == 3 ? 1.0f : 0.0f);
+        mvp[e] = a;
+    }
+}
 // Instance transforms for the rasteriser, one thread per (env, instance): a robot-link thread composes the joint
 // transforms of its body's ancestors only (same operations, in the same order, as fk_all() for that chain), an object
 // thread converts the object's quaternion; the 12 floats of an instance are stored as three 16-byte words, so a wave
@@ -266,21 +280,11 @@ __device__ __forceinline__ void instance_setup_core(const BodyParams &B, const R
         p = mk(op7[0], op7[1], op7[2]);
     }
     // mvp = VP * [R p; 0 1] (same summation order as the oracle's 4x4 product, no FMA contraction), then the shading
-    // constants: the raster and shading workgroups just copy these 128 bytes per instance into LDS
+    // constants: the raster and shading workgroups just copy these 128 bytes per instance into LDS.  VP is the env's own
+    // camera with per-env cameras (several envs per wave here: vector loads), else the handle's (scalar loads, as before).
     float mvp[16];
-    {
-#pragma clang fp contract(off)
-        const float xf[12] = {R.m[0], R.m[1], R.m[2], R.m[3], R.m[4], R.m[5], R.m[6], R.m[7], R.m[8], p.x, p.y, p.z};
-#pragma unroll
-        for (int e = 0; e < 16; e++) {
-            const int r = e >> 2, c = e & 3;
-            float a = 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) a += RM.VP[4 * r + k] * (c < 3 ? xf[3 * k + c] : xf[9 + k]);
-            a += RM.VP[4 * r + 3] * (c == 3 ? 1.0f : 0.0f);
-            mvp[e] = a;
-        }
-    }
+    if (D.env_cam) instance_mvp(D.env_cam + (size_t)env * cam_floats(RM.ntiles) + CAM_VP, R, p, mvp);
+    else instance_mvp(RM.VP, R, p, mvp);
     const int tidx = RM.in_tex[i];
     float4 *o = (float4 *)(D.inst_xf + ((size_t)env * MAXINST + i) * 32);
     o[0] = make_float4(mvp[0], mvp[1], mvp[2], mvp[3]);

@@ -18,13 +18,22 @@ mass is randomised -- uniform density).  reset(seed=...) draws every env's value
 same-step autoreset draws again for the truncated envs only.  The values in force are returned under `infos["object_dynamics"]`
 (a dict of arrays like BatchedREALRobotEnv.object_dynamics(): every env after reset(); after an autoreset
 `infos["_object_dynamics"]` masks the envs that drew new ones).
+Domain randomisation of the eye camera: `camera_randomization={'translation': 0.03, 'rotation': 3.0, 'fov': (75, 85)}` gives every env
+its own camera (BatchedREALRobotEnv.set_env_cameras): the view is [R | t] V0, a perturbation in camera coordinates of the default
+eye V0 (look-at from (0.01, 0, 1.2) to the table, up +z), with t uniform in +-translation metres per axis and R = Rz Ry Rx of
+angles uniform in +-rotation degrees; the projection is perspective(fov, W / H, 0.1, 100) with fov uniform in (low, high) degrees
+(missing keys: no translation, no rotation, fov 80).  Drawn like the dynamics -- every env on reset(seed=...), the truncated envs on
+the same-step autoreset, before the re-render -- from a generator of its own (the dynamics draws of a seed do not depend on it).
+The matrices in force are returned as `infos["camera"] = {"view": [N, 4, 4], "proj": [N, 4, 4]}` (float32, row-major); after an
+autoreset `infos["_camera"]` masks the envs that drew.
 """
 import numpy as np
 
 from . import _native as nat
-from . import spaces
+from . import mathutil, spaces
 from .batched import BatchedREALRobotEnv
 from .envs.robot import Kuka
+from .model import load_model
 
 try:                                    # optional dependency
     from gymnasium.vector import VectorEnv as _Base
@@ -46,7 +55,8 @@ def _batch_dict_space(space, n):
 
 class REALRobotVectorEnv(_Base):
     def __init__(self, num_envs, objects=3, additional_obs=False, eye_width=320, eye_height=240, device=0,
-                 max_episode_steps=int(15e6), render_every_step=True, device_obs=False, solver=None, dynamics_randomization=None):
+                 max_episode_steps=int(15e6), render_every_step=True, device_obs=False, solver=None, dynamics_randomization=None,
+                 camera_randomization=None):
         self.num_envs = int(num_envs)
         self._robot = Kuka(additional_obs, objects, eye_width, eye_height, env=None)
         self.single_action_space = spaces.Dict({"joint_command": self._robot.action_space, "render": spaces.MultiBinary(1)})
@@ -77,6 +87,29 @@ class REALRobotVectorEnv(_Base):
                 self._dyn_rand[k] = (lo, hi)
             self._dyn_default = self._be.default_object_dynamics()
         self._dyn_rng = np.random.default_rng()
+        self._cam_rand = None
+        if camera_randomization:
+            cr = dict(translation=0.0, rotation=0.0, fov=(80.0, 80.0))
+            for k, r in camera_randomization.items():
+                if k not in cr:
+                    raise ValueError("camera_randomization: unknown field %r (known: %s)" % (k, ', '.join(cr)))
+                if k == 'fov':
+                    lo, hi = (float(x) for x in r)
+                    if not (np.isfinite(lo) and np.isfinite(hi) and 0 < lo <= hi < 180):
+                        raise ValueError("camera_randomization['fov']: need finite 0 < low <= high < 180 (degrees)")
+                    cr[k] = (lo, hi)
+                else:
+                    v = float(r)
+                    if not (np.isfinite(v) and v >= 0):
+                        raise ValueError("camera_randomization[%r]: need a finite value >= 0" % k)
+                    cr[k] = v
+            self._cam_rand = cr
+            self._cam_aspect = float(eye_width) / float(eye_height)
+            self._cam_view0 = mathutil.look_at((0.01, 0.0, 1.2), np.asarray(load_model()['table_pos'], np.float64), (0.0, 0.0, 1.0))
+            self._cam_view = np.broadcast_to(self._cam_view0.astype(np.float32), (self.num_envs, 4, 4)).copy()
+            self._cam_proj = np.broadcast_to(mathutil.perspective(80.0, self._cam_aspect, 0.1, 100.0).astype(np.float32),
+                                             (self.num_envs, 4, 4)).copy()
+        self._cam_rng = np.random.default_rng()
 
     DYNAMICS_FIELDS = ('mass', 'inertia', 'friction', 'restitution', 'rolling', 'spinning')
 
@@ -96,6 +129,30 @@ class REALRobotVectorEnv(_Base):
         self._be.set_object_dynamics(env_mask=mask.astype(np.uint8), **args)
         return self._be.object_dynamics()
 
+    @staticmethod
+    def _rot_zyx(a):
+        """R = Rz(a[2]) Ry(a[1]) Rx(a[0]) for rows of angles a [n, 3] (radians) -> [n, 3, 3]."""
+        cx, sx, cy, sy, cz, sz = np.cos(a[:, 0]), np.sin(a[:, 0]), np.cos(a[:, 1]), np.sin(a[:, 1]), np.cos(a[:, 2]), np.sin(a[:, 2])
+        o, z = np.ones_like(cx), np.zeros_like(cx)
+        Rx = np.stack([o, z, z, z, cx, -sx, z, sx, cx], -1).reshape(-1, 3, 3)
+        Ry = np.stack([cy, z, sy, z, o, z, -sy, z, cy], -1).reshape(-1, 3, 3)
+        Rz = np.stack([cz, -sz, z, sz, cz, z, z, z, o], -1).reshape(-1, 3, 3)
+        return Rz @ Ry @ Rx
+
+    def _draw_cameras(self, mask):
+        """Draws new cameras for the envs in `mask` (bool [N]) and applies them; returns the matrices in force."""
+        cr, n = self._cam_rand, int(mask.sum())
+        t = self._cam_rng.uniform(-cr['translation'], cr['translation'], size=(n, 3))
+        ang = np.radians(self._cam_rng.uniform(-cr['rotation'], cr['rotation'], size=(n, 3)))
+        fov = self._cam_rng.uniform(*cr['fov'], size=n)
+        T = np.tile(np.eye(4), (n, 1, 1))
+        T[:, :3, :3], T[:, :3, 3] = self._rot_zyx(ang), t
+        self._cam_view[mask] = (T @ self._cam_view0).astype(np.float32)
+        self._cam_proj[mask] = np.stack([mathutil.perspective(f, self._cam_aspect, 0.1, 100.0) for f in fov]).astype(np.float32) \
+            if n else np.zeros((0, 4, 4), np.float32)
+        self._be.set_env_cameras(self._cam_view, self._cam_proj, env_mask=mask.astype(np.uint8))
+        return {"view": self._cam_view.copy(), "proj": self._cam_proj.copy()}
+
     # ------------------------------------------------------------------ observations
     def _obs(self, rendered):
         be = self._be
@@ -113,8 +170,11 @@ class REALRobotVectorEnv(_Base):
         infos = {}
         if seed is not None:
             self._dyn_rng = np.random.default_rng(seed)
+            self._cam_rng = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(1,)))
         if self._dyn_rand:
             infos["object_dynamics"] = self._draw_dynamics(np.ones(self.num_envs, bool))
+        if self._cam_rand:
+            infos["camera"] = self._draw_cameras(np.ones(self.num_envs, bool))
         self._be.reset()
         self._steps[:] = 0
         if self.render_every_step:
@@ -147,6 +207,9 @@ class REALRobotVectorEnv(_Base):
             if self._dyn_rand:
                 infos["object_dynamics"] = self._draw_dynamics(truncated)
                 infos["_object_dynamics"] = truncated.copy()
+            if self._cam_rand:
+                infos["camera"] = self._draw_cameras(truncated)
+                infos["_camera"] = truncated.copy()
             self._be.reset(truncated.astype(np.uint8))
             self._steps[truncated] = 0
             if render:
