@@ -14,7 +14,8 @@ nothing of the oracle (oracle/rr_oracle.c) or of the HIP kernels, and where it c
 
 The narrow phase is not restated: the contact points, normals and distances of the step come in as input (records in the
 layout of the contact lists: bodyA, bodyB, linkA, x (3), n (3), dist, normal force, mu).  Every function of the preparation
-broadcasts over leading batch dimensions (prep() checks whole batches of the device's preparation record).
+broadcasts over leading batch dimensions (prep() checks whole batches of the device's preparation record).  With fewer than three
+objects the state keeps its 61 entries: the slots of the absent objects pass through a step unchanged.
 """
 import numpy as np
 
@@ -274,6 +275,31 @@ def warm_start(contacts, prev, factor):
         if min(mine)[1] == i:
             lam0[i] = factor * float(prev[j][10]) * DT
     return lam0
+
+
+SKINS = ('skin_00', 'skin_01', 'skin_10', 'skin_11')      # Kuka.get_touch_sensors' order (robot.py:156)
+CONTACT_THRESHOLD = 0.1                                    # Kuka.contact_threshold (robot.py:66, 136)
+
+
+def touch_sensors(contacts, forces, order=SKINS, threshold=CONTACT_THRESHOLD, statics=True):
+    """get_touch_sensors (robot.py:131-163) from contact records [n, 12] and their normal forces [n]: sensor k is the largest
+    force of the contacts whose body A is the robot, whose link A is skin `order[k]` and whose |distance| is below `threshold`
+    (None: no threshold); 0 if there is none.  The reference's object_names holds the table: static contacts count
+    (statics=False leaves them out, a negative control)."""
+    from real_robots_amd._native import LINK_NAMES
+    c = np.asarray(contacts, dtype=np.float64).reshape(-1, 12)
+    f = np.asarray(forces, dtype=np.float64).reshape(-1)
+    ok = (c[:, 0] >= 0) & (c[:, 0] < 16)
+    if threshold is not None:
+        ok &= np.abs(c[:, 9]) < threshold
+    if not statics:
+        ok &= c[:, 1] >= 0
+    out = np.zeros(len(order))
+    for k, name in enumerate(order):
+        sel = ok & (c[:, 2] == LINK_NAMES.index(name))
+        if sel.any():
+            out[k] = f[sel].max()
+    return out
 
 
 def plane_space(n):

@@ -5,6 +5,8 @@ those share -- a sign in a row, the frame of an inertia, a missing gyroscopic or
 them all.  Here the reference is computed independently: the Lagrangian bias by complex step, complex-step contact Jacobians,
 dense rows over generalised velocities, materials combined from each env's own dynamics rows.
 """
+import time
+
 import numpy as np
 import pytest
 
@@ -12,8 +14,10 @@ from real_robots_amd import _native as nat
 from real_robots_amd.batched import BatchedREALRobotEnv
 from real_robots_amd.distributed import synthetic_actions
 from tests import numpy_step as ns
-from tests.test_gpu_contacts_fuzz import state_bounds, SENS_FACTOR, SENS_RUNS
+from tests.test_gpu_contacts_fuzz import state_bounds, CRUSH_FORCE, SENS_FACTOR, SENS_RUNS, _grasp_script
 from tests.test_gpu_object_dynamics import PATHS, _drive
+from tests.test_gpu_solver_params import SECOND, THIRD
+from tests.test_numpy_step import VARIANTS as CPU_VARIANTS
 from tests.test_gpu_round6 import (_make, _rich_states, S_BR, S_BP, S_BAX, S_MINV, S_QDS, S_OR, S_OIINV, S_OVS, S_OWS, S_OP,
                                    S_TOTAL)
 
@@ -22,9 +26,9 @@ pytestmark = pytest.mark.gpu
 PREP_PATHS = {'scalar': {'RR_PREP_SCALAR': '1', 'RR_NO_LOOKAHEAD': '1'}, 'p16': {'RR_NO_LOOKAHEAD': '1'}, 'lookahead': {}}
 
 
-def random_dynamics(n, seed):
-    """Per-env dynamics rows [n, 3, 8]: mass x 0.2-5, anisotropic inertia (each axis x 0.5-2 on top of the mass ratio), friction,
-    restitution, rolling and spinning friction drawn around the model's."""
+def random_dynamics(n, seed, nobj=3):
+    """Per-env dynamics rows [n, nobj, 8]: mass x 0.2-5, anisotropic inertia (each axis x 0.5-2 on top of the mass ratio), friction,
+    restitution, rolling and spinning friction drawn around the model's (drawn for three objects, the leading nobj kept)."""
     rng = np.random.default_rng(seed)
     d = np.broadcast_to(ns.default_dynamics(), (n, 3, 8)).copy()
     k = np.exp(rng.uniform(np.log(0.2), np.log(5.0), (n, 3)))
@@ -33,7 +37,7 @@ def random_dynamics(n, seed):
     d[..., 4] = rng.uniform(0.1, 1.2, (n, 3))
     d[..., 5] = rng.uniform(0.0, 0.8, (n, 3))
     d[..., 6:8] = rng.uniform(0.0, 0.05, (n, 3, 2))
-    return d.astype(np.float32)
+    return np.ascontiguousarray(d[:, :nobj]).astype(np.float32)
 
 
 def edge_states(N, seed):
@@ -68,13 +72,14 @@ def edge_states(N, seed):
     return st.astype(np.float32)
 
 
-def prep_ratios(rec, st, dyn):
-    """Worst ratio of |device - numpy| to the float32 ceiling of every field of RR_F_PREP."""
-    N = len(st)
-    ref = ns.prep(st.astype(np.float64), dyn.astype(np.float64))
+def prep_ratios(rec, st, dyn, nobj=3):
+    """Worst ratio of |device - numpy| to the float32 ceiling of every field of RR_F_PREP (the object fields of the nobj objects
+    present: the record keeps room for three)."""
+    N, k = len(st), nobj
+    ref = ns.prep(st.astype(np.float64), dyn.astype(np.float64), nobj=k)
     rec = rec.astype(np.float64)
     qd = np.abs(st[:, 11:22].astype(np.float64)).max(1, keepdims=True)
-    ob = st[:, 22:61].astype(np.float64).reshape(N, 3, 13)
+    ob = st[:, 22:22 + 13 * k].astype(np.float64).reshape(N, k, 13)
     ob[ref['oob']] = 0.0
     vn = np.linalg.norm(ob[..., 7:10], axis=-1)[..., None]
     wn = np.linalg.norm(ob[..., 10:13], axis=-1)[..., None]
@@ -84,18 +89,18 @@ def prep_ratios(rec, st, dyn):
     # ceiling.  A term of float32 epsilon x the mass matrix's condition (~1e3 here) times |dt M^-1 b| covers that rounding.)
     bterm = np.abs(ns.DT * np.einsum('nij,nj->ni', Minv, ref['bias'])).max(1, keepdims=True)
     scale_m = np.sqrt(np.einsum('nii,njj->nij', Minv, Minv))
-    Iinv = ref['oIinv'].reshape(N, 3, 9)
+    Iinv = ref['oIinv'].reshape(N, k, 9)
     out = {
         'frames R': np.abs(rec[:, S_BR:S_BP] - ref['R'].reshape(N, 99)) / 2e-6,
         'frames p': np.abs(rec[:, S_BP:S_BAX] - ref['p'].reshape(N, 33)) / 2e-6,
         'joint axes': np.abs(rec[:, S_BAX:S_MINV] - ref['axis'].reshape(N, 33)) / 2e-6,
         'M^-1': np.abs(rec[:, S_MINV:S_QDS].reshape(N, 11, 11) - Minv) / (1e-4 * scale_m),
         'qd*': np.abs(rec[:, S_QDS:S_OR] - ref['qds']) / (2e-4 + 2e-6 * qd + 5e-5 * bterm),
-        'object R': np.abs(rec[:, S_OR:S_OIINV] - ref['oR'].reshape(N, 27)) / 2e-6,
-        'object I^-1': np.abs(rec[:, S_OIINV:S_OVS].reshape(N, 3, 9) - Iinv) / (1e-5 * np.abs(Iinv).max(-1, keepdims=True)),
-        'v*': np.abs(rec[:, S_OVS:S_OWS].reshape(N, 3, 3) - ref['ovs']) / (1e-6 * (1 + vn)),
-        'w*': np.abs(rec[:, S_OWS:S_OP].reshape(N, 3, 3) - ref['ows']) / (1e-6 * (1 + wn)),
-        'collision position': np.abs(rec[:, S_OP:S_TOTAL].reshape(N, 3, 3) - ref['opos']) / 2e-6,
+        'object R': np.abs(rec[:, S_OR:S_OR + 9 * k] - ref['oR'].reshape(N, 9 * k)) / 2e-6,
+        'object I^-1': np.abs(rec[:, S_OIINV:S_OIINV + 9 * k].reshape(N, k, 9) - Iinv) / (1e-5 * np.abs(Iinv).max(-1, keepdims=True)),
+        'v*': np.abs(rec[:, S_OVS:S_OVS + 3 * k].reshape(N, k, 3) - ref['ovs']) / (1e-6 * (1 + vn)),
+        'w*': np.abs(rec[:, S_OWS:S_OWS + 3 * k].reshape(N, k, 3) - ref['ows']) / (1e-6 * (1 + wn)),
+        'collision position': np.abs(rec[:, S_OP:S_OP + 3 * k].reshape(N, k, 3) - ref['opos']) / 2e-6,
     }
     q = out['qd*']
     n, j = np.unravel_index(int(np.argmax(q)), q.shape)
@@ -104,116 +109,240 @@ def prep_ratios(rec, st, dyn):
     return {k: float(v.max()) for k, v in out.items()}
 
 
-@pytest.mark.parametrize('N', [1, 5, 17, 4096])
-def test_prep_record_matches_the_numpy_preparation(monkeypatch, N):
+PREP_CASES = [pytest.param(3, N, id=str(N)) for N in (1, 5, 17, 4096)] + \
+    [pytest.param(k, N, id='objects%d-N%d' % (k, N)) for k in (1, 2) for N in (5, 17)]
+
+
+@pytest.mark.parametrize('objects,N', PREP_CASES)
+def test_prep_record_matches_the_numpy_preparation(monkeypatch, objects, N):
     """RR_F_PREP field by field against numpy under the three preparation paths: the thread-per-env kernels, the 16-lane kernel,
-    and the look-ahead (the record then describes the state the step left).  Ceilings from float32 arithmetic, not measured."""
+    and the look-ahead (the record then describes the state the step left).  Ceilings from float32 arithmetic, not measured.
+    With one or two objects (P.nobj < 3: the object lanes' guards, the object stride of the per-env rows) only the objects present
+    are compared."""
     st = edge_states(N, 3)
-    dyn = random_dynamics(N, 5)
+    dyn = random_dynamics(N, 5, objects)
     for path, envv in PREP_PATHS.items():
-        env = _make(monkeypatch, envv, N, objects=3, width=64, height=64)
+        env = _make(monkeypatch, envv, N, objects=objects, width=64, height=64)
         env.set_object_dynamics(**BatchedREALRobotEnv._dynamics_dict(dyn))
         env.state = st
         env.step(None)
         rec, used = env.host(nat.F_PREP), (st if path != 'lookahead' else env.state)
         assert (env.host(nat.F_ERRFLAGS) == 0).all()
         env.close()
-        r = prep_ratios(rec, used, dyn)
-        print("N=%d %s: worst |device - numpy| / ceiling: %s" % (N, path, ', '.join('%s %.3f' % kv for kv in r.items())))
+        r = prep_ratios(rec, used, dyn, objects)
+        print("objects=%d N=%d %s: worst |device - numpy| / ceiling: %s" % (objects, N, path, ', '.join('%s %.3f' % kv for kv in r.items())))
         assert max(r.values()) < 1.0, (path, r)
 
 
-def _perturbed_spread(st0, cmd, cd, prev, dyn, iters, ref, rng):
-    """The numpy step's own spread when every entry of the float32 start state moves by one unit in the last place."""
-    sj = so = sv = 0.0
+def _perturbed_spread(st0, cmd, cd, prev, dyn, iters, ref, rng, nobj=3, solver=None):
+    """The numpy step's own spread when every entry of the float32 start state and of the contact records' points, normals and
+    distances moves by one unit in the last place (the fuzz test's oracle_sensitivity re-collides, so its contacts move with the
+    state; these records are fixed input here and are moved themselves): the largest deviation from the unperturbed result
+    (state `ref`, normal forces `ref_f`) in joints, object pose, object velocity and the contacts' normal forces."""
+    ref_s, ref_f = ref
+    sj = so = sv = sf = 0.0
+
+    def ulp(a):
+        up = rng.random(a.shape) < 0.5
+        return np.where(up, np.nextafter(a, np.float32(np.inf)), np.nextafter(a, np.float32(-np.inf)))
     for _ in range(SENS_RUNS):
-        up = rng.random(st0.shape) < 0.5
-        stp = np.where(up, np.nextafter(st0, np.float32(np.inf)), np.nextafter(st0, np.float32(-np.inf)))
-        d = np.abs(ns.step(stp.astype(np.float64), cmd, cd, dyn=dyn, prev=prev, solver_iters=iters)['state'] - ref)
-        dobj = d[22:61].reshape(3, 13)
+        cdp = cd.copy()
+        cdp[:, 3:10] = ulp(cd[:, 3:10])
+        r = ns.step(ulp(st0).astype(np.float64), cmd, cdp, dyn=dyn, prev=prev, solver=solver, solver_iters=iters, nobj=nobj)
+        d = np.abs(r['state'] - ref_s)
+        dobj = d[22:22 + 13 * nobj].reshape(nobj, 13)
         sj, so, sv = max(sj, float(d[:22].max())), max(so, float(dobj[:, :7].max())), max(sv, float(dobj[:, 7:].max()))
-    return sj, so, sv
+        if len(cd):
+            sf = max(sf, float(np.abs(r['lambda_n'] / ns.DT - ref_f).max()))
+    return sj, so, sv, sf
 
 
-def _dev(a, b):
+def _dev(a, b, nobj=3):
     d = np.abs(np.asarray(a, np.float64) - b)
-    dobj = d[22:61].reshape(3, 13)
+    dobj = d[22:22 + 13 * nobj].reshape(nobj, 13)
     return float(d[:22].max()), float(dobj[:, :7].max()), float(dobj[:, 7:].max())
 
 
-@pytest.mark.parametrize('path', list(PATHS) + ['iters1'])
-def test_contact_step_matches_the_numpy_step(monkeypatch, path):
+def force_bound(fmax):
+    """Per-contact bound on |device - numpy| of the normal forces (N) of a step whose largest force is fmax: the fuzz test's bound
+    against the float oracle (tests/test_gpu_contacts_fuzz.py::_check_forces), 0.1 % of the largest force + 0.02 N up to
+    CRUSH_FORCE, the relative part growing with the force above it like state_bounds.  The touch sensors are maxima of these
+    forces: the same bound holds for them."""
+    return 1e-3 * max(1.0, fmax / CRUSH_FORCE) * fmax + 0.02
+
+
+SKIN_SWAP = ('skin_00', 'skin_10', 'skin_01', 'skin_11')            # a negative control: sensors 1 and 2 exchanged
+SOLVERS = {'second': SECOND, 'third': THIRD, 'cpu_solver': CPU_VARIANTS['solver'][1]}
+# (objects, path or solver set, N): the five original cases keep their ids
+CONTACT_CASES = [pytest.param(3, p, 96, id=p) for p in list(PATHS) + ['iters1']] + [
+    pytest.param(1, 'default', 96, id='objects1'), pytest.param(2, 'default', 96, id='objects2'),
+    pytest.param(3, 'second', 96, id='second'), pytest.param(3, 'third', 96, id='third'),
+    pytest.param(3, 'cpu_solver', 96, id='cpu_solver'),
+    pytest.param(1, 'default', 17, id='objects1-N17'), pytest.param(3, 'default', 4096, id='N4096')]
+ORIGINAL = set(PATHS) | {'iters1'}
+GRASP_T0, GRASP_CHECKS = 300, (300, 310, 318, 326)      # the grasp envs' script starts at step 300; checks at these rows (closed)
+
+
+@pytest.mark.parametrize('objects,path,N', CONTACT_CASES)
+def test_contact_step_matches_the_numpy_step(monkeypatch, objects, path, N):
     """One step of the contact solve from each checked env's device state and contact history, against the numpy step on the
-    device's own new contact list, in a 96-env batch with per-env dynamics driven like the per-env dynamics tests."""
-    N = 96
+    device's own new contact list, in a batch with per-env dynamics driven like the per-env dynamics tests; every fourth env
+    (i % 4 == 1) is then reset and closes the gripper on the cube (tests/test_gpu_contacts_fuzz.py::_grasp_script), which loads
+    the distal skins by kilonewtons (the four checked steps after the reset take the grasp envs alone).
+    Per checked env: the state, the normal forces (rr_get_contacts column 10) against numpy's lambda_n / dt, the touch sensors
+    against the reference's rule (robot.py:131-163) on numpy's forces -- and exactly on the device's own; the absent objects'
+    state slots unchanged bit for bit; the observation fields (robot.py:203-211) equal to the state bit for bit.
+    Cases: the five placements / one sweep at N = 96 with three objects, one and two objects, the solver parameter sets of
+    tests/test_gpu_solver_params.py and tests/test_numpy_step.py, a partial 16-env light workgroup (N = 17), the headline
+    batch (N = 4096, default placement)."""
+    t_start = time.time()
+    k = objects
     iters = 1 if path == 'iters1' else 50
-    env = _make(monkeypatch, PATHS.get(path, {}), N, objects=3, width=64, height=64, solver_iters=iters)
-    dyn = random_dynamics(N, 9)
+    solver = SOLVERS.get(path)
+    env = _make(monkeypatch, PATHS.get(path, {}), N, objects=k, width=64, height=64, solver_iters=iters, solver=solver)
+    original = path in ORIGINAL and k == 3 and N == 96
+    mirror = None if original else env.map_observations()      # (the new cases also check the mapped mirror)
+    dyn = random_dynamics(N, 9, k)
     env.set_object_dynamics(**BatchedREALRobotEnv._dynamics_dict(dyn))
     dyn64 = dyn.astype(np.float64)
     _drive([env], 160, seed=3)
+    grasp = np.arange(N) % 4 == 1
+    script = _grasp_script()
     rng = np.random.default_rng(1)
-    occurred, seen_cls, pairs, limit_active, worst, checked = set(), set(), set(), 0, [0.0, 0.0, 0.0], 0
+    occurred, seen_cls, pairs, limit_active, checked = set(), set(), set(), 0, 0
+    worst = dict(joints=0.0, pose=0.0, velocity=0.0, force=0.0, touch=0.0)
+    touch_loaded, escapes, diverged = 0, 0, set()
     controls = []
     cls_name = lambda b: 'object' if b >= 16 else 'robot' if b >= 0 else 'static'
     lim = ns.model()['body_limits']
     limited = [j for j in range(11) if lim[j][0] < lim[j][1]]
-    for t in range(160, 300):
+    check_t = [t for t in range(160, 300) if t % 35 == 0] + [GRASP_T0 + g for g in GRASP_CHECKS]
+    for t in range(160, GRASP_T0 + len(script)):
+        if t == GRASP_T0:
+            env.reset(grasp.astype(np.uint8))
         cmd = (synthetic_actions(range(N), t, seed=3) * 1.6).astype(np.float32)
-        if t % 35 != 0:
+        if t >= GRASP_T0:
+            cmd[grasp] = script[t - GRASP_T0]
+        if t not in check_t:
             env.step(cmd)
             continue
         st0 = env.state
         caches = [env.contacts(i) for i in range(N)]
         env.step(cmd)
         st1, cls = env.state, env.host(nat.F_ENV_CLASS)
-        occurred |= set(int(c) for c in cls)
+        touch = env.host(nat.F_TOUCH)
+        # (a parameter set without the rate limit and with a velocity gain below 1 lets an env of a large batch diverge under these
+        # full-range commands -- in float64 too, tests/test_gpu_solver_params.py: such an env must carry the error flag, and is not
+        # checked)
+        live = np.isfinite(st0).all(1) & np.isfinite(st1).all(1)
+        assert (env.host(nat.F_ERRFLAGS)[~live] & 1).all(), "a non-finite env without the error flag"
+        diverged |= set(np.flatnonzero(~live).tolist())
+        if t < GRASP_T0:                          # (the grasp window checks the grasp envs only)
+            occurred |= set(int(c) for c in cls[live])
+        # every env: the absent objects' slots pass through the step; the observation fields are the state's, bit for bit
+        u0, u1 = st0.view(np.uint32), st1.view(np.uint32)
+        assert np.array_equal(u1[:, 22 + 13 * k:], u0[:, 22 + 13 * k:]), "absent object slots changed (t %d)" % t
+        joints = np.concatenate([st1[:, :8], -st1[:, 8:9]], axis=1)
+        poses = np.ascontiguousarray(st1[:, 22:22 + 13 * k].reshape(N, k, 13)[..., :7])
+        obs = {'joints': env.host(nat.F_JOINTS), 'obj_pose': env.host(nat.F_OBJ_POSE)}
+        assert np.array_equal(obs['joints'].view(np.uint32), joints.view(np.uint32)), t
+        assert np.array_equal(obs['obj_pose'].view(np.uint32), poses.view(np.uint32)), t
+        if mirror is not None:
+            env.sync()
+            for key, want in (('joints', joints), ('obj_pose', poses), ('touch', touch)):
+                assert np.array_equal(mirror[key].view(np.uint32), want.view(np.uint32)), (t, key)
         new = [env.contacts(i) for i in range(N)]
-        picks = []
+        picks = [0, N - 1] if N > 96 else []
         for c in (0, 1, 2):                       # every class, most contacts first
             members = [i for i in range(N) if cls[i] == c]
-            picks += sorted(members, key=lambda i: -len(new[i]))[:3]
+            picks += sorted(members, key=lambda i: -len(new[i]))[:3 if N <= 96 else 2]
         # envs with an object x object contact, and envs with a robot contact and a limited joint within 0.01 rad of a limit
         picks += [i for i in range(N) if ((new[i][:, 0] >= 16) & (new[i][:, 1] >= 16)).any()][:3]
-        picks += [i for i in range(N) if ((new[i][:, 0] >= 0) & (new[i][:, 0] < 16)).any()
-                  and min(min(abs(st0[i][j] - lim[j][0]), abs(st0[i][j] - lim[j][1])) for j in limited) < 0.01][:3]
-        for i in sorted(set(picks)):
-            cd = env.contacts(i)
-            res = ns.step(st0[i].astype(np.float64), cmd[i].astype(np.float64), cd, dyn=dyn64[i], prev=caches[i], solver_iters=iters)
-            ref = res['state']
+        if N <= 96:
+            picks += [i for i in range(N) if ((new[i][:, 0] >= 0) & (new[i][:, 0] < 16)).any()
+                      and min(min(abs(st0[i][j] - lim[j][0]), abs(st0[i][j] - lim[j][1])) for j in limited) < 0.01][:3]
+        if t >= GRASP_T0:                         # the grasp envs with the most loaded skins
+            picks = sorted(np.flatnonzero(grasp), key=lambda i: (-int((touch[i] > 1.0).sum()), -float(touch[i].sum())))[:4]
+        for i in sorted(set(int(x) for x in picks if live[x])):
+            cd = new[i]
+            res = ns.step(st0[i].astype(np.float64), cmd[i].astype(np.float64), cd, dyn=dyn64[i], prev=caches[i], solver=solver,
+                          solver_iters=iters, nobj=k)
+            ref, f_np = res['state'], res['lambda_n'] / ns.DT
             assert np.array_equal(cd[:, 11], res['mat'][:, 0].astype(np.float32)), "mu of env %d" % i
-            fmax = float(cd[:, 10].max()) if len(cd) else 0.0
-            b = state_bounds(fmax)
-            d = _dev(st1[i], ref)
-            if any(x > y for x, y in zip(d, b)):
-                s = _perturbed_spread(st0[i], cmd[i].astype(np.float64), cd, caches[i], dyn64[i], iters, ref, rng)
-                b = tuple(max(x, SENS_FACTOR * y) for x, y in zip(b, s))
-            assert all(x <= y for x, y in zip(d, b)), (path, i, int(cls[i]), fmax, d, b)
-            worst = [max(w, x / y) for w, x, y in zip(worst, d, state_bounds(fmax))]
+            f_dev = cd[:, 10].astype(np.float64)
+            fmax = float(f_dev.max()) if len(cd) else 0.0
+            # the touch sensors are the rule on the device's own forces, exactly (a maximum is the same in any order)
+            assert np.array_equal(touch[i], ns.touch_sensors(cd, f_dev).astype(np.float32)), (path, t, i, touch[i])
+            b = state_bounds(fmax) + (force_bound(fmax),)
+            d = _dev(st1[i], ref, k) + (float(np.abs(f_dev - f_np).max()) if len(cd) else 0.0,
+                                        float(np.abs(touch[i] - ns.touch_sensors(cd, f_np)).max()))
+            flat = b[:3] + (b[3], b[3])
+            bb = flat
+            if any(x > y for x, y in zip(d, flat)):
+                sp = _perturbed_spread(st0[i], cmd[i].astype(np.float64), cd, caches[i], dyn64[i], iters, (ref, f_np), rng, k, solver)
+                sp = sp + (sp[3],)
+                bb = tuple(max(x, SENS_FACTOR * y) for x, y in zip(flat, sp))
+                escapes += 1
+            assert all(x <= y for x, y in zip(d, bb)), (path, t, i, int(cls[i]), fmax, d, bb)
+            for key, x, y in zip(worst, d, flat):
+                worst[key] = max(worst[key], x / y)
             seen_cls.add(int(cls[i]))
             checked += 1
+            touch_loaded += int((touch[i] > 1.0).sum())
             pairs |= {(cls_name(int(c[0])), cls_name(int(c[1]))) for c, l in zip(cd, res['lambda_n']) if l > 0}
             limit_active += sum(1 for r, l in zip(res['rows'], res['lam']) if r[0] == 'limit' and l > 0)
-            controls.append((i, st0[i], cmd[i], cd, caches[i], st1[i], b))
-    print("%s: %d checks; worst deviation / flat bound: joints %.3f, object pose %.3f, object velocity %.3f; pairs %s; %d active limit rows"
-          % (path, checked, worst[0], worst[1], worst[2], sorted(pairs), limit_active))
+            controls.append((i, st0[i], cmd[i], cd, caches[i], st1[i], bb, touch[i], f_np))
+    print("objects=%d %s N=%d: %d checks, classes %s; worst deviation / flat bound: joints %.3f, object pose %.3f, object velocity "
+          "%.3f, normal force %.3f, touch %.3f (%d over a flat bound, held to %.0f x numpy's one-ulp spread); %d touch readings "
+          "above 1 N; pairs %s; %d active limit rows; %d envs diverged (flagged, not checked)"
+          % (k, path, N, checked, sorted(seen_cls), worst['joints'], worst['pose'], worst['velocity'], worst['force'], worst['touch'],
+             escapes, SENS_FACTOR, touch_loaded, sorted(pairs), limit_active, len(diverged)))
     assert seen_cls == occurred and len(occurred) >= 2, (seen_cls, occurred)
-    if path in ('default', 'scalar_prep', 'no_split'):
+    if path in ('default', 'scalar_prep', 'no_split') and original:
         assert occurred == {0, 1, 2}
     assert {('robot', 'object'), ('object', 'static')} <= pairs, pairs
-    if path != 'iters1':               # (one sweep per step drives another trajectory: no pile, no limit contact at these steps)
-        assert ('object', 'object') in pairs and limit_active > 0, (pairs, limit_active)
+    if path != 'iters1' and k >= 2:    # (one sweep per step drives another trajectory: no pile at these steps)
+        assert ('object', 'object') in pairs, pairs
+    if original and path != 'iters1':     # (nor a limit contact)
+        assert limit_active > 0, limit_active
+    assert touch_loaded >= 20, touch_loaded
+
     # negative controls on the checked cases: each slip must push some case far outside its bound
     def control(**kw):
         worst_c = 0.0
-        for i, s0, c, cd, prev, s1, b in controls:
+        for i, s0, c, cd, prev, s1, b, tch, f_np in controls:
             dn = dyn64[(i + 1) % N] if kw.get('neighbour') else dyn64[i]
-            r = ns.step(s0.astype(np.float64), c.astype(np.float64), cd, dyn=dn, prev=prev, solver_iters=iters, drop=kw.get('drop', ()))
-            worst_c = max(worst_c, max(x / y for x, y in zip(_dev(s1, r['state']), b)))
+            r = ns.step(s0.astype(np.float64), c.astype(np.float64), cd, dyn=dn, prev=prev, solver=kw.get('solver', solver),
+                        solver_iters=iters, nobj=k, drop=kw.get('drop', ()))
+            worst_c = max(worst_c, max(x / y for x, y in zip(_dev(s1, r['state'], k), b)))
         return worst_c
-    ratios = {'coriolis': control(drop=('coriolis',)), 'neighbour dynamics': control(neighbour=True)}
+
+    def touch_control(**kw):
+        worst_c, bad = 0.0, 0
+        for i, s0, c, cd, prev, s1, b, tch, f_np in controls:
+            dev = np.abs(tch - ns.touch_sensors(cd, f_np, **kw)).max()
+            worst_c = max(worst_c, dev / b[3])
+        return worst_c
+
+    ratios = {'coriolis': control(drop=('coriolis',)), 'neighbour dynamics': control(neighbour=True),
+              'skin order permuted': touch_control(order=SKIN_SWAP)}
+    # table contacts count (the reference's object_names holds the table): asserted where a skin's reading is a static contact's
+    table_loaded = sum(int((ns.touch_sensors(cd, f_np) > np.maximum(ns.touch_sensors(cd, f_np, statics=False), 1.0)).any())
+                       for _, _, _, cd, _, _, _, _, f_np in controls)
+    if table_loaded:
+        ratios['static contacts left out'] = touch_control(statics=False)
     if path == 'iters1':
         ratios['reversed normals'] = control(drop=('reverse_normals',))
-    print("%s: negative controls, worst deviation / bound: %s" % (path, ratios))
+    if solver is not None:
+        ratios['default parameters'] = control(solver={})
+    # (the 0.1 m contact threshold of robot.py:136 cannot bind here: no contact this pipeline makes is 0.1 m deep -- the deepest
+    # point of the thickest static shape, the 0.2 m table base, is 0.1 m from its surface, the other shapes are thinner -- so the
+    # rule without it gives the same sensors; that is checked, not assumed)
+    inert = touch_control(threshold=None)
+    deep = sum(int((np.abs(cd[:, 9]) >= ns.CONTACT_THRESHOLD).sum()) for _, _, _, cd, *_ in controls)
+    print("objects=%d %s N=%d: negative controls, worst deviation / bound: %s; threshold dropped: %.3f (%d contacts at 0.1 m or "
+          "deeper); %d checks with a skin loaded by the table; %.1f s" % (k, path, N, ', '.join('%s %.1f' % kv for kv in ratios.items()),
+                                                              inert, deep, table_loaded, time.time() - t_start))
     assert min(ratios.values()) > 10.0, ratios
+    assert deep == 0 and inert <= 1.0, (deep, inert)
     env.close()

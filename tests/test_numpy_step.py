@@ -32,9 +32,9 @@ def _goto(o, xyz, grip, n):
     return cmd
 
 
-def _scene_grasp():
+def _scene_grasp(nobj=3):
     """1: the gripper closed on the cube, lifting it."""
-    o = Oracle(3, 32, 32)
+    o = Oracle(nobj, 32, 32)
     for _ in range(100):
         o.step(None)
     _goto(o, [-0.1, 0, 0.55], [0.5, 0], 150)
@@ -93,7 +93,25 @@ def _scene_free():
     return o, rng.uniform(-1, 1, 9) * [1, 1, 1, 1, 1, 1, 1, 0, 0] + [0, 0, 0, 0, 0, 0, 0, 0.4, 0.3]
 
 
-SCENES = {'grasp': _scene_grasp, 'press': _scene_press, 'pile': _scene_pile, 'limit': _scene_limit, 'free': _scene_free}
+def _scene_grasp1():
+    """6: scene 1 with the cube alone (one object: no object x object pair, and the lifted cube touches nothing static)."""
+    return _scene_grasp(1)
+
+
+def _scene_pile2():
+    """7: two objects: the tomato dropped onto the cube, then a finger pressing it down against the cube's side."""
+    o = Oracle(2, 32, 32)
+    o.set_object_pose(1, [-0.1, 0.0, 0.40, 0, 0, 0, 1])
+    o.set_object_pose(0, [-0.1, 0.0, 0.32, 0, 0, 0, 1])
+    for _ in range(150):
+        o.step(None)
+    _goto(o, [-0.1, 0.0, 0.6], [0, 0], 120)
+    return o, _goto(o, [-0.1, 0.0, 0.52], [0, 0], 60)
+
+
+SCENES = {'grasp': _scene_grasp, 'press': _scene_press, 'pile': _scene_pile, 'limit': _scene_limit, 'free': _scene_free,
+          'grasp1': _scene_grasp1, 'pile2': _scene_pile2}
+NOBJ = {'grasp1': 1, 'pile2': 2}          # objects of a scene (the others: 3)
 _cache = {}
 
 
@@ -101,6 +119,7 @@ def scene(name):
     """(state, contact history, action) of a scene, built once."""
     if name not in _cache:
         o, cmd = SCENES[name]()
+        assert o.n_objects == NOBJ.get(name, 3)
         _cache[name] = (o.state.copy(), o.contacts(), np.asarray(cmd, dtype=np.float64))
     return _cache[name]
 
@@ -123,26 +142,30 @@ VARIANTS = variants()
 
 
 def oracle_step(monkeypatch, name, variant):
-    """The float64 oracle on the variant's patched model: one step from the scene -> (post-step state, contact records)."""
+    """The float64 oracle on the variant's patched model: one step from the scene -> (post-step state, contact records).  (The
+    variants' rows are [3, 8]; a scene with fewer objects uses the leading ones.)"""
     dyn, solver, iters = VARIANTS[variant]
     st, prev, cmd = scene(name)
     with monkeypatch.context() as m:
         m.setattr(oracle_mod, 'model_blob', lambda b=patched_blob(dyn): b)
-        o = Oracle(3, 32, 32, solver_iters=iters, **params_from_solver(solver))
+        o = Oracle(NOBJ.get(name, 3), 32, 32, solver_iters=iters, **params_from_solver(solver))
     o.state = st
     o.set_contact_cache(prev)
     o.step(cmd)
     return o.state.copy(), o.contacts()
 
 
-def numpy_step(name, variant, contacts, **kw):
-    dyn, solver, iters = VARIANTS[variant]
+def numpy_step(name, variant, contacts, dyn=None, **kw):
+    drow, solver, iters = VARIANTS[variant]
     st, prev, cmd = scene(name)
-    return ns.step(st, cmd, contacts, dyn=dyn.astype(np.float64), prev=prev, solver=solver, solver_iters=iters, **kw)
+    k = NOBJ.get(name, 3)
+    dyn = drow if dyn is None else dyn
+    return ns.step(st, cmd, contacts, dyn=dyn[:k].astype(np.float64), prev=prev, solver=solver, solver_iters=iters, nobj=k, **kw)
 
 
 def deviation(a, b):
-    """(worst velocity difference, worst pose difference) of two 61-states."""
+    """(worst velocity difference, worst pose difference) of two 61-states (every object slot: an absent object's must pass
+    through unchanged on both sides)."""
     d = np.abs(np.asarray(a) - np.asarray(b))
     v = np.concatenate([d[11:22], d[22:].reshape(3, 13)[:, 7:].ravel()])
     p = np.concatenate([d[:11], d[22:].reshape(3, 13)[:, :7].ravel()])
@@ -158,7 +181,8 @@ def kinds(res, contacts):
 
 
 EXPECT = {'grasp': {('robot', 'object'), ('object', 'static')}, 'press': {('robot', 'object'), ('object', 'static')},
-          'pile': {('robot', 'object'), ('object', 'object'), ('object', 'static')}, 'limit': set(), 'free': set()}
+          'pile': {('robot', 'object'), ('object', 'object'), ('object', 'static')}, 'limit': set(), 'free': set(),
+          'grasp1': {('robot', 'object')}, 'pile2': {('robot', 'object'), ('object', 'object'), ('object', 'static')}}
 
 
 def test_fk_matches_urdf_fixture():
@@ -221,36 +245,40 @@ def test_one_step_matches_the_numpy_step(monkeypatch, name, variant):
     assert np.array_equal(res['mat'][:, 0], co[:, 11])              # mu: the same products of the same float32 inputs
     act, pairs = kinds(res, co)
     assert EXPECT[name] <= pairs, pairs
-    if name == 'grasp':                                              # both finger links carry impulse
+    k = NOBJ.get(name, 3)
+    assert np.array_equal(res['state'][22 + 13 * k:], scene(name)[0][22 + 13 * k:])      # absent objects' slots: untouched
+    if name in ('grasp', 'grasp1'):                                  # both finger links carry impulse
         fingers = {int(c[0]) for c, l in zip(co, res['lambda_n']) if l > 1e-9 and 0 <= c[0] < 16}
         assert {7, 8} & fingers and {9, 10} & fingers, fingers
     if name == 'limit':
         assert 'limit' in act and not any(0 <= c[0] < 16 for c in co)
     if name == 'free':
         assert not any(0 <= c[0] < 16 for c in co) and not len(co)
-    if name in ('grasp', 'press', 'pile') and variant != 'iters1':
+    if name in ('grasp', 'press', 'pile', 'grasp1', 'pile2') and variant != 'iters1':
         assert {'normal', 'friction', 'torsional'} <= act, act
 
 
 def test_negative_controls_move_the_result():
-    """Each of these slips moves the numpy step far from the oracle: the check above can see them."""
+    """Each of these slips moves the numpy step far from the oracle: the check above can see them (with one, two and three
+    objects)."""
     mp = pytest.MonkeyPatch()
+    ratios = {}
     try:
         st1, co = oracle_step(mp, 'free', 'default')
-        assert deviation(numpy_step('free', 'default', co, drop=('coriolis',))['state'], st1)[0] > CONTROL * TOL_V
-        assert deviation(numpy_step('free', 'default', co, drop=('gyroscopic',))['state'], st1)[0] > CONTROL * TOL_V
-        for name in ('grasp', 'pile'):
+        ratios['free/coriolis'] = deviation(numpy_step('free', 'default', co, drop=('coriolis',))['state'], st1)[0] / TOL_V
+        ratios['free/gyroscopic'] = deviation(numpy_step('free', 'default', co, drop=('gyroscopic',))['state'], st1)[0] / TOL_V
+        for name in ('grasp', 'pile', 'grasp1', 'pile2'):
             st1, co = oracle_step(mp, name, 'heavy_aniso')
-            dyn, solver, iters = VARIANTS['heavy_aniso']
-            s, prev, cmd = scene(name)
-            swapped = ns.step(s, cmd, co, dyn=np.roll(dyn, 1, axis=0).astype(np.float64), prev=prev)     # a neighbour's row
-            assert deviation(swapped['state'], st1)[0] > CONTROL * TOL_V, name
+            rolled = np.roll(VARIANTS['heavy_aniso'][0], 1, axis=0)          # a neighbour's row (one object: the mustard's)
+            ratios[name + '/neighbour row'] = deviation(numpy_step(name, 'heavy_aniso', co, dyn=rolled)['state'], st1)[0] / TOL_V
             st1, co = oracle_step(mp, name, 'iters1')
-            assert deviation(numpy_step(name, 'iters1', co, drop=('reverse_normals',))['state'], st1)[0] > CONTROL * TOL_V, name
+            ratios[name + '/reversed normals'] = deviation(numpy_step(name, 'iters1', co, drop=('reverse_normals',))['state'], st1)[0] / TOL_V
             st1, co = oracle_step(mp, name, 'default')
-            assert deviation(numpy_step(name, 'default', co, drop=('torsional',))['state'], st1)[0] > CONTROL * TOL_V, name
+            ratios[name + '/torsional'] = deviation(numpy_step(name, 'default', co, drop=('torsional',))['state'], st1)[0] / TOL_V
     finally:
         mp.undo()
+    print("negative controls, worst |dv| / TOL_V: " + ', '.join('%s %.1e' % kv for kv in ratios.items()))
+    assert min(ratios.values()) > CONTROL, ratios
 
 
 def test_warm_start_pairs_with_the_previous_step():
