@@ -179,6 +179,32 @@ int rr_set_camera(rr_env *env, const float *view16, const float *proj16);
  * returns the handle to one camera for all envs.  Cameras are settings of the handle, not env state: rr_reset, rr_set_state,
  * rr_set_object_pose(s) and rr_checkpoint_restore keep them, checkpoints do not carry them.  Synchronous. */
 int rr_set_env_cameras(rr_env *env, const float *views16, const float *projs16, const uint8_t *env_mask_host);
+/* Per-env appearance (additive in ABI 7; pybullet's changeVisualShape(rgbaColor=...) and getCameraImage(lightDirection=...)):
+ * the envs whose mask byte is non-zero (NULL: all) get their own colour for every render instance and / or their own light
+ * direction.  colours: f32 [N][n_inst][3] host or NULL (keep); light_dirs: f32 [N][3] host or NULL (keep); rows of unmasked envs
+ * are not read.  n_inst and what each instance belongs to: rr_render_instances.  A colour replaces the model's colour of that
+ * instance for that env: the pixel stays floor(texel * colour * shade), clamped to 255.  A light direction replaces
+ * l = (-50, 30, 100) / |.| in shade = 0.6 + 0.35 max(n.l, 0) + 0.05 max(r_z, 0)^2; it points from the scene towards the light and
+ * is normalised in float32 on the host, once.  Colours of a masked env must be finite and >= 0, its light finite with a float32
+ * norm that is finite and > 1e-6; otherwise RR_EINVAL (the message names the env) and no env changes.  All three pointers NULL:
+ * back to the model's appearance for every env (a mask alone is RR_EINVAL).
+ * Does not render: a masked env keeps its last frame until its own next render, which shows the whole env in its new appearance --
+ * static instances and movable instances that did not move included.  The envs outside the mask are not touched.
+ * Appearance needs an env's own static layer, as rr_set_env_cameras does: the same buffers (19 bytes per pixel per env), allocated
+ * by whichever of the two calls comes first.  With an appearance in force rr_set_camera gives every env that one camera and keeps
+ * the per-env layers; rr_set_env_appearance(env, NULL, NULL, NULL) with no per-env cameras in force returns to the shared layer.
+ * A setting of the handle like the cameras: rr_reset, rr_set_state, rr_set_object_pose(s) and rr_checkpoint_restore keep it,
+ * checkpoints do not carry it.  Synchronous.
+ * Out of scope: the ambient / diffuse / specular coefficients (0.6, 0.35, 0.05 stay literals), a light colour of its own (a common
+ * factor on the colours does it), the background colour, per-env textures, transparency (there is no alpha). */
+int rr_set_env_appearance(rr_env *env, const float *colours, const float *light_dirs, const uint8_t *env_mask_host);
+/* What is in force: colours_out f32 [N][n_inst][3], light_dirs_out f32 [N][3] (unit vectors), either may be NULL.  On a fresh handle:
+ * the model's instance colours and the default light. */
+int rr_get_env_appearance(rr_env *env, float *colours_out, float *light_dirs_out);
+/* The render instances of the model: *n_inst of them; owner_out (i32 [n_inst][4] or NULL) gets {owner type 0 static / 1 robot body /
+ * 2 object, index of that body or object, uid (the value in RR_F_MASK), texture index or -1} of each.  The trailing instances of
+ * the objects that a handle with n_objects < 3 does not draw have a row too (their colours are stored, never read). */
+int rr_render_instances(rr_env *env, int32_t *n_inst, int32_t *owner_out);
 
 /* Device pointer + size of an observation/state buffer (valid until rr_destroy). */
 int rr_get_buffer(rr_env *env, int32_t field, void **dev_ptr, size_t *bytes);

@@ -32,7 +32,7 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_step_plan', 'rr_set_camera', 'rr_set_object_poses', 'rr_step_plan_masked', 'rr_checkpoint_bytes',
            'rr_checkpoint_save', 'rr_checkpoint_restore', 'rr_evaluate_goals', 'rr_device_microbench', 'rr_map_observations', 'rr_map_images', 'rr_sync_observations', 'rr_select_image_mirror',
            'rr_pack_image_delta', 'rr_apply_image_delta', 'rr_set_object_dynamics', 'rr_get_object_dynamics',
-           'rr_set_env_cameras')
+           'rr_set_env_cameras', 'rr_set_env_appearance', 'rr_get_env_appearance', 'rr_render_instances')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 
@@ -129,6 +129,9 @@ def load_library():
     L.rr_step_plan.argtypes = [vp, i32, vp]
     L.rr_set_camera.argtypes = [vp, vp, vp]
     L.rr_set_env_cameras.argtypes = [vp, vp, vp, vp]
+    L.rr_set_env_appearance.argtypes = [vp, vp, vp, vp]
+    L.rr_get_env_appearance.argtypes = [vp, vp, vp]
+    L.rr_render_instances.argtypes = [vp, C.POINTER(i32), vp]
     L.rr_set_object_poses.argtypes = [vp, vp, vp]
     L.rr_step_plan_masked.argtypes = [vp, vp, i32, vp]
     L.rr_evaluate_goals.argtypes = [vp, vp, vp, vp]

@@ -47,6 +47,7 @@ class BatchedREALRobotEnv:
         nat.check(self.L.rr_get_buffer(self.h, nat.F_FRAG_COUNT, C.byref(p_), C.byref(n_)))
         self._shapes[nat.F_FRAG_COUNT] = ((self.N, max(1, n_.value // (4 * self.N))), np.uint32)
         self._dyn_default = self._dynamics_raw()           # a fresh handle holds the model's object dynamics
+        self._app_default = self.env_appearance()          # ... and the model's appearance
 
     def map_images(self, mask=True):
         """Pinned host copies of the images that every rendered step refreshes (rr_map_images; a handful of envs only): numpy views
@@ -392,6 +393,80 @@ class BatchedREALRobotEnv:
             if m.shape != (N,):
                 raise ValueError("env_mask must have shape (%d,)" % N)
         nat.check(self.L.rr_set_env_cameras(self.h, v.ctypes.data, p.ctypes.data, m.ctypes.data if m is not None else None))
+
+    # ------------------------------------------------------------------ appearance (changeVisualShape / lightDirection)
+    def render_instances(self):
+        """The render instances of the model (rr_render_instances): int32 [n_inst, 4] rows {owner type 0 static / 1 robot body /
+        2 object, index of that body or object, uid (the value in the mask image), texture index or -1}.  Instances of objects
+        that this handle does not draw (objects < 3) have a row too."""
+        n = C.c_int32()
+        nat.check(self.L.rr_render_instances(self.h, C.byref(n), None))
+        out = np.empty((n.value, 4), np.int32)
+        nat.check(self.L.rr_render_instances(self.h, C.byref(n), out.ctypes.data))
+        return out
+
+    def _n_inst(self):
+        if getattr(self, '_n_inst_cached', None) is None:
+            n = C.c_int32()
+            nat.check(self.L.rr_render_instances(self.h, C.byref(n), None))
+            self._n_inst_cached = int(n.value)
+        return self._n_inst_cached
+
+    def env_appearance(self):
+        """Every env's appearance in force: {'colours': float32 [N, n_inst, 3], 'light_dirs': float32 [N, 3] (unit vectors)}."""
+        col = np.empty((self.N, self._n_inst(), 3), np.float32)
+        light = np.empty((self.N, 3), np.float32)
+        nat.check(self.L.rr_get_env_appearance(self.h, col.ctypes.data, light.ctypes.data))
+        return {'colours': col, 'light_dirs': light}
+
+    def default_env_appearance(self):
+        """The model's appearance (what a fresh handle has), same layout as `env_appearance()`."""
+        return {k: v.copy() for k, v in self._app_default.items()}
+
+    def set_env_appearance(self, colours=None, light_dirs=None, env_mask=None):
+        """Per-env appearance (rr_set_env_appearance; pybullet's changeVisualShape(rgbaColor=...) and getCameraImage(
+        lightDirection=...)).  colours broadcasts to [N, n_inst, 3] -- the colour that replaces the model's for every render
+        instance (`render_instances()` tells what each belongs to), finite and >= 0, no alpha; light_dirs broadcasts to [N, 3] --
+        the direction towards the light, finite and longer than 1e-6, normalised by the library; None keeps what is in force.
+        env_mask (uint8 / bool [N], None: all envs) selects the envs that change.  Anything else raises ValueError before the
+        library is called, and nothing changes.  All three None: back to the model's appearance for every env.
+        Does not render: a masked env keeps its last frame until its next render, which shows the whole env in its new appearance.
+        The appearance outlives reset(), `state = ...`, teleports and restore(); set_camera keeps it.  A sharded batch gathers
+        full image slabs after this call, as after set_camera."""
+        N = self.N
+        if colours is None and light_dirs is None:
+            if env_mask is not None:
+                raise ValueError("set_env_appearance: an env_mask needs colours or light_dirs")
+            nat.check(self.L.rr_set_env_appearance(self.h, None, None, None))
+            return
+
+        def arg(v, name, shape):
+            try:
+                with np.errstate(over='ignore'):
+                    a = np.broadcast_to(np.asarray(v, dtype=np.float64).astype(np.float32), shape)
+            except (ValueError, TypeError):
+                raise ValueError("%s: cannot broadcast an array of shape %s to %s" % (name, np.shape(v), shape))
+            if not np.isfinite(a).all():
+                raise ValueError("%s must be finite (in float32)" % name)
+            return np.ascontiguousarray(a)
+        c = l = None
+        if colours is not None:
+            c = arg(colours, 'colours', (N, self._n_inst(), 3))
+            if (c < 0).any():
+                raise ValueError("colours must be >= 0")
+        if light_dirs is not None:
+            l = arg(light_dirs, 'light_dirs', (N, 3))
+            with np.errstate(over='ignore'):
+                n2 = (l * l).sum(-1, dtype=np.float32)
+            if not np.isfinite(n2).all() or not (np.sqrt(n2) > 1e-6).all():
+                raise ValueError("light_dirs must be longer than 1e-6 (and their float32 norm finite)")
+        m = None
+        if env_mask is not None:
+            m = np.ascontiguousarray(env_mask).astype(np.uint8)
+            if m.shape != (N,):
+                raise ValueError("env_mask must have shape (%d,)" % N)
+        nat.check(self.L.rr_set_env_appearance(self.h, c.ctypes.data if c is not None else None, l.ctypes.data if l is not None else None,
+                                               m.ctypes.data if m is not None else None))
 
     def set_timing(self, on):
         nat.check(self.L.rr_set_timing(self.h, int(on)))

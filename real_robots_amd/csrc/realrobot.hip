@@ -188,6 +188,9 @@ struct DevPtrs {
     unsigned char *static_rgb; float *static_depth; int *static_mask;   // [H*W] shaded static layer (shared by all envs), or [N][H*W] with per-env cameras
     size_t static_stride;   // pixels between the static layers of two envs: 0 (one layer for all envs) or H*W (per-env cameras)
     const float *env_cam;   // [N][cam_floats(ntiles)] per-env cameras {VP, plane_norm, tile_plane} (rr_set_env_cameras); nullptr: RenderModel's for all envs
+    // per-env appearance (rr_set_env_appearance); nullptr: the model's for all envs.  Both need an env's own static layer (static_stride != 0).
+    const float *env_colour;   // [N][MAXINST][3] colour of every render instance of every env, in the place of RenderModel::in_color (instance_setup_core)
+    const float *env_light;    // [N][4] unit light direction {x, y, z, 0} of every env, in the place of the literal light of shade_pixel (shade_block)
     uint2 *frag_list;       // [N*ntiles][TILE_PIX] pixels won by moving triangles: {depth bits, pixel-in-tile << 18 | triangle}
     unsigned *frag_count;   // [N*ntiles]
     // dispatch order of k_raster's workgroups (dispatch_order_class): the (env, tile) items by falling cost of the previous frame

@@ -125,6 +125,10 @@ struct rr_env {
     int *cam_sel;                  // [N] class array of the rebuild launches: 0 the envs whose layer is rebuilt (sel 1 selects them), 1 the others
     unsigned long long *env_static_vis; unsigned char *env_static_rgb; float *env_static_depth; int *env_static_mask;   // [N][H*W]
     unsigned long long *shared_static_vis; unsigned char *shared_static_rgb; float *shared_static_depth; int *shared_static_mask;   // [H*W]
+    bool cam_per_env, app_per_env; // which of the two per-env settings is in force; the per-env layers are in use (D.env_cam set) while either is
+    // per-env appearance (rr_set_env_appearance): allocated by its first call; D.env_colour / D.env_light point at them while it is in force
+    std::vector<float> colour_host, light_host;    // [N][MAXINST][3], [N][4] (unit vectors): what is uploaded, and what rr_get_env_appearance returns
+    float *colour_dev, *light_dev;
 };
 
 // The combining rule of the contact materials of two shapes (btManifoldResult::calculateCombinedFriction / Restitution /
@@ -1724,32 +1728,115 @@ int rr_step_plan(rr_env *e, int32_t render_mode, const uint8_t *render_flags_hos
     return rr_step_plan_masked(e, nullptr, render_mode, render_flags_host);
 }
 
+// ---- per-env static layers: per-env cameras (rr_set_env_cameras) and per-env appearance (rr_set_env_appearance) -------------
+// Both need an env's own static layer -- its camera projects the never-moving instances, its light shades them, its colours
+// paint them -- and share one mode: the buffers below (19 bytes per pixel per env, allocated by whichever call comes first), a
+// camera record per env (the handle's camera for every env while only the appearance is per env), and one rebuild.  The handle
+// remembers which of the two settings is in force (cam_per_env, app_per_env); the mode lasts while either holds.
+static int ensure_env_layers(rr_env *e) {
+    if (e->cam_dev) return RR_OK;
+    const int N = e->P.N, CF = cam_floats(e->RM.ntiles);
+    const size_t px = (size_t)e->RM.W * e->RM.H;
+    int rc;
+    if ((rc = dev_alloc(e, &e->cam_dev, (size_t)N * CF)) != RR_OK || (rc = dev_alloc(e, &e->cam_sel, (size_t)N)) != RR_OK ||
+        (rc = dev_alloc(e, &e->env_static_vis, (size_t)N * px, false)) != RR_OK || (rc = dev_alloc(e, &e->env_static_rgb, (size_t)N * px * 3, false)) != RR_OK ||
+        (rc = dev_alloc(e, &e->env_static_depth, (size_t)N * px, false)) != RR_OK || (rc = dev_alloc(e, &e->env_static_mask, (size_t)N * px, false)) != RR_OK) {
+        e->cam_dev = nullptr;          // (what was allocated stays on the handle's list until rr_destroy; a later call allocates again)
+        return rc;
+    }
+    e->cam_host.assign((size_t)N * CF, 0.0f);
+    return RR_OK;
+}
+static dim3 env_layer_copy_grid(const rr_env *e) {
+    const size_t px = (size_t)e->RM.W * e->RM.H;
+    return dim3(std::min(16, (int)((px / 4 + COPY_THREADS - 1) / COPY_THREADS)), std::min(e->P.N, 65535));
+}
+// the handle's camera as the record of env i
+static void env_camera_from_handle(rr_env *e, int i) {
+    const RenderModel &RM = e->RM;
+    float *rec = e->cam_host.data() + (size_t)i * cam_floats(RM.ntiles);
+    memcpy(rec + CAM_VP, RM.VP, sizeof RM.VP);
+    memcpy(rec + CAM_PN, RM.plane_norm, sizeof RM.plane_norm);
+    memcpy(rec + CAM_TP, RM.tile_plane, sizeof(float) * 8 * RM.ntiles);
+}
+// Entering the mode (no-op inside it): every env has the handle's camera and a copy of the shared static layer.
+static int enter_env_layers(rr_env *e) {
+    if (e->D.env_cam) return RR_OK;
+    const int N = e->P.N;
+    const size_t px = (size_t)e->RM.W * e->RM.H;
+    for (int i = 0; i < N; i++) env_camera_from_handle(e, i);
+    ImageOut layers;
+    layers.rgb = e->env_static_rgb; layers.depth = e->env_static_depth; layers.mask = e->env_static_mask; layers.env_stride = px;
+    const dim3 copy_grid = env_layer_copy_grid(e);
+    hipLaunchKernelGGL(k_static_copy, copy_grid, dim3(COPY_THREADS), 0, e->stream, e->RM_dev, e->D, layers, 0, N, (const unsigned char *)nullptr);
+    hipLaunchKernelGGL(k_static_vis_spread, copy_grid, dim3(COPY_THREADS), 0, e->stream, (const unsigned long long *)e->shared_static_vis, e->env_static_vis, px, N);
+    HIPCHK(hipGetLastError());
+    e->D.env_cam = e->cam_dev; e->D.static_stride = px;
+    e->D.static_vis = e->D.static_vis_out = e->env_static_vis; e->D.static_rgb = e->env_static_rgb;
+    e->D.static_depth = e->env_static_depth; e->D.static_mask = e->env_static_mask;
+    return RR_OK;
+}
+// Leaving it: every env shares the handle's camera and static layer again (the caller rebuilds that layer).
+static void leave_env_layers(rr_env *e) {
+    e->D.env_cam = nullptr; e->D.static_stride = 0;
+    e->D.static_vis = e->D.static_vis_out = e->shared_static_vis; e->D.static_rgb = e->shared_static_rgb;
+    e->D.static_depth = e->shared_static_depth; e->D.static_mask = e->shared_static_mask;
+}
+// The rebuild of the static layers of the envs whose mask byte is set (nullptr: all), from the host's camera records and whatever
+// appearance e->D points at: build_static_layer's launches over a grid of all envs, of which only the masked ones stay (class
+// array cam_sel, sel 1) -- background, instance set-up, pass-1 visibility with the env's own fragment list as scratch, shading
+// into its layer.  Their lists are emptied and, once images exist, they become stale (a full copy of their own layer at their
+// next render).  The other envs are not touched.
+static int rebuild_env_layers(rr_env *e, const uint8_t *env_mask_host, const char *who) {
+    const RenderModel &RM = e->RM;
+    const int N = e->P.N, CF = cam_floats(RM.ntiles);
+    const size_t px = (size_t)RM.W * RM.H;
+    std::vector<int> sel(N, 1);
+    std::vector<uint8_t> mask(N, 0);
+    for (int i = 0; i < N; i++)
+        if (!env_mask_host || env_mask_host[i]) { sel[i] = 0; mask[i] = 1; }
+    HIPCHK(hipMemcpyAsync(e->cam_dev, e->cam_host.data(), sizeof(float) * N * CF, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->cam_sel, sel.data(), sizeof(int) * N, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->mask_dev, mask.data(), N, hipMemcpyHostToDevice, e->stream));
+    DevPtrs Db = e->D;
+    Db.static_vis = nullptr; Db.hgflag = e->cam_sel;
+    ImageOut layers;
+    layers.rgb = Db.static_rgb; layers.depth = Db.static_depth; layers.mask = Db.static_mask; layers.env_stride = px;
+    hipLaunchKernelGGL(k_background, env_layer_copy_grid(e), dim3(256), 0, e->stream, e->RM_dev, Db, N, (const unsigned char *)e->mask_dev);
+    hipLaunchKernelGGL(k_render_setup, dim3((N * MAXINST + 63) / 64), dim3(64), 0, e->stream, e->B, e->P, e->RM_dev, Db, 1);
+    hipLaunchKernelGGL(k_raster, dim3(N, RM.ntiles), dim3(RASTER_THREADS), 0, e->stream, e->P, e->RM_dev, Db, e->n_inst_used, 1, 0, 0, 1);
+    hipLaunchKernelGGL(k_shade, dim3(N, RM.ntiles, SHADE_SPLIT), dim3(SHADE_THREADS), 0, e->stream, e->RM_dev, Db, layers, 0, 0, 1, 0, (unsigned *)nullptr);
+    hipLaunchKernelGGL(k_camera_changed, dim3((N + 255) / 256), dim3(256), 0, e->stream, e->RM_dev, e->D, N, (const unsigned char *)e->mask_dev,
+                       e->images_valid ? e->stale_dev : (unsigned char *)nullptr);
+    HIPCHK(hipGetLastError());
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return fail(RR_EDEVICE, std::string(who) + ": static layer pass failed");
+    if (e->images_valid) e->stale_any = true;
+    return RR_OK;
+}
+
 // Replaces the fixed eye camera by an arbitrary one (row-major 4x4 view and projection, OpenGL conventions) and rebuilds
-// the static layer. Used for the debug camera of render('rgb_array') (EnvCamera, env.py:470-513).
+// the static layer. Used for the debug camera of render('rgb_array') (EnvCamera, env.py:470-513).  Ends per-env cameras; with a
+// per-env appearance in force the per-env layers stay: every env gets this camera and its layer is rebuilt.
 int rr_set_camera(rr_env *e, const float *view16, const float *proj16) {
     if (!e || (!view16) != (!proj16)) return fail(RR_EINVAL, "rr_set_camera: null argument (both matrices, or neither for the default eye)");
     HIPCHK(hipSetDevice(e->cfg.device));
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->D.env_cam) {          // per-env cameras end: every env shares the handle's camera and static layer again
-        e->D.env_cam = nullptr; e->D.static_stride = 0;
-        e->D.static_vis = e->D.static_vis_out = e->shared_static_vis; e->D.static_rgb = e->shared_static_rgb;
-        e->D.static_depth = e->shared_static_depth; e->D.static_mask = e->shared_static_mask;
-    }
+    e->cam_per_env = false;
+    if (e->D.env_cam && !e->app_per_env) leave_env_layers(e);
     if (!view16) look_at_persp(e->RM.VP, e->table_pos, e->RM.W, e->RM.H);       // back to the reference's eye camera (env.py:136-141, 253-255)
     else camera_vp(view16, proj16, e->RM.VP);
     frustum_plane_norms(e->RM, e->RM.VP, e->RM.plane_norm, e->RM.tile_plane);
     HIPCHK(hipMemcpy(e->RM_dev, &e->RM, sizeof e->RM, hipMemcpyHostToDevice));
-    int rc = build_static_layer(e);
-    if (rc != RR_OK) return rc;
-    return RR_OK;
+    if (e->D.env_cam) {
+        for (int i = 0; i < e->P.N; i++) env_camera_from_handle(e, i);
+        return rebuild_env_layers(e, nullptr, "rr_set_camera");
+    }
+    return build_static_layer(e);
 }
 
-// Per-env cameras.  The first call allocates a camera record and a static layer per env; entering per-env mode starts every env
-// from the handle's camera and a copy of its static layer.  The masked envs then get their record (camera_vp and
-// frustum_plane_norms, as rr_set_camera) and their layer is rebuilt by the launches of build_static_layer over a grid of all
-// envs, of which only the masked ones stay (class array cam_sel, sel 1): background, instance set-up, pass-1 visibility with the
-// env's own fragment list as scratch, shading into its layer.  Their lists are emptied and, once images exist, they become stale
-// (a full copy of their own layer at their next render).  The other envs are not touched.
+// Per-env cameras.  Entering per-env mode starts every env from the handle's camera and a copy of its static layer.  The masked
+// envs then get their record (camera_vp and frustum_plane_norms, as rr_set_camera) and their layer is rebuilt
+// (rebuild_env_layers).  The other envs are not touched.
 int rr_set_env_cameras(rr_env *e, const float *views16, const float *projs16, const uint8_t *env_mask_host) {
     if (!e || !views16 || !projs16) return fail(RR_EINVAL, "rr_set_env_cameras: null argument");
     const int N = e->P.N;
@@ -1763,60 +1850,112 @@ int rr_set_env_cameras(rr_env *e, const float *views16, const float *projs16, co
     HIPCHK(hipStreamSynchronize(e->stream));
     const RenderModel &RM = e->RM;
     const int CF = cam_floats(RM.ntiles);
-    const size_t px = (size_t)RM.W * RM.H;
     int rc;
-    if (!e->cam_dev) {
-        if ((rc = dev_alloc(e, &e->cam_dev, (size_t)N * CF)) != RR_OK || (rc = dev_alloc(e, &e->cam_sel, (size_t)N)) != RR_OK ||
-            (rc = dev_alloc(e, &e->env_static_vis, (size_t)N * px, false)) != RR_OK || (rc = dev_alloc(e, &e->env_static_rgb, (size_t)N * px * 3, false)) != RR_OK ||
-            (rc = dev_alloc(e, &e->env_static_depth, (size_t)N * px, false)) != RR_OK || (rc = dev_alloc(e, &e->env_static_mask, (size_t)N * px, false)) != RR_OK) {
-            e->cam_dev = nullptr;          // (what was allocated stays on the handle's list until rr_destroy; a later call allocates again)
-            return rc;
-        }
-        e->cam_host.assign((size_t)N * CF, 0.0f);
-    }
-    const dim3 copy_grid(std::min(16, (int)((px / 4 + COPY_THREADS - 1) / COPY_THREADS)), std::min(N, 65535));
-    if (!e->D.env_cam) {          // entering per-env mode: every env has the handle's camera and static layer
-        for (int i = 0; i < N; i++) {
-            float *rec = e->cam_host.data() + (size_t)i * CF;
-            memcpy(rec + CAM_VP, RM.VP, sizeof RM.VP);
-            memcpy(rec + CAM_PN, RM.plane_norm, sizeof RM.plane_norm);
-            memcpy(rec + CAM_TP, RM.tile_plane, sizeof(float) * 8 * RM.ntiles);
-        }
-        ImageOut layers;
-        layers.rgb = e->env_static_rgb; layers.depth = e->env_static_depth; layers.mask = e->env_static_mask; layers.env_stride = px;
-        hipLaunchKernelGGL(k_static_copy, copy_grid, dim3(COPY_THREADS), 0, e->stream, e->RM_dev, e->D, layers, 0, N, (const unsigned char *)nullptr);
-        hipLaunchKernelGGL(k_static_vis_spread, copy_grid, dim3(COPY_THREADS), 0, e->stream, (const unsigned long long *)e->shared_static_vis, e->env_static_vis, px, N);
-        HIPCHK(hipGetLastError());
-        e->D.env_cam = e->cam_dev; e->D.static_stride = px;
-        e->D.static_vis = e->D.static_vis_out = e->env_static_vis; e->D.static_rgb = e->env_static_rgb;
-        e->D.static_depth = e->env_static_depth; e->D.static_mask = e->env_static_mask;
-    }
-    std::vector<int> sel(N, 1);
-    std::vector<uint8_t> mask(N, 0);
+    if ((rc = ensure_env_layers(e)) != RR_OK || (rc = enter_env_layers(e)) != RR_OK) return rc;
+    e->cam_per_env = true;
     for (int i = 0; i < N; i++) {
         if (env_mask_host && !env_mask_host[i]) continue;
-        sel[i] = 0; mask[i] = 1;
         float *rec = e->cam_host.data() + (size_t)i * CF;
         camera_vp(views16 + 16 * (size_t)i, projs16 + 16 * (size_t)i, rec + CAM_VP);
         frustum_plane_norms(RM, rec + CAM_VP, rec + CAM_PN, (float (*)[8])(rec + CAM_TP));
     }
-    HIPCHK(hipMemcpyAsync(e->cam_dev, e->cam_host.data(), sizeof(float) * N * CF, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->cam_sel, sel.data(), sizeof(int) * N, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->mask_dev, mask.data(), N, hipMemcpyHostToDevice, e->stream));
-    // the rebuild: build_static_layer's launches with the masked envs selected
-    DevPtrs Db = e->D;
-    Db.static_vis = nullptr; Db.hgflag = e->cam_sel;
-    ImageOut layers;
-    layers.rgb = Db.static_rgb; layers.depth = Db.static_depth; layers.mask = Db.static_mask; layers.env_stride = px;
-    hipLaunchKernelGGL(k_background, copy_grid, dim3(256), 0, e->stream, e->RM_dev, Db, N, (const unsigned char *)e->mask_dev);
-    hipLaunchKernelGGL(k_render_setup, dim3((N * MAXINST + 63) / 64), dim3(64), 0, e->stream, e->B, e->P, e->RM_dev, Db, 1);
-    hipLaunchKernelGGL(k_raster, dim3(N, RM.ntiles), dim3(RASTER_THREADS), 0, e->stream, e->P, e->RM_dev, Db, e->n_inst_used, 1, 0, 0, 1);
-    hipLaunchKernelGGL(k_shade, dim3(N, RM.ntiles, SHADE_SPLIT), dim3(SHADE_THREADS), 0, e->stream, e->RM_dev, Db, layers, 0, 0, 1, 0, (unsigned *)nullptr);
-    hipLaunchKernelGGL(k_camera_changed, dim3((N + 255) / 256), dim3(256), 0, e->stream, e->RM_dev, e->D, N, (const unsigned char *)e->mask_dev,
-                       e->images_valid ? e->stale_dev : (unsigned char *)nullptr);
-    HIPCHK(hipGetLastError());
-    if (hipStreamSynchronize(e->stream) != hipSuccess) return fail(RR_EDEVICE, "rr_set_env_cameras: static layer pass failed");
-    if (e->images_valid) e->stale_any = true;
+    return rebuild_env_layers(e, env_mask_host, "rr_set_env_cameras");
+}
+
+// ---- per-env appearance ----------------------------------------------------------------------------------------------------
+// The light every env has until it is given one: shade_light's literals, in the same float32 operations (the sum of the
+// squares is an integer, the square root and the quotient are correctly rounded on both sides): the same bits.
+static void unit_light(const float *l, float *out4) {
+#pragma clang fp contract(off)
+    const float linv = 1.0f / sqrtf(l[0] * l[0] + l[1] * l[1] + l[2] * l[2]);
+    out4[0] = l[0] * linv; out4[1] = l[1] * linv; out4[2] = l[2] * linv; out4[3] = 0.0f;
+}
+static void default_light(float *out4) {
+    const float l[3] = {-50.0f, 30.0f, 100.0f};
+    unit_light(l, out4);
+}
+static void default_appearance(rr_env *e) {
+    const int N = e->P.N;
+    e->colour_host.assign((size_t)N * MAXINST * 3, 0.0f);
+    e->light_host.assign((size_t)N * 4, 0.0f);
+    for (int i = 0; i < N; i++) {
+        memcpy(e->colour_host.data() + (size_t)i * MAXINST * 3, e->RM.in_color, sizeof e->RM.in_color);
+        default_light(e->light_host.data() + (size_t)i * 4);
+    }
+}
+
+int rr_set_env_appearance(rr_env *e, const float *colours, const float *light_dirs, const uint8_t *env_mask_host) {
+    if (!e) return fail(RR_EINVAL, "null env");
+    if (!colours && !light_dirs && env_mask_host) return fail(RR_EINVAL, "rr_set_env_appearance: an env mask without colours or light directions");
+    const int N = e->P.N, ni = e->RM.ni;
+    for (int i = 0; i < N; i++) {
+        if (env_mask_host && !env_mask_host[i]) continue;
+        if (colours)
+            for (int k = 0; k < ni * 3; k++) {
+                const float c = colours[(size_t)i * ni * 3 + k];
+                if (!std::isfinite(c) || c < 0.0f)
+                    return fail(RR_EINVAL, "rr_set_env_appearance: negative or non-finite colour of env " + std::to_string(i) + " (no env changed)");
+            }
+        if (light_dirs) {
+            const float *l = light_dirs + 3 * (size_t)i;
+            const float n2 = l[0] * l[0] + l[1] * l[1] + l[2] * l[2];      // (float32, as the normalisation: an overflow is refused here)
+            if (!std::isfinite(l[0]) || !std::isfinite(l[1]) || !std::isfinite(l[2]) || !std::isfinite(n2) || !(sqrtf(n2) > 1e-6f))
+                return fail(RR_EINVAL, "rr_set_env_appearance: light direction of env " + std::to_string(i) + " is not finite or shorter than 1e-6 (no env changed)");
+        }
+    }
+    HIPCHK(hipSetDevice(e->cfg.device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    int rc;
+    if (!colours && !light_dirs) {          // back to the model's appearance for every env
+        if (!e->app_per_env) return RR_OK;
+        e->app_per_env = false;
+        e->D.env_colour = nullptr; e->D.env_light = nullptr;
+        default_appearance(e);
+        if (e->cam_per_env) return rebuild_env_layers(e, nullptr, "rr_set_env_appearance");      // the cameras stay per env
+        leave_env_layers(e);
+        return build_static_layer(e);
+    }
+    if (!e->colour_dev) {
+        if ((rc = dev_alloc(e, &e->colour_dev, (size_t)N * MAXINST * 3, false)) != RR_OK || (rc = dev_alloc(e, &e->light_dev, (size_t)N * 4, false)) != RR_OK) {
+            e->colour_dev = nullptr;
+            return rc;
+        }
+        default_appearance(e);
+    }
+    if ((rc = ensure_env_layers(e)) != RR_OK || (rc = enter_env_layers(e)) != RR_OK) return rc;
+    e->app_per_env = true;
+    for (int i = 0; i < N; i++) {
+        if (env_mask_host && !env_mask_host[i]) continue;
+        if (colours) memcpy(e->colour_host.data() + (size_t)i * MAXINST * 3, colours + (size_t)i * ni * 3, sizeof(float) * ni * 3);
+        if (light_dirs) unit_light(light_dirs + 3 * (size_t)i, e->light_host.data() + (size_t)i * 4);
+    }
+    HIPCHK(hipMemcpyAsync(e->colour_dev, e->colour_host.data(), sizeof(float) * e->colour_host.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->light_dev, e->light_host.data(), sizeof(float) * e->light_host.size(), hipMemcpyHostToDevice, e->stream));
+    e->D.env_colour = e->colour_dev; e->D.env_light = e->light_dev;
+    return rebuild_env_layers(e, env_mask_host, "rr_set_env_appearance");
+}
+
+int rr_get_env_appearance(rr_env *e, float *colours_out, float *light_dirs_out) {
+    if (!e) return fail(RR_EINVAL, "null env");
+    const int N = e->P.N, ni = e->RM.ni;
+    float l4[4];
+    default_light(l4);
+    const bool own = !e->colour_host.empty();
+    for (int i = 0; i < N; i++) {
+        if (colours_out) memcpy(colours_out + (size_t)i * ni * 3, own ? e->colour_host.data() + (size_t)i * MAXINST * 3 : &e->RM.in_color[0][0], sizeof(float) * ni * 3);
+        if (light_dirs_out) memcpy(light_dirs_out + 3 * (size_t)i, own ? e->light_host.data() + (size_t)i * 4 : l4, sizeof(float) * 3);
+    }
+    return RR_OK;
+}
+
+int rr_render_instances(rr_env *e, int32_t *n_inst, int32_t *owner_out) {
+    if (!e || !n_inst) return fail(RR_EINVAL, "null argument");
+    const RenderModel &RM = e->RM;
+    *n_inst = RM.ni;
+    if (owner_out)
+        for (int i = 0; i < RM.ni; i++) {
+            owner_out[4 * i] = RM.in_otype[i]; owner_out[4 * i + 1] = RM.in_oidx[i]; owner_out[4 * i + 2] = RM.in_uid[i]; owner_out[4 * i + 3] = RM.in_tex[i];
+        }
     return RR_OK;
 }
 

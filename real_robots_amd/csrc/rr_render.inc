@@ -199,7 +199,20 @@ __device__ __forceinline__ bool block_may_overlap(const STri &s, float ia, int p
 // mvp / sinst: per-instance constants of this env staged in LDS by stage_instances(); sinst holds 16 floats per instance
 // {R[9], colour[3], tex_off, tex_w (0: untextured; -1: one texel, in place of the offset), tex_h, uid}, which keeps the chain of dependent global loads of a
 // shaded pixel at two (triangle record, texel).
-struct ShadeCtx { const DevPtrs *D; const float *mvp; const float *sinst; int W, H; };
+// L0..L2: the unit light direction of the (env, tile) item being shaded (shade_light): uniform in the wave.
+struct ShadeCtx { const DevPtrs *D; const float *mvp; const float *sinst; int W, H; float L0, L1, L2; };
+// The light of an env: the handle-wide default l = (-50, 30, 100) normalised, or -- per-env appearance -- the env's own unit
+// vector, one 12-byte read through the scalar cache (env is uniform in the workgroup, as for the camera record in raster_tile).
+// The host's default_light() does the default's arithmetic in the same float32 operations: same bits.
+__device__ __forceinline__ void shade_light(const DevPtrs &D, int env, ShadeCtx &c) {
+    const float Lx = -50.0f, Ly = 30.0f, Lz = 100.0f;
+    const float linv = 1.0f / sqrtf(Lx * Lx + Ly * Ly + Lz * Lz);
+    c.L0 = Lx * linv; c.L1 = Ly * linv; c.L2 = Lz * linv;
+    if (D.env_light) {
+        const float *l = D.env_light + (size_t)__builtin_amdgcn_readfirstlane(env) * 4;
+        c.L0 = l[0]; c.L1 = l[1]; c.L2 = l[2];
+    }
+}
 // one 128-byte record per triangle {pos[9], nrm[9], inst, -, uv[6]}: 16-byte loads from a single cache line instead of 26
 // scattered dwords.  Every lane shades a different triangle, and what such a load costs is vector-memory issue, not cache misses
 // (round 5 probes: the same loads from ONE record through the scalar cache take 25 of the kernel's 89 us off, from 64 L1-resident
@@ -218,9 +231,7 @@ __device__ __forceinline__ TriRec load_tri_rec(const DevPtrs &D, int t) {
 __device__ __forceinline__ void shade_pixel(const ShadeCtx &c, const TriRec &tr, int px, int row, unsigned char *rgb3, int &mask) {
     const DevPtrs &D = *c.D;
     const int W = c.W, H = c.H;
-    const float Lx = -50.0f, Ly = 30.0f, Lz = 100.0f;
-    const float linv = 1.0f / sqrtf(Lx * Lx + Ly * Ly + Lz * Lz);
-    const float L0 = Lx * linv, L1 = Ly * linv, L2 = Lz * linv;
+    const float L0 = c.L0, L1 = c.L1, L2 = c.L2;
     float rec[20];
 #pragma unroll
     for (int k = 0; k < 5; k++) { rec[4 * k] = tr.v[k].x; rec[4 * k + 1] = tr.v[k].y; rec[4 * k + 2] = tr.v[k].z; rec[4 * k + 3] = tr.v[k].w; }
@@ -1035,6 +1046,7 @@ __device__ __forceinline__ void shade_block(const RenderModel &RM, const DevPtrs
 #endif
     ShadeCtx ctx;
     ctx.D = &D; ctx.mvp = &mvp[0][0]; ctx.sinst = &sinst[0][0]; ctx.W = RM.W; ctx.H = RM.H;
+    shade_light(D, env, ctx);
     const uint2 *lst = D.frag_list + ((size_t)env * RM.ntiles + tile) * TILE_PIX;
     const int tyi = tile / RM.ntx, row0 = tyi * RM.tile_h, tx0i = (tile - tyi * RM.ntx) * RM.tile_w;
     const size_t ebase = (size_t)env * out.env_stride;

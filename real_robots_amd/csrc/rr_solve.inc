@@ -293,7 +293,9 @@ __device__ __forceinline__ void instance_setup_core(const BodyParams &B, const R
     o[3] = make_float4(mvp[12], mvp[13], mvp[14], mvp[15]);
     o[4] = make_float4(R.m[0], R.m[1], R.m[2], R.m[3]);
     o[5] = make_float4(R.m[4], R.m[5], R.m[6], R.m[7]);
-    o[6] = make_float4(R.m[8], RM.in_color[i][0], RM.in_color[i][1], RM.in_color[i][2]);
+    // the instance's colour: the model's, or this env's own (rr_set_env_appearance)
+    const float *col = D.env_colour ? D.env_colour + ((size_t)env * MAXINST + i) * 3 : RM.in_color[i];
+    o[6] = make_float4(R.m[8], col[0], col[1], col[2]);
     o[7] = make_float4(__int_as_float(tidx >= 0 ? RM.tex_off[tidx] : 0), __int_as_float(tidx >= 0 ? RM.tex_w[tidx] : 0),
                        __int_as_float(tidx >= 0 ? RM.tex_h[tidx] : 0), __int_as_float(RM.in_uid[i]));
 }

@@ -33,6 +33,15 @@ class Goal:
         self.mask = mask
 
 
+def _sync_visual_shapes(cam, env):
+    """The colours set through `env._p.changeVisualShape` belong to the simulation, not to one camera: a camera's own backend
+    (EnvCamera, EyeCamera) takes them over before its next frame."""
+    ver = getattr(env, '_visual_version', 0)
+    if ver != getattr(cam, '_visual_seen', 0):
+        cam._be.set_env_appearance(colours=env._visual_colours)
+        cam._visual_seen = ver
+
+
 class EnvCamera:
     """Debug camera of render('rgb_array') (env.py:470-513): yaw/pitch/roll view at `distance` from `pos`, fov 80,
     rendered by the same HIP rasteriser through a second single-env backend that mirrors the simulation state."""
@@ -49,6 +58,7 @@ class EnvCamera:
                                            device=env._device)
             self._be.set_camera(view_from_yaw_pitch_roll(self.pos, self.dist, self.yaw, self.pitch, self.roll),
                                 perspective(self.fov, float(self.render_width) / self.render_height, 0.1, 100.0))
+        _sync_visual_shapes(self, env)
         self._be.state = env._backend().state
         self._be.render()
         return self._be.host(nat.F_RGB)[0]
@@ -80,6 +90,7 @@ class EyeCamera:
         if key != self._view_of:
             self._be.set_camera(view, perspective(self.fov, float(self.render_width) / self.render_height, 0.1, 100.0))
             self._view_of = key
+        _sync_visual_shapes(self, env)
         self._be.state = env._backend().state
         self._be.render()
         return self._be.host(nat.F_RGB)[0], self._be.host(nat.F_MASK)[0], self._be.host(nat.F_DEPTH)[0].astype(np.float64)
@@ -99,7 +110,7 @@ class EyeCamera:
 
 class _BulletShim:
     """`env._p`: the handful of pybullet client calls that callers of the reference use on the env (videomaker.py:84,124,
-    generate_goals.py:105) and changeDynamics / getDynamicsInfo of the objects, answered from the batched backend.  Anything else
+    generate_goals.py:105), changeDynamics / getDynamicsInfo of the objects and changeVisualShape, answered from the batched backend.  Anything else
     raises AttributeError -- there is no Bullet here."""
 
     def __init__(self, env):
@@ -158,6 +169,37 @@ class _BulletShim:
             a[0, o] = v
             args[field] = a
         be.set_object_dynamics(**args)
+
+    def changeVisualShape(self, objectUniqueId, linkIndex, **kwargs):
+        """pybullet.changeVisualShape(objectUniqueId, linkIndex, rgbaColor=...) for the objects (unique ids 2..) and the table (1),
+        linkIndex -1: the colour of every render instance of that body (BatchedREALRobotEnv.set_env_appearance; it multiplies the
+        texture, as Bullet's does), seen by get_retina(), the eye cameras and render('rgb_array').  rgbaColor: (r, g, b) or
+        (r, g, b, 1) -- there is no transparency.  Any other keyword, body, link or alpha raises NotImplementedError."""
+        n = self._env._n_objects
+        uid = int(objectUniqueId)
+        if not 1 <= uid < 2 + n:
+            raise NotImplementedError("changeVisualShape: body %r -- only the table (1) and the objects (unique ids 2..%d) are supported" % (objectUniqueId, 1 + n))
+        if int(linkIndex) != -1:
+            raise NotImplementedError("changeVisualShape: link %r -- these bodies have only their base (linkIndex -1)" % (linkIndex,))
+        other = sorted(k for k in kwargs if k != 'rgbaColor')
+        if other or 'rgbaColor' not in kwargs:
+            raise NotImplementedError("changeVisualShape: unsupported keyword(s) %s (supported: rgbaColor)" % (', '.join(other) or '(none given)'))
+        rgba = np.asarray(kwargs['rgbaColor'], dtype=np.float64).reshape(-1)
+        if rgba.shape[0] not in (3, 4):
+            raise ValueError("changeVisualShape: rgbaColor needs 3 or 4 components")
+        if rgba.shape[0] == 4 and rgba[3] != 1.0:
+            raise NotImplementedError("changeVisualShape: alpha %r -- there is no transparency (alpha 1 or absent)" % (rgba[3],))
+        env = self._env
+        be = env._backend()
+        owner = be.render_instances()
+        rows = np.flatnonzero(owner[:, 2] == uid)
+        if rows.size == 0:
+            raise NotImplementedError("changeVisualShape: body %r has no render instance" % (objectUniqueId,))
+        col = be.env_appearance()['colours']
+        col[0, rows] = rgba[:3]
+        be.set_env_appearance(colours=col)              # (validates: finite, >= 0)
+        env._visual_colours = col
+        env._visual_version = getattr(env, '_visual_version', 0) + 1
 
     def getDynamicsInfo(self, bodyUniqueId, linkIndex):
         """pybullet.getDynamicsInfo for the objects, in pybullet's layout: (mass, lateral friction, local inertia diagonal, local

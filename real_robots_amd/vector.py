@@ -26,6 +26,14 @@ angles uniform in +-rotation degrees; the projection is perspective(fov, W / H, 
 the same-step autoreset, before the re-render -- from a generator of its own (the dynamics draws of a seed do not depend on it).
 The matrices in force are returned as `infos["camera"] = {"view": [N, 4, 4], "proj": [N, 4, 4]}` (float32, row-major); after an
 autoreset `infos["_camera"]` masks the envs that drew.
+Domain randomisation of the appearance: `appearance_randomization={'colour': (0.7, 1.0), 'brightness': (0.8, 1.2), 'light': 30.0}` gives
+every env its own instance colours and light direction (BatchedREALRobotEnv.set_env_appearance): the colour of every render instance
+is the model's times a multiplier uniform in `colour` per channel, times one factor per env uniform in `brightness`; the light is the
+default direction turned by an angle uniform in [0, `light`] degrees about an axis drawn uniformly among those perpendicular to it
+(missing keys: multipliers 1, angle 0).  Drawn like the cameras -- every env on reset(seed=...), the truncated envs on the same-step
+autoreset, before the re-render -- from a third generator (the dynamics and camera draws of a seed do not depend on it).  The values
+in force are returned as `infos["appearance"] = {"colours": [N, n_inst, 3], "light_dirs": [N, 3]}` (float32; unit light vectors as
+drawn, in float32); after an autoreset `infos["_appearance"]` masks the envs that drew.
 """
 import numpy as np
 
@@ -56,7 +64,7 @@ def _batch_dict_space(space, n):
 class REALRobotVectorEnv(_Base):
     def __init__(self, num_envs, objects=3, additional_obs=False, eye_width=320, eye_height=240, device=0,
                  max_episode_steps=int(15e6), render_every_step=True, device_obs=False, solver=None, dynamics_randomization=None,
-                 camera_randomization=None):
+                 camera_randomization=None, appearance_randomization=None):
         self.num_envs = int(num_envs)
         self._robot = Kuka(additional_obs, objects, eye_width, eye_height, env=None)
         self.single_action_space = spaces.Dict({"joint_command": self._robot.action_space, "render": spaces.MultiBinary(1)})
@@ -110,6 +118,32 @@ class REALRobotVectorEnv(_Base):
             self._cam_proj = np.broadcast_to(mathutil.perspective(80.0, self._cam_aspect, 0.1, 100.0).astype(np.float32),
                                              (self.num_envs, 4, 4)).copy()
         self._cam_rng = np.random.default_rng()
+        self._app_rand = None
+        if appearance_randomization:
+            ar = dict(colour=(1.0, 1.0), brightness=(1.0, 1.0), light=0.0)
+            for k, r in appearance_randomization.items():
+                if k not in ar:
+                    raise ValueError("appearance_randomization: unknown field %r (known: %s)" % (k, ', '.join(ar)))
+                if k == 'light':
+                    v = float(r)
+                    if not (np.isfinite(v) and 0 <= v <= 180):
+                        raise ValueError("appearance_randomization['light']: need a finite angle in [0, 180] (degrees)")
+                    ar[k] = v
+                else:
+                    try:
+                        lo, hi = (float(x) for x in r)
+                    except (TypeError, ValueError):
+                        raise ValueError("appearance_randomization[%r]: need a (low, high) pair" % k)
+                    if not (np.isfinite(lo) and np.isfinite(hi) and 0 <= lo <= hi):
+                        raise ValueError("appearance_randomization[%r]: need finite 0 <= low <= high" % k)
+                    ar[k] = (lo, hi)
+            self._app_rand = ar
+            d = self._be.default_env_appearance()
+            self._app_colour0 = d['colours'][0].astype(np.float64)            # the model's colours [n_inst, 3]
+            self._app_light0 = d['light_dirs'][0].astype(np.float64)
+            self._app_light0 /= np.linalg.norm(self._app_light0)
+            self._app_colours, self._app_lights = d['colours'].copy(), d['light_dirs'].copy()
+        self._app_rng = np.random.default_rng()
 
     DYNAMICS_FIELDS = ('mass', 'inertia', 'friction', 'restitution', 'rolling', 'spinning')
 
@@ -153,6 +187,23 @@ class REALRobotVectorEnv(_Base):
         self._be.set_env_cameras(self._cam_view, self._cam_proj, env_mask=mask.astype(np.uint8))
         return {"view": self._cam_view.copy(), "proj": self._cam_proj.copy()}
 
+    def _draw_appearance(self, mask):
+        """Draws new colours and lights for the envs in `mask` (bool [N]) and applies them; returns the values in force."""
+        ar, n = self._app_rand, int(mask.sum())
+        mult = self._app_rng.uniform(*ar['colour'], size=(n,) + self._app_colour0.shape)
+        bright = self._app_rng.uniform(*ar['brightness'], size=n)
+        ang = np.radians(self._app_rng.uniform(0.0, ar['light'], size=n))
+        phi = self._app_rng.uniform(0.0, 2 * np.pi, size=n)
+        d = self._app_light0
+        u = np.cross(d, [1.0, 0.0, 0.0] if abs(d[0]) < 0.9 else [0.0, 1.0, 0.0])
+        u /= np.linalg.norm(u)
+        axis = np.cos(phi)[:, None] * u + np.sin(phi)[:, None] * np.cross(d, u)      # unit vectors perpendicular to d
+        # Rodrigues' rotation of d about an axis perpendicular to it: d cos a + (axis x d) sin a
+        self._app_lights[mask] = (np.cos(ang)[:, None] * d + np.sin(ang)[:, None] * np.cross(axis, d)).astype(np.float32)
+        self._app_colours[mask] = (self._app_colour0 * mult * bright[:, None, None]).astype(np.float32)
+        self._be.set_env_appearance(colours=self._app_colours, light_dirs=self._app_lights, env_mask=mask.astype(np.uint8))
+        return {"colours": self._app_colours.copy(), "light_dirs": self._app_lights.copy()}
+
     # ------------------------------------------------------------------ observations
     def _obs(self, rendered):
         be = self._be
@@ -171,10 +222,13 @@ class REALRobotVectorEnv(_Base):
         if seed is not None:
             self._dyn_rng = np.random.default_rng(seed)
             self._cam_rng = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(1,)))
+            self._app_rng = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(2,)))
         if self._dyn_rand:
             infos["object_dynamics"] = self._draw_dynamics(np.ones(self.num_envs, bool))
         if self._cam_rand:
             infos["camera"] = self._draw_cameras(np.ones(self.num_envs, bool))
+        if self._app_rand:
+            infos["appearance"] = self._draw_appearance(np.ones(self.num_envs, bool))
         self._be.reset()
         self._steps[:] = 0
         if self.render_every_step:
@@ -210,6 +264,9 @@ class REALRobotVectorEnv(_Base):
             if self._cam_rand:
                 infos["camera"] = self._draw_cameras(truncated)
                 infos["_camera"] = truncated.copy()
+            if self._app_rand:
+                infos["appearance"] = self._draw_appearance(truncated)
+                infos["_appearance"] = truncated.copy()
             self._be.reset(truncated.astype(np.uint8))
             self._steps[truncated] = 0
             if render:
