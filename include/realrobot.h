@@ -29,7 +29,8 @@ extern "C" {
                               pybullet's defaults (motor_kp .. solver_flags, in the place of reserved[7]: same struct size); checkpoint
                               header version 3 carries them too; RR_F_PREP; rr_pack_image_delta, rr_apply_image_delta;
                               7: rr_set_object_dynamics, rr_get_object_dynamics (per-env mass, inertia and contact materials of the
-                              objects); checkpoint header version 4 carries them */
+                              objects); checkpoint header version 4 carries them; rr_set_env_cameras, rr_set_env_appearance; rr_set_env_actuators,
+                              rr_get_env_actuators (per-env motor gains, motor force and joint damping; checkpoint header version 5 carries them) */
 
 enum {
     RR_OK = 0,
@@ -145,6 +146,29 @@ int rr_set_object_dynamics(rr_env *env, const float *dyn_host, const uint8_t *en
 /* Replaces pybullet.getDynamicsInfo(uid, -1) of the objects: every env's rows, same layout, f32 [N, n_obj, 8] host. */
 int rr_get_object_dynamics(rr_env *env, float *dyn_out_host);
 
+/* Per-env actuators (additive in ABI 7): f32 [N][11][4] host, one row per (env, movable joint) in the order of q[11] of RR_F_STATE (the
+ * seven arm joints, then the four finger joints) =
+ *   {kp (positionGain), kd (velocityGain), max_force, joint damping}.
+ * Replaces pybullet.setJointMotorControl2(POSITION_CONTROL, positionGain=, velocityGain=, force=) and changeDynamics(jointDamping=) of
+ * a joint for the envs whose mask byte is non-zero (NULL: all envs; the rows of the other envs are not read).  For that env and joint
+ * the row takes the place of the handle's motor_kp, motor_kd, motor_max_force (rr_config) and of the model blob's body_damping in
+ *   v_target = kp (target - q) / dt + (1 - kd) qd,   |motor impulse| <= max_force dt,   rhs = -bias - damping qd.
+ * act_host == NULL: the masked envs return to the handle's values.  All four values must be finite and >= 0 (max_force dt finite too);
+ * 0 is a LITERAL zero here (gain off, motor off, no damping) -- unlike rr_config, where 0 selects the default.  On any violation the
+ * call returns RR_EINVAL, the message names the env and the joint, and no env changes.  Defaults on a fresh handle: the handle's
+ * motor_kp, motor_kd, motor_max_force in every row and the blob's body_damping.  The values are part of the env, not of its state:
+ * they outlive rr_reset, rr_set_state and rr_set_object_pose(s), and checkpoints carry them (a continuation is only bit for bit with
+ * the same actuators; a restore puts the checkpoint's table in force; the handle's scalars are still compared).  The next step
+ * prepares itself again (the look-ahead ran with the old damping).  Neither rr_ik nor rr_plan_macro depend on the table.
+ * Ranges are the caller's responsibility: a velocity gain below 1, or large position gains without the rate limit, can diverge under
+ * full-range commands (in the float64 oracle as on the device); RR_F_ERRFLAGS tells.  Synchronous (the source is host memory).
+ * Out of scope: per-env rate limits and joint ranges (act_maxdiff, act_min / act_max, body_limits), per-env link masses / inertias
+ * of the robot (M^-1 is per env already, the body table of the preparation is not), per-env erp / warm start / object damping,
+ * action latency.  The handle's motor constants (rr_config) keep working exactly as they do. */
+int rr_set_env_actuators(rr_env *env, const float *act_host, const uint8_t *env_mask_host);
+/* What is in force for every env, same layout, f32 [N][11][4] host. */
+int rr_get_env_actuators(rr_env *env, float *act_out_host);
+
 /* Replaces one REALRobotEnv.step_joints() (env.py:326-356) for all N envs:
  *   limitActionByJoint (env.py:314-321), control_objects_limits (env.py:257-264), Kuka.apply_action
  *   (robot.py:188-201), scene.global_step() -> stepSimulation (env.py:340), calc_state/get_touch_sensors
@@ -222,7 +246,7 @@ int rr_set_state(rr_env *env, const float *state_host);
 /* Checkpoint = everything a restore needs to continue BIT FOR BIT where the save left off: the state (with the motor targets),
  * the contact history of the warm start (contact list + normal forces of the last solved step -- Bullet's persistent manifolds
  * with their cached impulses, which pybullet.saveState / restoreState carry too), episode clocks, error flags, touch sensors,
- * the per-env object home poses and the per-env object dynamics (rr_set_object_dynamics).  Opaque host blob of
+ * the per-env object home poses, the per-env object dynamics (rr_set_object_dynamics) and the per-env actuators (rr_set_env_actuators).  Opaque host blob of
  * rr_checkpoint_bytes() bytes, valid for env handles of the same num_envs / n_objects.  (Macro plans in flight are host-side policy state and not part of it.)  save + restore + step == step, tested. */
 int rr_checkpoint_bytes(rr_env *env, size_t *bytes);
 int rr_checkpoint_save(rr_env *env, void *dst_host, size_t bytes);

@@ -32,9 +32,13 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_step_plan', 'rr_set_camera', 'rr_set_object_poses', 'rr_step_plan_masked', 'rr_checkpoint_bytes',
            'rr_checkpoint_save', 'rr_checkpoint_restore', 'rr_evaluate_goals', 'rr_device_microbench', 'rr_map_observations', 'rr_map_images', 'rr_sync_observations', 'rr_select_image_mirror',
            'rr_pack_image_delta', 'rr_apply_image_delta', 'rr_set_object_dynamics', 'rr_get_object_dynamics',
-           'rr_set_env_cameras', 'rr_set_env_appearance', 'rr_get_env_appearance', 'rr_render_instances')
+           'rr_set_env_cameras', 'rr_set_env_appearance', 'rr_get_env_appearance', 'rr_render_instances',
+           'rr_set_env_actuators', 'rr_get_env_actuators')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
+# rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
+ACT_ROW = ('kp', 'kd', 'max_force', 'damping')
+N_JOINTS = 11
 
 
 class Config(C.Structure):
@@ -144,6 +148,8 @@ def load_library():
     L.rr_apply_image_delta.argtypes = [vp, vp, i32, C.c_uint32, C.c_size_t, vp, vp, vp]
     L.rr_set_object_dynamics.argtypes = [vp, vp, vp]
     L.rr_get_object_dynamics.argtypes = [vp, vp]
+    L.rr_set_env_actuators.argtypes = [vp, vp, vp]
+    L.rr_get_env_actuators.argtypes = [vp, vp]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]

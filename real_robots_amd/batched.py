@@ -48,6 +48,7 @@ class BatchedREALRobotEnv:
         self._shapes[nat.F_FRAG_COUNT] = ((self.N, max(1, n_.value // (4 * self.N))), np.uint32)
         self._dyn_default = self._dynamics_raw()           # a fresh handle holds the model's object dynamics
         self._app_default = self.env_appearance()          # ... and the model's appearance
+        self._act_default = self._actuators_raw()          # ... and the handle's motor constants with the model's joint damping
 
     def map_images(self, mask=True):
         """Pinned host copies of the images that every rendered step refreshes (rr_map_images; a handful of envs only): numpy views
@@ -176,8 +177,8 @@ class BatchedREALRobotEnv:
 
     def checkpoint(self):
         """Opaque snapshot (numpy uint8 array) of everything a later `restore` needs to continue bit for bit: state with motor
-        targets, contact history of the warm start, episode clocks, error flags, touch sensors, object home poses and object
-        dynamics."""
+        targets, contact history of the warm start, episode clocks, error flags, touch sensors, object home poses, object
+        dynamics and actuators."""
         n = C.c_size_t()
         nat.check(self.L.rr_checkpoint_bytes(self.h, C.byref(n)))
         buf = np.empty(n.value, np.uint8)
@@ -265,6 +266,59 @@ class BatchedREALRobotEnv:
             if m.shape != (N,):
                 raise ValueError("env_mask must have shape (%d,)" % N)
         nat.check(self.L.rr_set_object_dynamics(self.h, new.ctypes.data, m.ctypes.data if m is not None else None))
+
+    # ------------------------------------------------------------------ actuators (setJointMotorControl2 gains / force, jointDamping)
+    def _actuators_raw(self):
+        out = np.empty((self.N, nat.N_JOINTS, 4), np.float32)
+        nat.check(self.L.rr_get_env_actuators(self.h, out.ctypes.data))
+        return out
+
+    @staticmethod
+    def _actuators_dict(raw):
+        return {name: raw[..., k].copy() for k, name in enumerate(nat.ACT_ROW)}
+
+    def env_actuators(self):
+        """Every env's actuators in force: dict of float32 arrays kp, kd, max_force, damping [N, 11], the joints in the order of
+        q[11] of the state (seven arm joints, then the four finger joints)."""
+        return self._actuators_dict(self._actuators_raw())
+
+    def default_env_actuators(self):
+        """The handle's values (what a fresh handle has: `solver=` in every row, the model's joint damping), same layout."""
+        return self._actuators_dict(self._act_default)
+
+    def set_env_actuators(self, kp=None, kd=None, max_force=None, damping=None, env_mask=None):
+        """Per-env, per-joint motor constants and joint damping (rr_set_env_actuators; pybullet's setJointMotorControl2(
+        positionGain=, velocityGain=, force=) and changeDynamics(jointDamping=)).  Every argument broadcasts to [N, 11] (joints in the
+        order of q[11]); None keeps what is in force.  env_mask (uint8 / bool [N], None: all envs) selects the envs that change.
+        All values must be finite and >= 0 (in float32); 0 is a literal zero -- gain off, motor off, no damping.  Anything else
+        raises ValueError naming the field before the library is called, and nothing changes.  All four None: the masked envs
+        return to the handle's values (`default_env_actuators()`).
+        The values outlive reset(), `state = ...` and teleports, and checkpoints carry them.  The ranges are the caller's
+        responsibility: kd < 1, or large kp without the rate limit, can diverge under full-range commands (the error flags tell)."""
+        N, nj = self.N, nat.N_JOINTS
+        m = None
+        if env_mask is not None:
+            m = np.ascontiguousarray(env_mask).astype(np.uint8)
+            if m.shape != (N,):
+                raise ValueError("env_mask must have shape (%d,)" % N)
+        given = [(k, name, v) for k, (name, v) in enumerate(zip(nat.ACT_ROW, (kp, kd, max_force, damping))) if v is not None]
+        cols = []
+        for k, name, v in given:
+            try:
+                with np.errstate(over='ignore'):
+                    a = np.broadcast_to(np.asarray(v, dtype=np.float64).astype(np.float32), (N, nj))
+            except (ValueError, TypeError):
+                raise ValueError("%s: cannot broadcast an array of shape %s to %s" % (name, np.shape(v), (N, nj)))
+            if not np.isfinite(a).all() or (a < 0).any():
+                raise ValueError("%s must be finite (in float32) and >= 0" % name)
+            cols.append((k, a))
+        if not cols:
+            nat.check(self.L.rr_set_env_actuators(self.h, None, m.ctypes.data if m is not None else None))
+            return
+        new = self._actuators_raw()
+        for k, a in cols:
+            new[..., k] = a
+        nat.check(self.L.rr_set_env_actuators(self.h, new.ctypes.data, m.ctypes.data if m is not None else None))
 
     def set_object_home(self, env, obj, pose7):
         """Pose object `obj` of env `env` (None: every env) returns to on reset / when it leaves the table

@@ -164,6 +164,8 @@ struct DevPtrs {
     const float *body_tab; // [NB][16] per-body constants of k_prep16's body lanes (BT_*: com, inertia, mass, joint damping, axis)
     float *obj_home;   // [NOBJ*7][N] per-env pose an object is put back to by reset / the out-of-bounds rule (robot.py:19-24, mutable there)
     const float *obj_dyn;   // [NOBJ*4][N] per-env {mass, ixx, iyy, izz} of object i in rows 4 i .. 4 i + 3 (rr_set_object_dynamics; defaults: the blob's)
+    const float *env_act;   // [4][NB][N] per-env actuators: field k of joint j in row k NB + j, fields {kp, kd, max_force * dt, joint damping} (rr_set_env_actuators;
+                            // defaults: P.kp, P.kd, P.max_impulse, the blob's body_damping): lane j of the solve / preparation kernels reads its joint's
     const float4 *pair_mat;   // [N][npairs] per-env contact materials of every collision pair {friction, restitution, rolling, spinning}, combined
                               // on the host (pair_materials in rr_host.inc) from the shapes' values and the env's object dynamics
     float4 *grows;     // [N * GP_RECS][16] generic solver rows in the slot layout, as canonical normal rows and as the blocks the sweeps stream (GP_*)

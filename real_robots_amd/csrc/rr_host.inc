@@ -118,6 +118,9 @@ struct rr_env {
     std::vector<float> shape_mat;  // [ns][4] the blob's {friction, restitution, rolling, spinning} of every collision shape
     std::vector<int> shape_obj;    // [ns] the free object a shape belongs to, -1 for the table / shelf / robot
     std::vector<int> pair_shapes;  // [npairs][2] shapes a, b of every collision pair
+    // per-env actuators (rr_set_env_actuators): the host copy every upload of D.env_act is made from, and what rr_get_env_actuators returns
+    std::vector<float> act;        // [N][NB][4] {kp, kd, max_force, joint damping}
+    float act_default[NB][4];      // the handle's row of every joint: P.kp, P.kd, the motor force of rr_config, the blob's body_damping
     // per-env cameras (rr_set_env_cameras): allocated by its first call; D.env_cam / D.static_* point at them while the handle is in
     // per-env mode, at the shared layer below otherwise (rr_set_camera)
     std::vector<float> cam_host;   // [N][cam_floats(ntiles)] host copy of every env's record
@@ -141,6 +144,7 @@ static void pair_materials(const float *a, const float *b, float *out) {
     out[3] = std::min(a[3] * b[0] + b[3] * a[0], 10.0f);
 }
 static int upload_dynamics(rr_env *e);
+static int upload_actuators(rr_env *e);
 
 // The lagged host copy of the heavy (which 0) / very heavy (which 1) list length: written to mapped pinned memory by a recent
 // step's kernels, read here without any synchronisation -- it only ever selects a launch shape or a placement, never a result
@@ -490,6 +494,13 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
         for (int s = ns - 1; s >= 0; s--) if (e->shape_obj[s] == i) memcpy(row + 4, &e->shape_mat[4 * s], 16);
         for (int n = 0; n < N; n++) memcpy(&e->dyn[((size_t)n * P.nobj + i) * 8], row, 32);
     }
+    // the default actuators of every env: the handle's motor constants, the blob's joint damping
+    for (int j = 0; j < NB; j++) {
+        const float row[4] = {P.kp, P.kd, upstream(cfg->motor_max_force, 100000.0f), B.damping[j]};
+        memcpy(e->act_default[j], row, 16);
+    }
+    e->act.resize((size_t)N * NB * 4);
+    for (int n = 0; n < N; n++) memcpy(&e->act[(size_t)n * NB * 4], e->act_default, sizeof e->act_default);
     e->pair_host.resize((size_t)N * np * 4);
     for (int n = 0; n < N; n++) memcpy(&e->pair_host[(size_t)n * np * 4], S.pair_mat, (size_t)np * 16);
 
@@ -585,6 +596,12 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
         ALLOC(od_, (size_t)NOBJ * 4 * N); ALLOC(pm_, (size_t)N * np);
         D.obj_dyn = od_; D.pair_mat = pm_;
         if ((rc = upload_dynamics(e)) != RR_OK) { rr_destroy(e); return rc; }
+    }
+    {
+        float *ea_ = nullptr;
+        ALLOC(ea_, (size_t)NB * 4 * N);
+        D.env_act = ea_;
+        if ((rc = upload_actuators(e)) != RR_OK) { rr_destroy(e); return rc; }
     }
     ALLOC(D.grows, (size_t)N * GP_RECS * 16);        // (zeroed: the dummy block / contact records stay all zero)
     ALLOC(D.cmd, (size_t)N * 9);
@@ -831,6 +848,55 @@ int rr_set_object_dynamics(rr_env *e, const float *dyn_host, const uint8_t *env_
 int rr_get_object_dynamics(rr_env *e, float *dyn_out_host) {
     if (!e || !dyn_out_host) return fail(RR_EINVAL, "null argument");
     memcpy(dyn_out_host, e->dyn.data(), e->dyn.size() * 4);
+    return RR_OK;
+}
+
+// The device table of the per-env actuators from the host copy: D.env_act, SoA with the env index innermost, the motor force as the
+// impulse bound max_force * dt (the float product rr_create makes for P.max_impulse: the default table holds that very value).  Synchronous.
+static int upload_actuators(rr_env *e) {
+    const size_t N = e->P.N;
+    std::vector<float> ea((size_t)NB * 4 * N);
+    for (int j = 0; j < NB; j++)
+        for (int k = 0; k < 4; k++)
+            for (size_t n = 0; n < N; n++) {
+                const float v = e->act[(n * NB + j) * 4 + k];
+                ea[(size_t)(k * NB + j) * N + n] = k == 2 ? v * e->P.dt : v;
+            }
+    HIPCHK(hipSetDevice(e->cfg.device));
+    e->la_valid = false;          // the look-ahead's unconstrained joint velocities were made with the old damping
+    HIPCHK(hipMemcpyAsync((void *)e->D.env_act, ea.data(), ea.size() * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));   // the source is host memory
+    return RR_OK;
+}
+
+// setJointMotorControl2(positionGain=, velocityGain=, force=) / changeDynamics(jointDamping=) of the robot's joints, per env (rows
+// {kp, kd, max_force, joint damping} in the order of q[11]).  The rows of the masked envs are checked first and the call changes
+// nothing unless all of them are valid; a null table puts the masked envs back on the handle's values.
+int rr_set_env_actuators(rr_env *e, const float *act_host, const uint8_t *env_mask_host) {
+    if (!e) return fail(RR_EINVAL, "null argument");
+    const int N = e->P.N;
+    static const char *const what[4] = {"kp", "kd", "max_force", "joint_damping"};
+    if (act_host)
+        for (int n = 0; n < N; n++) {
+            if (env_mask_host && !env_mask_host[n]) continue;
+            for (int j = 0; j < NB; j++)
+                for (int k = 0; k < 4; k++) {
+                    const float v = act_host[((size_t)n * NB + j) * 4 + k];
+                    if (!std::isfinite(v) || !(v >= 0.0f) || (k == 2 && !std::isfinite(v * e->P.dt)))
+                        return fail(RR_EINVAL, "rr_set_env_actuators: env " + std::to_string(n) + " joint " + std::to_string(j) + ": " + what[k] +
+                                                   " must be finite and >= 0");
+                }
+        }
+    for (int n = 0; n < N; n++) {
+        if (env_mask_host && !env_mask_host[n]) continue;
+        memcpy(&e->act[(size_t)n * NB * 4], act_host ? act_host + (size_t)n * NB * 4 : &e->act_default[0][0], sizeof e->act_default);
+    }
+    return upload_actuators(e);
+}
+
+int rr_get_env_actuators(rr_env *e, float *act_out_host) {
+    if (!e || !act_out_host) return fail(RR_EINVAL, "null argument");
+    memcpy(act_out_host, e->act.data(), e->act.size() * 4);
     return RR_OK;
 }
 
@@ -1364,7 +1430,7 @@ int rr_set_state(rr_env *e, const float *state_host) {
 // ---- checkpoint: everything a later restore needs to continue bit for bit ----------------------------------------------------
 // {header, state slab [72][N] (incl. motor targets), contact count [N], contact list [N][48][3] float4, normal forces [N][48],
 //  timestep [N], errflags [N], touch [N][4], object home poses [21][N], object dynamics [N][nobj][8], pair materials
-//  [N][npairs][4]}: the 61-float state of RR_F_STATE plus the contact history of the warm start (Bullet: the persistent manifolds
+//  [N][npairs][4], actuators [N][11][4] (version 5)}: the 61-float state of RR_F_STATE plus the contact history of the warm start (Bullet: the persistent manifolds
 // with their cached impulses), the episode clocks and the per-env object data.
 // The header also carries every parameter the continuation depends on: a blob restored into a handle that steps differently
 // (other dt / ERP / margin / sweeps / warm-start factor / motor gains and force / damping / rate-limit switch / object-lane
@@ -1375,7 +1441,7 @@ struct CkptHeader { char magic[8]; int32_t version, N, nobj, iters; float dt, er
 static CkptHeader ckpt_header(const rr_env *e) {
     CkptHeader hd;
     memset(&hd, 0, sizeof hd);
-    memcpy(hd.magic, "RRCKPT04", 8); hd.version = 4; hd.N = e->P.N; hd.nobj = e->P.nobj; hd.iters = e->P.iters;
+    memcpy(hd.magic, "RRCKPT05", 8); hd.version = 5; hd.N = e->P.N; hd.nobj = e->P.nobj; hd.iters = e->P.iters;
     hd.dt = e->P.dt; hd.erp = e->P.erp; hd.margin = e->P.margin; hd.warmstart = e->P.warmstart;
     hd.os_cap = e->P.os_cap; hd.edge_contacts = e->P.edge_contacts; hd.urdf_inertia = e->cfg.use_urdf_inertia;
     hd.no_rate_limit = (e->cfg.solver_flags & RR_SOLVER_NO_RATE_LIMIT) ? 1 : 0;
@@ -1385,7 +1451,7 @@ static CkptHeader ckpt_header(const rr_env *e) {
 }
 static size_t ckpt_bytes(const rr_env *e) {
     const size_t N = e->P.N;
-    return sizeof(CkptHeader) + 4 * (ST_TOTAL * N + N + N * MAXC * 12 + N * MAXC + N + N + N * 4 + NOBJ * 7 * N) + 4 * (e->dyn.size() + e->pair_host.size());
+    return sizeof(CkptHeader) + 4 * (ST_TOTAL * N + N + N * MAXC * 12 + N * MAXC + N + N + N * 4 + NOBJ * 7 * N) + 4 * (e->dyn.size() + e->pair_host.size() + e->act.size());
 }
 int rr_checkpoint_bytes(rr_env *e, size_t *bytes) {
     if (!e || !bytes) return fail(RR_EINVAL, "null argument");
@@ -1403,13 +1469,15 @@ static int ckpt_copy(rr_env *e, char *host, bool save) {
         else HIPCHK(hipMemcpyAsync(p.dev, h, p.bytes, hipMemcpyHostToDevice, e->stream));
         h += p.bytes;
     }
-    // the object dynamics: from the host copies (a restore uploads them again)
-    for (std::vector<float> *v : {&e->dyn, &e->pair_host}) {
+    // the object dynamics and the actuators: from the host copies (a restore uploads them again)
+    for (std::vector<float> *v : {&e->dyn, &e->pair_host, &e->act}) {
         if (save) memcpy(h, v->data(), v->size() * 4);
         else memcpy(v->data(), h, v->size() * 4);
         h += v->size() * 4;
     }
-    return save ? RR_OK : upload_dynamics(e);
+    if (save) return RR_OK;
+    const int rc = upload_dynamics(e);
+    return rc != RR_OK ? rc : upload_actuators(e);
 }
 int rr_checkpoint_save(rr_env *e, void *dst_host, size_t bytes) {
     if (!e || !dst_host) return fail(RR_EINVAL, "null argument");

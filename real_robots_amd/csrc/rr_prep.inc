@@ -200,7 +200,7 @@ __device__ __forceinline__ void prep_body(const BodyParams &B, const SimParams &
     }
     float rhs[NB], qdd[NB];
 #pragma unroll
-    for (int i = 0; i < NB; i++) { rhs[i] = -bias[i] - B.damping[i] * qd[i]; qdd[i] = 0; }
+    for (int i = 0; i < NB; i++) { rhs[i] = -bias[i] - D.env_act[(size_t)(3 * NB + i) * N + env] * qd[i]; qdd[i] = 0; }      // (the env's own joint damping: rr_set_env_actuators)
 #pragma unroll
     for (int c = 0; c < NB; c++) {
         float y[NB], xcol[NB];
@@ -356,7 +356,8 @@ __device__ __forceinline__ void prep16_body(const BodyParams &B, const SimParams
     const float4 t0 = bt[0], t1 = bt[1], t2 = bt[2], t3 = bt[3];
     const v3 com_l = mk(t0.x, t0.y, t0.z);
     const float inertia_l[6] = {t0.w, t1.x, t1.y, t1.z, t1.w, t2.x};
-    const float mass_l = t2.y, damp_l = t2.z;
+    const float mass_l = t2.y;
+    const float damp_l = D.env_act[(size_t)(3 * NB + lb) * N + env];      // the env's own joint damping (rr_set_env_actuators; BT_DAMP is the blob's)
     const v3 axis_l = mk(t2.w, t3.x, t3.y);
     // ---- the local rotation of this lane's joint, to LDS for the chain
     {

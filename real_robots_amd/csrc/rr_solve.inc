@@ -431,6 +431,9 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
     myobj.vs = mk(SCR(S_OVS + 3 * ob_l), SCR(S_OVS + 3 * ob_l + 1), SCR(S_OVS + 3 * ob_l + 2));
     myobj.ws = mk(SCR(S_OWS + 3 * ob_l), SCR(S_OWS + 3 * ob_l + 1), SCR(S_OWS + 3 * ob_l + 2));
     myobj.imass = 1.0f / D.obj_dyn[(size_t)(4 * ob_l) * N + env];          // (the env's own mass: rr_set_object_dynamics)
+    // the lane's actuator: gains and impulse bound of its joint's motor (the env's own: rr_set_env_actuators)
+    const float *ea_l = D.env_act + ((size_t)lj * N + env);
+    const float act_kp = ea_l[0], act_kd = ea_l[(size_t)NB * N], act_imp = ea_l[(size_t)(2 * NB) * N];
     // ---- the command part of the step -- everything that needs the action: limitActionByJoint (env.py:314-321), the clipping
     // and gripper coupling of Kuka.apply_action (robot.py:188-201) -> the motor target of this lane's joint; a non-finite
     // command flags the env (robot.py:189 asserts) and the env does not step.  It also APPLIES the out-of-bounds rule
@@ -472,6 +475,9 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
     // M^-1 goes to LDS (row builders, limit rows)
 #pragma unroll
     for (int i = 0; i < 8; i++) if (l + 16 * i < NB * NB) LD(L_MINV + l + 16 * i) = minv_stage[i];
+    // the lane's actuator waits in the three words of its motor row (three registers less over the row build; a coop env's four
+    // groups hold the same values and store them in the same instruction)
+    if (l < NB) { LD(L_MOT + 3 * l) = act_kp; LD(L_MOT + 3 * l + 1) = act_kd; LD(L_MOT + 3 * l + 2) = act_imp; }
     float wsA = 0.0f, wsB = 0.0f;     // slot-layout velocity change of the warm-start impulses of the generic normal rows
     // lanes 11..13 publish "their" object's data in LDS: the row builder reads the data of a contact's objects from there
     // (20 floats per object: position, 1/mass, I^-1, v*, w*)
@@ -832,10 +838,10 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
     // ---- motor + limit rows: lane j < 11 builds the rows of joint j
     if (l < NB) {
         float dinv = 1.0f / LD(L_MINV + l * NB + l);
-        float vt = P.kp * (tgt_l - q_l) / dt + qds_l + P.kd * (0.0f - qds_l);
+        const float kp_l = LD(L_MOT + 3 * l), kd_l = LD(L_MOT + 3 * l + 1);      // (the lane's own words; + 2, the impulse bound, stays for the sweeps)
+        float vt = kp_l * (tgt_l - q_l) / dt + qds_l + kd_l * (0.0f - qds_l);
         LD(L_MOT + 3 * l) = (vt - qds_l) * dinv;
         LD(L_MOT + 3 * l + 1) = dinv;
-        LD(L_MOT + 3 * l + 2) = 0.0f;
         float lo = B.limits[l][0], hi = B.limits[l][1];
 #pragma unroll
         for (int side = 0; side < 2; side++) {
@@ -863,8 +869,8 @@ __device__ __forceinline__ void solve_body(const BodyParams &B, const SimParams 
     // (1 / mass of the lane's object as its L_OBJ record holds it -- the word the light object wave reads too; an LDS read
     // instead of a register held from the stage-in.  Lanes of objects the handle does not simulate have no rows to step.)
     const float inv_mass = lo_ >= 0 ? LD(L_OBJ + 20 * (lo_ >= 0 ? lo_ : 0) + 3) : 0.0f;
-    const float max_imp = P.max_impulse;
     const float m_rhs = l < NB ? LD(L_MOT + 3 * lj) : 0.0f, m_dinv = l < NB ? LD(L_MOT + 3 * lj + 1) : 0.0f;
+    const float max_imp = l < NB ? LD(L_MOT + 3 * lj + 2) : 0.0f;       // (per lane: the clamp of the lane's own motor row, the only one whose step is kept)
     float m_lam = 0.0f, m_c = m_rhs, m_keep = 0.0f;      // m_c = lambda + rhs of this lane's motor row (brought up to date once per sweep, SWEEP_MOTORS)
 #define LDB4(r, off) (*(const float4 *)&LD(L_OSL + (r) * 12 + (off)))
 #define LDT4(r, off) (*(const float4 *)&LD(L_OST + (r) * 8 + (off)))

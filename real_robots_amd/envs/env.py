@@ -328,6 +328,25 @@ class REALRobotEnv:
                                            solver_iters=self._solver_iters, solver=self._solver)
         return self._be
 
+    def set_actuators(self, kp=None, kd=None, max_force=None, damping=None):
+        """Motor gains, motor force and joint damping of this env's robot (pybullet's setJointMotorControl2(positionGain=,
+        velocityGain=, force=) / changeDynamics(jointDamping=) per joint): scalars or arrays of 11 in the order of the state's q[11]
+        (seven arm joints, then the four finger joints -- not pybullet's joint indices); None keeps what is in force, all None
+        returns to the values of `solver=` and the model.  BatchedREALRobotEnv.set_env_actuators on env 0 of the backend handle."""
+        def row(v, name):
+            if v is None:
+                return None
+            a = np.asarray(v, dtype=np.float64)
+            if a.shape not in ((), (nat.N_JOINTS,)):
+                raise ValueError("%s must be a scalar or an array of %d, not of shape %s" % (name, nat.N_JOINTS, a.shape))
+            return a
+        self._backend().set_env_actuators(kp=row(kp, 'kp'), kd=row(kd, 'kd'), max_force=row(max_force, 'max_force'),
+                                          damping=row(damping, 'damping'))
+
+    def actuators(self):
+        """The actuators in force: dict of float32 arrays kp, kd, max_force, damping [11] (order of q[11])."""
+        return {k: v[0] for k, v in self._backend().env_actuators().items()}
+
     def _sync_object_homes(self):
         """Kuka.object_poses is a plain dict that callers of the reference edit in place (tests/test_actions.py:95-98);
         reset and the out-of-bounds rule use it (robot.py:125-129, 165-185, env.py:257-264).  Edits are pushed to the

@@ -34,6 +34,15 @@ default direction turned by an angle uniform in [0, `light`] degrees about an ax
 autoreset, before the re-render -- from a third generator (the dynamics and camera draws of a seed do not depend on it).  The values
 in force are returned as `infos["appearance"] = {"colours": [N, n_inst, 3], "light_dirs": [N, 3]}` (float32; unit light vectors as
 drawn, in float32); after an autoreset `infos["_appearance"]` masks the envs that drew.
+Domain randomisation of the actuators: `actuator_randomization={'kp': (0.8, 1.2), 'kd': (1.0, 1.2), 'max_force': (0.5, 1.0), 'damping':
+(0.5, 2.0)}` gives every env AND joint its own motor gains, motor force and joint damping (BatchedREALRobotEnv.set_env_actuators): a
+multiplier of the handle's value (`solver=`, the model's joint damping), uniform in (low, high) per field, missing fields 1.  Drawn
+like the other three -- every env on reset(seed=...), the truncated envs on the same-step autoreset -- from a fourth generator (the
+dynamics, camera and appearance draws of a seed do not depend on it).  The values in force are returned as `infos["actuators"]` (a
+dict of float32 arrays kp, kd, max_force, damping [N, 11], joints in the order of the state's q[11]); after an autoreset
+`infos["_actuators"]` masks the envs that drew.  WARNING: the ranges are the user's responsibility.  A velocity gain below 1, or large
+position gains without the rate limit (`solver={'rate_limit': False}`), can diverge under full-range commands -- in the float64
+oracle as on the device; the error flags (RR_F_ERRFLAGS) tell.
 """
 import numpy as np
 
@@ -64,7 +73,7 @@ def _batch_dict_space(space, n):
 class REALRobotVectorEnv(_Base):
     def __init__(self, num_envs, objects=3, additional_obs=False, eye_width=320, eye_height=240, device=0,
                  max_episode_steps=int(15e6), render_every_step=True, device_obs=False, solver=None, dynamics_randomization=None,
-                 camera_randomization=None, appearance_randomization=None):
+                 camera_randomization=None, appearance_randomization=None, actuator_randomization=None):
         self.num_envs = int(num_envs)
         self._robot = Kuka(additional_obs, objects, eye_width, eye_height, env=None)
         self.single_action_space = spaces.Dict({"joint_command": self._robot.action_space, "render": spaces.MultiBinary(1)})
@@ -144,6 +153,21 @@ class REALRobotVectorEnv(_Base):
             self._app_light0 /= np.linalg.norm(self._app_light0)
             self._app_colours, self._app_lights = d['colours'].copy(), d['light_dirs'].copy()
         self._app_rng = np.random.default_rng()
+        self._act_rand = None
+        if actuator_randomization:
+            self._act_rand = {}
+            for k, r in actuator_randomization.items():
+                if k not in nat.ACT_ROW:
+                    raise ValueError("actuator_randomization: unknown field %r (known: %s)" % (k, ', '.join(nat.ACT_ROW)))
+                try:
+                    lo, hi = (float(x) for x in r)
+                except (TypeError, ValueError):
+                    raise ValueError("actuator_randomization[%r]: need a (low, high) pair" % k)
+                if not (np.isfinite(lo) and np.isfinite(hi) and 0 <= lo <= hi):
+                    raise ValueError("actuator_randomization[%r]: need finite 0 <= low <= high" % k)
+                self._act_rand[k] = (lo, hi)
+            self._act_default = self._be.default_env_actuators()
+        self._act_rng = np.random.default_rng()
 
     DYNAMICS_FIELDS = ('mass', 'inertia', 'friction', 'restitution', 'rolling', 'spinning')
 
@@ -204,6 +228,21 @@ class REALRobotVectorEnv(_Base):
         self._be.set_env_appearance(colours=self._app_colours, light_dirs=self._app_lights, env_mask=mask.astype(np.uint8))
         return {"colours": self._app_colours.copy(), "light_dirs": self._app_lights.copy()}
 
+    def _draw_actuators(self, mask):
+        """Draws new multipliers for the envs in `mask` (bool [N]) and applies them; returns the values in force.  One draw of
+        [n, 11] per field, in the order kp, kd, max_force, damping, for the fields that are randomised."""
+        n = int(mask.sum())
+        args = {}
+        cur = self._be.env_actuators()
+        for f in nat.ACT_ROW:
+            if f in self._act_rand:
+                m = self._act_rng.uniform(*self._act_rand[f], size=(n, nat.N_JOINTS))
+                v = cur[f].astype(np.float64)
+                v[mask] = self._act_default[f][mask].astype(np.float64) * m
+                args[f] = v
+        self._be.set_env_actuators(env_mask=mask.astype(np.uint8), **args)
+        return self._be.env_actuators()
+
     # ------------------------------------------------------------------ observations
     def _obs(self, rendered):
         be = self._be
@@ -223,12 +262,15 @@ class REALRobotVectorEnv(_Base):
             self._dyn_rng = np.random.default_rng(seed)
             self._cam_rng = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(1,)))
             self._app_rng = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(2,)))
+            self._act_rng = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(3,)))
         if self._dyn_rand:
             infos["object_dynamics"] = self._draw_dynamics(np.ones(self.num_envs, bool))
         if self._cam_rand:
             infos["camera"] = self._draw_cameras(np.ones(self.num_envs, bool))
         if self._app_rand:
             infos["appearance"] = self._draw_appearance(np.ones(self.num_envs, bool))
+        if self._act_rand:
+            infos["actuators"] = self._draw_actuators(np.ones(self.num_envs, bool))
         self._be.reset()
         self._steps[:] = 0
         if self.render_every_step:
@@ -267,6 +309,9 @@ class REALRobotVectorEnv(_Base):
             if self._app_rand:
                 infos["appearance"] = self._draw_appearance(truncated)
                 infos["_appearance"] = truncated.copy()
+            if self._act_rand:
+                infos["actuators"] = self._draw_actuators(truncated)
+                infos["_actuators"] = truncated.copy()
             self._be.reset(truncated.astype(np.uint8))
             self._steps[truncated] = 0
             if render:
