@@ -12,10 +12,10 @@ nothing of the oracle (oracle/rr_oracle.c) or of the HIP kernels, and where it c
 * every row a dense Jacobian over the generalised velocities (11 joints, then 6 per object) against a block-diagonal inverse
   mass, solved by projected Gauss-Seidel in Bullet's order: motors, joint limits, normals, lateral frictions, torsional frictions.
 
-The narrow phase is not restated: the contact points, normals and distances of the step come in as input (records in the
-layout of the contact lists: bodyA, bodyB, linkA, x (3), n (3), dist, normal force, mu).  Every function of the preparation
-broadcasts over leading batch dimensions (prep() checks whole batches of the device's preparation record).  With fewer than three
-objects the state keeps its 61 entries: the slots of the absent objects pass through a step unchanged.
+The narrow phase is restated in tests/numpy_collide.py; here the contact points, normals and distances of the step come in as
+input (records in the layout of the contact lists: bodyA, bodyB, linkA, x (3), n (3), dist, normal force, mu).  Every function of
+the preparation broadcasts over leading batch dimensions (prep() checks whole batches of the device's preparation record).  With
+fewer than three objects the state keeps its 61 entries: the slots of the absent objects pass through a step unchanged.
 """
 import numpy as np
 
