@@ -13,6 +13,29 @@ from . import _native as nat
 OBJECT_NAMES = ['cube', 'tomato', 'mustard']       # robot.py:49-50 (after "table")
 
 
+def _env_mask(env_mask, N):
+    """env_mask of a per-env setter -> (uint8 [N] or None, its address or None); a wrong shape raises ValueError."""
+    if env_mask is None:
+        return None, None
+    m = np.ascontiguousarray(env_mask).astype(np.uint8)
+    if m.shape != (N,):
+        raise ValueError("env_mask must have shape (%d,)" % N)
+    return m, m.ctypes.data
+
+
+def _float32_arg(v, name, shape, nonneg=False):
+    """v broadcast to float32 `shape`; a shape that does not broadcast, a value that is not finite in float32 or (nonneg)
+    a negative one raises ValueError naming the field."""
+    try:
+        with np.errstate(over='ignore'):
+            a = np.broadcast_to(np.asarray(v, dtype=np.float64).astype(np.float32), shape)
+    except (ValueError, TypeError):
+        raise ValueError("%s: cannot broadcast an array of shape %s to %s" % (name, np.shape(v), shape))
+    if not np.isfinite(a).all() or (nonneg and (a < 0).any()):
+        raise ValueError("%s must be finite (in float32)%s" % (name, " and >= 0" if nonneg else ""))
+    return np.ascontiguousarray(a)
+
+
 class BatchedREALRobotEnv:
     def __init__(self, num_envs, objects=3, width=320, height=240, device=0, solver_iters=50, envs_per_block=0,
                  stream=None, use_urdf_inertia=False, dt=0.0, erp=0.0, margin=0.0, want_mask=True, solver=None):
@@ -260,12 +283,8 @@ class BatchedREALRobotEnv:
         new = new.astype(np.float32)
         if not np.isfinite(new).all() or (new[..., :4] <= 0).any():     # (an inertia scaled out of float32's range)
             raise ValueError("mass and inertia must be finite and > 0 in float32")
-        m = None
-        if env_mask is not None:
-            m = np.ascontiguousarray(env_mask).astype(np.uint8)
-            if m.shape != (N,):
-                raise ValueError("env_mask must have shape (%d,)" % N)
-        nat.check(self.L.rr_set_object_dynamics(self.h, new.ctypes.data, m.ctypes.data if m is not None else None))
+        m, mp = _env_mask(env_mask, N)
+        nat.check(self.L.rr_set_object_dynamics(self.h, new.ctypes.data, mp))
 
     # ------------------------------------------------------------------ actuators (setJointMotorControl2 gains / force, jointDamping)
     def _actuators_raw(self):
@@ -296,29 +315,16 @@ class BatchedREALRobotEnv:
         The values outlive reset(), `state = ...` and teleports, and checkpoints carry them.  The ranges are the caller's
         responsibility: kd < 1, or large kp without the rate limit, can diverge under full-range commands (the error flags tell)."""
         N, nj = self.N, nat.N_JOINTS
-        m = None
-        if env_mask is not None:
-            m = np.ascontiguousarray(env_mask).astype(np.uint8)
-            if m.shape != (N,):
-                raise ValueError("env_mask must have shape (%d,)" % N)
-        given = [(k, name, v) for k, (name, v) in enumerate(zip(nat.ACT_ROW, (kp, kd, max_force, damping))) if v is not None]
-        cols = []
-        for k, name, v in given:
-            try:
-                with np.errstate(over='ignore'):
-                    a = np.broadcast_to(np.asarray(v, dtype=np.float64).astype(np.float32), (N, nj))
-            except (ValueError, TypeError):
-                raise ValueError("%s: cannot broadcast an array of shape %s to %s" % (name, np.shape(v), (N, nj)))
-            if not np.isfinite(a).all() or (a < 0).any():
-                raise ValueError("%s must be finite (in float32) and >= 0" % name)
-            cols.append((k, a))
+        m, mp = _env_mask(env_mask, N)
+        cols = [(k, _float32_arg(v, name, (N, nj), nonneg=True))
+                for k, (name, v) in enumerate(zip(nat.ACT_ROW, (kp, kd, max_force, damping))) if v is not None]
         if not cols:
-            nat.check(self.L.rr_set_env_actuators(self.h, None, m.ctypes.data if m is not None else None))
+            nat.check(self.L.rr_set_env_actuators(self.h, None, mp))
             return
         new = self._actuators_raw()
         for k, a in cols:
             new[..., k] = a
-        nat.check(self.L.rr_set_env_actuators(self.h, new.ctypes.data, m.ctypes.data if m is not None else None))
+        nat.check(self.L.rr_set_env_actuators(self.h, new.ctypes.data, mp))
 
     def set_object_home(self, env, obj, pose7):
         """Pose object `obj` of env `env` (None: every env) returns to on reset / when it leaves the table
@@ -441,12 +447,8 @@ class BatchedREALRobotEnv:
                 raise ValueError("%s must have shape (%d, 4, 4) or (4, 4), not %s" % (name, N, a.shape))
             return np.ascontiguousarray(a)
         v, p = arg(views, 'views'), arg(projs, 'projs')
-        m = None
-        if env_mask is not None:
-            m = np.ascontiguousarray(env_mask).astype(np.uint8)
-            if m.shape != (N,):
-                raise ValueError("env_mask must have shape (%d,)" % N)
-        nat.check(self.L.rr_set_env_cameras(self.h, v.ctypes.data, p.ctypes.data, m.ctypes.data if m is not None else None))
+        m, mp = _env_mask(env_mask, N)
+        nat.check(self.L.rr_set_env_cameras(self.h, v.ctypes.data, p.ctypes.data, mp))
 
     # ------------------------------------------------------------------ appearance (changeVisualShape / lightDirection)
     def render_instances(self):
@@ -493,34 +495,19 @@ class BatchedREALRobotEnv:
                 raise ValueError("set_env_appearance: an env_mask needs colours or light_dirs")
             nat.check(self.L.rr_set_env_appearance(self.h, None, None, None))
             return
-
-        def arg(v, name, shape):
-            try:
-                with np.errstate(over='ignore'):
-                    a = np.broadcast_to(np.asarray(v, dtype=np.float64).astype(np.float32), shape)
-            except (ValueError, TypeError):
-                raise ValueError("%s: cannot broadcast an array of shape %s to %s" % (name, np.shape(v), shape))
-            if not np.isfinite(a).all():
-                raise ValueError("%s must be finite (in float32)" % name)
-            return np.ascontiguousarray(a)
         c = l = None
         if colours is not None:
-            c = arg(colours, 'colours', (N, self._n_inst(), 3))
+            c = _float32_arg(colours, 'colours', (N, self._n_inst(), 3))
             if (c < 0).any():
                 raise ValueError("colours must be >= 0")
         if light_dirs is not None:
-            l = arg(light_dirs, 'light_dirs', (N, 3))
+            l = _float32_arg(light_dirs, 'light_dirs', (N, 3))
             with np.errstate(over='ignore'):
                 n2 = (l * l).sum(-1, dtype=np.float32)
             if not np.isfinite(n2).all() or not (np.sqrt(n2) > 1e-6).all():
                 raise ValueError("light_dirs must be longer than 1e-6 (and their float32 norm finite)")
-        m = None
-        if env_mask is not None:
-            m = np.ascontiguousarray(env_mask).astype(np.uint8)
-            if m.shape != (N,):
-                raise ValueError("env_mask must have shape (%d,)" % N)
-        nat.check(self.L.rr_set_env_appearance(self.h, c.ctypes.data if c is not None else None, l.ctypes.data if l is not None else None,
-                                               m.ctypes.data if m is not None else None))
+        m, mp = _env_mask(env_mask, N)
+        nat.check(self.L.rr_set_env_appearance(self.h, c.ctypes.data if c is not None else None, l.ctypes.data if l is not None else None, mp))
 
     def set_timing(self, on):
         nat.check(self.L.rr_set_timing(self.h, int(on)))

@@ -40,78 +40,52 @@ struct Blob {
     }
 };
 
-struct rr_env {
-    hipError_t step_err; const char *step_err_what;      // first failed event / wait / bound launch of the step path (HIPQ, step_status)
-    rr_config cfg;
-    BodyParams B;
-    SimParams P;
-    RenderModel RM;
-    RenderModel *RM_dev;
-    DevPtrs D;
-    hipStream_t stream;
-    int epb;                 // envs per block for physics kernels
-    int n_inst_used;
-    size_t field_bytes[RR_F_COUNT];
-    void *field_ptr[RR_F_COUNT];
-    float *state_aos;        // [N][61] staging for RR_F_STATE
-    unsigned char *mask_dev; // [N]
-    float *link_out;         // [N][nl][7]
-    IkModel IK;
-    float *plan; int *plan_step; float *ik_in; float *ik_out; float *ik_err;   // lazily allocated (macro / cartesian adapters)
-    float *score_out; unsigned char *score_mask;                               // lazily allocated (rr_evaluate_goals)
-    std::vector<void *> allocs;
-    bool timing;
-    bool full_copy;                // RR_FULL_COPY at create: the earlier image-update scheme, the static layer copied into every image before each frame (tests)
-    int split_max_pct;             // the heavy / light split is used while at most this share of the solver groups is heavy (RR_SPLIT_MAX_PCT)
-    int *h_hcount;                 // pinned host copy of D.hcount[0] (device-mapped: written by k_prep_a of the following step)
-    bool prep_scalar;              // RR_PREP_SCALAR=1: the thread-per-env preparation kernels instead of k_prep16 (A/B, tests)
-    bool split_heavy;              // heavy solver groups + their render on the side stream (RR_NO_SPLIT=1 turns it off: A/B, tests)
-    bool images_valid;       // every env's image holds its previous frame (static layer + the pixels of its fragment list)
-    unsigned char *stale_dev;  // [N] device: the env's image predates the current static layer (rr_set_camera after its last frame)
-    bool stale_any;          // some env may be stale: every render checks (cleared by a render of all envs)
-    hipEvent_t ev[2 * RR_NUM_KERNELS];
-    hipStream_t aux;         // side stream: the HBM-bound static-layer copy runs beside the VALU-bound physics / visibility kernels
-    hipEvent_t ev_fork, ev_join, ev_dyn, ev_join2, ev_vsolved, ev_hsolved, ev_rast;
-    hipStream_t aux2;              // the very heavy envs' solve + render (RR_HEAVY2_MIN)
-    std::vector<hipStream_t> unused_streams;   // RR_SKIP_QUEUES: created only to take hardware queue ids
-    // Look-ahead (DESIGN.md 5.2): the state part of step t+1 (k_prep_ab, k_collide) runs on the side streams behind the render
-    // of the heavy / very heavy envs of step t, beside the main stream's shading.
-    struct Frame { float4 *clist; int *ccount; float *cwarm; int *hgflag, *hlist, *hcount, *hlist2, *hcount2; } fr[2];
-    int cur;                       // fr[cur]: the frame of the last solved step (rr_get_contacts, contact history); fr[cur ^ 1]: the look-ahead's
-    bool la_valid;                 // fr[cur ^ 1] and the scratch slab hold the collision pass / dynamics of the next step for the present state
-    bool lookahead;                // RR_NO_LOOKAHEAD=1: never ahead, every step prepares itself in line (A/B, tests)
-    // cost-ordered dispatch of k_raster (RR_NO_RASTER_ORDER=1: env-major grid)
-    unsigned *item_perm;           // [8 * ceil(N / 8) * ntiles] the order, written by the extra workgroups of k_shade
-    bool ord_valid, ord_pending;   // item_perm holds an order; a k_raster has left costs that the next k_shade launch turns into one
-    bool collide_ordered;          // RR_COLLIDE_ORDER=0: k_collide in env order (default: by falling duration of the env's last collision pass)
-    void *obs_host;                // rr_map_observations: mapped pinned block {joints [N][9], touch [N][4], poses [N][nobj][7], timestep [N], errflags [N]} or nullptr
-    ObsMirror obs_dev;             // its device-visible addresses
-    hipEvent_t ev_obs;             // recorded behind the mirror's launches: rr_sync_observations waits for it alone
-    bool ev_obs_set;
-    void *img_host[3];             // rr_map_images: pinned host copies of RGB / depth / mask that every rendered step refreshes (or nullptr)
-    int img_sel;                   // rr_select_image_mirror: which of them a rendered step refreshes (bit 0 RGB, 1 depth, 2 mask)
-    bool coop_all;                 // RR_COOP_ALL=0: the one-launch solve of a small batch four envs to a wave (A/B, tests)
-    // Bounded run-ahead: a caller that never waits (bench.py, a training loop reading device buffers) gets hundreds of steps ahead of the
-    // device -- the "lagged" list lengths that pick a step's placement are then those of a step 100+ steps back (measured on the macro
-    // workload: readings 1 494 / 201 heavy / very heavy envs while the device solved 1 848 / 368, and 5 % of the step time lost to a
-    // placement chosen for the smaller lists).  Every run_ahead / 2 steps rr_step records an event behind the step and first waits for
-    // the one it recorded run_ahead steps earlier: the device always has run_ahead / 2 .. run_ahead steps in its queues, the readings are
-    // that old at most, and the marker's few microseconds on the main stream are paid once in run_ahead / 2 steps (one every step cost
-    // the headline 0.7 %).  RR_RUN_AHEAD=0: unbounded.
+// Every RR_* environment variable of the library (INTEGRATION.md has the table): read_settings() is the one place that reads
+// them, once at the top of rr_create; the rest of the code reads these members.  None is needed in production.
 #define RUN_AHEAD_MAX 64
-    hipEvent_t ahead_ev[2];
-    unsigned long long step_no;
-    int run_ahead;
-    int force_hcount[2];           // RR_FORCE_HCOUNT="h,vh": what the host-side decisions read instead of the lagged counters (tests; -1: the counters)
-    int n_shapes;
-    float table_pos[3];            // target of the default eye camera (env.py:253-255)
-    float t_ms[RR_NUM_KERNELS];
-    int t_n[RR_NUM_KERNELS];
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
-    // pinned staging ring for per-step host inputs (commands, render flags): a hipMemcpyAsync from pageable memory blocks
-    // the host until the copy is done; from these slots it is asynchronous, and a slot is reused only after the event
-    // recorded behind its copy has completed
-    char *pin_buf[4]; hipEvent_t pin_ev[4]; bool pin_used[4]; int pin_next; size_t pin_bytes;
+struct Settings {
+    int tile_w = 0;                // the tile width asked for (0: none); tile_layout ignores a width it cannot use
+    bool full_copy = false, split_heavy = true, lookahead = true, prep_scalar = false, collide_ordered = true, coop_all = true;
+    bool warmstart = true, edge_contacts = true, pair_cull = true, raster_order = true;
+    int run_ahead = 8, split_max_pct = 60, ablate = 0, heavy2_min = 16, os_cap = OS_CAP;
+    int force_hcount[2] = {-1, -1};
+    int skip_queues[2] = {0, 0};
+};
+static Settings read_settings() {
+    Settings s;
+    const char *v;
+    if ((v = getenv("RR_TILE_W"))) s.tile_w = atoi(v);                        // width of a raster tile in place of the tile rule's (A/B, tests)
+    s.full_copy = getenv("RR_FULL_COPY") != nullptr;                          // the earlier image update: the static layer copied into every image before each frame (tests)
+    s.split_heavy = getenv("RR_NO_SPLIT") == nullptr;                         // set: all envs solved and rendered on the main stream (A/B, tests)
+    s.lookahead = getenv("RR_NO_LOOKAHEAD") == nullptr;                       // set: every step prepares itself in line (A/B, tests)
+    if ((v = getenv("RR_PREP_SCALAR"))) s.prep_scalar = atoi(v) != 0;         // 1: the thread-per-env preparation kernels instead of k_prep16 (A/B, tests)
+    if ((v = getenv("RR_COLLIDE_ORDER"))) s.collide_ordered = atoi(v) != 0;   // 0: k_collide in env order instead of by falling duration of the last pass
+    if ((v = getenv("RR_RUN_AHEAD"))) s.run_ahead = std::max(0, std::min(atoi(v), RUN_AHEAD_MAX));   // steps a caller that never waits may get ahead (default 8; 0: unbounded)
+    if ((v = getenv("RR_COOP_ALL"))) s.coop_all = atoi(v) != 0;               // 0: the one-launch solve of a small batch four envs to a wave (A/B, tests)
+    if ((v = getenv("RR_FORCE_HCOUNT"))) sscanf(v, "%d,%d", &s.force_hcount[0], &s.force_hcount[1]);   // "h,vh": what the placement decisions read instead of the lagged counters (tests)
+    if ((v = getenv("RR_SPLIT_MAX_PCT"))) s.split_max_pct = atoi(v);          // the heavy / light split is used while at most this share of the envs is heavy (default 60)
+    if ((v = getenv("RR_ABLATE"))) s.ablate = atoi(v);                        // development build only: phase ablations and counters
+    if ((v = getenv("RR_HEAVY2_MIN"))) s.heavy2_min = atoi(v);                // generic contacts above which an env is "very heavy" (default 16; 1000: never; A/B 6..30: 13-16 best)
+    s.warmstart = getenv("RR_NO_WARMSTART") == nullptr;                       // set: cold start of the contact solver every step (diagnostics)
+    s.edge_contacts = getenv("RR_NO_EDGE_CONTACTS") == nullptr;               // set: vertex candidates only, no edge-edge pass (diagnostics)
+    if ((v = getenv("RR_SOLVER_POOL"))) s.os_cap = std::max(0, std::min(atoi(v) / 60, (int)OS_CAP));   // LDS floats for object-vs-static rows, 60 per contact; contacts beyond take the generic path (tests)
+    if ((v = getenv("RR_NO_PAIR_CULL"))) s.pair_cull = atoi(v) == 0;          // 1: k_collide without the pair cull of its broad phase (tests)
+    if ((v = getenv("RR_SKIP_QUEUES"))) sscanf(v, "%d,%d", &s.skip_queues[0], &s.skip_queues[1]);      // "a,b": unused streams created in front of aux / aux2 (create_device)
+    s.raster_order = getenv("RR_NO_RASTER_ORDER") == nullptr;                 // set: k_raster keeps its env-major grid instead of the cost order
+    return s;
+}
+static const bool g_debug_sync = getenv("RR_DEBUG_SYNC") != nullptr;          // synchronise and report after every kernel; read when the library is loaded (TIMED)
+
+// What rr_create computes from (cfg, blob) on the host and the handle keeps (parse_model fills it, create_device moves it into the rr_env).
+struct ModelTables {
+    BodyParams B = {};
+    SimParams P = {};
+    RenderModel RM = {};
+    IkModel IK = {};
+    int epb = 0;                   // envs per block for physics kernels
+    int n_inst_used = 0;
+    int n_shapes = 0;
+    float table_pos[3] = {};       // target of the default eye camera (env.py:253-255)
     // per-env object dynamics (rr_set_object_dynamics): host copies every upload of D.obj_dyn / D.pair_mat is made from
     std::vector<float> dyn;        // [N][nobj][8] {mass, ixx, iyy, izz, lateral friction, restitution, rolling, spinning}
     std::vector<float> pair_host;  // [N][npairs][4] the env's combined contact materials (pair_materials)
@@ -120,18 +94,87 @@ struct rr_env {
     std::vector<int> pair_shapes;  // [npairs][2] shapes a, b of every collision pair
     // per-env actuators (rr_set_env_actuators): the host copy every upload of D.env_act is made from, and what rr_get_env_actuators returns
     std::vector<float> act;        // [N][NB][4] {kp, kd, max_force, joint damping}
-    float act_default[NB][4];      // the handle's row of every joint: P.kp, P.kd, the motor force of rr_config, the blob's body_damping
+    float act_default[NB][4] = {}; // the handle's row of every joint: P.kp, P.kd, the motor force of rr_config, the blob's body_damping
+};
+
+// Everything rr_create needs from the model: the tables above and what is only uploaded.  The pointers point into the blob.
+struct HostModel : ModelTables {
+    ShapeData S = {};
+    float body_tab[NB * BT_STRIDE] = {};   // the body lanes' constants (k_prep16)
+    std::vector<float> soa;        // [9][nt] triangle positions
+    std::vector<float> rec;        // [nt][32] one 128-byte shading record per triangle {pos[9], nrm[9], inst, -, uv[6], pad}
+    std::vector<float> cvs;        // [nt / 64][3][64] the clusters' vertex positions
+    std::vector<int32_t> tv4;      // [nt] the corner indices as ds_bpermute byte addresses
+    const int32_t *tri_inst = nullptr;     // [nt]
+    const float *cluster_sphere = nullptr; // [nt / 64][4]
+    const uint8_t *tex = nullptr; size_t tex_bytes = 0;
+};
+
+struct rr_env : ModelTables {
+    hipError_t step_err = hipSuccess; const char *step_err_what = nullptr;      // first failed event / wait / bound launch of the step path (HIPQ, step_status)
+    rr_config cfg = {};
+    Settings set;                  // as read when the handle was made; split_heavy also goes off when the device refuses the split's dynamic LDS (create_device)
+    RenderModel *RM_dev = nullptr;
+    DevPtrs D = {};
+    hipStream_t stream = nullptr;
+    size_t field_bytes[RR_F_COUNT] = {};
+    void *field_ptr[RR_F_COUNT] = {};
+    float *state_aos = nullptr;        // [N][61] staging for RR_F_STATE
+    unsigned char *mask_dev = nullptr; // [N]
+    float *link_out = nullptr;         // [N][nl][7]
+    float *plan = nullptr; int *plan_step = nullptr; float *ik_in = nullptr; float *ik_out = nullptr; float *ik_err = nullptr;   // lazily allocated (macro / cartesian adapters)
+    float *score_out = nullptr; unsigned char *score_mask = nullptr;            // lazily allocated (rr_evaluate_goals)
+    std::vector<void *> allocs;
+    bool timing = false;
+    int *h_hcount = nullptr;       // pinned host copy of D.hcount[0] (device-mapped: written by k_prep_a of the following step)
+    bool images_valid = false;     // every env's image holds its previous frame (static layer + the pixels of its fragment list)
+    unsigned char *stale_dev = nullptr;  // [N] device: the env's image predates the current static layer (rr_set_camera after its last frame)
+    bool stale_any = false;        // some env may be stale: every render checks (cleared by a render of all envs)
+    hipEvent_t ev[2 * RR_NUM_KERNELS] = {};
+    hipStream_t aux = nullptr;     // side stream: the HBM-bound static-layer copy runs beside the VALU-bound physics / visibility kernels
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_dyn = nullptr, ev_join2 = nullptr, ev_vsolved = nullptr, ev_hsolved = nullptr, ev_rast = nullptr;
+    hipStream_t aux2 = nullptr;    // the very heavy envs' solve + render (Settings::heavy2_min)
+    std::vector<hipStream_t> unused_streams;   // Settings::skip_queues: created only to take hardware queue ids
+    // Look-ahead (DESIGN.md 5.2): the state part of step t+1 (k_prep_ab, k_collide) runs on the side streams behind the render
+    // of the heavy / very heavy envs of step t, beside the main stream's shading.
+    struct Frame { float4 *clist; int *ccount; float *cwarm; int *hgflag, *hlist, *hcount, *hlist2, *hcount2; } fr[2] = {};
+    int cur = 0;                   // fr[cur]: the frame of the last solved step (rr_get_contacts, contact history); fr[cur ^ 1]: the look-ahead's
+    bool la_valid = false;         // fr[cur ^ 1] and the scratch slab hold the collision pass / dynamics of the next step for the present state
+    // cost-ordered dispatch of k_raster (Settings::raster_order)
+    unsigned *item_perm = nullptr; // [8 * ceil(N / 8) * ntiles] the order, written by the extra workgroups of k_shade
+    bool ord_valid = false, ord_pending = false;   // item_perm holds an order; a k_raster has left costs that the next k_shade launch turns into one
+    void *obs_host = nullptr;      // rr_map_observations: mapped pinned block {joints [N][9], touch [N][4], poses [N][nobj][7], timestep [N], errflags [N]} or nullptr
+    ObsMirror obs_dev = {};        // its device-visible addresses
+    hipEvent_t ev_obs = nullptr;   // recorded behind the mirror's launches: rr_sync_observations waits for it alone
+    bool ev_obs_set = false;
+    void *img_host[3] = {};        // rr_map_images: pinned host copies of RGB / depth / mask that every rendered step refreshes (or nullptr)
+    int img_sel = 7;               // rr_select_image_mirror: which of them a rendered step refreshes (bit 0 RGB, 1 depth, 2 mask)
+    // Bounded run-ahead: a caller that never waits (bench.py, a training loop reading device buffers) gets hundreds of steps ahead of the
+    // device -- the "lagged" list lengths that pick a step's placement are then those of a step 100+ steps back (measured on the macro
+    // workload: readings 1 494 / 201 heavy / very heavy envs while the device solved 1 848 / 368, and 5 % of the step time lost to a
+    // placement chosen for the smaller lists).  Every run_ahead / 2 steps rr_step records an event behind the step and first waits for
+    // the one it recorded run_ahead steps earlier: the device always has run_ahead / 2 .. run_ahead steps in its queues, the readings are
+    // that old at most, and the marker's few microseconds on the main stream are paid once in run_ahead / 2 steps (one every step cost
+    // the headline 0.7 %).  Settings::run_ahead, 0: unbounded.
+    hipEvent_t ahead_ev[2] = {};
+    unsigned long long step_no = 0;
+    float t_ms[RR_NUM_KERNELS] = {};
+    int t_n[RR_NUM_KERNELS] = {};
+    // pinned staging ring for per-step host inputs (commands, render flags): a hipMemcpyAsync from pageable memory blocks
+    // the host until the copy is done; from these slots it is asynchronous, and a slot is reused only after the event
+    // recorded behind its copy has completed
+    char *pin_buf[4] = {}; hipEvent_t pin_ev[4] = {}; bool pin_used[4] = {}; int pin_next = 0; size_t pin_bytes = 0;
     // per-env cameras (rr_set_env_cameras): allocated by its first call; D.env_cam / D.static_* point at them while the handle is in
     // per-env mode, at the shared layer below otherwise (rr_set_camera)
     std::vector<float> cam_host;   // [N][cam_floats(ntiles)] host copy of every env's record
-    float *cam_dev;                // [N][cam_floats(ntiles)]
-    int *cam_sel;                  // [N] class array of the rebuild launches: 0 the envs whose layer is rebuilt (sel 1 selects them), 1 the others
-    unsigned long long *env_static_vis; unsigned char *env_static_rgb; float *env_static_depth; int *env_static_mask;   // [N][H*W]
-    unsigned long long *shared_static_vis; unsigned char *shared_static_rgb; float *shared_static_depth; int *shared_static_mask;   // [H*W]
-    bool cam_per_env, app_per_env; // which of the two per-env settings is in force; the per-env layers are in use (D.env_cam set) while either is
+    float *cam_dev = nullptr;      // [N][cam_floats(ntiles)]
+    int *cam_sel = nullptr;        // [N] class array of the rebuild launches: 0 the envs whose layer is rebuilt (sel 1 selects them), 1 the others
+    unsigned long long *env_static_vis = nullptr; unsigned char *env_static_rgb = nullptr; float *env_static_depth = nullptr; int *env_static_mask = nullptr;   // [N][H*W]
+    unsigned long long *shared_static_vis = nullptr; unsigned char *shared_static_rgb = nullptr; float *shared_static_depth = nullptr; int *shared_static_mask = nullptr;   // [H*W]
+    bool cam_per_env = false, app_per_env = false; // which of the two per-env settings is in force; the per-env layers are in use (D.env_cam set) while either is
     // per-env appearance (rr_set_env_appearance): allocated by its first call; D.env_colour / D.env_light point at them while it is in force
     std::vector<float> colour_host, light_host;    // [N][MAXINST][3], [N][4] (unit vectors): what is uploaded, and what rr_get_env_appearance returns
-    float *colour_dev, *light_dev;
+    float *colour_dev = nullptr, *light_dev = nullptr;
 };
 
 // The combining rule of the contact materials of two shapes (btManifoldResult::calculateCombinedFriction / Restitution /
@@ -148,9 +191,9 @@ static int upload_actuators(rr_env *e);
 
 // The lagged host copy of the heavy (which 0) / very heavy (which 1) list length: written to mapped pinned memory by a recent
 // step's kernels, read here without any synchronisation -- it only ever selects a launch shape or a placement, never a result
-// (every placement is forced and compared bitwise in tests/test_gpu_round4.py; RR_FORCE_HCOUNT pins what is read).
+// (every placement is forced and compared bitwise in tests/test_gpu_round4.py; Settings::force_hcount pins what is read).
 static inline int lagged_count(const rr_env *e, int which, int fallback) {
-    if (e->force_hcount[which] >= 0) return e->force_hcount[which];
+    if (e->set.force_hcount[which] >= 0) return e->set.force_hcount[which];
     return e->h_hcount ? ((volatile int *)e->h_hcount)[which] : fallback;
 }
 
@@ -245,6 +288,223 @@ static void frustum_plane_norms(const RenderModel &RM, const float *V, float *pl
     }
 }
 
+// a device array of `count` elements holding a copy of the host array `src` (`bytes` of it when that is not the whole array)
+template <typename T>
+static int dev_copy(rr_env *e, const T **p, const void *src, size_t count, size_t bytes = 0) {
+    T *q = nullptr;
+    const int rc = dev_alloc(e, &q, count);
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipMemcpy(q, src, bytes ? bytes : count * sizeof(T), hipMemcpyHostToDevice));
+    *p = q;
+    return RR_OK;
+}
+
+// Raster tiles of <= TILE_PIX pixels: full-width strips up to 128 columns (the 128 x 128 benchmark camera: four strips of 32
+// rows); 64 x 64 squares for wider images -- a cluster of the arm is ~25 pixels across at 320 x 240 and met three of the
+// 12-row strips a full-width tile would be there (set-up work x 3.1; squares: x 1.9).  Settings::tile_w overrides (A/B, tests).
+// The one place that knows the rule: rr_create's size check and the RenderModel both come from here.
+struct TileLayout { int tile_w, tile_h, ntx, ntiles, tile_xbits; unsigned w_magic; };
+static TileLayout tile_layout(int W, int H, int tile_w_override) {
+    TileLayout t;
+    t.tile_w = W <= 128 ? W : 64;
+    if (tile_w_override >= 4 && tile_w_override <= W && tile_w_override <= TILE_PIX) t.tile_w = tile_w_override;
+    t.ntx = (W + t.tile_w - 1) / t.tile_w;
+    t.tile_h = std::min(TILE_PIX / t.tile_w, H);
+    t.ntiles = t.ntx * ((H + t.tile_h - 1) / t.tile_h);
+    t.tile_xbits = 0; while ((1 << t.tile_xbits) < t.tile_w) t.tile_xbits++;
+    t.w_magic = (unsigned)((0x100000000ull + (unsigned long long)t.tile_w - 1) / (unsigned long long)t.tile_w);
+    return t;
+}
+
+// Phase 1 of rr_create, host only: everything the handle needs from (cfg, blob), checked.  Calls no HIP function and owns every
+// RR_EMODEL exit, so a malformed model is reported as such on any machine.  cfg has passed rr_create's argument checks.
+static int parse_model(const rr_config &cfg, const Blob &b, const Settings &set, HostModel &M) {
+    const int32_t *dims = b.i32("dims", 11);
+    if (!dims) return fail(RR_EMODEL, "rr_create: blob has no dims");
+    const int nb = dims[0], nl = dims[1], ns = dims[2], ni = dims[3], nt = dims[4], ntex = dims[5], n_static = dims[6], n_robot = dims[7];
+    if (nb != NB || ns > MAXSHAPES || dims[8] != VMAXC || dims[9] != FMAXC || ni > MAXINST || ni > RASTER_INST || nl > NLINK_MAX || ntex > 16 ||
+        n_static != 3 || n_robot != 16)
+        return fail(RR_EMODEL, "rr_create: blob dims do not match this build");
+    const int N = cfg.num_envs;
+#define NEED(p) if (!(p)) return fail(RR_EMODEL, "rr_create: blob entry missing/short: " #p)
+    const float *f; const int32_t *ip;
+    BodyParams &B = M.B;
+    NEED(ip = b.i32("body_parent", NB)); memcpy(B.parent, ip, sizeof B.parent);
+    if (memcmp(B.parent, PARENT_HOST, sizeof PARENT_HOST) != 0) return fail(RR_EMODEL, "rr_create: kinematic tree differs from the compiled-in one");
+    NEED(f = b.f32("body_jpos", NB * 3)); memcpy(B.jpos, f, sizeof B.jpos);
+    NEED(f = b.f32("body_jrot", NB * 9)); memcpy(B.jrot, f, sizeof B.jrot);
+    NEED(f = b.f32("body_axis", NB * 3)); memcpy(B.axis, f, sizeof B.axis);
+    NEED(f = b.f32("body_mass", NB)); memcpy(B.mass, f, sizeof B.mass);
+    NEED(f = b.f32("body_com", NB * 3)); memcpy(B.com, f, sizeof B.com);
+    NEED(f = b.f32(cfg.use_urdf_inertia ? "body_inertia_urdf" : "body_inertia", NB * 6)); memcpy(B.inertia, f, sizeof B.inertia);
+    NEED(f = b.f32("body_damping", NB)); memcpy(B.damping, f, sizeof B.damping);
+    NEED(f = b.f32("body_limits", NB * 2)); memcpy(B.limits, f, sizeof B.limits);
+    NEED(f = b.f32("robot_pos", 3)); memcpy(B.robot_pos, f, sizeof B.robot_pos);
+    NEED(f = b.f32("obj_mass", NOBJ)); memcpy(B.obj_mass, f, sizeof B.obj_mass);
+    NEED(f = b.f32("obj_inertia", NOBJ * 3)); memcpy(B.obj_inertia, f, sizeof B.obj_inertia);
+    NEED(f = b.f32("obj_pose0", NOBJ * 7)); memcpy(B.obj_pose0, f, sizeof B.obj_pose0);
+    NEED(f = b.f32("table_pos", 3)); memcpy(M.table_pos, f, sizeof M.table_pos); B.table_z = f[2];
+    NEED(f = b.f32("act_min", 9)); memcpy(B.act_min, f, sizeof B.act_min);
+    NEED(f = b.f32("act_max", 9)); memcpy(B.act_max, f, sizeof B.act_max);
+    NEED(f = b.f32("act_maxdiff", 9)); memcpy(B.act_maxdiff, f, sizeof B.act_maxdiff);
+    NEED(ip = b.i32("touch_links", 4)); memcpy(B.touch_links, ip, sizeof B.touch_links);
+    if (cfg.solver_flags & RR_SOLVER_NO_RATE_LIMIT)      // env.py:314-321 skipped: +-inf never clips (fminf / fmaxf of the command part)
+        for (int k = 0; k < 9; k++) B.act_maxdiff[k] = INFINITY;
+    for (int j = 0; j < NB; j++) {      // the body lanes' constants (k_prep16)
+        float *t = M.body_tab + j * BT_STRIDE;
+        for (int k = 0; k < 3; k++) { t[BT_COM + k] = B.com[j][k]; t[BT_AXIS + k] = B.axis[j][k]; }
+        for (int k = 0; k < 6; k++) t[BT_INERTIA + k] = B.inertia[j][k];
+        t[BT_MASS] = B.mass[j]; t[BT_DAMP] = B.damping[j];
+    }
+    const float *link_pos, *link_rot; const int32_t *link_body;
+    NEED(link_body = b.i32("link_body", nl)); NEED(link_pos = b.f32("link_pos", nl * 3)); NEED(link_rot = b.f32("link_rot", nl * 9));
+    {   // arm chain + gripper base frame (link id 8 = `base`, rigidly attached to body 6) for the IK kernels
+        IkModel &K = M.IK;
+        for (int j = 0; j < 7; j++) { memcpy(K.jpos[j], B.jpos[j], 12); memcpy(K.jrot[j], B.jrot[j], 36); memcpy(K.axis[j], B.axis[j], 12); }
+        memcpy(K.robot_pos, B.robot_pos, 12);
+        const int ee = 8;       // URDF depth-first id of the gripper `base` link (pybullet link index 7)
+        if (nl <= ee || link_body[ee] != 6) return fail(RR_EMODEL, "rr_create: gripper base link not found");
+        memcpy(K.ee_pos, link_pos + 3 * ee, 12); memcpy(K.ee_rot, link_rot + 9 * ee, 36);
+        K.single_seed = (cfg.solver_flags & RR_SOLVER_IK_SINGLE_SEED) ? 1 : 0;
+    }
+
+    SimParams &P = M.P;
+    P.N = N; P.nobj = cfg.n_objects; P.iters = cfg.solver_iters > 0 ? cfg.solver_iters : 50;
+    P.dt = cfg.dt > 0 ? cfg.dt : 0.005f; P.gravity = 9.81f; P.erp = cfg.erp > 0 ? cfg.erp : 0.2f;
+    P.margin = cfg.margin > 0 ? cfg.margin : 0.02f;
+    // the UPSTREAM constants (pybullet's defaults, SURVEY A.1.2 / A.1.4 / A.1.5) are parameters of the handle: 0 -> default, < 0 -> literal zero
+    auto upstream = [](float v, float dflt) { return v > 0.0f ? v : (v < 0.0f ? 0.0f : dflt); };
+    P.kp = upstream(cfg.motor_kp, 0.1f); P.kd = upstream(cfg.motor_kd, 1.0f);
+    P.max_impulse = upstream(cfg.motor_max_force, 100000.0f) * P.dt;
+    P.ablate = set.ablate; P.heavy2_min = set.heavy2_min; P.edge_contacts = set.edge_contacts ? 1 : 0; P.os_cap = set.os_cap;
+    P.warmstart = set.warmstart ? upstream(cfg.warmstart, 0.85f) : 0.0f;
+    P.lin_damp = upstream(cfg.lin_damping, 0.04f); P.ang_damp = upstream(cfg.ang_damping, 0.04f); P.rest_thresh = 0.2f;
+    M.epb = cfg.envs_per_block > 0 ? std::min(cfg.envs_per_block, 64) : 64;   // physics kernels are compiled with __launch_bounds__(64)
+
+    // shapes + pair table (same order as the oracle's collide())
+    ShapeData &S = M.S;
+    NEED(ip = b.i32("shape_owner", ns * 4));
+    for (int s = 0; s < ns; s++) { S.otype[s] = ip[4 * s]; S.oidx[s] = ip[4 * s + 1]; S.link[s] = ip[4 * s + 2]; }
+    NEED(ip = b.i32("shape_nv", ns)); memcpy(S.nv, ip, ns * 4);
+    NEED(ip = b.i32("shape_nf", ns)); memcpy(S.nf, ip, ns * 4);
+    NEED(f = b.f32("shape_verts", ns * VMAXC * 3)); memcpy(S.verts, f, (size_t)ns * VMAXC * 3 * 4);
+    NEED(f = b.f32("shape_planes", ns * FMAXC * 4)); memcpy(S.planes, f, (size_t)ns * FMAXC * 4 * 4);
+    NEED(f = b.f32("shape_sphere", ns * 4)); memcpy(S.sphere, f, (size_t)ns * 4 * 4);
+    NEED(f = b.f32("shape_mat", ns * 2));
+    for (int s = 0; s < ns; s++) { S.fric[s] = f[2 * s]; S.rest[s] = f[2 * s + 1]; }
+    NEED(f = b.f32("shape_roll", ns * 2));       // URDF <rolling_friction>, <spinning_friction> (cube.urdf:6-7, kuka_gripper.urdf:292-296 ...)
+    for (int s = 0; s < ns; s++) { S.roll[s] = f[2 * s]; S.spin[s] = f[2 * s + 1]; }
+    {   // (optional field: the radii hold for margins up to the one they were compiled for)
+        const float *ro = b.f32("shape_roff", ns + 1);
+        for (int s = 0; s < ns; s++) S.roff[s] = (ro && P.margin <= ro[ns] && set.pair_cull) ? ro[s] : INFINITY;
+    }
+    NEED(ip = b.i32("shape_ne", ns)); memcpy(S.ne, ip, ns * 4);
+    NEED(f = b.f32("shape_edges", ns * EMAXC * 12)); memcpy(S.edges, f, (size_t)ns * EMAXC * 12 * 4);
+    for (int s = 0; s < ns; s++) if (S.ne[s] < 0 || S.ne[s] > EMAXC) return fail(RR_EMODEL, "rr_create: bad shape_ne");
+    int np = 0, s_obj0 = n_static + n_robot;
+    for (int i = 0; i < P.nobj; i++) for (int s = 0; s < n_static; s++) { S.pair_a[np] = s_obj0 + i; S.pair_b[np++] = s; }
+    for (int i = 0; i < P.nobj; i++) for (int j = i + 1; j < P.nobj; j++) { S.pair_a[np] = s_obj0 + i; S.pair_b[np++] = s_obj0 + j; }
+    for (int r = 0; r < n_robot; r++) for (int s = 0; s < 2; s++) { S.pair_a[np] = n_static + r; S.pair_b[np++] = s; }
+    for (int r = 0; r < n_robot; r++) for (int i = 0; i < P.nobj; i++) { S.pair_a[np] = n_static + r; S.pair_b[np++] = s_obj0 + i; }
+    P.npairs = np;
+    M.n_shapes = ns;
+    if (ns > CSHAPES) return fail(RR_EMODEL, "rr_create: more collision shapes than k_collide stages in LDS");
+    for (int k = 0; k < np; k++) {
+        const int sa = S.pair_a[k], sb = S.pair_b[k];
+        S.pair_meta[k][0] = S.otype[sa] == 0 ? -1 : (S.otype[sa] == 1 ? S.oidx[sa] : 16 + S.oidx[sa]);
+        S.pair_meta[k][1] = S.otype[sb] == 0 ? -1 : (S.otype[sb] == 1 ? S.oidx[sb] : 16 + S.oidx[sb]);
+        S.pair_meta[k][2] = S.link[sa]; S.pair_meta[k][3] = 0;
+        const float ma[4] = {S.fric[sa], S.rest[sa], S.roll[sa], S.spin[sa]}, mb[4] = {S.fric[sb], S.rest[sb], S.roll[sb], S.spin[sb]};
+        pair_materials(ma, mb, S.pair_mat[k]);
+        M.pair_shapes.push_back(sa); M.pair_shapes.push_back(sb);
+    }
+    for (int s = 0; s < ns; s++) {
+        M.shape_mat.insert(M.shape_mat.end(), {S.fric[s], S.rest[s], S.roll[s], S.spin[s]});
+        M.shape_obj.push_back(S.otype[s] == 2 && S.oidx[s] >= 0 && S.oidx[s] < P.nobj ? S.oidx[s] : -1);
+    }
+    // the default dynamics of every env: the blob's mass and inertia of an object, the materials of its first collision shape
+    // (the model has one per object), and the blob's pair table
+    M.dyn.assign((size_t)N * P.nobj * 8, 0.0f);
+    for (int i = 0; i < P.nobj; i++) {
+        float row[8] = {B.obj_mass[i], B.obj_inertia[i][0], B.obj_inertia[i][1], B.obj_inertia[i][2], 0.0f, 0.0f, 0.0f, 0.0f};
+        for (int s = ns - 1; s >= 0; s--) if (M.shape_obj[s] == i) memcpy(row + 4, &M.shape_mat[4 * s], 16);
+        for (int n = 0; n < N; n++) memcpy(&M.dyn[((size_t)n * P.nobj + i) * 8], row, 32);
+    }
+    // the default actuators of every env: the handle's motor constants, the blob's joint damping
+    for (int j = 0; j < NB; j++) {
+        const float row[4] = {P.kp, P.kd, upstream(cfg.motor_max_force, 100000.0f), B.damping[j]};
+        memcpy(M.act_default[j], row, 16);
+    }
+    M.act.resize((size_t)N * NB * 4);
+    for (int n = 0; n < N; n++) memcpy(&M.act[(size_t)n * NB * 4], M.act_default, sizeof M.act_default);
+    M.pair_host.resize((size_t)N * np * 4);
+    for (int n = 0; n < N; n++) memcpy(&M.pair_host[(size_t)n * np * 4], S.pair_mat, (size_t)np * 16);
+
+    // k_collide's warm-start matching looks for the previous contacts of the same bodies (bodyA, bodyB, linkA) among the
+    // pairs pair-2 .. pair+2 only: pairs with equal keys must form runs of at most three consecutive pairs (one collision shape
+    // per robot link against table / shelf, one per object against the three statics)
+    for (int k = 0; k < np; k++)
+        for (int j = 0; j < np; j++) {
+            const bool same = S.pair_meta[k][0] == S.pair_meta[j][0] && S.pair_meta[k][1] == S.pair_meta[j][1] && S.pair_meta[k][2] == S.pair_meta[j][2];
+            if (same && std::abs(k - j) > 2) return fail(RR_EMODEL, "rr_create: collision pairs of the same bodies are more than two apart in the pair table (warm-start matching window)");
+        }
+
+    // render model
+    RenderModel &RM = M.RM;
+    RM.ni = ni; RM.nt = nt; RM.W = cfg.width; RM.H = cfg.height; RM.nl = nl;
+    const TileLayout tl = tile_layout(RM.W, RM.H, set.tile_w);
+    RM.tile_w = tl.tile_w; RM.tile_h = tl.tile_h; RM.ntx = tl.ntx; RM.ntiles = tl.ntiles; RM.tile_xbits = tl.tile_xbits; RM.w_magic = tl.w_magic;
+    NEED(ip = b.i32("inst_owner", ni * 4));
+    for (int i = 0; i < ni; i++) { RM.in_otype[i] = ip[4 * i]; RM.in_oidx[i] = ip[4 * i + 1]; RM.in_uid[i] = ip[4 * i + 2]; RM.in_tex[i] = ip[4 * i + 3]; }
+    NEED(f = b.f32("inst_color", ni * 3)); memcpy(RM.in_color, f, (size_t)ni * 12);
+    NEED(ip = b.i32("tex_info", ntex * 3));
+    for (int t = 0; t < ntex; t++) { RM.tex_off[t] = ip[3 * t]; RM.tex_w[t] = ip[3 * t + 1]; RM.tex_h[t] = ip[3 * t + 2]; }
+    NEED(M.tex = b.u8("tex_data", &M.tex_bytes));
+    // a one-texel texture (the arm's colours: tools/compile_model.py stores uniform images as 1 x 1) travels with the instance
+    // constants -- width -1, the texel in place of the offset: its fragments fetch neither texture coordinates nor texels
+    for (int t = 0; t < ntex; t++)
+        if (RM.tex_w[t] == 1 && RM.tex_h[t] == 1 && (size_t)RM.tex_off[t] * 4 + 4 <= M.tex_bytes) {
+            uint32_t px; memcpy(&px, M.tex + (size_t)RM.tex_off[t] * 4, 4);
+            RM.tex_off[t] = (int)px; RM.tex_w[t] = -1;
+        }
+    memcpy(RM.link_body, link_body, nl * 4); memcpy(RM.link_pos, link_pos, (size_t)nl * 12); memcpy(RM.link_rot, link_rot, (size_t)nl * 36);
+    NEED(ip = b.i32("inst_range", ni * 2));
+    const int n_static_inst = dims[10];
+    RM.first_dynamic_tri = (n_static_inst < ni) ? ip[2 * n_static_inst] : nt;
+    look_at_persp(RM.VP, M.table_pos, RM.W, RM.H);
+    frustum_plane_norms(RM, RM.VP, RM.plane_norm, RM.tile_plane);
+    M.n_inst_used = ni - (NOBJ - P.nobj);
+
+    // geometry: positions SoA [9][NT], one shading record per triangle, the clusters' vertices and corner indices
+    const float *tp, *tn, *tu, *cvb; const int32_t *tv;
+    NEED(tp = b.f32("tri_pos", (size_t)nt * 9)); NEED(tn = b.f32("tri_nrm", (size_t)nt * 9));
+    NEED(tu = b.f32("tri_uv", (size_t)nt * 6)); NEED(M.tri_inst = b.i32("tri_inst", nt));
+    if (nt % 64 != 0 || nt / 64 > MAXWIN || nt >= (1 << 18)) return fail(RR_EMODEL, "rr_create: triangle count must be a multiple of the cluster size 64 and below 65536");
+    NEED(M.cluster_sphere = b.f32("cluster_sphere", (size_t)(nt / 64) * 4));
+    NEED(cvb = b.f32("cluster_verts", (size_t)nt * 3)); NEED(tv = b.i32("tri_vidx", nt));
+#undef NEED
+    M.soa.resize((size_t)nt * 9);
+    for (int t = 0; t < nt; t++) for (int k = 0; k < 9; k++) M.soa[(size_t)k * nt + t] = tp[(size_t)t * 9 + k];
+    M.rec.assign((size_t)nt * 32, 0.0f);
+    for (int t = 0; t < nt; t++) {
+        float *r = &M.rec[(size_t)t * 32];
+        memcpy(r, tp + (size_t)t * 9, 36); memcpy(r + 9, tn + (size_t)t * 9, 36); memcpy(r + 18, M.tri_inst + t, 4);
+        memcpy(r + 20, tu + (size_t)t * 6, 24);          // (chunks 5, 6: only textured instances' fragments fetch them, load_tri_rec)
+    }
+    M.cvs.resize((size_t)nt * 3);          // [cluster][64][3] -> [cluster][3][64]
+    for (int c = 0; c < nt / 64; c++)
+        for (int v = 0; v < 64; v++)
+            for (int k = 0; k < 3; k++) M.cvs[((size_t)c * 3 + k) * 64 + v] = cvb[((size_t)c * 64 + v) * 3 + k];
+    // (the corner indices go to the device as ds_bpermute byte addresses, index x 4 in each byte: one bit-field extract per
+    // corner in the window loop instead of a shift and a mask)
+    M.tv4.resize((size_t)nt);
+    for (int t = 0; t < nt; t++) {
+        const int a0 = tv[t] & 63, a1 = (tv[t] >> 8) & 63, a2 = (tv[t] >> 16) & 63;
+        M.tv4[t] = (a0 << 2) | (a1 << 10) | (a2 << 18);
+    }
+    return RR_OK;
+}
+
 extern "C" {
 
 const char *rr_last_error(void) { return g_err.c_str(); }
@@ -259,20 +519,12 @@ int rr_destroy(rr_env *e) {
     if (e->aux) { hipStreamSynchronize(e->aux); hipStreamDestroy(e->aux); }
     if (e->aux2) { hipStreamSynchronize(e->aux2); hipStreamDestroy(e->aux2); }
     for (hipStream_t s : e->unused_streams) hipStreamDestroy(s);
-
-    if (e->ev_join2) hipEventDestroy(e->ev_join2);
-    if (e->ev_vsolved) hipEventDestroy(e->ev_vsolved);
-    if (e->ev_hsolved) hipEventDestroy(e->ev_hsolved);
-    if (e->ev_rast) hipEventDestroy(e->ev_rast);
-    if (e->ev_fork) hipEventDestroy(e->ev_fork);
-    if (e->ev_join) hipEventDestroy(e->ev_join);
-    if (e->ev_dyn) hipEventDestroy(e->ev_dyn);
+    for (hipEvent_t ev : {e->ev_join2, e->ev_vsolved, e->ev_hsolved, e->ev_rast, e->ev_fork, e->ev_join, e->ev_dyn, e->ev_obs, e->ahead_ev[0], e->ahead_ev[1]})
+        if (ev) hipEventDestroy(ev);
     for (int i = 0; i < 4; i++) { if (e->pin_buf[i]) hipHostFree(e->pin_buf[i]); if (e->pin_ev[i]) hipEventDestroy(e->pin_ev[i]); }
     if (e->h_hcount) hipHostFree(e->h_hcount);
     if (e->obs_host) hipHostFree(e->obs_host);
     for (int i = 0; i < 3; i++) if (e->img_host[i]) hipHostFree(e->img_host[i]);
-    if (e->ev_obs) hipEventDestroy(e->ev_obs);
-    for (int i = 0; i < 2; i++) if (e->ahead_ev[i]) hipEventDestroy(e->ahead_ev[i]);
     delete e;
     return RR_OK;
 }
@@ -325,242 +577,21 @@ static int build_static_layer(rr_env *e) {
     return RR_OK;
 }
 
-int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, void *stream, rr_env **out) {
-    if (!cfg || !model_blob || !out) return fail(RR_EINVAL, "rr_create: null argument");
-    if (cfg->abi_version != RR_ABI_VERSION) return fail(RR_EINVAL, "rr_create: abi_version mismatch");
-    if (cfg->num_envs < 1) return fail(RR_EINVAL, "rr_create: num_envs < 1");
-    if ((unsigned long long)cfg->num_envs * GP_ENV_BYTES + 4096ull >= (1ull << 32)) return fail(RR_EINVAL, "rr_create: more than 33222 envs per rr_env (32-bit byte offsets of the solver's row store)");
-    if (cfg->n_objects < 1 || cfg->n_objects > NOBJ) return fail(RR_EINVAL, "rr_create: n_objects must be 1..3");
-    for (float v : {cfg->motor_kp, cfg->motor_kd, cfg->motor_max_force, cfg->warmstart, cfg->lin_damping, cfg->ang_damping, cfg->dt, cfg->erp, cfg->margin})
-        if (!std::isfinite(v)) return fail(RR_EINVAL, "rr_create: non-finite motor / solver constant");
-    if (cfg->solver_flags & ~(RR_SOLVER_NO_RATE_LIMIT | RR_SOLVER_IK_SINGLE_SEED)) return fail(RR_EINVAL, "rr_create: unknown solver_flags bit");
-    *out = nullptr;
-    if (cfg->width < 4 || cfg->height < 1 || cfg->width % 4 != 0 || cfg->width > 1024 || cfg->height > 1024)
-        return fail(RR_EINVAL, "rr_create: width must be a multiple of 4 in [4,1024], height in [1,1024] (10-bit box origins in the rasteriser's records)");
-    {   // (the raster tiles of this image: rr_create lays them out below by the same rule; the tile index is 8 bits with one sentinel)
-        int tw_ = cfg->width <= 128 ? cfg->width : 64;
-        if (getenv("RR_TILE_W")) { const int t_ = atoi(getenv("RR_TILE_W")); if (t_ >= 4 && t_ <= cfg->width && t_ <= TILE_PIX) tw_ = t_; }
-        int th_ = TILE_PIX / tw_; if (th_ > cfg->height) th_ = cfg->height;
-        const int nt_ = ((cfg->width + tw_ - 1) / tw_) * ((cfg->height + th_ - 1) / th_);
-        if (nt_ > 255) return fail(RR_EINVAL, "rr_create: image too large: more than 255 raster tiles of 4096 pixels (e.g. 1024 x 960 fits, 1024 x 961 does not)");
-    }
-    Blob b;
-    if (!b.init(model_blob, blob_bytes)) return fail(RR_EMODEL, "rr_create: bad model blob header");
-    const int32_t *dims = b.i32("dims", 11);
-    if (!dims) return fail(RR_EMODEL, "rr_create: blob has no dims");
-    int nb = dims[0], nl = dims[1], ns = dims[2], ni = dims[3], nt = dims[4], ntex = dims[5], n_static = dims[6], n_robot = dims[7];
-    if (nb != NB || ns > MAXSHAPES || dims[8] != VMAXC || dims[9] != FMAXC || ni > MAXINST || ni > RASTER_INST || nl > NLINK_MAX || ntex > 16 ||
-        n_static != 3 || n_robot != 16)
-        return fail(RR_EMODEL, "rr_create: blob dims do not match this build");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(RR_EDEVICE, "rr_create: no HIP device available (this library has no CPU fallback)");
-    if (cfg->device < 0 || cfg->device >= ndev) return fail(RR_EINVAL, "rr_create: bad device ordinal");
-    HIPCHK(hipSetDevice(cfg->device));
-
-    rr_env *e = new rr_env();
-    memset(&e->B, 0, sizeof e->B); memset(&e->RM, 0, sizeof e->RM); memset(&e->D, 0, sizeof e->D);
-    memset(e->ev, 0, sizeof e->ev); memset(e->t_ms, 0, sizeof e->t_ms); memset(e->t_n, 0, sizeof e->t_n);
-    e->timing = false; e->step_err = hipSuccess; e->step_err_what = nullptr;
-    memset(e->pin_buf, 0, sizeof e->pin_buf); memset(e->pin_ev, 0, sizeof e->pin_ev); memset(e->pin_used, 0, sizeof e->pin_used); e->pin_next = 0; e->pin_bytes = 0;
-    e->full_copy = getenv("RR_FULL_COPY") != nullptr;
-    e->split_heavy = getenv("RR_NO_SPLIT") == nullptr;
-    e->lookahead = getenv("RR_NO_LOOKAHEAD") == nullptr;
-    e->item_perm = nullptr; e->ord_valid = e->ord_pending = false;
-    e->prep_scalar = getenv("RR_PREP_SCALAR") && atoi(getenv("RR_PREP_SCALAR")) != 0;
-    e->collide_ordered = !(getenv("RR_COLLIDE_ORDER") && atoi(getenv("RR_COLLIDE_ORDER")) == 0);
-    e->force_hcount[0] = e->force_hcount[1] = -1;
-    e->run_ahead = getenv("RR_RUN_AHEAD") ? std::max(0, std::min(atoi(getenv("RR_RUN_AHEAD")), RUN_AHEAD_MAX)) : 8;
-    e->step_no = 0;
-    e->coop_all = !(getenv("RR_COOP_ALL") && atoi(getenv("RR_COOP_ALL")) == 0);
-    e->obs_host = nullptr; memset(&e->obs_dev, 0, sizeof e->obs_dev);
-    e->img_host[0] = e->img_host[1] = e->img_host[2] = nullptr;
-    e->img_sel = 7;
-    e->ev_obs = nullptr; e->ev_obs_set = false;
-    if (getenv("RR_FORCE_HCOUNT")) sscanf(getenv("RR_FORCE_HCOUNT"), "%d,%d", &e->force_hcount[0], &e->force_hcount[1]);
-
-    e->h_hcount = nullptr;
-    e->split_max_pct = getenv("RR_SPLIT_MAX_PCT") ? atoi(getenv("RR_SPLIT_MAX_PCT")) : 60;
-    if (hipHostMalloc((void **)&e->h_hcount, 4 * sizeof(int), hipHostMallocMapped) == hipSuccess) { e->h_hcount[0] = 0; e->h_hcount[1] = 0; e->h_hcount[2] = -1; e->h_hcount[3] = 0; } else e->h_hcount = nullptr;
-    e->plan = nullptr; e->plan_step = nullptr; e->ik_in = nullptr; e->ik_out = nullptr; e->ik_err = nullptr;
-    e->score_out = nullptr; e->score_mask = nullptr;
-    e->cfg = *cfg;
+// Phase 2 of rr_create, device: allocations, uploads, streams and events, first reset and the static layer.  rr_create owns the
+// handle: every failure here just returns, and the caller's guard destroys what was built.
+static int create_device(rr_env *e, const rr_config &cfg, const Settings &set, HostModel &M, void *stream) {
+    e->cfg = cfg;
     e->stream = (hipStream_t)stream;
-    const int N = cfg->num_envs;
-#define NEED(p) if (!(p)) { rr_destroy(e); return fail(RR_EMODEL, "rr_create: blob entry missing/short: " #p); }
-    const float *f; const int32_t *ip;
-    BodyParams &B = e->B;
-    NEED(ip = b.i32("body_parent", NB)); memcpy(B.parent, ip, sizeof B.parent);
-    if (memcmp(B.parent, PARENT_HOST, sizeof PARENT_HOST) != 0) { rr_destroy(e); return fail(RR_EMODEL, "rr_create: kinematic tree differs from the compiled-in one"); }
-    NEED(f = b.f32("body_jpos", NB * 3)); memcpy(B.jpos, f, sizeof B.jpos);
-    NEED(f = b.f32("body_jrot", NB * 9)); memcpy(B.jrot, f, sizeof B.jrot);
-    NEED(f = b.f32("body_axis", NB * 3)); memcpy(B.axis, f, sizeof B.axis);
-    NEED(f = b.f32("body_mass", NB)); memcpy(B.mass, f, sizeof B.mass);
-    NEED(f = b.f32("body_com", NB * 3)); memcpy(B.com, f, sizeof B.com);
-    NEED(f = b.f32(cfg->use_urdf_inertia ? "body_inertia_urdf" : "body_inertia", NB * 6)); memcpy(B.inertia, f, sizeof B.inertia);
-    NEED(f = b.f32("body_damping", NB)); memcpy(B.damping, f, sizeof B.damping);
-    NEED(f = b.f32("body_limits", NB * 2)); memcpy(B.limits, f, sizeof B.limits);
-    NEED(f = b.f32("robot_pos", 3)); memcpy(B.robot_pos, f, sizeof B.robot_pos);
-    NEED(f = b.f32("obj_mass", NOBJ)); memcpy(B.obj_mass, f, sizeof B.obj_mass);
-    NEED(f = b.f32("obj_inertia", NOBJ * 3)); memcpy(B.obj_inertia, f, sizeof B.obj_inertia);
-    NEED(f = b.f32("obj_pose0", NOBJ * 7)); memcpy(B.obj_pose0, f, sizeof B.obj_pose0);
-    const float *table_pos;
-    NEED(table_pos = b.f32("table_pos", 3)); B.table_z = table_pos[2];
-    NEED(f = b.f32("act_min", 9)); memcpy(B.act_min, f, sizeof B.act_min);
-    NEED(f = b.f32("act_max", 9)); memcpy(B.act_max, f, sizeof B.act_max);
-    NEED(f = b.f32("act_maxdiff", 9)); memcpy(B.act_maxdiff, f, sizeof B.act_maxdiff);
-    NEED(ip = b.i32("touch_links", 4)); memcpy(B.touch_links, ip, sizeof B.touch_links);
-    {   // arm chain + gripper base frame (link id 8 = `base`, rigidly attached to body 6) for the IK kernels
-        IkModel &K = e->IK;
-        memset(&K, 0, sizeof K);
-        for (int j = 0; j < 7; j++) { memcpy(K.jpos[j], B.jpos[j], 12); memcpy(K.jrot[j], B.jrot[j], 36); memcpy(K.axis[j], B.axis[j], 12); }
-        memcpy(K.robot_pos, B.robot_pos, 12);
-        const float *lp, *lr; const int32_t *lb;
-        NEED(lb = b.i32("link_body", nl)); NEED(lp = b.f32("link_pos", nl * 3)); NEED(lr = b.f32("link_rot", nl * 9));
-        const int ee = 8;       // URDF depth-first id of the gripper `base` link (pybullet link index 7)
-        if (nl <= ee || lb[ee] != 6) { rr_destroy(e); return fail(RR_EMODEL, "rr_create: gripper base link not found"); }
-        memcpy(K.ee_pos, lp + 3 * ee, 12); memcpy(K.ee_rot, lr + 9 * ee, 36);
-        K.single_seed = (cfg->solver_flags & RR_SOLVER_IK_SINGLE_SEED) ? 1 : 0;
-    }
-
-    SimParams &P = e->P;
-    P.N = N; P.nobj = cfg->n_objects; P.iters = cfg->solver_iters > 0 ? cfg->solver_iters : 50;
-    P.dt = cfg->dt > 0 ? cfg->dt : 0.005f; P.gravity = 9.81f; P.erp = cfg->erp > 0 ? cfg->erp : 0.2f;
-    P.margin = cfg->margin > 0 ? cfg->margin : 0.02f;
-    // the UPSTREAM constants (pybullet's defaults, SURVEY A.1.2 / A.1.4 / A.1.5) are parameters of the handle: 0 -> default, < 0 -> literal zero
-    auto upstream = [](float v, float dflt) { return v > 0.0f ? v : (v < 0.0f ? 0.0f : dflt); };
-    P.kp = upstream(cfg->motor_kp, 0.1f); P.kd = upstream(cfg->motor_kd, 1.0f);
-    P.max_impulse = upstream(cfg->motor_max_force, 100000.0f) * P.dt;
-    if (cfg->solver_flags & RR_SOLVER_NO_RATE_LIMIT)      // env.py:314-321 skipped: +-inf never clips (fminf / fmaxf of the command part)
-        for (int k = 0; k < 9; k++) B.act_maxdiff[k] = INFINITY;
-    P.ablate = getenv("RR_ABLATE") ? atoi(getenv("RR_ABLATE")) : 0;
-    P.heavy2_min = getenv("RR_HEAVY2_MIN") ? atoi(getenv("RR_HEAVY2_MIN")) : 16;      // generic contacts above which an env is "very heavy" (1000: never; A/B 6..30: 13-16 best)
-    P.warmstart = getenv("RR_NO_WARMSTART") ? 0.0f : upstream(cfg->warmstart, 0.85f);       // (the variable: diagnostics, cold start every step)
-    P.edge_contacts = getenv("RR_NO_EDGE_CONTACTS") ? 0 : 1;       // (diagnostics: vertex candidates only)
-    // RR_SOLVER_POOL (tests): LDS floats for object-vs-static rows, 60 per contact; contacts beyond it take the generic (slot layout) path
-    P.os_cap = getenv("RR_SOLVER_POOL") ? std::max(0, std::min(atoi(getenv("RR_SOLVER_POOL")) / 60, (int)OS_CAP)) : OS_CAP;
-    P.lin_damp = upstream(cfg->lin_damping, 0.04f); P.ang_damp = upstream(cfg->ang_damping, 0.04f); P.rest_thresh = 0.2f;
-    e->epb = cfg->envs_per_block > 0 ? cfg->envs_per_block : 64;
-    if (e->epb > 64) e->epb = 64;   // physics kernels are compiled with __launch_bounds__(64)
-
-    // shapes + pair table (same order as the oracle's collide())
-    std::vector<ShapeData> sdv(1);
-    ShapeData &S = sdv[0];
-    memset(&S, 0, sizeof S);
-    NEED(ip = b.i32("shape_owner", ns * 4));
-    for (int s = 0; s < ns; s++) { S.otype[s] = ip[4 * s]; S.oidx[s] = ip[4 * s + 1]; S.link[s] = ip[4 * s + 2]; }
-    NEED(ip = b.i32("shape_nv", ns)); memcpy(S.nv, ip, ns * 4);
-    NEED(ip = b.i32("shape_nf", ns)); memcpy(S.nf, ip, ns * 4);
-    NEED(f = b.f32("shape_verts", ns * VMAXC * 3)); memcpy(S.verts, f, (size_t)ns * VMAXC * 3 * 4);
-    NEED(f = b.f32("shape_planes", ns * FMAXC * 4)); memcpy(S.planes, f, (size_t)ns * FMAXC * 4 * 4);
-    NEED(f = b.f32("shape_sphere", ns * 4)); memcpy(S.sphere, f, (size_t)ns * 4 * 4);
-    NEED(f = b.f32("shape_mat", ns * 2));
-    for (int s = 0; s < ns; s++) { S.fric[s] = f[2 * s]; S.rest[s] = f[2 * s + 1]; }
-    NEED(f = b.f32("shape_roll", ns * 2));       // URDF <rolling_friction>, <spinning_friction> (cube.urdf:6-7, kuka_gripper.urdf:292-296 ...)
-    for (int s = 0; s < ns; s++) { S.roll[s] = f[2 * s]; S.spin[s] = f[2 * s + 1]; }
-    {   // (optional field: the radii hold for margins up to the one they were compiled for)
-        const float *ro = b.f32("shape_roff", ns + 1);
-        for (int s = 0; s < ns; s++) S.roff[s] = (ro && P.margin <= ro[ns] && !(getenv("RR_NO_PAIR_CULL") && atoi(getenv("RR_NO_PAIR_CULL")))) ? ro[s] : INFINITY;
-    }
-    NEED(ip = b.i32("shape_ne", ns)); memcpy(S.ne, ip, ns * 4);
-    NEED(f = b.f32("shape_edges", ns * EMAXC * 12)); memcpy(S.edges, f, (size_t)ns * EMAXC * 12 * 4);
-    for (int s = 0; s < ns; s++) if (S.ne[s] < 0 || S.ne[s] > EMAXC) { rr_destroy(e); return fail(RR_EMODEL, "rr_create: bad shape_ne"); }
-    int np = 0, s_obj0 = n_static + n_robot;
-    for (int i = 0; i < P.nobj; i++) for (int s = 0; s < n_static; s++) { S.pair_a[np] = s_obj0 + i; S.pair_b[np++] = s; }
-    for (int i = 0; i < P.nobj; i++) for (int j = i + 1; j < P.nobj; j++) { S.pair_a[np] = s_obj0 + i; S.pair_b[np++] = s_obj0 + j; }
-    for (int r = 0; r < n_robot; r++) for (int s = 0; s < 2; s++) { S.pair_a[np] = n_static + r; S.pair_b[np++] = s; }
-    for (int r = 0; r < n_robot; r++) for (int i = 0; i < P.nobj; i++) { S.pair_a[np] = n_static + r; S.pair_b[np++] = s_obj0 + i; }
-    P.npairs = np;
-    e->n_shapes = ns;
-    if (ns > CSHAPES) { rr_destroy(e); return fail(RR_EMODEL, "rr_create: more collision shapes than k_collide stages in LDS"); }
-    for (int k = 0; k < np; k++) {
-        const int sa = S.pair_a[k], sb = S.pair_b[k];
-        S.pair_meta[k][0] = S.otype[sa] == 0 ? -1 : (S.otype[sa] == 1 ? S.oidx[sa] : 16 + S.oidx[sa]);
-        S.pair_meta[k][1] = S.otype[sb] == 0 ? -1 : (S.otype[sb] == 1 ? S.oidx[sb] : 16 + S.oidx[sb]);
-        S.pair_meta[k][2] = S.link[sa]; S.pair_meta[k][3] = 0;
-        const float ma[4] = {S.fric[sa], S.rest[sa], S.roll[sa], S.spin[sa]}, mb[4] = {S.fric[sb], S.rest[sb], S.roll[sb], S.spin[sb]};
-        pair_materials(ma, mb, S.pair_mat[k]);
-        e->pair_shapes.push_back(sa); e->pair_shapes.push_back(sb);
-    }
-    for (int s = 0; s < ns; s++) {
-        e->shape_mat.insert(e->shape_mat.end(), {S.fric[s], S.rest[s], S.roll[s], S.spin[s]});
-        e->shape_obj.push_back(S.otype[s] == 2 && S.oidx[s] >= 0 && S.oidx[s] < P.nobj ? S.oidx[s] : -1);
-    }
-    // the default dynamics of every env: the blob's mass and inertia of an object, the materials of its first collision shape
-    // (the model has one per object), and the blob's pair table
-    e->dyn.assign((size_t)N * P.nobj * 8, 0.0f);
-    for (int i = 0; i < P.nobj; i++) {
-        float row[8] = {B.obj_mass[i], B.obj_inertia[i][0], B.obj_inertia[i][1], B.obj_inertia[i][2], 0.0f, 0.0f, 0.0f, 0.0f};
-        for (int s = ns - 1; s >= 0; s--) if (e->shape_obj[s] == i) memcpy(row + 4, &e->shape_mat[4 * s], 16);
-        for (int n = 0; n < N; n++) memcpy(&e->dyn[((size_t)n * P.nobj + i) * 8], row, 32);
-    }
-    // the default actuators of every env: the handle's motor constants, the blob's joint damping
-    for (int j = 0; j < NB; j++) {
-        const float row[4] = {P.kp, P.kd, upstream(cfg->motor_max_force, 100000.0f), B.damping[j]};
-        memcpy(e->act_default[j], row, 16);
-    }
-    e->act.resize((size_t)N * NB * 4);
-    for (int n = 0; n < N; n++) memcpy(&e->act[(size_t)n * NB * 4], e->act_default, sizeof e->act_default);
-    e->pair_host.resize((size_t)N * np * 4);
-    for (int n = 0; n < N; n++) memcpy(&e->pair_host[(size_t)n * np * 4], S.pair_mat, (size_t)np * 16);
-
-    // k_collide's warm-start matching looks for the previous contacts of the same bodies (bodyA, bodyB, linkA) among the
-    // pairs pair-2 .. pair+2 only: pairs with equal keys must form runs of at most three consecutive pairs (one collision shape
-    // per robot link against table / shelf, one per object against the three statics)
-    for (int k = 0; k < np; k++)
-        for (int j = 0; j < np; j++) {
-            const bool same = S.pair_meta[k][0] == S.pair_meta[j][0] && S.pair_meta[k][1] == S.pair_meta[j][1] && S.pair_meta[k][2] == S.pair_meta[j][2];
-            if (same && std::abs(k - j) > 2) { rr_destroy(e); return fail(RR_EMODEL, "rr_create: collision pairs of the same bodies are more than two apart in the pair table (warm-start matching window)"); }
-        }
-
-    // render model
-    RenderModel &RM = e->RM;
-    RM.ni = ni; RM.nt = nt; RM.W = cfg->width; RM.H = cfg->height; RM.nl = nl;
-    // Raster tiles of <= TILE_PIX pixels: full-width strips up to 128 columns (the 128 x 128 benchmark camera: four strips of 32
-    // rows); 64 x 64 squares for wider images -- a cluster of the arm is ~25 pixels across at 320 x 240 and met three of the
-    // 12-row strips a full-width tile would be there (set-up work x 3.1; squares: x 1.9).  RR_TILE_W overrides (A/B, tests).
-    RM.tile_w = RM.W <= 128 ? RM.W : 64;
-    if (getenv("RR_TILE_W")) { const int tw_ = atoi(getenv("RR_TILE_W")); if (tw_ >= 4 && tw_ <= RM.W && tw_ <= TILE_PIX) RM.tile_w = tw_; }
-    RM.ntx = (RM.W + RM.tile_w - 1) / RM.tile_w;
-    RM.tile_h = TILE_PIX / RM.tile_w; if (RM.tile_h > RM.H) RM.tile_h = RM.H;
-    RM.ntiles = RM.ntx * ((RM.H + RM.tile_h - 1) / RM.tile_h);
-    RM.tile_xbits = 0; while ((1 << RM.tile_xbits) < RM.tile_w) RM.tile_xbits++;
-    RM.w_magic = (unsigned)((0x100000000ull + (unsigned long long)RM.tile_w - 1) / (unsigned long long)RM.tile_w);
-    if (RM.W > 1024 || RM.H > 1024 || RM.ntiles > 255) { rr_destroy(e); *out = nullptr; return fail(RR_EINVAL, "rr_create: image too large (checked on entry)"); }
-    NEED(ip = b.i32("inst_owner", ni * 4));
-    for (int i = 0; i < ni; i++) { RM.in_otype[i] = ip[4 * i]; RM.in_oidx[i] = ip[4 * i + 1]; RM.in_uid[i] = ip[4 * i + 2]; RM.in_tex[i] = ip[4 * i + 3]; }
-    NEED(f = b.f32("inst_color", ni * 3)); memcpy(RM.in_color, f, (size_t)ni * 12);
-    NEED(ip = b.i32("tex_info", ntex * 3));
-    for (int t = 0; t < ntex; t++) { RM.tex_off[t] = ip[3 * t]; RM.tex_w[t] = ip[3 * t + 1]; RM.tex_h[t] = ip[3 * t + 2]; }
-    {   // a one-texel texture (the arm's colours: tools/compile_model.py stores uniform images as 1 x 1) travels with the instance
-        // constants -- width -1, the texel in place of the offset: its fragments fetch neither texture coordinates nor texels
-        size_t tb_ = 0;
-        const uint8_t *tx_ = b.u8("tex_data", &tb_);
-        NEED(tx_);
-        for (int t = 0; t < ntex; t++)
-            if (RM.tex_w[t] == 1 && RM.tex_h[t] == 1 && (size_t)RM.tex_off[t] * 4 + 4 <= tb_) {
-                uint32_t px; memcpy(&px, tx_ + (size_t)RM.tex_off[t] * 4, 4);
-                RM.tex_off[t] = (int)px; RM.tex_w[t] = -1;
-            }
-    }
-    NEED(ip = b.i32("link_body", nl)); memcpy(RM.link_body, ip, nl * 4);
-    NEED(f = b.f32("link_pos", nl * 3)); memcpy(RM.link_pos, f, (size_t)nl * 12);
-    NEED(f = b.f32("link_rot", nl * 9)); memcpy(RM.link_rot, f, (size_t)nl * 36);
-    {
-        const int32_t *ir;
-        NEED(ir = b.i32("inst_range", ni * 2));
-        int n_static_inst = dims[10];
-        RM.first_dynamic_tri = (n_static_inst < ni) ? ir[2 * n_static_inst] : nt;
-    }
-    memcpy(e->table_pos, table_pos, sizeof e->table_pos);
-    look_at_persp(RM.VP, table_pos, RM.W, RM.H);
-    frustum_plane_norms(RM, RM.VP, RM.plane_norm, RM.tile_plane);
-    e->n_inst_used = ni - (NOBJ - P.nobj);
-
-    // device allocations
+    HIPCHK(hipSetDevice(cfg.device));
+    static_cast<ModelTables &>(*e) = std::move(static_cast<ModelTables &>(M));
+    e->set = set;
+    if (hipHostMalloc((void **)&e->h_hcount, 4 * sizeof(int), hipHostMallocMapped) == hipSuccess) { e->h_hcount[0] = 0; e->h_hcount[1] = 0; e->h_hcount[2] = -1; e->h_hcount[3] = 0; } else e->h_hcount = nullptr;
+    const SimParams &P = e->P;
+    const RenderModel &RM = e->RM;
+    const int N = P.N, nt = RM.nt, np = P.npairs;
     DevPtrs &D = e->D;
-    int rc;
-#define ALLOC(ptr, count) if ((rc = dev_alloc(e, &(ptr), (count))) != RR_OK) { rr_destroy(e); return rc; }
+#define RRCHK(x) do { const int rc_ = (x); if (rc_ != RR_OK) return rc_; } while (0)
+#define ALLOC(ptr, count) RRCHK(dev_alloc(e, &(ptr), (count)))
     ALLOC(D.state, (size_t)ST_TOTAL * N);
     ALLOC(D.scratch, (size_t)S_TOTAL * N);
     for (int f = 0; f < 2; f++) {
@@ -568,40 +599,23 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
         ALLOC(F.clist, (size_t)N * MAXC * 3); ALLOC(F.ccount, (size_t)N); ALLOC(F.cwarm, (size_t)N * MAXC);
         ALLOC(F.hgflag, (size_t)N); ALLOC(F.hlist, (size_t)N); ALLOC(F.hcount, (size_t)4); ALLOC(F.hlist2, (size_t)N); ALLOC(F.hcount2, (size_t)4);
     }
-    e->cur = 0; e->la_valid = false;
     bind_frames(e);
     ALLOC(D.cforce, (size_t)N * MAXC);
-    {   // the body lanes' constants (k_prep16)
-        float tab[NB * BT_STRIDE] = {0};
-        for (int b = 0; b < NB; b++) {
-            float *t = tab + b * BT_STRIDE;
-            for (int k = 0; k < 3; k++) { t[BT_COM + k] = B.com[b][k]; t[BT_AXIS + k] = B.axis[b][k]; }
-            for (int k = 0; k < 6; k++) t[BT_INERTIA + k] = B.inertia[b][k];
-            t[BT_MASS] = B.mass[b]; t[BT_DAMP] = B.damping[b];
-        }
-        float *bt = nullptr;
-        ALLOC(bt, (size_t)NB * BT_STRIDE);
-        if (hipMemcpy(bt, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) { rr_destroy(e); return fail(RR_EDEVICE, "rr_create: upload of the body table failed"); }
-        D.body_tab = bt;
-    }
+    RRCHK(dev_copy(e, &D.body_tab, M.body_tab, (size_t)NB * BT_STRIDE));
     ALLOC(D.collide_cost, (size_t)N); ALLOC(D.collide_bin, (size_t)N); ALLOC(D.collide_perm, (size_t)8 * ((N + 7) / 8));      // (zeroed: the first order is arbitrary)
     ALLOC(D.ccount_pub, (size_t)N); ALLOC(D.class_pub, (size_t)N);
-    e->D.hcount_host = nullptr;
-    if (e->h_hcount && hipHostGetDevicePointer((void **)&e->D.hcount_host, e->h_hcount, 0) != hipSuccess) e->D.hcount_host = nullptr;
+    if (e->h_hcount && hipHostGetDevicePointer((void **)&D.hcount_host, e->h_hcount, 0) != hipSuccess) D.hcount_host = nullptr;
     ALLOC(D.timestep, (size_t)N);
     ALLOC(D.errflags, (size_t)N);
     ALLOC(D.obj_home, (size_t)NOBJ * 7 * N);
     {
-        float *od_ = nullptr; float4 *pm_ = nullptr;
+        float *od_ = nullptr; float4 *pm_ = nullptr; float *ea_ = nullptr;
         ALLOC(od_, (size_t)NOBJ * 4 * N); ALLOC(pm_, (size_t)N * np);
         D.obj_dyn = od_; D.pair_mat = pm_;
-        if ((rc = upload_dynamics(e)) != RR_OK) { rr_destroy(e); return rc; }
-    }
-    {
-        float *ea_ = nullptr;
+        RRCHK(upload_dynamics(e));
         ALLOC(ea_, (size_t)NB * 4 * N);
         D.env_act = ea_;
-        if ((rc = upload_actuators(e)) != RR_OK) { rr_destroy(e); return rc; }
+        RRCHK(upload_actuators(e));
     }
     ALLOC(D.grows, (size_t)N * GP_RECS * 16);        // (zeroed: the dummy block / contact records stay all zero)
     ALLOC(D.cmd, (size_t)N * 9);
@@ -614,68 +628,21 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
     const size_t npx = (size_t)N * RM.W * RM.H;
     ALLOC(D.rgb, npx * 3);
     ALLOC(D.depth, npx);
-    if (!(cfg->flags & RR_FLAG_NO_MASK)) ALLOC(D.mask, npx);
+    if (!(cfg.flags & RR_FLAG_NO_MASK)) ALLOC(D.mask, npx);
     ALLOC(e->state_aos, (size_t)N * NSTATE);
     ALLOC(e->mask_dev, (size_t)N);
-    ALLOC(e->link_out, (size_t)N * nl * 7);
-    {   // geometry: positions SoA [9][NT], normals/uv AoS
-        const float *tp, *tn, *tu; const int32_t *ti;
-        NEED(tp = b.f32("tri_pos", (size_t)nt * 9)); NEED(tn = b.f32("tri_nrm", (size_t)nt * 9));
-        NEED(tu = b.f32("tri_uv", (size_t)nt * 6)); NEED(ti = b.i32("tri_inst", nt));
-        std::vector<float> soa((size_t)nt * 9);
-        for (int t = 0; t < nt; t++) for (int k = 0; k < 9; k++) soa[(size_t)k * nt + t] = tp[(size_t)t * 9 + k];
-        std::vector<float> rec((size_t)nt * 32, 0.0f);
-        for (int t = 0; t < nt; t++) {
-            float *r = &rec[(size_t)t * 32];
-            memcpy(r, tp + (size_t)t * 9, 36); memcpy(r + 9, tn + (size_t)t * 9, 36); memcpy(r + 18, ti + t, 4);
-            memcpy(r + 20, tu + (size_t)t * 6, 24);          // (chunks 5, 6: only textured instances' fragments fetch them, load_tri_rec)
-        }
-        float *dp; float4 *drec; int *di; unsigned *dt_; ShapeData *ds;
-        ALLOC(dp, (size_t)nt * 9); ALLOC(drec, (size_t)nt * 8); ALLOC(di, (size_t)nt);
-        hipMemcpy(dp, soa.data(), (size_t)nt * 36, hipMemcpyHostToDevice);
-        hipMemcpy(drec, rec.data(), (size_t)nt * 128, hipMemcpyHostToDevice);
-        hipMemcpy(di, ti, (size_t)nt * 4, hipMemcpyHostToDevice);
-        size_t texbytes = 0;
-        const uint8_t *tex = b.u8("tex_data", &texbytes);
-        NEED(tex);
-        ALLOC(dt_, texbytes / 4 + 1);
-        hipMemcpy(dt_, tex, texbytes, hipMemcpyHostToDevice);
-        ALLOC(ds, 1);
-        hipMemcpy(ds, &S, sizeof S, hipMemcpyHostToDevice);
-        ALLOC(e->RM_dev, 1);
-        hipMemcpy(e->RM_dev, &e->RM, sizeof e->RM, hipMemcpyHostToDevice);
-        D.tri_pos = dp; D.tri_rec = drec; D.tri_inst = di; D.tex = dt_; D.shapes = ds;
-        {
-            const float *cs;
-            if (nt % 64 != 0 || nt / 64 > MAXWIN || nt >= (1 << 18)) { rr_destroy(e); return fail(RR_EMODEL, "rr_create: triangle count must be a multiple of the cluster size 64 and below 65536"); }
-            NEED(cs = b.f32("cluster_sphere", (size_t)(nt / 64) * 4));
-            {
-                const float *cvb; const int32_t *tv;
-                NEED(cvb = b.f32("cluster_verts", (size_t)nt * 3)); NEED(tv = b.i32("tri_vidx", nt));
-                std::vector<float> cvs((size_t)nt * 3);          // [cluster][64][3] -> [cluster][3][64]
-                for (int c = 0; c < nt / 64; c++)
-                    for (int v = 0; v < 64; v++)
-                        for (int k = 0; k < 3; k++) cvs[((size_t)c * 3 + k) * 64 + v] = cvb[((size_t)c * 64 + v) * 3 + k];
-                float *dcv; int *dtv;
-                ALLOC(dcv, (size_t)nt * 3); ALLOC(dtv, (size_t)nt);
-                hipMemcpy(dcv, cvs.data(), (size_t)nt * 12, hipMemcpyHostToDevice);
-                // (the corner indices go to the device as ds_bpermute byte addresses, index x 4 in each byte: one bit-field extract per
-                // corner in the window loop instead of a shift and a mask)
-                std::vector<int32_t> tv4((size_t)nt);
-                for (int t_ = 0; t_ < nt; t_++) {
-                    const int a0 = tv[t_] & 63, a1 = (tv[t_] >> 8) & 63, a2 = (tv[t_] >> 16) & 63;
-                    tv4[t_] = (a0 << 2) | (a1 << 10) | (a2 << 18);
-                }
-                hipMemcpy(dtv, tv4.data(), (size_t)nt * 4, hipMemcpyHostToDevice);
-                D.cluster_verts = dcv; D.tri_vidx = dtv;
-            }
-            float4 *dcs;
-            ALLOC(dcs, (size_t)nt / 64);
-            hipMemcpy(dcs, cs, (size_t)(nt / 64) * 16, hipMemcpyHostToDevice);
-            D.cluster_sphere = dcs;
-        }
-    }
-    for (int i = 0; i < 2 * RR_NUM_KERNELS; i++) hipEventCreate(&e->ev[i]);
+    ALLOC(e->link_out, (size_t)N * RM.nl * 7);
+    RRCHK(dev_copy(e, &D.tri_pos, M.soa.data(), (size_t)nt * 9));
+    RRCHK(dev_copy(e, &D.tri_rec, M.rec.data(), (size_t)nt * 8));
+    RRCHK(dev_copy(e, &D.tri_inst, M.tri_inst, (size_t)nt));
+    RRCHK(dev_copy(e, &D.tex, M.tex, M.tex_bytes / 4 + 1, M.tex_bytes));
+    RRCHK(dev_copy(e, &D.shapes, &M.S, 1));
+    ALLOC(e->RM_dev, 1);
+    HIPCHK(hipMemcpy(e->RM_dev, &e->RM, sizeof e->RM, hipMemcpyHostToDevice));
+    RRCHK(dev_copy(e, &D.cluster_verts, M.cvs.data(), (size_t)nt * 3));
+    RRCHK(dev_copy(e, &D.tri_vidx, M.tv4.data(), (size_t)nt));
+    RRCHK(dev_copy(e, &D.cluster_sphere, M.cluster_sphere, (size_t)nt / 64));
+    for (int i = 0; i < 2 * RR_NUM_KERNELS; i++) HIPCHK(hipEventCreate(&e->ev[i]));
     {
         // fork / join events order two streams of the same device: no timing, no system-scope fence (the cache writeback
         // and invalidation a default event performs when it is recorded costs ~6 us on the stream that records it)
@@ -690,16 +657,14 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
         // sensitive to it: with one unused stream created in front of `aux` (or of `aux2`) the headline step takes 0.89 ms instead of
         // 0.585, with one in front of each 0.585 again (round 6, NOTEBOOK.md B; tools/ubench/queue_probe.hip shows 50-70 us of extra
         // launch latency between some pairs of queues).  The order below is the one measured in bench.py's process, alone and behind an
-        // RCCL process group; RR_SKIP_QUEUES="a,b" creates a / b unused streams in front of aux / aux2 -- for a host process whose
-        // stream history differs (scratch/streams_check.py compares the settings on the spot).
-        int skip_a = 0, skip_b = 0;
-        if (getenv("RR_SKIP_QUEUES")) sscanf(getenv("RR_SKIP_QUEUES"), "%d,%d", &skip_a, &skip_b);
+        // RCCL process group; Settings::skip_queues creates a / b unused streams in front of aux / aux2 -- for a host process whose
+        // stream history differs (scratch/streams_check.py compares the settings on the spot).  Do not reorder these calls.
         auto skip_queues = [&](int n) { for (int i = 0; i < n && i < 8; i++) { hipStream_t unused; if (hipStreamCreateWithFlags(&unused, hipStreamNonBlocking) != hipSuccess) return false; e->unused_streams.push_back(unused); } return true; };
-        if (!skip_queues(skip_a) || !side_stream(&e->aux) || hipEventCreateWithFlags(&e->ev_fork, evf) != hipSuccess ||
+        if (!skip_queues(set.skip_queues[0]) || !side_stream(&e->aux) || hipEventCreateWithFlags(&e->ev_fork, evf) != hipSuccess ||
             hipEventCreateWithFlags(&e->ev_join, evf) != hipSuccess || hipEventCreateWithFlags(&e->ev_dyn, evf) != hipSuccess ||
-            !skip_queues(skip_b) || !side_stream(&e->aux2) || hipEventCreateWithFlags(&e->ev_join2, evf) != hipSuccess ||
+            !skip_queues(set.skip_queues[1]) || !side_stream(&e->aux2) || hipEventCreateWithFlags(&e->ev_join2, evf) != hipSuccess ||
             hipEventCreateWithFlags(&e->ev_vsolved, evf) != hipSuccess || hipEventCreateWithFlags(&e->ev_hsolved, evf) != hipSuccess ||
-            hipEventCreateWithFlags(&e->ev_rast, evf) != hipSuccess) { rr_destroy(e); return fail(RR_EDEVICE, "rr_create: side stream"); }
+            hipEventCreateWithFlags(&e->ev_rast, evf) != hipSuccess) return fail(RR_EDEVICE, "rr_create: side stream");
     }
     e->field_ptr[RR_F_JOINTS] = D.joints; e->field_bytes[RR_F_JOINTS] = (size_t)N * 9 * 4;
     e->field_ptr[RR_F_TOUCH] = D.touch; e->field_bytes[RR_F_TOUCH] = (size_t)N * 4 * 4;
@@ -715,35 +680,64 @@ int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, v
     e->field_ptr[RR_F_PREP] = D.scratch; e->field_bytes[RR_F_PREP] = (size_t)N * S_TOTAL * 4;
     static_assert(S_TOTAL == 378, "include/realrobot.h documents RR_F_PREP as 378 floats per env");
     refresh_frame_fields(e);
-    *out = e;
-    for (int i = 0; i < NOBJ; i++) { const int rh = rr_set_object_home(e, -1, i, e->B.obj_pose0[i]); if (rh != RR_OK) { rr_destroy(e); *out = nullptr; return rh; } }
-    int r = rr_reset(e, nullptr);
-    if (r != RR_OK) { rr_destroy(e); *out = nullptr; return r; }
-    {
-        const size_t spx = (size_t)RM.W * RM.H;
-        if ((r = dev_alloc(e, &e->D.static_rgb, spx * 3)) != RR_OK || (r = dev_alloc(e, &e->D.static_depth, spx)) != RR_OK ||
-            (r = dev_alloc(e, &e->D.static_mask, spx)) != RR_OK || (r = dev_alloc(e, &e->D.frag_count, (size_t)N * RM.ntiles)) != RR_OK ||
-            (r = dev_alloc(e, &e->D.frag_list, (size_t)N * RM.ntiles * TILE_PIX, false)) != RR_OK) { rr_destroy(e); *out = nullptr; return r; }
-        if (!getenv("RR_NO_RASTER_ORDER") && (long long)N * RM.ntiles >= 2048 && (long long)N * RM.ntiles <= (1 << 20) && N < (1 << 24)) {
-            if ((r = dev_alloc(e, &e->D.item_cost, (size_t)N * RM.ntiles)) != RR_OK || (r = dev_alloc(e, &e->D.item_bin, (size_t)N * RM.ntiles)) != RR_OK || (r = dev_alloc(e, &e->item_perm, (size_t)8 * ((N + 7) / 8) * RM.ntiles)) != RR_OK) { rr_destroy(e); *out = nullptr; return r; }
-        }
-        if ((r = dev_alloc(e, &e->D.static_vis_out, spx)) != RR_OK) { rr_destroy(e); *out = nullptr; return r; }
-        e->field_ptr[RR_F_FRAG_COUNT] = e->D.frag_count;
-        e->shared_static_vis = e->D.static_vis_out; e->shared_static_rgb = e->D.static_rgb;
-        e->shared_static_depth = e->D.static_depth; e->shared_static_mask = e->D.static_mask;
-        if ((r = build_static_layer(e)) != RR_OK) { rr_destroy(e); *out = nullptr; return r; }
+    for (int i = 0; i < NOBJ; i++) RRCHK(rr_set_object_home(e, -1, i, e->B.obj_pose0[i]));
+    RRCHK(rr_reset(e, nullptr));
+    const size_t spx = (size_t)RM.W * RM.H, items = (size_t)N * RM.ntiles;
+    ALLOC(D.static_rgb, spx * 3); ALLOC(D.static_depth, spx); ALLOC(D.static_mask, spx); ALLOC(D.frag_count, items);
+    RRCHK(dev_alloc(e, &D.frag_list, items * TILE_PIX, false));
+    if (set.raster_order && items >= 2048 && items <= (1 << 20) && N < (1 << 24)) {
+        ALLOC(D.item_cost, items); ALLOC(D.item_bin, items); ALLOC(e->item_perm, (size_t)8 * ((N + 7) / 8) * RM.ntiles);
     }
+    ALLOC(D.static_vis_out, spx);
+#undef ALLOC
+    e->field_ptr[RR_F_FRAG_COUNT] = D.frag_count;
+    e->shared_static_vis = D.static_vis_out; e->shared_static_rgb = D.static_rgb;
+    e->shared_static_depth = D.static_depth; e->shared_static_mask = D.static_mask;
+    RRCHK(build_static_layer(e));
+#undef RRCHK
     // the 256-thread form of k_solve (heavy solver groups, four per workgroup) and the light envs' solve with an object wave (five
     // waves, sixteen envs) ask for 158 KiB of dynamic LDS: only the heavy / light split launches them, and a device that cannot grant
     // it runs without the split (same results, one launch)
     const int lds_split = (int)(4 * SGRP * LF_TOTAL * sizeof(float));
-    if (e->split_heavy && (hipFuncSetAttribute((const void *)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, lds_split) != hipSuccess ||
+    if (e->set.split_heavy && (hipFuncSetAttribute((const void *)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, lds_split) != hipSuccess ||
                            hipFuncSetAttribute((const void *)k_solve_rs, hipFuncAttributeMaxDynamicSharedMemorySize, lds_split) != hipSuccess ||
                            hipFuncSetAttribute((const void *)k_solve_light_ow, hipFuncAttributeMaxDynamicSharedMemorySize, lds_split) != hipSuccess)) {
         (void)hipGetLastError();
-        e->split_heavy = false;
+        e->set.split_heavy = false;
     }
-    if (hipGetLastError() != hipSuccess) { rr_destroy(e); *out = nullptr; return fail(RR_EDEVICE, "rr_create: device error during set-up"); }
+    if (hipGetLastError() != hipSuccess) return fail(RR_EDEVICE, "rr_create: device error during set-up");
+    return RR_OK;
+}
+
+int rr_create(const rr_config *cfg, const void *model_blob, size_t blob_bytes, void *stream, rr_env **out) {
+    if (!cfg || !model_blob || !out) return fail(RR_EINVAL, "rr_create: null argument");
+    *out = nullptr;
+    if (cfg->abi_version != RR_ABI_VERSION) return fail(RR_EINVAL, "rr_create: abi_version mismatch");
+    if (cfg->num_envs < 1) return fail(RR_EINVAL, "rr_create: num_envs < 1");
+    if ((unsigned long long)cfg->num_envs * GP_ENV_BYTES + 4096ull >= (1ull << 32)) return fail(RR_EINVAL, "rr_create: more than 33222 envs per rr_env (32-bit byte offsets of the solver's row store)");
+    if (cfg->n_objects < 1 || cfg->n_objects > NOBJ) return fail(RR_EINVAL, "rr_create: n_objects must be 1..3");
+    for (float v : {cfg->motor_kp, cfg->motor_kd, cfg->motor_max_force, cfg->warmstart, cfg->lin_damping, cfg->ang_damping, cfg->dt, cfg->erp, cfg->margin})
+        if (!std::isfinite(v)) return fail(RR_EINVAL, "rr_create: non-finite motor / solver constant");
+    if (cfg->solver_flags & ~(RR_SOLVER_NO_RATE_LIMIT | RR_SOLVER_IK_SINGLE_SEED)) return fail(RR_EINVAL, "rr_create: unknown solver_flags bit");
+    if (cfg->width < 4 || cfg->height < 1 || cfg->width % 4 != 0 || cfg->width > 1024 || cfg->height > 1024)
+        return fail(RR_EINVAL, "rr_create: width must be a multiple of 4 in [4,1024], height in [1,1024] (10-bit box origins in the rasteriser's records)");
+    const Settings set = read_settings();
+    if (tile_layout(cfg->width, cfg->height, set.tile_w).ntiles > 255)      // (the tile index is 8 bits with one sentinel)
+        return fail(RR_EINVAL, "rr_create: image too large: more than 255 raster tiles of 4096 pixels (e.g. 1024 x 960 fits, 1024 x 961 does not)");
+    Blob b;
+    if (!b.init(model_blob, blob_bytes)) return fail(RR_EMODEL, "rr_create: bad model blob header");
+    const std::unique_ptr<HostModel> M(new HostModel());
+    const int rm = parse_model(*cfg, b, set, *M);
+    if (rm != RR_OK) return rm;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(RR_EDEVICE, "rr_create: no HIP device available (this library has no CPU fallback)");
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(RR_EINVAL, "rr_create: bad device ordinal");
+    struct Destroy { void operator()(rr_env *p) const { rr_destroy(p); } };
+    std::unique_ptr<rr_env, Destroy> e(new rr_env());       // the one owner of the half-built handle
+    const int rc = create_device(e.get(), *cfg, set, *M, stream);
+    if (rc != RR_OK) return rc;
+    *out = e.release();
     return RR_OK;
 }
 
@@ -936,7 +930,6 @@ int rr_set_object_poses(rr_env *e, const float *poses_host, const uint8_t *env_m
     return RR_OK;
 }
 
-static bool g_debug_sync = getenv("RR_DEBUG_SYNC") != nullptr;
 #define TIMED(id, launch)                                                   \
     do {                                                                    \
         if (e->timing) hipEventRecord(e->ev[2 * (id)], e->stream);          \
@@ -957,7 +950,7 @@ static int ensure_images(rr_env *e, DevPtrs &D) {
     const int N = e->P.N;
     const ImageOut io = env_images(e);
     const int copy_blocks = std::min(16, (e->RM.W * e->RM.H / 4 + COPY_THREADS - 1) / COPY_THREADS);
-    if (!e->images_valid || e->full_copy) {
+    if (!e->images_valid || e->set.full_copy) {
         DevPtrs Dall = D;
         if (!e->images_valid) Dall.render_flags = nullptr;      // first frame: every env, flagged or not -- all images become valid
         TIMED(5, hipLaunchKernelGGL(k_static_copy, dim3(copy_blocks, std::min(N, 65535)), dim3(COPY_THREADS), 0, e->stream, e->RM_dev, Dall, io, 1, N,
@@ -979,11 +972,6 @@ static int ensure_images(rr_env *e, DevPtrs &D) {
     return 1;
 }
 
-// The three render kernels for the envs selected by `sel` (env_selected) on `st`.  The images persist in HBM from frame to
-// frame: only the pixels of the previous frame's fragment lists are put back to the static layer (`restore`), DESIGN.md 5.
-// `setup_done`: the instances of these envs are set up already (by the light solve).
-// Visibility pass of the envs selected by `sel` (all, or the light ones): one workgroup per (env, tile), dispatched in the order of the
-// last frame's costs when the batch is large enough to matter; the shading launch behind it makes the next order (DESIGN.md 5).
 // The first failed event / wait / bound launch of the step path (HIPQ, LAUNCH_EV), reported once by the entry point that queued it.
 static int step_status(rr_env *e) {
     if (e->step_err == hipSuccess) return RR_OK;
@@ -992,6 +980,8 @@ static int step_status(rr_env *e) {
     e->la_valid = false;                 // (whatever the look-ahead queued is not to be trusted)
     return fail(RR_EDEVICE, msg);
 }
+// Visibility pass of the envs selected by `sel` (all, or the light ones): one workgroup per (env, tile), dispatched in the order of the
+// last frame's costs when the batch is large enough to matter; the shading launch behind it makes the next order (DESIGN.md 5).
 static void launch_raster(rr_env *e, const DevPtrs &D, int restore, int sel, hipStream_t st) {
     const int N = e->P.N, nt = e->RM.ntiles;
     DevPtrs Do = D;
@@ -1017,7 +1007,10 @@ static void launch_shade(rr_env *e, const DevPtrs &D, const ImageOut &io, int se
     LAUNCH_EV(done, k_shade, dim3(N + (ord ? 1 : 0), e->RM.ntiles, SHADE_SPLIT), dim3(SHADE_THREADS), 0, st, e->RM_dev, D, io, 1, 0, sel, ord ? N : 0, e->item_perm);
     if (ord) { e->ord_pending = false; e->ord_valid = true; }
 }
-// (done: an event that completes with the last launch of the untimed form)
+// The three render kernels for the envs selected by `sel` (env_selected) on `st`.  The images persist in HBM from frame to
+// frame: only the pixels of the previous frame's fragment lists are put back to the static layer (`restore`), DESIGN.md 5.
+// `setup_done`: the instances of these envs are set up already (by the light solve).
+// `done`: an event that completes with the last launch of the untimed form.
 static void launch_render(rr_env *e, const DevPtrs &D, int restore, int sel, hipStream_t st, bool timed, bool setup_done = false, hipEvent_t done = nullptr) {
     const int N = e->P.N;
     const ImageOut io = env_images(e);
@@ -1059,22 +1052,22 @@ static int do_render(rr_env *e, bool use_flags) {
 
 // ---- look-ahead: the state part of the NEXT step (k_prep_a -> k_collide, k_prep_b beside them) ------------------------------
 // Per-class launches (sel: pick_env) cover N work items whatever the class.
-#define COOP_ALL_MAX 1024   // up to this many envs a step that solves all envs in one launch gives every env its own wave (RR_COOP_ALL=0: four to a wave)
+#define COOP_ALL_MAX 1024   // up to this many envs a step that solves all envs in one launch gives every env its own wave (Settings::coop_all off: four to a wave)
 #define COLLIDE_ORDER_MIN_N 1024   // up to this many envs all collision workgroups are resident at once: no order needed
 #define SMALL_N_MAX 64      // up to this many envs a step without the three-stream split runs as one chain on the main stream (rr_step)
 // (collision pass in cost order: the eight sorting workgroups ride on the preparation launch in front of it -- batches of more than
-// one round of collision workgroups, all envs; RR_COLLIDE_ORDER=0: env order)
-static inline bool collide_in_order(const rr_env *e, int sel) { return sel == 0 && e->collide_ordered && e->epb == 64 && e->P.N > COLLIDE_ORDER_MIN_N; }
+// one round of collision workgroups, all envs; Settings::collide_ordered off: env order)
+static inline bool collide_in_order(const rr_env *e, int sel) { return sel == 0 && e->set.collide_ordered && e->epb == 64 && e->P.N > COLLIDE_ORDER_MIN_N; }
 static inline dim3 prep_grid(const rr_env *e, int sel) { return dim3(env_grid(e).x + (collide_in_order(e, sel) ? 8 : 0)); }
 static inline dim3 prep16_grid(const rr_env *e, int sel, bool order);
 static void launch_prep_a(rr_env *e, int sel, int zero_counts, hipStream_t st, hipEvent_t done = nullptr) {
-    if (e->prep_scalar) LAUNCH_EV(done, k_prep_a, prep_grid(e, sel), dim3(e->epb), 0, st, e->B, e->P, e->D, sel, zero_counts, collide_in_order(e, sel) ? e->P.N : 0);
+    if (e->set.prep_scalar) LAUNCH_EV(done, k_prep_a, prep_grid(e, sel), dim3(e->epb), 0, st, e->B, e->P, e->D, sel, zero_counts, collide_in_order(e, sel) ? e->P.N : 0);
     else LAUNCH_EV(done, k_prep_a16, prep16_grid(e, sel, true), dim3(128), 0, st, e->B, e->P, e->D, sel, zero_counts, collide_in_order(e, sel) ? e->P.N : 0);
 }
-// (k_prep16: one env per 16-lane group, four envs per 64-thread workgroup; RR_PREP_SCALAR=1: the thread-per-env kernels)
+// (k_prep16: one env per 16-lane group, four envs per 64-thread workgroup; Settings::prep_scalar: the thread-per-env kernels)
 static inline dim3 prep16_grid(const rr_env *e, int sel, bool order) { return dim3((e->P.N + P16_ENVS - 1) / P16_ENVS + (order && collide_in_order(e, sel) ? 8 : 0)); }
 static void launch_prep_b(rr_env *e, int sel, hipStream_t st, hipEvent_t done = nullptr) {
-    if (e->prep_scalar) LAUNCH_EV(done, k_prep_b, env_grid(e), dim3(e->epb), 0, st, e->B, e->P, e->D, sel);
+    if (e->set.prep_scalar) LAUNCH_EV(done, k_prep_b, env_grid(e), dim3(e->epb), 0, st, e->B, e->P, e->D, sel);
     else LAUNCH_EV(done, k_prep_b16, prep16_grid(e, sel, false), dim3(64), 0, st, e->B, e->P, e->D, sel);
 }
 static void launch_collide(rr_env *e, int sel, hipStream_t st, hipEvent_t done = nullptr) {
@@ -1083,7 +1076,7 @@ static void launch_collide(rr_env *e, int sel, hipStream_t st, hipEvent_t done =
     LAUNCH_EV(done, k_collide, grid, dim3(COLLIDE_THREADS), 0, st, e->P, e->D, e->n_shapes, sel, ordered ? 1 : 0);
 }
 static void launch_prep_ab(rr_env *e, int sel, hipStream_t st) {
-    if (e->prep_scalar) hipLaunchKernelGGL(k_prep_ab, prep_grid(e, sel), dim3(e->epb), 0, st, e->B, e->P, e->D, sel, collide_in_order(e, sel) ? e->P.N : 0);
+    if (e->set.prep_scalar) hipLaunchKernelGGL(k_prep_ab, prep_grid(e, sel), dim3(e->epb), 0, st, e->B, e->P, e->D, sel, collide_in_order(e, sel) ? e->P.N : 0);
     else hipLaunchKernelGGL(k_prep_ab16, prep16_grid(e, sel, true), dim3(128), 0, st, e->B, e->P, e->D, sel, collide_in_order(e, sel) ? e->P.N : 0);
 }
 static void launch_prep_serial(rr_env *e, int sel, int zero_counts) {
@@ -1154,7 +1147,7 @@ static int pin_acquire(rr_env *e, char **slot, int *idx) {
 //   3. mostly heavy envs, or a step without camera: one solve launch for everybody, look-ahead beside the render (step_single());
 //   3b. a step without camera of a large batch with a long very heavy list: the classes side by side, the very heavy envs a wave each (step_single());
 //   4. a handful of envs (the gym facade): one chain on the main stream, the mirror in front of the look-ahead (step_single());
-//   5. the reference: everything in line (RR_NO_SPLIT / RR_NO_LOOKAHEAD; the timing leg of bench.py runs placement 1's launches one
+//   5. the reference: everything in line (Settings::split_heavy / lookahead off; the timing leg of bench.py runs placement 1's launches one
 //      after the other under their timers).
 #define LA_VH_MAX 64         // look-ahead behind the very heavy envs' solve while their (lagged) number is at most this
 #define NORENDER_SPLIT_VH_MIN 64   // a step without camera runs its classes side by side from this many (lagged) very heavy envs on (step_single)
@@ -1212,7 +1205,7 @@ static int step_split(rr_env *e, const DevPtrs &D, int restore, bool ahead, int 
     // (the thread-per-env k_prep_ab needed a whole free SIMD for each of its 64 waves and sat in its queue until the visibility
     // pass' grid was exhausted -- which kept the collision pass, 39 KB of LDS per workgroup, out of the visibility pass' way;
     // k_prep_ab16 gets onto the machine at once, so the look-ahead is HELD behind the light envs' visibility pass by an event)
-    const bool la_after_raster = la_on_vh && !e->prep_scalar;
+    const bool la_after_raster = la_on_vh && !e->set.prep_scalar;
     if (la_on_vh && !la_after_raster) {
         HIPQ(hipStreamWaitEvent(e->aux2, e->ev_dyn, 0));
         HIPQ(hipStreamWaitEvent(e->aux2, e->ev_hsolved, 0));
@@ -1258,12 +1251,12 @@ static int step_split(rr_env *e, const DevPtrs &D, int restore, bool ahead, int 
 static int step_single(rr_env *e, bool overlap, bool ahead, int render_mode) {
     const int N = e->P.N;
     const size_t lds64 = (size_t)SGRP * LF_TOTAL * sizeof(float);
-    const bool small_n = N <= SMALL_N_MAX && e->split_heavy && !e->timing;
+    const bool small_n = N <= SMALL_N_MAX && e->set.split_heavy && !e->timing;
     if (small_n && N == 1) {
         launch_light_solve(e, nullptr, e->stream);
         launch_solve_class(e, 2, e->stream);
         launch_solve_class(e, 3, e->stream);
-    } else if (!render_mode && N > COOP_ALL_MAX && e->split_heavy && !e->timing && lagged_count(e, 1, 0) >= NORENDER_SPLIT_VH_MIN) {
+    } else if (!render_mode && N > COOP_ALL_MAX && e->set.split_heavy && !e->timing && lagged_count(e, 1, 0) >= NORENDER_SPLIT_VH_MIN) {
         // Placement 3b: a step without camera whose very heavy list is long (macro actions without the retina: 368 of 4 096 envs).  In the
         // one launch for everybody those envs are solved four to a wave, sixteen lanes building the rows of an env at the contact cap; side
         // by side on the three streams they get a wave each -- 0.765 -> 0.711 ms per step on the macro workload.  With a handful of
@@ -1279,7 +1272,7 @@ static int step_single(rr_env *e, bool overlap, bool ahead, int render_mode) {
         launch_light_solve(e, nullptr, e->stream);
         HIPQ(hipStreamWaitEvent(e->stream, e->ev_join, 0));
         HIPQ(hipStreamWaitEvent(e->stream, e->ev_join2, 0));
-    } else if (e->coop_all && N <= COOP_ALL_MAX && e->split_heavy)
+    } else if (e->set.coop_all && N <= COOP_ALL_MAX && e->set.split_heavy)
         TIMED(2, hipLaunchKernelGGL(k_solve, dim3((N + 3) / 4), dim3(256), lds64, e->stream, e->B, e->P, e->D, 0, 1));
     else
         TIMED(2, hipLaunchKernelGGL(k_solve, dim3((N + SGRP - 1) / SGRP), dim3(SGRP * 16), lds64, e->stream, e->B, e->P, e->D, 0, 0));
@@ -1329,8 +1322,8 @@ int rr_step(rr_env *e, const float *joint_cmd, int32_t cmd_on_device, int32_t re
     if (pin_idx >= 0) { HIPCHK(hipEventRecord(e->pin_ev[pin_idx], e->stream)); e->pin_used[pin_idx] = true; }
     const bool overlap = !e->timing;      // side streams in use (timing leg: everything on the main stream)
     // ---- bounded run-ahead (a batch: a handful of envs is waited for every step by its caller anyway)
-    const unsigned ahead_period = (unsigned)std::max(1, e->run_ahead / 2);
-    const bool bounded = e->run_ahead > 0 && N > SMALL_N_MAX && e->step_no % ahead_period == 0;      // (a marker step)
+    const unsigned ahead_period = (unsigned)std::max(1, e->set.run_ahead / 2);
+    const bool bounded = e->set.run_ahead > 0 && N > SMALL_N_MAX && e->step_no % ahead_period == 0;      // (a marker step)
     const int ahead_slot = (int)((e->step_no / ahead_period) & 1u);
     if (bounded) {
         if (!e->ahead_ev[ahead_slot]) HIPCHK(hipEventCreateWithFlags(&e->ahead_ev[ahead_slot], hipEventDisableTiming | hipEventDisableSystemFence));
@@ -1344,23 +1337,18 @@ int rr_step(rr_env *e, const float *joint_cmd, int32_t cmd_on_device, int32_t re
     e->D.cmd_in = (joint_cmd && cmd_on_device) ? joint_cmd : e->D.cmd;
     // (the number of heavy envs of a recent step, written to pinned host memory by the solve kernel without anybody waiting for it:
     // when most are heavy -- macro actions, every gripper pushing -- there is nothing to gain from the split)
-    const bool mostly_heavy = (long long)lagged_count(e, 0, 0) * 100 > (long long)N * e->split_max_pct;
-    const bool ahead = e->lookahead;            // this step ends with the state part of the next one
+    const bool mostly_heavy = (long long)lagged_count(e, 0, 0) * 100 > (long long)N * e->set.split_max_pct;
+    const bool ahead = e->set.lookahead;            // this step ends with the state part of the next one
     // (a step without camera runs all envs in one launch: its classes side by side measured 0.525 instead of 0.452 ms on config 2;
     // ONE env -- the gym facade -- renders in its chain on the main stream too: the split has nothing to overlap there)
-    if (render_mode && e->split_heavy && !mostly_heavy && !(N == 1 && !e->timing)) {
+    int rc;
+    if (render_mode && e->set.split_heavy && !mostly_heavy && !(N == 1 && !e->timing)) {
         DevPtrs D = e->D;
         if (render_mode != 2) D.render_flags = nullptr;
         const int restore = ensure_images(e, D);
-        const int rc = e->timing ? step_split_timed(e, D, restore, ahead, render_mode) : step_split(e, D, restore, ahead, render_mode);
-        if (rc != RR_OK) return rc;
-        HIPCHK(hipGetLastError());
-        if (bounded) HIPCHK(hipEventRecord(e->ahead_ev[ahead_slot], e->stream));
-        e->step_no++;
-        return step_status(e);
-    }
-    const int rc1 = step_single(e, overlap, ahead, render_mode);
-    if (rc1 != RR_OK) return rc1;
+        rc = e->timing ? step_split_timed(e, D, restore, ahead, render_mode) : step_split(e, D, restore, ahead, render_mode);
+    } else rc = step_single(e, overlap, ahead, render_mode);
+    if (rc != RR_OK) return rc;
     HIPCHK(hipGetLastError());
     if (bounded) HIPCHK(hipEventRecord(e->ahead_ev[ahead_slot], e->stream));
     e->step_no++;

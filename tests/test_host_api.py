@@ -116,6 +116,84 @@ def test_create_image_size_limit_matches_the_tile_rule(monkeypatch):
     assert re.search(r'e\.g\. (\d+) x (\d+) fits, (\d+) x (\d+) does not', src).groups() == fits + fails
 
 
+def _blob_entries(blob):
+    """name -> (byte position of the entry in the table, offset, nbytes): `RRMODEL1`, a u32 count at byte 8, the table at byte 16,
+    72 bytes an entry {name[32], dtype, ndim, shape[4], u64 offset, u64 nbytes} (Blob / BlobEntry in rr_host.inc)."""
+    import struct
+    assert blob[:8] == b'RRMODEL1'
+    out = {}
+    for i in range(struct.unpack_from('<I', blob, 8)[0]):
+        at = 16 + 72 * i
+        off, nbytes = struct.unpack_from('<QQ', blob, at + 56)
+        out[blob[at:at + 32].split(b'\0')[0].decode()] = (at, off, nbytes)
+    return out
+
+
+def _rename(blob, ent, name):
+    blob[ent[name][0]] ^= 0x20               # first letter to upper case: no entry of that name any more
+
+
+def _halve_nbytes(blob, ent, name):
+    import struct
+    struct.pack_into('<Q', blob, ent[name][0] + 64, ent[name][2] // 2)
+
+
+def _set_word(blob, ent, name, index, value):
+    import struct
+    struct.pack_into('<i', blob, ent[name][1] + 4 * index, value)
+
+
+@pytest.mark.parametrize('mutate, urdf, word', [
+    (lambda b, e: _rename(b, e, 'body_jpos'), 0, b'body_jpos'),
+    (lambda b, e: _halve_nbytes(b, e, 'shape_verts'), 0, b'shape_verts'),
+    (lambda b, e: _set_word(b, e, 'dims', 0, 10), 0, b'dims'),
+    (lambda b, e: _set_word(b, e, 'shape_ne', 0, 49), 0, b'shape_ne'),
+    (lambda b, e: _set_word(b, e, 'body_parent', 3, 0), 0, b'kinematic tree'),
+    (lambda b, e: _rename(b, e, 'body_inertia_urdf'), 1, b'body_inertia_urdf'),
+    (lambda b, e: _rename(b, e, 'body_inertia_urdf'), 0, None),
+], ids=['body_jpos-renamed', 'shape_verts-short', 'dims', 'shape_ne', 'body_parent', 'urdf-inertia-missing', 'urdf-inertia-unused'])
+def test_create_reports_a_malformed_model_before_it_looks_for_a_device(mutate, urdf, word):
+    """The model is parsed on the host before rr_create touches the device: a malformed blob returns RR_EMODEL with the
+    blob entry in the message and a null handle on any machine.  The last case is a valid model for its config (the
+    entry it lacks is not read): past the model checks, RR_EDEVICE without a GPU, a handle with one."""
+    L = nat.load_library()
+    blob = bytearray(nat.model_blob())
+    mutate(blob, _blob_entries(blob))
+    cfg = nat.Config()
+    cfg.abi_version, cfg.num_envs, cfg.n_objects, cfg.width, cfg.height = nat.RR_ABI_VERSION, 1, 1, 64, 64
+    cfg.use_urdf_inertia = urdf
+    h = C.c_void_p(0xdead)
+    rc = L.rr_create(C.byref(cfg), bytes(blob), len(blob), None, C.byref(h))
+    if word is not None:
+        assert rc == -3 and word in L.rr_last_error(), (rc, L.rr_last_error())      # RR_EMODEL
+        assert not h.value
+        return
+    import torch
+    if torch.cuda.is_available():
+        assert rc == 0 and h.value, (rc, L.rr_last_error())
+        assert L.rr_destroy(h) == 0
+    else:
+        assert rc == -2 and b'no CPU fallback' in L.rr_last_error() and not h.value, (rc, L.rr_last_error())
+
+
+def test_settings_reader_and_integration_table_name_the_same_variables():
+    """Every RR_* variable the library reads is read in one place, once, and INTEGRATION.md's table documents exactly those
+    (plus the ones the Python side reads)."""
+    src = open(os.path.join(ROOT, 'real_robots_amd', 'csrc', 'rr_host.inc')).read()
+    read = re.findall(r'getenv\("(RR_[A-Z0-9_]+)"\)', src)
+    assert len(read) == len(set(read)) > 0, sorted(read)
+    for inc in os.listdir(os.path.join(ROOT, 'real_robots_amd', 'csrc')):
+        if inc.endswith(('.inc', '.hip')) and inc != 'rr_host.inc':
+            assert 'getenv' not in open(os.path.join(ROOT, 'real_robots_amd', 'csrc', inc)).read(), inc
+    doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
+    table = doc[doc.index('## Environment variables'):]
+    documented = set()
+    for row in table.splitlines():
+        if row.startswith('| `RR_'):
+            documented |= set(re.findall(r'`(RR_[A-Z0-9_]+)', row.split('|')[1]))
+    assert set(read) == documented - {'RR_LIB', 'RR_MODEL', 'RR_NO_TORCH_PRELOAD'}
+
+
 def test_solver_dict_reaches_the_config_struct():
     """ABI 6: the constants the reference leaves to pybullet's defaults travel in rr_config (same 80 bytes as ABI 5's reserved
     words); 0 = default, an explicit zero is passed as the header's "literal zero" (negative)."""
