@@ -68,8 +68,12 @@ enum {
                                              eleven bodies (R 99, position 33, joint axis 33), M^-1 (121), unconstrained joint velocities (11), the objects'
                                              rotation / world inverse inertia / unconstrained velocities / collision position (27 + 27 + 9 + 9 + 9); after a
                                              step with the look-ahead it describes the state the step LEFT (tests compare the kernel's forms through it) */
-    RR_F_COUNT = 13
+    RR_F_CONTACTS = 13,      /* f32 [N, 48, 12]  the three fields of rr_contact_observations (additive in ABI 7), which see: as its LAST CALL */
+    RR_F_BODY_FORCE = 14,    /* f32 [N, RR_CONTACT_ROWS, 2]   left them -- steps do not refresh them; allocated on first use, all zero */
+    RR_F_BODY_PARTNERS = 15, /* u32 [N, RR_CONTACT_ROWS]      before the first call */
+    RR_F_COUNT = 16
 };
+#define RR_CONTACT_ROWS 20   /* body rows of RR_F_BODY_FORCE / RR_F_BODY_PARTNERS: the 17 URDF links, then objects 0..2 */
 
 /* rr_config.flags */
 #define RR_FLAG_NO_MASK 1   /* R2 environments have no `mask` observation (robot.py:99-112): do not produce RR_F_MASK */
@@ -295,6 +299,32 @@ int rr_link_poses(rr_env *env, float *out_host);
  * the contacts of the last step with the normal forces the solver found -- is also the contact history the next step's
  * warm start matches its contacts against (Bullet: persistent manifolds, m_warmstartingFactor 0.85). */
 int rr_get_contacts(rr_env *env, int32_t env_index, float *out_host, int32_t max_contacts, int32_t *count);
+/* Replaces Kuka.get_contacts (robot.py:131-150), with and without forces=True, for ALL envs at once and on the device (additive in
+ * ABI 7): one launch on the library's stream turns the contact list of the last solved step -- the one rr_get_contacts shows -- into
+ * three device fields (rr_get_buffer / rr_copy_to_host / DLPack).  The call checks the launch and returns without waiting.
+ *   RR_F_CONTACTS       f32 [N, 48, 12]: row c < RR_F_CONTACT_COUNT[env] is exactly the row rr_get_contacts gives for that env and
+ *                       contact, {bodyA, bodyB, linkA, x, y, z, nx, ny, nz, distance, normal_force, mu}; the rows from the count on
+ *                       are all zero.
+ *   RR_F_BODY_FORCE     f32 [N, RR_CONTACT_ROWS, 2]: {max, sum} of the normal force over the contacts of the row's body.
+ *   RR_F_BODY_PARTNERS  u32 [N, RR_CONTACT_ROWS]: what the row's body touches -- bit 0 a static body (table or shelf, body -1),
+ *                       bit 1 + j object j, bit 4 the robot.
+ * Rows 0..16 are the robot's URDF links in the order of rr_link_poses (data/realrobot_model_links.txt), rows 17..19 objects 0..2;
+ * the rows of objects the handle does not have stay zero.  Only contacts with |distance| < 0.1 count (robot.py:136, the test behind
+ * RR_F_TOUCH: the max column of the four skin links IS RR_F_TOUCH of an env that stepped).  A contact whose body A is a robot body
+ * (0..15) counts for the row of its linkA, one whose body A is object i for row 17 + i; a body B that is object j counts for row
+ * 17 + j as well, with partner bit 4 if A is a robot body and bit 1 + i if A is object i.  The model's collision pairs have a robot
+ * body or an object as A and a static body or an object as B -- no robot body is ever B, so bit 4 appears on object rows only.
+ * max and sum of a row are taken over its contacts in ascending contact index, in float32, one after the other from 0: a
+ * sequential float32 loop over rr_get_contacts' rows reproduces them bit for bit.
+ * The fields hold what the LAST CALL computed: steps do not refresh them (RR_F_CONTACT_COUNT, which they do refresh, is the count
+ * of the rows at the moment of the call only until the next step).  After rr_reset / rr_set_state of an env, or a step that refused
+ * its command (error flag 2), the env has no contacts and the next call gives it all-zero rows.
+ * The three buffers are allocated on first use -- by this call, or by rr_get_buffer / rr_copy_to_host of one of the fields --,
+ * zero-filled, and valid until rr_destroy; if the allocation fails the call returns RR_EDEVICE and the handle stays usable.
+ * STREAM CONTRACT as for the other zero-copy views (rr_step): the kernel runs on the library's stream behind the steps enqueued before
+ * it; readers on another stream order themselves after the call (event / rr_sync), and a later call rewrites the buffers in place.
+ * Out of scope: friction forces, contact positions in body frames, per-link rows for body B (body B is never a robot body). */
+int rr_contact_observations(rr_env *env);
 
 /* Replaces REALRobotEnv.evaluateGoal (env.py:181-200) for all envs at once: score[i] = sum over the objects o of env i whose
  * goal_mask byte is non-zero (NULL: every object) of exp(-(ln 4 / 0.10) * |goal_pos[i][o] - position[i][o]|), computed on the

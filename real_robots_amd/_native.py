@@ -16,8 +16,10 @@ LINK_NAMES = open(os.path.join(_HERE, 'data', 'realrobot_model_links.txt')).read
 
 RR_ABI_VERSION = 7
 (F_JOINTS, F_TOUCH, F_OBJ_POSE, F_RGB, F_DEPTH, F_MASK, F_TIMESTEP, F_ERRFLAGS, F_STATE, F_FRAG_COUNT, F_CONTACT_COUNT,
- F_ENV_CLASS, F_PREP) = range(13)
+ F_ENV_CLASS, F_PREP, F_CONTACTS, F_BODY_FORCE, F_BODY_PARTNERS) = range(16)
 PREP_FLOATS = 378          # RR_F_PREP: frames 165, M^-1 121, qd* 11, object terms 81 -- in this order (realrobot.hip S_*)
+MAX_CONTACTS = 48          # rows of RR_F_CONTACTS per env
+CONTACT_ROWS = 20          # RR_CONTACT_ROWS: body rows of RR_F_BODY_FORCE / RR_F_BODY_PARTNERS (17 URDF links, then objects 0..2)
 NUM_KERNELS = 9
 # id 5 = image set-up outside the two render kernels: the full static copy of the first frame (and of every frame with the
 # earlier scheme RR_FULL_COPY); it does not run in steady state
@@ -33,7 +35,7 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_checkpoint_save', 'rr_checkpoint_restore', 'rr_evaluate_goals', 'rr_device_microbench', 'rr_map_observations', 'rr_map_images', 'rr_sync_observations', 'rr_select_image_mirror',
            'rr_pack_image_delta', 'rr_apply_image_delta', 'rr_set_object_dynamics', 'rr_get_object_dynamics',
            'rr_set_env_cameras', 'rr_set_env_appearance', 'rr_get_env_appearance', 'rr_render_instances',
-           'rr_set_env_actuators', 'rr_get_env_actuators')
+           'rr_set_env_actuators', 'rr_get_env_actuators', 'rr_contact_observations')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
@@ -125,6 +127,7 @@ def load_library():
     L.rr_sync.argtypes = [vp]
     L.rr_link_poses.argtypes = [vp, vp]
     L.rr_get_contacts.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
+    L.rr_contact_observations.argtypes = [vp]
     L.rr_set_timing.argtypes = [vp, i32]
     L.rr_get_timing.argtypes = [vp, vp, vp]
     L.rr_ik.argtypes = [vp, vp, vp, vp]

@@ -65,7 +65,9 @@ class BatchedREALRobotEnv:
             nat.F_MASK: ((self.N, self.H, self.W), np.int32), nat.F_TIMESTEP: ((self.N,), np.int32),
             nat.F_ERRFLAGS: ((self.N,), np.uint32), nat.F_STATE: ((self.N, 61), np.float32),
             nat.F_FRAG_COUNT: ((self.N, 1), np.uint32), nat.F_CONTACT_COUNT: ((self.N,), np.int32),
-            nat.F_ENV_CLASS: ((self.N,), np.int32), nat.F_PREP: ((self.N, nat.PREP_FLOATS), np.float32)}
+            nat.F_ENV_CLASS: ((self.N,), np.int32), nat.F_PREP: ((self.N, nat.PREP_FLOATS), np.float32),
+            nat.F_CONTACTS: ((self.N, nat.MAX_CONTACTS, 12), np.float32),
+            nat.F_BODY_FORCE: ((self.N, nat.CONTACT_ROWS, 2), np.float32), nat.F_BODY_PARTNERS: ((self.N, nat.CONTACT_ROWS), np.uint32)}
         p_, n_ = C.c_void_p(), C.c_size_t()                  # the tile count is the library's choice: ask for it
         nat.check(self.L.rr_get_buffer(self.h, nat.F_FRAG_COUNT, C.byref(p_), C.byref(n_)))
         self._shapes[nat.F_FRAG_COUNT] = ((self.N, max(1, n_.value // (4 * self.N))), np.uint32)
@@ -356,6 +358,25 @@ class BatchedREALRobotEnv:
         n = C.c_int32()
         nat.check(self.L.rr_get_contacts(self.h, int(env), out.ctypes.data, 48, C.byref(n)))
         return out[:n.value]
+
+    def contact_observations(self, host=False):
+        """Kuka.get_contacts (robot.py:131-150) for the whole batch (rr_contact_observations): one launch on the library's stream
+        turns the contact list of the last solved step into
+          contacts [N, 48, 12] f32 -- the rows of `contacts(env)` for every env, all zero from the env's count on;
+          count [N] i32 -- the number of rows (the RR_F_CONTACT_COUNT field: the only one of the four that later steps refresh);
+          body_force [N, 20, 2] f32 -- {max, sum} of the normal force on every body of `body_row_names()`;
+          body_partners [N, 20] u32 -- what that body touches: bit 0 a static body, bit 1 + j object j, bit 4 the robot.
+        Returns them as device buffers (zero copy, valid after later work on the library's stream or `sync()`; they hold what the
+        last call computed), or with host=True as numpy arrays after a sync."""
+        nat.check(self.L.rr_contact_observations(self.h))
+        get = self.host if host else self.device_buffer
+        return {'contacts': get(nat.F_CONTACTS), 'count': get(nat.F_CONTACT_COUNT), 'body_force': get(nat.F_BODY_FORCE),
+                'body_partners': get(nat.F_BODY_PARTNERS)}
+
+    def body_row_names(self):
+        """The bodies of the rows of body_force / body_partners: the 17 URDF links, then this handle's objects (the rows of the
+        objects it does not have, up to 20, stay zero)."""
+        return list(nat.LINK_NAMES) + list(self.object_names)
 
     # ------------------------------------------------------------------ IK / macro plans (K8)
     def ik(self, targets):

@@ -124,6 +124,7 @@ struct rr_env : ModelTables {
     float *link_out = nullptr;         // [N][nl][7]
     float *plan = nullptr; int *plan_step = nullptr; float *ik_in = nullptr; float *ik_out = nullptr; float *ik_err = nullptr;   // lazily allocated (macro / cartesian adapters)
     float *score_out = nullptr; unsigned char *score_mask = nullptr;            // lazily allocated (rr_evaluate_goals)
+    float4 *co_contacts = nullptr; float2 *co_force = nullptr; unsigned *co_partners = nullptr;   // lazily allocated, one block (rr_contact_observations)
     std::vector<void *> allocs;
     bool timing = false;
     int *h_hcount = nullptr;       // pinned host copy of D.hcount[0] (device-mapped: written by k_prep_a of the following step)
@@ -679,6 +680,9 @@ static int create_device(rr_env *e, const rr_config &cfg, const Settings &set, H
     e->field_bytes[RR_F_CONTACT_COUNT] = (size_t)N * 4; e->field_bytes[RR_F_ENV_CLASS] = (size_t)N * 4;
     e->field_ptr[RR_F_PREP] = D.scratch; e->field_bytes[RR_F_PREP] = (size_t)N * S_TOTAL * 4;
     static_assert(S_TOTAL == 378, "include/realrobot.h documents RR_F_PREP as 378 floats per env");
+    // (pointers set once the buffers exist: ensure_contact_obs)
+    e->field_bytes[RR_F_CONTACTS] = (size_t)N * MAXC * 12 * 4; e->field_bytes[RR_F_BODY_FORCE] = (size_t)N * RR_CONTACT_ROWS * 2 * 4;
+    e->field_bytes[RR_F_BODY_PARTNERS] = (size_t)N * RR_CONTACT_ROWS * 4;
     refresh_frame_fields(e);
     for (int i = 0; i < NOBJ; i++) RRCHK(rr_set_object_home(e, -1, i, e->B.obj_pose0[i]));
     RRCHK(rr_reset(e, nullptr));
@@ -1383,9 +1387,47 @@ int rr_apply_image_delta(const uint32_t *records_dev, const uint32_t *totals_dev
     return RR_OK;
 }
 
+// The three buffers of rr_contact_observations (RR_F_CONTACTS, RR_F_BODY_FORCE, RR_F_BODY_PARTNERS): one block, allocated on first
+// use -- by the call or by rr_get_buffer / rr_copy_to_host of one of the fields --, zero-filled on the library's stream, freed with
+// the handle's other allocations (rr_destroy).  A failed allocation leaves the handle as it was.
+static int ensure_contact_obs(rr_env *e) {
+    if (e->co_contacts) return RR_OK;
+    if (e->RM.nl + NOBJ != RR_CONTACT_ROWS) return fail(RR_EMODEL, "rr_contact_observations: the model's link count + 3 objects is not RR_CONTACT_ROWS");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const size_t bc = e->field_bytes[RR_F_CONTACTS], bf = e->field_bytes[RR_F_BODY_FORCE], bp = e->field_bytes[RR_F_BODY_PARTNERS];
+    static_assert((MAXC * 12 * 4) % 16 == 0 && (RR_CONTACT_ROWS * 2 * 4) % 16 == 0, "the carved buffers stay 16-byte aligned");
+    void *q = nullptr;
+    hipError_t rc = hipMalloc(&q, bc + bf + bp);
+    if (rc == hipSuccess && (rc = hipMemsetAsync(q, 0, bc + bf + bp, e->stream)) != hipSuccess) hipFree(q);
+    if (rc != hipSuccess) {
+        (void)hipGetLastError();          // (not left behind for the next step's launch check)
+        return fail(RR_EDEVICE, std::string("rr_contact_observations: allocating the observation buffers: ") + hipGetErrorString(rc));
+    }
+    e->allocs.push_back(q);
+    e->co_contacts = (float4 *)q; e->co_force = (float2 *)((char *)q + bc); e->co_partners = (unsigned *)((char *)q + bc + bf);
+    e->field_ptr[RR_F_CONTACTS] = e->co_contacts; e->field_ptr[RR_F_BODY_FORCE] = e->co_force; e->field_ptr[RR_F_BODY_PARTNERS] = e->co_partners;
+    return RR_OK;
+}
+static inline bool contact_obs_field(int32_t field) { return field == RR_F_CONTACTS || field == RR_F_BODY_FORCE || field == RR_F_BODY_PARTNERS; }
+
+// Kuka.get_contacts (robot.py:131-150) for the whole batch, on the device.  Ordered like rr_get_contacts' copies: on the main stream,
+// which every rr_step has made wait for its side streams (ev_join / ev_join2) before it returns -- behind everything that wrote
+// clist / cforce / ccount of the current frame; the look-ahead's frame (clist_next) is not read.
+int rr_contact_observations(rr_env *e) {
+    if (!e) return fail(RR_EINVAL, "null env");
+    const int rc = ensure_contact_obs(e);
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    hipLaunchKernelGGL(k_contact_obs, dim3((e->P.N + CO_ENVS - 1) / CO_ENVS), dim3(64 * CO_ENVS), 0, e->stream, e->P, e->D, e->RM.nl,
+                       e->co_contacts, e->co_force, e->co_partners);
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
 int rr_get_buffer(rr_env *e, int32_t field, void **dev_ptr, size_t *bytes) {
     if (!e || field < 0 || field >= RR_F_COUNT) return fail(RR_EINVAL, "rr_get_buffer: bad field");
     refresh_frame_fields(e);
+    if (contact_obs_field(field)) { const int rc = ensure_contact_obs(e); if (rc != RR_OK) return rc; }
     if (dev_ptr) *dev_ptr = e->field_ptr[field];
     if (bytes) *bytes = e->field_bytes[field];
     return RR_OK;
@@ -1394,6 +1436,7 @@ int rr_get_buffer(rr_env *e, int32_t field, void **dev_ptr, size_t *bytes) {
 int rr_copy_to_host(rr_env *e, int32_t field, void *dst, size_t bytes) {
     if (!e || !dst || field < 0 || field >= RR_F_COUNT) return fail(RR_EINVAL, "rr_copy_to_host: bad argument");
     refresh_frame_fields(e);
+    if (contact_obs_field(field)) { const int rc = ensure_contact_obs(e); if (rc != RR_OK) return rc; }
     if (!e->field_ptr[field]) return fail(RR_EINVAL, "rr_copy_to_host: field not available (RR_FLAG_NO_MASK)");
     if (bytes != e->field_bytes[field]) return fail(RR_EINVAL, "rr_copy_to_host: size mismatch");
     HIPCHK(hipSetDevice(e->cfg.device));

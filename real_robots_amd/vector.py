@@ -43,6 +43,10 @@ dict of float32 arrays kp, kd, max_force, damping [N, 11], joints in the order o
 `infos["_actuators"]` masks the envs that drew.  WARNING: the ranges are the user's responsibility.  A velocity gain below 1, or large
 position gains without the rate limit (`solver={'rate_limit': False}`), can diverge under full-range commands -- in the float64
 oracle as on the device; the error flags (RR_F_ERRFLAGS) tell.
+Contact observations: `contact_obs=True` adds `body_force` [N, 20, 2] (float32: {max, sum} of the normal force on each of the 17
+robot links and the three objects) and `body_partners` [N, 20] (uint32 bit mask: bit 0 a static body, bit 1 + j object j, bit 4 the
+robot) to the observation dict and to the spaces (BatchedREALRobotEnv.contact_observations), computed where the other entries are
+gathered: after a same-step autoreset they describe the reset state.  The default leaves dict and spaces as they are.
 """
 import numpy as np
 
@@ -73,11 +77,17 @@ def _batch_dict_space(space, n):
 class REALRobotVectorEnv(_Base):
     def __init__(self, num_envs, objects=3, additional_obs=False, eye_width=320, eye_height=240, device=0,
                  max_episode_steps=int(15e6), render_every_step=True, device_obs=False, solver=None, dynamics_randomization=None,
-                 camera_randomization=None, appearance_randomization=None, actuator_randomization=None):
+                 camera_randomization=None, appearance_randomization=None, actuator_randomization=None, contact_obs=False):
         self.num_envs = int(num_envs)
         self._robot = Kuka(additional_obs, objects, eye_width, eye_height, env=None)
         self.single_action_space = spaces.Dict({"joint_command": self._robot.action_space, "render": spaces.MultiBinary(1)})
         self.single_observation_space = self._robot.observation_space
+        self.contact_obs = bool(contact_obs)
+        if self.contact_obs:
+            self.single_observation_space = spaces.Dict(dict(
+                self._robot.observation_space.spaces,
+                body_force=spaces.Box(low=0.0, high=np.inf, shape=(nat.CONTACT_ROWS, 2), dtype=np.float32),
+                body_partners=spaces.Box(low=0, high=31, shape=(nat.CONTACT_ROWS,), dtype=np.uint32)))
         # batched spaces = the single spaces with a leading env axis (gymnasium.vector.utils.batch_space)
         self.action_space = spaces.Dict({
             "joint_command": spaces.Box(low=np.tile(self._robot.min_joints, (self.num_envs, 1)),
@@ -254,6 +264,9 @@ class REALRobotVectorEnv(_Base):
                 obs["mask"] = get(nat.F_MASK)
         if self.additional_obs:
             obs["object_positions"] = get(nat.F_OBJ_POSE)
+        if self.contact_obs:
+            co = be.contact_observations(host=not self.device_obs)
+            obs["body_force"], obs["body_partners"] = co["body_force"], co["body_partners"]
         return obs
 
     def reset(self, *, seed=None, options=None):
