@@ -82,8 +82,6 @@ extern "C" int rr_debug_solver_prof(unsigned long long *out16, int reset) {
 #define CSHAPES 24       // collision shapes staged in LDS (rr_create checks the model: 22)
 #define COLLIDE_WAVES_ 4
 #define VH_MAX 1024         // cap of the very heavy list (k_collide)
-#define COOP_MAX_VH 512     // the same for the very heavy list (rr_host.inc launch_solve_class)
-#define COOP_MAX 256        // (1024 measured on the macro workload, 388 very heavy envs: no gain) lists up to this long (lagged host count) are solved one env per wave (coop row build); longer ones four to a wave
 #ifdef RR_RASTER_STATS
 #define CABL(bit) (P.ablate & (bit))      // development build: phase ablations (256 stage only, 512 no pairs, 1024 cull only)
 // per-env phase cycles of k_collide (scratch/cprof.py): 0 stage, 1 sphere tests, 2 loads + cull, 3 prefilter, 4 all-plane pass,

@@ -190,12 +190,18 @@ static void pair_materials(const float *a, const float *b, float *out) {
 static int upload_dynamics(rr_env *e);
 static int upload_actuators(rr_env *e);
 
-// The lagged host copy of the heavy (which 0) / very heavy (which 1) list length: written to mapped pinned memory by a recent
-// step's kernels, read here without any synchronisation -- it only ever selects a launch shape or a placement, never a result
-// (every placement is forced and compared bitwise in tests/test_gpu_round4.py; Settings::force_hcount pins what is read).
-static inline int lagged_count(const rr_env *e, int which, int fallback) {
-    if (e->set.force_hcount[which] >= 0) return e->set.force_hcount[which];
-    return e->h_hcount ? ((volatile int *)e->h_hcount)[which] : fallback;
+// The lagged host copies of the heavy / very heavy list lengths: written to mapped pinned memory by a recent step's kernels while
+// the host runs, read here without any synchronisation -- ONCE per step (rr_step), so that every decision of a step's plan
+// (plan_step, rr_plan.inc) rests on the same two numbers.  They only ever select a launch shape or a placement, never a result
+// (every placement is forced and compared bitwise in tests/test_gpu_round4.py).  Settings::force_hcount pins what is read, here and
+// nowhere else; without the pinned words a reading is known only when both are pinned.
+static inline PlanCounts lagged_counts(const rr_env *e) {
+    const int *f = e->set.force_hcount;
+    PlanCounts c = {0, 0, e->h_hcount != nullptr || (f[0] >= 0 && f[1] >= 0)};
+    if (e->h_hcount) { c.h = ((volatile int *)e->h_hcount)[0]; c.vh = ((volatile int *)e->h_hcount)[1]; }
+    if (f[0] >= 0) c.h = f[0];
+    if (f[1] >= 0) c.vh = f[1];
+    return c;
 }
 
 // k_obs (joint angles and object poses of the state -> observation buffers) and, when mapped, the host mirror behind it
@@ -1014,51 +1020,41 @@ static void launch_shade(rr_env *e, const DevPtrs &D, const ImageOut &io, int se
 // The three render kernels for the envs selected by `sel` (env_selected) on `st`.  The images persist in HBM from frame to
 // frame: only the pixels of the previous frame's fragment lists are put back to the static layer (`restore`), DESIGN.md 5.
 // `setup_done`: the instances of these envs are set up already (by the light solve).
-// `done`: an event that completes with the last launch of the untimed form.
-static void launch_render(rr_env *e, const DevPtrs &D, int restore, int sel, hipStream_t st, bool timed, bool setup_done = false, hipEvent_t done = nullptr) {
+// `done`: an event that completes with the last launch.
+// The heavy list (sel 2) in the form the plan picked (StepPlan::heavy_render); the very heavy one (sel 3) is always walked by one launch.
+static void launch_render(rr_env *e, const StepPlan &pl, const DevPtrs &D, int restore, int sel, hipStream_t st, bool setup_done = false, hipEvent_t done = nullptr) {
     const int N = e->P.N;
     const ImageOut io = env_images(e);
-    if (timed) {
-        if (!setup_done) TIMED(3, hipLaunchKernelGGL(k_render_setup, dim3((N * MAXINST + 63) / 64), dim3(64), 0, st, e->B, e->P, e->RM_dev, D, sel));
-        TIMED(4, launch_raster(e, D, restore, sel, st));
-        TIMED(6, launch_shade(e, D, io, sel, st));
-    } else {
-        // the heavy envs, a few (lagged host copy of their number: at most one item per workgroup): one list-walking launch for
-        // set-up, visibility and shading -- the tail of the step's longest chain; many: the three kernels (the fused one needs
-        // 128 VGPRs: two workgroups per CU, which a long list pays for)
-        if (sel == 3 || (sel == 2 && (long long)lagged_count(e, 0, e->P.N) * e->RM.ntiles <= RENDER_LIST_WGS)) {
-            LAUNCH_EV(done, k_render_list, dim3(std::min(N * e->RM.ntiles, sel == 3 ? 256 : RENDER_LIST_WGS)), dim3(RASTER_THREADS), 0, st, e->B, e->P, e->RM_dev, D, io, e->n_inst_used, restore, sel == 3 ? 1 : 0, setup_done ? 1 : 0);
-            return;
-        }
-        if (!setup_done) hipLaunchKernelGGL(k_render_setup, dim3((N * MAXINST + 63) / 64), dim3(64), 0, st, e->B, e->P, e->RM_dev, D, sel);
-        // (a heavy list of more than a third of the batch -- macro actions: 1 500 .. 2 000 of 4 096 envs -- is rasterised by the grid kernel
-        // over all (env, tile) workgroups, those of other classes leaving at once: four workgroups per CU at 64 VGPRs instead of the
-        // list walker's three at 79; macro workload 1.130 -> 1.101 ms.  A list of 660 envs -- the late window -- is better off with the
-        // walker: 0.679 against 0.711 ms)
-        // The threshold was a quarter of the batch until round 6; the off-bench schedule test (tests/test_gpu_round6.py: 1 230 heavy envs
-        // of 4 096 pressing the gripper on the table) measured the walker 3.6 % ahead there, the macro workload (1 486 .. 1 969 heavy
-        // envs) the grid 2.5 % ahead of a threshold of 0.4: a third of the batch lies between the two measured sides.
-        if (sel == 2 && (long long)lagged_count(e, 0, 0) * 3 > (long long)N) { DevPtrs Dp = D; Dp.item_perm = nullptr; hipLaunchKernelGGL(k_raster, dim3(N, e->RM.ntiles), dim3(RASTER_THREADS), 0, st, e->P, e->RM_dev, Dp, e->n_inst_used, 0, 0, restore, sel); }
-        else if (sel == 2) hipLaunchKernelGGL(k_raster_list, dim3(std::min(N * e->RM.ntiles, RASTER_LIST_WGS)), dim3(RASTER_THREADS), 0, st, e->P, e->RM_dev, D, e->n_inst_used, restore, 0);
-        else launch_raster(e, D, restore, sel, st);
-        launch_shade(e, D, io, sel, st, done);
+    if (sel == 3 || (sel == 2 && pl.heavy_render == RENDER_WALKER)) {
+        LAUNCH_EV(done, k_render_list, dim3(std::min(N * e->RM.ntiles, sel == 3 ? 256 : RENDER_LIST_WGS)), dim3(RASTER_THREADS), 0, st, e->B, e->P, e->RM_dev, D, io, e->n_inst_used, restore, sel == 3 ? 1 : 0, setup_done ? 1 : 0);
+        return;
     }
+    if (!setup_done) hipLaunchKernelGGL(k_render_setup, dim3((N * MAXINST + 63) / 64), dim3(64), 0, st, e->B, e->P, e->RM_dev, D, sel);
+    if (sel == 2 && pl.heavy_render == RENDER_GRID) { DevPtrs Dp = D; Dp.item_perm = nullptr; hipLaunchKernelGGL(k_raster, dim3(N, e->RM.ntiles), dim3(RASTER_THREADS), 0, st, e->P, e->RM_dev, Dp, e->n_inst_used, 0, 0, restore, sel); }
+    else if (sel == 2) hipLaunchKernelGGL(k_raster_list, dim3(std::min(N * e->RM.ntiles, RASTER_LIST_WGS)), dim3(RASTER_THREADS), 0, st, e->P, e->RM_dev, D, e->n_inst_used, restore, 0);
+    else launch_raster(e, D, restore, sel, st);
+    launch_shade(e, D, io, sel, st, done);
+}
+// The same three kernels under their timers (rr_render, a single-class step, the timing leg): the grid kernels whatever the class.
+static void launch_render_timed(rr_env *e, const DevPtrs &D, int restore, int sel, hipStream_t st, bool setup_done = false) {
+    const ImageOut io = env_images(e);
+    if (!setup_done) TIMED(3, hipLaunchKernelGGL(k_render_setup, dim3((e->P.N * MAXINST + 63) / 64), dim3(64), 0, st, e->B, e->P, e->RM_dev, D, sel));
+    TIMED(4, launch_raster(e, D, restore, sel, st));
+    TIMED(6, launch_shade(e, D, io, sel, st));
 }
 
 static int do_render(rr_env *e, bool use_flags) {
     DevPtrs D = e->D;
     if (!use_flags) D.render_flags = nullptr;
     const int restore = ensure_images(e, D);
-    launch_render(e, D, restore, 0, e->stream, true);
+    launch_render_timed(e, D, restore, 0, e->stream);
     HIPCHK(hipGetLastError());
     return RR_OK;
 }
 
 // ---- look-ahead: the state part of the NEXT step (k_prep_a -> k_collide, k_prep_b beside them) ------------------------------
 // Per-class launches (sel: pick_env) cover N work items whatever the class.
-#define COOP_ALL_MAX 1024   // up to this many envs a step that solves all envs in one launch gives every env its own wave (Settings::coop_all off: four to a wave)
 #define COLLIDE_ORDER_MIN_N 1024   // up to this many envs all collision workgroups are resident at once: no order needed
-#define SMALL_N_MAX 64      // up to this many envs a step without the three-stream split runs as one chain on the main stream (rr_step)
 // (collision pass in cost order: the eight sorting workgroups ride on the preparation launch in front of it -- batches of more than
 // one round of collision workgroups, all envs; Settings::collide_ordered off: env order)
 static inline bool collide_in_order(const rr_env *e, int sel) { return sel == 0 && e->set.collide_ordered && e->epb == 64 && e->P.N > COLLIDE_ORDER_MIN_N; }
@@ -1088,21 +1084,14 @@ static void launch_prep_serial(rr_env *e, int sel, int zero_counts) {
     launch_prep_b(e, sel, e->stream);
 }
 
-// The solve of the heavy (sel 2) / very heavy (sel 3) envs on `st`.  A list the lagged host count puts at <= COOP_MAX entries is
-// launched in the coop form: one env per wave, four waves per workgroup with one LDS region each (N waves: whatever the
-// list's actual length, every entry has its wave; the others exit at once); a longer one four envs to a wave.
-static void launch_solve_class(rr_env *e, int sel, hipStream_t st, const RenderModel *fused_rm = nullptr, hipEvent_t done = nullptr, bool beside_raster = true) {
+// The solve of the heavy (sel 2) / very heavy (sel 3) envs on `st`, in the form the plan picked (StepPlan::coop_*): one env per
+// wave, four waves per workgroup with one LDS region each (N waves: whatever the list's actual length, every entry has its
+// wave; the others exit at once), or four envs to a wave.  beside_raster false: a step without camera.
+static void launch_solve_class(rr_env *e, const StepPlan &pl, int sel, hipStream_t st, const RenderModel *fused_rm = nullptr, hipEvent_t done = nullptr, bool beside_raster = true) {
     const int N = e->P.N;
     const int ngroups = (N + SGRP - 1) / SGRP;
     const size_t lds64 = (size_t)SGRP * LF_TOTAL * sizeof(float);
-    const int lagged = lagged_count(e, sel == 2 ? 0 : 1, N);
-    // (the very heavy list in the coop form up to COOP_MAX_VH entries: its solve is the step's longest chain -- round 6's off-bench
-    // schedule check, 410 arms crushed on the table: 0.672 packed, 0.632 ms one env per wave; a long HEAVY list stays packed from
-    // COOP_MAX on: 700 waves with an LDS region each crowd the visibility pass out, NOTEBOOK.md B)
-    // -- unless the heavy list is long too (macro actions: 1 500+ heavy envs, packed, beside 380 very heavy ones: 3.82 -> 3.76 M in the coop form)
-    const bool h_long_ = (long long)lagged_count(e, 0, 0) * e->RM.ntiles > RENDER_LIST_WGS;
-    // (beside_raster false: a step without camera -- no visibility pass for the one-env-per-wave form's LDS regions to crowd out)
-    const bool coop = lagged <= (sel == 3 && (!h_long_ || !beside_raster) ? COOP_MAX_VH : COOP_MAX);
+    const bool coop = sel == 2 ? pl.coop_h : (beside_raster ? pl.coop_vh_beside : pl.coop_vh_alone);
     // (fused_rm: the step draws -- the kernel also sets up the render instances of its envs, as the light solve does)
     if (fused_rm) {
         if (coop) LAUNCH_EV(done, k_solve_rs, dim3((N + 3) / 4), dim3(256), lds64, st, e->B, e->P, e->D, sel, 1, fused_rm);
@@ -1141,20 +1130,8 @@ static int pin_acquire(rr_env *e, char **slot, int *idx) {
 }
 
 // ---- the schedule of one step --------------------------------------------------------------------------------------------------
-// Five placements (DESIGN.md 5.2), picked from the batch size and the lagged, never-waited-for host copies of the two heavy-list
-// lengths; none of them may change a result (every one is forced and compared bitwise against the in-line step,
-// tests/test_gpu_round4.py):
-//   1. split, a handful of very heavy envs (the benchmark's early window): step_split(), look-ahead behind the very heavy envs' solve;
-//      with a LONG heavy list (late window) the very heavy envs' render moves to the tail of the main stream;
-//   2. split, hundreds of very heavy envs (macro actions): step_split(), kinematics + collision pass of the look-ahead on the heavy
-//      stream, its dynamics half on the very heavy one;
-//   3. mostly heavy envs, or a step without camera: one solve launch for everybody, look-ahead beside the render (step_single());
-//   3b. a step without camera of a large batch with a long very heavy list: the classes side by side, the very heavy envs a wave each (step_single());
-//   4. a handful of envs (the gym facade): one chain on the main stream, the mirror in front of the look-ahead (step_single());
-//   5. the reference: everything in line (Settings::split_heavy / lookahead off; the timing leg of bench.py runs placement 1's launches one
-//      after the other under their timers).
-#define LA_VH_MAX 64         // look-ahead behind the very heavy envs' solve while their (lagged) number is at most this
-#define NORENDER_SPLIT_VH_MIN 64   // a step without camera runs its classes side by side from this many (lagged) very heavy envs on (step_single)
+// Which of the placements of DESIGN.md 5.2 a step takes, and every launch shape in it, is decided once by plan_step (rr_plan.inc);
+// the functions below carry a StepPlan out and decide nothing themselves.
 
 static void launch_light_solve(rr_env *e, const RenderModel *fused_rm, hipStream_t st, hipEvent_t done = nullptr) {
     const size_t lds64 = (size_t)SGRP * LF_TOTAL * sizeof(float);
@@ -1163,11 +1140,11 @@ static void launch_light_solve(rr_env *e, const RenderModel *fused_rm, hipStream
 
 // The same launches as step_split(), one after the other on the main stream, each under its timer -- 2 / 3 / 4 / 6 what the main
 // stream runs in an untimed step (the light envs), 7 / 8 what the side streams run beside it, 0 / 1 the look-ahead of the next step.
-static int step_split_timed(rr_env *e, const DevPtrs &D, int restore, bool ahead, int render_mode) {
+static int step_split_timed(rr_env *e, const StepPlan &pl, const DevPtrs &D, int restore, bool ahead, int render_mode) {
     TIMED(2, launch_light_solve(e, e->RM_dev, e->stream));
-    TIMED(7, { launch_solve_class(e, 2, e->stream, e->RM_dev); launch_solve_class(e, 3, e->stream, e->RM_dev); });
-    launch_render(e, D, restore, 1, e->stream, true, true);
-    TIMED(8, { launch_render(e, D, restore, 2, e->stream, false, true); launch_render(e, D, restore, 3, e->stream, false, true); });
+    TIMED(7, { launch_solve_class(e, pl, 2, e->stream, e->RM_dev); launch_solve_class(e, pl, 3, e->stream, e->RM_dev); });
+    launch_render_timed(e, D, restore, 1, e->stream, true);
+    TIMED(8, { launch_render(e, pl, D, restore, 2, e->stream, true); launch_render(e, pl, D, restore, 3, e->stream, true); });
     if (ahead) {
         TIMED(0, launch_prep_ab(e, 0, e->stream));
         TIMED(1, launch_collide(e, 0, e->stream));
@@ -1181,41 +1158,27 @@ static int step_split_timed(rr_env *e, const DevPtrs &D, int restore, bool ahead
 // heavy solve -> their render (-> the very heavy envs' render); very heavy stream: their solve (-> look-ahead).  Where the
 // look-ahead and the very heavy envs' render go was settled by measurement (DESIGN.md 5.2, NOTEBOOK.md B).
 // The solve kernels set up the render instances of their envs themselves.
-static int step_split(rr_env *e, const DevPtrs &D, int restore, bool ahead, int render_mode) {
-    // (a long heavy list is rendered by three launches, the longest chain of the step: the very heavy envs' render then goes to the
-    // tail of the main stream, which is done with the shading by then)
-    const bool h_long = (long long)lagged_count(e, 0, 0) * e->RM.ntiles > RENDER_LIST_WGS;
-    // placement 1 (else 2).  Placement 2 -- the look-ahead split over the two side streams -- was tuned on the macro workload (hundreds
-    // of very heavy envs AND 1 500+ heavy ones); with many very heavy envs but a short heavy list (round 6's off-bench schedule
-    // check: 410 arms crushed on the table, no other heavy env) placement 1 is 7.8 % faster: both lists must be long for 2.
-    const bool la_on_vh = ahead && (lagged_count(e, 1, 0) <= LA_VH_MAX || !h_long);
-    const bool la_side = ahead && !la_on_vh;
-    const bool vh_render_on_main = la_on_vh && h_long;
+static int step_split(rr_env *e, const StepPlan &pl, const DevPtrs &D, int restore, bool ahead, int render_mode) {
     // (the events that say "this class is solved" / "the collision pass is done" complete with those launches: LAUNCH_EV)
     HIPQ(hipEventRecord(e->ev_fork, e->stream));
     HIPQ(hipStreamWaitEvent(e->aux, e->ev_fork, 0));
-    launch_solve_class(e, 2, e->aux, e->RM_dev, ahead ? e->ev_hsolved : nullptr);
+    launch_solve_class(e, pl, 2, e->aux, e->RM_dev, ahead ? e->ev_hsolved : nullptr);
     // (ev_join: the heavy stream's last launch -- the heavy lists' render, or the very heavy envs' behind it, or placement 2's collision pass)
-    const bool vh_render_on_aux = la_on_vh && !vh_render_on_main;
-    const hipEvent_t join_ev = la_side ? nullptr : e->ev_join;
-    launch_render(e, D, restore, 2, e->aux, false, true, vh_render_on_aux ? nullptr : join_ev);
+    const hipEvent_t join_ev = pl.la_side ? nullptr : e->ev_join;
+    launch_render(e, pl, D, restore, 2, e->aux, true, pl.vh_render_on_aux ? nullptr : join_ev);
     HIPQ(hipStreamWaitEvent(e->aux2, e->ev_fork, 0));
-    launch_solve_class(e, 3, e->aux2, e->RM_dev, ahead ? e->ev_vsolved : nullptr);
-    if (vh_render_on_aux) {
+    launch_solve_class(e, pl, 3, e->aux2, e->RM_dev, ahead ? e->ev_vsolved : nullptr);
+    if (pl.vh_render_on_aux) {
         HIPQ(hipStreamWaitEvent(e->aux, e->ev_vsolved, 0));
-        launch_render(e, D, restore, 3, e->aux, false, true, join_ev);
-    } else if (!la_on_vh) launch_render(e, D, restore, 3, e->aux2, false, true);
+        launch_render(e, pl, D, restore, 3, e->aux, true, join_ev);
+    } else if (!pl.la_on_vh) launch_render(e, pl, D, restore, 3, e->aux2, true);
     launch_light_solve(e, e->RM_dev, e->stream, ahead ? e->ev_dyn : nullptr);
-    // (the thread-per-env k_prep_ab needed a whole free SIMD for each of its 64 waves and sat in its queue until the visibility
-    // pass' grid was exhausted -- which kept the collision pass, 39 KB of LDS per workgroup, out of the visibility pass' way;
-    // k_prep_ab16 gets onto the machine at once, so the look-ahead is HELD behind the light envs' visibility pass by an event)
-    const bool la_after_raster = la_on_vh && !e->set.prep_scalar;
-    if (la_on_vh && !la_after_raster) {
+    if (pl.la_on_vh && !pl.la_after_raster) {
         HIPQ(hipStreamWaitEvent(e->aux2, e->ev_dyn, 0));
         HIPQ(hipStreamWaitEvent(e->aux2, e->ev_hsolved, 0));
         launch_prep_ab(e, 0, e->aux2);
         launch_collide(e, 0, e->aux2, e->ev_join2);
-    } else if (la_side) {
+    } else if (pl.la_side) {
         // the heavy stream is done with its envs' render long before the very heavy envs' is: the kinematics half of the preparation
         // (69 VGPRs: it gets onto the machine beside the renders) and the collision pass go there once every solve is done, the
         // dynamics half (a whole SIMD per wave) behind the very heavy envs' render
@@ -1227,7 +1190,7 @@ static int step_split(rr_env *e, const DevPtrs &D, int restore, bool ahead, int 
         HIPQ(hipStreamWaitEvent(e->aux2, e->ev_hsolved, 0));
         launch_prep_b(e, 0, e->aux2, e->ev_join2);
     }
-    if (la_after_raster) {
+    if (pl.la_after_raster) {
         const ImageOut io = env_images(e);
         launch_raster(e, D, restore, 1, e->stream);
         HIPQ(hipEventRecord(e->ev_rast, e->stream));
@@ -1238,11 +1201,11 @@ static int step_split(rr_env *e, const DevPtrs &D, int restore, bool ahead, int 
         launch_shade(e, D, io, 1, e->stream);
     } else {
         if (!ahead) HIPQ(hipEventRecord(e->ev_join2, e->aux2));     // (with the look-ahead its last launch completes ev_join2)
-        launch_render(e, D, restore, 1, e->stream, false, true);
+        launch_render(e, pl, D, restore, 1, e->stream, true);
     }
-    if (vh_render_on_main) {
+    if (pl.vh_render_on_main) {
         HIPQ(hipStreamWaitEvent(e->stream, e->ev_vsolved, 0));
-        launch_render(e, D, restore, 3, e->stream, false, true);
+        launch_render(e, pl, D, restore, 3, e->stream, true);
     }
     if (ahead) e->la_valid = true;
     HIPQ(hipStreamWaitEvent(e->stream, e->ev_join, 0));
@@ -1251,58 +1214,50 @@ static int step_split(rr_env *e, const DevPtrs &D, int restore, bool ahead, int 
 }
 
 // Placements 3, 4 and 5: one class (or a handful of envs).  A single env is solved by the kernel of its own class (a launch whose
-// list is empty ends at once); up to COOP_ALL_MAX envs every env gets a wave of its own; otherwise four envs to a wave.
-static int step_single(rr_env *e, bool overlap, bool ahead, int render_mode) {
+// list is empty ends at once); a small batch with a wave for every env; otherwise four envs to a wave (StepPlan::single_solve).
+static int step_single(rr_env *e, const StepPlan &pl, bool overlap, bool ahead, int render_mode) {
     const int N = e->P.N;
     const size_t lds64 = (size_t)SGRP * LF_TOTAL * sizeof(float);
-    const bool small_n = N <= SMALL_N_MAX && e->set.split_heavy && !e->timing;
-    if (small_n && N == 1) {
+    if (pl.single_solve == SOLVE_CHAIN_N1) {
         launch_light_solve(e, nullptr, e->stream);
-        launch_solve_class(e, 2, e->stream);
-        launch_solve_class(e, 3, e->stream);
-    } else if (!render_mode && N > COOP_ALL_MAX && e->set.split_heavy && !e->timing && lagged_count(e, 1, 0) >= NORENDER_SPLIT_VH_MIN) {
-        // Placement 3b: a step without camera whose very heavy list is long (macro actions without the retina: 368 of 4 096 envs).  In the
-        // one launch for everybody those envs are solved four to a wave, sixteen lanes building the rows of an env at the contact cap; side
-        // by side on the three streams they get a wave each -- 0.765 -> 0.711 ms per step on the macro workload.  With a handful of
-        // very heavy envs (the headline's population) the one launch is ahead, 0.491 against 0.516 ms: the forks and joins cost more
-        // than the few long chains gain.
+        launch_solve_class(e, pl, 2, e->stream);
+        launch_solve_class(e, pl, 3, e->stream);
+    } else if (pl.single_solve == SOLVE_SIDE_BY_SIDE) {          // placement 3b
         HIPQ(hipEventRecord(e->ev_fork, e->stream));
         HIPQ(hipStreamWaitEvent(e->aux, e->ev_fork, 0));
-        launch_solve_class(e, 2, e->aux, nullptr, nullptr, false);
+        launch_solve_class(e, pl, 2, e->aux, nullptr, nullptr, false);
         HIPQ(hipEventRecord(e->ev_join, e->aux));
         HIPQ(hipStreamWaitEvent(e->aux2, e->ev_fork, 0));
-        launch_solve_class(e, 3, e->aux2, nullptr, nullptr, false);
+        launch_solve_class(e, pl, 3, e->aux2, nullptr, nullptr, false);
         HIPQ(hipEventRecord(e->ev_join2, e->aux2));
         launch_light_solve(e, nullptr, e->stream);
         HIPQ(hipStreamWaitEvent(e->stream, e->ev_join, 0));
         HIPQ(hipStreamWaitEvent(e->stream, e->ev_join2, 0));
-    } else if (e->set.coop_all && N <= COOP_ALL_MAX && e->set.split_heavy)
+    } else if (pl.single_solve == SOLVE_WAVE_PER_ENV)
         TIMED(2, hipLaunchKernelGGL(k_solve, dim3((N + 3) / 4), dim3(256), lds64, e->stream, e->B, e->P, e->D, 0, 1));
     else
         TIMED(2, hipLaunchKernelGGL(k_solve, dim3((N + SGRP - 1) / SGRP), dim3(SGRP * 16), lds64, e->stream, e->B, e->P, e->D, 0, 0));
     HIPCHK(hipGetLastError());
     int rc = RR_OK;
-    // (with a camera the state part of the next step runs on the side stream beside the render of this one)
-    const bool la_beside = ahead && render_mode && overlap && !small_n;
-    if (la_beside) {
+    if (pl.la_beside) {
         HIPQ(hipEventRecord(e->ev_fork, e->stream));
         HIPQ(hipStreamWaitEvent(e->aux, e->ev_fork, 0));
         launch_prep_ab(e, 0, e->aux);
         launch_collide(e, 0, e->aux, e->ev_join);
     }
     if (render_mode) rc = do_render(e, render_mode == 2);
-    if (la_beside) {
+    if (pl.la_beside) {
         HIPQ(hipStreamWaitEvent(e->stream, e->ev_join, 0));
         e->la_valid = true;
     } else if (ahead) {
         // (a handful of envs: the observations of this step are complete here -- the mirror goes in front of the look-ahead, so that
         // a caller waiting for the observations alone (rr_sync_observations) gets them 45 us earlier and the state part of the next
         // step runs while the host computes its next action)
-        if (small_n) { const int rm = launch_mirror(e, render_mode != 0); if (rm != RR_OK) return rm; launch_prep_ab(e, 0, e->stream); launch_collide(e, 0, e->stream); }
+        if (pl.small_n) { const int rm = launch_mirror(e, render_mode != 0); if (rm != RR_OK) return rm; launch_prep_ab(e, 0, e->stream); launch_collide(e, 0, e->stream); }
         else state_part_all(e, overlap);
         e->la_valid = true;
     }
-    if (!(small_n && ahead && !la_beside)) { const int rm = launch_mirror(e, render_mode != 0); if (rm != RR_OK) return rm; }
+    if (!(pl.small_n && ahead && !pl.la_beside)) { const int rm = launch_mirror(e, render_mode != 0); if (rm != RR_OK) return rm; }
     return rc;
 }
 
@@ -1339,19 +1294,21 @@ int rr_step(rr_env *e, const float *joint_cmd, int32_t cmd_on_device, int32_t re
     bind_frames(e);
     // a device-resident command buffer is read in place by the solve kernels (stream order protects it like a copy would)
     e->D.cmd_in = (joint_cmd && cmd_on_device) ? joint_cmd : e->D.cmd;
-    // (the number of heavy envs of a recent step, written to pinned host memory by the solve kernel without anybody waiting for it:
-    // when most are heavy -- macro actions, every gripper pushing -- there is nothing to gain from the split)
-    const bool mostly_heavy = (long long)lagged_count(e, 0, 0) * 100 > (long long)N * e->set.split_max_pct;
+    // ---- the plan of this step: the one reading of the lagged list lengths (behind the run-ahead wait: as fresh as it gets)
+    PlanIn in;
+    in.N = N; in.ntiles = e->RM.ntiles; in.render_mode = render_mode; in.timing = e->timing;
+    in.split_heavy = e->set.split_heavy; in.lookahead = e->set.lookahead; in.prep_scalar = e->set.prep_scalar; in.coop_all = e->set.coop_all;
+    in.split_max_pct = e->set.split_max_pct;
+    in.counts = lagged_counts(e);
+    const StepPlan pl = plan_step(in);
     const bool ahead = e->set.lookahead;            // this step ends with the state part of the next one
-    // (a step without camera runs all envs in one launch: its classes side by side measured 0.525 instead of 0.452 ms on config 2;
-    // ONE env -- the gym facade -- renders in its chain on the main stream too: the split has nothing to overlap there)
     int rc;
-    if (render_mode && e->set.split_heavy && !mostly_heavy && !(N == 1 && !e->timing)) {
+    if (pl.path != PATH_SINGLE) {
         DevPtrs D = e->D;
         if (render_mode != 2) D.render_flags = nullptr;
         const int restore = ensure_images(e, D);
-        rc = e->timing ? step_split_timed(e, D, restore, ahead, render_mode) : step_split(e, D, restore, ahead, render_mode);
-    } else rc = step_single(e, overlap, ahead, render_mode);
+        rc = pl.path == PATH_SPLIT_TIMED ? step_split_timed(e, pl, D, restore, ahead, render_mode) : step_split(e, pl, D, restore, ahead, render_mode);
+    } else rc = step_single(e, pl, overlap, ahead, render_mode);
     if (rc != RR_OK) return rc;
     HIPCHK(hipGetLastError());
     if (bounded) HIPCHK(hipEventRecord(e->ahead_ev[ahead_slot], e->stream));

@@ -1153,7 +1153,7 @@ __global__ void __launch_bounds__(SHADE_THREADS) k_shade(const RenderModel *RMp,
 // (env, tile) items (dynamic assignment: tiles differ a lot in cost; no LDS-filling workgroup is launched just to find that
 // its env is not on the list); for each item: the env's instance matrices (22 threads; the four tiles of an env write the
 // same values), the visibility pass of the tile, the shading of its fragment list.
-#define RENDER_LIST_WGS 768      // (two resident per CU: set-up, visibility and shading in one body need 128 VGPRs -- capped at 80 it spilled)
+// (launched with at most RENDER_LIST_WGS workgroups, rr_plan.inc: two resident per CU)
 template <int NT_>
 __device__ __forceinline__ void render_list_body(const BodyParams &B, const SimParams &P, const RenderModel *RMp, const DevPtrs &D, const ImageOut &out, int n_inst_used, int restore, int which, int setup_done) {
     const RenderModel &RM = *RMp;

@@ -1,5 +1,6 @@
 """GPU tests (-m gpu) of round 4, through the C ABI:
-* every placement rr_step's host side picks from the lagged heavy counters (csrc/realrobot.hip, "Look-ahead" block of rr_step)
+* every placement rr_step's host side picks from the lagged heavy counters (csrc/rr_plan.inc, plan_step; tests/test_step_plan.py
+  checks on the CPU which placement each knob setting below is)
   is FORCED through the knobs the library reads at rr_create and compared bitwise with the unsplit, in-line step
   (RR_NO_SPLIT=1 RR_NO_LOOKAHEAD=1): the schedule may never change a result (env.py:326-356 is one sequential step);
 * the macro workload and the late window of the headline workload exactly as bench.secondary_workloads runs them (4096 envs,
@@ -49,14 +50,15 @@ def _first_difference(a, b):
 # Every placement of realrobot.hip's rr_step, by the knob that forces it.  RR_FORCE_HCOUNT pins what the host-side decisions
 # read instead of the lagged counters ("heavy,very heavy"): launch shapes (coop form <= 256, list-walking render <= 768 items,
 # the look-ahead's placement) and placements then differ from what the device-side lists actually hold -- which is exactly the
-# situation of a lagged counter, and must not matter.
+# situation of a lagged counter, and must not matter.  (A long heavy list is read as 260 envs: more than the coop form's and the list
+# walker's caps, less than RR_SPLIT_MAX_PCT = 60 % of the 448 envs -- a reading above that share is placement 3 whatever else it says.)
 PLACEMENTS = [
     ('1: default (look-ahead behind the very heavy envs\' solve, their render behind the heavy envs\')', {}),
     ('1, empty lists assumed: coop solves, list-walking renders', {'RR_FORCE_HCOUNT': '0,0'}),
     ('1 with a long heavy list assumed: packed heavy solve, three-kernel render of the list, very heavy render at the main stream\'s tail',
-     {'RR_FORCE_HCOUNT': '2000,10'}),
+     {'RR_FORCE_HCOUNT': '260,10'}),
     ('2: many very heavy envs assumed: packed solves, kinematics + collide on the heavy stream, dynamics on the very heavy one',
-     {'RR_FORCE_HCOUNT': '2000,300'}),
+     {'RR_FORCE_HCOUNT': '260,300'}),
     ('3: split off (mostly heavy): one k_solve for all, look-ahead beside the render', {'RR_SPLIT_MAX_PCT': '0', 'RR_FORCE_HCOUNT': '1,0'}),
     ('1 <-> 3: the split switches off mid-run (more than 2 % heavy envs)', {'RR_SPLIT_MAX_PCT': '2'}),
     ('1 with k_collide in env order', {'RR_COLLIDE_ORDER': '0'}),
@@ -105,6 +107,29 @@ def test_every_schedule_placement_is_bitwise_the_inline_step(monkeypatch):
     assert (envs[0].host(nat.F_ERRFLAGS) == 0).all()
     for e in envs:
         e.close()
+
+
+# The one form of the heavy lists' render no reading reaches at 448 envs (a list too long for the walker, 192 envs, is more than a
+# third of them: the grid kernel): k_raster_list + k_shade, read at the smallest batch that has it.
+RASTER_LIST_FORM = {'RR_FORCE_HCOUNT': '200,10'}
+
+
+def test_raster_list_render_of_a_heavy_list_is_bitwise_the_inline_step(monkeypatch):
+    """640 envs at 128 x 128, full-range commands, a render every step: the heavy list rendered by k_raster_list + k_shade (placement
+    1': 200 heavy envs read, more than one list-walking launch takes, at most a third of the batch) is bitwise the in-line step."""
+    N, T = 640, 150
+    a = _make(monkeypatch, PLAIN, N, objects=3, width=128, height=128)
+    b = _make(monkeypatch, RASTER_LIST_FORM, N, objects=3, width=128, height=128)
+    for t in range(T):
+        cmd = synthetic_actions(range(N), t, seed=3).astype(np.float32)
+        a.step(cmd, render=True)
+        b.step(cmd, render=True)
+        if t % 50 == 49 or t < 2:
+            d = _first_difference(_snapshot(a), _snapshot(b))
+            assert d is None, (t, d)
+    cls = a.host(nat.F_ENV_CLASS)
+    assert (cls == 1).sum() >= 1, (cls == 1).sum()          # the list the form walks was not empty
+    a.close(); b.close()
 
 
 def test_collision_pass_order_and_pair_cull_change_no_result(monkeypatch):
