@@ -30,7 +30,9 @@ extern "C" {
                               header version 3 carries them too; RR_F_PREP; rr_pack_image_delta, rr_apply_image_delta;
                               7: rr_set_object_dynamics, rr_get_object_dynamics (per-env mass, inertia and contact materials of the
                               objects); checkpoint header version 4 carries them; rr_set_env_cameras, rr_set_env_appearance; rr_set_env_actuators,
-                              rr_get_env_actuators (per-env motor gains, motor force and joint damping; checkpoint header version 5 carries them) */
+                              rr_get_env_actuators (per-env motor gains, motor force and joint damping; checkpoint header version 5 carries them); rr_contact_observations;
+                              rr_set_goals, rr_set_env_goals, rr_set_episode, rr_episode_update, rr_episode_buffer (goal table and episode
+                              record on the device; checkpoints do not carry them) */
 
 enum {
     RR_OK = 0,
@@ -330,6 +332,66 @@ int rr_contact_observations(rr_env *env);
  * goal_mask byte is non-zero (NULL: every object) of exp(-(ln 4 / 0.10) * |goal_pos[i][o] - position[i][o]|), computed on the
  * device from the state.  goal_pos: f32 [N, n_obj, 3] (host), goal_mask: u8 [N, n_obj] (host), score_out: f32 [N] (host). */
 int rr_evaluate_goals(rr_env *env, const float *goal_pos_host, const uint8_t *goal_mask_host, float *score_out_host);
+
+/* ---- Goals and episodes on the device (additive in ABI 7) -------------------------------------------------------------------------
+ * A goal table and a per-env episode record live on the device; one launch per step (rr_episode_update) gives every env's score,
+ * reward and done bits and, on request, resets the finished envs into their next goal -- no host round trip.  The record's buffers
+ * are NOT fields of rr_get_buffer (RR_F_COUNT stays 16): they have this enum and rr_episode_buffer. */
+enum {
+    RR_EP_SCORE = 0,      /* f32 [N]            evaluateGoal of the env's goal at the last update (env.py:181-200); 0 without a goal */
+    RR_EP_REWARD = 1,     /* f32 [N]            score - previous score, one float32 subtraction */
+    RR_EP_DONE = 2,       /* u32 [N]            bit 0 truncated (RR_F_TIMESTEP >= horizon, env.py:345-352), bit 1 frozen (RR_F_ERRFLAGS & 5) */
+    RR_EP_GOAL_INDEX = 3, /* i32 [N]            the env's row of the goal table, -1: no goal */
+    RR_EP_EPISODE = 4,    /* i32 [N]            auto-resets of the env so far */
+    RR_EP_FINAL_OBS = 5,  /* f32 [N, 9 + 4 + 7 n_obj + 1]  joints, touch, object poses and score of the env's last finished episode; zero before */
+    RR_EP_GOAL_POS = 6,   /* f32 [N, n_obj, 3]  the goal's positions; NaN where the goal does not name the object, all NaN without a goal */
+    RR_EP_GOAL_RGB = 7,   /* u8  [N, H, W, 3]   the goal's image; all zero without a goal.  Exists only while the table has images */
+    RR_EP_COUNT = 8
+};
+/* Replaces the goal list of REALRobotEnv (load_goals / set_goal, env.py:151-166) with a device table of n_goals goals.  All arrays are
+ * host memory: start_poses f32 [G, n_obj, 7] (xyz + xyzw quaternion), final_pos f32 [G, n_obj, 3], flags u8 [G, n_obj], goal_rgb u8
+ * [G, H, W, 3] or NULL.  Flag bit 0: the object counts in the score (it is named in the goal's final_state); bit 1: the object has
+ * a start pose (it is named in initial_state), otherwise it starts from its home pose (rr_set_object_home).  Values of rows whose
+ * bit is clear are not read; a value that is read and is not finite returns RR_EINVAL (the message names goal and object) and
+ * nothing changes.  A new table leaves EVERY env without a goal (index -1) until rr_set_env_goals: indices into the old table mean
+ * nothing in the new one; n_goals == 0 drops the table.  Synchronous.  A failed allocation returns RR_EDEVICE, keeps the old table
+ * and leaves the handle usable.
+ * RR_EP_GOAL_RGB (N H W 3 bytes: 201 MB at 4096 envs of 128 x 128) is allocated by the first table that carries images and freed by a
+ * later table without: ITS POINTER MAY CHANGE whenever the image status of the table changes -- ask rr_episode_buffer again after
+ * rr_set_goals.  The pointers of all other RR_EP_* buffers survive rr_set_goals. */
+int rr_set_goals(rr_env *env, int32_t n_goals, const float *start_poses, const float *final_pos, const uint8_t *flags, const uint8_t *goal_rgb);
+/* Replaces the goal choice of REALRobotEnv.set_goal (env.py:151-158) for the envs whose mask byte is non-zero (NULL: all): goal_index
+ * i32 [N] host, -1: no goal, else a row in [0, G) (rows of unmasked envs are not read).  Stores the index, refreshes the env's
+ * RR_EP_GOAL_POS / RR_EP_GOAL_RGB and RE-BASES the env's previous score to the score of its CURRENT state: the next reward is taken
+ * against it.  Does not move objects and does not touch the state (the next step stays prepared).  An index out of range returns
+ * RR_EINVAL, the message names the env, and no env changes.  Synchronous. */
+int rr_set_env_goals(rr_env *env, const int32_t *goal_index, const uint8_t *env_mask_host);
+/* Episode rules of rr_episode_update: horizon > 0: an env is truncated once RR_F_TIMESTEP >= horizon (env.py:345-352); <= 0: never.
+ * goal_stride: an auto-reset takes the env from goal index i to (i + goal_stride) mod G; 0 keeps the goal; -1 (no goal) stays.
+ * Defaults: horizon 0, stride 1. */
+int rr_set_episode(rr_env *env, int32_t horizon, int32_t goal_stride);
+/* Replaces evaluateGoal and the `done` of step_joints (env.py:181-200, 345-352) and, with reset_done != 0, reset() + set_goal
+ * (env.py:151-166, 206-219) of the finished envs, for ALL envs in one launch on the library's stream; checks the launch and does not
+ * wait.  Per env: RR_EP_SCORE -- rr_evaluate_goals' arithmetic (one device function serves both) against the env's goal;
+ * RR_EP_REWARD = score - previous score, and the previous score becomes the score; RR_EP_DONE.  With reset_done != 0 every env with
+ * done != 0 then (1) gets its row of RR_EP_FINAL_OBS from the observation buffers as the step left them, (2) is reset as by rr_reset,
+ * (3) moves to its next goal, (4) has the objects with a start pose placed as by rr_set_object_poses -- the others keep their home
+ * pose --, (5) gets its RR_EP_GOAL_POS / RR_EP_GOAL_RGB refreshed, (6) has its previous score set to the score of the new start state
+ * and (7) its RR_EP_EPISODE incremented; score, reward and done of this call still describe the FINISHED episode.  The observation
+ * buffers are refreshed behind it and the next step prepares itself again, as after rr_reset; images are not rendered (rr_render).
+ * With reset_done == 0 the call changes no simulation state.
+ * The episode record is a setting of the handle, like the cameras: rr_reset, rr_set_state, rr_set_object_pose(s) and
+ * rr_checkpoint_restore leave it alone and checkpoints do not carry it -- after such an outside change the caller re-bases the
+ * previous score with rr_set_env_goals.
+ * Out of scope: orientation terms of the score, success thresholds, per-env horizons. */
+int rr_episode_update(rr_env *env, int32_t reset_done);
+/* Zero-copy device pointer + size of an RR_EP_* buffer, valid until rr_destroy (RR_EP_GOAL_RGB: until the table's image status
+ * changes, see rr_set_goals; RR_EINVAL for it while the table has no images).  The buffers are allocated on first use and
+ * zero-filled, except that every env starts without a goal: RR_EP_GOAL_INDEX -1, RR_EP_GOAL_POS NaN.  STREAM CONTRACT as for the other
+ * zero-copy views (rr_step): written on the library's stream, read-only for the caller. */
+int rr_episode_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
+/* Synchronising copy of a whole RR_EP_* buffer to host memory (rr_copy_to_host for the episode record). */
+int rr_episode_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
 
 /* Batched damped-least-squares inverse kinematics for link 7 (gripper `base`), seeded with each env's current joints.
  * Replaces pybullet.calculateInverseKinematics(0, 7, pos, orn, maxNumIterations=1000, residualThreshold=0.001) in

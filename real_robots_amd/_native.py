@@ -35,12 +35,17 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_checkpoint_save', 'rr_checkpoint_restore', 'rr_evaluate_goals', 'rr_device_microbench', 'rr_map_observations', 'rr_map_images', 'rr_sync_observations', 'rr_select_image_mirror',
            'rr_pack_image_delta', 'rr_apply_image_delta', 'rr_set_object_dynamics', 'rr_get_object_dynamics',
            'rr_set_env_cameras', 'rr_set_env_appearance', 'rr_get_env_appearance', 'rr_render_instances',
-           'rr_set_env_actuators', 'rr_get_env_actuators', 'rr_contact_observations')
+           'rr_set_env_actuators', 'rr_get_env_actuators', 'rr_contact_observations',
+           'rr_set_goals', 'rr_set_env_goals', 'rr_set_episode', 'rr_episode_update', 'rr_episode_buffer', 'rr_episode_copy_to_host')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
 ACT_ROW = ('kp', 'kd', 'max_force', 'damping')
 N_JOINTS = 11
+# buffers of rr_episode_buffer (the RR_EP_* enum: goals and episodes on the device)
+(EP_SCORE, EP_REWARD, EP_DONE, EP_GOAL_INDEX, EP_EPISODE, EP_FINAL_OBS, EP_GOAL_POS, EP_GOAL_RGB) = range(8)
+EP_NAMES = ('score', 'reward', 'done', 'goal_index', 'episode', 'final_obs', 'goal_pos', 'goal_rgb')
+GOAL_SCORED, GOAL_HAS_START = 1, 2      # rr_set_goals flag bits: the object counts in the score / has a start pose
 
 
 class Config(C.Structure):
@@ -153,6 +158,12 @@ def load_library():
     L.rr_get_object_dynamics.argtypes = [vp, vp]
     L.rr_set_env_actuators.argtypes = [vp, vp, vp]
     L.rr_get_env_actuators.argtypes = [vp, vp]
+    L.rr_set_goals.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.rr_set_env_goals.argtypes = [vp, vp, vp]
+    L.rr_set_episode.argtypes = [vp, i32, i32]
+    L.rr_episode_update.argtypes = [vp, i32]
+    L.rr_episode_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rr_episode_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]

@@ -348,6 +348,111 @@ class BatchedREALRobotEnv:
         nat.check(self.L.rr_evaluate_goals(self.h, g.ctypes.data, m.ctypes.data if m is not None else None, out.ctypes.data))
         return out
 
+    # ------------------------------------------------------------------ goals and episodes on the device
+    def set_goals(self, start_poses, final_pos, flags, goal_rgb=None):
+        """The goal table of the handle (rr_set_goals): start_poses [G, n_objects, 7] (xyz + xyzw quaternion), final_pos
+        [G, n_objects, 3], flags uint8 [G, n_objects] (bit 0 `_native.GOAL_SCORED`: the object counts in the score; bit 1
+        `_native.GOAL_HAS_START`: it has a start pose, else it starts from its home pose), goal_rgb uint8 [G, H, W, 3] or None.
+        Values whose bit is clear are not read (NaN is fine there); a value that is read must be finite.  G == 0 drops the table.
+        A new table leaves every env without a goal until `set_env_goals`."""
+        f = np.ascontiguousarray(flags, dtype=np.uint8)
+        if f.ndim != 2 or f.shape[1] != self.n_objects:
+            raise ValueError("flags must have shape (G, %d), not %s" % (self.n_objects, f.shape))
+        G = f.shape[0]
+        s = np.ascontiguousarray(start_poses, dtype=np.float32)
+        p = np.ascontiguousarray(final_pos, dtype=np.float32)
+        if s.shape != (G, self.n_objects, 7) or p.shape != (G, self.n_objects, 3):
+            raise ValueError("start_poses / final_pos must have shapes (%d, %d, 7) / (%d, %d, 3), not %s / %s"
+                             % (G, self.n_objects, G, self.n_objects, s.shape, p.shape))
+        if (~np.isfinite(p) & ((f & nat.GOAL_SCORED) != 0)[..., None]).any() or \
+                (~np.isfinite(s) & ((f & nat.GOAL_HAS_START) != 0)[..., None]).any():
+            raise ValueError("set_goals: a goal position / start pose that its flag selects is not finite")
+        r = None
+        if goal_rgb is not None:
+            r = np.ascontiguousarray(goal_rgb, dtype=np.uint8)
+            if r.shape != (G, self.H, self.W, 3):
+                raise ValueError("goal_rgb must have shape (%d, %d, %d, 3), not %s" % (G, self.H, self.W, r.shape))
+        nat.check(self.L.rr_set_goals(self.h, G, s.ctypes.data if G else None, p.ctypes.data if G else None, f.ctypes.data if G else None,
+                                      r.ctypes.data if (r is not None and G) else None))
+        self.n_goals, self.goal_images = G, bool(G and r is not None)
+
+    @staticmethod
+    def goal_arrays(goals, names):
+        """(start_poses [G, k, 7], final_pos [G, k, 3], flags [G, k], goal_rgb [G, H, W, 3] or None) of a list of `Goal` objects
+        for the objects `names`: what evaluate_batched gathers as g_init, g_final and g_mask -- NaN where a goal does not name an
+        object, flag bit 0 for the objects of final_state, bit 1 for those of initial_state.  goal_rgb: the goals' retinas when
+        every goal has one."""
+        names = list(names)
+        G, k = len(goals), len(names)
+        g_final = np.full((G, k, 3), np.nan, np.float32)
+        g_init = np.full((G, k, 7), np.nan, np.float32)
+        flags = np.zeros((G, k), np.uint8)
+        for j, g in enumerate(goals):
+            for n_, pose in (g.final_state or {}).items():
+                if n_ in names:
+                    g_final[j, names.index(n_)] = np.asarray(pose, np.float32)[:3]
+                    flags[j, names.index(n_)] |= nat.GOAL_SCORED
+            for n_, pose in (g.initial_state or {}).items():
+                if n_ in names:
+                    g_init[j, names.index(n_)] = np.asarray(pose, np.float32)
+                    flags[j, names.index(n_)] |= nat.GOAL_HAS_START
+        rgb = None
+        if G and all(getattr(g, 'retina', None) is not None for g in goals):
+            rgb = np.stack([np.asarray(g.retina, np.uint8) for g in goals])
+        return g_init, g_final, flags, rgb
+
+    def set_goals_from(self, goals, names=None):
+        """`set_goals` from `Goal` objects (envs.env.Goal: initial_state / final_state dicts name -> pose, retina); names: the
+        objects of the handle (default: `object_names`).  Returns the arrays of `goal_arrays`."""
+        arr = self.goal_arrays(goals, self.object_names if names is None else names)
+        self.set_goals(*arr)
+        return arr
+
+    def set_env_goals(self, index, env_mask=None):
+        """Goal index of the masked envs (rr_set_env_goals): int [N] (or one int for all), -1: no goal.  Refreshes their goal
+        observations and re-bases their previous score to the score of the current state; moves nothing."""
+        try:
+            idx = np.ascontiguousarray(np.broadcast_to(np.asarray(index, dtype=np.int32), (self.N,)))
+        except ValueError:
+            raise ValueError("index must have shape (%d,)" % self.N)
+        m, mp = _env_mask(env_mask, self.N)
+        nat.check(self.L.rr_set_env_goals(self.h, idx.ctypes.data, mp))
+
+    def set_episode(self, horizon, goal_stride=1):
+        """horizon > 0: an env is truncated once its timestep reaches it (<= 0: never); goal_stride: an auto-reset takes an env
+        from goal i to (i + goal_stride) mod G (rr_set_episode)."""
+        nat.check(self.L.rr_set_episode(self.h, int(horizon), int(goal_stride)))
+
+    def episode_update(self, reset_done=False):
+        """One launch on the library's stream (rr_episode_update): score, reward = score - previous score and done bits (1
+        truncated, 2 frozen) of every env; with reset_done the envs with done != 0 are reset into their next goal on the device
+        (their last observation goes to the `final_obs` buffer).  Does not wait and does not render."""
+        nat.check(self.L.rr_episode_update(self.h, 1 if reset_done else 0))
+
+    def _episode_shape(self, which):
+        N, k = self.N, self.n_objects
+        return {nat.EP_SCORE: ((N,), np.float32), nat.EP_REWARD: ((N,), np.float32), nat.EP_DONE: ((N,), np.uint32),
+                nat.EP_GOAL_INDEX: ((N,), np.int32), nat.EP_EPISODE: ((N,), np.int32),
+                nat.EP_FINAL_OBS: ((N, 13 + 7 * k + 1), np.float32), nat.EP_GOAL_POS: ((N, k, 3), np.float32),
+                nat.EP_GOAL_RGB: ((N, self.H, self.W, 3), np.uint8)}[which]
+
+    def episode_buffer(self, name, host=False):
+        """A buffer of the episode record (rr_episode_buffer), by name (`_native.EP_NAMES`: score, reward, done, goal_index,
+        episode, final_obs [N, 9 + 4 + 7 n_objects + 1], goal_pos [N, n_objects, 3], goal_rgb [N, H, W, 3]) or EP_* constant: a
+        device view (DLPack / __cuda_array_interface__, zero copy; ordering as for the other device buffers), or with host=True a
+        numpy copy after a wait.  goal_rgb exists only while the goal table has images -- ask again after `set_goals`."""
+        which = nat.EP_NAMES.index(name) if isinstance(name, str) and name in nat.EP_NAMES else name
+        if not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.EP_NAMES):
+            raise ValueError("unknown episode buffer %r (known: %s)" % (name, ', '.join(nat.EP_NAMES)))
+        shape, dt = self._episode_shape(int(which))
+        if host:
+            out = np.empty(shape, dt)
+            nat.check(self.L.rr_episode_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
+            return out
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(self.L.rr_episode_buffer(self.h, int(which), C.byref(p), C.byref(n)))
+        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
+
     def link_poses(self):
         out = np.empty((self.N, len(nat.LINK_NAMES), 7), np.float32)
         nat.check(self.L.rr_link_poses(self.h, out.ctypes.data))

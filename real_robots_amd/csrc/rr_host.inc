@@ -176,6 +176,17 @@ struct rr_env : ModelTables {
     // per-env appearance (rr_set_env_appearance): allocated by its first call; D.env_colour / D.env_light point at them while it is in force
     std::vector<float> colour_host, light_host;    // [N][MAXINST][3], [N][4] (unit vectors): what is uploaded, and what rr_get_env_appearance returns
     float *colour_dev = nullptr, *light_dev = nullptr;
+    // goals and episodes (rr_set_goals .. rr_episode_update): a setting of the handle like the cameras.  The record's buffers are one
+    // block, allocated on first use and kept until rr_destroy (in `allocs`); the table and RR_EP_GOAL_RGB are replaced by rr_set_goals
+    // and freed by it / by rr_destroy.
+    GoalTable goals = {};          // device table in force (G 0: none)
+    void *goals_block = nullptr;   // its allocation {start, final_pos, flags}
+    unsigned char *goals_rgb = nullptr;      // [G][H*W*3] the table's images or nullptr
+    EpisodeRec ep = {};            // ep.score == nullptr: not allocated yet
+    int *ep_index_stage = nullptr; // [N] staging of rr_set_env_goals' indices
+    unsigned char *ep_goal_rgb = nullptr;    // RR_EP_GOAL_RGB [N][H*W*3]: exists exactly while the table has images
+    size_t ep_bytes[RR_EP_COUNT] = {};
+    int ep_horizon = 0, ep_stride = 1;
 };
 
 // The combining rule of the contact materials of two shapes (btManifoldResult::calculateCombinedFriction / Restitution /
@@ -522,6 +533,7 @@ int rr_destroy(rr_env *e) {
     hipSetDevice(e->cfg.device);
     hipStreamSynchronize(e->stream);
     for (void *p : e->allocs) hipFree(p);
+    for (void *p : {e->goals_block, (void *)e->goals_rgb, (void *)e->ep_goal_rgb}) if (p) hipFree(p);
     for (int i = 0; i < 2 * RR_NUM_KERNELS; i++) if (e->ev[i]) hipEventDestroy(e->ev[i]);
     if (e->aux) { hipStreamSynchronize(e->aux); hipStreamDestroy(e->aux); }
     if (e->aux2) { hipStreamSynchronize(e->aux2); hipStreamDestroy(e->aux2); }
@@ -2012,6 +2024,195 @@ int rr_render_instances(rr_env *e, int32_t *n_inst, int32_t *owner_out) {
         for (int i = 0; i < RM.ni; i++) {
             owner_out[4 * i] = RM.in_otype[i]; owner_out[4 * i + 1] = RM.in_oidx[i]; owner_out[4 * i + 2] = RM.in_uid[i]; owner_out[4 * i + 3] = RM.in_tex[i];
         }
+    return RR_OK;
+}
+
+// ---- goals and episodes on the device (rr_episode.inc) ------------------------------------------------------------------------
+static inline size_t image_bytes(const rr_env *e) { return (size_t)e->RM.W * e->RM.H * 3; }
+static inline dim3 ep_grid(const rr_env *e) { return dim3((e->P.N + 255) / 256); }
+
+// RR_EP_GOAL_RGB of the envs whose "goal changed" byte the last k_episode / k_env_goals launch set
+static void launch_goal_image(rr_env *e) {
+    if (!e->ep_goal_rgb) return;
+    const size_t B = image_bytes(e);
+    const int N = e->P.N, G = e->goals_rgb ? e->goals.G : 0;
+    if (B % 16 == 0) {
+        const unsigned units = (unsigned)(B / 16), chunks = (units + GI_CHUNK - 1) / GI_CHUNK;
+        hipLaunchKernelGGL(k_goal_image<uint4>, dim3((unsigned)N * chunks), dim3(GI_THREADS), 0, e->stream, N, G, units, chunks, e->ep.goal_index, e->ep.changed,
+                           (const uint4 *)e->goals_rgb, (uint4 *)e->ep_goal_rgb);
+    } else {
+        const unsigned units = (unsigned)(B / 4), chunks = (units + GI_CHUNK - 1) / GI_CHUNK;
+        hipLaunchKernelGGL(k_goal_image<unsigned>, dim3((unsigned)N * chunks), dim3(GI_THREADS), 0, e->stream, N, G, units, chunks, e->ep.goal_index, e->ep.changed,
+                           (const unsigned *)e->goals_rgb, (unsigned *)e->ep_goal_rgb);
+    }
+}
+
+// every env of the mask (nullptr: all) to the goal index_dev[env] (nullptr: no goal), on the library's stream
+static void launch_env_goals(rr_env *e, const int *index_dev, const unsigned char *mask_dev) {
+    hipLaunchKernelGGL(k_env_goals, ep_grid(e), dim3(256), 0, e->stream, e->P, e->D, e->goals, e->ep, index_dev, mask_dev);
+    launch_goal_image(e);
+}
+
+// The episode record: one block, allocated on first use, zero-filled, every env without a goal (index -1, RR_EP_GOAL_POS all NaN).
+// A failed allocation leaves the handle as it was (as ensure_contact_obs).
+static int ensure_episode(rr_env *e) {
+    if (e->ep.score) return RR_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const size_t N = e->P.N, nobj = e->P.nobj;
+    static_assert(RR_EP_GOAL_RGB == RR_EP_COUNT - 1, "the image buffer is the last one and not part of the block");
+    size_t *b = e->ep_bytes;
+    b[RR_EP_SCORE] = b[RR_EP_REWARD] = b[RR_EP_DONE] = b[RR_EP_GOAL_INDEX] = b[RR_EP_EPISODE] = N * 4;
+    b[RR_EP_FINAL_OBS] = N * (13 + 7 * nobj + 1) * 4;
+    b[RR_EP_GOAL_POS] = N * nobj * 12;
+    b[RR_EP_GOAL_RGB] = N * image_bytes(e);
+    auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    size_t total = 0;
+    for (int i = 0; i < RR_EP_GOAL_RGB; i++) total += up(b[i]);
+    total += 3 * up(N * 4);                     // previous score, index staging, "goal changed" bytes
+    void *q = nullptr;
+    hipError_t rc = hipMalloc(&q, total);
+    if (rc == hipSuccess && (rc = hipMemsetAsync(q, 0, total, e->stream)) != hipSuccess) hipFree(q);
+    if (rc != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(RR_EDEVICE, std::string("rr_episode: allocating the episode record: ") + hipGetErrorString(rc));
+    }
+    e->allocs.push_back(q);
+    char *p = (char *)q;
+    auto take = [&](size_t bytes) { char *r = p; p += up(bytes); return r; };
+    EpisodeRec &E = e->ep;
+    E.score = (float *)take(b[RR_EP_SCORE]); E.reward = (float *)take(b[RR_EP_REWARD]); E.done = (unsigned *)take(b[RR_EP_DONE]);
+    E.goal_index = (int *)take(b[RR_EP_GOAL_INDEX]); E.episode = (int *)take(b[RR_EP_EPISODE]);
+    E.final_obs = (float *)take(b[RR_EP_FINAL_OBS]); E.goal_pos = (float *)take(b[RR_EP_GOAL_POS]);
+    E.prev = (float *)take(N * 4); e->ep_index_stage = (int *)take(N * 4); E.changed = (unsigned char *)take(N * 4);
+    launch_env_goals(e, nullptr, nullptr);
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+int rr_set_goals(rr_env *e, int32_t n_goals, const float *start_poses, const float *final_pos, const uint8_t *flags, const uint8_t *goal_rgb) {
+    if (!e || n_goals < 0 || (n_goals > 0 && (!start_poses || !final_pos || !flags))) return fail(RR_EINVAL, "rr_set_goals: bad argument");
+    const size_t G = (size_t)n_goals, nobj = e->P.nobj, B = image_bytes(e);
+    for (size_t g = 0; g < G; g++)
+        for (size_t i = 0; i < nobj; i++) {
+            const unsigned f = flags[g * nobj + i];
+            bool ok = true;
+            if (f & 1u) for (int k = 0; k < 3; k++) ok = ok && std::isfinite(final_pos[(g * nobj + i) * 3 + k]);
+            if (f & 2u) for (int k = 0; k < 7; k++) ok = ok && std::isfinite(start_poses[(g * nobj + i) * 7 + k]);
+            if (!ok) return fail(RR_EINVAL, "rr_set_goals: goal " + std::to_string(g) + ", object " + std::to_string(i) + ": a value that is read is not finite");
+        }
+    int rc = ensure_episode(e);
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const bool images = G > 0 && goal_rgb != nullptr;
+    // everything the new table needs is allocated before anything of the old one is given up
+    auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t bs = up(G * nobj * 28), bf = up(G * nobj * 12), bfl = up(G * nobj);
+    void *blk = nullptr, *rgb = nullptr, *env_rgb = nullptr;
+    hipError_t hrc = hipSuccess;
+    if (G > 0) hrc = hipMalloc(&blk, bs + bf + bfl);
+    if (hrc == hipSuccess && images) hrc = hipMalloc(&rgb, G * B);
+    if (hrc == hipSuccess && images && !e->ep_goal_rgb) {
+        hrc = hipMalloc(&env_rgb, (size_t)e->P.N * B);
+        if (hrc == hipSuccess) hrc = hipMemsetAsync(env_rgb, 0, (size_t)e->P.N * B, e->stream);
+    }
+    if (hrc == hipSuccess && G > 0) {
+        hrc = hipMemcpyAsync(blk, start_poses, G * nobj * 28, hipMemcpyHostToDevice, e->stream);
+        if (hrc == hipSuccess) hrc = hipMemcpyAsync((char *)blk + bs, final_pos, G * nobj * 12, hipMemcpyHostToDevice, e->stream);
+        if (hrc == hipSuccess) hrc = hipMemcpyAsync((char *)blk + bs + bf, flags, G * nobj, hipMemcpyHostToDevice, e->stream);
+        if (hrc == hipSuccess && images) hrc = hipMemcpyAsync(rgb, goal_rgb, G * B, hipMemcpyHostToDevice, e->stream);
+    }
+    // (the wait also ends every queued kernel that reads the old table)
+    if (hrc == hipSuccess) hrc = hipStreamSynchronize(e->stream);
+    if (hrc != hipSuccess) {
+        (void)hipStreamSynchronize(e->stream);
+        for (void *p : {blk, rgb, env_rgb}) if (p) hipFree(p);
+        (void)hipGetLastError();
+        return fail(RR_EDEVICE, std::string("rr_set_goals: allocating / uploading the goal table: ") + hipGetErrorString(hrc));
+    }
+    if (e->goals_block) hipFree(e->goals_block);
+    if (e->goals_rgb) hipFree(e->goals_rgb);
+    e->goals_block = blk; e->goals_rgb = (unsigned char *)rgb;
+    e->goals.G = (int)G;
+    e->goals.start = (const float *)blk; e->goals.final_pos = (const float *)((char *)blk + bs); e->goals.flags = (const unsigned char *)blk + bs + bf;
+    if (!G) e->goals = GoalTable{};
+    if (env_rgb) e->ep_goal_rgb = (unsigned char *)env_rgb;
+    else if (!images && e->ep_goal_rgb) { hipFree(e->ep_goal_rgb); e->ep_goal_rgb = nullptr; }
+    // indices into the old table mean nothing in the new one: every env is without a goal until rr_set_env_goals
+    launch_env_goals(e, nullptr, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return RR_OK;
+}
+
+int rr_set_env_goals(rr_env *e, const int32_t *goal_index, const uint8_t *env_mask_host) {
+    if (!e || !goal_index) return fail(RR_EINVAL, "null argument");
+    const int N = e->P.N;
+    for (int i = 0; i < N; i++)
+        if ((!env_mask_host || env_mask_host[i]) && (goal_index[i] < -1 || goal_index[i] >= e->goals.G))
+            return fail(RR_EINVAL, "rr_set_env_goals: env " + std::to_string(i) + ": goal index " + std::to_string(goal_index[i]) + " is not -1 or in [0, " + std::to_string(e->goals.G) + ")");
+    const int rc = ensure_episode(e);
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    HIPCHK(hipMemcpyAsync(e->ep_index_stage, goal_index, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+    const unsigned char *m = nullptr;
+    if (env_mask_host) { HIPCHK(hipMemcpyAsync(e->mask_dev, env_mask_host, N, hipMemcpyHostToDevice, e->stream)); m = e->mask_dev; }
+    launch_env_goals(e, e->ep_index_stage, m);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));   // the arguments are host memory
+    return RR_OK;
+}
+
+int rr_set_episode(rr_env *e, int32_t horizon, int32_t goal_stride) {
+    if (!e) return fail(RR_EINVAL, "null env");
+    e->ep_horizon = horizon; e->ep_stride = goal_stride;
+    return RR_OK;
+}
+
+int rr_episode_update(rr_env *e, int32_t reset_done) {
+    if (!e) return fail(RR_EINVAL, "null env");
+    const int rc = ensure_episode(e);
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const int G = e->goals.G;
+    const int stride = G > 0 ? (int)((((long long)e->ep_stride % G) + G) % G) : 0;
+    hipLaunchKernelGGL(k_episode, ep_grid(e), dim3(256), 0, e->stream, e->P, e->D, e->goals, e->ep, e->ep_horizon, stride, reset_done ? 1 : 0);
+    if (reset_done) {
+        launch_goal_image(e);
+        e->la_valid = false;      // the device may have reset envs the look-ahead prepared for (as rr_reset)
+        launch_obs(e);
+    }
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+static int episode_field(rr_env *e, int32_t which, void **ptr, const char *who) {
+    if (!e || which < 0 || which >= RR_EP_COUNT) return fail(RR_EINVAL, std::string(who) + ": bad buffer");
+    const int rc = ensure_episode(e);
+    if (rc != RR_OK) return rc;
+    if (which == RR_EP_GOAL_RGB && !e->ep_goal_rgb) return fail(RR_EINVAL, std::string(who) + ": RR_EP_GOAL_RGB exists only while the goal table has images");
+    void *const p[RR_EP_COUNT] = {e->ep.score, e->ep.reward, e->ep.done, e->ep.goal_index, e->ep.episode, e->ep.final_obs, e->ep.goal_pos, e->ep_goal_rgb};
+    *ptr = p[which];
+    return RR_OK;
+}
+
+int rr_episode_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
+    void *p = nullptr;
+    const int rc = episode_field(e, which, &p, "rr_episode_buffer");
+    if (rc != RR_OK) return rc;
+    if (dev_ptr) *dev_ptr = p;
+    if (bytes) *bytes = e->ep_bytes[which];
+    return RR_OK;
+}
+
+int rr_episode_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
+    if (!dst) return fail(RR_EINVAL, "rr_episode_copy_to_host: null destination");
+    void *p = nullptr;
+    const int rc = episode_field(e, which, &p, "rr_episode_copy_to_host");
+    if (rc != RR_OK) return rc;
+    if (bytes != e->ep_bytes[which]) return fail(RR_EINVAL, "rr_episode_copy_to_host: size mismatch");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    HIPCHK(hipMemcpyAsync(dst, p, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
     return RR_OK;
 }
 

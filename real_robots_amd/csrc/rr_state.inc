@@ -1,11 +1,8 @@
 // rr_state.inc -- part of realrobot.hip (included there, in this order; not a stand-alone translation unit).
 // reset / state io / observation kernels, render set-up
 // ---------------------------------------------------------------------------------------------- reset / state io
-__global__ void k_reset(BodyParams B, SimParams P, DevPtrs D, const unsigned char *mask) {
-    const int N = P.N;
-    int env = blockIdx.x * blockDim.x + threadIdx.x;
-    if (env >= N) return;
-    if (mask && !mask[env]) return;
+// what a reset does for one env (k_reset, and the auto-reset of k_episode in rr_episode.inc)
+__device__ __forceinline__ void reset_env(const DevPtrs &D, int N, int env) {
     float *state = D.state;
     for (int i = 0; i < ST_TOTAL; i++) STT(i) = 0;
     for (int i = 0; i < NOBJ; i++) {
@@ -17,6 +14,14 @@ __global__ void k_reset(BodyParams B, SimParams P, DevPtrs D, const unsigned cha
     for (int k = 0; k < 4; k++) D.touch[(size_t)env * 4 + k] = 0;
     D.ccount[env] = 0;
     D.ccount_pub[env] = 0; D.class_pub[env] = 0;
+}
+
+__global__ void k_reset(BodyParams B, SimParams P, DevPtrs D, const unsigned char *mask) {
+    const int N = P.N;
+    int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env >= N) return;
+    if (mask && !mask[env]) return;
+    reset_env(D, N, env);
 }
 
 __global__ void k_state_io(SimParams P, DevPtrs D, float *aos /*[N][61]*/, int to_aos) {
@@ -49,6 +54,12 @@ __global__ void k_state_io(SimParams P, DevPtrs D, float *aos /*[N][61]*/, int t
     }
 }
 
+// object i of one env to the pose p7 (xyz + xyzw quaternion), at rest (k_set_object_poses, and the start poses of k_episode)
+__device__ __forceinline__ void set_object_pose_env(float *state, int N, int env, int i, const float *p7) {
+    for (int k = 0; k < 3; k++) { STT(ST_OPOS + 3 * i + k) = p7[k]; STT(ST_OVEL + 3 * i + k) = 0; STT(ST_OANG + 3 * i + k) = 0; }
+    for (int k = 0; k < 4; k++) STT(ST_OQUAT + 4 * i + k) = p7[3 + k];
+}
+
 // rr_set_object_poses: poses [N][nobj][7] for the envs whose mask byte is set (nullptr: all); zeroes the velocities like
 // BodyPart.reset_pose -> resetBasePositionAndOrientation (env.py:159-162)
 __global__ void k_set_object_poses(SimParams P, DevPtrs D, const float *poses, const unsigned char *mask) {
@@ -56,29 +67,29 @@ __global__ void k_set_object_poses(SimParams P, DevPtrs D, const float *poses, c
     int env = blockIdx.x * blockDim.x + threadIdx.x;
     if (env >= N) return;
     if (mask && !mask[env]) return;
-    float *state = D.state;
-    for (int i = 0; i < P.nobj; i++) {
-        const float *p7 = poses + ((size_t)env * P.nobj + i) * 7;
-        for (int k = 0; k < 3; k++) { STT(ST_OPOS + 3 * i + k) = p7[k]; STT(ST_OVEL + 3 * i + k) = 0; STT(ST_OANG + 3 * i + k) = 0; }
-        for (int k = 0; k < 4; k++) STT(ST_OQUAT + 4 * i + k) = p7[3 + k];
-    }
+    for (int i = 0; i < P.nobj; i++) set_object_pose_env(D.state, N, env, i, poses + ((size_t)env * P.nobj + i) * 7);
 }
 
-// REALRobotEnv.evaluateGoal (env.py:181-200) for every env: sum over the goal's objects of exp(-(ln 4 / 0.10) |p_goal - p|)
+// REALRobotEnv.evaluateGoal (env.py:181-200) for one env: sum over the goal's objects of exp(-(ln 4 / 0.10) |p_goal - p|).  The ONE
+// place with the score's arithmetic: k_goal_score (rr_evaluate_goals) and k_episode (rr_episode_update) both call it, so the two
+// agree bit for bit.  goal_pos: the env's rows [nobj][3]; object i counts when goal_mask is nullptr or goal_mask[i] & bits.
+__device__ __forceinline__ float goal_score_env(const float *state, int N, int env, int nobj, const float *goal_pos, const unsigned char *goal_mask, unsigned bits) {
+    const float pos_const = 13.862943611198906f;        // -log(0.25) / 0.10: the score falls to 0.25 within 10 cm
+    float sc = 0.0f;
+    for (int i = 0; i < nobj; i++) {
+        if (goal_mask && !(goal_mask[i] & bits)) continue;
+        const float *g = goal_pos + 3 * i;
+        const float dx = g[0] - STT(ST_OPOS + 3 * i), dy = g[1] - STT(ST_OPOS + 3 * i + 1), dz = g[2] - STT(ST_OPOS + 3 * i + 2);
+        sc += expf(-pos_const * sqrtf(dx * dx + dy * dy + dz * dz));
+    }
+    return sc;
+}
+
 __global__ void k_goal_score(SimParams P, DevPtrs D, const float *goal_pos /*[N][nobj][3]*/, const unsigned char *goal_mask /*[N][nobj] or nullptr*/, float *score) {
     const int N = P.N;
     const int env = blockIdx.x * blockDim.x + threadIdx.x;
     if (env >= N) return;
-    const float *state = D.state;
-    const float pos_const = 13.862943611198906f;        // -log(0.25) / 0.10: the score falls to 0.25 within 10 cm
-    float sc = 0.0f;
-    for (int i = 0; i < P.nobj; i++) {
-        if (goal_mask && !goal_mask[(size_t)env * P.nobj + i]) continue;
-        const float *g = goal_pos + ((size_t)env * P.nobj + i) * 3;
-        const float dx = g[0] - STT(ST_OPOS + 3 * i), dy = g[1] - STT(ST_OPOS + 3 * i + 1), dz = g[2] - STT(ST_OPOS + 3 * i + 2);
-        sc += expf(-pos_const * sqrtf(dx * dx + dy * dy + dz * dz));
-    }
-    score[env] = sc;
+    score[env] = goal_score_env(D.state, N, env, P.nobj, goal_pos + (size_t)env * P.nobj * 3, goal_mask ? goal_mask + (size_t)env * P.nobj : nullptr, 0xffu);
 }
 
 // ---------------------------------------------------------------------------------------------- render setup

@@ -47,12 +47,25 @@ Contact observations: `contact_obs=True` adds `body_force` [N, 20, 2] (float32: 
 robot links and the three objects) and `body_partners` [N, 20] (uint32 bit mask: bit 0 a static body, bit 1 + j object j, bit 4 the
 robot) to the observation dict and to the spaces (BatchedREALRobotEnv.contact_observations), computed where the other entries are
 gathered: after a same-step autoreset they describe the reset state.  The default leaves dict and spaces as they are.
+Goals: `goals=` (the path of a goals dataset, or a list of `Goal` objects) with `goal_stride=` puts the goal table and the episode
+record on the device (BatchedREALRobotEnv.set_goals_from / episode_update; evaluateGoal, env.py:181-200).  reset() gives env i the
+goal i mod G and starts it from that goal's start poses; every step() returns as rewards the change of the env's goal score over
+the step (`score - previous score`; the first one of an episode is taken against the score of its start state) -- a device view
+with `device_obs=True`, a host copy otherwise --, `infos["goal_score"]` (the score behind the reward: on a truncation step that of
+the FINISHED episode) and `infos["goal_index"]` (the goal the returned observation belongs to).  The observations gain `"goal"`
+[N, H, W, 3] when the goals carry images (all zero for an env without a goal) and, with `additional_obs`, `"goal_positions"`
+[N, n_objects, 3] (NaN where the goal does not name the object).  A truncated env moves on to goal (index + goal_stride) mod G
+inside the step that truncated it, on the device: reset, start poses, goal observations; `infos["final_obs"]` comes from the
+device's record of the finished episode, in the layout above.  Terminations stay all False.  An env the step froze (a non-finite
+state, RR_F_ERRFLAGS & 5) is NOT reset at once: it is reset with the next truncation sweep -- the next step in which any env
+reaches `max_episode_steps` --, and is reported as truncated in that step.  Without `goals` nothing changes: zero rewards, the
+observation dict and infos as they were.
 """
 import numpy as np
 
 from . import _native as nat
 from . import mathutil, spaces
-from .batched import BatchedREALRobotEnv
+from .batched import OBJECT_NAMES, BatchedREALRobotEnv
 from .envs.robot import Kuka
 from .model import load_model
 
@@ -77,8 +90,11 @@ def _batch_dict_space(space, n):
 class REALRobotVectorEnv(_Base):
     def __init__(self, num_envs, objects=3, additional_obs=False, eye_width=320, eye_height=240, device=0,
                  max_episode_steps=int(15e6), render_every_step=True, device_obs=False, solver=None, dynamics_randomization=None,
-                 camera_randomization=None, appearance_randomization=None, actuator_randomization=None, contact_obs=False):
+                 camera_randomization=None, appearance_randomization=None, actuator_randomization=None, contact_obs=False,
+                 goals=None, goal_stride=1):
         self.num_envs = int(num_envs)
+        self._goals = None if goals is None else self._check_goals(goals, OBJECT_NAMES[:int(objects)], int(eye_height), int(eye_width))
+        self.goal_stride = int(goal_stride)
         self._robot = Kuka(additional_obs, objects, eye_width, eye_height, env=None)
         self.single_action_space = spaces.Dict({"joint_command": self._robot.action_space, "render": spaces.MultiBinary(1)})
         self.single_observation_space = self._robot.observation_space
@@ -102,6 +118,10 @@ class REALRobotVectorEnv(_Base):
         # host-side episode clocks (no device read-back per step): the batched env behind this adapter is private to it, every
         # path that resets an env goes through reset() / step() below and resets its clock with it
         self._steps = np.zeros(self.num_envs, np.int64)
+        if self._goals is not None:
+            self._g_init, self._g_final, self._g_flags, rgb = self._be.set_goals_from(self._goals)
+            self._goal_images = rgb is not None
+            self._be.set_episode(self.max_episode_steps, self.goal_stride)
         self._dyn_rand = None
         if dynamics_randomization:
             self._dyn_rand = {}
@@ -179,6 +199,33 @@ class REALRobotVectorEnv(_Base):
             self._act_default = self._be.default_env_actuators()
         self._act_rng = np.random.default_rng()
 
+    @staticmethod
+    def _check_goals(goals, names, H, W):
+        """`goals=` -> a non-empty list of Goal-like objects, checked on the host (before any device is touched): a path is loaded
+        like REALRobotEnv.load_goals; every goal needs `final_state` / `initial_state` dicts that name at least one of this env's
+        objects in final_state, and a retina -- if it has one -- of this env's camera size.  ValueError otherwise."""
+        import os
+        if isinstance(goals, (str, bytes, os.PathLike)):
+            if not os.path.exists(goals):
+                raise ValueError("goals: no goals dataset at %r" % (goals,))
+            goals = list(np.load(goals, allow_pickle=True).items())[0][1]
+        try:
+            goals = list(goals)
+        except TypeError:
+            raise ValueError("goals must be a path or a list of Goal objects, not %r" % type(goals).__name__)
+        if not goals:
+            raise ValueError("goals: the goal list is empty")
+        for k, g in enumerate(goals):
+            fs, ins = getattr(g, 'final_state', None), getattr(g, 'initial_state', None)
+            if not isinstance(fs, dict) or not isinstance(ins, dict):
+                raise ValueError("goals[%d] is not a Goal (final_state / initial_state dicts expected)" % k)
+            if not any(n in names for n in fs):
+                raise ValueError("goals[%d] names none of this env's objects (%s) in its final_state" % (k, ', '.join(names)))
+            r = getattr(g, 'retina', None)
+            if r is not None and np.shape(r) != (H, W, 3):
+                raise ValueError("goals[%d].retina has shape %s, this env's camera gives (%d, %d, 3)" % (k, np.shape(r), H, W))
+        return goals
+
     DYNAMICS_FIELDS = ('mass', 'inertia', 'friction', 'restitution', 'rolling', 'spinning')
 
     def _draw_dynamics(self, mask):
@@ -253,6 +300,21 @@ class REALRobotVectorEnv(_Base):
         self._be.set_env_actuators(env_mask=mask.astype(np.uint8), **args)
         return self._be.env_actuators()
 
+    def _redraw(self, truncated, infos):
+        """The domain-randomisation draws of a same-step autoreset: new values for the envs in `truncated`, reported in infos."""
+        if self._dyn_rand:
+            infos["object_dynamics"] = self._draw_dynamics(truncated)
+            infos["_object_dynamics"] = truncated.copy()
+        if self._cam_rand:
+            infos["camera"] = self._draw_cameras(truncated)
+            infos["_camera"] = truncated.copy()
+        if self._app_rand:
+            infos["appearance"] = self._draw_appearance(truncated)
+            infos["_appearance"] = truncated.copy()
+        if self._act_rand:
+            infos["actuators"] = self._draw_actuators(truncated)
+            infos["_actuators"] = truncated.copy()
+
     # ------------------------------------------------------------------ observations
     def _obs(self, rendered):
         be = self._be
@@ -267,6 +329,11 @@ class REALRobotVectorEnv(_Base):
         if self.contact_obs:
             co = be.contact_observations(host=not self.device_obs)
             obs["body_force"], obs["body_partners"] = co["body_force"], co["body_partners"]
+        if self._goals is not None:
+            if self._goal_images:
+                obs["goal"] = be.episode_buffer('goal_rgb', host=not self.device_obs)
+            if self.additional_obs:
+                obs["goal_positions"] = be.episode_buffer('goal_pos', host=not self.device_obs)
         return obs
 
     def reset(self, *, seed=None, options=None):
@@ -286,6 +353,15 @@ class REALRobotVectorEnv(_Base):
             infos["actuators"] = self._draw_actuators(np.ones(self.num_envs, bool))
         self._be.reset()
         self._steps[:] = 0
+        if self._goals is not None:
+            # env i starts goal i mod G from its start poses (set_goal, env.py:151-166); the first reward is taken against that state
+            gi = (np.arange(self.num_envs) % len(self._goals)).astype(np.int32)
+            start = self._be.host(nat.F_OBJ_POSE)
+            named = (self._g_flags[gi] & nat.GOAL_HAS_START) != 0
+            start[named] = self._g_init[gi][named]
+            self._be.set_object_poses(start)
+            self._be.set_env_goals(gi)
+            infos["goal_index"] = gi
         if self.render_every_step:
             self._be.render()
         return self._obs(self.render_every_step), infos
@@ -301,6 +377,8 @@ class REALRobotVectorEnv(_Base):
         truncated = self._steps >= self.max_episode_steps
         n = self.num_envs
         infos = {}
+        if self._goals is not None:
+            return self._finish_goal_step(render, truncated, infos)
         if truncated.any():
             # same-step autoreset: keep the finished episodes' last low-dim observation, reset those envs, re-render them
             # (gymnasium's layout: an object array with one dict per finished env and None elsewhere, plus the boolean mask)
@@ -313,23 +391,40 @@ class REALRobotVectorEnv(_Base):
                     fin[i]["object_positions"] = op[i]
             infos["final_obs"] = fin
             infos["_final_obs"] = truncated.copy()
-            if self._dyn_rand:
-                infos["object_dynamics"] = self._draw_dynamics(truncated)
-                infos["_object_dynamics"] = truncated.copy()
-            if self._cam_rand:
-                infos["camera"] = self._draw_cameras(truncated)
-                infos["_camera"] = truncated.copy()
-            if self._app_rand:
-                infos["appearance"] = self._draw_appearance(truncated)
-                infos["_appearance"] = truncated.copy()
-            if self._act_rand:
-                infos["actuators"] = self._draw_actuators(truncated)
-                infos["_actuators"] = truncated.copy()
+            self._redraw(truncated, infos)
             self._be.reset(truncated.astype(np.uint8))
             self._steps[truncated] = 0
             if render:
                 self._be.render()
         return self._obs(render), np.zeros(n), np.zeros(n, bool), truncated, infos
+
+    def _finish_goal_step(self, render, truncated, infos):
+        """The rest of a step() with goals: score, reward and done bits on the device and, on a truncation step, the reset of the
+        finished envs into their next goal there (one launch); the host reads back only what it returns as host data."""
+        be, n = self._be, self.num_envs
+        sweep = bool(truncated.any())
+        be.episode_update(reset_done=sweep)
+        get = (lambda name: be.episode_buffer(name)) if self.device_obs else (lambda name: be.episode_buffer(name, host=True))
+        rewards = get('reward')
+        infos["goal_score"] = get('score')
+        if sweep:
+            # the device reset every env with a done bit: the truncated ones and any the step froze earlier
+            truncated = truncated | (be.episode_buffer('done', host=True) != 0)
+            fo = be.episode_buffer('final_obs', host=True)
+            k = be.n_objects
+            fin = np.full(n, None, dtype=object)
+            for i in np.flatnonzero(truncated):
+                fin[i] = {"joint_positions": fo[i, :9].copy(), "touch_sensors": fo[i, 9:13].copy()}
+                if self.additional_obs:
+                    fin[i]["object_positions"] = fo[i, 13:13 + 7 * k].reshape(k, 7).copy()
+            infos["final_obs"] = fin
+            infos["_final_obs"] = truncated.copy()
+            self._redraw(truncated, infos)
+            self._steps[truncated] = 0
+            if render:
+                be.render()
+        infos["goal_index"] = get('goal_index')
+        return self._obs(render), rewards, np.zeros(n, bool), truncated, infos
 
     def close(self, **kwargs):
         self._be.close()
