@@ -88,7 +88,7 @@ typedef struct rr_config {
                                [1, 1024], at most 255 raster tiles of 4096 pixels (1024 x 960 fits, 1024 x 961 does not): RR_EINVAL otherwise */
     int32_t device;         /* HIP device ordinal */
     int32_t solver_iters;   /* PGS iterations; <=0 -> 50        SURVEY A.1.2 */
-    int32_t envs_per_block; /* physics kernels: envs (threads) per workgroup; <=0 -> default */
+    int32_t envs_per_block; /* accepted and ignored: no launch shape depends on it (the field stays for the ABI); pass 0 */
     float dt;               /* <=0 -> 0.005                     env.py:203-204 */
     float erp;              /* <=0 -> 0.2 */
     float margin;           /* <=0 -> 0.02 */

@@ -3,11 +3,12 @@
 // One process per GPU; N independent envs per device.  State lives in HBM as SoA [field][env] fp32 so that a
 // wavefront whose lanes are consecutive envs reads/writes 256-byte contiguous lines.  A step is these kernels
 // (main stream unless noted; DESIGN.md 5 has the work-item maps and what bounds each of them):
-//   k_prep_a        1 thread / env : action protocol (env.py:314-321, 257-264; robot.py:188-201), forward kinematics,
-//                                    object terms (rotation, world inverse inertia, unconstrained velocities); launch order
-//                                    of k_collide (last step's heavy envs first)
-//   k_prep_b        1 thread / env : joint-space mass matrix (composite rigid bodies), bias (RNEA), Cholesky, M^-1,
+//   k_prep_a16      16 lanes / env : forward kinematics (the action protocol's out-of-bounds rule, env.py:257-264, decides
+//                                    which object pose counts), object terms (rotation, world inverse inertia, unconstrained
+//                                    velocities) on a second wave; launch order of k_collide (last step's heavy envs first)
+//   k_prep_b16      16 lanes / env : joint-space mass matrix (composite rigid bodies), bias (RNEA), Cholesky, M^-1,
 //                                    unconstrained joint velocities -- side stream, beside k_collide
+//   k_prep_ab16                      both in one launch: the look-ahead of the next step (rr_prep.inc)
 //   k_collide       4 wavefronts / env: bounding spheres -> close pairs, dealt out among the waves -> lane-per-vertex convex
 //                                    tests + edge-edge pass -> <= 4 points / pair, listed in pair order; warm-start matching
 //                                    against the previous step's list; classifies the env (light / heavy / very heavy)
@@ -402,7 +403,7 @@ __device__ void fk_all(const BodyParams &bp_, const float *q, m3 *bR, v3 *bp, v3
 // env << 8 | tile, or ~0 behind the last one.
 // Costs change little from frame to frame (5 ms of motion); an order that is off only loads the shader engines less evenly, the
 // images do not depend on it.
-// The collision pass uses the same sort with one item per env (ntiles = 1, extra workgroups of the k_prep_a / k_prep_ab launch in
+// The collision pass uses the same sort with one item per env (ntiles = 1, extra workgroups of the k_prep_a16 / k_prep_ab16 launch in
 // front of it, NT_ = 64): its workgroups last 14 us +- 20 % with a tail up to 70 us, and in env order a quarter of the slots stay empty.
 #define ORDER_BINS 1024
 template <int NT_>

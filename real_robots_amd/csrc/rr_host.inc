@@ -45,7 +45,7 @@ struct Blob {
 #define RUN_AHEAD_MAX 64
 struct Settings {
     int tile_w = 0;                // the tile width asked for (0: none); tile_layout ignores a width it cannot use
-    bool full_copy = false, split_heavy = true, lookahead = true, prep_scalar = false, collide_ordered = true, coop_all = true;
+    bool full_copy = false, split_heavy = true, lookahead = true, collide_ordered = true, coop_all = true;
     bool warmstart = true, edge_contacts = true, pair_cull = true, raster_order = true;
     int run_ahead = 8, split_max_pct = 60, ablate = 0, heavy2_min = 16, os_cap = OS_CAP;
     int force_hcount[2] = {-1, -1};
@@ -58,7 +58,6 @@ static Settings read_settings() {
     s.full_copy = getenv("RR_FULL_COPY") != nullptr;                          // the earlier image update: the static layer copied into every image before each frame (tests)
     s.split_heavy = getenv("RR_NO_SPLIT") == nullptr;                         // set: all envs solved and rendered on the main stream (A/B, tests)
     s.lookahead = getenv("RR_NO_LOOKAHEAD") == nullptr;                       // set: every step prepares itself in line (A/B, tests)
-    if ((v = getenv("RR_PREP_SCALAR"))) s.prep_scalar = atoi(v) != 0;         // 1: the thread-per-env preparation kernels instead of k_prep16 (A/B, tests)
     if ((v = getenv("RR_COLLIDE_ORDER"))) s.collide_ordered = atoi(v) != 0;   // 0: k_collide in env order instead of by falling duration of the last pass
     if ((v = getenv("RR_RUN_AHEAD"))) s.run_ahead = std::max(0, std::min(atoi(v), RUN_AHEAD_MAX));   // steps a caller that never waits may get ahead (default 8; 0: unbounded)
     if ((v = getenv("RR_COOP_ALL"))) s.coop_all = atoi(v) != 0;               // 0: the one-launch solve of a small batch four envs to a wave (A/B, tests)
@@ -82,7 +81,6 @@ struct ModelTables {
     SimParams P = {};
     RenderModel RM = {};
     IkModel IK = {};
-    int epb = 0;                   // envs per block for physics kernels
     int n_inst_used = 0;
     int n_shapes = 0;
     float table_pos[3] = {};       // target of the default eye camera (env.py:253-255)
@@ -127,7 +125,7 @@ struct rr_env : ModelTables {
     float4 *co_contacts = nullptr; float2 *co_force = nullptr; unsigned *co_partners = nullptr;   // lazily allocated, one block (rr_contact_observations)
     std::vector<void *> allocs;
     bool timing = false;
-    int *h_hcount = nullptr;       // pinned host copy of D.hcount[0] (device-mapped: written by k_prep_a of the following step)
+    int *h_hcount = nullptr;       // pinned host copy of D.hcount[0] (device-mapped: written by the first solve launch of every step, solve_body)
     bool images_valid = false;     // every env's image holds its previous frame (static layer + the pixels of its fragment list)
     unsigned char *stale_dev = nullptr;  // [N] device: the env's image predates the current static layer (rr_set_camera after its last frame)
     bool stale_any = false;        // some env may be stale: every render checks (cleared by a render of all envs)
@@ -136,7 +134,7 @@ struct rr_env : ModelTables {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_dyn = nullptr, ev_join2 = nullptr, ev_vsolved = nullptr, ev_hsolved = nullptr, ev_rast = nullptr;
     hipStream_t aux2 = nullptr;    // the very heavy envs' solve + render (Settings::heavy2_min)
     std::vector<hipStream_t> unused_streams;   // Settings::skip_queues: created only to take hardware queue ids
-    // Look-ahead (DESIGN.md 5.2): the state part of step t+1 (k_prep_ab, k_collide) runs on the side streams behind the render
+    // Look-ahead (DESIGN.md 5.2): the state part of step t+1 (k_prep_ab16, k_collide) runs on the side streams behind the render
     // of the heavy / very heavy envs of step t, beside the main stream's shading.
     struct Frame { float4 *clist; int *ccount; float *cwarm; int *hgflag, *hlist, *hcount, *hlist2, *hcount2; } fr[2] = {};
     int cur = 0;                   // fr[cur]: the frame of the last solved step (rr_get_contacts, contact history); fr[cur ^ 1]: the look-ahead's
@@ -397,7 +395,6 @@ static int parse_model(const rr_config &cfg, const Blob &b, const Settings &set,
     P.ablate = set.ablate; P.heavy2_min = set.heavy2_min; P.edge_contacts = set.edge_contacts ? 1 : 0; P.os_cap = set.os_cap;
     P.warmstart = set.warmstart ? upstream(cfg.warmstart, 0.85f) : 0.0f;
     P.lin_damp = upstream(cfg.lin_damping, 0.04f); P.ang_damp = upstream(cfg.ang_damping, 0.04f); P.rest_thresh = 0.2f;
-    M.epb = cfg.envs_per_block > 0 ? std::min(cfg.envs_per_block, 64) : 64;   // physics kernels are compiled with __launch_bounds__(64)
 
     // shapes + pair table (same order as the oracle's collide())
     ShapeData &S = M.S;
@@ -771,8 +768,6 @@ int rr_set_stream(rr_env *e, void *stream) {
     return RR_OK;
 }
 
-static inline dim3 env_grid(const rr_env *e) { return dim3((e->P.N + e->epb - 1) / e->epb); }
-
 int rr_reset(rr_env *e, const uint8_t *mask_host) {
     if (!e) return fail(RR_EINVAL, "null env");
     HIPCHK(hipSetDevice(e->cfg.device));
@@ -1064,23 +1059,19 @@ static int do_render(rr_env *e, bool use_flags) {
     return RR_OK;
 }
 
-// ---- look-ahead: the state part of the NEXT step (k_prep_a -> k_collide, k_prep_b beside them) ------------------------------
+// ---- look-ahead: the state part of the NEXT step (k_prep_a16 -> k_collide, k_prep_b16 beside them) --------------------------
 // Per-class launches (sel: pick_env) cover N work items whatever the class.
 #define COLLIDE_ORDER_MIN_N 1024   // up to this many envs all collision workgroups are resident at once: no order needed
 // (collision pass in cost order: the eight sorting workgroups ride on the preparation launch in front of it -- batches of more than
 // one round of collision workgroups, all envs; Settings::collide_ordered off: env order)
-static inline bool collide_in_order(const rr_env *e, int sel) { return sel == 0 && e->set.collide_ordered && e->epb == 64 && e->P.N > COLLIDE_ORDER_MIN_N; }
-static inline dim3 prep_grid(const rr_env *e, int sel) { return dim3(env_grid(e).x + (collide_in_order(e, sel) ? 8 : 0)); }
-static inline dim3 prep16_grid(const rr_env *e, int sel, bool order);
-static void launch_prep_a(rr_env *e, int sel, int zero_counts, hipStream_t st, hipEvent_t done = nullptr) {
-    if (e->set.prep_scalar) LAUNCH_EV(done, k_prep_a, prep_grid(e, sel), dim3(e->epb), 0, st, e->B, e->P, e->D, sel, zero_counts, collide_in_order(e, sel) ? e->P.N : 0);
-    else LAUNCH_EV(done, k_prep_a16, prep16_grid(e, sel, true), dim3(128), 0, st, e->B, e->P, e->D, sel, zero_counts, collide_in_order(e, sel) ? e->P.N : 0);
-}
-// (k_prep16: one env per 16-lane group, four envs per 64-thread workgroup; Settings::prep_scalar: the thread-per-env kernels)
+static inline bool collide_in_order(const rr_env *e, int sel) { return sel == 0 && e->set.collide_ordered && e->P.N > COLLIDE_ORDER_MIN_N; }
+// (k_prep16: one env per 16-lane group, four envs per workgroup -- of 128 threads where the objects' wave rides along)
 static inline dim3 prep16_grid(const rr_env *e, int sel, bool order) { return dim3((e->P.N + P16_ENVS - 1) / P16_ENVS + (order && collide_in_order(e, sel) ? 8 : 0)); }
+static void launch_prep_a(rr_env *e, int sel, int zero_counts, hipStream_t st, hipEvent_t done = nullptr) {
+    LAUNCH_EV(done, k_prep_a16, prep16_grid(e, sel, true), dim3(128), 0, st, e->B, e->P, e->D, sel, zero_counts, collide_in_order(e, sel) ? e->P.N : 0);
+}
 static void launch_prep_b(rr_env *e, int sel, hipStream_t st, hipEvent_t done = nullptr) {
-    if (e->set.prep_scalar) LAUNCH_EV(done, k_prep_b, env_grid(e), dim3(e->epb), 0, st, e->B, e->P, e->D, sel);
-    else LAUNCH_EV(done, k_prep_b16, prep16_grid(e, sel, false), dim3(64), 0, st, e->B, e->P, e->D, sel);
+    LAUNCH_EV(done, k_prep_b16, prep16_grid(e, sel, false), dim3(64), 0, st, e->B, e->P, e->D, sel);
 }
 static void launch_collide(rr_env *e, int sel, hipStream_t st, hipEvent_t done = nullptr) {
     const bool ordered = collide_in_order(e, sel);
@@ -1088,12 +1079,7 @@ static void launch_collide(rr_env *e, int sel, hipStream_t st, hipEvent_t done =
     LAUNCH_EV(done, k_collide, grid, dim3(COLLIDE_THREADS), 0, st, e->P, e->D, e->n_shapes, sel, ordered ? 1 : 0);
 }
 static void launch_prep_ab(rr_env *e, int sel, hipStream_t st) {
-    if (e->set.prep_scalar) hipLaunchKernelGGL(k_prep_ab, prep_grid(e, sel), dim3(e->epb), 0, st, e->B, e->P, e->D, sel, collide_in_order(e, sel) ? e->P.N : 0);
-    else hipLaunchKernelGGL(k_prep_ab16, prep16_grid(e, sel, true), dim3(128), 0, st, e->B, e->P, e->D, sel, collide_in_order(e, sel) ? e->P.N : 0);
-}
-static void launch_prep_serial(rr_env *e, int sel, int zero_counts) {
-    launch_prep_a(e, sel, zero_counts, e->stream);
-    launch_prep_b(e, sel, e->stream);
+    hipLaunchKernelGGL(k_prep_ab16, prep16_grid(e, sel, true), dim3(128), 0, st, e->B, e->P, e->D, sel, collide_in_order(e, sel) ? e->P.N : 0);
 }
 
 // The solve of the heavy (sel 2) / very heavy (sel 3) envs on `st`, in the form the plan picked (StepPlan::coop_*): one env per
@@ -1112,7 +1098,7 @@ static void launch_solve_class(rr_env *e, const StepPlan &pl, int sel, hipStream
     else LAUNCH_EV(done, k_solve, dim3((ngroups + 3) / 4), dim3(256), 4 * lds64, st, e->B, e->P, e->D, sel, 0);
 }
 
-// The state part of a step for all envs on the main stream (k_prep_b beside k_collide on the side stream when `overlap`): at
+// The state part of a step for all envs on the main stream (k_prep_b16 beside k_collide on the side stream when `overlap`): at
 // the start of a step whose look-ahead is missing or stale, or at the end of a step that has a single class.
 static void state_part_all(rr_env *e, bool overlap) {
     if (overlap) {
@@ -1122,7 +1108,7 @@ static void state_part_all(rr_env *e, bool overlap) {
         launch_collide(e, 0, e->stream);
         HIPQ(hipStreamWaitEvent(e->stream, e->ev_dyn, 0));
     } else {
-        TIMED(0, launch_prep_serial(e, 0, 1));
+        TIMED(0, { launch_prep_a(e, 0, 1, e->stream); launch_prep_b(e, 0, e->stream); });
         TIMED(1, launch_collide(e, 0, e->stream));
     }
 }
@@ -1185,15 +1171,9 @@ static int step_split(rr_env *e, const StepPlan &pl, const DevPtrs &D, int resto
         launch_render(e, pl, D, restore, 3, e->aux, true, join_ev);
     } else if (!pl.la_on_vh) launch_render(e, pl, D, restore, 3, e->aux2, true);
     launch_light_solve(e, e->RM_dev, e->stream, ahead ? e->ev_dyn : nullptr);
-    if (pl.la_on_vh && !pl.la_after_raster) {
-        HIPQ(hipStreamWaitEvent(e->aux2, e->ev_dyn, 0));
-        HIPQ(hipStreamWaitEvent(e->aux2, e->ev_hsolved, 0));
-        launch_prep_ab(e, 0, e->aux2);
-        launch_collide(e, 0, e->aux2, e->ev_join2);
-    } else if (pl.la_side) {
+    if (pl.la_side) {
         // the heavy stream is done with its envs' render long before the very heavy envs' is: the kinematics half of the preparation
-        // (69 VGPRs: it gets onto the machine beside the renders) and the collision pass go there once every solve is done, the
-        // dynamics half (a whole SIMD per wave) behind the very heavy envs' render
+        // and the collision pass go there once every solve is done, the dynamics half behind the very heavy envs' render
         HIPQ(hipStreamWaitEvent(e->aux, e->ev_dyn, 0));
         HIPQ(hipStreamWaitEvent(e->aux, e->ev_vsolved, 0));
         launch_prep_a(e, 0, 0, e->aux);
@@ -1202,7 +1182,7 @@ static int step_split(rr_env *e, const StepPlan &pl, const DevPtrs &D, int resto
         HIPQ(hipStreamWaitEvent(e->aux2, e->ev_hsolved, 0));
         launch_prep_b(e, 0, e->aux2, e->ev_join2);
     }
-    if (pl.la_after_raster) {
+    if (pl.la_on_vh) {
         const ImageOut io = env_images(e);
         launch_raster(e, D, restore, 1, e->stream);
         HIPQ(hipEventRecord(e->ev_rast, e->stream));
@@ -1309,7 +1289,7 @@ int rr_step(rr_env *e, const float *joint_cmd, int32_t cmd_on_device, int32_t re
     // ---- the plan of this step: the one reading of the lagged list lengths (behind the run-ahead wait: as fresh as it gets)
     PlanIn in;
     in.N = N; in.ntiles = e->RM.ntiles; in.render_mode = render_mode; in.timing = e->timing;
-    in.split_heavy = e->set.split_heavy; in.lookahead = e->set.lookahead; in.prep_scalar = e->set.prep_scalar; in.coop_all = e->set.coop_all;
+    in.split_heavy = e->set.split_heavy; in.lookahead = e->set.lookahead; in.coop_all = e->set.coop_all;
     in.split_max_pct = e->set.split_max_pct;
     in.counts = lagged_counts(e);
     const StepPlan pl = plan_step(in);

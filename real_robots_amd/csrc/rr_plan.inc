@@ -42,7 +42,7 @@ struct PlanCounts { int h, vh; bool known; };
 struct PlanIn {
     int N, ntiles, render_mode;     // envs, raster tiles per env, rr_step's render_mode (0: a step without camera)
     bool timing;                    // the timing leg: everything on the main stream under its timers
-    bool split_heavy, lookahead, prep_scalar, coop_all; int split_max_pct;     // Settings
+    bool split_heavy, lookahead, coop_all; int split_max_pct;     // Settings
     PlanCounts counts;
 };
 
@@ -57,9 +57,8 @@ struct StepPlan {
     bool coop_h;                    // heavy solve one env per wave (else four to a wave)
     bool coop_vh_beside, coop_vh_alone;    // the same for the very heavy solve, beside a visibility pass / in a step without camera
     // PATH_SPLIT only
-    bool la_on_vh, la_side;         // look-ahead behind the very heavy envs' solve (placement 1) / split over the two side streams (2)
+    bool la_on_vh, la_side;         // look-ahead behind the very heavy envs' solve (placement 1), held behind the light envs' visibility pass by an event / split over the two side streams (2)
     bool vh_render_on_main, vh_render_on_aux;      // the very heavy envs' render at the main stream's tail (1') / behind the heavy envs' (1); neither: on their own stream (2, no look-ahead)
-    bool la_after_raster;           // the look-ahead is held behind the light envs' visibility pass by an event
     // PATH_SINGLE only
     bool small_n;                   // placement 4
     SingleSolve single_solve;       // ONE env class by class | 3b | one launch, a wave per env | one launch, four envs to a wave
@@ -108,10 +107,10 @@ static inline StepPlan plan_step(const PlanIn &in) {
     p.la_side = ahead && !p.la_on_vh;
     p.vh_render_on_main = p.la_on_vh && p.h_long;
     p.vh_render_on_aux = p.la_on_vh && !p.vh_render_on_main;
-    // (the thread-per-env k_prep_ab needed a whole free SIMD for each of its 64 waves and sat in its queue until the visibility
-    // pass' grid was exhausted -- which kept the collision pass, 39 KB of LDS per workgroup, out of the visibility pass' way;
-    // k_prep_ab16 gets onto the machine at once, so the look-ahead is HELD behind the light envs' visibility pass by an event)
-    p.la_after_raster = p.la_on_vh && !in.prep_scalar;
+    // (placement 1's look-ahead is HELD behind the light envs' visibility pass by an event, step_split: k_prep_ab16 -- 128-thread
+    // workgroups of <= 128 VGPRs -- gets onto the machine at once, and the collision pass behind it, 39 KB of LDS per workgroup,
+    // would then run beside the visibility pass and crowd it out.  A preparation whose waves each needed a whole free SIMD, rounds
+    // 1-5, sat in its queue until the visibility pass' grid was exhausted and kept the collision pass out of its way unasked.)
 
     p.small_n = N <= SMALL_N_MAX && in.split_heavy && !in.timing;
     // Placement 3b: a step without camera whose very heavy list is long (macro actions without the retina: 368 of 4 096 envs).  In the

@@ -16,11 +16,12 @@ __device__ __forceinline__ bool object_out_of_bounds(float x, float z, float tab
 
 // Object terms of object i of `env` -- rotation, world inverse inertia, unconstrained velocities -- of the pose that counts: an object
 // the out-of-bounds rule (env.py:257-264) sends home is taken at its home pose, at rest (the solve kernel writes that pose into the
-// state when the step starts).  One function for every form of the preparation (a thread per env, sixteen lanes per env): the same
+// state when the step starts).  One function for every kernel of the preparation (k_prep_a16 in line, k_prep_ab16 ahead): the same
 // expressions, hence the same bits.
 // (the object's principal inertias: the env's own, D.obj_dyn -- rr_set_object_dynamics)
-// Contraction-free: the two callers (a loop over the objects on one thread; one object per lane) otherwise get different fused
-// multiply-adds out of the same source -- a loop-invariant product hoisted here, fused there -- and the forms of a step must agree bit for bit.
+// Contraction-free: which products the compiler fuses into multiply-adds depends on the code it is inlined into -- a loop-invariant
+// product hoisted in one caller, fused in another -- and the forms of a step must agree bit for bit.  The bits themselves are
+// recorded: tests/golden/prep_thread_per_env.npz holds them as a loop over the objects on one thread computed them.
 #pragma clang fp contract(off)
 __device__ __forceinline__ void object_terms(const BodyParams &B, const SimParams &P, const DevPtrs &D, int env, int i, bool store = true) {
     const int N = P.N;
@@ -57,6 +58,7 @@ __device__ __forceinline__ void object_terms(const BodyParams &B, const SimParam
 }
 #pragma clang fp contract(fast)
 
+// ---------------------------------------------------------------------------------------------- k_prep16: sixteen lanes per env
 // The state part of the preparation -- everything of a step that does NOT need the action, i.e. a function of the state the
 // previous step left: PHASE 1 = forward kinematics and object terms (rotation, world inverse inertia, unconstrained
 // velocities; the out-of-bounds rule decides which object pose counts) -- all the collision kernel needs -- and PHASE 2 =
@@ -65,207 +67,14 @@ __device__ __forceinline__ void object_terms(const BodyParams &B, const SimParam
 // class by class (sel, pick_env), under the render of step t; only when the state was changed from outside in between
 // (reset, set_state, teleports) do they run in line at the start of the step.  (When the kernels are timed one by one the
 // two phases run back to back and are reported together as "k_prep".)
-template <int PHASE>
-__device__ __forceinline__ void prep_body(const BodyParams &B, const SimParams &P, const DevPtrs &D, int env) {
-    const int N = P.N;
-    const float *state = D.state;
-    float *scratch = D.scratch;
-    if (D.errflags[env] & 1u) return;   // frozen env
-    float q[NB], qd[NB];
-#pragma unroll
-    for (int i = 0; i < NB; i++) { q[i] = STT(ST_Q + i); qd[i] = STT(ST_QD + i); }
-    if (PHASE == 1) {
-        // ---- kinematics only, streamed: a body's frame goes to the scratch record as soon as it exists and only the frame at hand
-        // and the one the chain forks from are kept (fk_all's operations in fk_all's order: same bits).  The kernel then needs a
-        // third of the registers (69 instead of 194 VGPRs).
-        m3 Rc = {{1, 0, 0, 0, 1, 0, 0, 0, 1}}, Rf = Rc;
-        v3 pc = mk(B.robot_pos[0], B.robot_pos[1], B.robot_pos[2]), pf = pc;
-        constexpr int FORK = 6;                    // PARENT: a chain 0..8 with the second finger pair 9, 10 hanging off body 6
-        static_assert(PARENT[9] == FORK && PARENT[10] == 9 && PARENT[8] == 7 && PARENT[7] == 6, "streamed forward kinematics");
-#pragma unroll
-        for (int b = 0; b < NB; b++) {
-            if (b == 9) { Rc = Rf; pc = pf; }      // (bodies 0..8: the parent is the previous body; 9: body 6; 10: body 9)
-            m3 jr;
-#pragma unroll
-            for (int k = 0; k < 9; k++) jr.m[k] = B.jrot[b][k];
-            const m3 Rj = nc::mul(Rc, jr);
-            const v3 ax = mk(B.axis[b][0], B.axis[b][1], B.axis[b][2]);
-            const v3 pb = nc::add(pc, nc::mulv(Rc, mk(B.jpos[b][0], B.jpos[b][1], B.jpos[b][2])));
-            const m3 Rb = nc::mul(Rj, nc::axis_angle(ax, q[b]));
-            const v3 axw = nc::mulv(Rj, ax);
-#pragma unroll
-            for (int k = 0; k < 9; k++) SCR(S_BR + 9 * b + k) = Rb.m[k];
-            SCR(S_BP + 3 * b) = pb.x; SCR(S_BP + 3 * b + 1) = pb.y; SCR(S_BP + 3 * b + 2) = pb.z;
-            SCR(S_BAX + 3 * b) = axw.x; SCR(S_BAX + 3 * b + 1) = axw.y; SCR(S_BAX + 3 * b + 2) = axw.z;
-            Rc = Rb; pc = pb;
-            if (b == FORK) { Rf = Rb; pf = pb; }
-        }
-    }
-    // ---- kinematics
-    m3 bR[NB]; v3 bp[NB], bax[NB], bcom[NB]; m3 bI[NB];
-    if (PHASE != 1) fk_all(B, q, bR, bp, bax);
-#pragma unroll
-    for (int b = 0; b < (PHASE == 1 ? 0 : NB); b++) {
-        bcom[b] = bp[b] + mulv(bR[b], mk(B.com[b][0], B.com[b][1], B.com[b][2]));
-        bI[b] = inertia_world(bR[b], B.inertia[b]);
-        if (PHASE != 2) {
-#pragma unroll
-            for (int k = 0; k < 9; k++) SCR(S_BR + 9 * b + k) = bR[b].m[k];
-            SCR(S_BP + 3 * b) = bp[b].x; SCR(S_BP + 3 * b + 1) = bp[b].y; SCR(S_BP + 3 * b + 2) = bp[b].z;
-            SCR(S_BAX + 3 * b) = bax[b].x; SCR(S_BAX + 3 * b + 1) = bax[b].y; SCR(S_BAX + 3 * b + 2) = bax[b].z;
-        }
-    }
-    if (PHASE != 1) {
-    // ---- composite rigid body mass matrix
-    float cm[NB]; v3 cc[NB]; m3 cI[NB];
-#pragma unroll
-    for (int b = 0; b < NB; b++) { cm[b] = B.mass[b]; cc[b] = bcom[b]; cI[b] = bI[b]; }
-#pragma unroll
-    for (int b = NB - 1; b >= 1; b--) {
-        const int p = PARENT[b];
-        float mt = cm[p] + cm[b];
-        v3 c = (cc[p] * cm[p] + cc[b] * cm[b]) * (1.0f / mt);
-        v3 d1 = cc[p] - c, d2 = cc[b] - c;
-        float s1 = dot(d1, d1), s2 = dot(d2, d2);
-        float d1a[3] = {d1.x, d1.y, d1.z}, d2a[3] = {d2.x, d2.y, d2.z};
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                float e = (i == j) ? 1.0f : 0.0f;
-                cI[p].m[3 * i + j] = cI[p].m[3 * i + j] + cI[b].m[3 * i + j] + cm[p] * (s1 * e - d1a[i] * d1a[j]) + cm[b] * (s2 * e - d2a[i] * d2a[j]);
-            }
-        cm[p] = mt;
-        cc[p] = c;
-    }
-    float M[NB][NB];
-#pragma unroll
-    for (int i = 0; i < NB; i++)
-#pragma unroll
-        for (int j = 0; j < NB; j++) M[i][j] = 0;
-#pragma unroll
-    for (int j = 0; j < NB; j++) {
-        v3 Ia = mulv(cI[j], bax[j]);
-        v3 f = cross(bax[j], cc[j] - bp[j]) * cm[j];
-#pragma unroll
-        for (int i = j; i >= 0; i--) {
-            // ancestors-or-self of j: chain 0..6 is linear; fingers branch at body 6
-            bool anc = (i == j) || (i <= 6 && j <= 6) || (i <= 6 && j >= 7) || (i == 7 && j == 8) || (i == 9 && j == 10);
-            if (!anc) continue;
-            v3 nn = Ia + cross(cc[j] - bp[i], f);
-            float v = dot(bax[i], nn);
-            M[i][j] = v; M[j][i] = v;
-        }
-    }
-    // ---- RNEA bias (qdd = 0, base acceleration +g)
-    v3 w[NB], al[NB], ap[NB], F[NB], Nn[NB];
-#pragma unroll
-    for (int b = 0; b < NB; b++) {
-        const int p = PARENT[b];
-        v3 wp = mk(0, 0, 0), alp = mk(0, 0, 0), app = mk(0, 0, P.gravity), pp = mk(B.robot_pos[0], B.robot_pos[1], B.robot_pos[2]);
-        if (p >= 0) { wp = w[p >= 0 ? p : 0]; alp = al[p >= 0 ? p : 0]; app = ap[p >= 0 ? p : 0]; pp = bp[p >= 0 ? p : 0]; }
-        w[b] = wp + bax[b] * qd[b];
-        al[b] = alp + cross(wp, bax[b]) * qd[b];
-        v3 d = bp[b] - pp;
-        ap[b] = app + cross(alp, d) + cross(wp, cross(wp, d));
-        v3 r = bcom[b] - bp[b];
-        v3 ac = ap[b] + cross(al[b], r) + cross(w[b], cross(w[b], r));
-        F[b] = ac * B.mass[b];
-        Nn[b] = mulv(bI[b], al[b]) + cross(w[b], mulv(bI[b], w[b])) + cross(r, F[b]);
-    }
-    float bias[NB];
-#pragma unroll
-    for (int b = NB - 1; b >= 0; b--) {
-        bias[b] = dot(bax[b], Nn[b]);
-        const int p = PARENT[b];
-        if (p >= 0) {
-            const int pi = p >= 0 ? p : 0;
-            Nn[pi] = Nn[pi] + Nn[b] + cross(bp[b] - bp[pi], F[b]);
-            F[pi] = F[pi] + F[b];
-        }
-    }
-    // ---- Cholesky + inverse
-    // (divisions by the diagonal are multiplications by its reciprocal: 11 IEEE divisions instead of ~300)
-    float L[NB][NB], iL[NB];
-#pragma unroll
-    for (int i = 0; i < NB; i++) {
-#pragma unroll
-        for (int j = 0; j <= i; j++) {
-            float s = M[i][j];
-#pragma unroll
-            for (int k = 0; k < j; k++) s -= L[i][k] * L[j][k];
-            if (i == j) { L[i][i] = sqrtf(s); iL[i] = 1.0f / L[i][i]; }
-            else L[i][j] = s * iL[j];
-        }
-    }
-    float rhs[NB], qdd[NB];
-#pragma unroll
-    for (int i = 0; i < NB; i++) { rhs[i] = -bias[i] - D.env_act[(size_t)(3 * NB + i) * N + env] * qd[i]; qdd[i] = 0; }      // (the env's own joint damping: rr_set_env_actuators)
-#pragma unroll
-    for (int c = 0; c < NB; c++) {
-        float y[NB], xcol[NB];
-#pragma unroll
-        for (int i = 0; i < NB; i++) {
-            float s = (i == c) ? 1.0f : 0.0f;
-#pragma unroll
-            for (int k = 0; k < i; k++) s -= L[i][k] * y[k];
-            y[i] = s * iL[i];
-        }
-#pragma unroll
-        for (int i = NB - 1; i >= 0; i--) {
-            float s = y[i];
-#pragma unroll
-            for (int k = i + 1; k < NB; k++) s -= L[k][i] * xcol[k];
-            xcol[i] = s * iL[i];
-        }
-#pragma unroll
-        for (int i = 0; i < NB; i++) {
-            SCR(S_MINV + i * NB + c) = xcol[i];
-            qdd[i] += xcol[i] * rhs[c];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < NB; i++) SCR(S_QDS + i) = qd[i] + P.dt * qdd[i];
-    }
-    if (PHASE == 2) return;
-    // ---- objects: rotation, inverse inertia, unconstrained velocities -- of the pose that counts: an object the out-of-bounds
-    // rule (env.py:257-264) sends home is taken at its home pose, at rest (the solve kernel writes that pose into the state when the step starts)
-    for (int i = 0; i < P.nobj; i++) object_terms(B, P, D, env, i);
-}
-// One thread per env of the class `sel` (pick_env); the launches cover N work items whatever the class (a heavy list's length
-// is known on the device only; work items past its end exit at once).
-// order_n > 0: the launch has eight more workgroups (64 threads each) behind those of the envs; they make the dispatch order of the
-// collision pass that follows this launch on its stream from the durations the last one has left (dispatch_order_class, k_collide).
-template <int PHASE>
-__device__ __forceinline__ void prep_class(const BodyParams &B, const SimParams &P, const DevPtrs &D, int sel, int order_n) {
-    if (order_n > 0 && (int)blockIdx.x >= (int)gridDim.x - 8) {
-        dispatch_order_class<64>((int)blockIdx.x - ((int)gridDim.x - 8), order_n, 1, (order_n + 7) >> 3, D.collide_cost, D.collide_bin, D.collide_perm);
-        return;
-    }
-    const int env = pick_env(D, sel, blockIdx.x * blockDim.x + threadIdx.x, P.N);
-    if (env < 0) return;
-    prep_body<PHASE>(B, P, D, env);
-}
-__global__ void __launch_bounds__(64) k_prep_a(BodyParams B, SimParams P, DevPtrs D, int sel, int zero_counts, int order_n) {
-    if (zero_counts && blockIdx.x == 0 && threadIdx.x == 0) {       // in-line pass: the frame k_collide is about to fill holds stale counts
-        D.hcount_next[0] = 0; D.hcount_next[1] = 0; D.hcount2_next[0] = 0; D.hcount2_next[1] = 0;
-    }
-    prep_class<1>(B, P, D, sel, order_n);
-}
-__global__ void __launch_bounds__(64) k_prep_b(BodyParams B, SimParams P, DevPtrs D, int sel) { prep_class<2>(B, P, D, sel, 0); }
-// both phases in one launch (the look-ahead behind a class' solve: one kernel instead of two on that stream)
-__global__ void __launch_bounds__(64) k_prep_ab(BodyParams B, SimParams P, DevPtrs D, int sel, int order_n) { prep_class<0>(B, P, D, sel, order_n); }
-
-// ---------------------------------------------------------------------------------------------- k_prep16: sixteen lanes per env
-// The same preparation with one env per 16-lane group (four envs per wave) instead of one env per thread: the joint-space dynamics
-// of an env are ~7 000 operations, and one thread walking them at a lone wave's issue rate was the tail of every step (0.030 ms
-// alone, 0.080 ms under overlap -- each of its 64 waves wanted a whole SIMD at 194 VGPRs) and a third of the chain of one env
-// (BASELINE configs 1 and 2).  Here the work is spread the way north_star asks for -- the chain of frames and the per-body records
-// through LDS, per-body reductions through DPP:
+// One env per 16-lane group, four envs per wave: the joint-space dynamics of an env are ~7 000 operations, and ONE thread walking
+// them at a lone wave's issue rate (rounds 1-5) was the tail of every step (0.030 ms alone, 0.080 ms under overlap -- each of its
+// 64 waves wanted a whole SIMD at 194 VGPRs) and a third of the chain of one env (BASELINE configs 1 and 2).  Here the work is
+// spread the way north_star asks for -- the chain of frames and the per-body records through LDS, per-body reductions through DPP:
 //   * forward kinematics: lanes 0..2 walk the chain, lane r holding ROW r of the frame at hand (lanes 3..5 take the second finger
 //     pair, bodies 9 and 10, from body 6 on); the joints' local rotations are computed by the lanes of their bodies and read back
-//     from LDS.  Every output is fk_all's operations in fk_all's order, contraction-free: the same bits as fk_all and k_prep_a's
-//     streamed form (the collision pass compares its decisions bit for bit with the oracle);
+//     from LDS.  Every output is fk_all's operations in fk_all's order, contraction-free: the same bits as fk_all (the collision
+//     pass compares its decisions bit for bit with the oracle);
 //   * everything per body -- centre of mass, world inertia, the body's own RNEA terms, its column of the mass matrix, its row of
 //     the Cholesky factor, its column of M^-1 -- on the lane of that body (lanes 0..10);
 //   * the velocity recursion of RNEA: every body lane walks ITS OWN root path in lock step (level k = body k up to the fork at
@@ -273,12 +82,13 @@ __global__ void __launch_bounds__(64) k_prep_ab(BodyParams B, SimParams P, DevPt
 //   * RNEA's force pass as subtree sums: every body's force and its torque about the wrist (body 6's joint), summed leaf to root
 //     with one masked DPP multiply-add per value and tree edge, then referred back to the body's own joint;
 //   * the composite bodies: nine lanes hold one entry of the 3 x 3 inertia each, the merges run leaf to root;
-//   * the objects: a second wave of the workgroup, lane (env, object), the very function the thread-per-env form calls (object_terms).
-// ~2 700 issue slots instead of ~9 000 (ISA counts), 128-thread workgroups of <= 128 VGPRs that fit beside the render's.  The dynamics
-// are contractable fp32 as before, with v_rcp / v_rsq (1 ulp) for the composite masses and the Cholesky diagonal: NOT bit for bit the
-// thread-per-env kernel's, equal to it to rounding -- tests/test_gpu_round6.py compares M^-1 and the unconstrained velocities of the
-// two forms at 4096 envs; every form of a step uses this one kernel family, so the placements of a step stay bitwise equal.
-// RR_PREP_SCALAR=1: the thread-per-env kernels (A/B, tests).
+//   * the objects: a second wave of the workgroup, lane (env, object), each through object_terms.
+// ~2 700 issue slots where the one-thread walk took ~9 000 (ISA counts), 128-thread workgroups of <= 128 VGPRs that fit beside the
+// render's.  The dynamics are contractable fp32, with v_rcp / v_rsq (1 ulp) for the composite masses and the Cholesky diagonal: NOT
+// bit for bit a plain IEEE evaluation's, equal to it to rounding -- tests/test_gpu_round6.py compares frames and object terms bit
+// for bit, M^-1 and the unconstrained velocities to rounding, with a record of the one-thread kernels (tests/golden/
+// prep_thread_per_env.npz), tests/test_gpu_numpy_step.py every field with a float64 numpy preparation; every form of a step uses
+// this one kernel family, so the placements of a step stay bitwise equal.
 #define P16_ENVS 4
 // LDS record of an env: frames R [11][9]; per-body record BQ [11][8] = {axis xyz, joint velocity, position xyz, -}; local joint
 // rotations RAA [11][12]; composite bodies CI [11][9] and CC [11][4] = {centre xyz, mass}; M^-1 rows X [11][12]
@@ -434,7 +244,7 @@ __device__ __forceinline__ void prep16_body(const BodyParams &B, const SimParams
         const int e9 = l < 9 ? l : 0, ei = e9 / 3, ej = e9 % 3;
         auto node = [&](int b) { const float4 c = *(const float4 *)&lds[PL_CC + 4 * b]; P16Comp n; n.m = c.w; n.c = mk(c.x, c.y, c.z); n.I = lds[PL_CI + 9 * b + e9]; return n; };
         auto put = [&](int b, const P16Comp &n) { if (l < 9) lds[PL_CI + 9 * b + e9] = n.I; if (l == 0) *(float4 *)&lds[PL_CC + 4 * b] = make_float4(n.c.x, n.c.y, n.c.z, n.m); };
-        // (the order of the thread-per-env loop b = 10 .. 1: 10 -> 9, 9 -> 6, 8 -> 7, 7 -> 6, 6 -> 5, ... 1 -> 0)
+        // (every child into its parent, in the order of a loop b = 10 .. 1 over PARENT: 10 -> 9, 9 -> 6, 8 -> 7, 7 -> 6, 6 -> 5, ... 1 -> 0)
         const P16Comp n9 = p16_merge(node(9), node(10), ei, ej);
         P16Comp n6 = p16_merge(node(6), n9, ei, ej);
         const P16Comp n7 = p16_merge(node(7), node(8), ei, ej);

@@ -3,7 +3,6 @@ cd $GRAFT_REPO_ROOT
 bash tools/profile_round.sh r06 > gpurun_out/round_log.txt 2>&1
 O=gpurun_out/round
 cp $O/traffic_latest.json $O/sq_latest.json profiles/
-bash scratch/prof_prep.sh > gpurun_out/round/r06_prep_forms.txt 2>&1
 python scratch/timeline.py gpurun_out/round/stats 30 > gpurun_out/round/r06_timeline.txt 2>&1
 python bench.py --full --steps 200 --warmup 20 > $O/r06_bench.json 2> $O/bench2.err
 tail -c 300 gpurun_out/round/r06_bench.json

@@ -349,13 +349,13 @@ def per_joint_rows():
     return rows
 
 
-@pytest.mark.parametrize('prep', ['scalar', 'p16'])
+@pytest.mark.parametrize('prep', ['p16'])
 def test_per_joint_rows_against_the_numpy_helper(monkeypatch, prep):
     """One step with rows that differ between the joints, from states with and without robot contacts: device vs
     tests/numpy_actuators.step fed with the device's contact list, at the bounds tests/test_gpu_numpy_step.py applies to the same
     comparison with scalar parameters (state_bounds, force_bound; over a flat bound: SENS_FACTOR x the helper's own spread under
     one-ulp perturbations of its float32 inputs, as there); and RR_F_PREP's unconstrained joint velocities against the helper's
-    qd* under the per-joint damping at that file's ceiling for qd*, on both preparation forms."""
+    qd* under the per-joint damping at that file's ceiling for qd*, on the in-line preparation."""
     from tests import numpy_actuators as na
     from tests import numpy_step as ns
     from tests.test_gpu_contacts_fuzz import SENS_RUNS

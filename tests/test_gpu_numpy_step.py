@@ -23,7 +23,7 @@ from tests.test_gpu_round6 import (_make, _rich_states, S_BR, S_BP, S_BAX, S_MIN
 
 pytestmark = pytest.mark.gpu
 
-PREP_PATHS = {'scalar': {'RR_PREP_SCALAR': '1', 'RR_NO_LOOKAHEAD': '1'}, 'p16': {'RR_NO_LOOKAHEAD': '1'}, 'lookahead': {}}
+PREP_PATHS = {'p16': {'RR_NO_LOOKAHEAD': '1'}, 'lookahead': {}}
 
 
 def random_dynamics(n, seed, nobj=3):
@@ -115,8 +115,8 @@ PREP_CASES = [pytest.param(3, N, id=str(N)) for N in (1, 5, 17, 4096)] + \
 
 @pytest.mark.parametrize('objects,N', PREP_CASES)
 def test_prep_record_matches_the_numpy_preparation(monkeypatch, objects, N):
-    """RR_F_PREP field by field against numpy under the three preparation paths: the thread-per-env kernels, the 16-lane kernel,
-    and the look-ahead (the record then describes the state the step left).  Ceilings from float32 arithmetic, not measured.
+    """RR_F_PREP field by field against numpy under the two preparation paths: the in-line kernels (k_prep_a16 + k_prep_b16)
+    and the look-ahead (k_prep_ab16; the record then describes the state the step left).  Ceilings from float32 arithmetic, not measured.
     With one or two objects (P.nobj < 3: the object lanes' guards, the object stride of the per-env rows) only the objects present
     are compared."""
     st = edge_states(N, 3)
@@ -173,7 +173,7 @@ def force_bound(fmax):
 
 SKIN_SWAP = ('skin_00', 'skin_10', 'skin_01', 'skin_11')            # a negative control: sensors 1 and 2 exchanged
 SOLVERS = {'second': SECOND, 'third': THIRD, 'cpu_solver': CPU_VARIANTS['solver'][1]}
-# (objects, path or solver set, N): the five original cases keep their ids
+# (objects, path or solver set, N): the original cases keep their ids
 CONTACT_CASES = [pytest.param(3, p, 96, id=p) for p in list(PATHS) + ['iters1']] + [
     pytest.param(1, 'default', 96, id='objects1'), pytest.param(2, 'default', 96, id='objects2'),
     pytest.param(3, 'second', 96, id='second'), pytest.param(3, 'third', 96, id='third'),
@@ -192,7 +192,7 @@ def test_contact_step_matches_the_numpy_step(monkeypatch, objects, path, N):
     Per checked env: the state, the normal forces (rr_get_contacts column 10) against numpy's lambda_n / dt, the touch sensors
     against the reference's rule (robot.py:131-163) on numpy's forces -- and exactly on the device's own; the absent objects'
     state slots unchanged bit for bit; the observation fields (robot.py:203-211) equal to the state bit for bit.
-    Cases: the five placements / one sweep at N = 96 with three objects, one and two objects, the solver parameter sets of
+    Cases: the four placements / one sweep at N = 96 with three objects, one and two objects, the solver parameter sets of
     tests/test_gpu_solver_params.py and tests/test_numpy_step.py, a partial 16-env light workgroup (N = 17), the headline
     batch (N = 4096, default placement)."""
     t_start = time.time()
@@ -298,7 +298,7 @@ def test_contact_step_matches_the_numpy_step(monkeypatch, objects, path, N):
           % (k, path, N, checked, sorted(seen_cls), worst['joints'], worst['pose'], worst['velocity'], worst['force'], worst['touch'],
              escapes, SENS_FACTOR, touch_loaded, sorted(pairs), limit_active, len(diverged)))
     assert seen_cls == occurred and len(occurred) >= 2, (seen_cls, occurred)
-    if path in ('default', 'scalar_prep', 'no_split') and original:
+    if path in ('default', 'no_split') and original:
         assert occurred == {0, 1, 2}
     assert {('robot', 'object'), ('object', 'static')} <= pairs, pairs
     if path != 'iters1' and k >= 2:    # (one sweep per step drives another trajectory: no pile at these steps)

@@ -124,8 +124,7 @@ def _compare(mixed, uniform, envs, with_contacts):
             assert cm.shape == cu.shape and np.array_equal(cm.view(np.uint32), cu.view(np.uint32)), "contacts of env %d differ" % i
 
 
-PATHS = {'default': {}, 'scalar_prep': {'RR_PREP_SCALAR': '1', 'RR_NO_LOOKAHEAD': '1'},
-         'no_split': {'RR_NO_SPLIT': '1', 'RR_NO_LOOKAHEAD': '1'}, 'small_pool': {'RR_SOLVER_POOL': '300'}}
+PATHS = {'default': {}, 'no_split': {'RR_NO_SPLIT': '1', 'RR_NO_LOOKAHEAD': '1'}, 'small_pool': {'RR_SOLVER_POOL': '300'}}
 
 
 @pytest.mark.parametrize('path', list(PATHS))

@@ -39,7 +39,7 @@ def _same(a, b):
 
 
 def test_lookahead_is_bitwise_equivalent_to_inline_preparation(monkeypatch):
-    """Same seeded run twice: with the look-ahead (k_prep_a / k_prep_b / k_collide of step t+1 launched behind the solve of
+    """Same seeded run twice: with the look-ahead (k_prep_ab16 / k_collide of step t+1 launched behind the solve of
     step t, class by class, on side streams under the render) and with RR_NO_LOOKAHEAD=1 (every step prepares itself in line).
     Full-range commands (heavy and very heavy envs appear), per-env render flags, and everything that invalidates a
     look-ahead in between: reset masks, single and batched teleports, home-pose edits, set_state, a rejected command."""

@@ -17,9 +17,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'real_robots_amd', 'csrc')
 
-IN_FIELDS = ('N', 'ntiles', 'render_mode', 'timing', 'split_heavy', 'lookahead', 'prep_scalar', 'coop_all', 'split_max_pct', 'h', 'vh', 'known')
+IN_FIELDS = ('N', 'ntiles', 'render_mode', 'timing', 'split_heavy', 'lookahead', 'coop_all', 'split_max_pct', 'h', 'vh', 'known')
 OUT_FIELDS = ('path', 'mostly_heavy', 'h_long', 'heavy_render', 'coop_h', 'coop_vh_beside', 'coop_vh_alone', 'la_on_vh', 'la_side',
-              'vh_render_on_main', 'vh_render_on_aux', 'la_after_raster', 'small_n', 'single_solve', 'la_beside')
+              'vh_render_on_main', 'vh_render_on_aux', 'small_n', 'single_solve', 'la_beside')
 SPLIT, SPLIT_TIMED, SINGLE = 0, 1, 2                      # StepPlan::path
 WALKER, RASTER_LIST, GRID = 0, 1, 2                       # StepPlan::heavy_render
 CHAIN_N1, SIDE_BY_SIDE, WAVE_PER_ENV, PACKED = 0, 1, 2, 3  # StepPlan::single_solve
@@ -33,11 +33,11 @@ int main() {
         for (int &x : v) if (scanf("%%d", &x) != 1) return 0;
         PlanIn in;
         in.N = v[0]; in.ntiles = v[1]; in.render_mode = v[2]; in.timing = v[3] != 0;
-        in.split_heavy = v[4] != 0; in.lookahead = v[5] != 0; in.prep_scalar = v[6] != 0; in.coop_all = v[7] != 0; in.split_max_pct = v[8];
-        in.counts.h = v[9]; in.counts.vh = v[10]; in.counts.known = v[11] != 0;
+        in.split_heavy = v[4] != 0; in.lookahead = v[5] != 0; in.coop_all = v[6] != 0; in.split_max_pct = v[7];
+        in.counts.h = v[8]; in.counts.vh = v[9]; in.counts.known = v[10] != 0;
         const StepPlan p = plan_step(in);
         const int out[] = {(int)p.path, p.mostly_heavy, p.h_long, (int)p.heavy_render, p.coop_h, p.coop_vh_beside, p.coop_vh_alone, p.la_on_vh, p.la_side,
-                           p.vh_render_on_main, p.vh_render_on_aux, p.la_after_raster, p.small_n, (int)p.single_solve, p.la_beside};
+                           p.vh_render_on_main, p.vh_render_on_aux, p.small_n, (int)p.single_solve, p.la_beside};
         char line[sizeof out / sizeof out[0] + 2];
         int n = 0;
         for (int x : out) line[n++] = (char)('0' + x);      // (every field is a single digit)
@@ -73,7 +73,7 @@ def mirror(rows):
     r = {k: np.asarray(rows, np.int64).reshape(-1, len(IN_FIELDS))[:, i] for i, k in enumerate(IN_FIELDS)}
     N, nt, pct = r['N'], r['ntiles'], r['split_max_pct']
     render, timing, known = r['render_mode'] != 0, r['timing'] != 0, r['known'] != 0
-    split_heavy, ahead, prep_scalar, coop_all = (r[k] != 0 for k in ('split_heavy', 'lookahead', 'prep_scalar', 'coop_all'))
+    split_heavy, ahead, coop_all = (r[k] != 0 for k in ('split_heavy', 'lookahead', 'coop_all'))
     count = lambda which, fallback: np.where(known, r[('h', 'vh')[which]], fallback)
     o = {}
     # rr_step
@@ -95,7 +95,6 @@ def mirror(rows):
     o['la_side'] = ahead & ~o['la_on_vh']
     o['vh_render_on_main'] = o['la_on_vh'] & h_long
     o['vh_render_on_aux'] = o['la_on_vh'] & ~o['vh_render_on_main']
-    o['la_after_raster'] = o['la_on_vh'] & ~prep_scalar
     # step_single
     o['small_n'] = (N <= 64) & split_heavy & ~timing
     side = ~render & (N > 1024) & split_heavy & ~timing & (count(1, 0) >= 64)
@@ -108,7 +107,7 @@ def mirror(rows):
 def product_rows():
     """Every N x tiles x render mode x timing x one setting off in turn x split_max_pct, with both sides of every threshold for h and
     vh (the threshold and the threshold + 1, and N), and the case of no reading at all."""
-    settings = [(1, 1, 0, 1), (0, 1, 0, 1), (1, 0, 0, 1), (1, 1, 1, 1), (1, 1, 0, 0)]     # split_heavy, lookahead, prep_scalar, coop_all: the defaults, then each flipped
+    settings = [(1, 1, 1), (0, 1, 1), (1, 0, 1), (1, 1, 0)]     # split_heavy, lookahead, coop_all: the defaults, then each flipped
     rows = []
     for N, nt, pct in itertools.product((1, 2, 64, 65, 448, 1024, 1025, 1100, 4096), (1, 4, 12), (0, 2, 60)):
         thresholds = (0, 64, 256, 512, 768 // nt, N // 3, N * pct // 100)
@@ -119,8 +118,8 @@ def product_rows():
     return np.array(rows, np.int64)
 
 
-def row(N, ntiles, h=0, vh=0, known=1, render_mode=1, timing=0, split_heavy=1, lookahead=1, prep_scalar=0, coop_all=1, split_max_pct=60):
-    return (N, ntiles, render_mode, timing, split_heavy, lookahead, prep_scalar, coop_all, split_max_pct, h, vh, known)
+def row(N, ntiles, h=0, vh=0, known=1, render_mode=1, timing=0, split_heavy=1, lookahead=1, coop_all=1, split_max_pct=60):
+    return (N, ntiles, render_mode, timing, split_heavy, lookahead, coop_all, split_max_pct, h, vh, known)
 
 
 def placement(inp, plan):
@@ -143,7 +142,7 @@ def test_plan_is_the_decisions_the_host_code_made(plan_program):
     bad = np.flatnonzero((got != want).any(1))
     assert len(bad) == 0, (len(bad), dict(zip(IN_FIELDS, rows[bad[0]])), dict(zip(OUT_FIELDS, got[bad[0]])), dict(zip(OUT_FIELDS, want[bad[0]])))
     # (the product reaches every value of every field)
-    for k, n in zip(OUT_FIELDS, (3, 2, 2, 3, 2, 2, 2, 2, 2, 2, 2, 2, 2, 4, 2)):
+    for k, n in zip(OUT_FIELDS, (3, 2, 2, 3, 2, 2, 2, 2, 2, 2, 2, 2, 4, 2)):
         assert len(np.unique(got[:, OUT_FIELDS.index(k)])) == n, k
 
 
@@ -166,7 +165,7 @@ def test_the_named_workloads_take_the_rows_of_the_design_table(plan_program):
                      'gym facade': '4', '16 envs with camera': '1'}
     assert plans['gym facade'][1]['single_solve'] == CHAIN_N1 and plans['16 envs without camera'][1]['single_solve'] == WAVE_PER_ENV
     p = plans['early window'][1]
-    assert p['coop_h'] and p['coop_vh_beside'] and p['heavy_render'] == WALKER and p['vh_render_on_aux'] and p['la_after_raster']
+    assert p['coop_h'] and p['coop_vh_beside'] and p['heavy_render'] == WALKER and p['vh_render_on_aux'] and p['la_on_vh']
     p = plans['late window'][1]
     assert not p['coop_h'] and p['coop_vh_beside'] and p['heavy_render'] == RASTER_LIST and p['vh_render_on_main'] and not p['vh_render_on_aux']
     p = plans['macro'][1]
