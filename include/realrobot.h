@@ -32,7 +32,8 @@ extern "C" {
                               objects); checkpoint header version 4 carries them; rr_set_env_cameras, rr_set_env_appearance; rr_set_env_actuators,
                               rr_get_env_actuators (per-env motor gains, motor force and joint damping; checkpoint header version 5 carries them); rr_contact_observations;
                               rr_set_goals, rr_set_env_goals, rr_set_episode, rr_episode_update, rr_episode_buffer (goal table and episode
-                              record on the device; checkpoints do not carry them) */
+                              record on the device; checkpoints do not carry them); rr_snapshot_slots, rr_copy_envs (env forks and
+                              snapshot slots on the device) */
 
 enum {
     RR_OK = 0,
@@ -258,6 +259,57 @@ int rr_checkpoint_bytes(rr_env *env, size_t *bytes);
 int rr_checkpoint_save(rr_env *env, void *dst_host, size_t bytes);
 int rr_checkpoint_restore(rr_env *env, const void *src_host, size_t bytes);
 int rr_sync(rr_env *env);
+
+/* ---- Env forks and snapshot slots on the device (additive in ABI 7) ----------------------------------------------------------------
+ * Replaces pybullet.saveState() / restoreState(stateId) -- the IN-MEMORY variant, which the host-side rr_checkpoint_* calls do not
+ * cover -- and adds what a batched simulator needs for planning with itself as the model (MPPI / CEM rollouts, branching search):
+ * "env j becomes an exact copy of env i", for any map, and a whole batch put aside and brought back, all without the host.
+ * The RECORD of an env is what a checkpoint carries for it minus its settings:
+ *   rows 0..71 of the state slab (the 61 floats of RR_F_STATE and the motor targets); the contact count of the last solved step; the
+ *   live rows of that step's contact list and of its normal forces -- the rows below min(count, 48), the contact history of the warm
+ *   start --; RR_F_TIMESTEP; RR_F_ERRFLAGS; the four RR_F_TOUCH values; the published count and class (RR_F_CONTACT_COUNT,
+ *   RR_F_ENV_CLASS).
+ * The rows of the list and of the forces from the count on are NOT copied and are unspecified in a destination: every reader of
+ * the list (the collision pass's warm-start matching, the solve, rr_contact_observations, rr_get_contacts) stops at the count.
+ * NOT part of a record, and left with the destination env: the object home poses, the object dynamics and pair materials
+ * (rr_set_object_dynamics), the actuators (rr_set_env_actuators), the cameras and the appearance -- settings of the env, not its
+ * state --; the episode record (RR_EP_*: a setting of the handle, as for restores -- after a copy into running envs the caller
+ * re-bases the previous score with rr_set_env_goals); the fields of rr_contact_observations (they hold what its last call computed);
+ * a macro plan in flight and its cursor (rr_plan_macro: policy state); the images and the renderer's fragment lists.  A fork
+ * between envs with different settings is therefore not a continuation of the source: the copy steps with its own mass, gains,
+ * home poses and camera. */
+#define RR_SLOT_LIVE (-1)    /* the running envs, as a slot number of rr_copy_envs */
+#define RR_MAX_SLOTS 64
+/* n_slots snapshot slots, numbered 0 .. n_slots - 1, each a record for every env (2 820 bytes per env at full list capacity, every
+ * array rounded up to 256 bytes: 11.6 MB per slot at 4096 envs).  n_slots in [0, RR_MAX_SLOTS], RR_EINVAL otherwise.  Every new slot
+ * is filled with the present records of the running envs (on the library's stream), so no slot ever holds an unwritten record.
+ * A later call REPLACES all slots -- their contents are lost --; n_slots == 0 frees them.  A failed allocation returns RR_EDEVICE,
+ * keeps the old slots and leaves the handle usable.  Does not wait for the device unless it gives up old slots. */
+int rr_snapshot_slots(rr_env *env, int32_t n_slots);
+/* For every env i, the record of env i in dst_slot becomes the record of env src_index[i] in src_slot; RR_SLOT_LIVE names the
+ * running envs.  An index of -1 keeps env i as it is; src_index == NULL is the identity over all envs.  One call, four operations:
+ *   (RR_SLOT_LIVE, RR_SLOT_LIVE, idx)  fork between running envs         (s, RR_SLOT_LIVE, NULL)  restore (restoreState)
+ *   (RR_SLOT_LIVE, s, NULL or idx)     save (saveState)                  (s, RR_SLOT_LIVE, idx)   one saved env into many running ones
+ * and slot to slot.  A slot number outside [-1, n_slots) returns RR_EINVAL.
+ * src_index is i32 [N].  A HOST pointer (index_on_device == 0) is checked before anything is launched: an entry outside
+ * {-1} u [0, N) returns RR_EINVAL, the message names the env, and nothing changes; the array is copied into the pinned staging ring
+ * before the call returns (the caller may reuse it at once).  A DEVICE pointer (index_on_device != 0) is read in place on the
+ * library's stream under the STREAM CONTRACT of rr_step's cmd_on_device (produced on that stream or ordered before it; not
+ * overwritten before later work on that stream, or rr_sync); an entry out of range keeps that env as it is, like -1 (the kernel
+ * checks the range before it forms an address).
+ * With src_slot == dst_slot and an index -- running envs onto running envs included -- the copy behaves as if every source were
+ * read before any destination is written: swaps, cycles, chains and a broadcast from an env that is itself overwritten come out
+ * right.  Such a call goes through a hidden staging slot (two launches), allocated by the first one; if that fails the call returns
+ * RR_EDEVICE, changes nothing and the handle stays usable.  Different slots, or a NULL index: one launch.  (NULL with equal slots
+ * copies every record onto itself: nothing is done.)
+ * When dst_slot is RR_SLOT_LIVE the call is a change of state from outside, like rr_reset: the next step prepares itself again;
+ * a destination env takes the source's error bits 1, 2 and 4 -- a frozen env forks frozen -- while bit 8 is CLEARED: that bit
+ * describes the destination's own last rendered frame (rr_set_state clears it too); the observation buffers and a mapped host
+ * mirror are refreshed behind the copy.  The images are left alone: an env keeps its last frame until its own next render, which
+ * shows the new state.  The step that follows continues the SOURCE's run bit for bit (tested), given equal settings.
+ * On the library's stream, behind the steps enqueued before it; the call checks the launch and returns without waiting.
+ * Out of scope: copying settings, the episode record, macro plans or images (above); forks between two handles or two devices. */
+int rr_copy_envs(rr_env *env, int32_t src_slot, int32_t dst_slot, const int32_t *src_index, int32_t index_on_device);
 /* Host mirror of the low-dimensional observations, for callers that read them on the host after every step (the gym facade:
  * Kuka.calc_state + get_touch_sensors, robot.py:152-163, 203-211): a pinned, device-mapped host block
  *   { f32 joints [N][9] | f32 touch [N][4] | f32 object poses [N][n_obj][7] | i32 timestep [N] | u32 errflags [N] }

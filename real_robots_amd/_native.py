@@ -36,7 +36,8 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_pack_image_delta', 'rr_apply_image_delta', 'rr_set_object_dynamics', 'rr_get_object_dynamics',
            'rr_set_env_cameras', 'rr_set_env_appearance', 'rr_get_env_appearance', 'rr_render_instances',
            'rr_set_env_actuators', 'rr_get_env_actuators', 'rr_contact_observations',
-           'rr_set_goals', 'rr_set_env_goals', 'rr_set_episode', 'rr_episode_update', 'rr_episode_buffer', 'rr_episode_copy_to_host')
+           'rr_set_goals', 'rr_set_env_goals', 'rr_set_episode', 'rr_episode_update', 'rr_episode_buffer', 'rr_episode_copy_to_host',
+           'rr_snapshot_slots', 'rr_copy_envs')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
@@ -46,6 +47,7 @@ N_JOINTS = 11
 (EP_SCORE, EP_REWARD, EP_DONE, EP_GOAL_INDEX, EP_EPISODE, EP_FINAL_OBS, EP_GOAL_POS, EP_GOAL_RGB) = range(8)
 EP_NAMES = ('score', 'reward', 'done', 'goal_index', 'episode', 'final_obs', 'goal_pos', 'goal_rgb')
 GOAL_SCORED, GOAL_HAS_START = 1, 2      # rr_set_goals flag bits: the object counts in the score / has a start pose
+SLOT_LIVE, MAX_SLOTS = -1, 64           # RR_SLOT_LIVE: the running envs as a slot number of rr_copy_envs; RR_MAX_SLOTS
 
 
 class Config(C.Structure):
@@ -164,6 +166,8 @@ def load_library():
     L.rr_episode_update.argtypes = [vp, i32]
     L.rr_episode_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rr_episode_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
+    L.rr_snapshot_slots.argtypes = [vp, i32]
+    L.rr_copy_envs.argtypes = [vp, i32, i32, vp, i32]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]

@@ -214,6 +214,70 @@ class BatchedREALRobotEnv:
         buf = np.ascontiguousarray(ckpt, dtype=np.uint8)
         nat.check(self.L.rr_checkpoint_restore(self.h, buf.ctypes.data, buf.nbytes))
 
+    # ------------------------------------------------------------------ env forks and snapshot slots on the device
+    def _source_index(self, src_index):
+        """src_index of copy_envs -> (address or None, index_on_device, object that keeps the memory alive).  A host integer array
+        [N] is checked here for shape and range (-1 or an env); a device array (`__cuda_array_interface__`, a CUDA torch tensor) for
+        int32, contiguous and shape [N] -- its values are the kernel's to check.  Anything else raises ValueError."""
+        N = self.N
+        if src_index is None:
+            return None, 0, None
+        if hasattr(src_index, 'is_cuda') and hasattr(src_index, 'data_ptr'):        # a torch tensor
+            if src_index.is_cuda:
+                if str(src_index.dtype) != 'torch.int32' or tuple(src_index.shape) != (N,) or not src_index.is_contiguous():
+                    raise ValueError("a device src_index must be a contiguous int32 tensor of shape (%d,), not %s %s"
+                                     % (N, src_index.dtype, tuple(src_index.shape)))
+                return int(src_index.data_ptr()), 1, src_index
+            src_index = src_index.numpy()
+        cai = getattr(src_index, '__cuda_array_interface__', None)
+        if cai is not None:
+            if np.dtype(cai['typestr']) != np.dtype(np.int32) or tuple(cai['shape']) != (N,) or cai.get('strides') not in (None, (4,)):
+                raise ValueError("a device src_index must be a contiguous int32 array of shape (%d,), not %s %s"
+                                 % (N, cai['typestr'], tuple(cai['shape'])))
+            return int(cai['data'][0]), 1, src_index
+        a = np.asarray(src_index)
+        if a.dtype.kind not in 'iu':
+            raise ValueError("src_index must be an integer array, not %s" % a.dtype)
+        if a.shape != (N,):
+            raise ValueError("src_index must have shape (%d,), not %s" % (N, a.shape))
+        bad = np.flatnonzero((a < -1) | (a >= N))
+        if bad.size:
+            raise ValueError("src_index: env %d: %d is not -1 or in [0, %d)" % (bad[0], a[bad[0]], N))
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        return a.ctypes.data, 0, a
+
+    def snapshot_slots(self, n):
+        """n snapshot slots (0 .. 64) on the device (rr_snapshot_slots), every one filled with the present records of the running
+        envs; replaces all earlier slots, 0 frees them."""
+        nat.check(self.L.rr_snapshot_slots(self.h, int(n)))
+
+    def copy_envs(self, src_index=None, src_slot=None, dst_slot=None):
+        """The record of env i in dst_slot becomes the record of env src_index[i] in src_slot (rr_copy_envs); a slot of None is the
+        running envs.  src_index: None (identity), an integer array [N] on the host (-1: keep env i), or an int32 device array [N]
+        (`__cuda_array_interface__` / CUDA torch tensor, read in place on the library's stream; an entry out of range keeps that
+        env).  A record is the state with the motor targets, the contact history of the warm start, clock, error flags and touch
+        sensors: the copy continues its source's run bit for bit.  Settings (object dynamics, actuators, home poses, cameras,
+        appearance), the episode record and the images stay with the destination env.  Same slot with an index copies as if all
+        sources were read first (swaps and cycles are fine).  Does not wait for the device."""
+        ptr, on_dev, keep = self._source_index(src_index)
+        nat.check(self.L.rr_copy_envs(self.h, nat.SLOT_LIVE if src_slot is None else int(src_slot),
+                                      nat.SLOT_LIVE if dst_slot is None else int(dst_slot), ptr, on_dev))
+        del keep
+
+    def fork(self, src_index):
+        """Running env i becomes an exact copy of running env src_index[i] (-1: stays as it is), on the device."""
+        self.copy_envs(src_index)
+
+    def save_snapshot(self, slot, src_index=None):
+        """pybullet's in-memory saveState for the batch: the running envs' records into `slot` (with src_index: env
+        src_index[i] into place i)."""
+        self.copy_envs(src_index, None, slot)
+
+    def load_snapshot(self, slot, src_index=None):
+        """pybullet's restoreState: the records of `slot` into the running envs (with src_index: saved env src_index[i] into
+        running env i -- one saved env into many)."""
+        self.copy_envs(src_index, slot, None)
+
     def set_object_pose(self, env, obj, pose7):
         p = np.ascontiguousarray(pose7, dtype=np.float32)
         assert p.shape == (7,)

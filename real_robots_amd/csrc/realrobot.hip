@@ -464,5 +464,6 @@ __device__ __forceinline__ void dispatch_order_class(int x, int N, int ntiles, i
 #include "rr_render.inc"    // rasteriser: k_raster, k_shade, the list-walking render kernels
 #include "rr_gather.inc"    // delta image records for the observation gather (k_pack_delta, k_apply_delta)
 #include "rr_episode.inc"    // k_episode, k_goal_image: goal table and per-env episode record (score, reward, done, auto-reset into the next goal)
+#include "rr_fork.inc"    // k_fork: env records gathered on the device -- forks and snapshot slots (rr_snapshot_slots, rr_copy_envs)
 #include "rr_plan.inc"    // plan_step: the placement and launch shapes of one step from one reading of the lagged list lengths (host only, no HIP type)
 #include "rr_host.inc"    // host side: model blob, rr_env, the C ABI

@@ -185,6 +185,10 @@ struct rr_env : ModelTables {
     unsigned char *ep_goal_rgb = nullptr;    // RR_EP_GOAL_RGB [N][H*W*3]: exists exactly while the table has images
     size_t ep_bytes[RR_EP_COUNT] = {};
     int ep_horizon = 0, ep_stride = 1;
+    // env forks and snapshot slots (rr_snapshot_slots, rr_copy_envs): a setting-free copy of env records on the device
+    char *snap = nullptr; int n_slots = 0;   // the slots: one allocation of n_slots * fork_slot_bytes(N), replaced as a whole; freed by rr_destroy
+    char *fork_stage = nullptr;    // the hidden staging slot of the in-place copies: allocated by the first one (in `allocs`)
+    int *fork_index = nullptr;     // [N] device staging of a host index (in `allocs`)
 };
 
 // The combining rule of the contact materials of two shapes (btManifoldResult::calculateCombinedFriction / Restitution /
@@ -530,7 +534,7 @@ int rr_destroy(rr_env *e) {
     hipSetDevice(e->cfg.device);
     hipStreamSynchronize(e->stream);
     for (void *p : e->allocs) hipFree(p);
-    for (void *p : {e->goals_block, (void *)e->goals_rgb, (void *)e->ep_goal_rgb}) if (p) hipFree(p);
+    for (void *p : {e->goals_block, (void *)e->goals_rgb, (void *)e->ep_goal_rgb, (void *)e->snap}) if (p) hipFree(p);
     for (int i = 0; i < 2 * RR_NUM_KERNELS; i++) if (e->ev[i]) hipEventDestroy(e->ev[i]);
     if (e->aux) { hipStreamSynchronize(e->aux); hipStreamDestroy(e->aux); }
     if (e->aux2) { hipStreamSynchronize(e->aux2); hipStreamDestroy(e->aux2); }
@@ -1493,6 +1497,134 @@ int rr_checkpoint_restore(rr_env *e, const void *src_host, size_t bytes) {
     HIPCHK(hipMemsetAsync(e->D.hcount, 0, 16, e->stream)); HIPCHK(hipMemsetAsync(e->D.hcount2, 0, 16, e->stream));
     launch_obs(e);
     HIPCHK(hipStreamSynchronize(e->stream));   // the source is host memory
+    return RR_OK;
+}
+
+// ---- env forks and snapshot slots on the device (rr_fork.inc) -------------------------------------------------------------------
+// A slot is one block of the nine arrays of a ForkRec for all N envs, every array on a 256-byte boundary; the slots of a handle
+// are one allocation (rr_env::snap), the staging slot of the in-place copies another (rr_env::fork_stage, kept until rr_destroy).
+static const size_t FORK_PART_BYTES[9] = {4 * ST_TOTAL, 4, 4 * MAXC * 12, 4 * MAXC, 4, 4, 16, 4, 4};      // per env, in ForkRec's order
+static size_t fork_slot_bytes(size_t N) {
+    size_t total = 0;
+    for (size_t b : FORK_PART_BYTES) total += (b * N + 255) & ~(size_t)255;
+    return total;
+}
+static ForkRec fork_rec_at(char *base, size_t N) {
+    char *p[9];
+    for (int k = 0; k < 9; k++) { p[k] = base; base += (FORK_PART_BYTES[k] * N + 255) & ~(size_t)255; }
+    ForkRec r;
+    r.state = (float *)p[0]; r.ccount = (int *)p[1]; r.clist = (float4 *)p[2]; r.cforce = (float *)p[3]; r.timestep = (int *)p[4];
+    r.errflags = (unsigned *)p[5]; r.touch = (float *)p[6]; r.ccount_pub = (int *)p[7]; r.class_pub = (int *)p[8];
+    return r;
+}
+// The records of the running envs: the contact list, its count and the forces of the frame of the LAST SOLVED step, as bind_frames
+// left them (the look-ahead's frame, clist_next, is not part of a record: a copy into the running envs drops it, la_valid).
+static ForkRec fork_rec_live(const rr_env *e) {
+    const DevPtrs &D = e->D;
+    ForkRec r;
+    r.state = D.state; r.ccount = D.ccount; r.clist = D.clist; r.cforce = D.cforce; r.timestep = D.timestep;
+    r.errflags = D.errflags; r.touch = D.touch; r.ccount_pub = D.ccount_pub; r.class_pub = D.class_pub;
+    return r;
+}
+static ForkRec fork_rec(const rr_env *e, int slot) {
+    return slot == RR_SLOT_LIVE ? fork_rec_live(e) : fork_rec_at(e->snap + (size_t)slot * fork_slot_bytes(e->P.N), e->P.N);
+}
+// into a running env: the source's error bits 1, 2 and 4 (a frozen env forks frozen); bit 8 is cleared -- it describes the
+// destination's own last rendered frame (rr_set_state clears it as well)
+static inline unsigned fork_err_mask(int dst_slot) { return dst_slot == RR_SLOT_LIVE ? 7u : 0xffffffffu; }
+static void launch_fork(rr_env *e, const ForkRec &src, const ForkRec &dst, const int *idx_dev, int identity, unsigned err_mask) {
+    hipLaunchKernelGGL(k_fork, dim3((e->P.N + FK_GROUP - 1) / FK_GROUP, 5), dim3(256), 0, e->stream, e->P.N, src, dst, idx_dev, identity, err_mask);
+}
+// The first entry of a host index that is neither -1 nor an env, or -1 when there is none (no HIP type: plain host arithmetic).
+static int fork_bad_index(const int32_t *idx, int N) {
+    for (int i = 0; i < N; i++) if (idx[i] < -1 || idx[i] >= N) return i;
+    return -1;
+}
+// a device allocation that may fail without harm: the error is not left behind for the next step's launch check
+static int fork_alloc(void **p, size_t bytes, const char *what) {
+    const hipError_t rc = hipMalloc(p, bytes);
+    if (rc == hipSuccess) return RR_OK;
+    (void)hipGetLastError();
+    *p = nullptr;
+    return fail(RR_EDEVICE, std::string(what) + hipGetErrorString(rc));
+}
+
+int rr_snapshot_slots(rr_env *e, int32_t n_slots) {
+    if (!e) return fail(RR_EINVAL, "null env");
+    if (n_slots < 0 || n_slots > RR_MAX_SLOTS) return fail(RR_EINVAL, "rr_snapshot_slots: n_slots " + std::to_string(n_slots) + " is not in [0, " + std::to_string(RR_MAX_SLOTS) + "]");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const size_t N = e->P.N, sb = fork_slot_bytes(N);
+    void *blk = nullptr;
+    if (n_slots > 0) {
+        // the new slots exist before the old ones are given up; every one starts as a copy of the running envs
+        const int rc = fork_alloc(&blk, (size_t)n_slots * sb, "rr_snapshot_slots: allocating the slots: ");
+        if (rc != RR_OK) return rc;
+        const ForkRec live = fork_rec_live(e);
+        for (int k = 0; k < n_slots; k++) launch_fork(e, live, fork_rec_at((char *)blk + (size_t)k * sb, N), nullptr, 0, 0xffffffffu);
+        const hipError_t lrc = hipGetLastError();
+        if (lrc != hipSuccess) { (void)hipStreamSynchronize(e->stream); hipFree(blk); return fail(RR_EDEVICE, std::string("rr_snapshot_slots: ") + hipGetErrorString(lrc)); }
+    }
+    if (e->snap) {
+        HIPCHK(hipStreamSynchronize(e->stream));      // (ends every queued copy that reads or writes the old slots)
+        hipFree(e->snap);
+    }
+    e->snap = (char *)blk; e->n_slots = n_slots;
+    return RR_OK;
+}
+
+// On the library's stream, like rr_contact_observations: every rr_step has made that stream wait for its side streams (ev_join /
+// ev_join2 in step_split and step_single; the timed leg runs on it alone) before it returns, so the launch is ordered behind every
+// kernel that reads or writes the records of the running envs -- the look-ahead included -- without a wait of its own.
+int rr_copy_envs(rr_env *e, int32_t src_slot, int32_t dst_slot, const int32_t *src_index, int32_t index_on_device) {
+    if (!e) return fail(RR_EINVAL, "null env");
+    for (int32_t s : {src_slot, dst_slot})
+        if (s < RR_SLOT_LIVE || s >= e->n_slots)
+            return fail(RR_EINVAL, "rr_copy_envs: slot " + std::to_string(s) + " is not RR_SLOT_LIVE or in [0, " + std::to_string(e->n_slots) + ") (rr_snapshot_slots)");
+    const int N = e->P.N;
+    const bool host_index = src_index && !index_on_device;
+    if (host_index) {
+        const int bad = fork_bad_index(src_index, N);
+        if (bad >= 0) return fail(RR_EINVAL, "rr_copy_envs: env " + std::to_string(bad) + ": source index " + std::to_string(src_index[bad]) + " is not -1 or in [0, " + std::to_string(N) + ")");
+    }
+    if (src_slot == dst_slot && !src_index) return RR_OK;      // every record onto itself
+    HIPCHK(hipSetDevice(e->cfg.device));
+    // whatever has to be allocated is allocated before anything is launched: a failure leaves the handle as it was
+    const bool staged = src_slot == dst_slot;                  // (with an index: the map may read envs that it also writes)
+    if (staged && !e->fork_stage) {
+        void *q = nullptr;
+        const int rc = fork_alloc(&q, fork_slot_bytes(N), "rr_copy_envs: allocating the staging slot: ");
+        if (rc != RR_OK) return rc;
+        e->allocs.push_back(q); e->fork_stage = (char *)q;
+    }
+    const int *idx_dev = src_index;
+    if (host_index) {
+        if (!e->fork_index) {
+            void *q = nullptr;
+            const int rc = fork_alloc(&q, (size_t)N * 4, "rr_copy_envs: allocating the index staging: ");
+            if (rc != RR_OK) return rc;
+            e->allocs.push_back(q); e->fork_index = (int *)q;
+        }
+        // through the pinned ring, as rr_step's commands: the caller may reuse its array at once and nobody waits for the device
+        char *pin = nullptr; int pin_idx = -1;
+        const int rc = pin_acquire(e, &pin, &pin_idx);
+        if (rc != RR_OK) return rc;
+        memcpy(pin, src_index, (size_t)N * 4);
+        HIPCHK(hipMemcpyAsync(e->fork_index, pin, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipEventRecord(e->pin_ev[pin_idx], e->stream)); e->pin_used[pin_idx] = true;
+        idx_dev = e->fork_index;
+    }
+    const bool to_live = dst_slot == RR_SLOT_LIVE;
+    if (to_live) e->la_valid = false;      // the state changes from outside: the next step prepares itself in line (as rr_reset)
+    const ForkRec src = fork_rec(e, src_slot), dst = fork_rec(e, dst_slot);
+    if (staged) {
+        // as if every source were read before any destination is written: staging[i] = src[idx[i]], then dst[i] = staging[i] for the
+        // envs with a valid index -- two launches of the same kernel, ordered by the stream
+        const ForkRec stage = fork_rec_at(e->fork_stage, N);
+        launch_fork(e, src, stage, idx_dev, 0, 0xffffffffu);
+        launch_fork(e, stage, dst, idx_dev, 1, fork_err_mask(dst_slot));
+    } else launch_fork(e, src, dst, idx_dev, 0, fork_err_mask(dst_slot));
+    if (to_live) launch_obs(e);            // the observation buffers and a mapped host mirror follow
+    HIPCHK(hipGetLastError());
     return RR_OK;
 }
 
