@@ -33,20 +33,36 @@ def quat_to_mat(q):
                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
-def forward(q11):
-    """Returns (R[11,3,3], p[11,3], axis_world[11,3]) of the 11 moving bodies."""
-    m = load_model()
+_chain = None
+
+
+def _chain_f64():
+    """The model's chain constants in float64, converted once (the values of load_model(), no arithmetic)."""
+    global _chain
+    if _chain is None:
+        m = load_model()
+        b = int(m['link_body'][EE_LINK])
+        _chain = dict(robot_pos=m['robot_pos'].astype(np.float64), jrot=[m['body_jrot'][i].astype(np.float64) for i in range(11)],
+                      axis=[m['body_axis'][i].astype(np.float64) for i in range(11)],
+                      jpos=[m['body_jpos'][i].astype(np.float64) for i in range(11)],
+                      ee_body=b, ee_rot=m['link_rot'][EE_LINK].astype(np.float64), ee_pos=m['link_pos'][EE_LINK].astype(np.float64))
+    return _chain
+
+
+def forward(q11, nbodies=11):
+    """Returns (R[11,3,3], p[11,3], axis_world[11,3]) of the 11 moving bodies (the first `nbodies` filled in)."""
+    c = _chain_f64()
     R = np.zeros((11, 3, 3))
     p = np.zeros((11, 3))
     ax = np.zeros((11, 3))
-    for b in range(11):
+    for b in range(nbodies):
         if PARENT[b] < 0:
-            Rp, pp = np.eye(3), m['robot_pos'].astype(np.float64)
+            Rp, pp = np.eye(3), c['robot_pos']
         else:
             Rp, pp = R[PARENT[b]], p[PARENT[b]]
-        Rj = Rp @ m['body_jrot'][b].astype(np.float64)
-        a = m['body_axis'][b].astype(np.float64)
-        p[b] = pp + Rp @ m['body_jpos'][b].astype(np.float64)
+        Rj = Rp @ c['jrot'][b]
+        a = c['axis'][b]
+        p[b] = pp + Rp @ c['jpos'][b]
         R[b] = Rj @ _axis_angle(a, q11[b])
         ax[b] = Rj @ a
     return R, p, ax
@@ -66,31 +82,51 @@ def link_pose(q11, link):
 
 def ee_jacobian(q11):
     """6x7 geometric Jacobian (linear; angular) of the gripper base frame w.r.t. the 7 arm joints."""
-    R, p, ax = forward(q11)
-    Re, pe = link_pose(q11, EE_LINK)
+    R, p, ax = forward(q11, 7)                            # the arm: bodies 0..6 (the gripper base rides on body 6)
+    c = _chain_f64()
+    b = c['ee_body']                                      # (link_pose(q11, EE_LINK) without a second pass over the chain)
+    Re, pe = R[b] @ c['ee_rot'], p[b] + R[b] @ c['ee_pos']
     J = np.zeros((6, 7))
-    for k in range(7):
-        J[:3, k] = np.cross(ax[k], pe - p[k])
-        J[3:, k] = ax[k]
+    a, r = ax[:7], pe - p[:7]
+    J[0] = a[:, 1] * r[:, 2] - a[:, 2] * r[:, 1]          # cross(axis, lever), all seven joints at once
+    J[1] = a[:, 2] * r[:, 0] - a[:, 0] * r[:, 2]
+    J[2] = a[:, 0] * r[:, 1] - a[:, 1] * r[:, 0]
+    J[3:] = a.T
     return J, Re, pe
 
 
 ELBOW_UP_SEED = np.array([0.0, 0.6, 0.0, -1.3, 0.0, 1.2, 0.0])
 
 
+def pose_residual(Re, pe, target_pos, Rt):
+    """The 6-vector the solver drives to zero (the device's definition, rr_ik.inc ik_dls): position error, then half the
+    antisymmetric part of Rt Re^T (sin(angle) x axis of the orientation error)."""
+    dp = np.asarray(target_pos, dtype=np.float64) - pe
+    Rerr = Rt @ Re.T
+    w = 0.5 * np.array([Rerr[2, 1] - Rerr[1, 2], Rerr[0, 2] - Rerr[2, 0], Rerr[1, 0] - Rerr[0, 1]])
+    return np.concatenate([dp, w])
+
+
+def ee_residual(q11, target_pos, target_quat):
+    """Float64 residual norm of the gripper base at joints q11 against a target pose (position and orientation)."""
+    Re, pe = link_pose(np.asarray(q11, dtype=np.float64), EE_LINK)
+    Rt = quat_to_mat(np.asarray(target_quat, dtype=np.float64) / np.linalg.norm(target_quat))
+    return float(np.linalg.norm(pose_residual(Re, pe, target_pos, Rt)))
+
+
 def _dls(q, target_pos, Rt, max_iters, residual, damping, prev=None):
-    """`prev` (a list): receives the iterate before the last update and its residual -- where a float32 solver whose residual
+    """Returns (q, residual, number of updates applied: max_iters when the run never met the threshold).
+    `prev` (a list): receives the iterate before the last update and its residual -- where a float32 solver whose residual
     crosses the threshold one iteration earlier stops."""
     lam2 = damping * damping
     err = np.inf
-    for _ in range(int(max_iters)):
+    iters = int(max_iters)
+    for it in range(int(max_iters)):
         J, Re, pe = ee_jacobian(q)
-        dp = np.asarray(target_pos, dtype=np.float64) - pe
-        Rerr = Rt @ Re.T
-        w = 0.5 * np.array([Rerr[2, 1] - Rerr[1, 2], Rerr[0, 2] - Rerr[2, 0], Rerr[1, 0] - Rerr[0, 1]])
-        e = np.concatenate([dp, w])
+        e = pose_residual(Re, pe, target_pos, Rt)
         err = np.linalg.norm(e)
         if err < residual:
+            iters = it
             break
         if prev is not None:
             prev[:] = [q.copy(), float(err)]
@@ -100,7 +136,7 @@ def _dls(q, target_pos, Rt, max_iters, residual, damping, prev=None):
             dq *= 0.5 / n
         q[:7] += dq
         q[:7] = (q[:7] + np.pi) % (2 * np.pi) - np.pi
-    return q, err
+    return q, err, iters
 
 
 def inverse_kinematics(q11, target_pos, target_quat, max_iters=1000, residual=1e-3, damping=0.1, prefer=None, single_seed=False):
@@ -118,7 +154,7 @@ def inverse_kinematics(q11, target_pos, target_quat, max_iters=1000, residual=1e
     for seed in seeds:
         q = q0.copy()
         q[:7] = seed
-        q, err = _dls(q, target_pos, Rt, max_iters, residual, damping)
+        q, err, _ = _dls(q, target_pos, Rt, max_iters, residual, damping)
         _, p, _ = forward(q)
         if prefer is not None:     # continuity with the previous way-point of a plan
             key = (err < 10 * residual, -float(np.abs(q[:7] - np.asarray(prefer)[:7]).max()))
@@ -129,23 +165,43 @@ def inverse_kinematics(q11, target_pos, target_quat, max_iters=1000, residual=1e
     return best
 
 
-def ik_candidates(q11, target_pos, target_quat, prefer=None, max_iters=1000, residual=1e-3, damping=0.1):
-    """Every seed's DLS result [(q11, residual, key, q11 one update earlier, its residual)] in seed order (current joints,
+def ik_candidates(q11, target_pos, target_quat, prefer=None, max_iters=1000, residual=1e-3, damping=0.1, single_seed=False):
+    """Every seed's DLS result [(q11, residual, key, q11 one update earlier, its residual, updates applied)] in seed order (current joints,
     elbow-up, previous way-point) -- lets a test tell a branch disagreement (another seed won on a near-tie of the keys) or a
     stop one iteration apart (residual within rounding of the threshold) from an arithmetic disagreement."""
     q0 = np.array(q11, dtype=np.float64)
     Rt = quat_to_mat(np.asarray(target_quat, dtype=np.float64) / np.linalg.norm(target_quat))
     seeds = [q0[:7], ELBOW_UP_SEED] + ([np.asarray(prefer, dtype=np.float64)[:7]] if prefer is not None else [])
+    if single_seed:
+        seeds = seeds[:1]
     out = []
     for seed in seeds:
         q = q0.copy()
         q[:7] = seed
         prev = []
-        q, err = _dls(q, target_pos, Rt, max_iters, residual, damping, prev)
+        q, err, iters = _dls(q, target_pos, Rt, max_iters, residual, damping, prev)
         _, p, _ = forward(q)
         key = -float(np.abs(q[:7] - np.asarray(prefer)[:7]).max()) if prefer is not None else float(p[3][2])
-        out.append((q, float(err), key, prev[0] if prev else q, prev[1] if prev else float(err)))
+        out.append((q, float(err), key, prev[0] if prev else q, prev[1] if prev else float(err), iters))
     return out
+
+
+def segment_count(point_1, point_2, steps=500):
+    """interpolate3D's number of IK segments for the p1 -> p2 rows (env.py:433), in float64 on the inputs as given."""
+    dist = np.linalg.norm(np.asarray(point_2, dtype=np.float64) - np.asarray(point_1, dtype=np.float64))
+    return min(int(dist / 0.05) + 1, steps)
+
+
+def plan_way_points(macro_action):
+    """The IK way points of a macro plan in the order they are solved, [(first plan row, target xyz)]: above p1 (row 100), at p1
+    (200), the end of every p1 -> p2 segment (250 + i * chunk), above p2 (750).  Each one's rows run up to the next one's first
+    row; the last segment also holds the remainder rows up to 749; above p2 holds 750-799."""
+    p1, p2 = np.asarray(macro_action[0], dtype=np.float64), np.asarray(macro_action[1], dtype=np.float64)
+    pieces = segment_count(p1, p2)
+    chunk = 500 // pieces
+    coords = np.linspace(np.hstack([p1, 0.46]), np.hstack([p2, 0.46]), pieces + 1)
+    return ([(100, np.hstack([p1, 0.6])), (200, np.hstack([p1, 0.46]))] + [(250 + i * chunk, c) for i, c in enumerate(coords[1:])] +
+            [(750, np.hstack([p2, 0.6]))])
 
 
 def generate_plan(q_seed11, macro_action, single_seed=False):
