@@ -38,7 +38,11 @@ extern "C" {
 enum {
     RR_OK = 0,
     RR_EINVAL = -1,     /* bad argument */
-    RR_EDEVICE = -2,    /* HIP runtime error (no GPU, out of memory, launch failure) */
+    RR_EDEVICE = -2,    /* HIP runtime error (no GPU, out of memory, launch failure).  Memory that a call allocates on first use
+                           (contact observations, goal scores, plans and IK, per-env cameras and appearance, goal table and episode
+                           record, snapshot slots and fork staging, mapped host blocks, the staging ring) is allocated all or nothing:
+                           when that fails the call returns RR_EDEVICE, nothing has changed -- what the call would replace is kept --
+                           and the handle stays usable; a later call tries again. */
     RR_EMODEL = -3,     /* malformed model blob */
     RR_EACTION = -4     /* non-finite action (the reference asserts, robot.py:189) */
 };
@@ -283,8 +287,7 @@ int rr_sync(rr_env *env);
 /* n_slots snapshot slots, numbered 0 .. n_slots - 1, each a record for every env (2 820 bytes per env at full list capacity, every
  * array rounded up to 256 bytes: 11.6 MB per slot at 4096 envs).  n_slots in [0, RR_MAX_SLOTS], RR_EINVAL otherwise.  Every new slot
  * is filled with the present records of the running envs (on the library's stream), so no slot ever holds an unwritten record.
- * A later call REPLACES all slots -- their contents are lost --; n_slots == 0 frees them.  A failed allocation returns RR_EDEVICE,
- * keeps the old slots and leaves the handle usable.  Does not wait for the device unless it gives up old slots. */
+ * A later call REPLACES all slots -- their contents are lost --; n_slots == 0 frees them.  Does not wait for the device unless it gives up old slots. */
 int rr_snapshot_slots(rr_env *env, int32_t n_slots);
 /* For every env i, the record of env i in dst_slot becomes the record of env src_index[i] in src_slot; RR_SLOT_LIVE names the
  * running envs.  An index of -1 keeps env i as it is; src_index == NULL is the identity over all envs.  One call, four operations:
@@ -299,8 +302,7 @@ int rr_snapshot_slots(rr_env *env, int32_t n_slots);
  * checks the range before it forms an address).
  * With src_slot == dst_slot and an index -- running envs onto running envs included -- the copy behaves as if every source were
  * read before any destination is written: swaps, cycles, chains and a broadcast from an env that is itself overwritten come out
- * right.  Such a call goes through a hidden staging slot (two launches), allocated by the first one; if that fails the call returns
- * RR_EDEVICE, changes nothing and the handle stays usable.  Different slots, or a NULL index: one launch.  (NULL with equal slots
+ * right.  Such a call goes through a hidden staging slot (two launches), allocated by the first one.  Different slots, or a NULL index: one launch.  (NULL with equal slots
  * copies every record onto itself: nothing is done.)
  * When dst_slot is RR_SLOT_LIVE the call is a change of state from outside, like rr_reset: the next step prepares itself again;
  * a destination env takes the source's error bits 1, 2 and 4 -- a frozen env forks frozen -- while bit 8 is CLEARED: that bit
@@ -374,7 +376,7 @@ int rr_get_contacts(rr_env *env, int32_t env_index, float *out_host, int32_t max
  * of the rows at the moment of the call only until the next step).  After rr_reset / rr_set_state of an env, or a step that refused
  * its command (error flag 2), the env has no contacts and the next call gives it all-zero rows.
  * The three buffers are allocated on first use -- by this call, or by rr_get_buffer / rr_copy_to_host of one of the fields --,
- * zero-filled, and valid until rr_destroy; if the allocation fails the call returns RR_EDEVICE and the handle stays usable.
+ * zero-filled, and valid until rr_destroy.
  * STREAM CONTRACT as for the other zero-copy views (rr_step): the kernel runs on the library's stream behind the steps enqueued before
  * it; readers on another stream order themselves after the call (event / rr_sync), and a later call rewrites the buffers in place.
  * Out of scope: friction forces, contact positions in body frames, per-link rows for body B (body B is never a robot body). */
@@ -406,8 +408,7 @@ enum {
  * a start pose (it is named in initial_state), otherwise it starts from its home pose (rr_set_object_home).  Values of rows whose
  * bit is clear are not read; a value that is read and is not finite returns RR_EINVAL (the message names goal and object) and
  * nothing changes.  A new table leaves EVERY env without a goal (index -1) until rr_set_env_goals: indices into the old table mean
- * nothing in the new one; n_goals == 0 drops the table.  Synchronous.  A failed allocation returns RR_EDEVICE, keeps the old table
- * and leaves the handle usable.
+ * nothing in the new one; n_goals == 0 drops the table.  Synchronous.
  * RR_EP_GOAL_RGB (N H W 3 bytes: 201 MB at 4096 envs of 128 x 128) is allocated by the first table that carries images and freed by a
  * later table without: ITS POINTER MAY CHANGE whenever the image status of the table changes -- ask rr_episode_buffer again after
  * rr_set_goals.  The pointers of all other RR_EP_* buffers survive rr_set_goals. */

@@ -122,8 +122,9 @@ struct rr_env : ModelTables {
     float *link_out = nullptr;         // [N][nl][7]
     float *plan = nullptr; int *plan_step = nullptr; float *ik_in = nullptr; float *ik_out = nullptr; float *ik_err = nullptr;   // lazily allocated (macro / cartesian adapters)
     float *score_out = nullptr; unsigned char *score_mask = nullptr;            // lazily allocated (rr_evaluate_goals)
-    float4 *co_contacts = nullptr; float2 *co_force = nullptr; unsigned *co_partners = nullptr;   // lazily allocated, one block (rr_contact_observations)
-    std::vector<void *> allocs;
+    float4 *co_contacts = nullptr; float2 *co_force = nullptr; unsigned *co_partners = nullptr;   // lazily allocated (rr_contact_observations)
+    MemOwner mem;                  // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
+    bool created = false;
     bool timing = false;
     int *h_hcount = nullptr;       // pinned host copy of D.hcount[0] (device-mapped: written by the first solve launch of every step, solve_body)
     bool images_valid = false;     // every env's image holds its previous frame (static layer + the pixels of its fragment list)
@@ -174,11 +175,9 @@ struct rr_env : ModelTables {
     // per-env appearance (rr_set_env_appearance): allocated by its first call; D.env_colour / D.env_light point at them while it is in force
     std::vector<float> colour_host, light_host;    // [N][MAXINST][3], [N][4] (unit vectors): what is uploaded, and what rr_get_env_appearance returns
     float *colour_dev = nullptr, *light_dev = nullptr;
-    // goals and episodes (rr_set_goals .. rr_episode_update): a setting of the handle like the cameras.  The record's buffers are one
-    // block, allocated on first use and kept until rr_destroy (in `allocs`); the table and RR_EP_GOAL_RGB are replaced by rr_set_goals
-    // and freed by it / by rr_destroy.
+    // goals and episodes (rr_set_goals .. rr_episode_update): a setting of the handle like the cameras.  The record's buffers are
+    // allocated on first use and kept; the table and RR_EP_GOAL_RGB are replaced by rr_set_goals.
     GoalTable goals = {};          // device table in force (G 0: none)
-    void *goals_block = nullptr;   // its allocation {start, final_pos, flags}
     unsigned char *goals_rgb = nullptr;      // [G][H*W*3] the table's images or nullptr
     EpisodeRec ep = {};            // ep.score == nullptr: not allocated yet
     int *ep_index_stage = nullptr; // [N] staging of rr_set_env_goals' indices
@@ -186,9 +185,9 @@ struct rr_env : ModelTables {
     size_t ep_bytes[RR_EP_COUNT] = {};
     int ep_horizon = 0, ep_stride = 1;
     // env forks and snapshot slots (rr_snapshot_slots, rr_copy_envs): a setting-free copy of env records on the device
-    char *snap = nullptr; int n_slots = 0;   // the slots: one allocation of n_slots * fork_slot_bytes(N), replaced as a whole; freed by rr_destroy
-    char *fork_stage = nullptr;    // the hidden staging slot of the in-place copies: allocated by the first one (in `allocs`)
-    int *fork_index = nullptr;     // [N] device staging of a host index (in `allocs`)
+    char *snap = nullptr; int n_slots = 0;   // the slots: one allocation of n_slots * fork_slot_bytes(N), replaced as a whole
+    char *fork_stage = nullptr;    // the hidden staging slot of the in-place copies: allocated by the first one
+    int *fork_index = nullptr;     // [N] device staging of a host index
 };
 
 // The combining rule of the contact materials of two shapes (btManifoldResult::calculateCombinedFriction / Restitution /
@@ -238,15 +237,26 @@ static void launch_obs(rr_env *e) {
     launch_mirror(e);
 }
 
-template <typename T>
-static int dev_alloc(rr_env *e, T **p, size_t count, bool zero = true) {
-    void *q = nullptr;
-    HIPCHK(hipMalloc(&q, count * sizeof(T) + 16));
-    if (zero) HIPCHK(hipMemset(q, 0, count * sizeof(T) + 16));
-    e->allocs.push_back(q);
-    *p = (T *)q;
-    return RR_OK;
+// The HIP backend of the handle's memory owner (rr_mem.inc): the one place that allocates and frees for an rr_env.  A failure is taken
+// off HIP's last error -- not left behind for the next step's launch check.  Zero-fills of on-demand memory go on the library's stream:
+// every consumer runs on it or on a side stream ordered behind it by ev_fork (rr_create's, in front of its blocking uploads, are hipMemset).
+static const char *hip_mem_error(hipError_t rc) { if (rc == hipSuccess) return nullptr; (void)hipGetLastError(); return hipGetErrorString(rc); }
+static void *hip_mem_alloc(void *, MemKind kind, size_t bytes, const char **err) {
+    void *p = nullptr;
+    *err = hip_mem_error(kind == MEM_DEVICE ? hipMalloc(&p, bytes) : hipHostMalloc(&p, bytes, kind == MEM_PINNED_MAPPED ? hipHostMallocMapped : hipHostMallocDefault));
+    return *err ? nullptr : p;
 }
+static const char *hip_mem_zero(void *ctx, void *p, size_t bytes) {
+    const rr_env *e = (const rr_env *)ctx;
+    return hip_mem_error(e->created ? hipMemsetAsync(p, 0, bytes, e->stream) : hipMemset(p, 0, bytes));
+}
+static void hip_mem_release(void *, MemKind kind, void *p) { if (kind == MEM_DEVICE) (void)hipFree(p); else (void)hipHostFree(p); }
+// a group of parts for the handle, all or nothing; `what`: "<entry point>: allocating <what>"
+static int mem_get(rr_env *e, std::initializer_list<MemPart> parts, const char *what) {
+    const char *err = e->mem.acquire(parts);
+    return err ? fail(RR_EDEVICE, std::string(what) + ": " + err) : RR_OK;
+}
+#define RRCHK(x) do { const int rc_ = (x); if (rc_ != RR_OK) return rc_; } while (0)
 
 // VP = proj * view (row-major 4x4): the one product of a camera's matrices (rr_set_camera, rr_set_env_cameras, the default eye)
 static void camera_vp(const float *view16, const float *proj16, float *VP) {
@@ -306,17 +316,6 @@ static void frustum_plane_norms(const RenderModel &RM, const float *V, float *pl
             tile_plane[tile][4 + 2 * k] = ndx; tile_plane[tile][5 + 2 * k] = sqrtf(ax * ax + bx * bx + cx * cx);
         }
     }
-}
-
-// a device array of `count` elements holding a copy of the host array `src` (`bytes` of it when that is not the whole array)
-template <typename T>
-static int dev_copy(rr_env *e, const T **p, const void *src, size_t count, size_t bytes = 0) {
-    T *q = nullptr;
-    const int rc = dev_alloc(e, &q, count);
-    if (rc != RR_OK) return rc;
-    HIPCHK(hipMemcpy(q, src, bytes ? bytes : count * sizeof(T), hipMemcpyHostToDevice));
-    *p = q;
-    return RR_OK;
 }
 
 // Raster tiles of <= TILE_PIX pixels: full-width strips up to 128 columns (the 128 x 128 benchmark camera: four strips of 32
@@ -533,18 +532,14 @@ int rr_destroy(rr_env *e) {
     if (!e) return RR_OK;
     hipSetDevice(e->cfg.device);
     hipStreamSynchronize(e->stream);
-    for (void *p : e->allocs) hipFree(p);
-    for (void *p : {e->goals_block, (void *)e->goals_rgb, (void *)e->ep_goal_rgb, (void *)e->snap}) if (p) hipFree(p);
     for (int i = 0; i < 2 * RR_NUM_KERNELS; i++) if (e->ev[i]) hipEventDestroy(e->ev[i]);
     if (e->aux) { hipStreamSynchronize(e->aux); hipStreamDestroy(e->aux); }
     if (e->aux2) { hipStreamSynchronize(e->aux2); hipStreamDestroy(e->aux2); }
     for (hipStream_t s : e->unused_streams) hipStreamDestroy(s);
     for (hipEvent_t ev : {e->ev_join2, e->ev_vsolved, e->ev_hsolved, e->ev_rast, e->ev_fork, e->ev_join, e->ev_dyn, e->ev_obs, e->ahead_ev[0], e->ahead_ev[1]})
         if (ev) hipEventDestroy(ev);
-    for (int i = 0; i < 4; i++) { if (e->pin_buf[i]) hipHostFree(e->pin_buf[i]); if (e->pin_ev[i]) hipEventDestroy(e->pin_ev[i]); }
-    if (e->h_hcount) hipHostFree(e->h_hcount);
-    if (e->obs_host) hipHostFree(e->obs_host);
-    for (int i = 0; i < 3; i++) if (e->img_host[i]) hipHostFree(e->img_host[i]);
+    for (hipEvent_t ev : e->pin_ev) if (ev) hipEventDestroy(ev);
+    e->mem.release_all();
     delete e;
     return RR_OK;
 }
@@ -605,13 +600,15 @@ static int create_device(rr_env *e, const rr_config &cfg, const Settings &set, H
     HIPCHK(hipSetDevice(cfg.device));
     static_cast<ModelTables &>(*e) = std::move(static_cast<ModelTables &>(M));
     e->set = set;
-    if (hipHostMalloc((void **)&e->h_hcount, 4 * sizeof(int), hipHostMallocMapped) == hipSuccess) { e->h_hcount[0] = 0; e->h_hcount[1] = 0; e->h_hcount[2] = -1; e->h_hcount[3] = 0; } else e->h_hcount = nullptr;
+    e->mem.be = MemBackend{e, hip_mem_alloc, hip_mem_zero, hip_mem_release};
+    if (!e->mem.acquire({mem_part(&e->h_hcount, 4 * sizeof(int), true, MEM_PINNED_MAPPED)})) e->h_hcount[2] = -1;      // (the step runs without the word)
     const SimParams &P = e->P;
     const RenderModel &RM = e->RM;
     const int N = P.N, nt = RM.nt, np = P.npairs;
     DevPtrs &D = e->D;
-#define RRCHK(x) do { const int rc_ = (x); if (rc_ != RR_OK) return rc_; } while (0)
-#define ALLOC(ptr, count) RRCHK(dev_alloc(e, &(ptr), (count)))
+    // (one allocation per buffer, in this order; zeroed unless uploaded over)
+#define ALLOC(ptr, count) RRCHK(mem_get(e, {mem_part(&(ptr), (count) * sizeof *(ptr))}, "rr_create: allocating device memory"))
+#define COPY(ptr, src, count, bytes) do { ALLOC(ptr, count); HIPCHK(hipMemcpy((void *)(ptr), (src), (bytes) ? (bytes) : (count) * sizeof *(ptr), hipMemcpyHostToDevice)); } while (0)      // (bytes 0: the whole array)
     ALLOC(D.state, (size_t)ST_TOTAL * N);
     ALLOC(D.scratch, (size_t)S_TOTAL * N);
     for (int f = 0; f < 2; f++) {
@@ -621,7 +618,7 @@ static int create_device(rr_env *e, const rr_config &cfg, const Settings &set, H
     }
     bind_frames(e);
     ALLOC(D.cforce, (size_t)N * MAXC);
-    RRCHK(dev_copy(e, &D.body_tab, M.body_tab, (size_t)NB * BT_STRIDE));
+    COPY(D.body_tab, M.body_tab, (size_t)NB * BT_STRIDE, 0);
     ALLOC(D.collide_cost, (size_t)N); ALLOC(D.collide_bin, (size_t)N); ALLOC(D.collide_perm, (size_t)8 * ((N + 7) / 8));      // (zeroed: the first order is arbitrary)
     ALLOC(D.ccount_pub, (size_t)N); ALLOC(D.class_pub, (size_t)N);
     if (e->h_hcount && hipHostGetDevicePointer((void **)&D.hcount_host, e->h_hcount, 0) != hipSuccess) D.hcount_host = nullptr;
@@ -652,16 +649,16 @@ static int create_device(rr_env *e, const rr_config &cfg, const Settings &set, H
     ALLOC(e->state_aos, (size_t)N * NSTATE);
     ALLOC(e->mask_dev, (size_t)N);
     ALLOC(e->link_out, (size_t)N * RM.nl * 7);
-    RRCHK(dev_copy(e, &D.tri_pos, M.soa.data(), (size_t)nt * 9));
-    RRCHK(dev_copy(e, &D.tri_rec, M.rec.data(), (size_t)nt * 8));
-    RRCHK(dev_copy(e, &D.tri_inst, M.tri_inst, (size_t)nt));
-    RRCHK(dev_copy(e, &D.tex, M.tex, M.tex_bytes / 4 + 1, M.tex_bytes));
-    RRCHK(dev_copy(e, &D.shapes, &M.S, 1));
+    COPY(D.tri_pos, M.soa.data(), (size_t)nt * 9, 0);
+    COPY(D.tri_rec, M.rec.data(), (size_t)nt * 8, 0);
+    COPY(D.tri_inst, M.tri_inst, (size_t)nt, 0);
+    COPY(D.tex, M.tex, M.tex_bytes / 4 + 1, M.tex_bytes);
+    COPY(D.shapes, &M.S, (size_t)1, 0);
     ALLOC(e->RM_dev, 1);
     HIPCHK(hipMemcpy(e->RM_dev, &e->RM, sizeof e->RM, hipMemcpyHostToDevice));
-    RRCHK(dev_copy(e, &D.cluster_verts, M.cvs.data(), (size_t)nt * 3));
-    RRCHK(dev_copy(e, &D.tri_vidx, M.tv4.data(), (size_t)nt));
-    RRCHK(dev_copy(e, &D.cluster_sphere, M.cluster_sphere, (size_t)nt / 64));
+    COPY(D.cluster_verts, M.cvs.data(), (size_t)nt * 3, 0);
+    COPY(D.tri_vidx, M.tv4.data(), (size_t)nt, 0);
+    COPY(D.cluster_sphere, M.cluster_sphere, (size_t)nt / 64, 0);
     for (int i = 0; i < 2 * RR_NUM_KERNELS; i++) HIPCHK(hipEventCreate(&e->ev[i]));
     {
         // fork / join events order two streams of the same device: no timing, no system-scope fence (the cache writeback
@@ -707,17 +704,17 @@ static int create_device(rr_env *e, const rr_config &cfg, const Settings &set, H
     RRCHK(rr_reset(e, nullptr));
     const size_t spx = (size_t)RM.W * RM.H, items = (size_t)N * RM.ntiles;
     ALLOC(D.static_rgb, spx * 3); ALLOC(D.static_depth, spx); ALLOC(D.static_mask, spx); ALLOC(D.frag_count, items);
-    RRCHK(dev_alloc(e, &D.frag_list, items * TILE_PIX, false));
+    RRCHK(mem_get(e, {mem_part(&D.frag_list, items * TILE_PIX * sizeof *D.frag_list, false)}, "rr_create: allocating the fragment lists"));
     if (set.raster_order && items >= 2048 && items <= (1 << 20) && N < (1 << 24)) {
         ALLOC(D.item_cost, items); ALLOC(D.item_bin, items); ALLOC(e->item_perm, (size_t)8 * ((N + 7) / 8) * RM.ntiles);
     }
     ALLOC(D.static_vis_out, spx);
+#undef COPY
 #undef ALLOC
     e->field_ptr[RR_F_FRAG_COUNT] = D.frag_count;
     e->shared_static_vis = D.static_vis_out; e->shared_static_rgb = D.static_rgb;
     e->shared_static_depth = D.static_depth; e->shared_static_mask = D.static_mask;
     RRCHK(build_static_layer(e));
-#undef RRCHK
     // the 256-thread form of k_solve (heavy solver groups, four per workgroup) and the light envs' solve with an object wave (five
     // waves, sixteen envs) ask for 158 KiB of dynamic LDS: only the heavy / light split launches them, and a device that cannot grant
     // it runs without the split (same results, one launch)
@@ -729,6 +726,7 @@ static int create_device(rr_env *e, const rr_config &cfg, const Settings &set, H
         e->set.split_heavy = false;
     }
     if (hipGetLastError() != hipSuccess) return fail(RR_EDEVICE, "rr_create: device error during set-up");
+    e->created = true;
     return RR_OK;
 }
 
@@ -1121,10 +1119,13 @@ static void state_part_all(rr_env *e, bool overlap) {
 static int pin_acquire(rr_env *e, char **slot, int *idx) {
     const int i = e->pin_next;
     e->pin_next = (i + 1) & 3;
-    if (!e->pin_buf[i]) {
+    if (!e->pin_buf[i]) {          // buffer and event together or neither
         e->pin_bytes = (size_t)e->P.N * 37;
-        HIPCHK(hipHostMalloc((void **)&e->pin_buf[i], e->pin_bytes, hipHostMallocDefault));
-        HIPCHK(hipEventCreateWithFlags(&e->pin_ev[i], hipEventDisableTiming));
+        hipEvent_t ev = nullptr;
+        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        const int rc = mem_get(e, {mem_part(&e->pin_buf[i], e->pin_bytes, false, MEM_PINNED)}, "rr_step: allocating the pinned staging ring");
+        if (rc != RR_OK) { hipEventDestroy(ev); return rc; }
+        e->pin_ev[i] = ev;
     }
     if (e->pin_used[i]) HIPCHK(hipEventSynchronize(e->pin_ev[i]));
     *slot = e->pin_buf[i]; *idx = i;
@@ -1340,24 +1341,14 @@ int rr_apply_image_delta(const uint32_t *records_dev, const uint32_t *totals_dev
     return RR_OK;
 }
 
-// The three buffers of rr_contact_observations (RR_F_CONTACTS, RR_F_BODY_FORCE, RR_F_BODY_PARTNERS): one block, allocated on first
-// use -- by the call or by rr_get_buffer / rr_copy_to_host of one of the fields --, zero-filled on the library's stream, freed with
-// the handle's other allocations (rr_destroy).  A failed allocation leaves the handle as it was.
+// The three buffers of rr_contact_observations (RR_F_CONTACTS, RR_F_BODY_FORCE, RR_F_BODY_PARTNERS): allocated on first use -- by the
+// call or by rr_get_buffer / rr_copy_to_host of one of the fields --, zero-filled.
 static int ensure_contact_obs(rr_env *e) {
     if (e->co_contacts) return RR_OK;
     if (e->RM.nl + NOBJ != RR_CONTACT_ROWS) return fail(RR_EMODEL, "rr_contact_observations: the model's link count + 3 objects is not RR_CONTACT_ROWS");
     HIPCHK(hipSetDevice(e->cfg.device));
-    const size_t bc = e->field_bytes[RR_F_CONTACTS], bf = e->field_bytes[RR_F_BODY_FORCE], bp = e->field_bytes[RR_F_BODY_PARTNERS];
-    static_assert((MAXC * 12 * 4) % 16 == 0 && (RR_CONTACT_ROWS * 2 * 4) % 16 == 0, "the carved buffers stay 16-byte aligned");
-    void *q = nullptr;
-    hipError_t rc = hipMalloc(&q, bc + bf + bp);
-    if (rc == hipSuccess && (rc = hipMemsetAsync(q, 0, bc + bf + bp, e->stream)) != hipSuccess) hipFree(q);
-    if (rc != hipSuccess) {
-        (void)hipGetLastError();          // (not left behind for the next step's launch check)
-        return fail(RR_EDEVICE, std::string("rr_contact_observations: allocating the observation buffers: ") + hipGetErrorString(rc));
-    }
-    e->allocs.push_back(q);
-    e->co_contacts = (float4 *)q; e->co_force = (float2 *)((char *)q + bc); e->co_partners = (unsigned *)((char *)q + bc + bf);
+    RRCHK(mem_get(e, {mem_part(&e->co_contacts, e->field_bytes[RR_F_CONTACTS]), mem_part(&e->co_force, e->field_bytes[RR_F_BODY_FORCE]),
+                      mem_part(&e->co_partners, e->field_bytes[RR_F_BODY_PARTNERS])}, "rr_contact_observations: allocating the observation buffers"));
     e->field_ptr[RR_F_CONTACTS] = e->co_contacts; e->field_ptr[RR_F_BODY_FORCE] = e->co_force; e->field_ptr[RR_F_BODY_PARTNERS] = e->co_partners;
     return RR_OK;
 }
@@ -1540,35 +1531,26 @@ static int fork_bad_index(const int32_t *idx, int N) {
     for (int i = 0; i < N; i++) if (idx[i] < -1 || idx[i] >= N) return i;
     return -1;
 }
-// a device allocation that may fail without harm: the error is not left behind for the next step's launch check
-static int fork_alloc(void **p, size_t bytes, const char *what) {
-    const hipError_t rc = hipMalloc(p, bytes);
-    if (rc == hipSuccess) return RR_OK;
-    (void)hipGetLastError();
-    *p = nullptr;
-    return fail(RR_EDEVICE, std::string(what) + hipGetErrorString(rc));
-}
 
 int rr_snapshot_slots(rr_env *e, int32_t n_slots) {
     if (!e) return fail(RR_EINVAL, "null env");
     if (n_slots < 0 || n_slots > RR_MAX_SLOTS) return fail(RR_EINVAL, "rr_snapshot_slots: n_slots " + std::to_string(n_slots) + " is not in [0, " + std::to_string(RR_MAX_SLOTS) + "]");
     HIPCHK(hipSetDevice(e->cfg.device));
     const size_t N = e->P.N, sb = fork_slot_bytes(N);
-    void *blk = nullptr;
+    char *blk = nullptr;
     if (n_slots > 0) {
         // the new slots exist before the old ones are given up; every one starts as a copy of the running envs
-        const int rc = fork_alloc(&blk, (size_t)n_slots * sb, "rr_snapshot_slots: allocating the slots: ");
-        if (rc != RR_OK) return rc;
+        RRCHK(mem_get(e, {mem_part(&blk, (size_t)n_slots * sb, false)}, "rr_snapshot_slots: allocating the slots"));
         const ForkRec live = fork_rec_live(e);
-        for (int k = 0; k < n_slots; k++) launch_fork(e, live, fork_rec_at((char *)blk + (size_t)k * sb, N), nullptr, 0, 0xffffffffu);
+        for (int k = 0; k < n_slots; k++) launch_fork(e, live, fork_rec_at(blk + (size_t)k * sb, N), nullptr, 0, 0xffffffffu);
         const hipError_t lrc = hipGetLastError();
-        if (lrc != hipSuccess) { (void)hipStreamSynchronize(e->stream); hipFree(blk); return fail(RR_EDEVICE, std::string("rr_snapshot_slots: ") + hipGetErrorString(lrc)); }
+        if (lrc != hipSuccess) { (void)hipStreamSynchronize(e->stream); e->mem.release(blk); return fail(RR_EDEVICE, std::string("rr_snapshot_slots: ") + hipGetErrorString(lrc)); }
     }
     if (e->snap) {
         HIPCHK(hipStreamSynchronize(e->stream));      // (ends every queued copy that reads or writes the old slots)
-        hipFree(e->snap);
+        e->mem.release(e->snap);
     }
-    e->snap = (char *)blk; e->n_slots = n_slots;
+    e->snap = blk; e->n_slots = n_slots;
     return RR_OK;
 }
 
@@ -1590,20 +1572,10 @@ int rr_copy_envs(rr_env *e, int32_t src_slot, int32_t dst_slot, const int32_t *s
     HIPCHK(hipSetDevice(e->cfg.device));
     // whatever has to be allocated is allocated before anything is launched: a failure leaves the handle as it was
     const bool staged = src_slot == dst_slot;                  // (with an index: the map may read envs that it also writes)
-    if (staged && !e->fork_stage) {
-        void *q = nullptr;
-        const int rc = fork_alloc(&q, fork_slot_bytes(N), "rr_copy_envs: allocating the staging slot: ");
-        if (rc != RR_OK) return rc;
-        e->allocs.push_back(q); e->fork_stage = (char *)q;
-    }
+    if (staged && !e->fork_stage) RRCHK(mem_get(e, {mem_part(&e->fork_stage, fork_slot_bytes(N), false)}, "rr_copy_envs: allocating the staging slot"));
     const int *idx_dev = src_index;
     if (host_index) {
-        if (!e->fork_index) {
-            void *q = nullptr;
-            const int rc = fork_alloc(&q, (size_t)N * 4, "rr_copy_envs: allocating the index staging: ");
-            if (rc != RR_OK) return rc;
-            e->allocs.push_back(q); e->fork_index = (int *)q;
-        }
+        if (!e->fork_index) RRCHK(mem_get(e, {mem_part(&e->fork_index, (size_t)N * 4, false)}, "rr_copy_envs: allocating the index staging"));
         // through the pinned ring, as rr_step's commands: the caller may reuse its array at once and nobody waits for the device
         char *pin = nullptr; int pin_idx = -1;
         const int rc = pin_acquire(e, &pin, &pin_idx);
@@ -1720,9 +1692,8 @@ int rr_map_observations(rr_env *e, void **host_ptr, size_t *bytes) {
     const size_t nb = 4 * (N * 9 + N * 4 + N * nobj * 7 + N + N);
     if (!e->obs_host) {
         void *h = nullptr, *d = nullptr;
-        HIPCHK(hipHostMalloc(&h, nb, hipHostMallocMapped));
-        memset(h, 0, nb);
-        if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) { hipHostFree(h); (void)hipGetLastError(); return fail(RR_EDEVICE, "rr_map_observations: pinned host memory is not device-mapped on this system"); }
+        RRCHK(mem_get(e, {mem_part(&h, nb, true, MEM_PINNED_MAPPED)}, "rr_map_observations: allocating the mapped block"));
+        if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) { e->mem.release(h); (void)hipGetLastError(); return fail(RR_EDEVICE, "rr_map_observations: pinned host memory is not device-mapped on this system"); }
         float *f = (float *)d;
         e->obs_dev.joints = f; e->obs_dev.touch = f + N * 9; e->obs_dev.objpose = f + N * 13;
         e->obs_dev.timestep = (int *)(f + N * (13 + nobj * 7)); e->obs_dev.errflags = (unsigned *)(f + N * (14 + nobj * 7));
@@ -1754,7 +1725,7 @@ int rr_map_images(rr_env *e, void **rgb_host, void **depth_host, void **mask_hos
         if (!out[i]) continue;
         if (!e->field_ptr[f[i]]) return fail(RR_EINVAL, "rr_map_images: field not available (RR_FLAG_NO_MASK)");
         if (!e->img_host[i]) {
-            HIPCHK(hipHostMalloc(&e->img_host[i], e->field_bytes[f[i]], hipHostMallocDefault));
+            RRCHK(mem_get(e, {mem_part(&e->img_host[i], e->field_bytes[f[i]], false, MEM_PINNED)}, "rr_map_images: allocating the pinned copy"));
             HIPCHK(hipMemcpyAsync(e->img_host[i], e->field_ptr[f[i]], e->field_bytes[f[i]], hipMemcpyDeviceToHost, e->stream));
         }
         *out[i] = e->img_host[i];
@@ -1827,8 +1798,7 @@ int rr_evaluate_goals(rr_env *e, const float *goal_pos_host, const uint8_t *goal
     if (!e || !goal_pos_host || !score_out_host) return fail(RR_EINVAL, "null argument");
     HIPCHK(hipSetDevice(e->cfg.device));
     const size_t N = e->P.N, nobj = e->P.nobj;
-    int rc;
-    if (!e->score_out && ((rc = dev_alloc(e, &e->score_out, N)) != RR_OK || (rc = dev_alloc(e, &e->score_mask, N * NOBJ)) != RR_OK)) return rc;
+    if (!e->score_out) RRCHK(mem_get(e, {mem_part(&e->score_out, N * 4), mem_part(&e->score_mask, N * NOBJ)}, "rr_evaluate_goals: allocating the score buffers"));
     static_assert(NSTATE >= NOBJ * 3, "the state staging buffer doubles as goal-position staging");
     HIPCHK(hipMemcpyAsync(e->state_aos, goal_pos_host, N * nobj * 12, hipMemcpyHostToDevice, e->stream));
     if (goal_mask_host) HIPCHK(hipMemcpyAsync(e->score_mask, goal_mask_host, N * nobj, hipMemcpyHostToDevice, e->stream));
@@ -1839,22 +1809,17 @@ int rr_evaluate_goals(rr_env *e, const float *goal_pos_host, const uint8_t *goal
     return RR_OK;
 }
 
-static int ensure_plan_buffers(rr_env *e) {
+static int ensure_plan_buffers(rr_env *e, const char *who) {
     if (e->plan) return RR_OK;
-    int rc;
     const size_t N = e->P.N;
-    if ((rc = dev_alloc(e, &e->plan, N * PLAN_LEN * 9)) != RR_OK) return rc;
-    if ((rc = dev_alloc(e, &e->plan_step, N)) != RR_OK) return rc;
-    if ((rc = dev_alloc(e, &e->ik_in, N * 7)) != RR_OK) return rc;
-    if ((rc = dev_alloc(e, &e->ik_out, N * 11)) != RR_OK) return rc;
-    if ((rc = dev_alloc(e, &e->ik_err, N)) != RR_OK) return rc;
-    return RR_OK;
+    return mem_get(e, {mem_part(&e->plan, N * PLAN_LEN * 36), mem_part(&e->plan_step, N * 4), mem_part(&e->ik_in, N * 28), mem_part(&e->ik_out, N * 44),
+                       mem_part(&e->ik_err, N * 4)}, who);
 }
 
 int rr_ik(rr_env *e, const float *targets_host, float *q_out_host, float *err_out_host) {
     if (!e || !targets_host || !q_out_host) return fail(RR_EINVAL, "null argument");
     HIPCHK(hipSetDevice(e->cfg.device));
-    int rc = ensure_plan_buffers(e);
+    int rc = ensure_plan_buffers(e, "rr_ik: allocating the plan and IK buffers");
     if (rc != RR_OK) return rc;
     const int N = e->P.N;
     HIPCHK(hipMemcpyAsync(e->ik_in, targets_host, (size_t)N * 28, hipMemcpyHostToDevice, e->stream));
@@ -1869,7 +1834,7 @@ int rr_ik(rr_env *e, const float *targets_host, float *q_out_host, float *err_ou
 int rr_plan_macro(rr_env *e, const float *macro_host, const uint8_t *env_mask_host) {
     if (!e || !macro_host) return fail(RR_EINVAL, "null argument");
     HIPCHK(hipSetDevice(e->cfg.device));
-    int rc = ensure_plan_buffers(e);
+    int rc = ensure_plan_buffers(e, "rr_plan_macro: allocating the plan and IK buffers");
     if (rc != RR_OK) return rc;
     const int N = e->P.N;
     // the macro targets travel through the (otherwise idle) ik_out staging buffer: [N][4]
@@ -1913,17 +1878,13 @@ int rr_step_plan(rr_env *e, int32_t render_mode, const uint8_t *render_flags_hos
 // paint them -- and share one mode: the buffers below (19 bytes per pixel per env, allocated by whichever call comes first), a
 // camera record per env (the handle's camera for every env while only the appearance is per env), and one rebuild.  The handle
 // remembers which of the two settings is in force (cam_per_env, app_per_env); the mode lasts while either holds.
-static int ensure_env_layers(rr_env *e) {
+static int ensure_env_layers(rr_env *e, const char *who) {
     if (e->cam_dev) return RR_OK;
     const int N = e->P.N, CF = cam_floats(e->RM.ntiles);
     const size_t px = (size_t)e->RM.W * e->RM.H;
-    int rc;
-    if ((rc = dev_alloc(e, &e->cam_dev, (size_t)N * CF)) != RR_OK || (rc = dev_alloc(e, &e->cam_sel, (size_t)N)) != RR_OK ||
-        (rc = dev_alloc(e, &e->env_static_vis, (size_t)N * px, false)) != RR_OK || (rc = dev_alloc(e, &e->env_static_rgb, (size_t)N * px * 3, false)) != RR_OK ||
-        (rc = dev_alloc(e, &e->env_static_depth, (size_t)N * px, false)) != RR_OK || (rc = dev_alloc(e, &e->env_static_mask, (size_t)N * px, false)) != RR_OK) {
-        e->cam_dev = nullptr;          // (what was allocated stays on the handle's list until rr_destroy; a later call allocates again)
-        return rc;
-    }
+    RRCHK(mem_get(e, {mem_part(&e->cam_dev, (size_t)N * CF * 4), mem_part(&e->cam_sel, (size_t)N * 4),
+                      mem_part(&e->env_static_vis, N * px * 8, false), mem_part(&e->env_static_rgb, N * px * 3, false),
+                      mem_part(&e->env_static_depth, N * px * 4, false), mem_part(&e->env_static_mask, N * px * 4, false)}, who));
     e->cam_host.assign((size_t)N * CF, 0.0f);
     return RR_OK;
 }
@@ -2031,7 +1992,7 @@ int rr_set_env_cameras(rr_env *e, const float *views16, const float *projs16, co
     const RenderModel &RM = e->RM;
     const int CF = cam_floats(RM.ntiles);
     int rc;
-    if ((rc = ensure_env_layers(e)) != RR_OK || (rc = enter_env_layers(e)) != RR_OK) return rc;
+    if ((rc = ensure_env_layers(e, "rr_set_env_cameras: allocating the per-env static layers")) != RR_OK || (rc = enter_env_layers(e)) != RR_OK) return rc;
     e->cam_per_env = true;
     for (int i = 0; i < N; i++) {
         if (env_mask_host && !env_mask_host[i]) continue;
@@ -2096,13 +2057,11 @@ int rr_set_env_appearance(rr_env *e, const float *colours, const float *light_di
         return build_static_layer(e);
     }
     if (!e->colour_dev) {
-        if ((rc = dev_alloc(e, &e->colour_dev, (size_t)N * MAXINST * 3, false)) != RR_OK || (rc = dev_alloc(e, &e->light_dev, (size_t)N * 4, false)) != RR_OK) {
-            e->colour_dev = nullptr;
-            return rc;
-        }
+        RRCHK(mem_get(e, {mem_part(&e->colour_dev, (size_t)N * MAXINST * 12, false), mem_part(&e->light_dev, (size_t)N * 16, false)},
+                      "rr_set_env_appearance: allocating the appearance tables"));
         default_appearance(e);
     }
-    if ((rc = ensure_env_layers(e)) != RR_OK || (rc = enter_env_layers(e)) != RR_OK) return rc;
+    if ((rc = ensure_env_layers(e, "rr_set_env_appearance: allocating the per-env static layers")) != RR_OK || (rc = enter_env_layers(e)) != RR_OK) return rc;
     e->app_per_env = true;
     for (int i = 0; i < N; i++) {
         if (env_mask_host && !env_mask_host[i]) continue;
@@ -2165,37 +2124,23 @@ static void launch_env_goals(rr_env *e, const int *index_dev, const unsigned cha
     launch_goal_image(e);
 }
 
-// The episode record: one block, allocated on first use, zero-filled, every env without a goal (index -1, RR_EP_GOAL_POS all NaN).
-// A failed allocation leaves the handle as it was (as ensure_contact_obs).
+// The episode record: allocated on first use, zero-filled, every env without a goal (index -1, RR_EP_GOAL_POS all NaN).
 static int ensure_episode(rr_env *e) {
     if (e->ep.score) return RR_OK;
     HIPCHK(hipSetDevice(e->cfg.device));
     const size_t N = e->P.N, nobj = e->P.nobj;
-    static_assert(RR_EP_GOAL_RGB == RR_EP_COUNT - 1, "the image buffer is the last one and not part of the block");
+    static_assert(RR_EP_GOAL_RGB == RR_EP_COUNT - 1, "the image buffer is the last one and not part of the record");
     size_t *b = e->ep_bytes;
     b[RR_EP_SCORE] = b[RR_EP_REWARD] = b[RR_EP_DONE] = b[RR_EP_GOAL_INDEX] = b[RR_EP_EPISODE] = N * 4;
     b[RR_EP_FINAL_OBS] = N * (13 + 7 * nobj + 1) * 4;
     b[RR_EP_GOAL_POS] = N * nobj * 12;
     b[RR_EP_GOAL_RGB] = N * image_bytes(e);
-    auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    size_t total = 0;
-    for (int i = 0; i < RR_EP_GOAL_RGB; i++) total += up(b[i]);
-    total += 3 * up(N * 4);                     // previous score, index staging, "goal changed" bytes
-    void *q = nullptr;
-    hipError_t rc = hipMalloc(&q, total);
-    if (rc == hipSuccess && (rc = hipMemsetAsync(q, 0, total, e->stream)) != hipSuccess) hipFree(q);
-    if (rc != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(RR_EDEVICE, std::string("rr_episode: allocating the episode record: ") + hipGetErrorString(rc));
-    }
-    e->allocs.push_back(q);
-    char *p = (char *)q;
-    auto take = [&](size_t bytes) { char *r = p; p += up(bytes); return r; };
     EpisodeRec &E = e->ep;
-    E.score = (float *)take(b[RR_EP_SCORE]); E.reward = (float *)take(b[RR_EP_REWARD]); E.done = (unsigned *)take(b[RR_EP_DONE]);
-    E.goal_index = (int *)take(b[RR_EP_GOAL_INDEX]); E.episode = (int *)take(b[RR_EP_EPISODE]);
-    E.final_obs = (float *)take(b[RR_EP_FINAL_OBS]); E.goal_pos = (float *)take(b[RR_EP_GOAL_POS]);
-    E.prev = (float *)take(N * 4); e->ep_index_stage = (int *)take(N * 4); E.changed = (unsigned char *)take(N * 4);
+    RRCHK(mem_get(e, {mem_part(&E.score, b[RR_EP_SCORE]), mem_part(&E.reward, b[RR_EP_REWARD]), mem_part(&E.done, b[RR_EP_DONE]),
+                      mem_part(&E.goal_index, b[RR_EP_GOAL_INDEX]), mem_part(&E.episode, b[RR_EP_EPISODE]),
+                      mem_part(&E.final_obs, b[RR_EP_FINAL_OBS]), mem_part(&E.goal_pos, b[RR_EP_GOAL_POS]),
+                      mem_part(&E.prev, N * 4), mem_part(&e->ep_index_stage, N * 4), mem_part(&E.changed, N * 4)},      // previous score, index staging, "goal changed" bytes
+                  "rr_episode: allocating the episode record"));
     launch_env_goals(e, nullptr, nullptr);
     HIPCHK(hipGetLastError());
     return RR_OK;
@@ -2217,38 +2162,35 @@ int rr_set_goals(rr_env *e, int32_t n_goals, const float *start_poses, const flo
     HIPCHK(hipSetDevice(e->cfg.device));
     const bool images = G > 0 && goal_rgb != nullptr;
     // everything the new table needs is allocated before anything of the old one is given up
-    auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t bs = up(G * nobj * 28), bf = up(G * nobj * 12), bfl = up(G * nobj);
-    void *blk = nullptr, *rgb = nullptr, *env_rgb = nullptr;
+    GoalTable T = {};
+    unsigned char *rgb = nullptr, *env_rgb = nullptr;
+    MemPart parts[5];
+    size_t np = 0;
+    if (G > 0) { parts[np++] = mem_part(&T.start, G * nobj * 28, false); parts[np++] = mem_part(&T.final_pos, G * nobj * 12, false); parts[np++] = mem_part(&T.flags, G * nobj, false); }
+    if (images) parts[np++] = mem_part(&rgb, G * B, false);
+    if (images && !e->ep_goal_rgb) parts[np++] = mem_part(&env_rgb, (size_t)e->P.N * B);
+    const char *err = e->mem.acquire(parts, np);
+    if (err) return fail(RR_EDEVICE, std::string("rr_set_goals: allocating the goal table: ") + err);
+    T.G = (int)G;
     hipError_t hrc = hipSuccess;
-    if (G > 0) hrc = hipMalloc(&blk, bs + bf + bfl);
-    if (hrc == hipSuccess && images) hrc = hipMalloc(&rgb, G * B);
-    if (hrc == hipSuccess && images && !e->ep_goal_rgb) {
-        hrc = hipMalloc(&env_rgb, (size_t)e->P.N * B);
-        if (hrc == hipSuccess) hrc = hipMemsetAsync(env_rgb, 0, (size_t)e->P.N * B, e->stream);
-    }
-    if (hrc == hipSuccess && G > 0) {
-        hrc = hipMemcpyAsync(blk, start_poses, G * nobj * 28, hipMemcpyHostToDevice, e->stream);
-        if (hrc == hipSuccess) hrc = hipMemcpyAsync((char *)blk + bs, final_pos, G * nobj * 12, hipMemcpyHostToDevice, e->stream);
-        if (hrc == hipSuccess) hrc = hipMemcpyAsync((char *)blk + bs + bf, flags, G * nobj, hipMemcpyHostToDevice, e->stream);
+    if (G > 0) {
+        hrc = hipMemcpyAsync((void *)T.start, start_poses, G * nobj * 28, hipMemcpyHostToDevice, e->stream);
+        if (hrc == hipSuccess) hrc = hipMemcpyAsync((void *)T.final_pos, final_pos, G * nobj * 12, hipMemcpyHostToDevice, e->stream);
+        if (hrc == hipSuccess) hrc = hipMemcpyAsync((void *)T.flags, flags, G * nobj, hipMemcpyHostToDevice, e->stream);
         if (hrc == hipSuccess && images) hrc = hipMemcpyAsync(rgb, goal_rgb, G * B, hipMemcpyHostToDevice, e->stream);
     }
     // (the wait also ends every queued kernel that reads the old table)
     if (hrc == hipSuccess) hrc = hipStreamSynchronize(e->stream);
     if (hrc != hipSuccess) {
         (void)hipStreamSynchronize(e->stream);
-        for (void *p : {blk, rgb, env_rgb}) if (p) hipFree(p);
+        e->mem.release(T.start); e->mem.release(T.final_pos); e->mem.release(T.flags); e->mem.release(rgb); e->mem.release(env_rgb);
         (void)hipGetLastError();
-        return fail(RR_EDEVICE, std::string("rr_set_goals: allocating / uploading the goal table: ") + hipGetErrorString(hrc));
+        return fail(RR_EDEVICE, std::string("rr_set_goals: uploading the goal table: ") + hipGetErrorString(hrc));
     }
-    if (e->goals_block) hipFree(e->goals_block);
-    if (e->goals_rgb) hipFree(e->goals_rgb);
-    e->goals_block = blk; e->goals_rgb = (unsigned char *)rgb;
-    e->goals.G = (int)G;
-    e->goals.start = (const float *)blk; e->goals.final_pos = (const float *)((char *)blk + bs); e->goals.flags = (const unsigned char *)blk + bs + bf;
-    if (!G) e->goals = GoalTable{};
-    if (env_rgb) e->ep_goal_rgb = (unsigned char *)env_rgb;
-    else if (!images && e->ep_goal_rgb) { hipFree(e->ep_goal_rgb); e->ep_goal_rgb = nullptr; }
+    e->mem.release(e->goals.start); e->mem.release(e->goals.final_pos); e->mem.release(e->goals.flags); e->mem.release(e->goals_rgb);
+    e->goals = T; e->goals_rgb = rgb;
+    if (env_rgb) e->ep_goal_rgb = env_rgb;
+    else if (!images) e->mem.release(e->ep_goal_rgb);
     // indices into the old table mean nothing in the new one: every env is without a goal until rr_set_env_goals
     launch_env_goals(e, nullptr, nullptr);
     HIPCHK(hipGetLastError());
