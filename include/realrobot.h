@@ -33,13 +33,14 @@ extern "C" {
                               rr_get_env_actuators (per-env motor gains, motor force and joint damping; checkpoint header version 5 carries them); rr_contact_observations;
                               rr_set_goals, rr_set_env_goals, rr_set_episode, rr_episode_update, rr_episode_buffer (goal table and episode
                               record on the device; checkpoints do not carry them); rr_snapshot_slots, rr_copy_envs (env forks and
-                              snapshot slots on the device) */
+                              snapshot slots on the device); rr_set_kinematic_points, rr_get_kinematic_points, rr_kinematic_observations,
+                              rr_kinematic_buffer, rr_kinematic_copy_to_host (link states and Jacobians of the whole batch) */
 
 enum {
     RR_OK = 0,
     RR_EINVAL = -1,     /* bad argument */
     RR_EDEVICE = -2,    /* HIP runtime error (no GPU, out of memory, launch failure).  Memory that a call allocates on first use
-                           (contact observations, goal scores, plans and IK, per-env cameras and appearance, goal table and episode
+                           (contact and kinematic observations, goal scores, plans and IK, per-env cameras and appearance, goal table and episode
                            record, snapshot slots and fork staging, mapped host blocks, the staging ring) is allocated all or nothing:
                            when that fails the call returns RR_EDEVICE, nothing has changed -- what the call would replace is kept --
                            and the handle stays usable; a later call tries again. */
@@ -445,6 +446,63 @@ int rr_episode_update(rr_env *env, int32_t reset_done);
 int rr_episode_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
 /* Synchronising copy of a whole RR_EP_* buffer to host memory (rr_copy_to_host for the episode record). */
 int rr_episode_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
+
+/* ---- Kinematic observations on the device (additive in ABI 7) ----------------------------------------------------------------------
+ * Replaces pybullet's getJointState(s) velocity, getLinkState(computeLinkVelocity=1), getBaseVelocity and calculateJacobian(body,
+ * link, localPosition, ...) for ALL envs at once and on the device: one launch on the library's stream (rr_kinematic_observations)
+ * turns the present state into seven device buffers.  They are NOT fields of rr_get_buffer (RR_F_COUNT stays 16): they have this
+ * enum and rr_kinematic_buffer, like the episode record. */
+enum {
+    RR_KIN_JOINT_VEL = 0,  /* f32 [N, 11]        qd, the order of q[11] in RR_F_STATE                          getJointState(s)[1] */
+    RR_KIN_LINK_POSE = 1,  /* f32 [N, 17, 7]     the rows of rr_link_poses (COM frame, xyz + xyzw)             getLinkState[0:2]   */
+    RR_KIN_LINK_VEL = 2,   /* f32 [N, 17, 6]     world linear velocity of that frame's origin, then angular    getLinkState[6:8]   */
+    RR_KIN_OBJ_VEL = 3,    /* f32 [N, n_obj, 6]  linear, angular                                               getBaseVelocity     */
+    RR_KIN_POINT_POS = 4,  /* f32 [N, P, 3]      world position of every point in force                                            */
+    RR_KIN_POINT_VEL = 5,  /* f32 [N, P, 6]      its world linear velocity, its link's angular velocity                            */
+    RR_KIN_JACOBIAN = 6,   /* f32 [N, P, 6, 11]  rows: linear xyz, angular xyz; columns: q[11]                 calculateJacobian   */
+    RR_KIN_COUNT = 7
+};
+#define RR_KIN_MAX_POINTS 8
+/* The points of RR_KIN_POINT_POS / RR_KIN_POINT_VEL / RR_KIN_JACOBIAN: point j is (link[j], local_pos[j]) -- a URDF link id in
+ * [0, 17), the order of rr_link_poses and data/realrobot_model_links.txt, and a position in that link's COM frame (pybullet's
+ * localPosition; local_pos f32 [P][3] host, NULL: zeros).  Its world position is x = p_link + R_link local_pos.  A fresh handle
+ * has ONE point: link 8 (gripper `base`, the link rr_ik solves for) at (0, 0, 0).  n_points outside [1, RR_KIN_MAX_POINTS], a
+ * link out of range or a local_pos that is not finite returns RR_EINVAL -- the message names the point -- and the points in force
+ * stay as they are.  The points are a setting of the handle, like the cameras: rr_reset, rr_set_state, rr_copy_envs and
+ * rr_checkpoint_restore keep them and checkpoints do not carry them.  Synchronous (it waits for the library's stream: an
+ * observation call enqueued earlier still sees the earlier points) and launches nothing; after a change the three point buffers
+ * hold unspecified data until the next rr_kinematic_observations. */
+int rr_set_kinematic_points(rr_env *env, int32_t n_points, const int32_t *link, const float *local_pos);
+/* The points in force: *n_points, link_out i32 [P], local_pos_out f32 [P][3] (room for RR_KIN_MAX_POINTS); each output may be NULL. */
+int rr_get_kinematic_points(rr_env *env, int32_t *n_points, int32_t *link_out, float *local_pos_out);
+/* One launch on the library's stream turns the PRESENT state -- whatever the last step, reset, rr_set_state, rr_set_object_pose(s),
+ * rr_copy_envs or restore left -- into the seven buffers; the call checks the launch and returns without waiting.  It reads the
+ * state (joint positions and velocities, object velocities), the model and the points, and writes the seven buffers only: not the
+ * preparation record (RR_F_PREP: after an outside change of state that describes an older state), no error flag; the next step
+ * stays prepared and no later step is affected.  The buffers hold what the LAST CALL computed: steps do not refresh them.
+ * For link l on moving body b with COM-frame origin x, over the joints k that move b (b and its ancestors), with world joint axis
+ * a_k and joint position p_k:   v = sum_k qd_k a_k x (x - p_k),   w = sum_k qd_k a_k;   a point takes its own x.  Column k of a
+ * point's Jacobian is [a_k x (x - p_k); a_k] for such a k and +0.0 in all six rows otherwise.  Link 0 is rigid with the world: its
+ * velocity row, and the velocity and every Jacobian column of a point on it, are +0.0.  Plain float32 arithmetic on the frames of
+ * the step's own forward kinematics; RR_KIN_LINK_POSE is the expression of rr_link_poses.  RR_KIN_JOINT_VEL and RR_KIN_OBJ_VEL are
+ * the floats of RR_F_STATE, bit for bit: its columns 11..21, and per object the six behind pos3 quat4.  An env whose state is not
+ * finite (error flag 1) is computed like any other: its rows may be non-finite.
+ * The Jacobian's columns are the eleven joints as INDEPENDENT coordinates.  The nine command entries drive them as Kuka.apply_action
+ * does (robot.py:188-201): command c < 7 drives q[c]; command 7 drives q[7] and q[9]; command 8 drives -q[8] and -q[10].  With that
+ * [11, 9] matrix Q, dq = Q dcmd and the Jacobian over the commands is J Q.
+ * All seven buffers are allocated on first use -- by this call, or by rr_kinematic_buffer / rr_kinematic_copy_to_host --, all or
+ * nothing, zero-filled, and valid until rr_destroy.  The three point buffers are allocated once for RR_KIN_MAX_POINTS points, so
+ * no pointer ever changes; their layout is compact [N, P, ...] for the P in force, and `bytes` reports that size.
+ * STREAM CONTRACT as for the other zero-copy views (rr_step, rr_contact_observations): the kernel runs on the library's stream behind
+ * the work enqueued before it; readers on another stream order themselves after the call (event / rr_sync), and a later call
+ * rewrites the buffers in place.
+ * Out of scope: mass matrix, bias and gravity terms (the motors are position controlled: nothing here would consume them), Jacobian
+ * time derivatives, URDF link frames (COM frames only, as rr_link_poses), points on objects, refreshing from inside a step. */
+int rr_kinematic_observations(rr_env *env);
+/* Zero-copy device pointer + size in bytes of an RR_KIN_* buffer (read-only for the caller); which outside [0, RR_KIN_COUNT): RR_EINVAL. */
+int rr_kinematic_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
+/* Synchronising copy of a whole RR_KIN_* buffer (its `bytes`) to host memory. */
+int rr_kinematic_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
 
 /* Batched damped-least-squares inverse kinematics for link 7 (gripper `base`), seeded with each env's current joints.
  * Replaces pybullet.calculateInverseKinematics(0, 7, pos, orn, maxNumIterations=1000, residualThreshold=0.001) in

@@ -37,7 +37,8 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_set_env_cameras', 'rr_set_env_appearance', 'rr_get_env_appearance', 'rr_render_instances',
            'rr_set_env_actuators', 'rr_get_env_actuators', 'rr_contact_observations',
            'rr_set_goals', 'rr_set_env_goals', 'rr_set_episode', 'rr_episode_update', 'rr_episode_buffer', 'rr_episode_copy_to_host',
-           'rr_snapshot_slots', 'rr_copy_envs')
+           'rr_snapshot_slots', 'rr_copy_envs',
+           'rr_set_kinematic_points', 'rr_get_kinematic_points', 'rr_kinematic_observations', 'rr_kinematic_buffer', 'rr_kinematic_copy_to_host')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
@@ -47,6 +48,17 @@ N_JOINTS = 11
 (EP_SCORE, EP_REWARD, EP_DONE, EP_GOAL_INDEX, EP_EPISODE, EP_FINAL_OBS, EP_GOAL_POS, EP_GOAL_RGB) = range(8)
 EP_NAMES = ('score', 'reward', 'done', 'goal_index', 'episode', 'final_obs', 'goal_pos', 'goal_rgb')
 GOAL_SCORED, GOAL_HAS_START = 1, 2      # rr_set_goals flag bits: the object counts in the score / has a start pose
+# buffers of rr_kinematic_buffer (the RR_KIN_* enum), per env: joint_vel [11], link_pose [17, 7], link_vel [17, 6], obj_vel [n_obj, 6],
+# point_pos [P, 3], point_vel [P, 6], jacobian [P, 6, 11] for the P points in force (rr_set_kinematic_points)
+KIN_FIELDS = ('joint_vel', 'link_pose', 'link_vel', 'obj_vel', 'point_pos', 'point_vel', 'jacobian')
+KIN_MAX_POINTS = 8
+EE_LINK = 8                             # URDF link id of gripper `base`: the default point, the link rr_ik solves for
+# dq = Q_FROM_CMD @ dcmd: how the nine command entries drive the eleven joints (Kuka.apply_action, robot.py:188-201: command 7
+# drives q[7] and q[9], command 8 drives -q[8] and -q[10]); the Jacobian over the commands is J @ Q_FROM_CMD
+Q_FROM_CMD = np.zeros((N_JOINTS, 9), np.float32)
+Q_FROM_CMD[np.arange(7), np.arange(7)] = 1.0
+Q_FROM_CMD[[7, 9], 7] = 1.0
+Q_FROM_CMD[[8, 10], 8] = -1.0
 SLOT_LIVE, MAX_SLOTS = -1, 64           # RR_SLOT_LIVE: the running envs as a slot number of rr_copy_envs; RR_MAX_SLOTS
 
 
@@ -168,6 +180,11 @@ def load_library():
     L.rr_episode_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_snapshot_slots.argtypes = [vp, i32]
     L.rr_copy_envs.argtypes = [vp, i32, i32, vp, i32]
+    L.rr_set_kinematic_points.argtypes = [vp, i32, vp, vp]
+    L.rr_get_kinematic_points.argtypes = [vp, C.POINTER(i32), vp, vp]
+    L.rr_kinematic_observations.argtypes = [vp]
+    L.rr_kinematic_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rr_kinematic_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]

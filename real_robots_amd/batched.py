@@ -542,6 +542,85 @@ class BatchedREALRobotEnv:
         return {'contacts': get(nat.F_CONTACTS), 'count': get(nat.F_CONTACT_COUNT), 'body_force': get(nat.F_BODY_FORCE),
                 'body_partners': get(nat.F_BODY_PARTNERS)}
 
+    # ------------------------------------------------------------------ kinematic observations
+    @staticmethod
+    def _kinematic_points_arg(links, local_pos=None):
+        """(links, local_pos) of `set_kinematic_points` -> (int32 [P], float32 [P, 3]); every argument error is a ValueError raised
+        here, before the native call."""
+        if isinstance(links, (str, int, np.integer)):
+            links = [links]
+        idx = []
+        for l in links:
+            if isinstance(l, str):
+                if l not in nat.LINK_NAMES:
+                    raise ValueError("unknown link %r (known: %s)" % (l, ', '.join(nat.LINK_NAMES)))
+                l = nat.LINK_NAMES.index(l)
+            elif not isinstance(l, (int, np.integer)) or isinstance(l, (bool, np.bool_)):
+                raise ValueError("a link is a name of LINK_NAMES or an index, not %r" % (l,))
+            if not 0 <= int(l) < len(nat.LINK_NAMES):
+                raise ValueError("link index %d is not in [0, %d)" % (int(l), len(nat.LINK_NAMES)))
+            idx.append(int(l))
+        if not 1 <= len(idx) <= nat.KIN_MAX_POINTS:
+            raise ValueError("%d points: between 1 and %d are allowed" % (len(idx), nat.KIN_MAX_POINTS))
+        if local_pos is None:
+            loc = np.zeros((len(idx), 3), np.float32)
+        else:
+            with np.errstate(over='ignore'):
+                loc = np.ascontiguousarray(np.asarray(local_pos, dtype=np.float64).astype(np.float32))
+            if loc.shape != (len(idx), 3):
+                raise ValueError("local_pos must have shape (%d, 3), not %s" % (len(idx), loc.shape))
+            if not np.isfinite(loc).all():
+                raise ValueError("local_pos must be finite (in float32)")
+        return np.array(idx, np.int32), loc
+
+    def set_kinematic_points(self, links, local_pos=None):
+        """The points of `kinematic_observations` (rr_set_kinematic_points): up to 8 pairs of a robot link -- a name of
+        `_native.LINK_NAMES` or its index -- and a position [P, 3] in that link's COM frame (pybullet's localPosition; None: the
+        frame's origin).  A fresh env has one point, the gripper base (`_native.EE_LINK`) at its origin.  A setting of the env,
+        like the cameras: resets, `state`, forks and `restore` keep it."""
+        idx, loc = self._kinematic_points_arg(links, local_pos)
+        nat.check(self.L.rr_set_kinematic_points(self.h, len(idx), idx.ctypes.data, loc.ctypes.data))
+
+    def kinematic_points(self):
+        """(links int32 [P], local_pos float32 [P, 3]) in force (rr_get_kinematic_points)."""
+        n = C.c_int32()
+        idx, loc = np.zeros(nat.KIN_MAX_POINTS, np.int32), np.zeros((nat.KIN_MAX_POINTS, 3), np.float32)
+        nat.check(self.L.rr_get_kinematic_points(self.h, C.byref(n), idx.ctypes.data, loc.ctypes.data))
+        return idx[:n.value].copy(), loc[:n.value].copy()
+
+    def _kinematic_shape(self, which, P):
+        N = self.N
+        return ((N, 11), (N, len(nat.LINK_NAMES), 7), (N, len(nat.LINK_NAMES), 6), (N, self.n_objects, 6), (N, P, 3), (N, P, 6),
+                (N, P, 6, 11))[which]
+
+    def kinematic_buffer(self, name, host=False):
+        """One buffer of the kinematic observations as its LAST `kinematic_observations` call left it (all zero before the first),
+        by name (`_native.KIN_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait."""
+        which = nat.KIN_FIELDS.index(name) if isinstance(name, str) and name in nat.KIN_FIELDS else name
+        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.KIN_FIELDS):
+            raise ValueError("unknown kinematic buffer %r (known: %s)" % (name, ', '.join(nat.KIN_FIELDS)))
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(self.L.rr_kinematic_buffer(self.h, int(which), C.byref(p), C.byref(n)))
+        shape = self._kinematic_shape(int(which), n.value // (4 * self.N * (3, 6, 66)[int(which) - 4]) if which >= 4 else 0)
+        if host:
+            out = np.empty(shape, np.float32)
+            nat.check(self.L.rr_kinematic_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
+            return out
+        return nat.DeviceBuffer(p.value, shape, '<f4', self)
+
+    def kinematic_observations(self, host=False):
+        """getJointState / getLinkState(computeLinkVelocity=1) / getBaseVelocity / calculateJacobian for the whole batch
+        (rr_kinematic_observations): one launch on the library's stream turns the present state into (float32)
+          joint_vel [N, 11] -- qd in the order of q[11] of the state;
+          link_pose [N, 17, 7] -- the rows of `link_poses()`; link_vel [N, 17, 6] -- world linear velocity of that frame's origin, angular;
+          obj_vel [N, n_objects, 6] -- linear, angular;
+          point_pos [N, P, 3], point_vel [N, P, 6], jacobian [N, P, 6, 11] -- for the P points of `set_kinematic_points`: rows linear
+          xyz then angular xyz, columns the eleven joints (`jacobian @ _native.Q_FROM_CMD`: over the nine command entries).
+        Returns them as device buffers (zero copy, DLPack; valid after later work on the library's stream or `sync()`; they hold what
+        the last call computed -- steps do not refresh them), or with host=True as numpy arrays after a sync."""
+        nat.check(self.L.rr_kinematic_observations(self.h))
+        return {name: self.kinematic_buffer(i, host=host) for i, name in enumerate(nat.KIN_FIELDS)}
+
     def body_row_names(self):
         """The bodies of the rows of body_force / body_partners: the 17 URDF links, then this handle's objects (the rows of the
         objects it does not have, up to 20, stay zero)."""

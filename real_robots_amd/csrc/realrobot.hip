@@ -460,6 +460,7 @@ __device__ __forceinline__ void dispatch_order_class(int x, int N, int ntiles, i
 #include "rr_solve.inc"    // k_solve / k_solve_rs / k_solve_light_ow: command part, row build, projected Gauss-Seidel, integration
 #include "rr_state.inc"    // reset / state io / observation kernels, render set-up
 #include "rr_contacts.inc"    // k_contact_obs: contact records and per-body forces of the whole batch (rr_contact_observations)
+#include "rr_kin.inc"    // k_kinematics: joint / link / object velocities, link poses, point Jacobians of the whole batch (rr_kinematic_observations)
 #include "rr_ik.inc"    // inverse kinematics and macro plans (K8)
 #include "rr_render.inc"    // rasteriser: k_raster, k_shade, the list-walking render kernels
 #include "rr_gather.inc"    // delta image records for the observation gather (k_pack_delta, k_apply_delta)

@@ -123,6 +123,12 @@ struct rr_env : ModelTables {
     float *plan = nullptr; int *plan_step = nullptr; float *ik_in = nullptr; float *ik_out = nullptr; float *ik_err = nullptr;   // lazily allocated (macro / cartesian adapters)
     float *score_out = nullptr; unsigned char *score_mask = nullptr;            // lazily allocated (rr_evaluate_goals)
     float4 *co_contacts = nullptr; float2 *co_force = nullptr; unsigned *co_partners = nullptr;   // lazily allocated (rr_contact_observations)
+    // kinematic observations (rr_kinematic_observations): the seven RR_KIN_* buffers, allocated together on first use (the three point buffers for
+    // RR_KIN_MAX_POINTS points, once); the points are a setting of the handle: a host copy and the device copy k_kinematics reads
+    float *kin[RR_KIN_COUNT] = {};
+    int kin_np = 1;                // points in force: a fresh handle has link 8 (gripper `base`) at the origin of its COM frame
+    KinPoints kin_pts = {{8}, {}};
+    KinPoints *kin_pts_dev = nullptr;
     MemOwner mem;                  // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
     bool created = false;
     bool timing = false;
@@ -252,10 +258,11 @@ static const char *hip_mem_zero(void *ctx, void *p, size_t bytes) {
 }
 static void hip_mem_release(void *, MemKind kind, void *p) { if (kind == MEM_DEVICE) (void)hipFree(p); else (void)hipHostFree(p); }
 // a group of parts for the handle, all or nothing; `what`: "<entry point>: allocating <what>"
-static int mem_get(rr_env *e, std::initializer_list<MemPart> parts, const char *what) {
-    const char *err = e->mem.acquire(parts);
+static int mem_get(rr_env *e, const MemPart *parts, size_t n, const char *what) {
+    const char *err = e->mem.acquire(parts, n);
     return err ? fail(RR_EDEVICE, std::string(what) + ": " + err) : RR_OK;
 }
+static int mem_get(rr_env *e, std::initializer_list<MemPart> parts, const char *what) { return mem_get(e, parts.begin(), parts.size(), what); }
 #define RRCHK(x) do { const int rc_ = (x); if (rc_ != RR_OK) return rc_; } while (0)
 
 // VP = proj * view (row-major 4x4): the one product of a camera's matrices (rr_set_camera, rr_set_env_cameras, the default eye)
@@ -1365,6 +1372,109 @@ int rr_contact_observations(rr_env *e) {
     hipLaunchKernelGGL(k_contact_obs, dim3((e->P.N + CO_ENVS - 1) / CO_ENVS), dim3(64 * CO_ENVS), 0, e->stream, e->P, e->D, e->RM.nl,
                        e->co_contacts, e->co_force, e->co_partners);
     HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+// The seven buffers of rr_kinematic_observations and the device copy of the points: allocated on first use -- by the call or by
+// rr_kinematic_buffer / rr_kinematic_copy_to_host -- in one list, zero-filled; the points in force go up behind it.
+static size_t kin_bytes(const rr_env *e, int which, int np) {
+    const size_t row[RR_KIN_COUNT] = {NB, KIN_LINKS * 7, KIN_LINKS * 6, (size_t)6 * e->P.nobj, (size_t)3 * np, (size_t)6 * np, (size_t)6 * NB * np};
+    return (size_t)e->P.N * row[which] * 4;
+}
+static int ensure_kinematics(rr_env *e, const char *who) {
+    if (e->kin[0]) return RR_OK;
+    if (e->RM.nl != KIN_LINKS) return fail(RR_EMODEL, std::string(who) + ": the model does not have the 17 URDF links of rr_link_poses");
+    for (int l = 0; l < KIN_LINKS; l++)
+        if (e->RM.link_body[l] >= NB) return fail(RR_EMODEL, std::string(who) + ": link " + std::to_string(l) + " of the model is on a body outside the kinematic tree");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    float *b[RR_KIN_COUNT] = {};
+    KinPoints *pd = nullptr;
+    MemPart parts[RR_KIN_COUNT + 1];
+    for (int i = 0; i < RR_KIN_COUNT; i++) parts[i] = mem_part(&b[i], kin_bytes(e, i, RR_KIN_MAX_POINTS));
+    parts[RR_KIN_COUNT] = mem_part(&pd, sizeof(KinPoints), false);
+    RRCHK(mem_get(e, parts, RR_KIN_COUNT + 1, (std::string(who) + ": allocating the observation buffers").c_str()));
+    hipError_t rc = hipMemcpyAsync(pd, &e->kin_pts, sizeof(KinPoints), hipMemcpyHostToDevice, e->stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);      // (the source is the handle's own memory)
+    if (rc != hipSuccess) {
+        (void)hipStreamSynchronize(e->stream);
+        for (int i = 0; i < RR_KIN_COUNT; i++) e->mem.release(b[i]);
+        e->mem.release(pd);
+        (void)hipGetLastError();
+        return fail(RR_EDEVICE, std::string(who) + ": uploading the points: " + hipGetErrorString(rc));
+    }
+    for (int i = 0; i < RR_KIN_COUNT; i++) e->kin[i] = b[i];
+    e->kin_pts_dev = pd;
+    return RR_OK;
+}
+
+int rr_set_kinematic_points(rr_env *e, int32_t n_points, const int32_t *link, const float *local_pos) {
+    if (!e) return fail(RR_EINVAL, "rr_set_kinematic_points: null env");
+    if (n_points < 1 || n_points > RR_KIN_MAX_POINTS)
+        return fail(RR_EINVAL, n_points < 1 ? "rr_set_kinematic_points: n_points " + std::to_string(n_points) + ": point 0 is missing (at least one point)"
+                                            : "rr_set_kinematic_points: n_points " + std::to_string(n_points) + ": point " + std::to_string(RR_KIN_MAX_POINTS) +
+                                                  " is beyond RR_KIN_MAX_POINTS (" + std::to_string(RR_KIN_MAX_POINTS) + ")");
+    if (!link) return fail(RR_EINVAL, "rr_set_kinematic_points: null link array");
+    KinPoints K = {};
+    for (int j = 0; j < n_points; j++) {
+        if (link[j] < 0 || link[j] >= KIN_LINKS)
+            return fail(RR_EINVAL, "rr_set_kinematic_points: point " + std::to_string(j) + ": link " + std::to_string(link[j]) + " is not in [0, " + std::to_string(KIN_LINKS) + ")");
+        K.link[j] = link[j];
+        for (int k = 0; k < 3; k++) {
+            const float v = local_pos ? local_pos[3 * j + k] : 0.0f;
+            if (!std::isfinite(v)) return fail(RR_EINVAL, "rr_set_kinematic_points: point " + std::to_string(j) + ": local_pos is not finite");
+            K.local[j][k] = v;
+        }
+    }
+    if (e->kin_pts_dev) {      // (before the buffers exist the host copy is all there is: ensure_kinematics uploads it)
+        HIPCHK(hipSetDevice(e->cfg.device));
+        HIPCHK(hipStreamSynchronize(e->stream));      // an observation call enqueued earlier still reads the earlier points
+        HIPCHK(hipMemcpy(e->kin_pts_dev, &K, sizeof K, hipMemcpyHostToDevice));
+    }
+    e->kin_pts = K; e->kin_np = n_points;
+    return RR_OK;
+}
+
+int rr_get_kinematic_points(rr_env *e, int32_t *n_points, int32_t *link_out, float *local_pos_out) {
+    if (!e) return fail(RR_EINVAL, "rr_get_kinematic_points: null env");
+    if (n_points) *n_points = e->kin_np;
+    if (link_out) memcpy(link_out, e->kin_pts.link, (size_t)e->kin_np * 4);
+    if (local_pos_out) memcpy(local_pos_out, e->kin_pts.local, (size_t)e->kin_np * 12);
+    return RR_OK;
+}
+
+// getJointState / getLinkState / getBaseVelocity / calculateJacobian for the whole batch, on the device.  On the main stream like
+// rr_contact_observations: behind every step, reset and state upload enqueued before it (every rr_step has made that stream wait for
+// its side streams before it returns).  Reads D.state only -- never the scratch slab of the look-ahead -- and leaves la_valid alone.
+int rr_kinematic_observations(rr_env *e) {
+    if (!e) return fail(RR_EINVAL, "rr_kinematic_observations: null env");
+    RRCHK(ensure_kinematics(e, "rr_kinematic_observations"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const KinOut O = {e->kin[RR_KIN_JOINT_VEL], e->kin[RR_KIN_LINK_POSE], e->kin[RR_KIN_LINK_VEL], e->kin[RR_KIN_OBJ_VEL],
+                      e->kin[RR_KIN_POINT_POS], e->kin[RR_KIN_POINT_VEL], e->kin[RR_KIN_JACOBIAN]};
+    hipLaunchKernelGGL(k_kinematics, dim3((e->P.N + KIN_ENVS - 1) / KIN_ENVS), dim3(KIN_THREADS), 0, e->stream, e->B, e->P, e->RM_dev, e->D, O,
+                       e->kin_pts_dev, e->kin_np);
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+int rr_kinematic_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_kinematic_buffer: null env");
+    if (which < 0 || which >= RR_KIN_COUNT) return fail(RR_EINVAL, "rr_kinematic_buffer: buffer " + std::to_string(which) + " is not in [0, RR_KIN_COUNT)");
+    RRCHK(ensure_kinematics(e, "rr_kinematic_buffer"));
+    if (dev_ptr) *dev_ptr = e->kin[which];
+    if (bytes) *bytes = kin_bytes(e, which, e->kin_np);
+    return RR_OK;
+}
+
+int rr_kinematic_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_kinematic_copy_to_host: null env");
+    if (!dst) return fail(RR_EINVAL, "rr_kinematic_copy_to_host: null destination");
+    if (which < 0 || which >= RR_KIN_COUNT) return fail(RR_EINVAL, "rr_kinematic_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_KIN_COUNT)");
+    if (bytes != kin_bytes(e, which, e->kin_np)) return fail(RR_EINVAL, "rr_kinematic_copy_to_host: size mismatch");
+    RRCHK(ensure_kinematics(e, "rr_kinematic_copy_to_host"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    HIPCHK(hipMemcpyAsync(dst, e->kin[which], bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
     return RR_OK;
 }
 

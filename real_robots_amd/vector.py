@@ -47,6 +47,13 @@ Contact observations: `contact_obs=True` adds `body_force` [N, 20, 2] (float32: 
 robot links and the three objects) and `body_partners` [N, 20] (uint32 bit mask: bit 0 a static body, bit 1 + j object j, bit 4 the
 robot) to the observation dict and to the spaces (BatchedREALRobotEnv.contact_observations), computed where the other entries are
 gathered: after a same-step autoreset they describe the reset state.  The default leaves dict and spaces as they are.
+Kinematic observations: `kinematic_obs=True` adds `joint_velocities` [N, 11], `link_poses` [N, 17, 7], `link_velocities` [N, 17, 6],
+`object_velocities` [N, n_objects, 6], `point_positions` [N, P, 3], `point_velocities` [N, P, 6] and `jacobian` [N, P, 6, 11] (float32,
+unbounded; BatchedREALRobotEnv.kinematic_observations) to the observation dict and to the spaces, computed where the other entries are
+gathered, device views or host copies by `device_obs`.  `kinematic_points=` is a sequence of links (names or indices), or a pair
+(links, local_pos [P, 3]); the default is the one point of a fresh handle, the gripper base.  `jacobian @ _native.Q_FROM_CMD` is the
+Jacobian over the nine entries of `joint_command`.  The default leaves dict and spaces as they are.  These two arguments and the ones
+behind them (`contact_obs`, `goals`, `goal_stride`) are keyword-only.
 Goals: `goals=` (the path of a goals dataset, or a list of `Goal` objects) with `goal_stride=` puts the goal table and the episode
 record on the device (BatchedREALRobotEnv.set_goals_from / episode_update; evaluateGoal, env.py:181-200).  reset() gives env i the
 goal i mod G and starts it from that goal's start poses; every step() returns as rewards the change of the env's goal score over
@@ -88,10 +95,15 @@ def _batch_dict_space(space, n):
 
 
 class REALRobotVectorEnv(_Base):
+    # observation key -> field of BatchedREALRobotEnv.kinematic_observations
+    KINEMATIC_KEYS = (("joint_velocities", "joint_vel"), ("link_poses", "link_pose"), ("link_velocities", "link_vel"),
+                      ("object_velocities", "obj_vel"), ("point_positions", "point_pos"), ("point_velocities", "point_vel"),
+                      ("jacobian", "jacobian"))
+
     def __init__(self, num_envs, objects=3, additional_obs=False, eye_width=320, eye_height=240, device=0,
                  max_episode_steps=int(15e6), render_every_step=True, device_obs=False, solver=None, dynamics_randomization=None,
-                 camera_randomization=None, appearance_randomization=None, actuator_randomization=None, contact_obs=False,
-                 goals=None, goal_stride=1):
+                 camera_randomization=None, appearance_randomization=None, actuator_randomization=None, *, kinematic_obs=False,
+                 kinematic_points=None, contact_obs=False, goals=None, goal_stride=1):
         self.num_envs = int(num_envs)
         self._goals = None if goals is None else self._check_goals(goals, OBJECT_NAMES[:int(objects)], int(eye_height), int(eye_width))
         self.goal_stride = int(goal_stride)
@@ -104,6 +116,22 @@ class REALRobotVectorEnv(_Base):
                 self._robot.observation_space.spaces,
                 body_force=spaces.Box(low=0.0, high=np.inf, shape=(nat.CONTACT_ROWS, 2), dtype=np.float32),
                 body_partners=spaces.Box(low=0, high=31, shape=(nat.CONTACT_ROWS,), dtype=np.uint32)))
+        self.kinematic_obs = bool(kinematic_obs)
+        kin_points = None
+        if kinematic_points is not None:
+            if not self.kinematic_obs:
+                raise ValueError("kinematic_points needs kinematic_obs=True")
+            kp = kinematic_points
+            pair = isinstance(kp, tuple) and len(kp) == 2 and not isinstance(kp[1], (str, int, np.integer))
+            kin_points = BatchedREALRobotEnv._kinematic_points_arg(*(kp if pair else (kp,)))
+        if self.kinematic_obs:
+            n_pts, n_links = 1 if kin_points is None else len(kin_points[0]), len(nat.LINK_NAMES)
+            box = lambda *shape: spaces.Box(low=-np.inf, high=np.inf, shape=shape, dtype=np.float32)
+            self.single_observation_space = spaces.Dict(dict(
+                self.single_observation_space.spaces,
+                joint_velocities=box(nat.N_JOINTS), link_poses=box(n_links, 7), link_velocities=box(n_links, 6),
+                object_velocities=box(int(objects), 6), point_positions=box(n_pts, 3), point_velocities=box(n_pts, 6),
+                jacobian=box(n_pts, 6, nat.N_JOINTS)))
         # batched spaces = the single spaces with a leading env axis (gymnasium.vector.utils.batch_space)
         self.action_space = spaces.Dict({
             "joint_command": spaces.Box(low=np.tile(self._robot.min_joints, (self.num_envs, 1)),
@@ -115,6 +143,8 @@ class REALRobotVectorEnv(_Base):
         self.render_every_step, self.device_obs, self.additional_obs = bool(render_every_step), bool(device_obs), bool(additional_obs)
         self._be = BatchedREALRobotEnv(self.num_envs, objects=objects, width=eye_width, height=eye_height, device=device,
                                        want_mask=additional_obs, solver=solver)
+        if kin_points is not None:
+            self._be.set_kinematic_points(*kin_points)
         # host-side episode clocks (no device read-back per step): the batched env behind this adapter is private to it, every
         # path that resets an env goes through reset() / step() below and resets its clock with it
         self._steps = np.zeros(self.num_envs, np.int64)
@@ -329,6 +359,10 @@ class REALRobotVectorEnv(_Base):
         if self.contact_obs:
             co = be.contact_observations(host=not self.device_obs)
             obs["body_force"], obs["body_partners"] = co["body_force"], co["body_partners"]
+        if self.kinematic_obs:
+            ko = be.kinematic_observations(host=not self.device_obs)
+            for key, name in self.KINEMATIC_KEYS:
+                obs[key] = ko[name]
         if self._goals is not None:
             if self._goal_images:
                 obs["goal"] = be.episode_buffer('goal_rgb', host=not self.device_obs)
