@@ -34,7 +34,9 @@ extern "C" {
                               rr_set_goals, rr_set_env_goals, rr_set_episode, rr_episode_update, rr_episode_buffer (goal table and episode
                               record on the device; checkpoints do not carry them); rr_snapshot_slots, rr_copy_envs (env forks and
                               snapshot slots on the device); rr_set_kinematic_points, rr_get_kinematic_points, rr_kinematic_observations,
-                              rr_kinematic_buffer, rr_kinematic_copy_to_host (link states and Jacobians of the whole batch) */
+                              rr_kinematic_buffer, rr_kinematic_copy_to_host (link states and Jacobians of the whole batch); rr_write_state,
+                              rr_read_state (masked state writes by column groups -- resets, teleports, postures, velocity kicks -- and state
+                              reads on the device) */
 
 enum {
     RR_OK = 0,
@@ -255,6 +257,58 @@ int rr_copy_to_host(rr_env *env, int32_t field, void *dst, size_t bytes);
  * (rr_set_object_pose(s) keeps the history, like resetBasePositionAndOrientation keeps Bullet's manifolds: cached points of a
  * teleported body are farther than the contact margin from its new contacts and match nothing.) */
 int rr_set_state(rr_env *env, const float *state_host);
+/* ---- State writes and reads on the device (additive in ABI 7) ------------------------------------------------------------------------
+ * Replaces resetJointState, resetBasePositionAndOrientation and resetBaseVelocity of pybullet for ALL envs at once, with the tensor and
+ * the mask in device memory if the caller wishes: a device program decides which envs restart and where they start -- a curriculum
+ * over start poses, randomised postures, early termination on its own criterion, objects put where a sampled plan says -- with no
+ * host round trip (the set_*_state_tensor_indexed of batched simulators).  rr_reset, rr_set_object_poses and rr_set_state take host
+ * memory, and the last one has no mask.  A read-modify-write of the object twists (rr_read_state, arithmetic, RR_W_OBJ_VEL) is an
+ * impulse, dv = J / m, applied between two steps.
+ * state: f32 [N, 61], the rows of RR_F_STATE; env_mask: u8 [N], an env takes part when its byte is non-zero (a one-byte bool array
+ * is a valid mask), NULL: all envs.  parts: which column groups of the row are written, and what happens around them: */
+#define RR_W_JOINT_POS 1   /* columns 0..10 of the RR_F_STATE row: q[11] */
+#define RR_W_JOINT_VEL 2   /* columns 11..21: qd[11] */
+#define RR_W_OBJ_POSE  4   /* per object o < n_objects, columns 22+13o .. +6: pos3 quat4 */
+#define RR_W_OBJ_VEL   8   /* per object, columns 22+13o+7 .. +12: lin3 ang3 */
+#define RR_W_RESET     16  /* the env is first reset exactly as by rr_reset */
+#define RR_W_FRESH     32  /* afterwards: error flags 0, touch 0, contact history dropped (what rr_set_state does behind its write) */
+/* Order per masked env: (1) the reset, if RR_W_RESET is set; (2) the selected column groups are copied from the env's row of `state`;
+ * (3) the fresh-start clean-up, if RR_W_FRESH is set.  Columns outside the selected groups, rows of unmasked envs and the columns of
+ * objects >= n_objects are never used: a NaN there does not reach the state.
+ * RR_W_OBJ_POSE without RR_W_OBJ_VEL zeroes the object's twist -- resetBasePositionAndOrientation, as rr_set_object_poses does --;
+ * with both bits both come from the tensor; RR_W_OBJ_VEL alone leaves the pose in place: the velocity kick.
+ * Without RR_W_RESET or RR_W_FRESH these are KEPT, as rr_set_object_poses keeps them: the contact history of the warm start,
+ * RR_F_TIMESTEP, the error flags, the touch sensors and the motor-target rows of the state slab.  So an env frozen by error flag 1
+ * stays frozen unless RR_W_FRESH (or RR_W_RESET) is given.
+ * Equivalences, each bit for bit (tested):
+ *   parts == RR_W_RESET (state may be NULL)                  rr_reset(mask)
+ *   RR_W_OBJ_POSE                                            rr_set_object_poses(poses, mask), the poses in their columns of the rows
+ *   15 | RR_W_FRESH with a NULL mask                         rr_set_state (on a handle with three objects: rr_set_state also writes the
+ *                                                            columns of the objects the handle does not have)
+ *   RR_W_RESET | RR_W_OBJ_POSE                               steps 2 and 4 of the auto-reset of rr_episode_update
+ * on_device != 0: both pointers are device memory, read IN PLACE on the library's stream under the STREAM CONTRACT of rr_step's
+ * cmd_on_device (produced on that stream or ordered before it; not overwritten before later work on that stream, or rr_sync); the
+ * call allocates nothing, checks the launch and returns without waiting.  on_device == 0: both are host memory; the call stages them
+ * and is synchronous, like rr_set_state.
+ * Values are not validated, as in rr_set_state and rr_set_object_poses: a non-finite value is caught by the next step's guard (error
+ * flag 1).  RR_EINVAL, with nothing changed: a null env; a bit outside the six; parts == 0; state == NULL while any of the four
+ * column bits is set.
+ * Like every change of state from outside, the next step prepares itself again; the observation buffers and a mapped host mirror
+ * are refreshed behind the write; images are left alone (an env keeps its last frame until its next render).  The episode record,
+ * macro plans in flight, settings and the fields of the observation calls are not touched: after a write into running envs the
+ * caller re-bases the previous score with rr_set_env_goals, as after rr_reset.
+ * Out of scope: writing the clock or the motor targets; per-env object sets; writes into snapshot slots (go through rr_copy_envs);
+ * validation on the device; an indexed form (a list of env ids instead of a mask); options of the gym vector env, whose episode
+ * clocks live on the host. */
+int rr_write_state(rr_env *env, const float *state, const uint8_t *env_mask, uint32_t parts, int32_t on_device);
+/* One launch on the library's stream gathers the PRESENT state of every env into the device buffer of RR_F_STATE (rr_get_buffer):
+ * f32 [N, 61], the rows rr_copy_to_host(RR_F_STATE) returns.  The call checks the launch and returns without waiting; the buffer is
+ * valid for readers ordered behind it (STREAM CONTRACT as for the other zero-copy views, rr_step) and holds what the last such call
+ * -- or rr_copy_to_host(RR_F_STATE) -- computed: steps do not refresh it.  The same buffer is the STAGING AREA of rr_set_state,
+ * rr_set_object_poses, rr_evaluate_goals and the host path of rr_write_state: those calls overwrite it.  (It may be passed to
+ * rr_write_state with on_device != 0 as it is: that path reads in place and stages nothing.) */
+int rr_read_state(rr_env *env);
+
 /* Checkpoint = everything a restore needs to continue BIT FOR BIT where the save left off: the state (with the motor targets),
  * the contact history of the warm start (contact list + normal forces of the last solved step -- Bullet's persistent manifolds
  * with their cached impulses, which pybullet.saveState / restoreState carry too), episode clocks, error flags, touch sensors,

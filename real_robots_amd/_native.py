@@ -38,7 +38,8 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_set_env_actuators', 'rr_get_env_actuators', 'rr_contact_observations',
            'rr_set_goals', 'rr_set_env_goals', 'rr_set_episode', 'rr_episode_update', 'rr_episode_buffer', 'rr_episode_copy_to_host',
            'rr_snapshot_slots', 'rr_copy_envs',
-           'rr_set_kinematic_points', 'rr_get_kinematic_points', 'rr_kinematic_observations', 'rr_kinematic_buffer', 'rr_kinematic_copy_to_host')
+           'rr_set_kinematic_points', 'rr_get_kinematic_points', 'rr_kinematic_observations', 'rr_kinematic_buffer', 'rr_kinematic_copy_to_host',
+           'rr_write_state', 'rr_read_state')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
@@ -60,6 +61,10 @@ Q_FROM_CMD[np.arange(7), np.arange(7)] = 1.0
 Q_FROM_CMD[[7, 9], 7] = 1.0
 Q_FROM_CMD[[8, 10], 8] = -1.0
 SLOT_LIVE, MAX_SLOTS = -1, 64           # RR_SLOT_LIVE: the running envs as a slot number of rr_copy_envs; RR_MAX_SLOTS
+# `parts` of rr_write_state (the RR_W_* bits): the column groups of the 61-float state row that are written, a reset in front of them,
+# the fresh-start clean-up of rr_set_state behind them
+W_JOINT_POS, W_JOINT_VEL, W_OBJ_POSE, W_OBJ_VEL, W_RESET, W_FRESH = 1, 2, 4, 8, 16, 32
+W_COLUMNS = W_JOINT_POS | W_JOINT_VEL | W_OBJ_POSE | W_OBJ_VEL
 
 
 class Config(C.Structure):
@@ -185,6 +190,8 @@ def load_library():
     L.rr_kinematic_observations.argtypes = [vp]
     L.rr_kinematic_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rr_kinematic_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
+    L.rr_write_state.argtypes = [vp, vp, vp, C.c_uint32, i32]
+    L.rr_read_state.argtypes = [vp]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]

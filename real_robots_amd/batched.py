@@ -23,6 +23,13 @@ def _env_mask(env_mask, N):
     return m, m.ctypes.data
 
 
+def _on_device(a):
+    """a CUDA torch tensor or an object with `__cuda_array_interface__`"""
+    if hasattr(a, 'is_cuda') and hasattr(a, 'data_ptr'):
+        return bool(a.is_cuda)
+    return getattr(a, '__cuda_array_interface__', None) is not None
+
+
 def _float32_arg(v, name, shape, nonneg=False):
     """v broadcast to float32 `shape`; a shape that does not broadcast, a value that is not finite in float32 or (nonneg)
     a negative one raises ValueError naming the field."""
@@ -118,8 +125,12 @@ class BatchedREALRobotEnv:
 
     # ------------------------------------------------------------------ stepping
     def reset(self, env_mask=None):
+        """rr_reset of the masked envs (None: all).  A mask in device memory (a CUDA torch tensor, `__cuda_array_interface__`) is
+        read in place on the library's stream, without a host round trip (`write_state(reset=True)`)."""
         if env_mask is None:
             nat.check(self.L.rr_reset(self.h, None))
+        elif _on_device(env_mask):
+            self.write_state(None, env_mask, reset=True)
         else:
             m = np.ascontiguousarray(env_mask, dtype=np.uint8)
             assert m.shape == (self.N,)
@@ -199,6 +210,70 @@ class BatchedREALRobotEnv:
         s = np.ascontiguousarray(s, dtype=np.float32)
         assert s.shape == (self.N, 61)
         nat.check(self.L.rr_set_state(self.h, s.ctypes.data))
+
+    # ------------------------------------------------------------------ state writes and reads on the device
+    def _state_arg(self, a, name, kinds, shape):
+        """An argument of write_state -> (address, 1 on the device / 0 on the host, object that keeps the memory alive).  A CUDA
+        torch tensor or a `__cuda_array_interface__` object is device memory, anything else a host array; either must have one of
+        the dtypes `kinds` (numpy names) and exactly `shape`, and be contiguous: a ValueError naming the argument otherwise."""
+        what = "%s must be a contiguous %s array of shape %s" % (name, ' or '.join(kinds), shape)
+        if hasattr(a, 'is_cuda') and hasattr(a, 'data_ptr'):        # a torch tensor
+            if a.is_cuda:
+                if str(a.dtype).replace('torch.', '') not in kinds or tuple(a.shape) != shape or not a.is_contiguous():
+                    raise ValueError("%s, not %s %s%s" % (what, a.dtype, tuple(a.shape), '' if a.is_contiguous() else ' (not contiguous)'))
+                return int(a.data_ptr()), 1, a
+            a = a.numpy()
+        cai = getattr(a, '__cuda_array_interface__', None)
+        if cai is not None:
+            dt = np.dtype(cai['typestr'])
+            dense = tuple(int(np.prod(shape[i + 1:])) * dt.itemsize for i in range(len(shape)))
+            if dt.name not in kinds or tuple(cai['shape']) != shape or cai.get('strides') not in (None, dense):
+                raise ValueError("%s, not %s %s strides %s" % (what, cai['typestr'], tuple(cai['shape']), cai.get('strides')))
+            return int(cai['data'][0]), 1, a
+        a = np.asarray(a)
+        if a.dtype.name not in kinds or a.shape != shape or not a.flags.c_contiguous:
+            raise ValueError("%s, not %s %s%s" % (what, a.dtype, a.shape, '' if a.flags.c_contiguous else ' (not contiguous)'))
+        return a.ctypes.data, 0, a
+
+    def write_state(self, state=None, env_mask=None, *, joint_pos=False, joint_vel=False, obj_pose=False, obj_vel=False, reset=False,
+                    fresh=False):
+        """Masked write into the state by column groups (rr_write_state): resets, teleports, postures and velocity kicks decided
+        on the device.  state: float32 [N, 61], the rows of `state` / `read_state()` -- q[11] qd[11], per object pos3 quat4 lin3
+        ang3; env_mask: uint8 or bool [N] (None: all envs).  Both are CUDA torch tensors / `__cuda_array_interface__` objects, read
+        in place on the library's stream without waiting (produce them on that stream or synchronise first, and keep them unchanged
+        until later work on that stream), or both host arrays (staged, synchronous).  Per masked env, in this order: `reset` (as
+        `reset()`), then the selected groups -- joint_pos (columns 0..10), joint_vel (11..21), obj_pose (pos3 quat4 of this handle's
+        objects; without obj_vel the object's twist is zeroed, a teleport), obj_vel (lin3 ang3; alone: a velocity kick) --, then
+        `fresh`: error flags 0, touch 0, contact history dropped, what `state = ...` does behind its write.  Without reset / fresh
+        the contact history, clock, error flags, touch sensors and motor targets are kept (a frozen env stays frozen).  Columns
+        that are not selected, rows of unmasked envs and columns of objects the handle does not have are not used (NaN is fine
+        there); selected values are not validated -- the next step's guard flags a non-finite state.  Wrong dtype, shape,
+        contiguity, arguments on different sides, column flags without a state or no flag at all raise ValueError before the library
+        is called.  The episode record is not touched: re-base the score with `set_env_goals`, as after `reset()`."""
+        parts = ((nat.W_JOINT_POS if joint_pos else 0) | (nat.W_JOINT_VEL if joint_vel else 0) | (nat.W_OBJ_POSE if obj_pose else 0) |
+                 (nat.W_OBJ_VEL if obj_vel else 0) | (nat.W_RESET if reset else 0) | (nat.W_FRESH if fresh else 0))
+        if parts == 0:
+            raise ValueError("write_state: none of joint_pos, joint_vel, obj_pose, obj_vel, reset, fresh is set")
+        if state is None and parts & nat.W_COLUMNS:
+            raise ValueError("write_state: state is None, but joint_pos / joint_vel / obj_pose / obj_vel need one")
+        if state is not None and not parts & nat.W_COLUMNS:
+            raise ValueError("write_state: a state without any of joint_pos, joint_vel, obj_pose, obj_vel")
+        sp, s_dev, s_keep = (None, None, None) if state is None else self._state_arg(state, 'state', ('float32',), (self.N, 61))
+        mp, m_dev, m_keep = (None, None, None) if env_mask is None else self._state_arg(env_mask, 'env_mask', ('uint8', 'bool'), (self.N,))
+        if s_dev is not None and m_dev is not None and s_dev != m_dev:
+            raise ValueError("write_state: state and env_mask must live on the same side (state on the %s, env_mask on the %s)"
+                             % (('host', 'device')[s_dev], ('host', 'device')[m_dev]))
+        on_dev = s_dev if s_dev is not None else (m_dev or 0)
+        nat.check(self.L.rr_write_state(self.h, sp, mp, parts, on_dev))
+        del s_keep, m_keep
+
+    def read_state(self):
+        """One launch on the library's stream gathers the present state into the device buffer of the `state` field
+        (rr_read_state) and returns it: float32 [N, 61], zero copy (DLPack / `__cuda_array_interface__`), valid for readers ordered
+        behind the call.  Steps do not refresh it, and `state = ...`, `set_object_poses`, `evaluate_goals` and a host
+        `write_state` use the same buffer for staging: copy what has to last."""
+        nat.check(self.L.rr_read_state(self.h))
+        return self.device_buffer(nat.F_STATE)
 
     def checkpoint(self):
         """Opaque snapshot (numpy uint8 array) of everything a later `restore` needs to continue bit for bit: state with motor

@@ -1711,6 +1711,44 @@ int rr_copy_envs(rr_env *e, int32_t src_slot, int32_t dst_slot, const int32_t *s
 }
 
 
+// ---- state writes and reads on the device (rr_write.inc) --------------------------------------------------------------------------------
+// On the library's stream, like rr_copy_envs: every rr_step has made that stream wait for its side streams before it returns, so the
+// launch is ordered behind every kernel that reads or writes the state -- the look-ahead included -- without a wait of its own.
+static void launch_state_rw(rr_env *e, float *aos, const unsigned char *mask_dev, unsigned parts, int to_aos) {
+    hipLaunchKernelGGL(k_state_rw, dim3((e->P.N + SW_ENVS - 1) / SW_ENVS), dim3(SW_THREADS), 0, e->stream, e->P, e->D, aos, mask_dev, parts, to_aos);
+}
+
+int rr_write_state(rr_env *e, const float *state, const uint8_t *env_mask, uint32_t parts, int32_t on_device) {
+    if (!e) return fail(RR_EINVAL, "rr_write_state: null env");
+    const uint32_t cols = RR_W_JOINT_POS | RR_W_JOINT_VEL | RR_W_OBJ_POSE | RR_W_OBJ_VEL, all = cols | RR_W_RESET | RR_W_FRESH;
+    if (parts & ~all) return fail(RR_EINVAL, "rr_write_state: parts " + std::to_string(parts) + " has a bit outside the six RR_W_* (" + std::to_string(all) + ")");
+    if (parts == 0) return fail(RR_EINVAL, "rr_write_state: parts == 0 (nothing to write)");
+    if (!state && (parts & cols)) return fail(RR_EINVAL, "rr_write_state: a column group (parts & 15 = " + std::to_string(parts & cols) + ") needs a state tensor");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const int N = e->P.N;
+    const float *aos = (parts & cols) ? state : nullptr;      // (without a column bit the tensor is not looked at)
+    const unsigned char *m = env_mask;
+    if (!on_device) {
+        if (aos) { HIPCHK(hipMemcpyAsync(e->state_aos, aos, (size_t)N * NSTATE * 4, hipMemcpyHostToDevice, e->stream)); aos = e->state_aos; }
+        if (m) { HIPCHK(hipMemcpyAsync(e->mask_dev, m, N, hipMemcpyHostToDevice, e->stream)); m = e->mask_dev; }
+    }
+    e->la_valid = false;          // the state changes from outside: the next step prepares itself in line (as rr_reset)
+    launch_state_rw(e, const_cast<float *>(aos), m, parts, 0);
+    launch_obs(e);                // the observation buffers and a mapped host mirror follow
+    HIPCHK(hipGetLastError());
+    if (!on_device) HIPCHK(hipStreamSynchronize(e->stream));   // the arguments are host memory
+    return RR_OK;
+}
+
+int rr_read_state(rr_env *e) {
+    if (!e) return fail(RR_EINVAL, "rr_read_state: null env");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    launch_state_rw(e, e->state_aos, nullptr, 0u, 1);
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+
 // ---- device micro-benchmarks for bench.py's roofline (SURVEY 8(d): "achievable" measured in the same run) -------------------
 // kind 0: HBM copy (read + write), 1: HBM triad a = b + s c (2 reads + 1 write), 256 MiB per array, float4 per lane, grid-stride;
 // kind 2: VALU issue rate of a sample-test-like mix (sub, mul, fma, cmp, cndmask with real dependencies) at the raster kernel's
