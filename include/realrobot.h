@@ -36,13 +36,14 @@ extern "C" {
                               snapshot slots on the device); rr_set_kinematic_points, rr_get_kinematic_points, rr_kinematic_observations,
                               rr_kinematic_buffer, rr_kinematic_copy_to_host (link states and Jacobians of the whole batch); rr_write_state,
                               rr_read_state (masked state writes by column groups -- resets, teleports, postures, velocity kicks -- and state
-                              reads on the device) */
+                              reads on the device); rr_set_rays, rr_get_rays, rr_ray_cast, rr_ray_buffer, rr_ray_copy_to_host (segments of
+                              the whole batch against the collision hulls) */
 
 enum {
     RR_OK = 0,
     RR_EINVAL = -1,     /* bad argument */
     RR_EDEVICE = -2,    /* HIP runtime error (no GPU, out of memory, launch failure).  Memory that a call allocates on first use
-                           (contact and kinematic observations, goal scores, plans and IK, per-env cameras and appearance, goal table and episode
+                           (contact and kinematic observations, ray casts, goal scores, plans and IK, per-env cameras and appearance, goal table and episode
                            record, snapshot slots and fork staging, mapped host blocks, the staging ring) is allocated all or nothing:
                            when that fails the call returns RR_EDEVICE, nothing has changed -- what the call would replace is kept --
                            and the handle stays usable; a later call tries again. */
@@ -557,6 +558,68 @@ int rr_kinematic_observations(rr_env *env);
 int rr_kinematic_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
 /* Synchronising copy of a whole RR_KIN_* buffer (its `bytes`) to host memory. */
 int rr_kinematic_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
+
+/* ---- Ray casts against the collision hulls on the device (additive in ABI 7) ---------------------------------------------------------
+ * Replaces pybullet's rayTestBatch(rayFromPositions, rayToPositions, parentObjectUniqueId = robot, parentLinkIndex) for ALL envs at
+ * once and on the device: "what does this segment hit first, where, and with which normal" -- proximity and height sensors on the
+ * gripper, clearance checks along an approach, cheap range scans, line-of-sight tests.  One launch on the library's stream
+ * (rr_ray_cast) casts R segments per env against the model's convex collision hulls -- the shapes the step's collision pass uses:
+ * table, shelf, the robot's links, the handle's objects -- at the present state and writes two device buffers.  They are NOT fields
+ * of rr_get_buffer (RR_F_COUNT stays 16): they have this enum and rr_ray_buffer, like the kinematic observations. */
+enum {
+    RR_RAY_HIT = 0,   /* f32 [N, R, 8]  {fraction, distance (m) = fraction * |to - from|, x, y, z (world), nx, ny, nz (world, outward)} */
+    RR_RAY_ID = 1,    /* i32 [N, R, 4]  {uid as in RR_F_MASK, body as in the contact records (-1 static, 0..15 robot body, 16 + i object i),
+                                         URDF link of the shape or -1, collision shape index}; all -1 on a miss */
+    RR_RAY_COUNT = 2
+};
+#define RR_RAY_MAX 64
+/* The ray table: R = n_rays rays in [0, RR_RAY_MAX].  Ray j has a frame -- link[j] = -1: the world; a URDF link id in [0, 17): that
+ * link's COM frame, the frame of rr_link_poses and of the kinematic points, pybullet's parentLinkIndex -- and a default segment
+ * from_to[j] = {from xyz, to xyz} in that frame (f32 [R][6] host; NULL: all zeros, legal only if every cast brings its own segments:
+ * a zero-length segment is a miss).  A fresh handle has R = 0.  n_rays out of range, a link outside {-1} u [0, 17) or a coordinate
+ * that is not finite returns RR_EINVAL -- the message names the ray -- and the table in force stays as it is.  The table is a setting
+ * of the handle, like the kinematic points: rr_reset, rr_set_state, rr_write_state, rr_copy_envs and rr_checkpoint_restore keep it
+ * and checkpoints do not carry it.  Synchronous (it waits for the library's stream: a cast enqueued earlier still sees the earlier
+ * table) and launches nothing; after a change the two buffers hold unspecified data until the next rr_ray_cast. */
+int rr_set_rays(rr_env *env, int32_t n_rays, const int32_t *link, const float *from_to);
+/* The table in force: *n_rays, link_out i32 [R], from_to_out f32 [R][6] (room for RR_RAY_MAX); each output may be NULL. */
+int rr_get_rays(rr_env *env, int32_t *n_rays, int32_t *link_out, float *from_to_out);
+/* One launch on the library's stream casts the R segments of every env against the hulls at the PRESENT state -- whatever the last
+ * step, reset, rr_set_state, rr_write_state, rr_set_object_pose(s), rr_copy_envs or restore left -- and writes the two buffers; the
+ * call checks the launch and returns without waiting.  The kernel does its own forward kinematics from the state: it reads the state
+ * and the model only, not the preparation record (RR_F_PREP), changes no error flag, the next step stays prepared and no later step
+ * is affected.  The buffers hold what the LAST CALL computed: steps do not refresh them.
+ * rays == NULL: every env casts the table's segments.  Otherwise rays is f32 [N, R, 6], per-env segments {from xyz, to xyz} in the
+ * frames of the table's links.  on_device != 0: device memory, read IN PLACE on the library's stream under the STREAM CONTRACT of
+ * rr_step's cmd_on_device (produced on that stream or ordered before it; not rewritten before later work on that stream), nothing
+ * is allocated or staged and the values are not validated.  on_device == 0: host memory, checked finite (RR_EINVAL naming env and
+ * ray, nothing cast), staged, and the call waits for the stream -- the split of rr_write_state.  R == 0: RR_EINVAL.
+ * Semantics.  A shape's frame is the identity for the statics (table, shelf, the robot's fixed base), the body frame of the step's
+ * forward kinematics for a robot shape, and the object's pose for an object, with the rotation the step forms from the quaternion.
+ * The out-of-bounds re-pose of the step is not applied: the state is taken as it is.  Shapes of objects >= n_objects do not exist.
+ * A hull is the set {x : n_k . x - d_k <= 0 for all k} of its up to 192 planes.  For one segment o + t (to - from), t in [0, 1],
+ * expressed in a hull's frame: t_in is the largest entry parameter over the planes with n . dir < 0, t_out the smallest exit
+ * parameter over those with n . dir > 0; a plane parallel to the segment with the origin outside it rules the hull out.  The hull is
+ * hit iff the origin is outside it, t_in >= 0 and t_in <= min(t_out, 1).  The fraction is t_in and the normal that of the entering
+ * plane, turned into the world; among equal entry parameters the lowest plane index wins.  An origin INSIDE a hull (or on its
+ * surface) does not hit THAT hull -- Bullet's convex cast, and what lets a sensor sit inside its own link.  Over the hulls the
+ * smallest float32 fraction wins; equal fractions go to the lowest shape index.  A miss gives fraction 1.0, distance |to - from|,
+ * position the world end point, normal +0.0 and ids -1.  A zero-length segment is a miss.  A segment with a non-finite value (device
+ * path only) is a miss whose float fields may be non-finite.  An env whose state is not finite is computed like any other: its rows
+ * are unspecified.  No ray or state value ever forms an address.  Plain float32 arithmetic; the result is a function of the state
+ * and the segments alone (no atomics: identical from call to call).
+ * Both buffers are allocated on first use -- by this call, or by rr_ray_buffer / rr_ray_copy_to_host --, all or nothing, zero-filled,
+ * once for RR_RAY_MAX rays, and valid until rr_destroy: no pointer ever changes.  Their layout is compact [N, R, ...] for the R in
+ * force, and `bytes` reports that size.  STREAM CONTRACT as for the other zero-copy views (rr_step, rr_kinematic_observations): the
+ * kernel runs on the library's stream behind the work enqueued before it; readers on another stream order themselves after the call
+ * (event / rr_sync), and a later call rewrites the buffers in place.
+ * Out of scope: the render meshes (the hulls are the collision shapes, coarser than what the camera sees), collision filter masks,
+ * more than 64 rays per env, all hits along a ray (the first only), rays in object frames, refreshing from inside a step. */
+int rr_ray_cast(rr_env *env, const float *rays, int32_t on_device);
+/* Zero-copy device pointer + size in bytes of an RR_RAY_* buffer (read-only for the caller); which outside [0, RR_RAY_COUNT): RR_EINVAL. */
+int rr_ray_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
+/* Synchronising copy of a whole RR_RAY_* buffer (its `bytes`) to host memory. */
+int rr_ray_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
 
 /* Batched damped-least-squares inverse kinematics for link 7 (gripper `base`), seeded with each env's current joints.
  * Replaces pybullet.calculateInverseKinematics(0, 7, pos, orn, maxNumIterations=1000, residualThreshold=0.001) in

@@ -39,7 +39,8 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_set_goals', 'rr_set_env_goals', 'rr_set_episode', 'rr_episode_update', 'rr_episode_buffer', 'rr_episode_copy_to_host',
            'rr_snapshot_slots', 'rr_copy_envs',
            'rr_set_kinematic_points', 'rr_get_kinematic_points', 'rr_kinematic_observations', 'rr_kinematic_buffer', 'rr_kinematic_copy_to_host',
-           'rr_write_state', 'rr_read_state')
+           'rr_write_state', 'rr_read_state',
+           'rr_set_rays', 'rr_get_rays', 'rr_ray_cast', 'rr_ray_buffer', 'rr_ray_copy_to_host')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
@@ -60,6 +61,10 @@ Q_FROM_CMD = np.zeros((N_JOINTS, 9), np.float32)
 Q_FROM_CMD[np.arange(7), np.arange(7)] = 1.0
 Q_FROM_CMD[[7, 9], 7] = 1.0
 Q_FROM_CMD[[8, 10], 8] = -1.0
+# buffers of rr_ray_buffer (the RR_RAY_* enum), per env and ray: hit [8] f32 {fraction, distance, x, y, z, nx, ny, nz}, id [4] i32 {uid, body,
+# link, shape} (all -1 on a miss), for the R rays in force (rr_set_rays)
+RAY_FIELDS = ('hit', 'id')
+RAY_MAX = 64
 SLOT_LIVE, MAX_SLOTS = -1, 64           # RR_SLOT_LIVE: the running envs as a slot number of rr_copy_envs; RR_MAX_SLOTS
 # `parts` of rr_write_state (the RR_W_* bits): the column groups of the 61-float state row that are written, a reset in front of them,
 # the fresh-start clean-up of rr_set_state behind them
@@ -192,6 +197,11 @@ def load_library():
     L.rr_kinematic_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_write_state.argtypes = [vp, vp, vp, C.c_uint32, i32]
     L.rr_read_state.argtypes = [vp]
+    L.rr_set_rays.argtypes = [vp, i32, vp, vp]
+    L.rr_get_rays.argtypes = [vp, C.POINTER(i32), vp, vp]
+    L.rr_ray_cast.argtypes = [vp, vp, i32]
+    L.rr_ray_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rr_ray_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]
@@ -216,14 +226,16 @@ def check(rc):
 
 
 class DeviceBuffer:
-    """Device memory view exposing __cuda_array_interface__ (zero-copy into torch: torch.as_tensor(buf, device=...))."""
+    """Device memory view exposing __cuda_array_interface__ (zero-copy into torch: torch.as_tensor(buf, device=...)).
+    strides: bytes per axis for a view that is not compact row-major (a column of a wider buffer); None: compact."""
 
-    def __init__(self, ptr, shape, typestr, owner):
+    def __init__(self, ptr, shape, typestr, owner, strides=None):
         self.ptr, self.shape, self.typestr, self._owner = ptr, tuple(shape), typestr, owner
+        self.strides = None if strides is None else tuple(int(x) for x in strides)
 
     @property
     def __cuda_array_interface__(self):
-        return {'shape': self.shape, 'typestr': self.typestr, 'data': (self.ptr, False), 'version': 2, 'strides': None}
+        return {'shape': self.shape, 'typestr': self.typestr, 'data': (self.ptr, False), 'version': 2, 'strides': self.strides}
 
 
 # ---------------------------------------------------------------------------------------------- DLPack export
@@ -247,7 +259,7 @@ class _DLManagedTensor(C.Structure):
 _DLDeleter = C.CFUNCTYPE(None, C.POINTER(_DLManagedTensor))
 _DLManagedTensor._fields_ = [('dl_tensor', _DLTensor), ('manager_ctx', C.c_void_p), ('deleter', _DLDeleter)]
 KDL_ROCM = 10                       # DLDeviceType kDLROCM
-_dl_alive = {}                      # address of a DLManagedTensor handed out -> (struct, shape array, owner)
+_dl_alive = {}                      # address of a DLManagedTensor handed out -> (struct, shape array, strides array or None, owner)
 
 
 @_DLDeleter
@@ -268,7 +280,8 @@ def _dl_capsule_destructor(capsule):
         _dl_alive.pop(api.PyCapsule_GetPointer(capsule, b'dltensor'), None)
 
 
-def _dlpack_capsule(ptr, shape, np_dtype, device_id, owner):
+def _dlpack_capsule(ptr, shape, np_dtype, device_id, owner, strides=None):
+    """strides: bytes per axis (multiples of the item size) or None for compact row-major."""
     dt = np.dtype(np_dtype)
     code = {'f': 2, 'i': 0, 'u': 1}[dt.kind]
     m = _DLManagedTensor()
@@ -278,11 +291,12 @@ def _dlpack_capsule(ptr, shape, np_dtype, device_id, owner):
     m.dl_tensor.ndim = len(shape)
     m.dl_tensor.dtype = _DLDataType(code, dt.itemsize * 8, 1)
     m.dl_tensor.shape = shp
-    m.dl_tensor.strides = None          # compact row-major
+    std = None if strides is None else (C.c_int64 * len(shape))(*[x // dt.itemsize for x in strides])
+    m.dl_tensor.strides = std           # None: compact row-major; DLPack counts strides in elements
     m.dl_tensor.byte_offset = 0
     m.manager_ctx = None
     m.deleter = _dl_deleter
-    _dl_alive[C.addressof(m)] = (m, shp, owner)
+    _dl_alive[C.addressof(m)] = (m, shp, std, owner)
     api = C.pythonapi
     api.PyCapsule_New.argtypes, api.PyCapsule_New.restype = [C.c_void_p, C.c_char_p, _PyCapsuleDestructor], C.py_object
     return api.PyCapsule_New(C.addressof(m), b'dltensor', _dl_capsule_destructor)
@@ -292,7 +306,7 @@ def _dlpack(self, stream=None, **kwargs):
     """DLPack export of a device buffer (zero-copy into torch / cupy / jax on ROCm).  The buffer belongs to the env handle
     (kept alive by the capsule) and is rewritten by every step on the library's stream: `stream` is accepted for protocol
     compatibility, ordering follows the stream contract of include/realrobot.h."""
-    return _dlpack_capsule(self.ptr, self.shape, self.typestr, getattr(self._owner, 'device', 0), self._owner)
+    return _dlpack_capsule(self.ptr, self.shape, self.typestr, getattr(self._owner, 'device', 0), self._owner, self.strides)
 
 
 DeviceBuffer.__dlpack__ = _dlpack

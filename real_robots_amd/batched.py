@@ -696,6 +696,102 @@ class BatchedREALRobotEnv:
         nat.check(self.L.rr_kinematic_observations(self.h))
         return {name: self.kinematic_buffer(i, host=host) for i, name in enumerate(nat.KIN_FIELDS)}
 
+    # ------------------------------------------------------------------ ray casts against the collision hulls
+    @staticmethod
+    def _rays_arg(links, segments=None):
+        """(links, segments) of `set_rays` -> (int32 [R], float32 [R, 6]); every argument error is a ValueError raised here, before
+        the native call.  A link is a name of LINK_NAMES, its index, or 'world' / -1 for the world frame."""
+        if isinstance(links, (str, int, np.integer)):
+            links = [links]
+        idx = []
+        for l in links:
+            if isinstance(l, str):
+                if l != 'world' and l not in nat.LINK_NAMES:
+                    raise ValueError("unknown link %r (known: world, %s)" % (l, ', '.join(nat.LINK_NAMES)))
+                l = -1 if l == 'world' else nat.LINK_NAMES.index(l)
+            elif not isinstance(l, (int, np.integer)) or isinstance(l, (bool, np.bool_)):
+                raise ValueError("a link is 'world', a name of LINK_NAMES or an index, not %r" % (l,))
+            if not -1 <= int(l) < len(nat.LINK_NAMES):
+                raise ValueError("link index %d is neither -1 (the world) nor in [0, %d)" % (int(l), len(nat.LINK_NAMES)))
+            idx.append(int(l))
+        if len(idx) > nat.RAY_MAX:
+            raise ValueError("%d rays: at most %d are allowed" % (len(idx), nat.RAY_MAX))
+        if segments is None:
+            seg = np.zeros((len(idx), 6), np.float32)
+        else:
+            try:
+                with np.errstate(over='ignore'):
+                    seg = np.ascontiguousarray(np.asarray(segments, dtype=np.float64).astype(np.float32))
+            except (ValueError, TypeError):
+                raise ValueError("segments must be an array of shape (%d, 6)" % len(idx))
+            if seg.shape != (len(idx), 6):
+                raise ValueError("segments must have shape (%d, 6), not %s" % (len(idx), seg.shape))
+            if not np.isfinite(seg).all():
+                raise ValueError("segments must be finite (in float32)")
+        return np.array(idx, np.int32), seg
+
+    def set_rays(self, links, segments=None):
+        """The ray table of `ray_cast` (rr_set_rays): up to 64 rays, each a frame -- 'world' / -1, or a robot link by name of
+        `_native.LINK_NAMES` or index: that link's COM frame, pybullet's parentLinkIndex -- and a default segment [R, 6] {from xyz,
+        to xyz} in that frame (None: zeros, for tables whose casts always bring their own segments).  A fresh env has no rays.  A
+        setting of the env, like the kinematic points: resets, `state`, forks and `restore` keep it."""
+        idx, seg = self._rays_arg(links, segments)
+        nat.check(self.L.rr_set_rays(self.h, len(idx), idx.ctypes.data, seg.ctypes.data))
+
+    def rays(self):
+        """(links int32 [R], segments float32 [R, 6]) in force (rr_get_rays)."""
+        n = C.c_int32()
+        idx, seg = np.zeros(nat.RAY_MAX, np.int32), np.zeros((nat.RAY_MAX, 6), np.float32)
+        nat.check(self.L.rr_get_rays(self.h, C.byref(n), idx.ctypes.data, seg.ctypes.data))
+        return idx[:n.value].copy(), seg[:n.value].copy()
+
+    def ray_buffer(self, name, host=False):
+        """One buffer of the ray casts as the LAST `ray_cast` call left it (all zero before the first), by name
+        (`_native.RAY_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait."""
+        which = nat.RAY_FIELDS.index(name) if isinstance(name, str) and name in nat.RAY_FIELDS else name
+        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.RAY_FIELDS):
+            raise ValueError("unknown ray buffer %r (known: %s)" % (name, ', '.join(nat.RAY_FIELDS)))
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(self.L.rr_ray_buffer(self.h, int(which), C.byref(p), C.byref(n)))
+        cols, dt = ((8, np.float32), (4, np.int32))[int(which)]
+        shape = (self.N, n.value // (4 * cols * self.N), cols)
+        if host:
+            out = np.empty(shape, dt)
+            nat.check(self.L.rr_ray_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
+            return out
+        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
+
+    def ray_cast(self, rays=None, host=False):
+        """pybullet's rayTestBatch for the whole batch (rr_ray_cast): one launch on the library's stream casts the R rays of
+        `set_rays` of every env against the collision hulls -- table, shelf, robot links, this env's objects -- at the present
+        state and returns
+          hit [N, R, 8] float32 -- {fraction, distance (m), x, y, z (world), nx, ny, nz (world, outward)} of the first hull hit; a
+              miss: fraction 1, the segment's length, its end point, a zero normal;
+          id [N, R, 4] int32 -- {uid as in the mask image, body as in the contact records, URDF link or -1, collision shape}; all -1
+              on a miss.
+        rays: None (the table's segments for every env) or float32 [N, R, 6] per-env segments in the frames of the table's links -- a
+        numpy array (checked finite, staged, synchronous) or a CUDA torch tensor / `__cuda_array_interface__` object, read in place
+        on the library's stream without waiting (produce it on that stream or synchronise first; values are not validated: a
+        non-finite segment is a miss).  A ray that starts inside a hull does not hit that hull (a sensor may sit inside its own
+        link).  Returns device buffers (zero copy, DLPack; valid after later work on the library's stream or `sync()`; they hold what
+        the last call computed -- steps do not refresh them), or with host=True numpy arrays after a sync."""
+        R = len(self.rays()[0])
+        if R == 0:
+            raise ValueError("ray_cast: the ray table is empty (set_rays)")
+        rp, on_dev, keep = (None, 0, None) if rays is None else self._state_arg(rays, 'rays', ('float32',), (self.N, R, 6))
+        nat.check(self.L.rr_ray_cast(self.h, rp, on_dev))
+        del keep
+        return {name: self.ray_buffer(i, host=host) for i, name in enumerate(nat.RAY_FIELDS)}
+
+    @staticmethod
+    def ray_column(buf, col):
+        """Column `col` of a buffer of `ray_cast` as [N, R]: a numpy view, or a strided device view (zero copy) of a device buffer."""
+        if isinstance(buf, np.ndarray):
+            return buf[:, :, col]
+        item = np.dtype(buf.typestr).itemsize
+        N, R, cols = buf.shape
+        return nat.DeviceBuffer(buf.ptr + col * item, (N, R), buf.typestr, buf._owner, strides=(R * cols * item, cols * item))
+
     def body_row_names(self):
         """The bodies of the rows of body_force / body_partners: the 17 URDF links, then this handle's objects (the rows of the
         objects it does not have, up to 20, stay zero)."""

@@ -83,6 +83,7 @@ struct ModelTables {
     IkModel IK = {};
     int n_inst_used = 0;
     int n_shapes = 0;
+    int shape_uid[MAXSHAPES] = {};   // the uid of every collision shape as in RR_F_MASK (the blob's shape_owner, column 3): RR_RAY_ID
     float table_pos[3] = {};       // target of the default eye camera (env.py:253-255)
     // per-env object dynamics (rr_set_object_dynamics): host copies every upload of D.obj_dyn / D.pair_mat is made from
     std::vector<float> dyn;        // [N][nobj][8] {mass, ixx, iyy, izz, lateral friction, restitution, rolling, spinning}
@@ -129,6 +130,12 @@ struct rr_env : ModelTables {
     int kin_np = 1;                // points in force: a fresh handle has link 8 (gripper `base`) at the origin of its COM frame
     KinPoints kin_pts = {{8}, {}};
     KinPoints *kin_pts_dev = nullptr;
+    // ray casts (rr_ray_cast): the two RR_RAY_* buffers and the staging of a host caller's segments, allocated together on first use for
+    // RR_RAY_MAX rays, once; the ray table is a setting of the handle like the points: a host copy and the device copy k_ray_cast reads
+    float4 *ray_hit = nullptr; int4 *ray_id = nullptr; float *ray_stage = nullptr;
+    int ray_n = 0;                 // rays in force: a fresh handle has none
+    RayTable ray_tab = {};
+    RayTable *ray_tab_dev = nullptr;
     MemOwner mem;                  // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
     bool created = false;
     bool timing = false;
@@ -409,7 +416,7 @@ static int parse_model(const rr_config &cfg, const Blob &b, const Settings &set,
     // shapes + pair table (same order as the oracle's collide())
     ShapeData &S = M.S;
     NEED(ip = b.i32("shape_owner", ns * 4));
-    for (int s = 0; s < ns; s++) { S.otype[s] = ip[4 * s]; S.oidx[s] = ip[4 * s + 1]; S.link[s] = ip[4 * s + 2]; }
+    for (int s = 0; s < ns; s++) { S.otype[s] = ip[4 * s]; S.oidx[s] = ip[4 * s + 1]; S.link[s] = ip[4 * s + 2]; M.shape_uid[s] = ip[4 * s + 3]; }
     NEED(ip = b.i32("shape_nv", ns)); memcpy(S.nv, ip, ns * 4);
     NEED(ip = b.i32("shape_nf", ns)); memcpy(S.nf, ip, ns * 4);
     NEED(f = b.f32("shape_verts", ns * VMAXC * 3)); memcpy(S.verts, f, (size_t)ns * VMAXC * 3 * 4);
@@ -1474,6 +1481,119 @@ int rr_kinematic_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes)
     RRCHK(ensure_kinematics(e, "rr_kinematic_copy_to_host"));
     HIPCHK(hipSetDevice(e->cfg.device));
     HIPCHK(hipMemcpyAsync(dst, e->kin[which], bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return RR_OK;
+}
+
+// ---- ray casts against the collision hulls (rr_ray.inc) ---------------------------------------------------------------------------------
+// The two buffers of rr_ray_cast, the staging of a host caller's segments and the device copy of the ray table: allocated on first
+// use -- by the cast or by rr_ray_buffer / rr_ray_copy_to_host -- in one list, zero-filled, for RR_RAY_MAX rays; the table in force
+// goes up behind it.
+static size_t ray_bytes(const rr_env *e, int which, int R) { return (size_t)e->P.N * R * (which == RR_RAY_HIT ? 32 : 16); }
+static int ensure_rays(rr_env *e, const char *who) {
+    if (e->ray_hit) return RR_OK;
+    if (e->RM.nl != KIN_LINKS) return fail(RR_EMODEL, std::string(who) + ": the model does not have the 17 URDF links of rr_link_poses");
+    for (int l = 0; l < KIN_LINKS; l++)
+        if (e->RM.link_body[l] >= NB) return fail(RR_EMODEL, std::string(who) + ": link " + std::to_string(l) + " of the model is on a body outside the kinematic tree");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    float4 *hit = nullptr; int4 *id = nullptr; float *stage = nullptr;
+    RayTable *td = nullptr;
+    RRCHK(mem_get(e, {mem_part(&hit, ray_bytes(e, RR_RAY_HIT, RR_RAY_MAX)), mem_part(&id, ray_bytes(e, RR_RAY_ID, RR_RAY_MAX)),
+                      mem_part(&stage, (size_t)e->P.N * RR_RAY_MAX * 24), mem_part(&td, sizeof(RayTable), false)},
+                  (std::string(who) + ": allocating the ray buffers").c_str()));
+    memcpy(e->ray_tab.uid, e->shape_uid, sizeof e->ray_tab.uid);
+    hipError_t rc = hipMemcpyAsync(td, &e->ray_tab, sizeof(RayTable), hipMemcpyHostToDevice, e->stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);      // (the source is the handle's own memory)
+    if (rc != hipSuccess) {
+        (void)hipStreamSynchronize(e->stream);
+        e->mem.release(hit); e->mem.release(id); e->mem.release(stage); e->mem.release(td);
+        (void)hipGetLastError();
+        return fail(RR_EDEVICE, std::string(who) + ": uploading the ray table: " + hipGetErrorString(rc));
+    }
+    e->ray_hit = hit; e->ray_id = id; e->ray_stage = stage; e->ray_tab_dev = td;
+    return RR_OK;
+}
+
+int rr_set_rays(rr_env *e, int32_t n_rays, const int32_t *link, const float *from_to) {
+    if (!e) return fail(RR_EINVAL, "rr_set_rays: null env");
+    if (n_rays < 0 || n_rays > RR_RAY_MAX)
+        return fail(RR_EINVAL, n_rays < 0 ? "rr_set_rays: n_rays " + std::to_string(n_rays) + " is negative"
+                                          : "rr_set_rays: n_rays " + std::to_string(n_rays) + ": ray " + std::to_string(RR_RAY_MAX) + " is beyond RR_RAY_MAX (" +
+                                                std::to_string(RR_RAY_MAX) + ")");
+    if (n_rays > 0 && !link) return fail(RR_EINVAL, "rr_set_rays: null link array");
+    RayTable T = {};
+    memcpy(T.uid, e->shape_uid, sizeof T.uid);
+    for (int j = 0; j < n_rays; j++) {
+        if (link[j] < -1 || link[j] >= KIN_LINKS)
+            return fail(RR_EINVAL, "rr_set_rays: ray " + std::to_string(j) + ": link " + std::to_string(link[j]) + " is neither -1 (the world) nor in [0, " + std::to_string(KIN_LINKS) + ")");
+        T.link[j] = link[j];
+        for (int k = 0; k < 6; k++) {
+            const float v = from_to ? from_to[6 * j + k] : 0.0f;
+            if (!std::isfinite(v)) return fail(RR_EINVAL, "rr_set_rays: ray " + std::to_string(j) + ": from_to is not finite");
+            T.seg[j][k] = v;
+        }
+    }
+    for (int j = n_rays; j < RR_RAY_MAX; j++) T.link[j] = -1;
+    if (e->ray_tab_dev) {      // (before the buffers exist the host copy is all there is: ensure_rays uploads it)
+        HIPCHK(hipSetDevice(e->cfg.device));
+        HIPCHK(hipStreamSynchronize(e->stream));      // a cast enqueued earlier still reads the earlier table
+        HIPCHK(hipMemcpy(e->ray_tab_dev, &T, sizeof T, hipMemcpyHostToDevice));
+    }
+    e->ray_tab = T; e->ray_n = n_rays;
+    return RR_OK;
+}
+
+int rr_get_rays(rr_env *e, int32_t *n_rays, int32_t *link_out, float *from_to_out) {
+    if (!e) return fail(RR_EINVAL, "rr_get_rays: null env");
+    if (n_rays) *n_rays = e->ray_n;
+    if (link_out) memcpy(link_out, e->ray_tab.link, (size_t)e->ray_n * 4);
+    if (from_to_out) memcpy(from_to_out, e->ray_tab.seg, (size_t)e->ray_n * 24);
+    return RR_OK;
+}
+
+// rayTestBatch for the whole batch, on the device.  On the main stream like rr_kinematic_observations: behind every step, reset and
+// state write enqueued before it.  Reads D.state and the model only -- never the scratch slab of the look-ahead -- and leaves la_valid
+// and the error flags alone.
+int rr_ray_cast(rr_env *e, const float *rays, int32_t on_device) {
+    if (!e) return fail(RR_EINVAL, "rr_ray_cast: null env");
+    const int R = e->ray_n, N = e->P.N;
+    if (R == 0) return fail(RR_EINVAL, "rr_ray_cast: the ray table is empty (rr_set_rays)");
+    if (rays && !on_device)
+        for (size_t i = 0; i < (size_t)N * R * 6; i++)
+            if (!std::isfinite(rays[i]))
+                return fail(RR_EINVAL, "rr_ray_cast: env " + std::to_string(i / ((size_t)R * 6)) + ", ray " + std::to_string(i / 6 % R) + ": the segment is not finite");
+    RRCHK(ensure_rays(e, "rr_ray_cast"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const float *seg = rays;
+    if (rays && !on_device) {
+        HIPCHK(hipMemcpyAsync(e->ray_stage, rays, (size_t)N * R * 24, hipMemcpyHostToDevice, e->stream));
+        seg = e->ray_stage;
+    }
+    hipLaunchKernelGGL(k_ray_cast, dim3((N + RAY_ENVS - 1) / RAY_ENVS), dim3(RAY_THREADS), 0, e->stream, e->B, e->P, e->RM_dev, e->D, e->n_shapes,
+                       e->ray_tab_dev, seg, R, e->ray_hit, e->ray_id);
+    HIPCHK(hipGetLastError());
+    if (rays && !on_device) HIPCHK(hipStreamSynchronize(e->stream));   // the argument is host memory
+    return RR_OK;
+}
+
+int rr_ray_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_ray_buffer: null env");
+    if (which < 0 || which >= RR_RAY_COUNT) return fail(RR_EINVAL, "rr_ray_buffer: buffer " + std::to_string(which) + " is not in [0, RR_RAY_COUNT)");
+    RRCHK(ensure_rays(e, "rr_ray_buffer"));
+    if (dev_ptr) *dev_ptr = which == RR_RAY_HIT ? (void *)e->ray_hit : (void *)e->ray_id;
+    if (bytes) *bytes = ray_bytes(e, which, e->ray_n);
+    return RR_OK;
+}
+
+int rr_ray_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_ray_copy_to_host: null env");
+    if (!dst) return fail(RR_EINVAL, "rr_ray_copy_to_host: null destination");
+    if (which < 0 || which >= RR_RAY_COUNT) return fail(RR_EINVAL, "rr_ray_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_RAY_COUNT)");
+    if (bytes != ray_bytes(e, which, e->ray_n)) return fail(RR_EINVAL, "rr_ray_copy_to_host: size mismatch");
+    RRCHK(ensure_rays(e, "rr_ray_copy_to_host"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    if (bytes == 0) return RR_OK;
+    HIPCHK(hipMemcpyAsync(dst, which == RR_RAY_HIT ? (void *)e->ray_hit : (void *)e->ray_id, bytes, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return RR_OK;
 }

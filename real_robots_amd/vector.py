@@ -53,7 +53,13 @@ unbounded; BatchedREALRobotEnv.kinematic_observations) to the observation dict a
 gathered, device views or host copies by `device_obs`.  `kinematic_points=` is a sequence of links (names or indices), or a pair
 (links, local_pos [P, 3]); the default is the one point of a fresh handle, the gripper base.  `jacobian @ _native.Q_FROM_CMD` is the
 Jacobian over the nine entries of `joint_command`.  The default leaves dict and spaces as they are.  These two arguments and the ones
-behind them (`contact_obs`, `goals`, `goal_stride`) are keyword-only.
+behind them (`ray_sensors`, `contact_obs`, `goals`, `goal_stride`) are keyword-only.
+Ray sensors: `ray_sensors=(links, segments)` -- the arguments of BatchedREALRobotEnv.set_rays: R links (names, indices, 'world' / -1)
+and segments [R, 6] {from xyz, to xyz} in those links' COM frames -- casts the table against the collision hulls where the other
+entries are gathered (BatchedREALRobotEnv.ray_cast: pybullet's rayTestBatch) and adds `ray_distance` [N, R] (float32, metres along the
+ray to the first hit; the segment's length on a miss) and `ray_uid` [N, R] (int32, the uid of the mask image; -1 on a miss) to the
+observation dict and to the spaces.  With `device_obs` they are strided device views (DLPack / `__cuda_array_interface__`) of the
+cast's two buffers.  The default leaves dict and spaces as they are.
 Goals: `goals=` (the path of a goals dataset, or a list of `Goal` objects) with `goal_stride=` puts the goal table and the episode
 record on the device (BatchedREALRobotEnv.set_goals_from / episode_update; evaluateGoal, env.py:181-200).  reset() gives env i the
 goal i mod G and starts it from that goal's start poses; every step() returns as rewards the change of the env's goal score over
@@ -103,7 +109,7 @@ class REALRobotVectorEnv(_Base):
     def __init__(self, num_envs, objects=3, additional_obs=False, eye_width=320, eye_height=240, device=0,
                  max_episode_steps=int(15e6), render_every_step=True, device_obs=False, solver=None, dynamics_randomization=None,
                  camera_randomization=None, appearance_randomization=None, actuator_randomization=None, *, kinematic_obs=False,
-                 kinematic_points=None, contact_obs=False, goals=None, goal_stride=1):
+                 kinematic_points=None, ray_sensors=None, contact_obs=False, goals=None, goal_stride=1):
         self.num_envs = int(num_envs)
         self._goals = None if goals is None else self._check_goals(goals, OBJECT_NAMES[:int(objects)], int(eye_height), int(eye_width))
         self.goal_stride = int(goal_stride)
@@ -132,6 +138,19 @@ class REALRobotVectorEnv(_Base):
                 joint_velocities=box(nat.N_JOINTS), link_poses=box(n_links, 7), link_velocities=box(n_links, 6),
                 object_velocities=box(int(objects), 6), point_positions=box(n_pts, 3), point_velocities=box(n_pts, 6),
                 jacobian=box(n_pts, 6, nat.N_JOINTS)))
+        ray_table = None
+        if ray_sensors is not None:
+            if not (isinstance(ray_sensors, (tuple, list)) and len(ray_sensors) == 2):
+                raise ValueError("ray_sensors is a pair (links, segments [R, 6])")
+            ray_table = BatchedREALRobotEnv._rays_arg(*ray_sensors)
+            n_rays = len(ray_table[0])
+            if n_rays == 0:
+                raise ValueError("ray_sensors: at least one ray")
+            self.single_observation_space = spaces.Dict(dict(
+                self.single_observation_space.spaces,
+                ray_distance=spaces.Box(low=0.0, high=np.inf, shape=(n_rays,), dtype=np.float32),
+                ray_uid=spaces.Box(low=-1, high=np.iinfo(np.int32).max, shape=(n_rays,), dtype=np.int32)))
+        self.ray_sensors = ray_table is not None
         # batched spaces = the single spaces with a leading env axis (gymnasium.vector.utils.batch_space)
         self.action_space = spaces.Dict({
             "joint_command": spaces.Box(low=np.tile(self._robot.min_joints, (self.num_envs, 1)),
@@ -145,6 +164,8 @@ class REALRobotVectorEnv(_Base):
                                        want_mask=additional_obs, solver=solver)
         if kin_points is not None:
             self._be.set_kinematic_points(*kin_points)
+        if ray_table is not None:
+            self._be.set_rays(*ray_table)
         # host-side episode clocks (no device read-back per step): the batched env behind this adapter is private to it, every
         # path that resets an env goes through reset() / step() below and resets its clock with it
         self._steps = np.zeros(self.num_envs, np.int64)
@@ -363,6 +384,9 @@ class REALRobotVectorEnv(_Base):
             ko = be.kinematic_observations(host=not self.device_obs)
             for key, name in self.KINEMATIC_KEYS:
                 obs[key] = ko[name]
+        if self.ray_sensors:
+            rc = be.ray_cast(host=not self.device_obs)
+            obs["ray_distance"], obs["ray_uid"] = be.ray_column(rc['hit'], 1), be.ray_column(rc['id'], 0)
         if self._goals is not None:
             if self._goal_images:
                 obs["goal"] = be.episode_buffer('goal_rgb', host=not self.device_obs)
