@@ -37,13 +37,14 @@ extern "C" {
                               rr_kinematic_buffer, rr_kinematic_copy_to_host (link states and Jacobians of the whole batch); rr_write_state,
                               rr_read_state (masked state writes by column groups -- resets, teleports, postures, velocity kicks -- and state
                               reads on the device); rr_set_rays, rr_get_rays, rr_ray_cast, rr_ray_buffer, rr_ray_copy_to_host (segments of
-                              the whole batch against the collision hulls) */
+                              the whole batch against the collision hulls); rr_set_distance_pairs, rr_get_distance_pairs, rr_closest_points,
+                              rr_distance_buffer, rr_distance_copy_to_host (distance and closest points of pairs of collision hulls) */
 
 enum {
     RR_OK = 0,
     RR_EINVAL = -1,     /* bad argument */
     RR_EDEVICE = -2,    /* HIP runtime error (no GPU, out of memory, launch failure).  Memory that a call allocates on first use
-                           (contact and kinematic observations, ray casts, goal scores, plans and IK, per-env cameras and appearance, goal table and episode
+                           (contact and kinematic observations, ray casts, closest points, goal scores, plans and IK, per-env cameras and appearance, goal table and episode
                            record, snapshot slots and fork staging, mapped host blocks, the staging ring) is allocated all or nothing:
                            when that fails the call returns RR_EDEVICE, nothing has changed -- what the call would replace is kept --
                            and the handle stays usable; a later call tries again. */
@@ -620,6 +621,77 @@ int rr_ray_cast(rr_env *env, const float *rays, int32_t on_device);
 int rr_ray_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
 /* Synchronising copy of a whole RR_RAY_* buffer (its `bytes`) to host memory. */
 int rr_ray_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
+
+/* ---- Closest points between collision hulls on the device (additive in ABI 7) --------------------------------------------------------
+ * Replaces pybullet's getClosestPoints(bodyA, bodyB, distance, linkIndexA, linkIndexB) for ALL envs at once and on the device: "how
+ * far apart are these two bodies, and where are the nearest points" -- clearance costs of rollouts on forked envs, reach and grasp
+ * shaping by the surface distance of a pad and an object, early termination on a keep-out distance.  One launch on the library's
+ * stream (rr_closest_points) computes Q pairs of collision shapes per env -- the convex shapes the step's collision pass uses: table,
+ * shelf, the robot's links, the handle's objects -- at the present state and writes two device buffers.  They are NOT fields of
+ * rr_get_buffer (RR_F_COUNT stays 16): they have this enum and rr_distance_buffer, like the ray casts. */
+enum {
+    RR_DIST_POINTS = 0,   /* f32 [N, Q, 12] {distance (m), lower bound (m), a xyz, b xyz (world), n xyz (world, from b towards a), +0.0} */
+    RR_DIST_ID = 1,       /* i32 [N, Q, 4]  {status, iterations, body A, body B}: bodies as in the contact records (-1 static, 0..15 robot
+                                             body, 16 + i object i) */
+    RR_DIST_COUNT = 2
+};
+#define RR_DIST_MAX 96      /* = the model's pair capacity: the step's whole collision table fits */
+/* The pair table: Q = n_pairs pairs in [0, RR_DIST_MAX].  Pair j is two collision-shape indices shape_a[j], shape_b[j] (i32 [Q],
+ * host): the index is column 3 of RR_RAY_ID, the order of the model blob's shape_owner.  A fresh handle has Q = 0.  n_pairs == -1
+ * (the arrays are ignored) installs the step's own collision pairs in list order -- every object x every static shape, object x
+ * object, every moving robot shape x table and shelf, every moving robot shape x every object; pairs of objects the handle does not
+ * have are left out (92 pairs at three objects).  max_distance (m) is the cull: a pair whose bounding spheres are further apart gets
+ * status 2 instead of a search; max_distance <= 0 or +inf: no cull.  n_pairs out of range, an index outside the model's shapes,
+ * a == b, a shape of an object >= n_objects, a NaN max_distance or a null array with n_pairs > 0 returns RR_EINVAL -- the message
+ * names the pair -- and the table in force stays as it is.  The table is a setting of the handle, like the rays: rr_reset,
+ * rr_set_state, rr_write_state, rr_copy_envs and rr_checkpoint_restore keep it and checkpoints do not carry it.  Synchronous (it waits
+ * for the library's stream: a query enqueued earlier still sees the earlier table) and launches nothing; after a change the two
+ * buffers hold unspecified data until the next rr_closest_points. */
+int rr_set_distance_pairs(rr_env *env, int32_t n_pairs, const int32_t *shape_a, const int32_t *shape_b, float max_distance);
+/* The table in force: *n_pairs, shape_a_out / shape_b_out i32 [Q] (room for RR_DIST_MAX), *max_distance_out; each output may be NULL. */
+int rr_get_distance_pairs(rr_env *env, int32_t *n_pairs, int32_t *shape_a_out, int32_t *shape_b_out, float *max_distance_out);
+/* One launch on the library's stream computes the Q pairs of every env at the PRESENT state -- whatever the last step, reset,
+ * rr_set_state, rr_write_state, rr_set_object_pose(s), rr_copy_envs or restore left -- and writes the two buffers; the call checks the
+ * launch and returns without waiting.  The kernel does its own forward kinematics from the state: it reads the state, the model and
+ * the table only, not the preparation record (RR_F_PREP), changes no error flag, the next step stays prepared and no later step is
+ * affected.  The buffers hold what the LAST CALL computed: steps do not refresh them.  Q == 0: RR_EINVAL.
+ * Semantics.  A shape is the CONVEX HULL OF ITS VERTEX SET (up to 192 vertices, the blob's shape_verts) -- not the intersection of its
+ * planes, which the model compiler fitted within 0.3 mm of the vertices and which the ray casts and the step's collision pass use.
+ * A shape's frame is that of rr_ray_cast: the identity for the statics (table, shelf, the robot's fixed base), the body frame of the
+ * step's forward kinematics for a robot shape, and the object's pose for an object, with the rotation the step forms from the
+ * quaternion.  The out-of-bounds re-pose of the step is not applied: the state is taken as it is.
+ * distance is the Euclidean distance of the two hulls; a and b are world points of A and B that realise it (|a - b| = distance; the
+ * points need not be unique, the vector a - b is); n = (a - b) / distance is the unit vector from b towards a, pybullet's
+ * contactNormalOnB; lower bound is a value the search has proved <= the distance, from the support plane of its last directions:
+ * distance - lower bound bounds the error of distance from above.  status:
+ *   0  separated and converged: the fields as above;
+ *   1  overlapping or touching (a distance of at most 1e-6 m counts as touching): distance = lower bound = 0, n = +0.0, a = b = some
+ *      finite point.  PENETRATION DEPTH IS OUT OF SCOPE: inside the 2 cm margin the contact records (rr_contact_observations) carry
+ *      it; there is no negative distance;
+ *   2  culled: the gap of the two bounding spheres (the blob's shape_sphere, which hold the vertices) exceeds max_distance; distance =
+ *      lower bound = that gap (a true lower bound of the hull distance), a and b the points of the spheres on the line of their
+ *      centres, n along the centres; iterations = 0;
+ *   3  the iteration cap (32) was reached: distance is an upper bound (|a - b| of two points of the hulls), lower bound the best
+ *      bound proved.
+ * The search is GJK in float32 on the vertex sets.  It ends with status 0 when (distance - lower bound) <= 1e-12 distance (squared norms are summed in float64), when the
+ * support vertex pair is already in the simplex, or when rounding allows no nearer point.  Support ties go to the lowest vertex
+ * index, reductions run in a fixed order, there are no atomics: the result is a function of the state and the table alone,
+ * identical from call to call, independent of N, of the env's position in the batch and of its neighbours; row (env, j) depends on
+ * pair j alone, so a permuted table gives permuted rows.  Every loop bound is a constant or a model count, never data: an env
+ * whose state is not finite is computed like any other and finishes like any other; its rows are unspecified.  No state value ever
+ * forms an address.
+ * Both buffers are allocated on first use -- by this call, or by rr_distance_buffer / rr_distance_copy_to_host --, all or nothing,
+ * zero-filled, once for RR_DIST_MAX pairs, and valid until rr_destroy: no pointer ever changes.  Their layout is compact [N, Q, ...]
+ * for the Q in force, and `bytes` reports that size.  STREAM CONTRACT as for the other zero-copy views (rr_step, rr_ray_cast): the
+ * kernel runs on the library's stream behind the work enqueued before it; readers on another stream order themselves after the call
+ * (event / rr_sync), and a later call rewrites the buffers in place.
+ * Out of scope: penetration depth and negative distances, an all-pairs broad phase, groups of shapes reduced on the device (a min
+ * over columns in the caller's tensor program does it), points in body frames, the render meshes, refreshing from inside a step. */
+int rr_closest_points(rr_env *env);
+/* Zero-copy device pointer + size in bytes of an RR_DIST_* buffer (read-only for the caller); which outside [0, RR_DIST_COUNT): RR_EINVAL. */
+int rr_distance_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
+/* Synchronising copy of a whole RR_DIST_* buffer (its `bytes`) to host memory. */
+int rr_distance_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
 
 /* Batched damped-least-squares inverse kinematics for link 7 (gripper `base`), seeded with each env's current joints.
  * Replaces pybullet.calculateInverseKinematics(0, 7, pos, orn, maxNumIterations=1000, residualThreshold=0.001) in

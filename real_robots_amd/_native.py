@@ -40,7 +40,8 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_snapshot_slots', 'rr_copy_envs',
            'rr_set_kinematic_points', 'rr_get_kinematic_points', 'rr_kinematic_observations', 'rr_kinematic_buffer', 'rr_kinematic_copy_to_host',
            'rr_write_state', 'rr_read_state',
-           'rr_set_rays', 'rr_get_rays', 'rr_ray_cast', 'rr_ray_buffer', 'rr_ray_copy_to_host')
+           'rr_set_rays', 'rr_get_rays', 'rr_ray_cast', 'rr_ray_buffer', 'rr_ray_copy_to_host',
+           'rr_set_distance_pairs', 'rr_get_distance_pairs', 'rr_closest_points', 'rr_distance_buffer', 'rr_distance_copy_to_host')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
@@ -65,6 +66,10 @@ Q_FROM_CMD[[8, 10], 8] = -1.0
 # link, shape} (all -1 on a miss), for the R rays in force (rr_set_rays)
 RAY_FIELDS = ('hit', 'id')
 RAY_MAX = 64
+# buffers of rr_distance_buffer (the RR_DIST_* enum), per env and pair: points [12] f32 {distance, lower bound, a xyz, b xyz, n xyz, +0.0},
+# id [4] i32 {status, iterations, body A, body B}, for the Q pairs in force (rr_set_distance_pairs)
+DIST_FIELDS = ('points', 'id')
+DIST_MAX = 96
 SLOT_LIVE, MAX_SLOTS = -1, 64           # RR_SLOT_LIVE: the running envs as a slot number of rr_copy_envs; RR_MAX_SLOTS
 # `parts` of rr_write_state (the RR_W_* bits): the column groups of the 61-float state row that are written, a reset in front of them,
 # the fresh-start clean-up of rr_set_state behind them
@@ -202,6 +207,11 @@ def load_library():
     L.rr_ray_cast.argtypes = [vp, vp, i32]
     L.rr_ray_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rr_ray_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
+    L.rr_set_distance_pairs.argtypes = [vp, i32, vp, vp, C.c_float]
+    L.rr_get_distance_pairs.argtypes = [vp, C.POINTER(i32), vp, vp, C.POINTER(C.c_float)]
+    L.rr_closest_points.argtypes = [vp]
+    L.rr_distance_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rr_distance_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]

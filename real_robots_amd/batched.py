@@ -792,6 +792,132 @@ class BatchedREALRobotEnv:
         N, R, cols = buf.shape
         return nat.DeviceBuffer(buf.ptr + col * item, (N, R), buf.typestr, buf._owner, strides=(R * cols * item, cols * item))
 
+    # ------------------------------------------------------------------ closest points between collision hulls
+    @staticmethod
+    def collision_shapes():
+        """One row per collision shape of the model, in the order of the shape indices (column 3 of the ray casts' `id`): a list of
+        dicts {index, uid (as in the mask image), body (as in the contact records: -1 static, 0..15 robot body, 16 + i object i),
+        link (URDF link or -1), name}.  The name is the link's name of `_native.LINK_NAMES`, or 'table' / 'shelf' / 'robot_base' for
+        the statics, or 'cube' / 'tomato' / 'mustard'."""
+        from .model import load_model
+        scenery = iter(('table', 'shelf'))
+        rows = []
+        for s, (kind, idx, link, uid) in enumerate(np.array(load_model()['shape_owner']).tolist()):
+            if kind == 0:
+                name = 'robot_base' if link >= 0 else next(scenery)
+            else:
+                name = nat.LINK_NAMES[link] if kind == 1 else OBJECT_NAMES[idx]
+            rows.append(dict(index=s, uid=uid, body=-1 if kind == 0 else idx if kind == 1 else 16 + idx, link=link, name=name))
+        return rows
+
+    @staticmethod
+    def _distance_arg(pairs, max_distance=None, n_objects=3):
+        """(pairs, max_distance) of `set_distance_pairs` -> (n_pairs, int32 [Q], int32 [Q], float); every argument error is a
+        ValueError raised here, before the native call.  pairs: 'collision' (n_pairs = -1: the step's own collision pairs), or a
+        sequence of (a, b), each a shape by name of `collision_shapes()` or by index."""
+        md = 0.0 if max_distance is None else max_distance
+        if isinstance(md, (bool, np.bool_, str)) or not isinstance(md, (int, float, np.integer, np.floating)) or np.isnan(md):
+            raise ValueError("max_distance is None or a number of metres (<= 0 or inf: no cull), not %r" % (max_distance,))
+        md = float(np.float32(md))
+        empty = np.zeros(0, np.int32)
+        if isinstance(pairs, str):
+            if pairs != 'collision':
+                raise ValueError("pairs is 'collision' or a sequence of (shape a, shape b), not %r" % (pairs,))
+            return -1, empty, empty, md
+        shapes = BatchedREALRobotEnv.collision_shapes()
+        names = {r['name']: r['index'] for r in shapes}
+        out = []
+        try:
+            pairs = list(pairs)
+        except TypeError:
+            raise ValueError("pairs is 'collision' or a sequence of (shape a, shape b), not %r" % (pairs,))
+        if len(pairs) > nat.DIST_MAX:
+            raise ValueError("%d pairs: at most %d are allowed" % (len(pairs), nat.DIST_MAX))
+        for j, pr in enumerate(pairs):
+            if isinstance(pr, (str, bytes)) or not hasattr(pr, '__len__') or len(pr) != 2:
+                raise ValueError("pair %d: a pair is (shape a, shape b), not %r" % (j, pr))
+            ab = []
+            for x in pr:
+                if isinstance(x, str):
+                    if x not in names:
+                        raise ValueError("pair %d: unknown shape %r (known: %s)" % (j, x, ', '.join(names)))
+                    x = names[x]
+                elif not isinstance(x, (int, np.integer)) or isinstance(x, (bool, np.bool_)):
+                    raise ValueError("pair %d: a shape is a name of collision_shapes() or an index, not %r" % (j, x))
+                if not 0 <= int(x) < len(shapes):
+                    raise ValueError("pair %d: shape index %d is not in [0, %d)" % (j, int(x), len(shapes)))
+                if shapes[int(x)]['body'] >= 16 + int(n_objects):
+                    raise ValueError("pair %d: shape %d (%s) belongs to an object this env (%d objects) does not have"
+                                     % (j, int(x), shapes[int(x)]['name'], int(n_objects)))
+                ab.append(int(x))
+            if ab[0] == ab[1]:
+                raise ValueError("pair %d: a == b (shape %d)" % (j, ab[0]))
+            out.append(ab)
+        arr = np.array(out, np.int32).reshape(-1, 2)
+        return len(out), np.ascontiguousarray(arr[:, 0]), np.ascontiguousarray(arr[:, 1]), md
+
+    def set_distance_pairs(self, pairs, max_distance=None):
+        """The pair table of `closest_points` (rr_set_distance_pairs): up to 96 pairs (a, b) of collision shapes, each by name
+        (`collision_shapes()`: a link's name, 'table', 'shelf', 'robot_base', 'cube', 'tomato', 'mustard') or by index; or
+        'collision' for the step's own collision pairs in list order.  max_distance (m): pairs whose bounding spheres are further
+        apart are culled (status 2); None, <= 0 or inf: no cull.  A fresh env has no pairs.  A setting of the env, like the rays:
+        resets, `state`, forks and `restore` keep it."""
+        n, a, b, md = self._distance_arg(pairs, max_distance, self.n_objects)
+        nat.check(self.L.rr_set_distance_pairs(self.h, n, a.ctypes.data if n > 0 else None, b.ctypes.data if n > 0 else None, md))
+
+    def distance_pairs(self):
+        """(pairs int32 [Q, 2], max_distance) in force (rr_get_distance_pairs)."""
+        n, md = C.c_int32(), C.c_float()
+        a, b = np.zeros(nat.DIST_MAX, np.int32), np.zeros(nat.DIST_MAX, np.int32)
+        nat.check(self.L.rr_get_distance_pairs(self.h, C.byref(n), a.ctypes.data, b.ctypes.data, C.byref(md)))
+        return np.stack([a[:n.value], b[:n.value]], 1), md.value
+
+    def distance_buffer(self, name, host=False):
+        """One buffer of the closest points as the LAST `closest_points` call left it (all zero before the first), by name
+        (`_native.DIST_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait."""
+        which = nat.DIST_FIELDS.index(name) if isinstance(name, str) and name in nat.DIST_FIELDS else name
+        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.DIST_FIELDS):
+            raise ValueError("unknown distance buffer %r (known: %s)" % (name, ', '.join(nat.DIST_FIELDS)))
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(self.L.rr_distance_buffer(self.h, int(which), C.byref(p), C.byref(n)))
+        cols, dt = ((12, np.float32), (4, np.int32))[int(which)]
+        shape = (self.N, n.value // (4 * cols * self.N), cols)
+        if host:
+            out = np.empty(shape, dt)
+            nat.check(self.L.rr_distance_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
+            return out
+        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
+
+    @staticmethod
+    def distance_columns(pts, ids):
+        """The named columns of the two buffers of `closest_points`: numpy views, or strided device views (zero copy)."""
+        if isinstance(pts, np.ndarray):
+            cut = lambda lo: pts[:, :, lo:lo + 3]
+        else:
+            N, Q, cols = pts.shape
+            cut = lambda lo: nat.DeviceBuffer(pts.ptr + 4 * lo, (N, Q, 3), pts.typestr, pts._owner, strides=(Q * cols * 4, cols * 4, 4))
+        col = BatchedREALRobotEnv.ray_column
+        return dict(distance=col(pts, 0), lower=col(pts, 1), point_a=cut(2), point_b=cut(5), normal=cut(8), status=col(ids, 0),
+                    iterations=col(ids, 1), body_a=col(ids, 2), body_b=col(ids, 3))
+
+    def closest_points(self, host=False):
+        """pybullet's getClosestPoints for the whole batch (rr_closest_points): one launch on the library's stream computes the Q
+        pairs of `set_distance_pairs` of every env at the present state and returns, as [N, Q] (the points and the normal [N, Q, 3])
+        columns of the two buffers,
+          distance float32 -- Euclidean distance (m) of the convex hulls of the two shapes' vertex sets; 0 when they overlap or touch
+              (no penetration depth: inside the 2 cm margin the contact records carry it);
+          lower float32 -- a proved lower bound of the distance (distance - lower bounds the error from above);
+          point_a, point_b float32 -- world points of A and B that realise the distance; normal -- the unit vector from b to a;
+          status int32 -- 0 separated, 1 overlapping or touching, 2 culled by max_distance (distance is the bounding spheres' gap),
+              3 iteration cap reached (distance is an upper bound); iterations int32; body_a, body_b int32 -- as in the contact
+              records.
+        Device views (zero copy, strided, DLPack; valid after later work on the library's stream or `sync()`; they hold what the last
+        call computed -- steps do not refresh them), or with host=True numpy views of host copies after a sync."""
+        if len(self.distance_pairs()[0]) == 0:
+            raise ValueError("closest_points: the pair table is empty (set_distance_pairs)")
+        nat.check(self.L.rr_closest_points(self.h))
+        return self.distance_columns(self.distance_buffer(0, host=host), self.distance_buffer(1, host=host))
+
     def body_row_names(self):
         """The bodies of the rows of body_force / body_partners: the 17 URDF links, then this handle's objects (the rows of the
         objects it does not have, up to 20, stay zero)."""

@@ -84,6 +84,7 @@ struct ModelTables {
     int n_inst_used = 0;
     int n_shapes = 0;
     int shape_uid[MAXSHAPES] = {};   // the uid of every collision shape as in RR_F_MASK (the blob's shape_owner, column 3): RR_RAY_ID
+    int shape_kind[MAXSHAPES] = {}, shape_idx[MAXSHAPES] = {};   // owner of every collision shape (0 static, 1 robot body, 2 object; its index): rr_set_distance_pairs
     float table_pos[3] = {};       // target of the default eye camera (env.py:253-255)
     // per-env object dynamics (rr_set_object_dynamics): host copies every upload of D.obj_dyn / D.pair_mat is made from
     std::vector<float> dyn;        // [N][nobj][8] {mass, ixx, iyy, izz, lateral friction, restitution, rolling, spinning}
@@ -136,6 +137,12 @@ struct rr_env : ModelTables {
     int ray_n = 0;                 // rays in force: a fresh handle has none
     RayTable ray_tab = {};
     RayTable *ray_tab_dev = nullptr;
+    // closest points (rr_closest_points): the two RR_DIST_* buffers, allocated together on first use for RR_DIST_MAX pairs, once; the pair
+    // table is a setting of the handle like the rays: a host copy and the device copy k_closest_points reads
+    float4 *dist_pts = nullptr; int4 *dist_id = nullptr;
+    int dist_n = 0;                // pairs in force: a fresh handle has none
+    DistTable dist_tab = {};
+    DistTable *dist_tab_dev = nullptr;
     MemOwner mem;                  // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
     bool created = false;
     bool timing = false;
@@ -416,7 +423,7 @@ static int parse_model(const rr_config &cfg, const Blob &b, const Settings &set,
     // shapes + pair table (same order as the oracle's collide())
     ShapeData &S = M.S;
     NEED(ip = b.i32("shape_owner", ns * 4));
-    for (int s = 0; s < ns; s++) { S.otype[s] = ip[4 * s]; S.oidx[s] = ip[4 * s + 1]; S.link[s] = ip[4 * s + 2]; M.shape_uid[s] = ip[4 * s + 3]; }
+    for (int s = 0; s < ns; s++) { S.otype[s] = ip[4 * s]; S.oidx[s] = ip[4 * s + 1]; S.link[s] = ip[4 * s + 2]; M.shape_uid[s] = ip[4 * s + 3]; M.shape_kind[s] = ip[4 * s]; M.shape_idx[s] = ip[4 * s + 1]; }
     NEED(ip = b.i32("shape_nv", ns)); memcpy(S.nv, ip, ns * 4);
     NEED(ip = b.i32("shape_nf", ns)); memcpy(S.nf, ip, ns * 4);
     NEED(f = b.f32("shape_verts", ns * VMAXC * 3)); memcpy(S.verts, f, (size_t)ns * VMAXC * 3 * 4);
@@ -1594,6 +1601,111 @@ int rr_ray_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
     HIPCHK(hipSetDevice(e->cfg.device));
     if (bytes == 0) return RR_OK;
     HIPCHK(hipMemcpyAsync(dst, which == RR_RAY_HIT ? (void *)e->ray_hit : (void *)e->ray_id, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return RR_OK;
+}
+
+// ---- closest points between collision hulls (rr_dist.inc) ------------------------------------------------------------------------------
+// The two buffers of rr_closest_points and the device copy of the pair table: allocated on first use -- by the query or by
+// rr_distance_buffer / rr_distance_copy_to_host -- in one list, zero-filled, for RR_DIST_MAX pairs; the table in force goes up behind it.
+static size_t dist_bytes(const rr_env *e, int which, int Q) { return (size_t)e->P.N * Q * (which == RR_DIST_POINTS ? 48 : 16); }
+static int ensure_dist(rr_env *e, const char *who) {
+    if (e->dist_pts) return RR_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    float4 *pts = nullptr; int4 *id = nullptr;
+    DistTable *td = nullptr;
+    RRCHK(mem_get(e, {mem_part(&pts, dist_bytes(e, RR_DIST_POINTS, RR_DIST_MAX)), mem_part(&id, dist_bytes(e, RR_DIST_ID, RR_DIST_MAX)),
+                      mem_part(&td, sizeof(DistTable), false)},
+                  (std::string(who) + ": allocating the distance buffers").c_str()));
+    hipError_t rc = hipMemcpyAsync(td, &e->dist_tab, sizeof(DistTable), hipMemcpyHostToDevice, e->stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);      // (the source is the handle's own memory)
+    if (rc != hipSuccess) {
+        (void)hipStreamSynchronize(e->stream);
+        e->mem.release(pts); e->mem.release(id); e->mem.release(td);
+        (void)hipGetLastError();
+        return fail(RR_EDEVICE, std::string(who) + ": uploading the pair table: " + hipGetErrorString(rc));
+    }
+    e->dist_pts = pts; e->dist_id = id; e->dist_tab_dev = td;
+    return RR_OK;
+}
+
+int rr_set_distance_pairs(rr_env *e, int32_t n_pairs, const int32_t *shape_a, const int32_t *shape_b, float max_distance) {
+    if (!e) return fail(RR_EINVAL, "rr_set_distance_pairs: null env");
+    if (n_pairs < -1 || n_pairs > RR_DIST_MAX)
+        return fail(RR_EINVAL, n_pairs < 0 ? "rr_set_distance_pairs: n_pairs " + std::to_string(n_pairs) + " is neither -1 (the step's collision pairs) nor a count"
+                                           : "rr_set_distance_pairs: n_pairs " + std::to_string(n_pairs) + ": pair " + std::to_string(RR_DIST_MAX) +
+                                                 " is beyond RR_DIST_MAX (" + std::to_string(RR_DIST_MAX) + ")");
+    if (std::isnan(max_distance)) return fail(RR_EINVAL, "rr_set_distance_pairs: max_distance is NaN");
+    static_assert(RR_DIST_MAX == MAXPAIRS, "the step's whole collision table fits the pair table");
+    const bool own = n_pairs == -1;
+    const int Q = own ? e->P.npairs : n_pairs;
+    if (!own && Q > 0 && (!shape_a || !shape_b)) return fail(RR_EINVAL, "rr_set_distance_pairs: null shape array");
+    DistTable T = {};
+    T.max_distance = max_distance;
+    for (int j = 0; j < Q; j++) {
+        const int ab[2] = {own ? e->pair_shapes[2 * j] : shape_a[j], own ? e->pair_shapes[2 * j + 1] : shape_b[j]};
+        for (int k = 0; k < 2; k++) {
+            const std::string which = "rr_set_distance_pairs: pair " + std::to_string(j) + ": shape " + (k ? "b" : "a") + " = " + std::to_string(ab[k]);
+            if (ab[k] < 0 || ab[k] >= e->n_shapes) return fail(RR_EINVAL, which + " is not in [0, " + std::to_string(e->n_shapes) + ")");
+            if (e->shape_kind[ab[k]] == 2 && (e->shape_idx[ab[k]] < 0 || e->shape_idx[ab[k]] >= e->P.nobj))
+                return fail(RR_EINVAL, which + " belongs to object " + std::to_string(e->shape_idx[ab[k]]) + ", which this handle (" + std::to_string(e->P.nobj) + " objects) does not have");
+            if (e->shape_kind[ab[k]] == 1 && (e->shape_idx[ab[k]] < 0 || e->shape_idx[ab[k]] >= NB))
+                return fail(RR_EMODEL, which + " is on a body outside the kinematic tree");
+        }
+        if (ab[0] == ab[1]) return fail(RR_EINVAL, "rr_set_distance_pairs: pair " + std::to_string(j) + ": a == b (shape " + std::to_string(ab[0]) + ")");
+        T.a[j] = ab[0]; T.b[j] = ab[1];
+    }
+    if (e->dist_tab_dev) {     // (before the buffers exist the host copy is all there is: ensure_dist uploads it)
+        HIPCHK(hipSetDevice(e->cfg.device));
+        HIPCHK(hipStreamSynchronize(e->stream));      // a query enqueued earlier still reads the earlier table
+        HIPCHK(hipMemcpy(e->dist_tab_dev, &T, sizeof T, hipMemcpyHostToDevice));
+    }
+    e->dist_tab = T; e->dist_n = Q;
+    return RR_OK;
+}
+
+int rr_get_distance_pairs(rr_env *e, int32_t *n_pairs, int32_t *shape_a_out, int32_t *shape_b_out, float *max_distance_out) {
+    if (!e) return fail(RR_EINVAL, "rr_get_distance_pairs: null env");
+    if (n_pairs) *n_pairs = e->dist_n;
+    if (shape_a_out) memcpy(shape_a_out, e->dist_tab.a, (size_t)e->dist_n * 4);
+    if (shape_b_out) memcpy(shape_b_out, e->dist_tab.b, (size_t)e->dist_n * 4);
+    if (max_distance_out) *max_distance_out = e->dist_tab.max_distance;
+    return RR_OK;
+}
+
+// getClosestPoints for the whole batch, on the device.  On the main stream like rr_ray_cast: behind every step, reset and state write
+// enqueued before it.  Reads D.state and the model only -- never the scratch slab of the look-ahead -- and leaves la_valid and the
+// error flags alone.
+int rr_closest_points(rr_env *e) {
+    if (!e) return fail(RR_EINVAL, "rr_closest_points: null env");
+    const int Q = e->dist_n, N = e->P.N;
+    if (Q == 0) return fail(RR_EINVAL, "rr_closest_points: the pair table is empty (rr_set_distance_pairs)");
+    RRCHK(ensure_dist(e, "rr_closest_points"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    hipLaunchKernelGGL(k_closest_points, dim3((N + DIST_ENVS - 1) / DIST_ENVS), dim3(DIST_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q,
+                       e->dist_pts, e->dist_id);
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+int rr_distance_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_distance_buffer: null env");
+    if (which < 0 || which >= RR_DIST_COUNT) return fail(RR_EINVAL, "rr_distance_buffer: buffer " + std::to_string(which) + " is not in [0, RR_DIST_COUNT)");
+    RRCHK(ensure_dist(e, "rr_distance_buffer"));
+    if (dev_ptr) *dev_ptr = which == RR_DIST_POINTS ? (void *)e->dist_pts : (void *)e->dist_id;
+    if (bytes) *bytes = dist_bytes(e, which, e->dist_n);
+    return RR_OK;
+}
+
+int rr_distance_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_distance_copy_to_host: null env");
+    if (!dst) return fail(RR_EINVAL, "rr_distance_copy_to_host: null destination");
+    if (which < 0 || which >= RR_DIST_COUNT) return fail(RR_EINVAL, "rr_distance_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_DIST_COUNT)");
+    if (bytes != dist_bytes(e, which, e->dist_n)) return fail(RR_EINVAL, "rr_distance_copy_to_host: size mismatch");
+    RRCHK(ensure_dist(e, "rr_distance_copy_to_host"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    if (bytes == 0) return RR_OK;
+    HIPCHK(hipMemcpyAsync(dst, which == RR_DIST_POINTS ? (void *)e->dist_pts : (void *)e->dist_id, bytes, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return RR_OK;
 }

@@ -53,13 +53,19 @@ unbounded; BatchedREALRobotEnv.kinematic_observations) to the observation dict a
 gathered, device views or host copies by `device_obs`.  `kinematic_points=` is a sequence of links (names or indices), or a pair
 (links, local_pos [P, 3]); the default is the one point of a fresh handle, the gripper base.  `jacobian @ _native.Q_FROM_CMD` is the
 Jacobian over the nine entries of `joint_command`.  The default leaves dict and spaces as they are.  These two arguments and the ones
-behind them (`ray_sensors`, `contact_obs`, `goals`, `goal_stride`) are keyword-only.
+behind them (`ray_sensors`, `distance_pairs`, `distance_max`, `contact_obs`, `goals`, `goal_stride`) are keyword-only.
 Ray sensors: `ray_sensors=(links, segments)` -- the arguments of BatchedREALRobotEnv.set_rays: R links (names, indices, 'world' / -1)
 and segments [R, 6] {from xyz, to xyz} in those links' COM frames -- casts the table against the collision hulls where the other
 entries are gathered (BatchedREALRobotEnv.ray_cast: pybullet's rayTestBatch) and adds `ray_distance` [N, R] (float32, metres along the
 ray to the first hit; the segment's length on a miss) and `ray_uid` [N, R] (int32, the uid of the mask image; -1 on a miss) to the
 observation dict and to the spaces.  With `device_obs` they are strided device views (DLPack / `__cuda_array_interface__`) of the
 cast's two buffers.  The default leaves dict and spaces as they are.
+Pair distances: `distance_pairs=` -- the `pairs` of BatchedREALRobotEnv.set_distance_pairs: (a, b) collision shapes by name or index,
+or 'collision' -- with `distance_max=` (metres; None: no cull) computes the closest points of the pairs where the other entries are
+gathered (BatchedREALRobotEnv.closest_points: pybullet's getClosestPoints) and adds `pair_distance` [N, Q] (float32, metres between
+the two convex hulls; 0 when they overlap) and `pair_status` [N, Q] (int32: 0 separated, 1 overlapping, 2 culled, 3 iteration cap)
+to the observation dict and to the spaces.  With `device_obs` they are strided device views of the query's two buffers.  The
+default leaves dict and spaces as they are.
 Goals: `goals=` (the path of a goals dataset, or a list of `Goal` objects) with `goal_stride=` puts the goal table and the episode
 record on the device (BatchedREALRobotEnv.set_goals_from / episode_update; evaluateGoal, env.py:181-200).  reset() gives env i the
 goal i mod G and starts it from that goal's start poses; every step() returns as rewards the change of the env's goal score over
@@ -109,7 +115,7 @@ class REALRobotVectorEnv(_Base):
     def __init__(self, num_envs, objects=3, additional_obs=False, eye_width=320, eye_height=240, device=0,
                  max_episode_steps=int(15e6), render_every_step=True, device_obs=False, solver=None, dynamics_randomization=None,
                  camera_randomization=None, appearance_randomization=None, actuator_randomization=None, *, kinematic_obs=False,
-                 kinematic_points=None, ray_sensors=None, contact_obs=False, goals=None, goal_stride=1):
+                 kinematic_points=None, ray_sensors=None, distance_pairs=None, distance_max=None, contact_obs=False, goals=None, goal_stride=1):
         self.num_envs = int(num_envs)
         self._goals = None if goals is None else self._check_goals(goals, OBJECT_NAMES[:int(objects)], int(eye_height), int(eye_width))
         self.goal_stride = int(goal_stride)
@@ -151,6 +157,21 @@ class REALRobotVectorEnv(_Base):
                 ray_distance=spaces.Box(low=0.0, high=np.inf, shape=(n_rays,), dtype=np.float32),
                 ray_uid=spaces.Box(low=-1, high=np.iinfo(np.int32).max, shape=(n_rays,), dtype=np.int32)))
         self.ray_sensors = ray_table is not None
+        dist_table = None
+        if distance_pairs is not None:
+            dist_table = BatchedREALRobotEnv._distance_arg(distance_pairs, distance_max, int(objects))
+            n_pairs = len(dist_table[1])
+            if dist_table[0] == -1:
+                own = np.array(load_model()['shape_owner'])
+                n_obj, n_rob, n_sta = int(objects), int((own[:, 0] == 1).sum()), int((own[:, 0] == 0).sum())
+                n_pairs = n_obj * n_sta + n_obj * (n_obj - 1) // 2 + 2 * n_rob + n_rob * n_obj
+            if n_pairs == 0:
+                raise ValueError("distance_pairs: at least one pair")
+            self.single_observation_space = spaces.Dict(dict(
+                self.single_observation_space.spaces,
+                pair_distance=spaces.Box(low=0.0, high=np.inf, shape=(n_pairs,), dtype=np.float32),
+                pair_status=spaces.Box(low=0, high=3, shape=(n_pairs,), dtype=np.int32)))
+        self.pair_distances = dist_table is not None
         # batched spaces = the single spaces with a leading env axis (gymnasium.vector.utils.batch_space)
         self.action_space = spaces.Dict({
             "joint_command": spaces.Box(low=np.tile(self._robot.min_joints, (self.num_envs, 1)),
@@ -166,6 +187,8 @@ class REALRobotVectorEnv(_Base):
             self._be.set_kinematic_points(*kin_points)
         if ray_table is not None:
             self._be.set_rays(*ray_table)
+        if dist_table is not None:
+            self._be.set_distance_pairs(distance_pairs, distance_max)
         # host-side episode clocks (no device read-back per step): the batched env behind this adapter is private to it, every
         # path that resets an env goes through reset() / step() below and resets its clock with it
         self._steps = np.zeros(self.num_envs, np.int64)
@@ -387,6 +410,9 @@ class REALRobotVectorEnv(_Base):
         if self.ray_sensors:
             rc = be.ray_cast(host=not self.device_obs)
             obs["ray_distance"], obs["ray_uid"] = be.ray_column(rc['hit'], 1), be.ray_column(rc['id'], 0)
+        if self.pair_distances:
+            cp = be.closest_points(host=not self.device_obs)
+            obs["pair_distance"], obs["pair_status"] = cp['distance'], cp['status']
         if self._goals is not None:
             if self._goal_images:
                 obs["goal"] = be.episode_buffer('goal_rgb', host=not self.device_obs)
