@@ -38,13 +38,15 @@ extern "C" {
                               rr_read_state (masked state writes by column groups -- resets, teleports, postures, velocity kicks -- and state
                               reads on the device); rr_set_rays, rr_get_rays, rr_ray_cast, rr_ray_buffer, rr_ray_copy_to_host (segments of
                               the whole batch against the collision hulls); rr_set_distance_pairs, rr_get_distance_pairs, rr_closest_points,
-                              rr_distance_buffer, rr_distance_copy_to_host (distance and closest points of pairs of collision hulls) */
+                              rr_distance_buffer, rr_distance_copy_to_host (distance and closest points of pairs of collision hulls);
+                              rr_posture_clearance, rr_posture_buffer, rr_posture_copy_to_host (clearance of the pair table at candidate
+                              joint postures, the nearest pair reduced on the device) */
 
 enum {
     RR_OK = 0,
     RR_EINVAL = -1,     /* bad argument */
     RR_EDEVICE = -2,    /* HIP runtime error (no GPU, out of memory, launch failure).  Memory that a call allocates on first use
-                           (contact and kinematic observations, ray casts, closest points, goal scores, plans and IK, per-env cameras and appearance, goal table and episode
+                           (contact and kinematic observations, ray casts, closest points, posture clearance, goal scores, plans and IK, per-env cameras and appearance, goal table and episode
                            record, snapshot slots and fork staging, mapped host blocks, the staging ring) is allocated all or nothing:
                            when that fails the call returns RR_EDEVICE, nothing has changed -- what the call would replace is kept --
                            and the handle stays usable; a later call tries again. */
@@ -692,6 +694,64 @@ int rr_closest_points(rr_env *env);
 int rr_distance_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
 /* Synchronising copy of a whole RR_DIST_* buffer (its `bytes`) to host memory. */
 int rr_distance_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
+
+/* ---- Clearance at candidate joint postures on the device (additive in ABI 7) ----------------------------------------------------------
+ * The question of planners, MPPI / CEM samplers and trajectory optimisers: "how much clearance would the arm have at THESE K joint
+ * postures, given where this env's objects are now?"  One launch on the library's stream (rr_posture_clearance) evaluates K candidate
+ * postures per env of the whole batch against the pair table of rr_set_distance_pairs and writes four device buffers: per posture the
+ * distance and status of every pair, and the full record of the NEAREST pair, reduced on the device.  Nothing of the simulation is
+ * disturbed, and no handle of N * K envs is needed.  The buffers are NOT fields of rr_get_buffer and not RR_DIST_* buffers
+ * (RR_F_COUNT stays 16, RR_DIST_COUNT stays 2): they have this enum and rr_posture_buffer. */
+enum {
+    RR_PC_NEAREST = 0,    /* f32 [N, K, 12] the RR_DIST_POINTS row {distance, lower bound, a xyz, b xyz, n xyz, +0.0} of the nearest pair of that posture */
+    RR_PC_ID = 1,         /* i32 [N, K, 4]  {status of that row, pair index j in the table, body A, body B} */
+    RR_PC_DISTANCE = 2,   /* f32 [N, K, Q]  the distance column of every pair, as rr_closest_points would report it */
+    RR_PC_STATUS = 3,     /* i32 [N, K, Q]  byte 0: status 0..3, byte 1: iterations, bytes 2..3: zero */
+    RR_PC_COUNT = 4
+};
+#define RR_PC_MAX_POSTURES 32
+/* What is computed.  Posture (e, k), k in [0, K = n_postures), is evaluated as if columns 0..10 of env e's RR_F_STATE row were
+ * postures[e][k][0..10]; the objects stay at env e's PRESENT pose -- whatever the last step, reset, rr_set_state, rr_write_state,
+ * rr_set_object_pose(s), rr_copy_envs or restore left.  The pair table and the cull are those of rr_set_distance_pairs, and a pair
+ * means exactly what it means to rr_closest_points (the block above: the convex hulls of the vertex sets, the shapes' frames, the
+ * statuses 0 to 3, the relative gap 1e-12 that ends the search, touching at 1e-6 m, the cap of 32 trips, support ties to the lowest
+ * vertex index); the two kernels run the same device text for a pair.
+ * Input.  postures is f32 [N][K][11], C order: the eleven INDEPENDENT joints in the order of the state's q[11].  The nine entries of a
+ * joint command map into them through the binding's _native.Q_FROM_CMD (the coupled finger joints follow their drivers); this call
+ * takes the 11 columns only.
+ * The nearest row.  RR_PC_NEAREST / RR_PC_ID hold the pair at the FIRST MINIMUM of that posture's RR_PC_DISTANCE row: the lowest
+ * pair index among equal values, so two overlapping pairs tie at 0 and the lower index wins.  A culled pair (status 2) takes part with
+ * its sphere gap, a status-3 pair with its upper bound; the status in RR_PC_ID says which kind won.  The comparison is d < best over
+ * ascending j, starting from pair 0 with best = +inf: a NaN never wins against a number, and the pair index is always in [0, Q) (pair 0
+ * where no distance of the row is below +inf).
+ * No effect on the simulation.  The call reads the state (the objects' columns), the model, the pair table and the tensor, and writes
+ * the four buffers only: not the state, not the preparation record (RR_F_PREP), no error flag, no RR_DIST_* buffer.  The next step
+ * stays prepared and no later step is affected.  The buffers hold what the LAST CALL computed.
+ * on_device != 0: postures is device memory, read IN PLACE on the library's stream under the STREAM CONTRACT of rr_step's
+ * cmd_on_device (produced on that stream or ordered before it; not rewritten before later work on that stream); the call allocates
+ * nothing beyond the first-use buffers, checks the launch and returns without waiting.  on_device == 0: host memory, staged through a
+ * buffer of the handle's own (N * 32 * 11 floats, allocated by the first such call), and the call waits for the stream.
+ * Values are NOT validated on either path.  A non-finite posture, or an env whose object pose is not finite, is computed like any
+ * other and finishes like any other -- every loop bound is a constant or a model count -- and its rows are unspecified (the pair
+ * index stays in [0, Q), the status bytes in 0..3, the iterations <= 32).  No value of the tensor ever forms an address.
+ * Errors: RR_EINVAL with nothing changed, the message naming the cause, for a null env, null postures, n_postures outside
+ * [1, RR_PC_MAX_POSTURES], and Q == 0 (an empty pair table).
+ * Buffers.  All four are allocated on first use -- by this call, or by rr_posture_buffer / rr_posture_copy_to_host --, all or nothing
+ * through the handle's memory owner, zero-filled, sized once for RR_PC_MAX_POSTURES x RR_DIST_MAX, and valid until rr_destroy: no
+ * pointer ever changes.  The layout is compact [N, K, ...] for the K of the last query and the Q in force, and `bytes` reports that;
+ * before the first query K counts as 0.  After rr_set_distance_pairs the buffers hold unspecified data until the next query.  STREAM
+ * CONTRACT for readers as for the other zero-copy views: the kernel runs on the library's stream behind the work enqueued before it;
+ * readers on another stream order themselves after the call (event / rr_sync), and a later call rewrites the buffers in place.
+ * Determinism.  No atomics and a fixed reduction order: row (e, k) is a function of (env e's objects, posture (e, k), the table)
+ * alone -- identical from call to call, independent of N, of K, of the row's place and of its neighbours.
+ * Out of scope: candidate object poses; per-posture pair tables; signed distances and penetration depth; gradients (n . (J_a - J_b)
+ * with the Jacobians of rr_kinematic_observations at the present state is the caller's to form); rays and kinematics at candidate
+ * postures; a switch of the vector env (postures are an argument, not an observation). */
+int rr_posture_clearance(rr_env *env, const float *postures /* f32 [N][K][11] */, int32_t n_postures, int32_t on_device);
+/* Zero-copy device pointer + size in bytes of an RR_PC_* buffer (read-only for the caller); which outside [0, RR_PC_COUNT): RR_EINVAL. */
+int rr_posture_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
+/* Synchronising copy of a whole RR_PC_* buffer (its `bytes`) to host memory. */
+int rr_posture_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
 
 /* Batched damped-least-squares inverse kinematics for link 7 (gripper `base`), seeded with each env's current joints.
  * Replaces pybullet.calculateInverseKinematics(0, 7, pos, orn, maxNumIterations=1000, residualThreshold=0.001) in

@@ -918,6 +918,91 @@ class BatchedREALRobotEnv:
         nat.check(self.L.rr_closest_points(self.h))
         return self.distance_columns(self.distance_buffer(0, host=host), self.distance_buffer(1, host=host))
 
+    # ------------------------------------------------------------------ clearance at candidate postures
+    @staticmethod
+    def _posture_arg(postures, N):
+        """The `postures` argument of `posture_clearance` for a handle of N envs -> K.  It is float32 [N, K, 11], C-contiguous, K in
+        [1, 32]: a numpy array, a CUDA torch tensor or a `__cuda_array_interface__` object; every violation is a ValueError raised
+        here, before the native call."""
+        what = "postures must be a C-contiguous float32 array of shape (%d, K, 11), 1 <= K <= %d" % (N, nat.PC_MAX_POSTURES)
+        a = postures
+        if hasattr(a, 'is_cuda') and hasattr(a, 'data_ptr'):        # a torch tensor
+            dt, shape, dense = str(a.dtype).replace('torch.', ''), tuple(a.shape), bool(a.is_contiguous())
+        elif getattr(a, '__cuda_array_interface__', None) is not None:
+            cai = a.__cuda_array_interface__
+            dt, shape = np.dtype(cai['typestr']).name, tuple(cai['shape'])
+            dense = cai.get('strides') in (None, tuple(int(np.prod(shape[i + 1:])) * 4 for i in range(len(shape))))
+        else:
+            try:
+                a = np.asarray(a)
+            except (ValueError, TypeError):
+                raise ValueError("%s, not %r" % (what, type(postures).__name__))
+            dt, shape, dense = a.dtype.name, a.shape, bool(a.flags.c_contiguous)
+        if dt != 'float32' or len(shape) != 3 or shape[0] != N or shape[2] != nat.N_JOINTS or not 1 <= shape[1] <= nat.PC_MAX_POSTURES or not dense:
+            raise ValueError("%s, not %s %s%s" % (what, dt, tuple(shape), '' if dense else ' (not contiguous)'))
+        return int(shape[1])
+
+    def posture_buffer(self, name, host=False):
+        """One buffer of `posture_clearance` as the LAST call left it (all zero, and K = 0, before the first), by name
+        (`_native.PC_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait.  Shapes: nearest
+        [N, K, 12] float32, id [N, K, 4] int32, distance [N, K, Q] float32, status [N, K, Q] int32."""
+        which = nat.PC_FIELDS.index(name) if isinstance(name, str) and name in nat.PC_FIELDS else name
+        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.PC_FIELDS):
+            raise ValueError("unknown posture buffer %r (known: %s)" % (name, ', '.join(nat.PC_FIELDS)))
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(self.L.rr_posture_buffer(self.h, int(which), C.byref(p), C.byref(n)))
+        Q = len(self.distance_pairs()[0])
+        cols, dt = ((12, np.float32), (4, np.int32), (Q, np.float32), (Q, np.int32))[int(which)]
+        shape = (self.N, n.value // (4 * cols * self.N) if cols else 0, cols)
+        if host:
+            out = np.empty(shape, dt)
+            nat.check(self.L.rr_posture_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
+            return out
+        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
+
+    @staticmethod
+    def status_bytes(status):
+        """(pair_status, pair_iterations) of the status words [N, K, Q] of `posture_clearance`: bytes 0 and 1 of every int32 as
+        uint8 [N, K, Q] -- numpy views, or strided device views (zero copy)."""
+        if isinstance(status, np.ndarray):
+            b = status.view(np.uint8).reshape(status.shape + (4,))
+            return b[..., 0], b[..., 1]
+        N, K, Q = status.shape
+        view = lambda byte: nat.DeviceBuffer(status.ptr + byte, (N, K, Q), np.dtype(np.uint8).str, status._owner, strides=(K * Q * 4, Q * 4, 4))
+        return view(0), view(1)
+
+    def posture_clearance(self, postures, host=False):
+        """The clearance of K candidate joint postures per env (rr_posture_clearance): one launch on the library's stream evaluates
+        posture (e, k) as if env e's joints q[11] were postures[e, k] -- the objects stay where they are now -- against the pairs
+        of `set_distance_pairs`, and reduces to the NEAREST pair on the device.  The simulation is not touched: no state write, the
+        next step stays prepared.  postures: float32 [N, K, 11], 1 <= K <= 32, C-contiguous, the eleven independent joints (a
+        nine-entry command maps through `_native.Q_FROM_CMD`) -- a numpy array (staged, synchronous) or a CUDA torch tensor /
+        `__cuda_array_interface__` object, read in place on the library's stream without waiting (produce it on that stream or
+        synchronise first); values are not validated.  Returns
+          distance, lower float32 [N, K]; point_a, point_b, normal float32 [N, K, 3] -- the `closest_points` record of the nearest
+              pair: the first minimum of the posture's pair_distance row (the lowest pair index among equal values);
+          status int32 [N, K] -- that record's status (0 separated, 1 overlapping, 2 culled: the spheres' gap, 3 cap: an upper bound);
+          pair int32 [N, K] -- its index in the pair table; body_a, body_b int32 [N, K] -- as in the contact records;
+          pair_distance float32 [N, K, Q] -- every pair's distance, as `closest_points` would report it at that posture;
+          pair_status, pair_iterations uint8 [N, K, Q] -- bytes 0 and 1 of the status words.
+        Device views (zero copy, strided, DLPack; valid after later work on the library's stream or `sync()`; they hold what the last
+        call computed), or with host=True numpy views of host copies after a sync."""
+        K = self._posture_arg(postures, self.N)
+        if len(self.distance_pairs()[0]) == 0:
+            raise ValueError("posture_clearance: the pair table is empty (set_distance_pairs)")
+        ptr, on_dev, keep = self._state_arg(postures, 'postures', ('float32',), (self.N, K, nat.N_JOINTS))
+        nat.check(self.L.rr_posture_clearance(self.h, ptr, K, on_dev))
+        del keep
+        near, ids, dist, st = (self.posture_buffer(i, host=host) for i in range(len(nat.PC_FIELDS)))
+        if isinstance(near, np.ndarray):
+            cut = lambda lo: near[:, :, lo:lo + 3]
+        else:
+            cut = lambda lo: nat.DeviceBuffer(near.ptr + 4 * lo, (self.N, K, 3), near.typestr, near._owner, strides=(K * 48, 48, 4))
+        col = self.ray_column
+        ps, pi = self.status_bytes(st)
+        return dict(distance=col(near, 0), lower=col(near, 1), point_a=cut(2), point_b=cut(5), normal=cut(8), status=col(ids, 0),
+                    pair=col(ids, 1), body_a=col(ids, 2), body_b=col(ids, 3), pair_distance=dist, pair_status=ps, pair_iterations=pi)
+
     def body_row_names(self):
         """The bodies of the rows of body_force / body_partners: the 17 URDF links, then this handle's objects (the rows of the
         objects it does not have, up to 20, stay zero)."""

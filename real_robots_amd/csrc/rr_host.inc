@@ -143,6 +143,11 @@ struct rr_env : ModelTables {
     int dist_n = 0;                // pairs in force: a fresh handle has none
     DistTable dist_tab = {};
     DistTable *dist_tab_dev = nullptr;
+    // clearance at candidate postures (rr_posture_clearance): the four RR_PC_* buffers, allocated together on first use for
+    // RR_PC_MAX_POSTURES x RR_DIST_MAX, once; the host path's staging buffer is a part of its own, got by the first host-path call
+    void *pc_buf[RR_PC_COUNT] = {};
+    int pc_k = 0;                  // postures per env of the last query: 0 before the first
+    float *pc_stage = nullptr;
     MemOwner mem;                  // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
     bool created = false;
     bool timing = false;
@@ -1706,6 +1711,75 @@ int rr_distance_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) 
     HIPCHK(hipSetDevice(e->cfg.device));
     if (bytes == 0) return RR_OK;
     HIPCHK(hipMemcpyAsync(dst, which == RR_DIST_POINTS ? (void *)e->dist_pts : (void *)e->dist_id, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return RR_OK;
+}
+
+// ---- clearance at candidate postures (rr_posture.inc) ----------------------------------------------------------------------------------
+// The four buffers of rr_posture_clearance: allocated on first use -- by the query or by rr_posture_buffer / rr_posture_copy_to_host --
+// in one list, zero-filled, for RR_PC_MAX_POSTURES postures of RR_DIST_MAX pairs.  The layout in force is [N, K, ...] for the K of the
+// last query (0 before the first) and the Q of the pair table.
+static size_t pc_bytes(const rr_env *e, int which, int K, int Q) {
+    return (size_t)e->P.N * K * (which == RR_PC_NEAREST ? 48 : which == RR_PC_ID ? 16 : (size_t)Q * 4);
+}
+static int ensure_posture(rr_env *e, const char *who) {
+    if (e->pc_buf[0]) return RR_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    void *b[RR_PC_COUNT] = {};
+    MemPart parts[RR_PC_COUNT];
+    for (int i = 0; i < RR_PC_COUNT; i++) parts[i] = mem_part(&b[i], pc_bytes(e, i, RR_PC_MAX_POSTURES, RR_DIST_MAX));
+    RRCHK(mem_get(e, parts, RR_PC_COUNT, (std::string(who) + ": allocating the posture buffers").c_str()));
+    for (int i = 0; i < RR_PC_COUNT; i++) e->pc_buf[i] = b[i];
+    return RR_OK;
+}
+
+// The clearance of K candidate postures per env, on the device.  On the main stream like rr_closest_points: behind every step, reset
+// and state write enqueued before it.  Reads D.state (the objects), the model, the pair table and the tensor; writes the four buffers
+// and nothing else -- not the state, the scratch slab of the look-ahead, la_valid, an error flag or an RR_DIST_* buffer.
+int rr_posture_clearance(rr_env *e, const float *postures, int32_t n_postures, int32_t on_device) {
+    if (!e) return fail(RR_EINVAL, "rr_posture_clearance: null env");
+    if (!postures) return fail(RR_EINVAL, "rr_posture_clearance: null postures");
+    if (n_postures < 1 || n_postures > RR_PC_MAX_POSTURES)
+        return fail(RR_EINVAL, "rr_posture_clearance: n_postures " + std::to_string(n_postures) + " is not in [1, RR_PC_MAX_POSTURES = " +
+                                   std::to_string(RR_PC_MAX_POSTURES) + "]");
+    const int Q = e->dist_n, N = e->P.N, K = n_postures;
+    if (Q == 0) return fail(RR_EINVAL, "rr_posture_clearance: the pair table is empty (rr_set_distance_pairs)");
+    RRCHK(ensure_dist(e, "rr_posture_clearance"));        // (the device copy of the pair table)
+    RRCHK(ensure_posture(e, "rr_posture_clearance"));
+    if (!on_device && !e->pc_stage)
+        RRCHK(mem_get(e, {mem_part(&e->pc_stage, (size_t)N * RR_PC_MAX_POSTURES * 44, false)}, "rr_posture_clearance: allocating the staging buffer"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const float *src = postures;
+    if (!on_device) {
+        HIPCHK(hipMemcpyAsync(e->pc_stage, postures, (size_t)N * K * 44, hipMemcpyHostToDevice, e->stream));
+        src = e->pc_stage;
+    }
+    hipLaunchKernelGGL(k_posture_clearance, dim3((unsigned)N * K), dim3(PC_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
+                       (float4 *)e->pc_buf[RR_PC_NEAREST], (int4 *)e->pc_buf[RR_PC_ID], (float *)e->pc_buf[RR_PC_DISTANCE], (int *)e->pc_buf[RR_PC_STATUS]);
+    HIPCHK(hipGetLastError());
+    e->pc_k = K;
+    if (!on_device) HIPCHK(hipStreamSynchronize(e->stream));   // the argument is host memory
+    return RR_OK;
+}
+
+int rr_posture_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_posture_buffer: null env");
+    if (which < 0 || which >= RR_PC_COUNT) return fail(RR_EINVAL, "rr_posture_buffer: buffer " + std::to_string(which) + " is not in [0, RR_PC_COUNT)");
+    RRCHK(ensure_posture(e, "rr_posture_buffer"));
+    if (dev_ptr) *dev_ptr = e->pc_buf[which];
+    if (bytes) *bytes = pc_bytes(e, which, e->pc_k, e->dist_n);
+    return RR_OK;
+}
+
+int rr_posture_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_posture_copy_to_host: null env");
+    if (!dst) return fail(RR_EINVAL, "rr_posture_copy_to_host: null destination");
+    if (which < 0 || which >= RR_PC_COUNT) return fail(RR_EINVAL, "rr_posture_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_PC_COUNT)");
+    if (bytes != pc_bytes(e, which, e->pc_k, e->dist_n)) return fail(RR_EINVAL, "rr_posture_copy_to_host: size mismatch");
+    RRCHK(ensure_posture(e, "rr_posture_copy_to_host"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    if (bytes == 0) return RR_OK;
+    HIPCHK(hipMemcpyAsync(dst, e->pc_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return RR_OK;
 }
