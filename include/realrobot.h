@@ -40,7 +40,9 @@ extern "C" {
                               the whole batch against the collision hulls); rr_set_distance_pairs, rr_get_distance_pairs, rr_closest_points,
                               rr_distance_buffer, rr_distance_copy_to_host (distance and closest points of pairs of collision hulls);
                               rr_posture_clearance, rr_posture_buffer, rr_posture_copy_to_host (clearance of the pair table at candidate
-                              joint postures, the nearest pair reduced on the device) */
+                              joint postures, the nearest pair reduced on the device); rr_signed_distance, rr_signed_buffer,
+                              rr_signed_copy_to_host (signed distance of the pair table: penetration depth, direction and witness points
+                              where hulls overlap, at the present state or at candidate postures) */
 
 enum {
     RR_OK = 0,
@@ -752,6 +754,77 @@ int rr_posture_clearance(rr_env *env, const float *postures /* f32 [N][K][11] */
 int rr_posture_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
 /* Synchronising copy of a whole RR_PC_* buffer (its `bytes`) to host memory. */
 int rr_posture_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
+
+/* ---- Signed distance and penetration depth on the device (additive in ABI 7) -----------------------------------------------------------
+ * rr_closest_points and rr_posture_clearance stop at the surface: every overlapping pair is "0".  This query goes on: over the pair
+ * table of rr_set_distance_pairs, for every env at once, a pair whose hulls are apart gets what rr_closest_points reports, and a pair
+ * whose hulls OVERLAP gets a NEGATIVE distance, minus the penetration depth -- the length of the shortest translation of shape a that
+ * separates the two convex hulls --, the direction of that translation, two witness points and a proved bound: what pybullet's
+ * getClosestPoints returns for penetrating bodies, and what a sampler needs to tell a finger 1 mm into the cube from a forearm 20 cm
+ * through the table and to push the candidate out.  One launch on the library's stream, at the present state or at K candidate joint
+ * postures per env.  The buffers are NOT fields of rr_get_buffer and not RR_DIST_* / RR_PC_* buffers (RR_F_COUNT stays 16,
+ * RR_DIST_COUNT 2, RR_PC_COUNT 4): they have this enum and rr_signed_buffer.  K' below is 1 for a present-state query, else K. */
+enum {
+    RR_SD_DEEPEST = 0,    /* f32 [N, K', 12] {signed distance, bound, a xyz, b xyz, n xyz, +0.0} of the pair at the FIRST MINIMUM of that row's signed distances */
+    RR_SD_ID = 1,         /* i32 [N, K', 4]  {status of that row, pair index j in the table, body A, body B} */
+    RR_SD_SIGNED = 2,     /* f32 [N, K', Q]  the signed distance of every pair */
+    RR_SD_STATUS = 3,     /* i32 [N, K', Q]  byte 0: status 0..5, byte 1: GJK iterations, byte 2: expansion trips, byte 3: zero */
+    RR_SD_POINTS = 4,     /* f32 [N, Q, 12]  the full record of every pair; written by a PRESENT-STATE query only */
+    RR_SD_COUNT = 5
+};
+/* Arguments.  postures == NULL with n_postures == 0: the present state -- one row per env, K' = 1, the joints from the state.
+ * Otherwise the arguments are exactly those of rr_posture_clearance: postures f32 [N][K][11], K = n_postures in
+ * [1, RR_PC_MAX_POSTURES], the objects at env e's present pose; on_device != 0: device memory read in place on the library's stream
+ * under that call's STREAM CONTRACT, the call returns without waiting; on_device == 0: host memory, staged, and the call waits.
+ * Shapes, frames, the pair table, the cull and the GJK (relative gap 1e-12, touching at 1e-6 m, 32 trips, ties to the lowest vertex
+ * index) are those of rr_closest_points.
+ * The record.  For both signs a is a point of hull A, b a point of hull B, n a unit vector from b towards a, and a - b = signed * n.
+ * Separated (status 0, 2, 3): the RR_DIST_POINTS row of rr_closest_points.  Overlapping (status 1): signed = -depth, where depth is
+ * the smallest separating translation the search found: moving shape a by depth * n separates the hulls (depth is the width of the
+ * overlap along n: max over B of n . b minus min over A of n . a), so it is an upper bound of the true depth and one that is always
+ * achievable; bound = -(the distance of the search polytope's nearest face from the origin of the Minkowski difference), a proved
+ * lower bound of the depth: -bound <= true depth <= -signed.  a and b are the barycentric weights, on the two shapes' support
+ * vertices, of the origin's projection on that nearest face (of coplanar faces the one that holds the projection); like the closest
+ * points of parallel faces they need not be unique.  status:
+ *   0  separated and converged;
+ *   1  overlapping, the expansion converged: (-signed) - (-bound) <= 1e-6 m, or the support vertex pair was already a vertex of
+ *      the polytope;
+ *   2  culled by max_distance (the spheres' gap, as rr_closest_points);
+ *   3  the GJK's iteration cap (32): signed is an upper bound of the distance;
+ *   4  touching: the GJK ended with a distance of at most 1e-6 m, or its tetrahedron was too flat to expand; signed = bound = 0,
+ *      n = +0.0, a = b = some finite point: the status-1 row of rr_closest_points;
+ *   5  the expansion's cap (32 trips, or more than 64 faces): signed (the smallest width seen, with its n) and bound are still valid
+ *      bounds of the depth; a and b are those of the nearest face, and a - b = signed * n holds only as far as the bounds agree.
+ * The search for the depth is an expanding polytope from the GJK's final tetrahedron, one wave per pair, in float32 with float64
+ * face normals and plane distances; ties (nearest face, support vertex) go to the lowest lane / vertex index, every reduction runs
+ * in a fixed order, there are no atomics: a row is a function of (env e's objects, its joints, the table) alone -- identical from
+ * call to call, independent of N, K, the row's place and its neighbours, and a permuted table gives permuted columns.  Every loop
+ * bound is a constant, a model count or a count of at most 64 faces, never a coordinate: a non-finite posture or state is computed
+ * like any other and finishes like any other; its rows are unspecified (the pair index stays in [0, Q), the status in 0..5, the
+ * iterations and trips <= 32).  No value of the tensor or the state ever forms an address.
+ * The deepest row.  RR_SD_DEEPEST / RR_SD_ID hold the pair at the first minimum of the row's RR_SD_SIGNED values, by
+ * rr_posture_clearance's rule: d < best over ascending j from best = +inf -- the lowest pair index among equal values, pair 0 where
+ * nothing is below +inf; a NaN never wins.  A culled pair takes part with its sphere gap.
+ * RR_SD_POINTS is written by a present-state query only; a posture query leaves it untouched (at K = 32 it would be 600 MB for
+ * 4096 envs, which is why the posture form keeps the layout of rr_posture_clearance).
+ * No effect on the simulation.  The call reads the state, the model, the pair table and the tensor and writes these five buffers
+ * only: not the state, not the preparation record, no error flag, no RR_DIST_* or RR_PC_* buffer.  The next step stays prepared.
+ * Errors: RR_EINVAL with nothing allocated and no buffer pointer changed, the message naming the cause, for a null env, an empty
+ * pair table, n_postures outside [1, RR_PC_MAX_POSTURES] with postures given, and postures == NULL with n_postures != 0.
+ * Buffers.  All five are allocated on first use -- by this call, or by rr_signed_buffer / rr_signed_copy_to_host --, all or nothing
+ * through the handle's memory owner, zero-filled, sized once for RR_PC_MAX_POSTURES x RR_DIST_MAX (RR_SD_POINTS for RR_DIST_MAX), and
+ * valid until rr_destroy: no pointer ever changes.  The layout is compact for the K' of the last query (0 before the first) and the
+ * Q in force, and `bytes` reports that; RR_SD_POINTS reports N * Q * 48.  After rr_set_distance_pairs the buffers hold unspecified
+ * data until the next query.  STREAM CONTRACT for readers as for the other zero-copy views: the kernel runs on the library's stream
+ * behind the work enqueued before it; readers on another stream order themselves after the call (event / rr_sync), and a later call
+ * rewrites the buffers in place.
+ * Out of scope: gradients with respect to the joints; a switch of the vector env; penetration of non-convex shapes (a shape is the
+ * convex hull of its vertex set); any use by the step -- the step's own narrow phase is untouched. */
+int rr_signed_distance(rr_env *env, const float *postures /* f32 [N][K][11] or NULL */, int32_t n_postures, int32_t on_device);
+/* Zero-copy device pointer + size in bytes of an RR_SD_* buffer (read-only for the caller); which outside [0, RR_SD_COUNT): RR_EINVAL. */
+int rr_signed_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
+/* Synchronising copy of a whole RR_SD_* buffer (its `bytes`) to host memory. */
+int rr_signed_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
 
 /* Batched damped-least-squares inverse kinematics for link 7 (gripper `base`), seeded with each env's current joints.
  * Replaces pybullet.calculateInverseKinematics(0, 7, pos, orn, maxNumIterations=1000, residualThreshold=0.001) in

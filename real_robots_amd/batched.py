@@ -961,15 +961,18 @@ class BatchedREALRobotEnv:
         return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
 
     @staticmethod
-    def status_bytes(status):
-        """(pair_status, pair_iterations) of the status words [N, K, Q] of `posture_clearance`: bytes 0 and 1 of every int32 as
-        uint8 [N, K, Q] -- numpy views, or strided device views (zero copy)."""
+    def status_bytes(status, offset=0):
+        """Bytes `offset` and `offset + 1` of every int32 of the status words [N, K, Q] as uint8 [N, K, Q] -- numpy views, or
+        strided device views (zero copy).  offset 0: (pair_status, pair_iterations) of `posture_clearance` and `signed_distance`;
+        offset 1: (pair_iterations, pair_expansions) of `signed_distance`."""
+        if isinstance(offset, (bool, np.bool_)) or not isinstance(offset, (int, np.integer)) or not 0 <= offset <= 2:
+            raise ValueError("offset is 0, 1 or 2 (a status word has four bytes), not %r" % (offset,))
         if isinstance(status, np.ndarray):
             b = status.view(np.uint8).reshape(status.shape + (4,))
-            return b[..., 0], b[..., 1]
+            return b[..., offset], b[..., offset + 1]
         N, K, Q = status.shape
         view = lambda byte: nat.DeviceBuffer(status.ptr + byte, (N, K, Q), np.dtype(np.uint8).str, status._owner, strides=(K * Q * 4, Q * 4, 4))
-        return view(0), view(1)
+        return view(offset), view(offset + 1)
 
     def posture_clearance(self, postures, host=False):
         """The clearance of K candidate joint postures per env (rr_posture_clearance): one launch on the library's stream evaluates
@@ -1002,6 +1005,85 @@ class BatchedREALRobotEnv:
         ps, pi = self.status_bytes(st)
         return dict(distance=col(near, 0), lower=col(near, 1), point_a=cut(2), point_b=cut(5), normal=cut(8), status=col(ids, 0),
                     pair=col(ids, 1), body_a=col(ids, 2), body_b=col(ids, 3), pair_distance=dist, pair_status=ps, pair_iterations=pi)
+
+    # ------------------------------------------------------------------ signed distance and penetration depth
+    def signed_buffer(self, name, host=False):
+        """One buffer of `signed_distance` as the LAST call left it (all zero, and K' = 0, before the first), by name
+        (`_native.SD_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait.  Shapes: deepest
+        [N, K', 12] float32, id [N, K', 4] int32, signed [N, K', Q] float32, status [N, K', Q] int32, points [N, Q, 12] float32
+        (K' = 1 after a present-state query; `points` is written by present-state queries only)."""
+        which = nat.SD_FIELDS.index(name) if isinstance(name, str) and name in nat.SD_FIELDS else name
+        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.SD_FIELDS):
+            raise ValueError("unknown signed-distance buffer %r (known: %s)" % (name, ', '.join(nat.SD_FIELDS)))
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(self.L.rr_signed_buffer(self.h, int(which), C.byref(p), C.byref(n)))
+        Q = len(self.distance_pairs()[0])
+        cols, dt = ((12, np.float32), (4, np.int32), (Q, np.float32), (Q, np.int32), (12, np.float32))[int(which)]
+        shape = (self.N, n.value // (4 * cols * self.N) if cols else 0, cols)
+        if host:
+            out = np.empty(shape, dt)
+            nat.check(self.L.rr_signed_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
+            return out
+        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
+
+    def signed_distance(self, postures=None, host=False):
+        """The SIGNED distance of the pairs of `set_distance_pairs` for every env (rr_signed_distance): where two hulls are apart,
+        what `closest_points` reports; where they overlap, minus the penetration depth -- the length of the shortest translation
+        of shape a that separates the two convex hulls --, its direction, two witness points and a proved bound.  One launch on the
+        library's stream; the simulation is not touched.  postures None: the present state, one row per env; else float32
+        [N, K, 11] exactly as for `posture_clearance` (a numpy array is staged, a CUDA tensor is read in place).  Returns, with a
+        leading [N, K] (postures) or [N] (present state),
+          distance float32 -- the signed distance of the DEEPEST pair: the first minimum of the row's pair_distance; bound float32 --
+              for an overlapping pair minus a proved lower bound of the depth (-bound <= true depth <= -distance), else the lower
+              bound of the distance;
+          point_a, point_b, normal float32 [..., 3] -- a point of each hull and the unit vector from b towards a, a - b = distance *
+              normal for both signs: moving shape a by -distance * normal separates an overlapping pair;
+          status int32 -- 0 separated, 1 overlapping (the expansion converged), 2 culled (the spheres' gap), 3 GJK cap, 4 touching
+              (distance = bound = 0, normal 0), 5 expansion cap (distance and bound are still valid bounds); pair, body_a, body_b
+              int32 -- the pair's index in the table and the bodies as in the contact records;
+          pair_distance float32 [..., Q]; pair_status, pair_iterations, pair_expansions uint8 [..., Q] -- bytes 0, 1 and 2 of the
+              status words: status, GJK iterations, expansion trips;
+        and for the present state also every pair's record as [N, Q] columns: pair_bound, pair_point_a, pair_point_b, pair_normal
+        ([N, Q, 3]).  Device views (zero copy, strided, DLPack; valid after later work on the library's stream or `sync()`; they
+        hold what the last call computed), or with host=True numpy views of host copies after a sync."""
+        present = postures is None
+        K = 1 if present else self._posture_arg(postures, self.N)
+        if len(self.distance_pairs()[0]) == 0:
+            raise ValueError("signed_distance: the pair table is empty (set_distance_pairs)")
+        if present:
+            nat.check(self.L.rr_signed_distance(self.h, None, 0, 0))
+        else:
+            ptr, on_dev, keep = self._state_arg(postures, 'postures', ('float32',), (self.N, K, nat.N_JOINTS))
+            nat.check(self.L.rr_signed_distance(self.h, ptr, K, on_dev))
+            del keep
+        deep, ids, dist, st = (self.signed_buffer(i, host=host) for i in range(4))
+        if isinstance(deep, np.ndarray):
+            cut = lambda lo: deep[:, :, lo:lo + 3]
+        else:
+            cut = lambda lo: nat.DeviceBuffer(deep.ptr + 4 * lo, (self.N, K, 3), deep.typestr, deep._owner, strides=(K * 48, 48, 4))
+        col = self.ray_column
+        ps, pi = self.status_bytes(st)
+        pe = self.status_bytes(st, 1)[1]
+        out = dict(distance=col(deep, 0), bound=col(deep, 1), point_a=cut(2), point_b=cut(5), normal=cut(8), status=col(ids, 0),
+                   pair=col(ids, 1), body_a=col(ids, 2), body_b=col(ids, 3), pair_distance=dist, pair_status=ps, pair_iterations=pi,
+                   pair_expansions=pe)
+        if not present:
+            return out
+
+        def drop(v):        # the K' = 1 axis of a present-state query
+            if isinstance(v, np.ndarray):
+                return v[:, 0]
+            strides = v.strides if v.strides is not None else tuple(int(np.prod(v.shape[i + 1:])) * np.dtype(v.typestr).itemsize for i in range(len(v.shape)))
+            return nat.DeviceBuffer(v.ptr, v.shape[:1] + v.shape[2:], v.typestr, v._owner, strides=strides[:1] + strides[2:])
+        out = {k: drop(v) for k, v in out.items()}
+        pts = self.signed_buffer('points', host=host)
+        if isinstance(pts, np.ndarray):
+            cutq = lambda lo: pts[:, :, lo:lo + 3]
+        else:
+            Q = pts.shape[1]
+            cutq = lambda lo: nat.DeviceBuffer(pts.ptr + 4 * lo, (self.N, Q, 3), pts.typestr, pts._owner, strides=(Q * 48, 48, 4))
+        out.update(pair_bound=col(pts, 1), pair_point_a=cutq(2), pair_point_b=cutq(5), pair_normal=cutq(8))
+        return out
 
     def body_row_names(self):
         """The bodies of the rows of body_force / body_partners: the 17 URDF links, then this handle's objects (the rows of the

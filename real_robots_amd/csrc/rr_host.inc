@@ -148,6 +148,10 @@ struct rr_env : ModelTables {
     void *pc_buf[RR_PC_COUNT] = {};
     int pc_k = 0;                  // postures per env of the last query: 0 before the first
     float *pc_stage = nullptr;
+    // signed distance (rr_signed_distance): the five RR_SD_* buffers, allocated together on first use for RR_PC_MAX_POSTURES x RR_DIST_MAX
+    // (RR_SD_POINTS for RR_DIST_MAX), once; a host caller's postures go through pc_stage
+    void *sd_buf[RR_SD_COUNT] = {};
+    int sd_k = 0;                  // rows per env of the last query (1: the present state): 0 before the first
     MemOwner mem;                  // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
     bool created = false;
     bool timing = false;
@@ -1780,6 +1784,80 @@ int rr_posture_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
     HIPCHK(hipSetDevice(e->cfg.device));
     if (bytes == 0) return RR_OK;
     HIPCHK(hipMemcpyAsync(dst, e->pc_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return RR_OK;
+}
+
+// ---- signed distance and penetration depth (rr_signed.inc) -----------------------------------------------------------------------------
+// The five buffers of rr_signed_distance: allocated on first use -- by the query or by rr_signed_buffer / rr_signed_copy_to_host -- in
+// one list, zero-filled, for RR_PC_MAX_POSTURES rows of RR_DIST_MAX pairs (the per-pair records of the present state for RR_DIST_MAX
+// pairs).  The layout in force is [N, K', ...] for the K' of the last query (0 before the first) and the Q of the pair table.
+static size_t sd_bytes(const rr_env *e, int which, int K, int Q) {
+    if (which == RR_SD_POINTS) return (size_t)e->P.N * Q * 48;
+    return (size_t)e->P.N * K * (which == RR_SD_DEEPEST ? 48 : which == RR_SD_ID ? 16 : (size_t)Q * 4);
+}
+static int ensure_signed(rr_env *e, const char *who) {
+    if (e->sd_buf[0]) return RR_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    void *b[RR_SD_COUNT] = {};
+    MemPart parts[RR_SD_COUNT];
+    for (int i = 0; i < RR_SD_COUNT; i++) parts[i] = mem_part(&b[i], sd_bytes(e, i, RR_PC_MAX_POSTURES, RR_DIST_MAX));
+    RRCHK(mem_get(e, parts, RR_SD_COUNT, (std::string(who) + ": allocating the signed-distance buffers").c_str()));
+    for (int i = 0; i < RR_SD_COUNT; i++) e->sd_buf[i] = b[i];
+    return RR_OK;
+}
+
+// The signed distance of the pair table at the present state (postures == NULL) or at K candidate postures per env.  On the main stream
+// like rr_posture_clearance: behind every step, reset and state write enqueued before it.  Reads D.state, the model, the pair table and
+// the tensor; writes the five buffers (RR_SD_POINTS at the present state only) and nothing else -- not the state, the scratch slab of
+// the look-ahead, la_valid, an error flag or an RR_DIST_* / RR_PC_* buffer.
+int rr_signed_distance(rr_env *e, const float *postures, int32_t n_postures, int32_t on_device) {
+    if (!e) return fail(RR_EINVAL, "rr_signed_distance: null env");
+    if (!postures && n_postures != 0)
+        return fail(RR_EINVAL, "rr_signed_distance: null postures with n_postures " + std::to_string(n_postures) + " (the present state is NULL with 0)");
+    if (postures && (n_postures < 1 || n_postures > RR_PC_MAX_POSTURES))
+        return fail(RR_EINVAL, "rr_signed_distance: n_postures " + std::to_string(n_postures) + " is not in [1, RR_PC_MAX_POSTURES = " +
+                                   std::to_string(RR_PC_MAX_POSTURES) + "]");
+    const int Q = e->dist_n, N = e->P.N, K = postures ? n_postures : 1;
+    if (Q == 0) return fail(RR_EINVAL, "rr_signed_distance: the pair table is empty (rr_set_distance_pairs)");
+    RRCHK(ensure_dist(e, "rr_signed_distance"));          // (the device copy of the pair table)
+    RRCHK(ensure_signed(e, "rr_signed_distance"));
+    const bool stage = postures && !on_device;
+    if (stage && !e->pc_stage)
+        RRCHK(mem_get(e, {mem_part(&e->pc_stage, (size_t)N * RR_PC_MAX_POSTURES * 44, false)}, "rr_signed_distance: allocating the staging buffer"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const float *src = postures;
+    if (stage) {
+        HIPCHK(hipMemcpyAsync(e->pc_stage, postures, (size_t)N * K * 44, hipMemcpyHostToDevice, e->stream));
+        src = e->pc_stage;
+    }
+    hipLaunchKernelGGL(k_signed_distance, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
+                       (float4 *)e->sd_buf[RR_SD_DEEPEST], (int4 *)e->sd_buf[RR_SD_ID], (float *)e->sd_buf[RR_SD_SIGNED], (int *)e->sd_buf[RR_SD_STATUS],
+                       postures ? (float4 *)nullptr : (float4 *)e->sd_buf[RR_SD_POINTS]);
+    HIPCHK(hipGetLastError());
+    e->sd_k = K;
+    if (stage) HIPCHK(hipStreamSynchronize(e->stream));        // the argument is host memory
+    return RR_OK;
+}
+
+int rr_signed_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_signed_buffer: null env");
+    if (which < 0 || which >= RR_SD_COUNT) return fail(RR_EINVAL, "rr_signed_buffer: buffer " + std::to_string(which) + " is not in [0, RR_SD_COUNT)");
+    RRCHK(ensure_signed(e, "rr_signed_buffer"));
+    if (dev_ptr) *dev_ptr = e->sd_buf[which];
+    if (bytes) *bytes = sd_bytes(e, which, e->sd_k, e->dist_n);
+    return RR_OK;
+}
+
+int rr_signed_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_signed_copy_to_host: null env");
+    if (!dst) return fail(RR_EINVAL, "rr_signed_copy_to_host: null destination");
+    if (which < 0 || which >= RR_SD_COUNT) return fail(RR_EINVAL, "rr_signed_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_SD_COUNT)");
+    if (bytes != sd_bytes(e, which, e->sd_k, e->dist_n)) return fail(RR_EINVAL, "rr_signed_copy_to_host: size mismatch");
+    RRCHK(ensure_signed(e, "rr_signed_copy_to_host"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    if (bytes == 0) return RR_OK;
+    HIPCHK(hipMemcpyAsync(dst, e->sd_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return RR_OK;
 }
