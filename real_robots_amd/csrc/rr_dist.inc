@@ -7,7 +7,7 @@
 //
 // DIST_ENVS envs (one) per 256-thread workgroup, ONE WAVE64 PER (env, pair): item i of the workgroup is pair i / DIST_ENVS of env
 // i % DIST_ENVS, wave w takes the items w, w + 4, ...  Phases 1 and 2 are k_ray_cast's (dist_stage_frames: the step's frames in LDS).
-// Per item, all 64 lanes:
+// Per item, all 64 lanes (dist_pair):
 //   a  the two shapes' frames from LDS; the bounding-sphere gap, and with a cull the status-2 record;
 //   b  lane l takes the vertices l, l + 64, l + 128 of A and of B, once, into registers: turned into the world ABOUT THE SHAPE'S
 //      SPHERE CENTRE, R (x - c_local), so that they keep the rounding of a shape-sized number; the centres' difference cc is carried
@@ -132,6 +132,140 @@ __device__ __forceinline__ v3 dist_fetch(const v3 x0, const v3 x1, const v3 x2, 
 __device__ __forceinline__ double dist_ddot(const v3 a, const v3 b) { return (double)a.x * b.x + (double)a.y * b.y + (double)a.z * b.z; }
 __device__ __forceinline__ float dist_det(const v3 a, const v3 b, const v3 c) { return dot(a, cross(b, c)); }
 
+// One pair of the table for the 64 lanes of one wave: steps a to c of the header, the text that k_closest_points and
+// k_posture_clearance (rr_posture.inc) both run; it returns the record's three float4, status, trips and the owners of the two
+// shapes, the same values in every lane.  (k_signed_distance keeps a copy of its own, sd_pair: rr_signed.inc says why.)
+struct DistItem { float4 o0, o1, o2; int status, iters, ota, oia, otb, oib; };
+__device__ __forceinline__ DistItem dist_pair(const ShapeData *__restrict__ S, const DistTable *__restrict__ tab, const int j, const float *fr, const float *ob,
+                                                const bool cull, const float maxd, const int lane) {
+    // a.  (The table is validated by rr_set_distance_pairs; the clamps only keep the model's tables in range.)
+    const int sa = min(max(__builtin_amdgcn_readfirstlane(tab->a[j]), 0), MAXSHAPES - 1), sb = min(max(__builtin_amdgcn_readfirstlane(tab->b[j]), 0), MAXSHAPES - 1);
+    const int ota = S->otype[sa], otb = S->otype[sb];
+    const int oia = min(max(S->oidx[sa], 0), ota == 2 ? NOBJ - 1 : NB - 1), oib = min(max(S->oidx[sb], 0), otb == 2 ? NOBJ - 1 : NB - 1);
+    m3 Ra, Rb; v3 pa, pb;
+    ray_shape_frame(ota, oia, fr, ob, &Ra, &pa);
+    ray_shape_frame(otb, oib, fr, ob, &Rb, &pb);
+    const v3 sca = mk(S->sphere[sa][0], S->sphere[sa][1], S->sphere[sa][2]), scb = mk(S->sphere[sb][0], S->sphere[sb][1], S->sphere[sb][2]);
+    const v3 ca = mulv(Ra, sca) + pa, cb = mulv(Rb, scb) + pb;
+    const float ra = S->sphere[sa][3], rb = S->sphere[sb][3];
+    const v3 cc = ca - cb;
+    const float cn = sqrtf(dot(cc, cc));
+    const float gap = cn - ra - rb;
+    float4 o0, o1, o2;
+    int status, iters = 0;
+    if (cull && gap > maxd) {
+        const v3 u = cc * (1.0f / cn);
+        const v3 xa = ca - u * ra, xb = cb + u * rb;
+        status = 2;
+        o0 = make_float4(gap, gap, xa.x, xa.y); o1 = make_float4(xa.z, xb.x, xb.y, xb.z); o2 = make_float4(u.x, u.y, u.z, 0.0f);
+    } else {
+        // b
+        v3 xa[DIST_TRIPS], xb[DIST_TRIPS];
+        const int nva = min(max(S->nv[sa], 1), VMAXC), nvb = min(max(S->nv[sb], 1), VMAXC);
+#pragma unroll
+        for (int t = 0; t < DIST_TRIPS; t++) {
+            const int ka = min(64 * t + lane, nva - 1), kb = min(64 * t + lane, nvb - 1);
+            xa[t] = mulv(Ra, mk(S->verts[sa][ka][0], S->verts[sa][ka][1], S->verts[sa][ka][2]) - sca);
+            xb[t] = mulv(Rb, mk(S->verts[sb][kb][0], S->verts[sb][kb][1], S->verts[sb][kb][2]) - scb);
+        }
+        // c.  The simplex: three slots {r = a - b about the centres (the point is r + cc), a, b, the two vertex indices, weight}; weight 0: the slot is free.
+        v3 sr[3], sA[3], sB[3];
+        int ia[3], ib[3];
+        float lam[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int k = 0; k < 3; k++) { sr[k] = sA[k] = sB[k] = mk(0.0f, 0.0f, 0.0f); ia[k] = ib[k] = -1; }
+        v3 v = cn > 0.0f ? cc : mk(1.0f, 0.0f, 0.0f);             // the first direction: between the sphere centres (no point of the simplex yet)
+        double vv = INFINITY;
+        float lower = 0.0f;
+        status = 3;
+        for (int it = 0; it < DIST_ITER_CAP; it++) {
+            iters = it + 1;
+            const int ja = dist_support(xa, v * -1.0f, lane), jb = dist_support(xb, v, lane);
+            const v3 wa = dist_fetch(xa[0], xa[1], xa[2], ja), wb = dist_fetch(xb[0], xb[1], xb[2], jb);
+            const v3 r = wa - wb, w = r + cc;
+            const double vw = dist_ddot(v, w);
+            const float vn = sqrtf(dot(v, v));
+            if (vn > 0.0f) lower = fmaxf(lower, (float)vw / vn);
+            bool stop = false;
+            if (it > 0) {
+                bool dup = false;
+#pragma unroll
+                for (int k = 0; k < 3; k++) dup = dup || (lam[k] > 0.0f && ia[k] == ja && ib[k] == jb);
+                stop = dup || vv - vw <= (double)DIST_EPS * vv;
+            }
+            if (__builtin_amdgcn_readfirstlane(stop)) { status = 0; break; }
+            // the nearest point of the features that hold w: weights l[0..2] of the slots and lw of w
+            float l[3] = {0.0f, 0.0f, 0.0f}, lw = 1.0f;
+            v3 nv = w;
+            double nvv = dist_ddot(w, w);
+#pragma unroll
+            for (int k = 0; k < 3; k++) {                           // segments w -- slot k
+                const v3 d = sr[k] - r;
+                const float dd = dot(d, d);
+                const float t = fminf(fmaxf(-dot(w, d) / dd, 0.0f), 1.0f);
+                const v3 p = w + d * t;
+                const double pp = dist_ddot(p, p);
+                if (lam[k] > 0.0f && dd > 0.0f && pp < nvv) {
+                    nvv = pp; nv = p; lw = 1.0f - t;
+                    l[0] = l[1] = l[2] = 0.0f; l[k] = t;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 3; k++) {                           // triangles w, slot f, slot g: (0, 1), (1, 2), (2, 0)
+                const int f = k, g = (k + 1) % 3;
+                const v3 ab = sr[f] - r, ac = sr[g] - r, wf = sr[f] + cc, wg = sr[g] + cc;
+                const float d1 = -dot(ab, w), d2 = -dot(ac, w), d3 = -dot(ab, wf), d4 = -dot(ac, wf), d5 = -dot(ab, wg), d6 = -dot(ac, wg);
+                const float va = d3 * d6 - d5 * d4, vb = d5 * d2 - d1 * d6, vc = d1 * d4 - d3 * d2;
+                const v3 n = cross(ab, ac);
+                const float nn = dot(n, n);
+                const v3 p = n * (dot(n, w) / nn);
+                const double pp = dist_ddot(p, p);
+                const bool in = lam[f] > 0.0f && lam[g] > 0.0f && va > 0.0f && vb > 0.0f && vc > 0.0f && nn > 1e-10f * dot(ab, ab) * dot(ac, ac);
+                if (in && pp < nvv) {
+                    const float q = 1.0f / (va + vb + vc);
+                    nvv = pp; nv = p; lw = va * q;
+                    l[0] = l[1] = l[2] = 0.0f; l[f] = vb * q; l[g] = vc * q;
+                }
+            }
+            bool inside = false;
+            if (lam[0] > 0.0f && lam[1] > 0.0f && lam[2] > 0.0f) {  // the tetrahedron slot 0, 1, 2, w
+                const v3 a = sr[0] + cc, ab = sr[1] - sr[0], ac = sr[2] - sr[0], ad = r - sr[0];
+                const float V = dist_det(ab, ac, ad);
+                const float La = dist_det(sr[1] + cc, sr[2] + cc, w), Lb = dist_det(a * -1.0f, ac, ad), Lc = dist_det(ab, a * -1.0f, ad), Ld = dist_det(ab, ac, a * -1.0f);
+                const float sg = V > 0.0f ? 1.0f : -1.0f;
+                inside = fabsf(V) > 1e-6f * sqrtf(dot(ab, ab) * dot(ac, ac) * dot(ad, ad)) && La * sg >= 0.0f && Lb * sg >= 0.0f && Lc * sg >= 0.0f && Ld * sg >= 0.0f;
+            }
+            if (__builtin_amdgcn_readfirstlane(inside)) { status = 1; break; }
+            if (__builtin_amdgcn_readfirstlane(it > 0 && !(nvv < vv))) { status = 0; break; }     // not strictly nearer: v stays
+            // w into the first free slot
+            bool placed = false;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const bool here = !placed && !(l[k] > 0.0f);
+                if (here) { sr[k] = r; sA[k] = wa; sB[k] = wb; ia[k] = ja; ib[k] = jb; }
+                lam[k] = here ? lw : l[k];
+                placed = placed || here;
+            }
+            v = nv; vv = nvv;
+            if (__builtin_amdgcn_readfirstlane(vv <= (double)DIST_TOUCH * DIST_TOUCH)) { status = 1; break; }
+        }
+        v3 xA = mk(0.0f, 0.0f, 0.0f), xB = xA;                  // the weighted vertices about the centres, then the centres
+#pragma unroll
+        for (int k = 0; k < 3; k++) { xA = xA + sA[k] * lam[k]; xB = xB + sB[k] * lam[k]; }
+        xA = xA + ca; xB = xB + cb;
+        if (status == 1) {
+            o0 = make_float4(0.0f, 0.0f, xA.x, xA.y); o1 = make_float4(xA.z, xA.x, xA.y, xA.z); o2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        } else {
+            const float dist = sqrtf((float)vv);
+            const v3 n = v * (1.0f / dist);
+            o0 = make_float4(dist, fminf(lower, dist), xA.x, xA.y); o1 = make_float4(xA.z, xB.x, xB.y, xB.z); o2 = make_float4(n.x, n.y, n.z, 0.0f);
+        }
+    }
+    DistItem R;
+    R.o0 = o0; R.o1 = o1; R.o2 = o2; R.status = status; R.iters = iters; R.ota = ota; R.oia = oia; R.otb = otb; R.oib = oib;
+    return R;
+}
+
 __global__ void __launch_bounds__(DIST_THREADS) k_closest_points(BodyParams B, SimParams P, DevPtrs D, const DistTable *__restrict__ tab, int Q,
                                                                  float4 *__restrict__ out_pts /*[N][Q][3]*/, int4 *__restrict__ out_id /*[N][Q]*/) {
     static_assert(64 * DIST_TRIPS == VMAXC && DIST_ENVS <= DIST_WAVES * 64 / 4, "a lane holds three vertices of a shape; dist_stage_frames' threads");
@@ -149,134 +283,11 @@ __global__ void __launch_bounds__(DIST_THREADS) k_closest_points(BodyParams B, S
     for (int i = wave; i < items; i += DIST_WAVES) {
         const int e = i % DIST_ENVS, j = i / DIST_ENVS, env = env0 + e;
         if (env >= N) continue;                                                                 // (uniform in the wave)
-        const float *fr = s_fr[e], *ob = s_ob[e];
-        // a.  (The table is validated by rr_set_distance_pairs; the clamps only keep the model's tables in range.)
-        const int sa = min(max(__builtin_amdgcn_readfirstlane(tab->a[j]), 0), MAXSHAPES - 1), sb = min(max(__builtin_amdgcn_readfirstlane(tab->b[j]), 0), MAXSHAPES - 1);
-        const int ota = S->otype[sa], otb = S->otype[sb];
-        const int oia = min(max(S->oidx[sa], 0), ota == 2 ? NOBJ - 1 : NB - 1), oib = min(max(S->oidx[sb], 0), otb == 2 ? NOBJ - 1 : NB - 1);
-        m3 Ra, Rb; v3 pa, pb;
-        ray_shape_frame(ota, oia, fr, ob, &Ra, &pa);
-        ray_shape_frame(otb, oib, fr, ob, &Rb, &pb);
-        const v3 sca = mk(S->sphere[sa][0], S->sphere[sa][1], S->sphere[sa][2]), scb = mk(S->sphere[sb][0], S->sphere[sb][1], S->sphere[sb][2]);
-        const v3 ca = mulv(Ra, sca) + pa, cb = mulv(Rb, scb) + pb;
-        const float ra = S->sphere[sa][3], rb = S->sphere[sb][3];
-        const v3 cc = ca - cb;
-        const float cn = sqrtf(dot(cc, cc));
-        const float gap = cn - ra - rb;
-        float4 o0, o1, o2;
-        int status, iters = 0;
-        if (cull && gap > maxd) {
-            const v3 u = cc * (1.0f / cn);
-            const v3 xa = ca - u * ra, xb = cb + u * rb;
-            status = 2;
-            o0 = make_float4(gap, gap, xa.x, xa.y); o1 = make_float4(xa.z, xb.x, xb.y, xb.z); o2 = make_float4(u.x, u.y, u.z, 0.0f);
-        } else {
-            // b
-            v3 xa[DIST_TRIPS], xb[DIST_TRIPS];
-            const int nva = min(max(S->nv[sa], 1), VMAXC), nvb = min(max(S->nv[sb], 1), VMAXC);
-#pragma unroll
-            for (int t = 0; t < DIST_TRIPS; t++) {
-                const int ka = min(64 * t + lane, nva - 1), kb = min(64 * t + lane, nvb - 1);
-                xa[t] = mulv(Ra, mk(S->verts[sa][ka][0], S->verts[sa][ka][1], S->verts[sa][ka][2]) - sca);
-                xb[t] = mulv(Rb, mk(S->verts[sb][kb][0], S->verts[sb][kb][1], S->verts[sb][kb][2]) - scb);
-            }
-            // c.  The simplex: three slots {r = a - b about the centres (the point is r + cc), a, b, the two vertex indices, weight}; weight 0: the slot is free.
-            v3 sr[3], sA[3], sB[3];
-            int ia[3], ib[3];
-            float lam[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int k = 0; k < 3; k++) { sr[k] = sA[k] = sB[k] = mk(0.0f, 0.0f, 0.0f); ia[k] = ib[k] = -1; }
-            v3 v = cn > 0.0f ? cc : mk(1.0f, 0.0f, 0.0f);             // the first direction: between the sphere centres (no point of the simplex yet)
-            double vv = INFINITY;
-            float lower = 0.0f;
-            status = 3;
-            for (int it = 0; it < DIST_ITER_CAP; it++) {
-                iters = it + 1;
-                const int ja = dist_support(xa, v * -1.0f, lane), jb = dist_support(xb, v, lane);
-                const v3 wa = dist_fetch(xa[0], xa[1], xa[2], ja), wb = dist_fetch(xb[0], xb[1], xb[2], jb);
-                const v3 r = wa - wb, w = r + cc;
-                const double vw = dist_ddot(v, w);
-                const float vn = sqrtf(dot(v, v));
-                if (vn > 0.0f) lower = fmaxf(lower, (float)vw / vn);
-                bool stop = false;
-                if (it > 0) {
-                    bool dup = false;
-#pragma unroll
-                    for (int k = 0; k < 3; k++) dup = dup || (lam[k] > 0.0f && ia[k] == ja && ib[k] == jb);
-                    stop = dup || vv - vw <= (double)DIST_EPS * vv;
-                }
-                if (__builtin_amdgcn_readfirstlane(stop)) { status = 0; break; }
-                // the nearest point of the features that hold w: weights l[0..2] of the slots and lw of w
-                float l[3] = {0.0f, 0.0f, 0.0f}, lw = 1.0f;
-                v3 nv = w;
-                double nvv = dist_ddot(w, w);
-#pragma unroll
-                for (int k = 0; k < 3; k++) {                           // segments w -- slot k
-                    const v3 d = sr[k] - r;
-                    const float dd = dot(d, d);
-                    const float t = fminf(fmaxf(-dot(w, d) / dd, 0.0f), 1.0f);
-                    const v3 p = w + d * t;
-                    const double pp = dist_ddot(p, p);
-                    if (lam[k] > 0.0f && dd > 0.0f && pp < nvv) {
-                        nvv = pp; nv = p; lw = 1.0f - t;
-                        l[0] = l[1] = l[2] = 0.0f; l[k] = t;
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 3; k++) {                           // triangles w, slot f, slot g: (0, 1), (1, 2), (2, 0)
-                    const int f = k, g = (k + 1) % 3;
-                    const v3 ab = sr[f] - r, ac = sr[g] - r, wf = sr[f] + cc, wg = sr[g] + cc;
-                    const float d1 = -dot(ab, w), d2 = -dot(ac, w), d3 = -dot(ab, wf), d4 = -dot(ac, wf), d5 = -dot(ab, wg), d6 = -dot(ac, wg);
-                    const float va = d3 * d6 - d5 * d4, vb = d5 * d2 - d1 * d6, vc = d1 * d4 - d3 * d2;
-                    const v3 n = cross(ab, ac);
-                    const float nn = dot(n, n);
-                    const v3 p = n * (dot(n, w) / nn);
-                    const double pp = dist_ddot(p, p);
-                    const bool in = lam[f] > 0.0f && lam[g] > 0.0f && va > 0.0f && vb > 0.0f && vc > 0.0f && nn > 1e-10f * dot(ab, ab) * dot(ac, ac);
-                    if (in && pp < nvv) {
-                        const float q = 1.0f / (va + vb + vc);
-                        nvv = pp; nv = p; lw = va * q;
-                        l[0] = l[1] = l[2] = 0.0f; l[f] = vb * q; l[g] = vc * q;
-                    }
-                }
-                bool inside = false;
-                if (lam[0] > 0.0f && lam[1] > 0.0f && lam[2] > 0.0f) {  // the tetrahedron slot 0, 1, 2, w
-                    const v3 a = sr[0] + cc, ab = sr[1] - sr[0], ac = sr[2] - sr[0], ad = r - sr[0];
-                    const float V = dist_det(ab, ac, ad);
-                    const float La = dist_det(sr[1] + cc, sr[2] + cc, w), Lb = dist_det(a * -1.0f, ac, ad), Lc = dist_det(ab, a * -1.0f, ad), Ld = dist_det(ab, ac, a * -1.0f);
-                    const float sg = V > 0.0f ? 1.0f : -1.0f;
-                    inside = fabsf(V) > 1e-6f * sqrtf(dot(ab, ab) * dot(ac, ac) * dot(ad, ad)) && La * sg >= 0.0f && Lb * sg >= 0.0f && Lc * sg >= 0.0f && Ld * sg >= 0.0f;
-                }
-                if (__builtin_amdgcn_readfirstlane(inside)) { status = 1; break; }
-                if (__builtin_amdgcn_readfirstlane(it > 0 && !(nvv < vv))) { status = 0; break; }     // not strictly nearer: v stays
-                // w into the first free slot
-                bool placed = false;
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const bool here = !placed && !(l[k] > 0.0f);
-                    if (here) { sr[k] = r; sA[k] = wa; sB[k] = wb; ia[k] = ja; ib[k] = jb; }
-                    lam[k] = here ? lw : l[k];
-                    placed = placed || here;
-                }
-                v = nv; vv = nvv;
-                if (__builtin_amdgcn_readfirstlane(vv <= (double)DIST_TOUCH * DIST_TOUCH)) { status = 1; break; }
-            }
-            v3 xA = mk(0.0f, 0.0f, 0.0f), xB = xA;                  // the weighted vertices about the centres, then the centres
-#pragma unroll
-            for (int k = 0; k < 3; k++) { xA = xA + sA[k] * lam[k]; xB = xB + sB[k] * lam[k]; }
-            xA = xA + ca; xB = xB + cb;
-            if (status == 1) {
-                o0 = make_float4(0.0f, 0.0f, xA.x, xA.y); o1 = make_float4(xA.z, xA.x, xA.y, xA.z); o2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            } else {
-                const float dist = sqrtf((float)vv);
-                const v3 n = v * (1.0f / dist);
-                o0 = make_float4(dist, fminf(lower, dist), xA.x, xA.y); o1 = make_float4(xA.z, xB.x, xB.y, xB.z); o2 = make_float4(n.x, n.y, n.z, 0.0f);
-            }
-        }
+        const DistItem R = dist_pair(S, tab, j, s_fr[e], s_ob[e], cull, maxd, lane);
         if (lane == 0) {
             const size_t r = (size_t)env * Q + j;
-            out_pts[3 * r] = o0; out_pts[3 * r + 1] = o1; out_pts[3 * r + 2] = o2;
-            out_id[r] = make_int4(status, iters, ota == 0 ? -1 : (ota == 1 ? oia : 16 + oia), otb == 0 ? -1 : (otb == 1 ? oib : 16 + oib));
+            out_pts[3 * r] = R.o0; out_pts[3 * r + 1] = R.o1; out_pts[3 * r + 2] = R.o2;
+            out_id[r] = make_int4(R.status, R.iters, R.ota == 0 ? -1 : (R.ota == 1 ? R.oia : 16 + R.oia), R.otb == 0 ? -1 : (R.otb == 1 ? R.oib : 16 + R.oib));
         }
     }
 }

@@ -8,8 +8,9 @@
 // One 256-thread workgroup per row (env, posture), grid N * K' exactly (K' = 1 at the present state); its four waves take every
 // fourth pair, ONE WAVE64 PER PAIR.  Phases 1, 2 and 4 are k_posture_clearance's (the staged floats, the frames, the reduction to the
 // row's first minimum through LDS behind the one barrier every wave reaches); the joints come from the tensor or, without one, from
-// D.state.  A pair is steps a to c of rr_dist.inc's header RESTATED once more as sd_pair (the standing rule: a pull request that adds
-// a kernel leaves every existing kernel's text alone), with two additions: the GJK tells its two status-1 exits apart -- the
+// D.state.  A pair is steps a to c of rr_dist.inc's header RESTATED as sd_pair (running rr_dist.inc's text here was built and measured:
+// this kernel went from 117 to 131 VGPRs, three waves per SIMD, and held to 128 by a launch bound it was 0.1 to 0.3 % slower on the
+// collision table; so it keeps its copy: DESIGN.md), with two additions: the GJK tells its two status-1 exits apart -- the
 // tetrahedron that holds the origin, or |v| <= DIST_TOUCH --, and at the first it hands over the tetrahedron: the three slots and w,
 // each with its r = a_i - b_j about the sphere centres and its two vertex indices.
 //

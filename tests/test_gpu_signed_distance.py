@@ -231,9 +231,11 @@ def test_bit_identity():
     assert bothk.sum() >= 1000 and np.abs(pc['pair_distance'].astype(np.float64) - first['pair_distance'])[bothk].max() <= TOL_DIST
     dec = ref['decided'].reshape(4, 4, 80)
     assert (first['pair_status'][dec] == pc['pair_status'][dec]).all() and (first['pair_distance'][dec & (pc['pair_status'] == 1)] < 0).all()
-    print('non-overlapping items whose distance bits differ: from rr_closest_points %d of %d, from rr_posture_clearance %d of %d'
-          % ((_bits(cp['distance']) != _bits(present['pair_distance']))[both].sum(), both.sum(),
-             (_bits(pc['pair_distance']) != _bits(first['pair_distance']))[bothk].sum(), bothk.sum()))
+    # sd_pair's first half is rr_dist.inc's dist_pair restated: the same bits, and the same full record where both write one
+    assert (_bits(cp['distance']) == _bits(present['pair_distance']))[both].all()
+    assert (_bits(pc['pair_distance']) == _bits(first['pair_distance']))[bothk].all()
+    points, sd_points = env.distance_buffer(0, host=True), env.signed_buffer('points', host=True)      # RR_DIST_POINTS, RR_SD_POINTS: [4, 80, 12]
+    assert points.shape == sd_points.shape == (4, 80, 12) and (_bits(points) == _bits(sd_points))[both].all()
     # a permuted pair table: permuted columns, permuted back
     perm = np.random.default_rng(3).permutation(80)
     inv = np.argsort(perm)
