@@ -42,7 +42,9 @@ extern "C" {
                               rr_posture_clearance, rr_posture_buffer, rr_posture_copy_to_host (clearance of the pair table at candidate
                               joint postures, the nearest pair reduced on the device); rr_signed_distance, rr_signed_buffer,
                               rr_signed_copy_to_host (signed distance of the pair table: penetration depth, direction and witness points
-                              where hulls overlap, at the present state or at candidate postures) */
+                              where hulls overlap, at the present state or at candidate postures); rr_signed_gradient,
+                              rr_signed_gradient_buffer, rr_signed_gradient_copy_to_host (that query plus the joint gradients of the
+                              deepest pair's signed distance and of a hinge collision cost, reduced on the device) */
 
 enum {
     RR_OK = 0,
@@ -746,9 +748,10 @@ enum {
  * readers on another stream order themselves after the call (event / rr_sync), and a later call rewrites the buffers in place.
  * Determinism.  No atomics and a fixed reduction order: row (e, k) is a function of (env e's objects, posture (e, k), the table)
  * alone -- identical from call to call, independent of N, of K, of the row's place and of its neighbours.
- * Out of scope: candidate object poses; per-posture pair tables; signed distances and penetration depth; gradients (n . (J_a - J_b)
- * with the Jacobians of rr_kinematic_observations at the present state is the caller's to form); rays and kinematics at candidate
- * postures; a switch of the vector env (postures are an argument, not an observation). */
+ * Out of scope: candidate object poses; per-posture pair tables; signed distances and penetration depth (rr_signed_distance);
+ * gradients over the joints (rr_signed_gradient computes them at the candidate postures themselves; n . (J_a - J_b) with the
+ * Jacobians of rr_kinematic_observations holds at the present state only); rays and kinematics at candidate postures; a switch of
+ * the vector env (postures are an argument, not an observation). */
 int rr_posture_clearance(rr_env *env, const float *postures /* f32 [N][K][11] */, int32_t n_postures, int32_t on_device);
 /* Zero-copy device pointer + size in bytes of an RR_PC_* buffer (read-only for the caller); which outside [0, RR_PC_COUNT): RR_EINVAL. */
 int rr_posture_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
@@ -818,13 +821,70 @@ enum {
  * data until the next query.  STREAM CONTRACT for readers as for the other zero-copy views: the kernel runs on the library's stream
  * behind the work enqueued before it; readers on another stream order themselves after the call (event / rr_sync), and a later call
  * rewrites the buffers in place.
- * Out of scope: gradients with respect to the joints; a switch of the vector env; penetration of non-convex shapes (a shape is the
- * convex hull of its vertex set); any use by the step -- the step's own narrow phase is untouched. */
+ * Out of scope: gradients with respect to the joints (rr_signed_gradient below: this query plus the gradients); a switch of the
+ * vector env; penetration of non-convex shapes (a shape is the convex hull of its vertex set); any use by the step -- the step's
+ * own narrow phase is untouched. */
 int rr_signed_distance(rr_env *env, const float *postures /* f32 [N][K][11] or NULL */, int32_t n_postures, int32_t on_device);
 /* Zero-copy device pointer + size in bytes of an RR_SD_* buffer (read-only for the caller); which outside [0, RR_SD_COUNT): RR_EINVAL. */
 int rr_signed_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
 /* Synchronising copy of a whole RR_SD_* buffer (its `bytes`) to host memory. */
 int rr_signed_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
+
+/* ---- Joint gradients of the signed distance on the device (additive in ABI 7) ----------------------------------------------------------
+ * What a trajectory optimiser needs and a sampler does not: d(signed distance) / d(joint), at the present state or AT the K candidate
+ * postures -- where rr_kinematic_observations has no Jacobian to offer.  One call is rr_signed_distance with the same arguments plus,
+ * per row, the gradient of the deepest pair's signed distance over the eleven joints, a hinge collision cost over ALL pairs and that
+ * cost's gradient, both reduced on the device; a present-state query also gets every pair's gradient.  The buffers are not fields of
+ * rr_get_buffer and not buffers of the queries above (RR_F_COUNT stays 16, the count of the signed-distance enum 5): they have this
+ * enum and rr_signed_gradient_buffer.  K' is 1 for a present-state query, else K. */
+enum {
+    RR_SG_GRADIENT = 0,       /* f32 [N, K', 12] {d s* / dq_0..10, +0.0}: s* the signed distance of the row's RR_SD_DEEPEST pair */
+    RR_SG_COST = 1,           /* f32 [N, K', 12] {dC / dq_0..10, C} */
+    RR_SG_PAIR_GRADIENT = 2,  /* f32 [N, Q, 12]  {d s_j / dq_0..10, +0.0} of every pair; written by a PRESENT-STATE query only */
+    RR_SG_COUNT = 3
+};
+/* Arguments.  env, postures, n_postures and on_device mean what they mean to rr_signed_distance: the present state (NULL, 0) or
+ * K <= RR_PC_MAX_POSTURES postures f32 [N][K][11], device memory read in place under that call's STREAM CONTRACT or host memory
+ * staged (the call then waits); values are not validated.  margin (m, finite, >= 0) is the distance below which a pair costs.
+ * What the call writes.  The five buffers of rr_signed_distance get what rr_signed_distance with the same arguments would write,
+ * byte for byte (so the per-pair columns exist once, and rr_signed_buffer reads them); the three RR_SG_* buffers are written in addition.
+ * The gradient.  With the record of pair j -- a on shape A, b on shape B, n the unit normal from b towards a, a - b = s n for both
+ * signs of the signed distance s --,
+ *     ds/dq_k = [joint k moves A's body] n . (a_k x (a - p_k)) - [joint k moves B's body] n . (a_k x (b - p_k)),
+ * a_k the world axis of joint k at that row's posture and p_k its position; "moves": k is the body's own joint or an ancestor's.
+ * Static shapes (table, shelf, robot_base) and the objects have no columns: the objects stay where they are, as for
+ * rr_posture_clearance, and a joint that moves neither shape gets +0.0.  The columns are over the eleven independent joints of the
+ * state's q[11]; over the nine command entries the gradient is gradient @ Q_FROM_CMD of the binding.  By status of the pair:
+ * 0, 1: the gradient of the signed distance; 2 (culled): the same expression on the sphere points, exactly the gradient of the
+ * reported sphere gap; 3, 5: the expression on the record as reported; 4 (touching, n = +0.0): +0.0 in every column.  Where the
+ * witness features switch (face against face, parallel edges) s has a kink: the result is the gradient of the ACTIVE feature pair,
+ * a generalised gradient, and like the witness points themselves it need not be unique there.  Plain float32.
+ * The cost.  With c_j = margin - s_j where that is > 0 and 0 otherwise (a NaN therefore contributes nothing),
+ *     C = 1/2 sum_j c_j^2,     dC/dq = - sum_j c_j ds_j/dq,
+ * over every pair of the table with its RR_SD_SIGNED value; margin 0 counts penetrations only.
+ * Summation order: each of the row's four waves sums its pairs j = w, w + 4, ... ascending, in float32, from +0.0; then the waves
+ * are summed in the order 0, 1, 2, 3.  No atomics: a row is identical from call to call and independent of N, K, the row's place
+ * and its neighbours.  RR_SG_PAIR_GRADIENT rows follow a permuted table; the cost sums do NOT stay bit-identical under a permuted
+ * table (another order of the same terms).
+ * No effect on the simulation: the call reads what rr_signed_distance reads and writes these eight buffers only; the next step stays
+ * prepared.  Every loop bound is a constant or a count, no value of the tensor or the state forms an address; non-finite input
+ * finishes like any other and its rows are unspecified.
+ * Errors: RR_EINVAL with nothing allocated and nothing changed, the message naming the cause, for what rr_signed_distance refuses
+ * (null env, an empty pair table, n_postures outside [1, RR_PC_MAX_POSTURES] with postures given, NULL postures with n_postures
+ * != 0), for a margin that is NaN, infinite or negative, and for a cull in force (0 < max_distance < inf) with margin >
+ * max_distance: a culled pair's sphere gap would then enter the hinge as if it were a distance.
+ * Buffers.  All three are allocated on first use -- by this call, or by rr_signed_gradient_buffer /
+ * rr_signed_gradient_copy_to_host --, all or nothing through the handle's memory owner, zero-filled, sized once for
+ * RR_PC_MAX_POSTURES rows (RR_SG_PAIR_GRADIENT for RR_DIST_MAX pairs) and valid until rr_destroy: no pointer ever changes.  The
+ * layout is compact for the K' of the last gradient query (0 before the first) and the Q in force, and `bytes` reports that.  After
+ * rr_set_distance_pairs the buffers hold unspecified data until the next query.  STREAM CONTRACT for readers as for the sibling views.
+ * Out of scope: gradients with respect to object poses; per-pair gradients at postures (600 MB at 4096 x 32 x 96: narrow the table
+ * instead); second derivatives; a switch of the vector env; any use by the step. */
+int rr_signed_gradient(rr_env *env, const float *postures /* f32 [N][K][11] or NULL */, int32_t n_postures, int32_t on_device, float margin);
+/* Zero-copy device pointer + size in bytes of an RR_SG_* buffer (read-only for the caller); which outside [0, RR_SG_COUNT): RR_EINVAL. */
+int rr_signed_gradient_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
+/* Synchronising copy of a whole RR_SG_* buffer (its `bytes`) to host memory. */
+int rr_signed_gradient_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
 
 /* Batched damped-least-squares inverse kinematics for link 7 (gripper `base`), seeded with each env's current joints.
  * Replaces pybullet.calculateInverseKinematics(0, 7, pos, orn, maxNumIterations=1000, residualThreshold=0.001) in

@@ -43,7 +43,8 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_set_rays', 'rr_get_rays', 'rr_ray_cast', 'rr_ray_buffer', 'rr_ray_copy_to_host',
            'rr_set_distance_pairs', 'rr_get_distance_pairs', 'rr_closest_points', 'rr_distance_buffer', 'rr_distance_copy_to_host',
            'rr_posture_clearance', 'rr_posture_buffer', 'rr_posture_copy_to_host',
-           'rr_signed_distance', 'rr_signed_buffer', 'rr_signed_copy_to_host')
+           'rr_signed_distance', 'rr_signed_buffer', 'rr_signed_copy_to_host',
+           'rr_signed_gradient', 'rr_signed_gradient_buffer', 'rr_signed_gradient_copy_to_host')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
@@ -81,6 +82,9 @@ PC_MAX_POSTURES = 32
 # {signed distance, bound, a xyz, b xyz, n xyz, +0.0} of the pair at the first minimum, id [4] i32 {status, pair index, body A, body B}, signed [Q] f32,
 # status [Q] i32 {byte 0 status 0..5, byte 1 GJK iterations, byte 2 expansion trips}; points [N, Q, 12] f32: every pair's record, present-state queries only
 SD_FIELDS = ('deepest', 'id', 'signed', 'status', 'points')
+# buffers of rr_signed_gradient_buffer (the RR_SG_* enum), rows of 12 f32: gradient [N, K', 12] {d s*/dq_0..10, +0.0} of the row's deepest pair,
+# cost [N, K', 12] {dC/dq_0..10, C} of the hinge cost over all pairs, pair_gradient [N, Q, 12] {d s_j/dq_0..10, +0.0}: present-state queries only
+SG_FIELDS = ('gradient', 'cost', 'pair_gradient')
 SLOT_LIVE, MAX_SLOTS = -1, 64           # RR_SLOT_LIVE: the running envs as a slot number of rr_copy_envs; RR_MAX_SLOTS
 # `parts` of rr_write_state (the RR_W_* bits): the column groups of the 61-float state row that are written, a reset in front of them,
 # the fresh-start clean-up of rr_set_state behind them
@@ -229,6 +233,9 @@ def load_library():
     L.rr_signed_distance.argtypes = [vp, vp, i32, i32]
     L.rr_signed_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rr_signed_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
+    L.rr_signed_gradient.argtypes = [vp, vp, i32, i32, C.c_float]
+    L.rr_signed_gradient_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rr_signed_gradient_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]

@@ -1056,6 +1056,10 @@ class BatchedREALRobotEnv:
             ptr, on_dev, keep = self._state_arg(postures, 'postures', ('float32',), (self.N, K, nat.N_JOINTS))
             nat.check(self.L.rr_signed_distance(self.h, ptr, K, on_dev))
             del keep
+        return self._signed_columns(present, K, host)
+
+    def _signed_columns(self, present, K, host):
+        """The dict of `signed_distance` over the RR_SD_* buffers as the last query (K' = K rows per env) left them."""
         deep, ids, dist, st = (self.signed_buffer(i, host=host) for i in range(4))
         if isinstance(deep, np.ndarray):
             cut = lambda lo: deep[:, :, lo:lo + 3]
@@ -1083,6 +1087,72 @@ class BatchedREALRobotEnv:
             Q = pts.shape[1]
             cutq = lambda lo: nat.DeviceBuffer(pts.ptr + 4 * lo, (self.N, Q, 3), pts.typestr, pts._owner, strides=(Q * 48, 48, 4))
         out.update(pair_bound=col(pts, 1), pair_point_a=cutq(2), pair_point_b=cutq(5), pair_normal=cutq(8))
+        return out
+
+    # ------------------------------------------------------------------ joint gradients of the signed distance
+    def signed_gradient_buffer(self, name, host=False):
+        """One buffer of `signed_distance_gradient` as the LAST call left it (all zero, and K' = 0, before the first), by name
+        (`_native.SG_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait.  Shapes: gradient
+        [N, K', 12] float32 {d s*/dq_0..10, +0.0}, cost [N, K', 12] float32 {dC/dq_0..10, C}, pair_gradient [N, Q, 12] float32
+        {d s_j/dq_0..10, +0.0} (K' = 1 after a present-state query; `pair_gradient` is written by present-state queries only)."""
+        which = nat.SG_FIELDS.index(name) if isinstance(name, str) and name in nat.SG_FIELDS else name
+        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.SG_FIELDS):
+            raise ValueError("unknown signed-gradient buffer %r (known: %s)" % (name, ', '.join(nat.SG_FIELDS)))
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(self.L.rr_signed_gradient_buffer(self.h, int(which), C.byref(p), C.byref(n)))
+        shape = (self.N, n.value // (48 * self.N), 12)
+        if host:
+            out = np.empty(shape, np.float32)
+            nat.check(self.L.rr_signed_gradient_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
+            return out
+        return nat.DeviceBuffer(p.value, shape, np.dtype(np.float32).str, self)
+
+    @staticmethod
+    def _gradient_views(buf, present):
+        """(the eleven joint columns [..., 11], column 11 [...]) of a [N, R, 12] buffer of rows -- numpy views or strided device views
+        (zero copy); present: without the K' = 1 axis."""
+        if isinstance(buf, np.ndarray):
+            g, last = buf[:, :, :11], buf[:, :, 11]
+            return (g[:, 0], last[:, 0]) if present else (g, last)
+        N, R = buf.shape[:2]
+        if present:
+            return (nat.DeviceBuffer(buf.ptr, (N, 11), buf.typestr, buf._owner, strides=(R * 48, 4)),
+                    nat.DeviceBuffer(buf.ptr + 44, (N,), buf.typestr, buf._owner, strides=(R * 48,)))
+        return (nat.DeviceBuffer(buf.ptr, (N, R, 11), buf.typestr, buf._owner, strides=(R * 48, 48, 4)),
+                nat.DeviceBuffer(buf.ptr + 44, (N, R), buf.typestr, buf._owner, strides=(R * 48, 48)))
+
+    def signed_distance_gradient(self, postures=None, margin=0.0, host=False):
+        """`signed_distance` plus its derivatives over the eleven joints (rr_signed_gradient), for trajectory optimisers: one
+        launch on the library's stream at the present state (postures None) or at K candidate postures per env, the objects where
+        they are now; the simulation is not touched.  The arguments are `signed_distance`'s; margin (m, finite, >= 0; with a cull in
+        force at most the table's max_distance) is the distance below which a pair costs.  Returns `signed_distance`'s dict (the
+        same bytes in the same buffers) and, with a leading [N, K] (postures) or [N] (present state),
+          gradient float32 [..., 11] -- d(distance)/dq of the DEEPEST pair: n . (a_k x (a - p_k)) over the joints that move shape a's
+              body minus the same on b over those that move b's; +0.0 for a joint that moves neither and for a touching pair
+              (status 4); at a kink of the distance (face against face) the gradient of the active feature pair;
+          cost float32 [...] -- C = 1/2 sum_j max(margin - pair_distance_j, 0)^2 over all pairs, summed on the device in a fixed order;
+          cost_gradient float32 [..., 11] -- dC/dq = -sum_j max(margin - pair_distance_j, 0) d(pair_distance_j)/dq;
+        and for the present state pair_gradient float32 [N, Q, 11], every pair's gradient.  The columns are the joints of the
+        state's q[11]: `gradient @ _native.Q_FROM_CMD` is the gradient over the nine command entries (the coupled finger joints
+        follow their drivers), and likewise for cost_gradient and pair_gradient.  Device views (zero copy, strided, DLPack; valid
+        after later work on the library's stream or `sync()`; they hold what the last call computed), or with host=True numpy views
+        of host copies after a sync."""
+        present = postures is None
+        K = 1 if present else self._posture_arg(postures, self.N)
+        if len(self.distance_pairs()[0]) == 0:
+            raise ValueError("signed_distance_gradient: the pair table is empty (set_distance_pairs)")
+        if present:
+            nat.check(self.L.rr_signed_gradient(self.h, None, 0, 0, float(margin)))
+        else:
+            ptr, on_dev, keep = self._state_arg(postures, 'postures', ('float32',), (self.N, K, nat.N_JOINTS))
+            nat.check(self.L.rr_signed_gradient(self.h, ptr, K, on_dev, float(margin)))
+            del keep
+        out = self._signed_columns(present, K, host)
+        grad, cost = (self.signed_gradient_buffer(i, host=host) for i in range(2))
+        out['gradient'] = self._gradient_views(grad, present)[0]
+        out['cost_gradient'], out['cost'] = self._gradient_views(cost, present)
+        if present:
+            out['pair_gradient'] = self._gradient_views(self.signed_gradient_buffer('pair_gradient', host=host), False)[0]
         return out
 
     def body_row_names(self):

@@ -471,6 +471,7 @@ __device__ __forceinline__ void dispatch_order_class(int x, int N, int ntiles, i
 #include "rr_dist.inc"    // k_closest_points: distance and closest points of pairs of collision hulls of the whole batch at the present state (rr_closest_points)
 #include "rr_posture.inc"    // k_posture_clearance: every pair's distance and the nearest pair's record at K candidate joint postures per env (rr_posture_clearance)
 #include "rr_signed.inc"    // k_signed_distance: every pair's signed distance -- minus the penetration depth where the hulls overlap -- and the deepest pair's record, at the present state or at K postures (rr_signed_distance)
-#include "rr_plan.inc"    // plan_step: the placement and launch shapes of one step from one reading of the lagged list lengths (host only, no HIP type)
+#include "rr_grad.inc"    // k_signed_gradient: k_signed_distance plus the joint gradients of the deepest pair's signed distance and of a hinge cost over all pairs (rr_signed_gradient)
+#include "rr_plan.inc"   // plan_step: the placement and launch shapes of one step from one reading of the lagged list lengths (host only, no HIP type)
 #include "rr_mem.inc"    // MemOwner: the one owner of the handle's device and pinned memory, all-or-nothing group allocation (host only, no HIP type)
 #include "rr_host.inc"    // host side: model blob, rr_env, the C ABI

@@ -152,6 +152,10 @@ struct rr_env : ModelTables {
     // (RR_SD_POINTS for RR_DIST_MAX), once; a host caller's postures go through pc_stage
     void *sd_buf[RR_SD_COUNT] = {};
     int sd_k = 0;                  // rows per env of the last query (1: the present state): 0 before the first
+    // joint gradients of the signed distance (rr_signed_gradient): the three RR_SG_* buffers, allocated together on first use for
+    // RR_PC_MAX_POSTURES rows (RR_SG_PAIR_GRADIENT for RR_DIST_MAX pairs), once; the call writes the RR_SD_* buffers too
+    void *sg_buf[RR_SG_COUNT] = {};
+    int sg_k = 0;                  // rows per env of the last gradient query: 0 before the first
     MemOwner mem;                  // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
     bool created = false;
     bool timing = false;
@@ -1858,6 +1862,86 @@ int rr_signed_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
     HIPCHK(hipSetDevice(e->cfg.device));
     if (bytes == 0) return RR_OK;
     HIPCHK(hipMemcpyAsync(dst, e->sd_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return RR_OK;
+}
+
+// ---- joint gradients of the signed distance (rr_grad.inc) ------------------------------------------------------------------------------
+// The three buffers of rr_signed_gradient: allocated on first use -- by the query or by rr_signed_gradient_buffer /
+// rr_signed_gradient_copy_to_host -- in one list, zero-filled, for RR_PC_MAX_POSTURES rows (the pair rows of the present state for
+// RR_DIST_MAX pairs).  The layout in force is that of the last gradient query's K' (0 before the first) and the Q of the pair table.
+static size_t sg_bytes(const rr_env *e, int which, int K, int Q) {
+    return (size_t)e->P.N * (which == RR_SG_PAIR_GRADIENT ? Q : K) * 48;
+}
+static int ensure_signed_gradient(rr_env *e, const char *who) {
+    if (e->sg_buf[0]) return RR_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    void *b[RR_SG_COUNT] = {};
+    MemPart parts[RR_SG_COUNT];
+    for (int i = 0; i < RR_SG_COUNT; i++) parts[i] = mem_part(&b[i], sg_bytes(e, i, RR_PC_MAX_POSTURES, RR_DIST_MAX));
+    RRCHK(mem_get(e, parts, RR_SG_COUNT, (std::string(who) + ": allocating the signed-gradient buffers").c_str()));
+    for (int i = 0; i < RR_SG_COUNT; i++) e->sg_buf[i] = b[i];
+    return RR_OK;
+}
+
+// rr_signed_distance with the joint gradients: the same launch shape on the main stream, the same reads, and the five RR_SD_* buffers
+// written as that call writes them; the three RR_SG_* buffers (RR_SG_PAIR_GRADIENT at the present state only) in addition, and
+// nothing else.
+int rr_signed_gradient(rr_env *e, const float *postures, int32_t n_postures, int32_t on_device, float margin) {
+    if (!e) return fail(RR_EINVAL, "rr_signed_gradient: null env");
+    if (!postures && n_postures != 0)
+        return fail(RR_EINVAL, "rr_signed_gradient: null postures with n_postures " + std::to_string(n_postures) + " (the present state is NULL with 0)");
+    if (postures && (n_postures < 1 || n_postures > RR_PC_MAX_POSTURES))
+        return fail(RR_EINVAL, "rr_signed_gradient: n_postures " + std::to_string(n_postures) + " is not in [1, RR_PC_MAX_POSTURES = " +
+                                   std::to_string(RR_PC_MAX_POSTURES) + "]");
+    if (!(margin >= 0.0f) || std::isinf(margin)) return fail(RR_EINVAL, "rr_signed_gradient: margin " + std::to_string(margin) + " is not a finite number >= 0");
+    const int Q = e->dist_n, N = e->P.N, K = postures ? n_postures : 1;
+    if (Q == 0) return fail(RR_EINVAL, "rr_signed_gradient: the pair table is empty (rr_set_distance_pairs)");
+    const float maxd = e->dist_tab.max_distance;
+    if (maxd > 0.0f && maxd < INFINITY && margin > maxd)
+        return fail(RR_EINVAL, "rr_signed_gradient: margin " + std::to_string(margin) + " is above the pair table's max_distance " + std::to_string(maxd) +
+                                   " (a culled pair's sphere gap would enter the hinge as a distance)");
+    RRCHK(ensure_dist(e, "rr_signed_gradient"));          // (the device copy of the pair table)
+    RRCHK(ensure_signed(e, "rr_signed_gradient"));
+    RRCHK(ensure_signed_gradient(e, "rr_signed_gradient"));
+    const bool stage = postures && !on_device;
+    if (stage && !e->pc_stage)
+        RRCHK(mem_get(e, {mem_part(&e->pc_stage, (size_t)N * RR_PC_MAX_POSTURES * 44, false)}, "rr_signed_gradient: allocating the staging buffer"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const float *src = postures;
+    if (stage) {
+        HIPCHK(hipMemcpyAsync(e->pc_stage, postures, (size_t)N * K * 44, hipMemcpyHostToDevice, e->stream));
+        src = e->pc_stage;
+    }
+    hipLaunchKernelGGL(k_signed_gradient, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
+                       (float4 *)e->sd_buf[RR_SD_DEEPEST], (int4 *)e->sd_buf[RR_SD_ID], (float *)e->sd_buf[RR_SD_SIGNED], (int *)e->sd_buf[RR_SD_STATUS],
+                       postures ? (float4 *)nullptr : (float4 *)e->sd_buf[RR_SD_POINTS], margin,
+                       (float *)e->sg_buf[RR_SG_GRADIENT], (float *)e->sg_buf[RR_SG_COST], postures ? (float *)nullptr : (float *)e->sg_buf[RR_SG_PAIR_GRADIENT]);
+    HIPCHK(hipGetLastError());
+    e->sd_k = K;
+    e->sg_k = K;
+    if (stage) HIPCHK(hipStreamSynchronize(e->stream));        // the argument is host memory
+    return RR_OK;
+}
+
+int rr_signed_gradient_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_signed_gradient_buffer: null env");
+    if (which < 0 || which >= RR_SG_COUNT) return fail(RR_EINVAL, "rr_signed_gradient_buffer: buffer " + std::to_string(which) + " is not in [0, RR_SG_COUNT)");
+    RRCHK(ensure_signed_gradient(e, "rr_signed_gradient_buffer"));
+    if (dev_ptr) *dev_ptr = e->sg_buf[which];
+    if (bytes) *bytes = sg_bytes(e, which, e->sg_k, e->dist_n);
+    return RR_OK;
+}
+
+int rr_signed_gradient_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_signed_gradient_copy_to_host: null env");
+    if (!dst) return fail(RR_EINVAL, "rr_signed_gradient_copy_to_host: null destination");
+    if (which < 0 || which >= RR_SG_COUNT) return fail(RR_EINVAL, "rr_signed_gradient_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_SG_COUNT)");
+    if (bytes != sg_bytes(e, which, e->sg_k, e->dist_n)) return fail(RR_EINVAL, "rr_signed_gradient_copy_to_host: size mismatch");
+    RRCHK(ensure_signed_gradient(e, "rr_signed_gradient_copy_to_host"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    if (bytes == 0) return RR_OK;
+    HIPCHK(hipMemcpyAsync(dst, e->sg_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return RR_OK;
 }
