@@ -44,7 +44,9 @@ extern "C" {
                               rr_signed_copy_to_host (signed distance of the pair table: penetration depth, direction and witness points
                               where hulls overlap, at the present state or at candidate postures); rr_signed_gradient,
                               rr_signed_gradient_buffer, rr_signed_gradient_copy_to_host (that query plus the joint gradients of the
-                              deepest pair's signed distance and of a hinge collision cost, reduced on the device) */
+                              deepest pair's signed distance and of a hinge collision cost, reduced on the device);
+                              rr_swept_clearance, rr_sweep_reach, rr_sweep_buffer, rr_sweep_copy_to_host (first contact of the pair
+                              table along joint-space segments, by conservative advancement) */
 
 enum {
     RR_OK = 0,
@@ -885,6 +887,72 @@ int rr_signed_gradient(rr_env *env, const float *postures /* f32 [N][K][11] or N
 int rr_signed_gradient_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
 /* Synchronising copy of a whole RR_SG_* buffer (its `bytes`) to host memory. */
 int rr_signed_gradient_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
+
+/* ---- Swept clearance along joint-space segments on the device (additive in ABI 7) ------------------------------------------------------
+ * The queries above answer a question about a POSTURE; a planner's unit of work is an EDGE: "is the motion from q0 to q1 free, and
+ * if not, where does it first touch and what?"  Sampling the edge proves nothing -- an arm passes through the shelf lip between two
+ * free samples -- and costs 32 x Q pair searches whether the edge is near anything or not.  rr_swept_clearance decides K segments
+ * per env of the whole batch by CONSERVATIVE ADVANCEMENT in one launch on the library's stream: it needs only the proved lower bound
+ * of a pair's distance (the `lower` column of RR_DIST_POINTS) and a bound on how fast that distance can change, which for eleven
+ * revolute joints is a constant table.  The buffers are NOT fields of rr_get_buffer and not buffers of the queries above: they have
+ * this enum and rr_sweep_buffer. */
+enum {
+    RR_SW_STOP = 0,   /* f32 [N, K, 12] {fraction, q_stop[0..10]}: q_stop is the posture the kernel evaluated last */
+    RR_SW_HIT = 1,    /* f32 [N, K, 12] the RR_DIST_POINTS row of the reported pair at q_stop; all +0.0 at status 0 */
+    RR_SW_ID = 2,     /* i32 [N, K, 4]  {status, reported pair (-1 at status 0), steps, pair evaluations} */
+    RR_SW_FREE = 3,   /* f32 [N, K, Q]  min(free_j, 1): every pair's proved free horizon at the end */
+    RR_SW_COUNT = 4
+};
+#define RR_SW_MAX_STEPS 64
+/* Input.  segments is f32 [N][K][2][11], C order, K = n_segments in [1, RR_PC_MAX_POSTURES]: the start posture q0 and the end
+ * posture q1 of K independent segments per env, the eleven joints in the order of rr_posture_clearance.  The motion is
+ * q(t) = q0 + t (q1 - q0), t in [0, 1]; the objects stay at env e's PRESENT pose; the pair table and the cull are those of
+ * rr_set_distance_pairs.  on_device means what it means to rr_posture_clearance: device memory read in place on the library's stream
+ * under that call's STREAM CONTRACT, without waiting, or host memory staged through a buffer of the handle's own (N * 32 * 22 floats,
+ * allocated by the first such call), and the call waits.  Values are not validated.
+ * The reach table.  R[k][s], built on the host in float64 when the handle is made and rounded UP to float32: for a robot shape s on
+ * body b with joint k an ancestor-or-self of b, |sphere centre of s| + sphere radius of s + the sum of |body_jpos[m]| over the
+ * bodies m on the chain from b up to, but not including, k; otherwise 0.  It bounds the distance of every point of s from joint k's
+ * origin at any posture.  rr_sweep_reach returns it.
+ * The pair bound.  B_j = sum of |q1_k - q0_k| (R[k][a] + R[k][b]) over the joints k that are an ancestor-or-self of the body of
+ * exactly one of the two shapes (a joint above both moves them rigidly and changes no distance; statics and objects have no
+ * joints): the distance of pair j is B_j-Lipschitz in t.  Summed in float32 over ascending k and scaled by 1 + 2^-20.
+ * The advancement.  One common t per segment, from 0; every pair carries a horizon free_j, from 0.  A step evaluates the pairs with
+ * free_j <= t at q(t) = fma(t, q1 - q0, q0) with the device text of rr_closest_points and rr_posture_clearance.  With
+ * g = lower_j - safety: unless g > tolerance the pair HITS (so does a NaN); otherwise free_j = t + g / B_j, or +inf when B_j == 0.
+ * If a pair hits, the row stops at this t and the lowest pair index among the hits is reported.  Otherwise t = min_j free_j (the
+ * first minimum: the lowest index among equals); at or beyond 1 the row is free.  Every step advances t by more than
+ * tolerance / max B.  At most RR_SW_MAX_STEPS postures are evaluated whatever the data, non-finite input included: a non-finite row
+ * leaves the loop within the cap, its outputs unspecified, with status in {0, 1, 3}.
+ * Status.  0: free, fraction = 1.0 exactly.  1: hit, fraction = the t of the stop; 0 for a segment that starts within
+ * safety + tolerance.  3: step cap, fraction = the t reached: a proved free prefix, and the caller continues from q_stop; RR_SW_HIT
+ * then holds the pair with the smallest horizon (the lowest index among equals), evaluated at q_stop.  `steps` counts the postures
+ * evaluated, `pair evaluations` the pair searches of those steps (the one search that writes RR_SW_HIT of a stopped row is not
+ * counted).
+ * Guarantees.  For every pair j and every t < min(free_j, 1) the distance of pair j along the motion exceeds safety; for every
+ * t < fraction every pair's distance exceeds safety.  A pair that is never evaluated again keeps the horizon of its last evaluation;
+ * a pair that hits keeps the horizon it had.  (A culled pair's lower bound is its sphere gap, which is a lower bound too.)
+ * No effect on the simulation: the call reads what rr_posture_clearance reads, and the reach table, and writes these four buffers
+ * only; the next step stays prepared.  No atomics and a fixed reduction order: row (e, k) is a function of (env e's objects, segment
+ * (e, k), the tables, safety, tolerance) alone.  No value of the tensor or the state forms an address.
+ * Errors: RR_EINVAL with nothing allocated and nothing changed, the message naming the cause, for a null env, null segments,
+ * n_segments outside [1, RR_PC_MAX_POSTURES], Q == 0, safety < 0 or NaN or infinite, tolerance < 1e-6 or NaN or infinite, and a cull
+ * in force (0 < max_distance < inf) with max_distance < safety + tolerance: a culled pair's sphere gap could otherwise fake a hit.
+ * Buffers.  All four are allocated on first use -- by this call, or by rr_sweep_buffer / rr_sweep_copy_to_host --, all or nothing
+ * through the handle's memory owner, zero-filled, sized once for RR_PC_MAX_POSTURES x RR_DIST_MAX, and valid until rr_destroy: no
+ * pointer ever changes.  The layout is compact for the K of the last query (0 before the first) and the Q in force, and `bytes`
+ * reports that.  After rr_set_distance_pairs the buffers hold unspecified data until the next query.  STREAM CONTRACT for readers as
+ * for the sibling views.
+ * Out of scope: objects that move during the sweep; every pair's first hit (the earliest alone is reported); gradients of the hit
+ * time; polylines as a type (stack the waypoints into segments); Cartesian segments; a switch of the vector env; any use by the step. */
+int rr_swept_clearance(rr_env *env, const float *segments /* f32 [N][K][2][11] */, int32_t n_segments, int32_t on_device, float safety, float tolerance);
+/* The reach table R[k][s] of the handle's model, f32 [11][n_shapes] (n_shapes: the model's collision shapes, the index space of
+ * rr_set_distance_pairs), to host memory.  Null env or null out: RR_EINVAL. */
+int rr_sweep_reach(rr_env *env, float *out /* f32 [11][n_shapes] */);
+/* Zero-copy device pointer + size in bytes of an RR_SW_* buffer (read-only for the caller); which outside [0, RR_SW_COUNT): RR_EINVAL. */
+int rr_sweep_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
+/* Synchronising copy of a whole RR_SW_* buffer (its `bytes`) to host memory. */
+int rr_sweep_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
 
 /* Batched damped-least-squares inverse kinematics for link 7 (gripper `base`), seeded with each env's current joints.
  * Replaces pybullet.calculateInverseKinematics(0, 7, pos, orn, maxNumIterations=1000, residualThreshold=0.001) in

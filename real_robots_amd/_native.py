@@ -44,7 +44,8 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_set_distance_pairs', 'rr_get_distance_pairs', 'rr_closest_points', 'rr_distance_buffer', 'rr_distance_copy_to_host',
            'rr_posture_clearance', 'rr_posture_buffer', 'rr_posture_copy_to_host',
            'rr_signed_distance', 'rr_signed_buffer', 'rr_signed_copy_to_host',
-           'rr_signed_gradient', 'rr_signed_gradient_buffer', 'rr_signed_gradient_copy_to_host')
+           'rr_signed_gradient', 'rr_signed_gradient_buffer', 'rr_signed_gradient_copy_to_host',
+           'rr_swept_clearance', 'rr_sweep_reach', 'rr_sweep_buffer', 'rr_sweep_copy_to_host')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
@@ -85,6 +86,11 @@ SD_FIELDS = ('deepest', 'id', 'signed', 'status', 'points')
 # buffers of rr_signed_gradient_buffer (the RR_SG_* enum), rows of 12 f32: gradient [N, K', 12] {d s*/dq_0..10, +0.0} of the row's deepest pair,
 # cost [N, K', 12] {dC/dq_0..10, C} of the hinge cost over all pairs, pair_gradient [N, Q, 12] {d s_j/dq_0..10, +0.0}: present-state queries only
 SG_FIELDS = ('gradient', 'cost', 'pair_gradient')
+# buffers of rr_sweep_buffer (the RR_SW_* enum), per env and segment: stop [12] f32 {fraction, q_stop[11]}, hit [12] f32 (the `points` row of the
+# reported pair at q_stop), id [4] i32 {status, pair, steps, pair evaluations}, free [Q] f32 (every pair's free horizon, at most 1), for the K
+# segments of the last rr_swept_clearance and the Q pairs in force
+SW_FIELDS = ('stop', 'hit', 'id', 'free')
+SW_MAX_STEPS = 64
 SLOT_LIVE, MAX_SLOTS = -1, 64           # RR_SLOT_LIVE: the running envs as a slot number of rr_copy_envs; RR_MAX_SLOTS
 # `parts` of rr_write_state (the RR_W_* bits): the column groups of the 61-float state row that are written, a reset in front of them,
 # the fresh-start clean-up of rr_set_state behind them
@@ -236,6 +242,10 @@ def load_library():
     L.rr_signed_gradient.argtypes = [vp, vp, i32, i32, C.c_float]
     L.rr_signed_gradient_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rr_signed_gradient_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
+    L.rr_swept_clearance.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float]
+    L.rr_sweep_reach.argtypes = [vp, vp]
+    L.rr_sweep_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rr_sweep_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]

@@ -1155,6 +1155,89 @@ class BatchedREALRobotEnv:
             out['pair_gradient'] = self._gradient_views(self.signed_gradient_buffer('pair_gradient', host=host), False)[0]
         return out
 
+    # ------------------------------------------------------------------ swept clearance along joint-space segments
+    @staticmethod
+    def _segment_arg(segments, N):
+        """The `segments` argument of `swept_clearance` for a handle of N envs -> K.  It is float32 [N, K, 2, 11], C-contiguous, K in
+        [1, 32]: a numpy array, a CUDA torch tensor or a `__cuda_array_interface__` object; every violation is a ValueError raised
+        here, before the native call."""
+        what = "segments must be a C-contiguous float32 array of shape (%d, K, 2, 11), 1 <= K <= %d" % (N, nat.PC_MAX_POSTURES)
+        a = segments
+        if hasattr(a, 'is_cuda') and hasattr(a, 'data_ptr'):        # a torch tensor
+            dt, shape, dense = str(a.dtype).replace('torch.', ''), tuple(a.shape), bool(a.is_contiguous())
+        elif getattr(a, '__cuda_array_interface__', None) is not None:
+            cai = a.__cuda_array_interface__
+            dt, shape = np.dtype(cai['typestr']).name, tuple(cai['shape'])
+            dense = cai.get('strides') in (None, tuple(int(np.prod(shape[i + 1:])) * 4 for i in range(len(shape))))
+        else:
+            try:
+                a = np.asarray(a)
+            except (ValueError, TypeError):
+                raise ValueError("%s, not %r" % (what, type(segments).__name__))
+            dt, shape, dense = a.dtype.name, a.shape, bool(a.flags.c_contiguous)
+        if dt != 'float32' or len(shape) != 4 or shape[0] != N or shape[2] != 2 or shape[3] != nat.N_JOINTS or not 1 <= shape[1] <= nat.PC_MAX_POSTURES or not dense:
+            raise ValueError("%s, not %s %s%s" % (what, dt, tuple(shape), '' if dense else ' (not contiguous)'))
+        return int(shape[1])
+
+    def sweep_buffer(self, name, host=False):
+        """One buffer of `swept_clearance` as the LAST call left it (all zero, and K = 0, before the first), by name
+        (`_native.SW_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait.  Shapes: stop
+        [N, K, 12] float32, hit [N, K, 12] float32, id [N, K, 4] int32, free [N, K, Q] float32."""
+        which = nat.SW_FIELDS.index(name) if isinstance(name, str) and name in nat.SW_FIELDS else name
+        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.SW_FIELDS):
+            raise ValueError("unknown sweep buffer %r (known: %s)" % (name, ', '.join(nat.SW_FIELDS)))
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(self.L.rr_sweep_buffer(self.h, int(which), C.byref(p), C.byref(n)))
+        Q = len(self.distance_pairs()[0])
+        cols, dt = ((12, np.float32), (12, np.float32), (4, np.int32), (Q, np.float32))[int(which)]
+        shape = (self.N, n.value // (4 * cols * self.N) if cols else 0, cols)
+        if host:
+            out = np.empty(shape, dt)
+            nat.check(self.L.rr_sweep_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
+            return out
+        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
+
+    def sweep_reach(self):
+        """The reach table of `swept_clearance` (rr_sweep_reach), float32 [11, n_shapes]: how far a point of collision shape s can be
+        from joint k's origin at any posture, rounded up; 0 where joint k does not move shape s."""
+        out = np.zeros((nat.N_JOINTS, len(self.collision_shapes())), np.float32)
+        nat.check(self.L.rr_sweep_reach(self.h, out.ctypes.data))
+        return out
+
+    def swept_clearance(self, segments, safety=0.0, tolerance=1e-3, host=False):
+        """Is the joint-space motion q(t) = q0 + t (q1 - q0), t in [0, 1], free of the pairs of `set_distance_pairs` by `safety`, and if
+        not, where does it first touch and what (rr_swept_clearance)?  One launch on the library's stream decides K segments per env
+        by conservative advancement -- a proof, not a sampling: it steps t by (proved lower bound of the distance - safety) / (a bound
+        of the distance's rate from the reach table) and re-evaluates only the pairs whose proved horizon has run out.  The objects
+        stay where they are now; the simulation is not touched.  segments: float32 [N, K, 2, 11], 1 <= K <= 32, C-contiguous, start
+        and end posture over the eleven independent joints -- a numpy array (staged, synchronous) or a CUDA torch tensor /
+        `__cuda_array_interface__` object, read in place on the library's stream; safety (m, finite, >= 0); tolerance (m, finite,
+        >= 1e-6): a pair whose lower bound is within safety + tolerance hits.  Returns, as [N, K] columns,
+          fraction float32 -- 1.0 for a free segment, else the t of the stop: every pair's distance exceeds safety for t < fraction;
+          q_stop float32 [N, K, 11] -- the posture evaluated last;
+          status int32 -- 0 free, 1 hit, 3 step cap (a proved free prefix: continue from q_stop); pair int32 -- the reported pair
+              (the lowest index among the hits; at status 3 the pair with the smallest horizon; -1 at status 0);
+          steps, evaluations int32 -- postures evaluated (at most 64) and pair searches;
+          distance, lower, point_a, point_b ([N, K, 3]), normal ([N, K, 3]) float32 -- the `closest_points` record of the reported
+              pair at q_stop (all +0.0 at status 0);
+          pair_free_until float32 [N, K, Q] -- for every pair the t up to which it is proved further than safety (at most 1).
+        Device views (zero copy, strided, DLPack; valid after later work on the library's stream or `sync()`; they hold what the last
+        call computed), or with host=True numpy views of host copies after a sync."""
+        K = self._segment_arg(segments, self.N)
+        if len(self.distance_pairs()[0]) == 0:
+            raise ValueError("swept_clearance: the pair table is empty (set_distance_pairs)")
+        ptr, on_dev, keep = self._state_arg(segments, 'segments', ('float32',), (self.N, K, 2, nat.N_JOINTS))
+        nat.check(self.L.rr_swept_clearance(self.h, ptr, K, on_dev, float(safety), float(tolerance)))
+        del keep
+        stop, hit, ids, free = (self.sweep_buffer(i, host=host) for i in range(len(nat.SW_FIELDS)))
+        if isinstance(hit, np.ndarray):
+            cut = lambda buf, lo, n: buf[:, :, lo:lo + n]
+        else:
+            cut = lambda buf, lo, n: nat.DeviceBuffer(buf.ptr + 4 * lo, (self.N, K, n), buf.typestr, buf._owner, strides=(K * 48, 48, 4))
+        col = self.ray_column
+        return dict(fraction=col(stop, 0), q_stop=cut(stop, 1, 11), status=col(ids, 0), pair=col(ids, 1), steps=col(ids, 2), evaluations=col(ids, 3),
+                    distance=col(hit, 0), lower=col(hit, 1), point_a=cut(hit, 2, 3), point_b=cut(hit, 5, 3), normal=cut(hit, 8, 3), pair_free_until=free)
+
     def body_row_names(self):
         """The bodies of the rows of body_force / body_partners: the 17 URDF links, then this handle's objects (the rows of the
         objects it does not have, up to 20, stay zero)."""

@@ -470,6 +470,7 @@ __device__ __forceinline__ void dispatch_order_class(int x, int N, int ntiles, i
 #include "rr_ray.inc"    // k_ray_cast: segments of the whole batch against the collision hulls at the present state (rr_ray_cast)
 #include "rr_dist.inc"    // k_closest_points: distance and closest points of pairs of collision hulls of the whole batch at the present state (rr_closest_points)
 #include "rr_posture.inc"    // k_posture_clearance: every pair's distance and the nearest pair's record at K candidate joint postures per env (rr_posture_clearance)
+#include "rr_sweep.inc"    // k_swept_clearance: first contact of the pair table along K joint-space segments per env, by conservative advancement (rr_swept_clearance)
 #include "rr_signed.inc"    // k_signed_distance: every pair's signed distance -- minus the penetration depth where the hulls overlap -- and the deepest pair's record, at the present state or at K postures (rr_signed_distance)
 #include "rr_grad.inc"    // k_signed_gradient: k_signed_distance plus the joint gradients of the deepest pair's signed distance and of a hinge cost over all pairs (rr_signed_gradient)
 #include "rr_plan.inc"   // plan_step: the placement and launch shapes of one step from one reading of the lagged list lengths (host only, no HIP type)

@@ -95,6 +95,8 @@ struct ModelTables {
     // per-env actuators (rr_set_env_actuators): the host copy every upload of D.env_act is made from, and what rr_get_env_actuators returns
     std::vector<float> act;        // [N][NB][4] {kp, kd, max_force, joint damping}
     float act_default[NB][4] = {}; // the handle's row of every joint: P.kp, P.kd, the motor force of rr_config, the blob's body_damping
+    // swept clearance (rr_swept_clearance): R[k][s], how far a point of shape s can be from joint k's origin; 0 where k does not move s
+    SweepReach sweep_reach = {};
 };
 
 // Everything rr_create needs from the model: the tables above and what is only uploaded.  The pointers point into the blob.
@@ -156,6 +158,12 @@ struct rr_env : ModelTables {
     // RR_PC_MAX_POSTURES rows (RR_SG_PAIR_GRADIENT for RR_DIST_MAX pairs), once; the call writes the RR_SD_* buffers too
     void *sg_buf[RR_SG_COUNT] = {};
     int sg_k = 0;                  // rows per env of the last gradient query: 0 before the first
+    // swept clearance (rr_swept_clearance): the four RR_SW_* buffers and the device copy of the reach table, allocated together on
+    // first use for RR_PC_MAX_POSTURES x RR_DIST_MAX, once; the host path's staging buffer is a part of its own, got by the first host-path call
+    void *sw_buf[RR_SW_COUNT] = {};
+    int sw_k = 0;                  // segments per env of the last query: 0 before the first
+    SweepReach *sw_reach_dev = nullptr;
+    float *sw_stage = nullptr;
     MemOwner mem;                  // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
     bool created = false;
     bool timing = false;
@@ -461,6 +469,20 @@ static int parse_model(const rr_config &cfg, const Blob &b, const Settings &set,
     P.npairs = np;
     M.n_shapes = ns;
     if (ns > CSHAPES) return fail(RR_EMODEL, "rr_create: more collision shapes than k_collide stages in LDS");
+    // the reach table of rr_swept_clearance, in float64 and rounded up: |sphere centre| + radius in the shape's body b, plus the joint
+    // offsets |jpos[m]| of the bodies m from b up to the child of k on b's chain
+    for (int s = 0; s < ns; s++) {
+        if (S.otype[s] != 1 || S.oidx[s] < 0 || S.oidx[s] >= NB) continue;
+        const double c[3] = {S.sphere[s][0], S.sphere[s][1], S.sphere[s][2]};
+        double r = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]) + (double)S.sphere[s][3];
+        for (int k = S.oidx[s]; k >= 0; k = PARENT_HOST[k]) {
+            float f = (float)r;
+            if ((double)f < r) f = std::nextafterf(f, INFINITY);
+            M.sweep_reach.r[k][s] = f;
+            const double j[3] = {B.jpos[k][0], B.jpos[k][1], B.jpos[k][2]};
+            r += std::sqrt(j[0] * j[0] + j[1] * j[1] + j[2] * j[2]);
+        }
+    }
     for (int k = 0; k < np; k++) {
         const int sa = S.pair_a[k], sb = S.pair_b[k];
         S.pair_meta[k][0] = S.otype[sa] == 0 ? -1 : (S.otype[sa] == 1 ? S.oidx[sa] : 16 + S.oidx[sa]);
@@ -1942,6 +1964,102 @@ int rr_signed_gradient_copy_to_host(rr_env *e, int32_t which, void *dst, size_t 
     HIPCHK(hipSetDevice(e->cfg.device));
     if (bytes == 0) return RR_OK;
     HIPCHK(hipMemcpyAsync(dst, e->sg_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return RR_OK;
+}
+
+// ---- swept clearance along joint-space segments (rr_sweep.inc) -------------------------------------------------------------------------
+// The four buffers of rr_swept_clearance and the device copy of the reach table: allocated on first use -- by the query or by
+// rr_sweep_buffer / rr_sweep_copy_to_host -- in one list, zero-filled, for RR_PC_MAX_POSTURES segments of RR_DIST_MAX pairs; the table
+// goes up behind it.  The layout in force is [N, K, ...] for the K of the last query (0 before the first) and the Q of the pair table.
+static size_t sw_bytes(const rr_env *e, int which, int K, int Q) {
+    return (size_t)e->P.N * K * (which == RR_SW_STOP || which == RR_SW_HIT ? 48 : which == RR_SW_ID ? 16 : (size_t)Q * 4);
+}
+static int ensure_sweep(rr_env *e, const char *who) {
+    if (e->sw_buf[0]) return RR_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    void *b[RR_SW_COUNT] = {};
+    SweepReach *rd = nullptr;
+    MemPart parts[RR_SW_COUNT + 1];
+    for (int i = 0; i < RR_SW_COUNT; i++) parts[i] = mem_part(&b[i], sw_bytes(e, i, RR_PC_MAX_POSTURES, RR_DIST_MAX));
+    parts[RR_SW_COUNT] = mem_part(&rd, sizeof(SweepReach), false);
+    RRCHK(mem_get(e, parts, RR_SW_COUNT + 1, (std::string(who) + ": allocating the sweep buffers").c_str()));
+    hipError_t rc = hipMemcpyAsync(rd, &e->sweep_reach, sizeof(SweepReach), hipMemcpyHostToDevice, e->stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);      // (the source is the handle's own memory)
+    if (rc != hipSuccess) {
+        (void)hipStreamSynchronize(e->stream);
+        for (int i = 0; i < RR_SW_COUNT; i++) e->mem.release(b[i]);
+        e->mem.release(rd);
+        (void)hipGetLastError();
+        return fail(RR_EDEVICE, std::string(who) + ": uploading the reach table: " + hipGetErrorString(rc));
+    }
+    for (int i = 0; i < RR_SW_COUNT; i++) e->sw_buf[i] = b[i];
+    e->sw_reach_dev = rd;
+    return RR_OK;
+}
+
+// Conservative advancement along K segments per env, on the device.  On the main stream like rr_posture_clearance: behind every step,
+// reset and state write enqueued before it.  Reads D.state (the objects), the model, the pair table, the reach table and the tensor;
+// writes the four buffers and nothing else -- not the state, the scratch slab of the look-ahead, la_valid, an error flag or a buffer of
+// another query.
+int rr_swept_clearance(rr_env *e, const float *segments, int32_t n_segments, int32_t on_device, float safety, float tolerance) {
+    if (!e) return fail(RR_EINVAL, "rr_swept_clearance: null env");
+    if (!segments) return fail(RR_EINVAL, "rr_swept_clearance: null segments");
+    if (n_segments < 1 || n_segments > RR_PC_MAX_POSTURES)
+        return fail(RR_EINVAL, "rr_swept_clearance: n_segments " + std::to_string(n_segments) + " is not in [1, RR_PC_MAX_POSTURES = " +
+                                   std::to_string(RR_PC_MAX_POSTURES) + "]");
+    const int Q = e->dist_n, N = e->P.N, K = n_segments;
+    if (Q == 0) return fail(RR_EINVAL, "rr_swept_clearance: the pair table is empty (rr_set_distance_pairs)");
+    if (!(safety >= 0.0f) || !std::isfinite(safety)) return fail(RR_EINVAL, "rr_swept_clearance: safety " + std::to_string(safety) + " is not a finite number >= 0");
+    if (!(tolerance >= 1e-6f) || !std::isfinite(tolerance))
+        return fail(RR_EINVAL, "rr_swept_clearance: tolerance " + std::to_string(tolerance) + " is not a finite number >= 1e-6");
+    const float maxd = e->dist_tab.max_distance;
+    if (maxd > 0.0f && maxd < INFINITY && maxd < safety + tolerance)
+        return fail(RR_EINVAL, "rr_swept_clearance: the cull's max_distance " + std::to_string(maxd) + " is below safety + tolerance = " +
+                                   std::to_string(safety + tolerance) + ": a culled pair's sphere gap could fake a hit");
+    RRCHK(ensure_dist(e, "rr_swept_clearance"));          // (the device copy of the pair table)
+    RRCHK(ensure_sweep(e, "rr_swept_clearance"));
+    if (!on_device && !e->sw_stage)
+        RRCHK(mem_get(e, {mem_part(&e->sw_stage, (size_t)N * RR_PC_MAX_POSTURES * 88, false)}, "rr_swept_clearance: allocating the staging buffer"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const float *src = segments;
+    if (!on_device) {
+        HIPCHK(hipMemcpyAsync(e->sw_stage, segments, (size_t)N * K * 88, hipMemcpyHostToDevice, e->stream));
+        src = e->sw_stage;
+    }
+    hipLaunchKernelGGL(k_swept_clearance, dim3((unsigned)N * K), dim3(SWEEP_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, e->sw_reach_dev, src, K,
+                       safety, tolerance, (float *)e->sw_buf[RR_SW_STOP], (float4 *)e->sw_buf[RR_SW_HIT], (int4 *)e->sw_buf[RR_SW_ID], (float *)e->sw_buf[RR_SW_FREE]);
+    HIPCHK(hipGetLastError());
+    e->sw_k = K;
+    if (!on_device) HIPCHK(hipStreamSynchronize(e->stream));   // the argument is host memory
+    return RR_OK;
+}
+
+int rr_sweep_reach(rr_env *e, float *out) {
+    if (!e) return fail(RR_EINVAL, "rr_sweep_reach: null env");
+    if (!out) return fail(RR_EINVAL, "rr_sweep_reach: null destination");
+    for (int k = 0; k < NB; k++) memcpy(out + (size_t)k * e->n_shapes, e->sweep_reach.r[k], (size_t)e->n_shapes * 4);
+    return RR_OK;
+}
+
+int rr_sweep_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_sweep_buffer: null env");
+    if (which < 0 || which >= RR_SW_COUNT) return fail(RR_EINVAL, "rr_sweep_buffer: buffer " + std::to_string(which) + " is not in [0, RR_SW_COUNT)");
+    RRCHK(ensure_sweep(e, "rr_sweep_buffer"));
+    if (dev_ptr) *dev_ptr = e->sw_buf[which];
+    if (bytes) *bytes = sw_bytes(e, which, e->sw_k, e->dist_n);
+    return RR_OK;
+}
+
+int rr_sweep_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_sweep_copy_to_host: null env");
+    if (!dst) return fail(RR_EINVAL, "rr_sweep_copy_to_host: null destination");
+    if (which < 0 || which >= RR_SW_COUNT) return fail(RR_EINVAL, "rr_sweep_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_SW_COUNT)");
+    if (bytes != sw_bytes(e, which, e->sw_k, e->dist_n)) return fail(RR_EINVAL, "rr_sweep_copy_to_host: size mismatch");
+    RRCHK(ensure_sweep(e, "rr_sweep_copy_to_host"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    if (bytes == 0) return RR_OK;
+    HIPCHK(hipMemcpyAsync(dst, e->sw_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return RR_OK;
 }
