@@ -954,6 +954,64 @@ int rr_sweep_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
 /* Synchronising copy of a whole RR_SW_* buffer (its `bytes`) to host memory. */
 int rr_sweep_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
 
+/* ---- Kinematics at candidate joint postures on the device (additive in ABI 7) ----------------------------------------------------------
+ * The queries above answer for the COLLISION side of K candidate postures per env; the other half of a sampler's or optimiser's
+ * objective is "where would the tool be at these postures, and what is the Jacobian there?".  rr_kinematic_observations gives link
+ * poses and Jacobians at the PRESENT state only.  One launch on the library's stream (rr_posture_kinematics) evaluates K candidate
+ * postures per env of the whole batch and writes three device buffers.  The same [N, K, 11] tensor feeds rr_posture_kinematics (the
+ * task cost and its Jacobian), rr_signed_gradient (the collision cost and its gradient) and rr_swept_clearance (the edge check).  The
+ * buffers are NOT fields of rr_get_buffer and not RR_KIN_* or RR_PC_* buffers (RR_F_COUNT stays 16, RR_KIN_COUNT 7, RR_PC_COUNT 4):
+ * they have this enum and rr_posture_kinematics_buffer. */
+enum {
+    RR_PK_LINK_POSE = 0,  /* f32 [N, K, 17, 7]     the RR_KIN_LINK_POSE row (COM frame, xyz + xyzw) of every URDF link at posture (e, k) */
+    RR_PK_POINT_POS = 1,  /* f32 [N, K, P, 3]      world position of every kinematic point in force                                     */
+    RR_PK_JACOBIAN = 2,   /* f32 [N, K, P, 6, 11]  the RR_KIN_JACOBIAN block of every point: rows linear xyz, angular xyz; columns q[11]  */
+    RR_PK_COUNT = 3
+};
+/* Input.  postures, n_postures (K in [1, RR_PC_MAX_POSTURES]) and on_device mean exactly what they mean to rr_posture_clearance:
+ * f32 [N][K][11], C order, the eleven INDEPENDENT joints in the order of the state's q[11].  on_device != 0: device memory, read IN
+ * PLACE on the library's stream under that call's STREAM CONTRACT (produced on that stream or ordered before it; not rewritten before
+ * later work on that stream); the call allocates nothing beyond the first-use buffers, checks the launch and returns without waiting.
+ * on_device == 0: host memory, staged through the posture staging buffer of rr_posture_clearance (the handle's own, allocated by the
+ * first host-path call of any posture query), and the call waits for the stream.  Values are NOT validated and NOT clamped to the
+ * joint limits: the posture is evaluated as given.  The points are those of rr_set_kinematic_points: the P in force, on a fresh
+ * handle the gripper base.
+ * What is computed.  Row (e, k) is what rr_kinematic_observations would write into RR_KIN_LINK_POSE, RR_KIN_POINT_POS and
+ * RR_KIN_JACOBIAN for env e if columns 0..10 of its RR_F_STATE row were postures[e][k][0..10]: the frames of the step's own forward
+ * kinematics, in its operation order; the link expression of rr_link_poses; column k of a point's Jacobian is [a_k x (x - p_k); a_k]
+ * if joint k moves the point's link and +0.0 in all six rows otherwise (the block above has the symbols and the map from the nine
+ * command entries).  For a candidate equal to env e's present joints the three rows are those buffers BIT FOR BIT.  The velocity
+ * fields of rr_kinematic_observations have no counterpart here: a candidate has no joint velocity.
+ * A row is a function of (posture (e, k), the model, the points) ALONE.  It is independent of env e's state -- joints, objects, error
+ * flags: N is the batch shape this query shares with its siblings, not an input.
+ * No effect on the simulation.  The call reads the tensor, the model and the points, and writes these three buffers only: not the
+ * state, not the preparation record (RR_F_PREP), no error flag, no RR_KIN_* buffer and no buffer of another query.  The next step
+ * stays prepared and no later step is affected.  The buffers hold what the LAST CALL computed.
+ * Every loop bound is a constant or a model count, and no value of the tensor ever forms an address: a non-finite posture finishes
+ * like any other and its rows are unspecified.
+ * Determinism.  No atomics: row (e, k) is identical from call to call, independent of N, of K, of the row's place and of its
+ * neighbours.
+ * Errors: RR_EINVAL with nothing allocated and nothing changed, the message naming the function and the cause, for a null env, null
+ * postures, n_postures outside [1, RR_PC_MAX_POSTURES], and a model that rr_kinematic_observations refuses (not the 17 URDF links of
+ * rr_link_poses, or a link on a body outside the kinematic tree).
+ * Buffers.  All three are allocated on first use -- by this call, or by rr_posture_kinematics_buffer /
+ * rr_posture_kinematics_copy_to_host --, all or nothing through the handle's memory owner, zero-filled, sized once for
+ * RR_PC_MAX_POSTURES x RR_KIN_MAX_POINTS -- N x 85 888 bytes: 352 MB at 4096 envs --, and valid until rr_destroy:
+ * no pointer ever changes.  The layout is compact for the K of the last query (0 before the first) and the P in force, and `bytes`
+ * reports that.
+ * After rr_set_kinematic_points the buffers hold unspecified data until the next query (a query enqueued before the change keeps the
+ * points it was launched with).  STREAM CONTRACT for readers as for the other zero-copy views: the kernel runs on the library's stream
+ * behind the work enqueued before it; readers on another stream order themselves after the call (event / rr_sync), and a later call
+ * rewrites the buffers in place.
+ * Out of scope: velocities (a candidate has none); candidate object poses; Jacobians of all 17 links (put points on the links that
+ * matter); a switch of the vector env (postures are an argument, not an observation); ray casts at candidate postures; any use by
+ * the step. */
+int rr_posture_kinematics(rr_env *env, const float *postures /* f32 [N][K][11] */, int32_t n_postures, int32_t on_device);
+/* Zero-copy device pointer + size in bytes of an RR_PK_* buffer (read-only for the caller); which outside [0, RR_PK_COUNT): RR_EINVAL. */
+int rr_posture_kinematics_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
+/* Synchronising copy of a whole RR_PK_* buffer (its `bytes`) to host memory. */
+int rr_posture_kinematics_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
+
 /* Batched damped-least-squares inverse kinematics for link 7 (gripper `base`), seeded with each env's current joints.
  * Replaces pybullet.calculateInverseKinematics(0, 7, pos, orn, maxNumIterations=1000, residualThreshold=0.001) in
  * step_cartesian (env.py:372-375).  targets: f32 [N, 7] (xyz + xyzw quaternion, host); q_out: f32 [N, 11] (all movable

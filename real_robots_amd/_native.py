@@ -45,7 +45,8 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_posture_clearance', 'rr_posture_buffer', 'rr_posture_copy_to_host',
            'rr_signed_distance', 'rr_signed_buffer', 'rr_signed_copy_to_host',
            'rr_signed_gradient', 'rr_signed_gradient_buffer', 'rr_signed_gradient_copy_to_host',
-           'rr_swept_clearance', 'rr_sweep_reach', 'rr_sweep_buffer', 'rr_sweep_copy_to_host')
+           'rr_swept_clearance', 'rr_sweep_reach', 'rr_sweep_buffer', 'rr_sweep_copy_to_host',
+           'rr_posture_kinematics', 'rr_posture_kinematics_buffer', 'rr_posture_kinematics_copy_to_host')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
@@ -91,6 +92,9 @@ SG_FIELDS = ('gradient', 'cost', 'pair_gradient')
 # segments of the last rr_swept_clearance and the Q pairs in force
 SW_FIELDS = ('stop', 'hit', 'id', 'free')
 SW_MAX_STEPS = 64
+# buffers of rr_posture_kinematics_buffer (the RR_PK_* enum), per env and candidate posture: link_pose [17, 7], point_pos [P, 3], jacobian [P, 6, 11] --
+# the rows of the kinematic observations of those names -- for the K postures of the last rr_posture_kinematics and the P points in force
+PK_FIELDS = ('link_pose', 'point_pos', 'jacobian')
 SLOT_LIVE, MAX_SLOTS = -1, 64           # RR_SLOT_LIVE: the running envs as a slot number of rr_copy_envs; RR_MAX_SLOTS
 # `parts` of rr_write_state (the RR_W_* bits): the column groups of the 61-float state row that are written, a reset in front of them,
 # the fresh-start clean-up of rr_set_state behind them
@@ -246,6 +250,9 @@ def load_library():
     L.rr_sweep_reach.argtypes = [vp, vp]
     L.rr_sweep_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rr_sweep_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
+    L.rr_posture_kinematics.argtypes = [vp, vp, i32, i32]
+    L.rr_posture_kinematics_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rr_posture_kinematics_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]

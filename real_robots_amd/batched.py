@@ -1238,6 +1238,45 @@ class BatchedREALRobotEnv:
         return dict(fraction=col(stop, 0), q_stop=cut(stop, 1, 11), status=col(ids, 0), pair=col(ids, 1), steps=col(ids, 2), evaluations=col(ids, 3),
                     distance=col(hit, 0), lower=col(hit, 1), point_a=cut(hit, 2, 3), point_b=cut(hit, 5, 3), normal=cut(hit, 8, 3), pair_free_until=free)
 
+    # ------------------------------------------------------------------ kinematics at candidate postures
+    def posture_kinematics_buffer(self, name, host=False):
+        """One buffer of `posture_kinematics` as the LAST call left it (all zero, and K = 0, before the first), by name
+        (`_native.PK_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait.  Shapes: link_pose
+        [N, K, 17, 7], point_pos [N, K, P, 3], jacobian [N, K, P, 6, 11] float32, for the P points of `set_kinematic_points`."""
+        which = nat.PK_FIELDS.index(name) if isinstance(name, str) and name in nat.PK_FIELDS else name
+        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.PK_FIELDS):
+            raise ValueError("unknown posture kinematics buffer %r (known: %s)" % (name, ', '.join(nat.PK_FIELDS)))
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(self.L.rr_posture_kinematics_buffer(self.h, int(which), C.byref(p), C.byref(n)))
+        P = len(self.kinematic_points()[0])
+        row = ((len(nat.LINK_NAMES), 7), (P, 3), (P, 6, nat.N_JOINTS))[int(which)]
+        shape = (self.N, n.value // (4 * self.N * int(np.prod(row)))) + row
+        if host:
+            out = np.empty(shape, np.float32)
+            nat.check(self.L.rr_posture_kinematics_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
+            return out
+        return nat.DeviceBuffer(p.value, shape, '<f4', self)
+
+    def posture_kinematics(self, postures, host=False):
+        """Where the links and the kinematic points would be at K candidate joint postures per env, and the points' Jacobians there
+        (rr_posture_kinematics): one launch on the library's stream evaluates posture (e, k) as if env e's joints q[11] were
+        postures[e, k] and writes (float32)
+          link_pose [N, K, 17, 7] -- the rows of `kinematic_observations()['link_pose']` (COM frame, xyz + xyzw);
+          point_pos [N, K, P, 3], jacobian [N, K, P, 6, 11] -- for the P points of `set_kinematic_points`: rows linear xyz then angular
+          xyz, columns the eleven joints (`jacobian @ _native.Q_FROM_CMD`: over the nine command entries).
+        A row depends on its posture, the model and the points alone -- not on the env's state; a candidate equal to the present joints
+        gets the bits of `kinematic_observations`.  There are no velocity fields: a candidate has no joint velocity.  The simulation
+        is not touched: no state write, the next step stays prepared.  postures: float32 [N, K, 11], 1 <= K <= 32, C-contiguous, the
+        eleven independent joints -- a numpy array (staged, synchronous) or a CUDA torch tensor / `__cuda_array_interface__` object,
+        read in place on the library's stream without waiting (produce it on that stream or synchronise first); values are neither
+        validated nor clamped to the joint limits.  Returns device buffers (zero copy, DLPack; valid after later work on the library's
+        stream or `sync()`; they hold what the last call computed), or with host=True numpy arrays after a sync."""
+        K = self._posture_arg(postures, self.N)
+        ptr, on_dev, keep = self._state_arg(postures, 'postures', ('float32',), (self.N, K, nat.N_JOINTS))
+        nat.check(self.L.rr_posture_kinematics(self.h, ptr, K, on_dev))
+        del keep
+        return {name: self.posture_kinematics_buffer(i, host=host) for i, name in enumerate(nat.PK_FIELDS)}
+
     def body_row_names(self):
         """The bodies of the rows of body_force / body_partners: the 17 URDF links, then this handle's objects (the rows of the
         objects it does not have, up to 20, stay zero)."""

@@ -164,6 +164,10 @@ struct rr_env : ModelTables {
     int sw_k = 0;                  // segments per env of the last query: 0 before the first
     SweepReach *sw_reach_dev = nullptr;
     float *sw_stage = nullptr;
+    // kinematics at candidate postures (rr_posture_kinematics): the three RR_PK_* buffers, allocated together on first use for
+    // RR_PC_MAX_POSTURES x RR_KIN_MAX_POINTS, once; a host caller's postures go through pc_stage; the points go to the kernel by value
+    float *pk_buf[RR_PK_COUNT] = {};
+    int pk_k = 0;                  // postures per env of the last query: 0 before the first
     MemOwner mem;                  // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
     bool created = false;
     bool timing = false;
@@ -2060,6 +2064,81 @@ int rr_sweep_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
     HIPCHK(hipSetDevice(e->cfg.device));
     if (bytes == 0) return RR_OK;
     HIPCHK(hipMemcpyAsync(dst, e->sw_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return RR_OK;
+}
+
+// ---- kinematics at candidate postures (rr_pkin.inc) -------------------------------------------------------------------------------------
+// The three buffers of rr_posture_kinematics: allocated on first use -- by the query or by rr_posture_kinematics_buffer /
+// rr_posture_kinematics_copy_to_host -- in one list, zero-filled, for RR_PC_MAX_POSTURES postures of RR_KIN_MAX_POINTS points.  The
+// layout in force is [N, K, ...] for the K of the last query (0 before the first) and the P of rr_set_kinematic_points.  The model
+// condition is ensure_kinematics': the kernel's link table has the 17 rows of rr_link_poses, every one on a body of the tree.
+static size_t pk_bytes(const rr_env *e, int which, int K, int np) {
+    const size_t row[RR_PK_COUNT] = {KIN_LINKS * 7, (size_t)3 * np, (size_t)6 * NB * np};
+    return (size_t)e->P.N * K * row[which] * 4;
+}
+static int ensure_pkin(rr_env *e, const char *who) {
+    if (e->pk_buf[0]) return RR_OK;
+    if (e->RM.nl != KIN_LINKS) return fail(RR_EINVAL, std::string(who) + ": the model does not have the 17 URDF links of rr_link_poses");
+    for (int l = 0; l < KIN_LINKS; l++)
+        if (e->RM.link_body[l] >= NB) return fail(RR_EINVAL, std::string(who) + ": link " + std::to_string(l) + " of the model is on a body outside the kinematic tree");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    float *b[RR_PK_COUNT] = {};
+    MemPart parts[RR_PK_COUNT];
+    for (int i = 0; i < RR_PK_COUNT; i++) parts[i] = mem_part(&b[i], pk_bytes(e, i, RR_PC_MAX_POSTURES, RR_KIN_MAX_POINTS));
+    RRCHK(mem_get(e, parts, RR_PK_COUNT, (std::string(who) + ": allocating the posture kinematics buffers").c_str()));
+    for (int i = 0; i < RR_PK_COUNT; i++) e->pk_buf[i] = b[i];
+    return RR_OK;
+}
+
+// Link poses, point positions and Jacobians at K candidate postures per env, on the device.  On the main stream like
+// rr_posture_clearance: behind every step, reset and state write enqueued before it.  Reads the tensor, the model and the points (the
+// handle's host copy goes to the kernel by value: a call enqueued earlier keeps the points it was launched with); writes the three
+// buffers and nothing else -- not the state, the scratch slab of the look-ahead, la_valid, an error flag or a buffer of another query.
+int rr_posture_kinematics(rr_env *e, const float *postures, int32_t n_postures, int32_t on_device) {
+    if (!e) return fail(RR_EINVAL, "rr_posture_kinematics: null env");
+    if (!postures) return fail(RR_EINVAL, "rr_posture_kinematics: null postures");
+    if (n_postures < 1 || n_postures > RR_PC_MAX_POSTURES)
+        return fail(RR_EINVAL, "rr_posture_kinematics: n_postures " + std::to_string(n_postures) + " is not in [1, RR_PC_MAX_POSTURES = " +
+                                   std::to_string(RR_PC_MAX_POSTURES) + "]");
+    const int N = e->P.N, K = n_postures;
+    RRCHK(ensure_pkin(e, "rr_posture_kinematics"));
+    if (!on_device && !e->pc_stage)
+        RRCHK(mem_get(e, {mem_part(&e->pc_stage, (size_t)N * RR_PC_MAX_POSTURES * 44, false)}, "rr_posture_kinematics: allocating the staging buffer"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const float *src = postures;
+    if (!on_device) {
+        HIPCHK(hipMemcpyAsync(e->pc_stage, postures, (size_t)N * K * 44, hipMemcpyHostToDevice, e->stream));
+        src = e->pc_stage;
+    }
+    const int rows = N * K;
+    const PkOut O = {e->pk_buf[RR_PK_LINK_POSE], e->pk_buf[RR_PK_POINT_POS], e->pk_buf[RR_PK_JACOBIAN]};
+    hipLaunchKernelGGL(k_posture_kinematics, dim3((unsigned)((rows + PK_ROWS - 1) / PK_ROWS)), dim3(PK_THREADS), 0, e->stream, e->B, e->RM_dev, src, rows, O,
+                       e->kin_pts, e->kin_np);
+    HIPCHK(hipGetLastError());
+    e->pk_k = K;
+    if (!on_device) HIPCHK(hipStreamSynchronize(e->stream));   // the argument is host memory
+    return RR_OK;
+}
+
+int rr_posture_kinematics_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_posture_kinematics_buffer: null env");
+    if (which < 0 || which >= RR_PK_COUNT) return fail(RR_EINVAL, "rr_posture_kinematics_buffer: buffer " + std::to_string(which) + " is not in [0, RR_PK_COUNT)");
+    RRCHK(ensure_pkin(e, "rr_posture_kinematics_buffer"));
+    if (dev_ptr) *dev_ptr = e->pk_buf[which];
+    if (bytes) *bytes = pk_bytes(e, which, e->pk_k, e->kin_np);
+    return RR_OK;
+}
+
+int rr_posture_kinematics_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_posture_kinematics_copy_to_host: null env");
+    if (!dst) return fail(RR_EINVAL, "rr_posture_kinematics_copy_to_host: null destination");
+    if (which < 0 || which >= RR_PK_COUNT) return fail(RR_EINVAL, "rr_posture_kinematics_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_PK_COUNT)");
+    if (bytes != pk_bytes(e, which, e->pk_k, e->kin_np)) return fail(RR_EINVAL, "rr_posture_kinematics_copy_to_host: size mismatch");
+    RRCHK(ensure_pkin(e, "rr_posture_kinematics_copy_to_host"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    if (bytes == 0) return RR_OK;
+    HIPCHK(hipMemcpyAsync(dst, e->pk_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return RR_OK;
 }
