@@ -1012,6 +1012,83 @@ int rr_posture_kinematics_buffer(rr_env *env, int32_t which, void **dev_ptr, siz
 /* Synchronising copy of a whole RR_PK_* buffer (its `bytes`) to host memory. */
 int rr_posture_kinematics_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
 
+/* ---- Inverse kinematics at candidate targets on the device (additive in ABI 7) ---------------------------------------------------------
+ * Every posture query above starts from joint postures [N, K, 11]; a user starts from tool poses: grasp candidates, pre-grasp poses,
+ * via points, the cartesian samples of a CEM.  rr_ik below solves one target per env, for link 7 only, from the env's present joints,
+ * through host arrays.  One launch on the library's stream (rr_posture_ik) solves K target poses per env of the whole batch, each from
+ * a seed of its own, and writes three device buffers; RR_PIK_POSTURE is the [N, K, 11] tensor that rr_posture_clearance,
+ * rr_signed_distance, rr_signed_gradient and rr_posture_kinematics read IN PLACE.  The buffers are NOT fields of rr_get_buffer and
+ * not RR_PK_* or RR_PC_* buffers (RR_F_COUNT stays 16, RR_KIN_COUNT 7, RR_PC_COUNT 4, RR_PK_COUNT 3): they have this enum and
+ * rr_posture_ik_buffer. */
+#define RR_PIK_MAX_ITERATIONS 256
+enum { RR_PIK_POSITION_ONLY = 1u, RR_PIK_CLAMP_LIMITS = 2u };   /* flags */
+typedef struct rr_ik_options {
+    int32_t point;           /* index into the points of rr_set_kinematic_points, [0, P)   default 0 */
+    int32_t max_iterations;  /* [1, RR_PIK_MAX_ITERATIONS]                                  default 32 */
+    float tolerance;         /* residual below which a row has converged, > 0, finite       default 1e-3 */
+    float damping;           /* lambda of J^T (J J^T + lambda^2 I)^-1 e, > 0, finite        default 0.1 (rr_ik's) */
+    float max_step;          /* cap on |dq|_inf per update, > 0, finite                     default 0.5 (rr_ik's) */
+    uint32_t flags;          /* default RR_PIK_CLAMP_LIMITS */
+} rr_ik_options;
+enum { RR_PIK_POSTURE = 0,  /* f32 [N, K, 11]  the solution; feeds every posture query in place */
+       RR_PIK_RESULT = 1,   /* f32 [N, K, 4]   {residual, position error (m), orientation error angle (rad), +0.0} */
+       RR_PIK_INFO = 2,     /* i32 [N, K, 2]   {status, iterations} */
+       RR_PIK_COUNT = 3 };
+/* Target.  targets[e][k] is the world pose of the tool frame: xyz, then an xyzw quaternion, which the call normalises (as rr_ik does).
+ * Tool frame.  Point opt->point of rr_set_kinematic_points: its position is the point's world position, its orientation the
+ * orientation of the point's link COM frame -- exactly what rr_posture_kinematics reports as point_pos and as the quaternion of
+ * link_pose[link].  Point 0 of a fresh handle is the gripper base: the frame rr_ik solves for.
+ * Seed.  Row (e, k) starts from seeds[e][k] (f32 [N][K][11], the state's q[11]); with seeds == NULL from columns 0..10 of env e's
+ * present state row, which the call READS and never writes.  on_device covers BOTH tensors and has the STREAM CONTRACT of
+ * rr_posture_clearance: device memory read in place on the library's stream, no wait; on_device == 0: host memory -- the seeds are
+ * staged through the posture staging buffer of rr_posture_clearance, the targets through a staging buffer [N, 32, 7] of their own
+ * (allocated through the handle's memory owner with whatever else the call still needs, all or nothing) -- and the call waits.
+ * Unknowns.  The seven arm joints.  Joints 7..10 (the fingers) are copied from the seed to the output unchanged; they may still
+ * place the tool, a point on a finger link being legal.  An arm joint that does not move the point's link (a point on link_3 has
+ * four) has a zero Jacobian column and keeps its seed value.
+ * Residual (rr_ik's): e_p = target - x; w = half the antisymmetric part of Rt Re^T (sin(angle) x axis of the orientation error);
+ * residual = |(e_p, w)|.  With RR_PIK_POSITION_ONLY residual = |e_p|, the system is 3 x 3 and the target quaternion is ignored by
+ * the solve.  The RR_PIK_RESULT row always carries |e_p|, and the TRUE angle atan2(|w|, (trace(Rt Re^T) - 1) / 2) against the
+ * given quaternion, so a caller can see an aliased orientation (in position-only mode it is informational, and NaN for a quaternion
+ * that cannot be normalised).
+ * Update (rr_ik's): dq = J^T (J J^T + lambda^2 I)^-1 e by Cholesky, scaled so that |dq|_inf <= max_step.  With RR_PIK_CLAMP_LIMITS
+ * the seed's arm joints are first clamped into the model's body_limits and every iterate is clamped too: every returned arm joint
+ * lies within its limits.  Without it every iterate is wrapped to (-pi, pi], as rr_ik does (a seed that needs no update is
+ * returned as given).
+ * Stop and status.  The residual is evaluated before each update and once more after the last; `iterations` is the number of
+ * updates applied, 0 .. max_iterations.  status 0: converged -- residual < tolerance and, in full-pose mode,
+ * (trace(Rt Re^T) - 1) / 2 > 0 (w vanishes at a half-turn too: stopping there would be a false success; such a row runs to the cap).
+ * status 1: the iteration cap; the row holds the last iterate and its residual.  status 2: the residual is not finite (a non-finite
+ * target or seed, a zero quaternion); the row's other values are unspecified.
+ * Independence and determinism.  Row (e, k) is a function of (its target, its seed, the options, the model, the points) ALONE and
+ * identical from call to call: independent of N, of K, of the row's place and of its neighbours; with seeds == NULL env e's joints
+ * enter as the seed and in no other way.  No atomics.
+ * Safety.  Every loop bound is a constant, a model count or max_iterations, and no value of a tensor ever forms an address.
+ * No effect on the simulation.  The call writes these three buffers and nothing else: not the state, not the preparation record
+ * (RR_F_PREP), no error flag, not the plan and IK buffers of rr_ik / rr_plan_macro, no buffer of another query.  The next step
+ * stays prepared.  The buffers hold what the LAST CALL computed.
+ * Cost.  One lane per row; a wave of 64 rows runs as long as its slowest row, so a few rows at the cap keep most waves for
+ * max_iterations updates.
+ * Errors: RR_EINVAL with nothing allocated and nothing changed, the message naming the function and the cause, for a null env, null
+ * targets, n_targets outside [1, RR_PC_MAX_POSTURES], point outside [0, P), max_iterations outside [1, RR_PIK_MAX_ITERATIONS], a
+ * tolerance, damping or max_step that is not finite or not > 0, an unknown flag bit, and a model that rr_kinematic_observations
+ * refuses.  opt == NULL: the defaults.
+ * Buffers.  All three are allocated on first use -- by this call, or by rr_posture_ik_buffer / rr_posture_ik_copy_to_host --, all
+ * or nothing through the handle's memory owner, zero-filled, sized once for RR_PC_MAX_POSTURES -- N x 2 176 bytes --, and valid until
+ * rr_destroy: no pointer ever changes.  The layout is compact for the K of the last call (0 before the first), and `bytes` reports
+ * that.  STREAM CONTRACT for readers as for the other zero-copy views: a posture query enqueued behind this call on the library's
+ * stream reads RR_PIK_POSTURE in order; readers on another stream order themselves after the call (event / rr_sync), and a later
+ * call rewrites the buffers in place.
+ * Out of scope: any use by the step (cartesian actions); null-space objectives; collision-aware IK (compose the posture with
+ * rr_signed_gradient); random restarts inside the call (give several rows the same target with different seeds); a switch of the
+ * vector env; any change to rr_ik, rr_plan_macro or the ik_single_seed option. */
+int rr_posture_ik(rr_env *env, const float *targets /* f32 [N][K][7] */, const float *seeds /* f32 [N][K][11] or NULL */,
+                  int32_t n_targets, int32_t on_device, const rr_ik_options *opt /* NULL: the defaults */);
+/* Zero-copy device pointer + size in bytes of an RR_PIK_* buffer (read-only for the caller); which outside [0, RR_PIK_COUNT): RR_EINVAL. */
+int rr_posture_ik_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
+/* Synchronising copy of a whole RR_PIK_* buffer (its `bytes`) to host memory. */
+int rr_posture_ik_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
+
 /* Batched damped-least-squares inverse kinematics for link 7 (gripper `base`), seeded with each env's current joints.
  * Replaces pybullet.calculateInverseKinematics(0, 7, pos, orn, maxNumIterations=1000, residualThreshold=0.001) in
  * step_cartesian (env.py:372-375).  targets: f32 [N, 7] (xyz + xyzw quaternion, host); q_out: f32 [N, 11] (all movable

@@ -46,7 +46,8 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_signed_distance', 'rr_signed_buffer', 'rr_signed_copy_to_host',
            'rr_signed_gradient', 'rr_signed_gradient_buffer', 'rr_signed_gradient_copy_to_host',
            'rr_swept_clearance', 'rr_sweep_reach', 'rr_sweep_buffer', 'rr_sweep_copy_to_host',
-           'rr_posture_kinematics', 'rr_posture_kinematics_buffer', 'rr_posture_kinematics_copy_to_host')
+           'rr_posture_kinematics', 'rr_posture_kinematics_buffer', 'rr_posture_kinematics_copy_to_host',
+           'rr_posture_ik', 'rr_posture_ik_buffer', 'rr_posture_ik_copy_to_host')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
@@ -95,6 +96,12 @@ SW_MAX_STEPS = 64
 # buffers of rr_posture_kinematics_buffer (the RR_PK_* enum), per env and candidate posture: link_pose [17, 7], point_pos [P, 3], jacobian [P, 6, 11] --
 # the rows of the kinematic observations of those names -- for the K postures of the last rr_posture_kinematics and the P points in force
 PK_FIELDS = ('link_pose', 'point_pos', 'jacobian')
+# buffers of rr_posture_ik_buffer (the RR_PIK_* enum), per env and target: posture f32 [11], result f32 [4] {residual, position error,
+# orientation error angle, 0}, info i32 [2] {status, iterations}, for the K targets of the last rr_posture_ik
+PIK_FIELDS = ('posture', 'result', 'info')
+PIK_MAX_ITERATIONS = 256
+PIK_POSITION_ONLY, PIK_CLAMP_LIMITS = 1, 2           # flags of rr_ik_options
+PIK_CONVERGED, PIK_CAP, PIK_NOT_FINITE = 0, 1, 2     # status
 SLOT_LIVE, MAX_SLOTS = -1, 64           # RR_SLOT_LIVE: the running envs as a slot number of rr_copy_envs; RR_MAX_SLOTS
 # `parts` of rr_write_state (the RR_W_* bits): the column groups of the 61-float state row that are written, a reset in front of them,
 # the fresh-start clean-up of rr_set_state behind them
@@ -253,6 +260,9 @@ def load_library():
     L.rr_posture_kinematics.argtypes = [vp, vp, i32, i32]
     L.rr_posture_kinematics_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rr_posture_kinematics_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
+    L.rr_posture_ik.argtypes = [vp, vp, vp, i32, i32, C.POINTER(IkOptions)]
+    L.rr_posture_ik_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rr_posture_ik_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]
@@ -265,6 +275,15 @@ def load_library():
         raise RuntimeError("real_robots_amd: ABI version mismatch, rebuild the HIP library")
     _lib = L
     return L
+
+
+class IkOptions(C.Structure):
+    """rr_ik_options (include/realrobot.h); the defaults are the header's."""
+    _fields_ = [('point', C.c_int32), ('max_iterations', C.c_int32), ('tolerance', C.c_float), ('damping', C.c_float),
+                ('max_step', C.c_float), ('flags', C.c_uint32)]
+
+    def __init__(self, point=0, max_iterations=32, tolerance=1e-3, damping=0.1, max_step=0.5, flags=PIK_CLAMP_LIMITS):
+        super().__init__(point, max_iterations, tolerance, damping, max_step, flags)
 
 
 class NativeError(RuntimeError):

@@ -1277,6 +1277,68 @@ class BatchedREALRobotEnv:
         del keep
         return {name: self.posture_kinematics_buffer(i, host=host) for i, name in enumerate(nat.PK_FIELDS)}
 
+    # ------------------------------------------------------------------ inverse kinematics at candidate targets
+    def posture_ik_buffer(self, name, host=False):
+        """One buffer of `posture_ik` as the LAST call left it (all zero, and K = 0, before the first), by name (`_native.PIK_FIELDS`)
+        or index: a device view (zero copy), or with host=True a numpy copy after a wait.  Shapes: posture [N, K, 11] float32, result
+        [N, K, 4] float32 {residual, position error, orientation error angle, 0}, info [N, K, 2] int32 {status, iterations}."""
+        which = nat.PIK_FIELDS.index(name) if isinstance(name, str) and name in nat.PIK_FIELDS else name
+        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.PIK_FIELDS):
+            raise ValueError("unknown posture IK buffer %r (known: %s)" % (name, ', '.join(nat.PIK_FIELDS)))
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(self.L.rr_posture_ik_buffer(self.h, int(which), C.byref(p), C.byref(n)))
+        cols, dt = ((nat.N_JOINTS, np.float32), (4, np.float32), (2, np.int32))[int(which)]
+        shape = (self.N, n.value // (4 * cols * self.N), cols)
+        if host:
+            out = np.empty(shape, dt)
+            nat.check(self.L.rr_posture_ik_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
+            return out
+        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
+
+    def posture_ik(self, targets, seeds=None, point=0, max_iterations=32, tolerance=1e-3, damping=0.1, max_step=0.5,
+                   position_only=False, clamp=True, host=False):
+        """Joint postures that put the tool at K target poses per env (rr_posture_ik): one launch on the library's stream solves
+        target (e, k) by damped least squares over the seven arm joints -- `ik()`'s residual and update -- from seed (e, k).
+          targets float32 [N, K, 7], 1 <= K <= 32: world xyz and xyzw quaternion (normalised by the call) of the tool frame, point
+              `point` of `set_kinematic_points`: the point's position, its link's COM frame orientation -- what `posture_kinematics`
+              reports as `point_pos` and the quaternion of `link_pose[link]`; point 0 of a fresh handle is the gripper base;
+          seeds float32 [N, K, 11] or None: the env's present joints (read, never written).  The finger joints 7..10 are copied to the
+              output; an arm joint that does not move the point's link keeps its seed value.
+        Both are numpy arrays (staged, synchronous) or both CUDA torch tensors / `__cuda_array_interface__` objects, read in place on the
+        library's stream without waiting; a mixed pair is a ValueError.  max_iterations in [1, 256]; a row stops when its residual
+        |(position error, sin(angle) axis)| (position_only: |position error|, a 3 x 3 system, the quaternion ignored) is below
+        `tolerance`; `damping` is lambda of J^T (J J^T + lambda^2 I)^-1 e, `max_step` caps |dq|inf of an update.  clamp=True keeps the arm
+        joints within the model's limits (the seed is clamped first); clamp=False wraps them to (-pi, pi] as `ik()` does.  Returns
+          posture float32 [N, K, 11] -- goes straight into `posture_clearance`, `signed_distance_gradient`, `posture_kinematics`;
+          residual, position_error (m), orientation_error (rad, the true angle) float32 [N, K];
+          status int32 [N, K] (0 converged, 1 iteration cap: the last iterate, 2 residual not finite: row unspecified), iterations
+          int32 [N, K] (updates applied).
+        Device views (zero copy, strided, DLPack; valid after later work on the library's stream or `sync()`; they hold what the last
+        call computed), or with host=True numpy views of host copies after a sync.  The simulation is not touched.  A wave of 64 rows
+        runs as long as its slowest row."""
+        what = "targets must be a C-contiguous float32 array of shape (%d, K, 7), 1 <= K <= %d" % (self.N, nat.PC_MAX_POSTURES)
+        cai = getattr(targets, '__cuda_array_interface__', None)
+        try:
+            shape = tuple(cai['shape'] if cai is not None else targets.shape if hasattr(targets, 'shape') else np.shape(targets))
+        except (ValueError, TypeError):
+            raise ValueError("%s, not %r" % (what, type(targets).__name__))
+        if len(shape) != 3 or shape[0] != self.N or shape[2] != 7 or not 1 <= shape[1] <= nat.PC_MAX_POSTURES:
+            raise ValueError("%s, not %s" % (what, shape))
+        K = int(shape[1])
+        tp, t_dev, t_keep = self._state_arg(targets, 'targets', ('float32',), (self.N, K, 7))
+        sp, s_dev, s_keep = (None, None, None) if seeds is None else self._state_arg(seeds, 'seeds', ('float32',), (self.N, K, nat.N_JOINTS))
+        if s_dev is not None and s_dev != t_dev:
+            raise ValueError("posture_ik: targets and seeds must live on the same side (targets on the %s, seeds on the %s)"
+                             % (('host', 'device')[t_dev], ('host', 'device')[s_dev]))
+        opt = nat.IkOptions(int(point), int(max_iterations), float(tolerance), float(damping), float(max_step),
+                            (nat.PIK_POSITION_ONLY if position_only else 0) | (nat.PIK_CLAMP_LIMITS if clamp else 0))
+        nat.check(self.L.rr_posture_ik(self.h, tp, sp, K, t_dev, C.byref(opt)))
+        del t_keep, s_keep
+        posture, result, info = (self.posture_ik_buffer(i, host=host) for i in range(len(nat.PIK_FIELDS)))
+        col = self.ray_column
+        return dict(posture=posture, residual=col(result, 0), position_error=col(result, 1), orientation_error=col(result, 2),
+                    status=col(info, 0), iterations=col(info, 1))
+
     def body_row_names(self):
         """The bodies of the rows of body_force / body_partners: the 17 URDF links, then this handle's objects (the rows of the
         objects it does not have, up to 20, stay zero)."""

@@ -168,6 +168,11 @@ struct rr_env : ModelTables {
     // RR_PC_MAX_POSTURES x RR_KIN_MAX_POINTS, once; a host caller's postures go through pc_stage; the points go to the kernel by value
     float *pk_buf[RR_PK_COUNT] = {};
     int pk_k = 0;                  // postures per env of the last query: 0 before the first
+    // inverse kinematics at candidate targets (rr_posture_ik): the three RR_PIK_* buffers, allocated together on first use for
+    // RR_PC_MAX_POSTURES, once; a host caller's seeds go through pc_stage, its targets through pik_stage [N, 32, 7]
+    void *pik_buf[RR_PIK_COUNT] = {};
+    int pik_k = 0;                 // targets per env of the last call: 0 before the first
+    float *pik_stage = nullptr;
     MemOwner mem;                  // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
     bool created = false;
     bool timing = false;
@@ -2139,6 +2144,110 @@ int rr_posture_kinematics_copy_to_host(rr_env *e, int32_t which, void *dst, size
     HIPCHK(hipSetDevice(e->cfg.device));
     if (bytes == 0) return RR_OK;
     HIPCHK(hipMemcpyAsync(dst, e->pk_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return RR_OK;
+}
+
+// ---- inverse kinematics at candidate targets (rr_pik.inc) ------------------------------------------------------------------------------
+// The three buffers of rr_posture_ik: allocated on first use -- by the call or by rr_posture_ik_buffer / rr_posture_ik_copy_to_host --
+// in one list, zero-filled, for RR_PC_MAX_POSTURES targets per env.  The layout in force is [N, K, ...] for the K of the last call
+// (0 before the first).  The model condition is ensure_pkin's: the kernel reads the link table of rr_link_poses.
+static size_t pik_bytes(const rr_env *e, int which, int K) {
+    const size_t row[RR_PIK_COUNT] = {NB * 4, 4 * 4, 2 * 4};
+    return (size_t)e->P.N * K * row[which];
+}
+// `stage_seeds` / `stage_targets`: the staging buffers a host-path call still lacks come in the same list, all or nothing
+static int ensure_pik(rr_env *e, const char *who, bool stage_seeds = false, bool stage_targets = false) {
+    stage_seeds = stage_seeds && !e->pc_stage;
+    stage_targets = stage_targets && !e->pik_stage;
+    const bool bufs = !e->pik_buf[0];
+    if (!bufs && !stage_seeds && !stage_targets) return RR_OK;
+    if (e->RM.nl != KIN_LINKS) return fail(RR_EINVAL, std::string(who) + ": the model does not have the 17 URDF links of rr_link_poses");
+    for (int l = 0; l < KIN_LINKS; l++)
+        if (e->RM.link_body[l] >= NB) return fail(RR_EINVAL, std::string(who) + ": link " + std::to_string(l) + " of the model is on a body outside the kinematic tree");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    void *b[RR_PIK_COUNT] = {};
+    float *ss = nullptr, *ts = nullptr;
+    MemPart parts[RR_PIK_COUNT + 2];
+    size_t n = 0;
+    if (bufs)
+        for (int i = 0; i < RR_PIK_COUNT; i++) parts[n++] = mem_part(&b[i], pik_bytes(e, i, RR_PC_MAX_POSTURES));
+    if (stage_seeds) parts[n++] = mem_part(&ss, (size_t)e->P.N * RR_PC_MAX_POSTURES * 44, false);
+    if (stage_targets) parts[n++] = mem_part(&ts, (size_t)e->P.N * RR_PC_MAX_POSTURES * 28, false);
+    RRCHK(mem_get(e, parts, n, (std::string(who) + ": allocating the posture IK buffers").c_str()));
+    if (bufs)
+        for (int i = 0; i < RR_PIK_COUNT; i++) e->pik_buf[i] = b[i];
+    if (stage_seeds) e->pc_stage = ss;
+    if (stage_targets) e->pik_stage = ts;
+    return RR_OK;
+}
+
+// K target tool poses per env solved on the device.  On the main stream like rr_posture_clearance: behind every step, reset and
+// state write enqueued before it.  Reads the two tensors (without seeds: the joint columns of the state), the model and the points
+// (the handle's host copy goes to the kernel by value); writes the three buffers and nothing else -- not the state, the scratch slab
+// of the look-ahead, la_valid, an error flag, the buffers of rr_ik / rr_plan_macro or a buffer of another query.
+int rr_posture_ik(rr_env *e, const float *targets, const float *seeds, int32_t n_targets, int32_t on_device, const rr_ik_options *opt) {
+    if (!e) return fail(RR_EINVAL, "rr_posture_ik: null env");
+    if (!targets) return fail(RR_EINVAL, "rr_posture_ik: null targets");
+    if (n_targets < 1 || n_targets > RR_PC_MAX_POSTURES)
+        return fail(RR_EINVAL, "rr_posture_ik: n_targets " + std::to_string(n_targets) + " is not in [1, RR_PC_MAX_POSTURES = " + std::to_string(RR_PC_MAX_POSTURES) + "]");
+    const rr_ik_options def = {0, 32, 1e-3f, 0.1f, 0.5f, RR_PIK_CLAMP_LIMITS};
+    const rr_ik_options o = opt ? *opt : def;
+    if (o.point < 0 || o.point >= e->kin_np)
+        return fail(RR_EINVAL, "rr_posture_ik: point " + std::to_string(o.point) + " is not in [0, P = " + std::to_string(e->kin_np) + ") (rr_set_kinematic_points)");
+    if (o.max_iterations < 1 || o.max_iterations > RR_PIK_MAX_ITERATIONS)
+        return fail(RR_EINVAL, "rr_posture_ik: max_iterations " + std::to_string(o.max_iterations) + " is not in [1, RR_PIK_MAX_ITERATIONS = " +
+                                   std::to_string(RR_PIK_MAX_ITERATIONS) + "]");
+    if (!(o.tolerance > 0.0f) || !std::isfinite(o.tolerance)) return fail(RR_EINVAL, "rr_posture_ik: tolerance " + std::to_string(o.tolerance) + " is not a finite number > 0");
+    if (!(o.damping > 0.0f) || !std::isfinite(o.damping)) return fail(RR_EINVAL, "rr_posture_ik: damping " + std::to_string(o.damping) + " is not a finite number > 0");
+    if (!(o.max_step > 0.0f) || !std::isfinite(o.max_step)) return fail(RR_EINVAL, "rr_posture_ik: max_step " + std::to_string(o.max_step) + " is not a finite number > 0");
+    if (o.flags & ~(uint32_t)(RR_PIK_POSITION_ONLY | RR_PIK_CLAMP_LIMITS)) return fail(RR_EINVAL, "rr_posture_ik: unknown flag bits in " + std::to_string(o.flags));
+    const int N = e->P.N, K = n_targets;
+    RRCHK(ensure_pik(e, "rr_posture_ik", !on_device && seeds, !on_device));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const float *tsrc = targets, *ssrc = seeds;
+    if (!on_device) {
+        HIPCHK(hipMemcpyAsync(e->pik_stage, targets, (size_t)N * K * 28, hipMemcpyHostToDevice, e->stream));
+        tsrc = e->pik_stage;
+        if (seeds) {
+            HIPCHK(hipMemcpyAsync(e->pc_stage, seeds, (size_t)N * K * 44, hipMemcpyHostToDevice, e->stream));
+            ssrc = e->pc_stage;
+        }
+    }
+    const int rows = N * K;
+    const PikOut O = {(float *)e->pik_buf[RR_PIK_POSTURE], (float *)e->pik_buf[RR_PIK_RESULT], (int *)e->pik_buf[RR_PIK_INFO]};
+    const PikOpt po = {o.point, o.max_iterations, o.tolerance, o.damping * o.damping, o.max_step, o.flags};
+    // (one instantiation per system size: 6 x 6 full pose, 3 x 3 position only)
+    if (o.flags & RR_PIK_POSITION_ONLY)
+        hipLaunchKernelGGL(k_posture_ik<1>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, e->stream, e->B, e->RM_dev, tsrc, ssrc, (const float *)e->D.state, N, K,
+                           O, e->kin_pts, po);
+    else
+        hipLaunchKernelGGL(k_posture_ik<0>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, e->stream, e->B, e->RM_dev, tsrc, ssrc, (const float *)e->D.state, N, K,
+                           O, e->kin_pts, po);
+    HIPCHK(hipGetLastError());
+    e->pik_k = K;
+    if (!on_device) HIPCHK(hipStreamSynchronize(e->stream));   // the arguments are host memory
+    return RR_OK;
+}
+
+int rr_posture_ik_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_posture_ik_buffer: null env");
+    if (which < 0 || which >= RR_PIK_COUNT) return fail(RR_EINVAL, "rr_posture_ik_buffer: buffer " + std::to_string(which) + " is not in [0, RR_PIK_COUNT)");
+    RRCHK(ensure_pik(e, "rr_posture_ik_buffer"));
+    if (dev_ptr) *dev_ptr = e->pik_buf[which];
+    if (bytes) *bytes = pik_bytes(e, which, e->pik_k);
+    return RR_OK;
+}
+
+int rr_posture_ik_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_posture_ik_copy_to_host: null env");
+    if (!dst) return fail(RR_EINVAL, "rr_posture_ik_copy_to_host: null destination");
+    if (which < 0 || which >= RR_PIK_COUNT) return fail(RR_EINVAL, "rr_posture_ik_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_PIK_COUNT)");
+    if (bytes != pik_bytes(e, which, e->pik_k)) return fail(RR_EINVAL, "rr_posture_ik_copy_to_host: size mismatch");
+    RRCHK(ensure_pik(e, "rr_posture_ik_copy_to_host"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    if (bytes == 0) return RR_OK;
+    HIPCHK(hipMemcpyAsync(dst, e->pik_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return RR_OK;
 }
