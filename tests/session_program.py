@@ -22,6 +22,17 @@ every written value is a fresh draw, so it differs from what is there.
 Values that depend on the handle are kept as recipes and resolved by the Session in float32 on the host, the same for every handle:
 object positions are offsets from BASE (where the reference puts cube, tomato, mustard on the table), cameras are eye / target /
 field of view, colours a tint per env.
+
+`program(..., queries=True)` draws a QUERY programme instead (sessions q70 and q5; the other programmes are drawn exactly as before,
+tests/test_session_program.py pins their digests): the same units, with three more mutators -- set_distance_pairs,
+set_kinematic_points, set_rays: the tables of the read-only batch queries are handle state -- and the nine query calls as observers
+(Q_OBSERVERS), each record with its own arguments: K in {1, 3, 32} postures (`_Draw.rows()['q']`), segments between two postures, IK
+goals (postures whose float64 tool pose at the point in force is the target: a recipe, resolved by `Session.ik_targets`) and seeds.
+A query record carries `compared`: True -- the plain-road twin makes the call too, with host arrays, and the result buffers of the
+two calls are compared; False -- the call is A's alone.  `check_query_conditions` asserts what a query programme holds.  The Session
+keeps the tables it has set (`points`, `max_distance`, `n_rays`) so that the arguments of later calls fit them, and `last`: which
+record wrote which result buffers last.  `probe_arguments` are the fixed query arguments of every comparison, `anchor_references`
+the float64 restatements on a state that a record itself defines (`is_anchor`).
 """
 import numpy as np
 
@@ -34,10 +45,28 @@ IMAGE_ONLY = ('set_camera', 'set_camera_default', 'set_env_cameras', 'set_env_ap
 OBSERVERS = ('ray_table', 'ray_dev', 'kinematic_observations', 'contact_observations', 'read_state', 'link_poses', 'evaluate_goals',
              'episode_peek', 'contacts', 'sync', 'sync_observations')
 RENDER_FORMS = (0, 1, 2)                    # no camera, all envs, per-env flags
+# the query programmes (sessions q70, q5): three more mutators -- the tables of the read-only batch queries are handle state -- and
+# the nine query calls as observers; `compared` of a query record: B makes the call too (host arrays against A's device tensors)
+Q_MUTATORS = ('set_distance_pairs', 'set_kinematic_points', 'set_rays')
+Q_OBSERVERS = ('closest_points', 'posture_clearance', 'signed_distance', 'signed_distance_at', 'signed_distance_gradient',
+               'swept_clearance', 'posture_kinematics', 'posture_ik', 'posture_ik_present')
+STATE_READERS = tuple(k for k in Q_OBSERVERS if k not in ('posture_kinematics', 'posture_ik'))     # (those two read tensors, model, points)
+PAIR_READERS = STATE_READERS[:6]            # ... and the pair table
+# which result buffers a query call writes: a compared record is judged on these, as its own call left them
+FAMILY = {'closest_points': ('dist',), 'posture_clearance': ('pc',), 'signed_distance': ('sd',), 'signed_distance_at': ('sd',),
+          'signed_distance_gradient': ('sd', 'sg'), 'swept_clearance': ('sw',), 'posture_kinematics': ('pk',), 'posture_ik': ('pik',),
+          'posture_ik_present': ('pik',)}
+# a query observer must stand directly behind each of these, with no step between (write_state: a pose part and a joint part)
+READ_BEHIND = ('write_state', 'fork_dev', 'load_snapshot', 'reset_dev', 'restore', 'set_object_poses', 'episode_reset',
+               'set_distance_pairs', 'set_kinematic_points')
+Q_KS, Q_PAIR_CLASSES, Q_RAY_COUNTS = (1, 3, 32), ('one', 'default', 'collision', 'full'), (1, 4, 64)
 
 # the sessions of tests/test_gpu_session.py: name -> (seed, N, objects, width, height, ops); the seed was fixed once, for the
 # coverage the device reports (NOTEBOOK.md), and is never changed to make a comparison pass
-SESSIONS = {'n70': (20261, 70, 3, 64, 64, 200), 'n5': (20262, 5, 1, 96, 64, 200), 'n1100': (20263, 1100, 3, 32, 32, 200)}
+Q_LENGTH = 74                               # what the conditions of a query programme cost (below)
+SESSIONS = {'n70': (20261, 70, 3, 64, 64, 200), 'n5': (20262, 5, 1, 96, 64, 200), 'n1100': (20263, 1100, 3, 32, 32, 200),
+            'q70': (20264, 70, 3, 64, 64, Q_LENGTH), 'q5': (20265, 5, 1, 96, 64, Q_LENGTH)}
+QUERY_SESSIONS = ('q70', 'q5')              # drawn with program(..., queries=True)
 
 # What a programme holds, whatever its size (check_conditions): M = 23 mutator kinds, O = 11 observer kinds; a pair costs 2 ops, a
 # triple 3, an observer behind a pair 1.  Every mutator 3 times in pairs, once with each render form (138); every observer behind a
@@ -46,6 +75,36 @@ SESSIONS = {'n70': (20261, 70, 3, 64, 64, 200), 'n5': (20262, 5, 1, 96, 64, 200)
 # header names bitwise equal to host calls; one launch (2): a write that throws an object out of bounds within one step, in front of
 # a set_object_home.  194 ops; the rest are fillers.
 MIN_LENGTH = 200
+# A query programme holds other conditions (check_query_conditions).  Pairs (2 ops): each of the three table mutators with each render
+# form (18) -- two of the set_distance_pairs put the default table of `Session.setup` back in force and are glued in front of the two
+# anchors, a set_state and a full write_state, whose state is known on the CPU (4) --, a checkpoint and a save_snapshot (4).  Triples
+# (3 ops), a query observer directly between a mutator and a step: one behind each of write_state (object poses), fork_dev,
+# load_snapshot, reset_dev, restore, set_object_poses, episode_reset -- the seven state readers, rotated by the seed --, two behind a
+# set_distance_pairs, three behind a set_kinematic_points (posture_ik without seeds, posture_kinematics, posture_ik), and the last
+# unit: write_state (joint positions) -- posture_ik without seeds (39).  Every query observer once more behind a pair, directly in
+# front of the next unit's mutator (9).  74 ops; a longer programme gets further steps.
+Q_MIN_LENGTH = Q_LENGTH
+# collision shapes of the model by name (BatchedREALRobotEnv.collision_shapes; tests/test_session_program.py asserts the list)
+ROBOT_SHAPES = ('lbr_iiwa_link_1', 'lbr_iiwa_link_2', 'lbr_iiwa_link_3', 'lbr_iiwa_link_4', 'lbr_iiwa_link_5', 'lbr_iiwa_link_6',
+                'lbr_iiwa_link_7', 'base', 'finger_00', 'finger_01', 'skin_01', 'skin_00', 'finger_10', 'finger_11', 'skin_11', 'skin_10')
+STATIC_SHAPES = ('table', 'shelf', 'robot_base')
+OBJECT_SHAPES = ('cube', 'tomato', 'mustard')
+N_LINKS, FINGER_LINKS, ARM_LINKS = 17, tuple(range(9, 17)), tuple(range(1, 7))      # (LINK_NAMES: 9.. the gripper's; 1..6 below joint 7)
+PROBE_K, PROBE_ITERATIONS, PROBE_MARGIN = 2, 8, 0.25
+
+
+def default_pairs(nobj):
+    """the pair table of `Session.setup`, by name: robot-object, robot-static, robot-robot, object-object, object-static; the
+    objects are those the handle has (with fewer than three, a missing one is replaced by one it has; doubles are dropped)"""
+    o = [OBJECT_SHAPES[i % nobj] for i in range(3)]
+    pairs = [('skin_00', o[0]), ('finger_01', o[2]), ('lbr_iiwa_link_6', o[1]), ('skin_10', o[0]), ('finger_00', 'shelf'),
+             ('lbr_iiwa_link_7', 'table'), ('lbr_iiwa_link_5', 'table'), ('lbr_iiwa_link_7', 'robot_base'),
+             ('lbr_iiwa_link_3', 'lbr_iiwa_link_6'), (o[0], o[1]), (o[1], o[2]), (o[0], 'table'), (o[1], 'table'), (o[2], 'shelf')]
+    out = []
+    for p in pairs:
+        if p[0] != p[1] and p not in out:
+            out.append(p)
+    return out
 
 BASE = np.array([[-0.1, 0.0, 0.45], [-0.1, -0.3, 0.45], [-0.1, 0.3, 0.45]], np.float32)      # cube, tomato, mustard (robot.py:19-24)
 CMD_LO = np.array([-2.09, -2.09, -2.96, -2.09, -2.96, -2.09, -3.05, 0.0, 0.0], np.float32)
@@ -64,6 +123,8 @@ class _Draw:
         self.cmd = rng.uniform(CMD_LO, CMD_HI, (N, 9)).astype(np.float32)
         self.sel = 7
         self.n_write = 0
+        self.n_points = self.n_rays = self.n_query = 0
+        self.n_kind = {}
 
     def mask(self):
         """uint8 [N], never all-clear, not all-set when N > 1; set bytes are any non-zero value"""
@@ -176,7 +237,84 @@ class _Draw:
                 sel ^= int(rng.choice([1, 2, 4]))
             self.sel = sel
             op.update(sel=sel)
+        elif kind == 'set_distance_pairs':          # (a query programme passes `pairs=` itself: the class of the table)
+            raise AssertionError("set_distance_pairs is drawn by table()")
+        elif kind == 'set_kinematic_points':
+            P = int(rng.integers(1, 9))
+            links = rng.integers(1, N_LINKS, P)
+            n = self.n_points
+            self.n_points += 1
+            finger, arm = FINGER_LINKS[int(rng.integers(len(FINGER_LINKS)))], ARM_LINKS[int(rng.integers(len(ARM_LINKS)))]
+            if P == 1:                              # the last point is the IK's: a finger link and a link below joint 7 take turns
+                links[0] = arm if n % 2 else finger
+            else:
+                links[P - 1], links[P - 2] = (arm, finger) if n % 2 else (finger, arm)
+            local = rng.uniform(0.01, 0.1, (P, 3)) * rng.choice([-1.0, 1.0], (P, 3))
+            op.update(links=links.astype(np.int32), local=local.astype(np.float32))
+        elif kind == 'set_rays':
+            R = int(Q_RAY_COUNTS[(self.n_rays + self.salt) % 3])
+            self.n_rays += 1
+            links = np.where(rng.random(R) < 0.5, -1, rng.integers(0, N_LINKS, R)).astype(np.int32)
+            if R > 1:
+                links[0], links[1] = -1, 8          # a world ray and a ray of the gripper base, whatever the draw
+            seg = np.zeros((R, 6), np.float32)
+            xy = rng.uniform([-0.3, -0.45], [0.2, 0.45], (R, 2))
+            seg[:, 0:2], seg[:, 3:5], seg[:, 2], seg[:, 5] = xy, xy + rng.uniform(-0.1, 0.1, xy.shape), 1.0, 0.2
+            local = links >= 0
+            seg[local, :3] = 0.0
+            seg[local, 3:] = rng.uniform([-0.1, -0.1, 0.2], [0.1, 0.1, 0.5], (int(local.sum()), 3))
+            op.update(links=links, segments=seg)
         # checkpoint, restore, episode_reset, set_camera_default: the kind says it all
+        return op
+
+    def table(self, cls):
+        """a set_distance_pairs record of class `cls`: 'default' (the table of Session.setup, no cull), 'one' pair, the step's own
+        'collision' table, or 'full': 96 pairs; pairs by name, only of objects the handle has; the others with or without a cull"""
+        rng, nobj = self.rng, self.nobj
+        md = None if cls == 'default' or rng.random() < 0.4 else float(np.float32(rng.uniform(0.05, 0.25)))
+        if cls == 'default':
+            pairs = default_pairs(nobj)
+        elif cls == 'collision':
+            pairs = 'collision'
+        else:
+            names = ROBOT_SHAPES + STATIC_SHAPES + OBJECT_SHAPES[:nobj]
+            pairs = []
+            while len(pairs) < (1 if cls == 'one' else 96):
+                a, b = (int(i) for i in rng.integers(len(names), size=2))
+                if a != b and not (a >= len(ROBOT_SHAPES) and b >= len(ROBOT_SHAPES) and max(a, b) < len(ROBOT_SHAPES) + 3):      # (not two statics)
+                    pairs.append((names[a], names[b]))
+        return dict(kind='set_distance_pairs', cls=cls, pairs=pairs, max_distance=md)
+
+    def postures(self, K):
+        """float32 [N, K, 11], every [:, k] a draw of rows()['q']"""
+        return np.ascontiguousarray(np.stack([self.rows()['q'] for _ in range(K)], axis=1))
+
+    def query(self, kind, compared):
+        """a query observer's record: K cycles through {1, 3, 32}; postures as rows()['q'], segments between two of them, IK goals
+        such postures (the Session turns them into tool poses at the point in force) and seeds the goals plus U(-0.3, 0.3)"""
+        rng = self.rng
+        op = dict(kind=kind, compared=bool(compared))
+        if kind in ('closest_points', 'signed_distance'):
+            return op
+        K = int(Q_KS[(self.n_query + self.salt) % 3])
+        self.n_query += 1
+        family = 'ik' if kind.startswith('posture_ik') else kind
+        n = self.n_kind[family] = self.n_kind.get(family, -1) + 1      # safety, margin, position_only and clamp take turns
+        if kind in ('posture_clearance', 'signed_distance_at', 'posture_kinematics'):
+            op.update(postures=self.postures(K))
+        elif kind == 'signed_distance_gradient':
+            op.update(postures=self.postures(K), margin=float(np.float32((0.03, 0.3, 0.0)[n % 3])))
+        elif kind == 'swept_clearance':
+            op.update(segments=np.ascontiguousarray(np.stack([self.postures(K), self.postures(K)], axis=2)),
+                      safety=float(np.float32((0.0, 0.01, 0.04)[n % 3])))
+        else:
+            goals = self.postures(K)
+            op.update(goals=goals, position_only=bool(n & 1), clamp=not n & 2,
+                      max_iterations=int(rng.choice([4, 16, 32])))
+            if kind == 'posture_ik':
+                seeds = goals.copy()
+                seeds[..., :7] += rng.uniform(-0.3, 0.3, seeds[..., :7].shape).astype(np.float32)
+                op.update(seeds=seeds)
         return op
 
     def launch(self, env, obj):
@@ -274,8 +412,145 @@ def _ordered(units, rng):
     return out
 
 
-def program(seed, N, nobj, length):
+def _query_program(seed, N, nobj, length):
+    """a query programme (the comment at Q_MIN_LENGTH): its own generator, so that the draws of the other programmes stay as they are"""
+    if length < Q_MIN_LENGTH:
+        raise ValueError("a query programme needs at least %d ops" % Q_MIN_LENGTH)
+    rng = np.random.default_rng([int(seed), int(N), int(nobj), int(length), 1])
+    salt = int(seed) % 7
+
+    def unit(mut, form=None, before=None, **kw):
+        return dict(mut=mut, form=int(rng.integers(3)) if form is None else int(form), before=before, behind=None, glue=None, fill=0, **kw)
+    forms = [int(f) for f in rng.permutation(3)]
+    classes = [str(c) for c in rng.permutation(['one', 'collision', 'full'])]
+    anchors = [unit('set_state'), unit('write_state', parts=15)]
+    glued = [dict(unit('set_distance_pairs', forms[k], cls='default'), glue=anchors[k]) for k in range(2)]
+    pairs = [unit('set_distance_pairs', forms[2], cls=classes[0])]
+    pairs += [unit(m, f) for m in ('set_kinematic_points', 'set_rays') for f in RENDER_FORMS]
+    pairs += [unit('checkpoint'), unit('save_snapshot')]
+    behind_state = ('write_state', 'fork_dev', 'load_snapshot', 'reset_dev', 'restore', 'set_object_poses', 'episode_reset')
+    triples = [unit(m, before=STATE_READERS[(i + salt) % 7], **({'parts': W_OBJ_POSE} if m == 'write_state' else {})) for i, m in enumerate(behind_state)]
+    triples += [unit('set_distance_pairs', before=PAIR_READERS[(salt + 3 * k) % 6], cls=classes[1 + k]) for k in range(2)]
+    triples += [unit('set_kinematic_points', before=o) for o in ('posture_ik_present', 'posture_kinematics', 'posture_ik')]
+    last = unit('write_state', before='posture_ik_present', parts=W_JOINT_POS)
+    hosts = pairs + anchors                   # every query observer once behind a pair, in front of the next unit's mutator
+    for o, k in zip(Q_OBSERVERS, rng.permutation(len(hosts))):
+        hosts[k]['behind'] = o
+    for _ in range(length - Q_MIN_LENGTH):
+        pairs[int(rng.integers(len(pairs)))]['fill'] += 1
+    todo = glued + pairs + triples
+    todo = [todo[i] for i in rng.permutation(len(todo))]
+    need = {'restore': 'checkpoint', 'load_snapshot': 'save_snapshot', 'episode_reset': 'reset_dev'}
+    order, seen = [], set()
+    while todo:
+        j = next(j for j, u in enumerate(todo) if need.get(u['mut']) is None or need[u['mut']] in seen)
+        u = todo.pop(j)
+        order += [u] + ([u['glue']] if u['glue'] else [])
+        seen.add(u['mut'])
+    order.append(last)
+    draw = _Draw(rng, N, nobj, salt=int(seed) % 4)
+    ops, n_seen, slot = [], {}, 0
+
+    def query(kind):
+        n = n_seen[kind] = n_seen.get(kind, 0) + 1
+        return draw.query(kind, (n + Q_OBSERVERS.index(kind) + salt) % 2 == 0)
+    for u in order:
+        mut = u['mut']
+        if mut == 'set_distance_pairs':
+            op = draw.table(u['cls'])
+        elif mut == 'write_state':
+            full = u['parts'] == 15
+            op = dict(kind=mut, parts=u['parts'], reset=False, fresh=full, rows=draw.rows(), mask=None if full else draw.mask())
+        else:
+            op = draw.mutator(mut)
+        if mut == 'save_snapshot':
+            slot = op['slot']
+        elif mut == 'load_snapshot':
+            op['slot'] = slot               # (a slot that has been saved)
+        ops.append(op)
+        if u['before'] is not None:
+            ops.append(query(u['before']))
+        ops.append(draw.step(u['form']))
+        ops += [draw.step(int(rng.integers(3))) for _ in range(u['fill'])]
+        if u['behind'] is not None:
+            ops.append(query(u['behind']))
+    assert len(ops) == length, (len(ops), length)
+    return ops
+
+
+def is_anchor(op):
+    """behind this op the state of every env is compose_state(op['rows']), known on the CPU"""
+    return op['kind'] == 'set_state' or (op['kind'] == 'write_state' and op['parts'] == 15 and op['fresh'] and op['mask'] is None)
+
+
+def check_query_conditions(ops, length, nobj):
+    """what a query programme drawn for a handle with `nobj` objects holds, asserted"""
+    assert len(ops) == length >= Q_MIN_LENGTH
+    kinds = [o['kind'] for o in ops]
+    muts = set(MUTATORS) | set(Q_MUTATORS)
+    assert set(kinds) <= set(STEP_KINDS) | muts | set(Q_OBSERVERS)
+    for m in Q_MUTATORS:
+        forms = [b['render'] for a, b in zip(ops, ops[1:]) if a['kind'] == m and b['kind'] == 'step']
+        assert set(forms) == set(RENDER_FORMS) and len(forms) >= 3, (m, forms)
+    around = [(p, o, n) for p, o, n in zip(ops, ops[1:], ops[2:]) if o['kind'] in Q_OBSERVERS]
+    step_mut = {o['kind'] for p, o, n in around if p['kind'] in STEP_KINDS and n['kind'] in muts}
+    assert step_mut == set(Q_OBSERVERS), set(Q_OBSERVERS) - step_mut
+    for k in Q_OBSERVERS:
+        front = [p['kind'] for p, o, n in around if o['kind'] == k and p['kind'] in muts and n['kind'] in STEP_KINDS]
+        assert front and set(front) != {'write_state'}, (k, front)
+        assert {o['compared'] for o in ops if o['kind'] == k} == {False, True}, k
+    read = [(a, b['kind']) for a, b in zip(ops, ops[1:]) if b['kind'] in STATE_READERS]
+    for m in READ_BEHIND:
+        assert any(a['kind'] == m for a, _ in read), m
+    assert any(a['kind'] == 'write_state' and a['parts'] & W_OBJ_POSE and not is_anchor(a) for a, _ in read)
+    assert any(a['kind'] == 'write_state' and a['parts'] & W_JOINT_POS and not is_anchor(a) for a, _ in read)
+    assert any(a['kind'] == 'set_distance_pairs' and b in PAIR_READERS for a, b in read)
+    assert any(a['kind'] == 'set_kinematic_points' and b == 'posture_ik_present' for a, b in read)
+    # the draws
+    K = {o[key].shape[1] for o in ops for key in ('postures', 'segments', 'goals') if o['kind'] in Q_OBSERVERS and key in o}
+    assert K == set(Q_KS), K
+    tables = [o for o in ops if o['kind'] == 'set_distance_pairs']
+    assert {o['cls'] for o in tables} == set(Q_PAIR_CLASSES)
+    assert any(o['max_distance'] is None for o in tables) and any(o['max_distance'] is not None for o in tables)
+    assert all(o['max_distance'] is None or 0.05 <= o['max_distance'] <= 0.25 for o in tables)
+    for o in tables:
+        want = {'one': 1, 'full': 96}.get(o['cls'])
+        assert (o['pairs'] == 'collision') == (o['cls'] == 'collision') and (o['cls'] != 'default' or o['pairs'] == default_pairs(nobj))
+        assert want is None or len(o['pairs']) == want
+        if o['pairs'] != 'collision':
+            assert all(a != b and {a, b} <= set(ROBOT_SHAPES + STATIC_SHAPES + OBJECT_SHAPES[:nobj]) for a, b in o['pairs'])
+    points = [o for o in ops if o['kind'] == 'set_kinematic_points']
+    assert all(1 <= len(o['links']) <= 8 and o['local'].shape == (len(o['links']), 3) and (np.abs(o['local']) >= 0.01).all() for o in points)
+    assert any(set(o['links'].tolist()) & set(FINGER_LINKS) for o in points) and any(set(o['links'].tolist()) & set(ARM_LINKS) for o in points)
+    assert any(o['links'][-1] in FINGER_LINKS for o in points) and any(o['links'][-1] in ARM_LINKS for o in points)
+    rays = [o for o in ops if o['kind'] == 'set_rays']
+    assert {len(o['links']) for o in rays} == set(Q_RAY_COUNTS)
+    assert any((o['links'] < 0).any() and (o['links'] >= 0).any() for o in rays)
+    for key, kind in (('safety', 'swept_clearance'), ('margin', 'signed_distance_gradient'), ('position_only', 'posture_ik'), ('clamp', 'posture_ik')):
+        assert len({o[key] for o in ops if o['kind'] in (kind, kind + '_present')}) >= 2, key
+    # what a unit needs, and the anchors: the state a record defines, with the default table in force
+    for i, k in enumerate(kinds):
+        assert k != 'restore' or 'checkpoint' in kinds[:i]
+        assert k != 'episode_reset' or 'reset_dev' in kinds[:i]
+        assert k != 'load_snapshot' or any(o['kind'] == 'save_snapshot' and o['slot'] == ops[i]['slot'] for o in ops[:i])
+    table, n_anchor = ('default', None), set()
+    for o in ops:
+        if o['kind'] == 'set_distance_pairs':
+            table = (o['cls'], o['max_distance'])
+        if is_anchor(o):
+            assert table == ('default', None), table
+            n_anchor.add(o['kind'])
+        for key in ('mask', 'flags'):
+            if o.get(key) is not None:
+                assert np.asarray(o[key]).any(), (o['kind'], key)
+    assert n_anchor == {'set_state', 'write_state'}
+    return dict(count={m: kinds.count(m) for m in muts | set(Q_OBSERVERS)})
+
+
+def program(seed, N, nobj, length, queries=False):
     """list of `length` op records (dicts with a 'kind'); the same arguments give the same programme"""
+    if queries:
+        return _query_program(seed, N, nobj, length)
     if length < MIN_LENGTH:
         raise ValueError("a programme needs at least %d ops" % MIN_LENGTH)
     rng = np.random.default_rng([int(seed), int(N), int(nobj), int(length)])
@@ -422,6 +697,10 @@ class Session:
         self.refused = 0
         self.episode = np.zeros(self.N, np.int32)        # the host route's count of auto-resets per env
         self.final_obs = np.zeros((self.N, 13 + 7 * self.nobj + 1), np.float32)
+        # the query tables in force, as the Session has set them (a fresh handle: the gripper base at its origin, no pairs, no rays)
+        self.points = (np.array([8], np.int32), np.zeros((1, 3), np.float32))
+        self.max_distance, self.n_rays = None, 0
+        self.last = {}                      # result buffers (FAMILY) -> the query record whose call wrote them last
 
     def setup(self):
         """what both handles get behind the warm-up: the ray table, snapshot slots, goals, the episode rule, a first checkpoint"""
@@ -431,6 +710,7 @@ class Session:
         seg[:N_WORLD_RAYS] = [[BASE[o % 3][0], BASE[o % 3][1], 1.0, BASE[o % 3][0], BASE[o % 3][1], 0.2] for o in range(N_WORLD_RAYS)]
         seg[N_WORLD_RAYS:, 5] = 0.4
         env.set_rays([-1] * N_WORLD_RAYS + [nat.EE_LINK] * N_LINK_RAYS, seg)
+        self.n_rays = N_WORLD_RAYS + N_LINK_RAYS
         env.snapshot_slots(N_SLOTS)
         self.goals = goal_table(self.nobj, env.W, env.H)
         env.set_goals(*self.goals)
@@ -438,6 +718,7 @@ class Session:
         env.set_env_goals(self.goal_index)
         env.set_episode(HORIZON, GOAL_STRIDE)
         self.ckpts.append(env.checkpoint())
+        env.set_distance_pairs(default_pairs(self.nobj))   # (a setting of the handle: resets, forks and restore keep it)
 
     def release(self):
         self.keep.clear()
@@ -671,6 +952,112 @@ class Session:
     def _sync_observations(self, op):
         if self._observe(op):
             self.env.sync_observations()
+
+    # ---- the query tables: settings of the handle, host calls on every road
+    def _set_distance_pairs(self, op):
+        self.env.set_distance_pairs(op['pairs'], op['max_distance'])
+        self.max_distance = op['max_distance']
+        for f in ('dist', 'pc', 'sd', 'sg', 'sw'):      # (laid out by the Q in force: an earlier record's results can no longer be read)
+            self.last.pop(f, None)
+
+    def _set_kinematic_points(self, op):
+        self.env.set_kinematic_points(op['links'].tolist(), op['local'])
+        self.points = (op['links'], op['local'])
+        self.last.pop('pk', None)                       # (laid out by the P in force)
+
+    def _set_rays(self, op):
+        self.env.set_rays(op['links'].tolist(), op['segments'])
+        self.n_rays = len(op['links'])
+
+    # ---- query observers: A makes every call, with device tensors; B the compared ones, with host arrays
+    def _asks(self, op):
+        """whether this road makes the record's call; notes which result buffers it writes"""
+        if self.road == 'host' and not op['compared']:
+            return False
+        for f in FAMILY[op['kind']]:
+            self.last[f] = op
+        return True
+
+    def _q(self, a):
+        return a if self.road == 'host' else self._d(a)
+
+    def margin(self, m):
+        """a gradient's margin may not exceed the cull of the table in force"""
+        return m if self.max_distance is None else min(m, self.max_distance)
+
+    def ik_targets(self, goals):
+        """float32 [N, K, 7]: the float64 tool pose (tests/numpy_pik.py) of the goal postures at the LAST point in force"""
+        from tests import numpy_pik as npk
+        from tests.numpy_kinematics import mat_to_quat
+        Re, x, _ = npk.tool_frame(goals.astype(np.float64), int(self.points[0][-1]), self.points[1][-1].astype(np.float64))
+        return np.ascontiguousarray(np.concatenate([x, mat_to_quat(Re)], -1).astype(np.float32))
+
+    def _closest_points(self, op):
+        if self._asks(op):
+            self.env.closest_points()
+
+    def _posture_clearance(self, op):
+        if self._asks(op):
+            self.env.posture_clearance(self._q(op['postures']))
+
+    def _signed_distance(self, op):
+        if self._asks(op):
+            self.env.signed_distance()
+
+    def _signed_distance_at(self, op):
+        if self._asks(op):
+            self.env.signed_distance(self._q(op['postures']))
+
+    def _signed_distance_gradient(self, op):
+        if self._asks(op):
+            self.env.signed_distance_gradient(self._q(op['postures']), margin=self.margin(op['margin']))
+
+    def _swept_clearance(self, op):
+        if self._asks(op):
+            self.env.swept_clearance(self._q(op['segments']), safety=op['safety'])
+
+    def _posture_kinematics(self, op):
+        if self._asks(op):
+            self.env.posture_kinematics(self._q(op['postures']))
+
+    def _posture_ik(self, op):
+        if self._asks(op):
+            seeds = self._q(op['seeds']) if 'seeds' in op else None
+            self.env.posture_ik(self._q(self.ik_targets(op['goals'])), seeds, point=len(self.points[0]) - 1, max_iterations=op['max_iterations'],
+                                position_only=op['position_only'], clamp=op['clamp'])
+
+    _posture_ik_present = _posture_ik
+
+
+ANCHOR_ENVS = 4
+
+
+def anchor_references(op, nobj, probe_q):
+    """The float64 restatements on the state a record defines (is_anchor), for the first ANCHOR_ENVS envs, the
+    default pair table and the probe's arguments: (state, pairs, reference at the present joints, reference at the probe's
+    postures).  tests/test_session_program.py asserts the decided share of both for the very records of q70 and q5."""
+    from tests import numpy_distance as nd
+    from tests import numpy_posture as npo
+    names = nd.names()
+    pairs = np.array([(names[x], names[y]) for x, y in default_pairs(nobj)], np.int32)
+    st = compose_state(op['rows'], nobj)[:ANCHOR_ENVS]
+    return st, pairs, nd.reference(st, pairs), nd.reference(npo.rows(st, probe_q['postures'][:len(st)]), pairs)
+
+
+def probe_arguments(N, nobj):
+    """the fixed arguments of the queries a comparison calls (tests/test_gpu_session.py), as host arrays: K = 2 postures, 2 segments
+    and 2 IK targets per env -- the tool poses of two postures at the point of a fresh handle -- with their seeds"""
+    from tests import numpy_pik as npk
+    from tests.numpy_kinematics import mat_to_quat
+    d = _Draw(np.random.default_rng([98, N]), N, nobj)
+    po, goals = d.postures(PROBE_K), d.postures(PROBE_K)
+    seg = np.ascontiguousarray(np.stack([d.postures(PROBE_K), d.postures(PROBE_K)], axis=2))
+    seg[:, :, 1] = seg[:, :, 0] + np.float32(0.25) * (seg[:, :, 1] - seg[:, :, 0])      # the first quarter of the way: the advancement's
+    seeds = goals.copy()                                                                 # steps are most of the probe's time
+    seeds[..., :7] += d.rng.uniform(-0.3, 0.3, seeds[..., :7].shape).astype(np.float32)
+    Re, x, _ = npk.tool_frame(goals.astype(np.float64))
+    targets = np.ascontiguousarray(np.concatenate([x, mat_to_quat(Re)], -1).astype(np.float32))
+    return dict(postures=po, segments=seg, targets=targets, seeds=seeds)
 
 
 def run(env, ops, road, to_device=torch_device, setup=True):

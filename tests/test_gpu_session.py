@@ -23,7 +23,23 @@ Three things are not a plain A == B:
 Both handles start from the 60-step run of tests/test_gpu_fork.py, which has contact history.
 
 Beside the three sizes: the 70-env programme twice on the default handle for one digest per op; once more with no wait of the test's
-between comparisons; and, for every mutator kind, the proof that the compared fields move when the call is made."""
+between comparisons; and, for every mutator kind, the proof that the compared fields move when the call is made.
+
+The read-only batch queries.  Every comparison -- of all of the above -- also makes the nine query calls on the handle (QUERIES:
+closest_points, posture_clearance, signed_distance at the present state and at postures, signed_distance_gradient, swept_clearance,
+posture_kinematics, posture_ik with and without seeds) with small fixed arguments (session_program.probe_arguments: 2 postures, 2
+segments, 2 targets per env, 8 IK iterations; CUDA tensors on the device road, host arrays on the host road), the pair, point and ray
+tables whatever the handle has at that moment, and compares every output column.  Two more sessions, q70 and q5, run a QUERY
+programme: the three tables change in the middle of the run, and query records with their own arguments (1, 3 or 32 rows per env)
+stand directly behind device-side forks, snapshot loads, masked writes, resets, auto-resets and restores and directly in front of the
+next step.  A `compared` record is made by B too, from host arrays, and the result buffers are compared as that call left them; a
+silent one is A's alone, and the next comparison shows that it changed nothing.  What a bit compare cannot see -- an error both roads
+share -- the float64 anchor does: behind a set_state and a full write_state the state is known on the CPU, and A's probe outputs
+are held against the float64 restatements of tests/numpy_distance.py, numpy_posture.py, numpy_kinematics.py and numpy_pik.py within
+the bounds of their own GPU tests (`_anchor`).  Invariants asserted on the way: the candidate queries (posture_kinematics, posture_ik
+with seeds) give the same bits at every comparison between two set_kinematic_points; posture_ik without seeds changes only in envs
+whose joints changed; the three table mutators move query and ray outputs and nothing else; a write of the object poses alone, or of
+the joints alone, moves every probe output that reads them."""
 import hashlib
 import time
 
@@ -43,6 +59,7 @@ STATE_FIELDS = dict(touch=nat.F_TOUCH, count=nat.F_CONTACT_COUNT, errflags=nat.F
                     obj_pose=nat.F_OBJ_POSE)
 IMAGE_FIELDS = dict(rgb=nat.F_RGB, depth=nat.F_DEPTH, mask=nat.F_MASK)
 _cache = {}
+_spent = {'queries': 0.0}     # wall time of the query probes of the comparisons, reported beside every session's time
 
 
 def _make(monkeypatch, env_vars, *args, **kw):
@@ -58,8 +75,20 @@ def _make(monkeypatch, env_vars, *args, **kw):
 def _program(name):
     if name not in _cache:
         seed, N, nobj, _, _, length = sp.SESSIONS[name]
-        _cache[name] = sp.program(seed, N, nobj, length)
+        _cache[name] = sp.program(seed, N, nobj, length, queries=name in sp.QUERY_SESSIONS)
     return _cache[name]
+
+
+def _took(t0):
+    q, _spent['queries'] = _spent['queries'], 0.0
+    return "%.1f s, %.1f s of it in the query probes of the comparisons" % (time.perf_counter() - t0, q)
+
+
+def _silent(op):
+    """an observer that B does not make: no comparison behind it, the next one shows whether A's call changed anything"""
+    if op['kind'] in sp.Q_OBSERVERS:
+        return not op['compared']
+    return op['kind'] in sp.OBSERVERS and op['kind'] != 'episode_peek'
 
 
 def _warm_up(envs, N):
@@ -93,6 +122,50 @@ class _Probe:
         self.segments_dev = sp.torch_device(self.segments)
         g = d.observer('evaluate_goals')
         self.goal_pos, self.goal_mask = g['goal_pos'], (np.arange(N * nobj).reshape(N, nobj) % 3 != 0).astype(np.uint8)
+        # per-env segments for every size of the ray table a programme sets: the four above, their first, sixteen shifted copies
+        wide = np.tile(self.segments, (1, 16, 1)) + (np.arange(64) // 4 * np.float32(0.004)).astype(np.float32)[None, :, None]
+        self.rays = {1: np.ascontiguousarray(self.segments[:, :1]), 4: self.segments, 64: np.ascontiguousarray(wide.astype(np.float32))}
+        self.rays_dev = {R: self.segments_dev if R == 4 else sp.torch_device(a) for R, a in self.rays.items()}
+        self.q = sp.probe_arguments(N, nobj)
+        self.q_dev = {k: sp.torch_device(a) for k, a in self.q.items()}
+
+
+QUERIES = ('closest_points()', 'posture_clearance(po)', 'signed_distance()', 'signed_distance(po)', 'signed_distance_gradient(po)',
+           'swept_clearance(seg)', 'posture_kinematics(po)', 'posture_ik(targets, seeds)', 'posture_ik(targets)')
+READS_JOINTS = ('closest_points()', 'signed_distance()', 'posture_ik(targets)')
+# the fields that the query tables move: the nine above, the rays, and the points of the kinematic observations
+TABLE_FIELDS = QUERIES + ('ray_cast', 'kinematic.point_', 'kinematic.jacobian')
+
+
+def _queries(env, sess, probe):
+    """the nine query calls with the probe's arguments -- device tensors on the device road, host arrays on the host road --, the
+    tables whatever the handle has at the moment, the IK at the last point: {'call.column': host array}"""
+    q = probe.q if sess.road == 'host' else probe.q_dev
+    ik = dict(point=len(sess.points[0]) - 1, max_iterations=sp.PROBE_ITERATIONS, host=True)
+    grad = lambda: {k: v for k, v in env.signed_distance_gradient(q['postures'], margin=sess.margin(sp.PROBE_MARGIN), host=True).items()
+                    if k in ('gradient', 'cost', 'cost_gradient', 'pair_distance')}      # (the rest are signed_distance's bytes once more)
+    calls = (lambda: env.closest_points(host=True), lambda: env.posture_clearance(q['postures'], host=True), lambda: env.signed_distance(host=True),
+             lambda: env.signed_distance(q['postures'], host=True), grad, lambda: env.swept_clearance(q['segments'], host=True),
+             lambda: env.posture_kinematics(q['postures'], host=True), lambda: env.posture_ik(q['targets'], q['seeds'], **ik),
+             lambda: env.posture_ik(q['targets'], **ik))
+    return {name + '.' + k: np.array(v) for name, call in zip(QUERIES, calls) for k, v in call().items()}
+
+
+_RAW = {'dist': ('distance_buffer', nat.DIST_FIELDS), 'pc': ('posture_buffer', nat.PC_FIELDS), 'sd': ('signed_buffer', nat.SD_FIELDS),
+        'sg': ('signed_gradient_buffer', nat.SG_FIELDS), 'sw': ('sweep_buffer', nat.SW_FIELDS), 'pk': ('posture_kinematics_buffer', nat.PK_FIELDS),
+        'pik': ('posture_ik_buffer', nat.PIK_FIELDS)}
+
+
+def _results(env, sess, families):
+    """the result buffers of the query records that wrote them last, as their own calls left them: {'family.buffer': host array}.
+    Two buffers are written at the present state only (RR_SD_POINTS, RR_SG_PAIR_GRADIENT): they are read behind such a call alone."""
+    d = {}
+    for f in families:
+        present = sess.last[f]['kind'] == 'signed_distance'
+        for name in _RAW[f][1]:
+            if (f, name) not in (('sd', 'points'), ('sg', 'pair_gradient')) or (f == 'sd' and present):
+                d[f + '.' + name] = getattr(env, _RAW[f][0])(name, host=True)
+    return d
 
 
 def _collect(env, sess, probe, img_envs, contact_envs, images=True):
@@ -108,8 +181,11 @@ def _collect(env, sess, probe, img_envs, contact_envs, images=True):
         d['episode.episode'], d['episode.final_obs'] = sess.episode.copy(), sess.final_obs.copy()
     for k, v in env.ray_cast(host=True).items():
         d['ray_cast().' + k] = v
-    for k, v in env.ray_cast(probe.segments if sess.road == 'host' else probe.segments_dev, host=True).items():
+    for k, v in env.ray_cast((probe.rays if sess.road == 'host' else probe.rays_dev)[sess.n_rays], host=True).items():
         d['ray_cast(rays).' + k] = v
+    t0 = time.perf_counter()
+    d.update(_queries(env, sess, probe))
+    _spent['queries'] += time.perf_counter() - t0
     for k, v in env.kinematic_observations(host=True).items():
         d['kinematic.' + k] = v
     for k, v in env.contact_observations(host=True).items():
@@ -141,6 +217,8 @@ def _assert_equal(a, b, i, ops, what, envs_of=None, skip=()):
     for k in a:
         if k in skip or k not in b:
             continue
+        if not isinstance(a[k], list) and a[k].shape != b[k].shape:        # (a table of another size on one side)
+            raise AssertionError("%s: %s: field %s has shape %s against %s" % (_where(i, ops), what, k, a[k].shape, b[k].shape))
         bad = _differing(a[k], b[k])
         if bad.size:
             sel = envs_of.get(k) if envs_of else None
@@ -165,7 +243,7 @@ class _Twin:
 
     def __init__(self, monkeypatch, name, road_a='device', twin=True):
         _, N, nobj, W, H, _ = sp.SESSIONS[name]
-        self.N, self.ops = N, _program(name)
+        self.name, self.N, self.ops = name, N, _program(name)
         self.A = BatchedREALRobotEnv(N, objects=nobj, width=W, height=H)
         self.B = _make(monkeypatch, PLAIN, N, objects=nobj, width=W, height=H) if twin else None
         self.envs = [e for e in (self.A, self.B) if e is not None]
@@ -193,22 +271,115 @@ class _Twin:
         return _collect(self.B, self.sb, self.probe, self.img_envs, self.contact_envs, images=images)
 
 
-def _run_twin(tw, counts=None):
+def _anchor(tw, op, a, i, figures):
+    """Behind a set_state, and behind a write_state of all four column groups with `fresh` and no mask, the state of every env is
+    compose_state(rows), known on the CPU: A's probe outputs of the first four envs against the float64 restatements the project has,
+    within the bounds of those restatements' own GPU tests (imported, not restated).  The default pair table is in force there
+    (check_query_conditions).  The recipe states hold no overlapping pair -- the objects hang 3 to 15 cm above the table, 30 cm apart
+    --: the overlapping regime stays with tests/test_gpu_signed_distance.py and with the bit compare against the twin.  The only
+    omission is what the reference leaves undecided (within numpy_distance.DECIDE of touching); at least 95 % are decided."""
+    from tests import numpy_distance as nd
+    from tests import numpy_kinematics as nk
+    from tests import numpy_pik as npk
+    from tests import numpy_posture as npo
+    from tests.test_gpu_distance import TOL as TOL_DISTANCE
+    from tests.test_gpu_kinematic_obs import TOL_JV, TOL_JW, TOL_POS, TOL_QUAT, _align
+    from tests.test_gpu_posture_ik import TOL_Q
+    from tests.test_gpu_posture_kinematics import _figures as pk_figures, _reference as pk_reference
+    from tests.test_gpu_posture_query import TOL as TOL_POSTURE
+    where, n, nobj = _where(i, tw.ops), min(sp.ANCHOR_ENVS, tw.N), tw.sa.nobj
+    assert (tw.A.distance_pairs()[1] == 0.0) and len(tw.A.distance_pairs()[0]) == len(sp.default_pairs(nobj)), where
+    st, pairs, ref, ref_po = sp.anchor_references(op, nobj, tw.probe.q)
+    cols = sp.part_columns(15, nobj)
+    assert (_bits(a['state'][:, cols]) == _bits(sp.compose_state(op['rows'], nobj)[:, cols])).all(), "%s: the state is not the record's" % where
+    fig = {}
+
+    def judge(name, f, fails, decided, items):
+        print("anchor %s %s %s: %s %s" % (tw.name, where.split(';')[0], name, {k: (float('%.3g' % v) if isinstance(v, float) else v) for k, v in f.items()}, fails))
+        assert not fails, (where, name, fails)
+        assert decided >= 0.95 * items and f.get('overlapping', 0) == 0, (where, name, decided, items)
+        fig[name] = f['distance_error']
+    cut = lambda call, **keys: {k: a[call + '.' + v][:n] for k, v in keys.items()}
+    same = {k: k for k in ('distance', 'lower', 'point_a', 'point_b', 'normal', 'status')}
+    f, fails = nd.compare(cut('closest_points()', **same), ref, TOL_DISTANCE, pairs)
+    judge('closest_points', f, fails, f['decided'], f['items'])
+    f, fails = nd.compare(cut('signed_distance()', distance='pair_distance', lower='pair_bound', point_a='pair_point_a', point_b='pair_point_b',
+                              normal='pair_normal', status='pair_status'), ref, TOL_DISTANCE, pairs)
+    judge('signed_distance', f, fails, f['decided'], f['items'])
+    out = {k[len('posture_clearance(po).'):]: v[:n].reshape((-1,) + v.shape[2:]) for k, v in a.items() if k.startswith('posture_clearance(po).')}
+    f, fails = npo.compare(out, ref_po, TOL_POSTURE, pairs)
+    judge('posture_clearance', f, fails, f['decided'], f['items'])
+    # link poses of the present state and of the candidates, the points in force
+    links, local = tw.sa.points[0].tolist(), tw.sa.points[1].astype(np.float64)
+    kin = nk.observations(st, links, local)
+    lp = a['kinematic.link_pose'][:n].astype(np.float64)
+    fig['link_pos'] = float(np.abs(lp[..., :3] - kin['link_pos']).max())
+    fig['link_quat'] = float(np.abs(_align(lp[..., 3:], kin['link_quat']) - kin['link_quat']).max())
+    fig['point_pos'] = float(np.abs(a['kinematic.point_pos'][:n] - kin['point_pos']).max())
+    pk = pk_figures({k: a['posture_kinematics(po).' + k][:n] for k in nat.PK_FIELDS}, pk_reference(tw.probe.q['postures'][:n], links, local))
+    fig.update({'pk_' + k: float(v) for k, v in pk.items()})
+    assert fig['link_pos'] < TOL_POS and fig['point_pos'] < TOL_POS and fig['link_quat'] < TOL_QUAT, (where, fig)
+    assert fig['pk_link_pos'] < TOL_POS and fig['pk_point_pos'] < TOL_POS and fig['pk_link_quat'] < TOL_QUAT, (where, fig)
+    assert fig['pk_jac_lin'] < TOL_JV and fig['pk_jac_ang'] < TOL_JW, (where, fig)
+    # the IK lands where the float64 iteration lands: rows with the same number of updates, and the clear-cut rows converge
+    K = tw.probe.q['targets'].shape[1]
+    present = np.ascontiguousarray(np.broadcast_to(st[:, None, :11], (n, K, 11)))
+    for call, seeds in (('posture_ik(targets, seeds)', tw.probe.q['seeds'][:n]), ('posture_ik(targets)', present)):
+        want = npk.solve(tw.probe.q['targets'][:n].reshape(-1, 7), seeds.reshape(-1, 11), links[-1], local[-1], max_iterations=sp.PROBE_ITERATIONS)
+        q, status, it = (a[call + '.' + k][:n].reshape((n * K,) + a[call + '.' + k].shape[2:]) for k in ('posture', 'status', 'iterations'))
+        clear = (want['status'] == 0) & (want['iterations'] <= npk.CLEAR_CUT)
+        count = it == want['iterations']
+        assert count.any() and (status[clear] == 0).all(), (where, call, status, want['status'])
+        fig[call] = float(np.abs(q.astype(np.float64) - want['posture']).max(-1)[count].max())
+        assert fig[call] <= TOL_Q, (where, call, fig[call])
+    print("anchor %s %s: %s" % (tw.name, where.split(';')[0], {k: float('%.3g' % v) for k, v in fig.items()}))
+    for k, v in fig.items():
+        figures[k] = max(figures.get(k, 0.0), v)
+    figures['anchors'] = figures.get('anchors', 0) + 1
+
+
+def _compare_results(tw, i, what):
+    """the result buffers that the same query record wrote last on A and on B (a compared record: A from device tensors, B from
+    host arrays), bit for bit, before the probe's calls of a comparison overwrite them"""
+    both = [f for f in tw.sa.last if tw.sb.last.get(f) is tw.sa.last[f]]
+    if both:
+        _assert_equal(_results(tw.A, tw.sa, both), _results(tw.B, tw.sb, both), i, tw.ops,
+                      "%s, the buffers of %s" % (what, ', '.join(sorted({tw.sa.last[f]['kind'] for f in both}))))
+    tw.sa.last.clear()
+    tw.sb.last.clear()
+
+
+def _run_twin(tw, counts=None, figures=None):
     """the programme on A and B with a comparison behind every op; returns the number of comparisons"""
     ops, compared = tw.ops, 0
     before = tw.collect_a()
     _assert_equal(before, tw.collect_b(True), 0, ops, "before the programme, A against B", tw.envs_of)
+    since_points = before
     for i, op in enumerate(ops):
         tw.sa.apply(op)
         tw.sb.apply(op)
-        if op['kind'] in sp.OBSERVERS and op['kind'] != 'episode_peek':
+        if _silent(op):
             continue                        # B made no call: the next comparison shows whether A's changed anything
+        _compare_results(tw, i, "A against B")
         a = tw.collect_a()
         stepped = sp.is_step(op)
         _assert_equal(a, tw.collect_b(stepped), i, ops, "A against B", tw.envs_of)
         if not stepped:
             _assert_equal(a, before, i, ops, "A's images against A's own of before the call", tw.envs_of, skip=[k for k in a if not k.startswith('image.')])
         _check_mirrors(tw.A, tw.sa, tw.mirror, tw.img_mirror, a, tw.img_envs, i, ops)
+        # what the header says of the candidate queries: tensors, model and points alone; without seeds, the joints besides
+        if op['kind'] == 'set_kinematic_points':
+            since_points = a
+        _assert_equal(a, since_points, i, ops, "a candidate query against its own output since the last set_kinematic_points", None,
+                      skip=[k for k in a if not k.startswith(('posture_kinematics(po).', 'posture_ik(targets, seeds).'))])
+        if op['kind'] != 'set_kinematic_points':
+            same = ~(_bits(a['state'][:, :11]) != _bits(before['state'][:, :11])).any(axis=1)
+            for k in a:
+                if k.startswith('posture_ik(targets).') and same.any():
+                    bad = _differing(a[k][same], before[k][same])
+                    assert bad.size == 0, "%s: %s changed in envs whose joints did not: %s" % (_where(i, ops), k, np.flatnonzero(same)[bad][:16].tolist())
+        if figures is not None and sp.is_anchor(op):
+            _anchor(tw, op, a, i, figures)
         compared += 1
         before = a
         for s in (tw.sa, tw.sb):
@@ -239,7 +410,7 @@ def test_n70_against_the_plain_twin(monkeypatch):
     tw = _Twin(monkeypatch, 'n70')
     n = _run_twin(tw, counts)
     tw.close()
-    print("session n70: coverage %s; %d compared ops; %.1f s" % (counts, n, time.perf_counter() - t0))
+    print("session n70: coverage %s; %d compared ops; %s" % (counts, n, _took(t0)))
     assert counts['heavy'] > 0 and counts['auto_resets'] > 0 and counts['refused'] > 0 and counts['partial_auto_resets'] > 0, counts
 
 
@@ -249,7 +420,7 @@ def _run_alone(monkeypatch, road):
     digests = []
     for i, op in enumerate(tw.ops):
         tw.sa.apply(op)
-        if op['kind'] in sp.OBSERVERS and op['kind'] != 'episode_peek':
+        if _silent(op):
             continue
         digests.append((i, _digest(tw.collect_a())))
         tw.sa.release()
@@ -269,7 +440,7 @@ def test_n70_twice_the_same(monkeypatch):
     ops = _program('n70')
     for (i, want), (j, got) in zip(first, again):
         assert i == j and got == want, "%s: the second run of the default handle differs from the first" % _where(j, ops)
-    print("session n70, the second run: %d digests; %.1f s" % (len(again), time.perf_counter() - t0))
+    print("session n70, the second run: %d digests; %s" % (len(again), _took(t0)))
 
 
 def test_n5_one_chain_placement_one_object_wide_image(monkeypatch):
@@ -279,7 +450,7 @@ def test_n5_one_chain_placement_one_object_wide_image(monkeypatch):
     tw = _Twin(monkeypatch, 'n5')
     n = _run_twin(tw)
     tw.close()
-    print("session n5: %d compared ops; %.1f s" % (n, time.perf_counter() - t0))
+    print("session n5: %d compared ops; %s" % (n, _took(t0)))
 
 
 def test_n1100_packed_solve(monkeypatch):
@@ -289,7 +460,33 @@ def test_n1100_packed_solve(monkeypatch):
     tw = _Twin(monkeypatch, 'n1100')
     n = _run_twin(tw)
     tw.close()
-    print("session n1100: %d compared ops; %.1f s" % (n, time.perf_counter() - t0))
+    print("session n1100: %d compared ops; %s" % (n, _took(t0)))
+
+
+def _query_session(monkeypatch, name):
+    t0 = time.perf_counter()
+    figures = {}
+    tw = _Twin(monkeypatch, name)
+    n = _run_twin(tw, figures=figures)
+    tw.close()
+    made = {k: sum(o['kind'] == k and o['compared'] for o in tw.ops) for k in sp.Q_OBSERVERS}
+    print("session %s: %d compared ops, compared query records %s; anchors: worst figures %s; %s"
+          % (name, n, made, {k: float('%.3g' % v) for k, v in figures.items()}, _took(t0)))
+    assert figures['anchors'] == sum(sp.is_anchor(o) for o in tw.ops) >= 2
+
+
+def test_q70_against_the_plain_twin(monkeypatch):
+    """70 envs, 3 objects, 64 x 64, the query programme: the pair table, the kinematic points and the ray table change in the middle of
+    the run (1, 14, 92 and 96 pairs, with and without a cull; 1 to 8 points; 1, 4 and 64 rays), and the nine query calls stand directly
+    behind device-side forks, snapshot loads, masked writes, resets, auto-resets and restores and directly in front of the step after
+    them, with 1, 3 and 32 rows per env.  A compared record is made by B too, from host arrays, and its result buffers are compared bit
+    for bit as the call left them; a silent one by A alone.  Behind the set_state and the full write_state: the float64 anchor."""
+    _query_session(monkeypatch, 'q70')
+
+
+def test_q5_against_the_plain_twin(monkeypatch):
+    """5 envs, 1 object, 96 x 64, the query programme: the one-chain placement, tables that may only name the one object."""
+    _query_session(monkeypatch, 'q5')
 
 
 class _NullEnv:
@@ -309,14 +506,17 @@ class _NoMemory:
         return 0
 
 
-def test_n70_free_running_between_comparisons(monkeypatch):
+@pytest.mark.parametrize('name', ['n70', 'q70'])
+def test_free_running_between_comparisons(monkeypatch, name):
     """The comparisons above wait for the device behind every op, and B's host road waits inside its calls.  Here A runs the same
     70-env programme as a training loop would: every device argument is uploaded before the first op, and A makes the ops of a chunk
     -- up to the eighth compared op -- back to back before B makes its own, so A's calls on the library's stream follow each other
     with no wait but the library's own (a device-road write, fork, reset, observer or episode update is enqueued while the side
-    streams still work on the step before).  A call that relied on a wait would differ from B at the end of the chunk."""
+    streams still work on the step before).  A call that relied on a wait would differ from B at the end of the chunk.
+    q70: every posture, segment, target and seed tensor of every query record is uploaded beforehand too, the device road of a query
+    reads it in place and does not wait, and the result buffers that the chunk's last compared record of a kind wrote are compared."""
     t0 = time.perf_counter()
-    tw = _Twin(monkeypatch, 'n70')
+    tw = _Twin(monkeypatch, name)
     staged = []
     dry = sp.Session(_NullEnv(tw.A), 'device', to_device=lambda a: staged.append(np.array(a)) or _NoMemory())
     dry.setup()
@@ -332,7 +532,7 @@ def test_n70_free_running_between_comparisons(monkeypatch):
     compared, flushed, chunk = 0, 0, []
     for i, op in enumerate(tw.ops):
         chunk.append(op)
-        compared += not (op['kind'] in sp.OBSERVERS and op['kind'] != 'episode_peek')
+        compared += not _silent(op)
         if compared - flushed >= 8 or i == len(tw.ops) - 1:
             flushed = compared
             for o in chunk:
@@ -340,12 +540,13 @@ def test_n70_free_running_between_comparisons(monkeypatch):
             for o in chunk:
                 tw.sb.apply(o)
             chunk = []
+            _compare_results(tw, i, "A (free running) against B")
             a = tw.collect_a()
             _assert_equal(a, tw.collect_b(True), i, tw.ops, "A (free running) against B", tw.envs_of)
             _check_mirrors(tw.A, tw.sa, tw.mirror, tw.img_mirror, a, tw.img_envs, i, tw.ops)
     assert not staged
     tw.close()
-    print("session n70, free running: %d compared ops, a comparison behind every eighth; %.1f s" % (compared, time.perf_counter() - t0))
+    print("session %s, free running: %d compared ops, a comparison behind every eighth; %s" % (name, compared, _took(t0)))
 
 
 def _first(ops, kind, **want):
@@ -360,7 +561,10 @@ def test_every_mutator_moves_the_next_step():
     load_snapshot of its slot; checkpoint a step, a checkpoint and a restore (of the checkpoint before last); plan_macro 101
     step_plan calls in place of the step -- rows 0..99 of every plan go to the same posture whatever the macro action, so a new plan
     shows from row 100 on (in the programmes above a plan_macro is therefore a call that must change nothing yet).
-    select_image_mirror moves A's mapped image mirror: the deselected block keeps the old frame."""
+    select_image_mirror moves A's mapped image mirror: the deselected block keeps the old frame.
+    The three table mutators (their first records of the q70 programme; for set_distance_pairs the first that is not the default
+    table) are a class of their own: every field they move is a query or ray output, at least one of their own calls moves, and no
+    state or image field does.  Last, on one of the two handles: _state_writes_move_the_probe."""
     name = 'n70'
     _, N, nobj, W, H, _ = sp.SESSIONS[name]
     ops = _program(name)
@@ -375,12 +579,14 @@ def test_every_mutator_moves_the_next_step():
     prefix = [step[0], dict(kind='checkpoint'), plan, camera, step[1]]
     step_plan = dict(kind='step_plan', idle=np.zeros(N, np.uint8), render=1, flags=None)
     everyone = np.arange(N)
-    for kind in sp.MUTATORS:
-        op = _first(ops, kind)
+    q_ops = _program('q70')                 # (the same handle size: the records of the three table mutators come from there)
+    for kind in sp.MUTATORS + sp.Q_MUTATORS:
+        op = _first(ops, kind) if kind in sp.MUTATORS else next(o for o in q_ops if o['kind'] == kind and o.get('cls') != 'default')
         got = []
         for env, with_op, mir in ((X, True, mirrors[0]), (Y, False, mirrors[1])):
             env.restore(base)
             env.set_env_appearance()
+            env.set_kinematic_points([nat.EE_LINK])       # (the tables are settings: a restore keeps them; setup puts back the other two)
             s = sp.Session(env, 'device')
             s.setup()
             env.set_episode(24, sp.GOAL_STRIDE)           # (every env is past it: an auto-reset here resets them all)
@@ -403,12 +609,40 @@ def test_every_mutator_moves_the_next_step():
             got.append(d)
             s.release()
         # (the episode counter and the final observation outlive the set-up: X alone has the auto-reset of an earlier kind in them)
-        moved = [k for k in got[0] if _differing(got[0][k], got[1][k]).size
+        reshaped = lambda k: not isinstance(got[0][k], list) and got[0][k].shape != got[1][k].shape      # (a table of another size)
+        moved = [k for k in got[0] if (reshaped(k) or _differing(got[0][k], got[1][k]).size)
                  and (kind == 'episode_reset' or k not in ('episode.episode', 'episode.final_obs'))]
         assert moved, "%s moves none of the compared fields" % kind
         if kind in sp.IMAGE_ONLY:
             assert all(k.startswith(('image.', 'mirror.')) for k in moved), (kind, moved)
+        elif kind in sp.Q_MUTATORS:             # a class of their own: query and ray outputs move, no state or image field does
+            assert all(k.startswith(TABLE_FIELDS) for k in moved), (kind, moved)
+            own = {'set_distance_pairs': QUERIES[:6], 'set_kinematic_points': QUERIES[6:] + ('kinematic.point_',), 'set_rays': ('ray_cast',)}[kind]
+            assert any(k.startswith(own) for k in moved), (kind, moved)
         elif kind not in ('set_env_goals',):
             assert 'state' in moved or 'contacts(i)' in moved, (kind, moved)
+    _state_writes_move_the_probe(X, N, nobj, probe, base)
     for e in (X, Y):
         e.close()
+
+
+def _state_writes_move_the_probe(env, N, nobj, probe, base):
+    """The probe's table and postures are not culled or saturated into blindness: a write_state of the object poses alone, with no
+    step, moves every probe output that reads the objects -- the six hull-distance calls --, and one of the joint positions alone
+    moves every one that reads the present joints: closest_points, signed_distance() and posture_ik without seeds (the candidate
+    forms replace the joints by their tensors, and the IK reads no object, so neither write has to move those)."""
+    env.restore(base)
+    env.set_kinematic_points([nat.EE_LINK])
+    s = sp.Session(env, 'device')
+    s.setup()
+    rows = sp._Draw(np.random.default_rng([97, N]), N, nobj).rows()
+    everyone = np.arange(N)
+    for parts, must in ((sp.W_OBJ_POSE, QUERIES[:6]), (sp.W_JOINT_POS, READS_JOINTS)):
+        d0 = _collect(env, s, probe, everyone, everyone, images=False)
+        s.apply(dict(kind='write_state', parts=parts, reset=False, fresh=False, rows=rows, mask=None))
+        d1 = _collect(env, s, probe, everyone, everyone, images=False)
+        moved = [k for k in d0 if _differing(d0[k], d1[k]).size]
+        for call in must:
+            assert any(k.startswith(call + '.') for k in moved), (parts, call, moved)
+        assert not any(k.startswith(('posture_kinematics(po).', 'posture_ik(targets, seeds).')) for k in moved), (parts, moved)
+        s.release()

@@ -1,5 +1,6 @@
 """CPU tests of the programmes that tests/test_gpu_session.py runs (tests/session_program.py): the coverage of the interleaving
-does not depend on luck.  For the very seeds and sizes of the GPU test (session_program.SESSIONS), all three of them:
+does not depend on luck.  For the very seeds and sizes of the GPU test (session_program.SESSIONS), n70, n5 and n1100 -- whose
+programmes are pinned by a digest taken from the generator as it was before the query programmes existed --:
 
 * the same arguments give the same programme, another seed another one;
 * every mutator kind at least 3 times, each directly followed at least once by a step without camera, with the camera of every env
@@ -15,16 +16,51 @@ does not depend on luck.  For the very seeds and sizes of the GPU test (session_
 
 23 mutator kinds, three times each, directly followed by a step, are 138 ops: a programme has 200, whatever the number of envs.
 
-A recording fake of BatchedREALRobotEnv shows which calls each road issues."""
+The query programmes of q70 and q5 (3 more mutator kinds, 9 query observer kinds; 74 ops): the conditions of
+`check_query_conditions`, spelled out at test_conditions_of_the_query_programmes_the_gpu_test_runs; a negative case for each kind of
+condition; and, for the very anchor records of the GPU test, that the float64 reference decides at least 95 % of the items, so that
+the anchor cannot silently compare nothing.
+
+A recording fake of BatchedREALRobotEnv shows which calls each road issues, for the query kinds too."""
 import numpy as np
 import pytest
 
 from tests import session_program as sp
 
 
+OLD = [name for name in sp.SESSIONS if name not in sp.QUERY_SESSIONS]
+assert OLD == ['n70', 'n5', 'n1100']
+# the three programmes from before the query programmes, as the parent commit's `program` drew them: blake2b-128 over every record's
+# kind and its keys in sorted order -- arrays (and the arrays of a recipe) by dtype, shape and bytes, everything else by its repr
+PINNED = {'n70': '0814dd1c46894a9a7d1660a2d276ee18', 'n5': '0fc90cd75a5fb425940149d1ff46cee7', 'n1100': '3c819adaf090f39665680cb5ccced3c7'}
+
+
 @pytest.fixture(scope='module')
 def programmes():
-    return {name: sp.program(seed, N, nobj, length) for name, (seed, N, nobj, _, _, length) in sp.SESSIONS.items()}
+    return {name: sp.program(seed, N, nobj, length, queries=name in sp.QUERY_SESSIONS) for name, (seed, N, nobj, _, _, length) in sp.SESSIONS.items()}
+
+
+def _digest(ops):
+    import hashlib
+    h = hashlib.blake2b(digest_size=16)
+    for o in ops:
+        h.update(o['kind'].encode())
+        for k in sorted(o):
+            v = o[k]
+            if isinstance(v, dict):
+                for kk in sorted(v):
+                    a = np.asarray(v[kk])
+                    h.update(('%s.%s%s%s' % (k, kk, a.dtype.str, a.shape)).encode() + np.ascontiguousarray(a).tobytes())
+            elif isinstance(v, np.ndarray):
+                h.update(('%s%s%s' % (k, v.dtype.str, v.shape)).encode() + np.ascontiguousarray(v).tobytes())
+            else:
+                h.update(('%s=%r' % (k, v)).encode())
+    return h.hexdigest()
+
+
+@pytest.mark.parametrize('name', OLD)
+def test_the_programmes_from_before_the_queries_are_unchanged(programmes, name):
+    assert _digest(programmes[name]) == PINNED[name]
 
 
 def _same(a, b):
@@ -35,7 +71,7 @@ def _same(a, b):
     return type(a) is type(b) and a == b
 
 
-@pytest.mark.parametrize('name', list(sp.SESSIONS))
+@pytest.mark.parametrize('name', OLD)
 def test_the_same_arguments_give_the_same_programme(programmes, name):
     seed, N, nobj, _, _, length = sp.SESSIONS[name]
     again = sp.program(seed, N, nobj, length)
@@ -52,7 +88,7 @@ def test_the_module_imports_neither_torch_nor_the_library():
     subprocess.check_call([sys.executable, '-c', code], cwd=str(__import__('pathlib').Path(__file__).resolve().parents[1]))
 
 
-@pytest.mark.parametrize('name', list(sp.SESSIONS))
+@pytest.mark.parametrize('name', OLD)
 def test_conditions_of_the_programmes_the_gpu_test_runs(programmes, name):
     length = sp.SESSIONS[name][5]
     assert length == 200
@@ -73,7 +109,7 @@ def test_every_subset_meets_reset_and_fresh_with_and_without(programmes):
         assert {c[0] for c in combos} == {False, True} and {c[1] for c in combos} == {False, True}, (parts, combos)
 
 
-@pytest.mark.parametrize('name', list(sp.SESSIONS))
+@pytest.mark.parametrize('name', OLD)
 def test_the_conditions_spelled_out(programmes, name):
     """the conditions once more, from the list of kinds alone (not through check_conditions)"""
     ops = programmes[name]
@@ -104,6 +140,90 @@ def test_a_condition_that_fails_is_noticed(programmes):
     ops = [dict(o, parts=3) if o['kind'] == 'write_state' and o['parts'] == 12 else o for o in programmes['n5']]
     with pytest.raises(AssertionError):
         sp.check_conditions(ops, 200)       # (no write throws an object out of bounds in front of a set_object_home)
+    # the query programmes: each of these breaks one condition and nothing else
+    _, _, nobj, _, _, length = sp.SESSIONS['q70']
+    q = programmes['q70']
+    sp.check_query_conditions(q, length, nobj)
+    at = next(i for i, o in enumerate(q) if o['kind'] == 'fork_dev')
+    assert q[at + 1]['kind'] in sp.STATE_READERS
+    broken = [
+        [dict(o, compared=True) if o['kind'] == 'swept_clearance' else o for o in q],                 # a kind that is never silent
+        q[:at + 1] + [dict(q[at + 1], kind='posture_kinematics')] + q[at + 2:],                      # no state reader behind the fork
+        [dict(o, cls='one') if o['kind'] == 'set_distance_pairs' and o['cls'] == 'full' else o for o in q],      # no table of 96 pairs
+        [dict(o, max_distance=0.1) if o['kind'] == 'set_distance_pairs' and o['cls'] == 'default' else o for o in q],   # a cull at the anchors
+        [dict(o, links=np.full_like(o['links'], 8)) if o['kind'] == 'set_kinematic_points' else o for o in q],   # the gripper base only
+        [o for o in q if o['kind'] != 'set_rays' or len(o['links']) != 64] + [dict(kind='render')],   # no table of 64 rays
+    ]
+    broken[-1] += [dict(kind='render')] * (length - len(broken[-1]))
+    for ops in broken:
+        assert len(ops) == length
+        with pytest.raises(AssertionError):
+            sp.check_query_conditions(ops, length, nobj)
+
+
+# ---------------------------------------------------------------------------------------------------- the query programmes
+@pytest.mark.parametrize('name', sp.QUERY_SESSIONS)
+def test_conditions_of_the_query_programmes_the_gpu_test_runs(programmes, name):
+    """q70 and q5: the three table mutators with every render form; each of the nine query observers directly between a step and a
+    mutator and directly between a mutator -- not a write_state every time -- and a step, compared and silent; a state-reading query
+    directly behind each of write_state (poses, joints), fork_dev, load_snapshot, reset_dev, restore, set_object_poses, episode_reset,
+    set_distance_pairs and set_kinematic_points; K in {1, 3, 32}; tables of 1, the default, 92 / 80 ('collision') and 96 pairs with
+    and without a cull; points on a finger link and below joint 7 with offsets; 1, 4 and 64 world and link rays; the two anchors with
+    the default table in force."""
+    seed, N, nobj, _, _, length = sp.SESSIONS[name]
+    ops = programmes[name]
+    assert length == sp.Q_LENGTH
+    sp.check_query_conditions(ops, length, nobj)
+    again = sp.program(seed, N, nobj, length, queries=True)
+    assert all(_same(a, b) for a, b in zip(ops, again))
+    assert not all(_same(a, b) for a, b in zip(ops, sp.program(seed + 1, N, nobj, length, queries=True)))
+    with pytest.raises(ValueError):
+        sp.program(seed, N, nobj, length - 1, queries=True)       # (too short for the conditions: refused, not thinned)
+    longer = sp.program(seed, N, nobj, length + 5, queries=True)
+    sp.check_query_conditions(longer, length + 5, nobj)
+    kinds = [o['kind'] for o in ops]
+    for k in sp.Q_OBSERVERS:                                       # once more, from the list of kinds alone
+        at = [i for i, x in enumerate(kinds) if x == k]
+        assert any(kinds[i - 1] == 'step' and kinds[i + 1] in sp.MUTATORS + sp.Q_MUTATORS for i in at), k
+        assert any(kinds[i - 1] in sp.MUTATORS + sp.Q_MUTATORS and kinds[i - 1] != 'write_state' and kinds[i + 1] == 'step' for i in at), k
+
+
+def test_the_shape_and_link_names_are_the_models():
+    from real_robots_amd import _native as nat
+    from real_robots_amd.batched import BatchedREALRobotEnv
+    rows = BatchedREALRobotEnv.collision_shapes()
+    by_body = lambda ok: tuple(r['name'] for r in rows if ok(r['body']))
+    assert sp.STATIC_SHAPES == by_body(lambda b: b < 0) and sp.ROBOT_SHAPES == by_body(lambda b: 0 <= b < 16) and sp.OBJECT_SHAPES == by_body(lambda b: b >= 16)
+    assert len(nat.LINK_NAMES) == sp.N_LINKS and all(nat.LINK_NAMES[l].startswith(('finger', 'skin')) for l in sp.FINGER_LINKS)
+    assert [nat.LINK_NAMES[l] for l in sp.ARM_LINKS] == ['lbr_iiwa_link_%d' % l for l in range(1, 7)]
+    for nobj in (1, 2, 3):
+        pairs = sp.default_pairs(nobj)
+        n, a, b, md = BatchedREALRobotEnv._distance_arg(pairs, None, nobj)           # (only objects the handle has)
+        assert 10 <= n == len(pairs) <= 14 and md == 0.0
+        kind = lambda x: 'o' if x in sp.OBJECT_SHAPES else 's' if x in sp.STATIC_SHAPES else 'r'
+        mixes = {''.join(sorted(kind(x) + kind(y))) for x, y in pairs}
+        assert mixes >= {'or', 'rs', 'rr', 'os'} and (('oo' in mixes) == (nobj > 1))
+
+
+@pytest.mark.parametrize('name', sp.QUERY_SESSIONS)
+def test_the_anchors_are_decided(programmes, name):
+    """The float64 anchor of the GPU test may omit only what the reference leaves undecided: for the very anchor records of q70 and
+    q5, the first four envs, the default table and the probe's postures, at least 95 % of the (env, pair) and (env, posture, pair)
+    items are decided, none overlaps, and the nearest pair of nearly every row is decided too."""
+    from tests import numpy_posture as npo
+    _, N, nobj, _, _, _ = sp.SESSIONS[name]
+    anchors = [o for o in programmes[name] if sp.is_anchor(o)]
+    assert {o['kind'] for o in anchors} == {'set_state', 'write_state'}
+    q = sp.probe_arguments(N, nobj)
+    assert q['postures'].shape == (N, sp.PROBE_K, 11) and q['segments'].shape == (N, 2, 2, 11) and q['targets'].shape == (N, 2, 7)
+    for o in anchors:
+        st, pairs, ref, ref_po = sp.anchor_references(o, nobj, q)
+        n = min(N, sp.ANCHOR_ENVS)
+        assert ref['decided'].shape == (n, len(pairs)) and ref_po['decided'].shape == (n * sp.PROBE_K, len(pairs))
+        for r in (ref, ref_po):
+            assert r['decided'].sum() >= 0.95 * r['decided'].size and (r['d'] > 0).all(), (o['kind'], r['decided'].sum(), r['d'].min())
+        assert npo.nearest(ref_po)[1].sum() >= 0.75 * n * sp.PROBE_K
+        assert ref['d'].min() < sp.PROBE_MARGIN                    # (the probe's gradient has a cost to report)
 
 
 def test_written_values_are_what_the_calls_get():
@@ -197,7 +317,7 @@ def _run(ops, road, N, nobj):
     return per_op, s
 
 
-@pytest.mark.parametrize('name', list(sp.SESSIONS))
+@pytest.mark.parametrize('name', OLD)
 def test_both_roads_issue_the_calls_they_should(programmes, name):
     _, N, nobj, _, _, _ = sp.SESSIONS[name]
     ops = programmes[name]
@@ -249,6 +369,37 @@ def test_both_roads_issue_the_calls_they_should(programmes, name):
     assert any(o['parts'] == 4 and not o['fresh'] and not o['reset'] for o in wrote) and any(o['parts'] == 4 and o['reset'] for o in wrote)
     assert any(o['parts'] == 15 and o['fresh'] and not o['reset'] and o['mask'] is None for o in wrote)
     assert any(o['parts'] == 0 for o in wrote)
+
+
+@pytest.mark.parametrize('name', sp.QUERY_SESSIONS)
+def test_both_roads_issue_the_query_calls_they_should(programmes, name):
+    """The table mutators are host calls on every road.  A query record: A calls with device tensors; B calls only where the record
+    is compared, with host arrays; a call without a tensor has no side.  The IK's point is the last of the table in force."""
+    _, N, nobj, _, _, _ = sp.SESSIONS[name]
+    ops = programmes[name]
+    dev, sd = _run(ops, 'device', N, nobj)
+    host, sh = _run(ops, 'host', N, nobj)
+    call = {'closest_points': 'closest_points', 'posture_clearance': 'posture_clearance', 'signed_distance': 'signed_distance',
+            'signed_distance_at': 'signed_distance', 'signed_distance_gradient': 'signed_distance_gradient', 'swept_clearance': 'swept_clearance',
+            'posture_kinematics': 'posture_kinematics', 'posture_ik': 'posture_ik', 'posture_ik_present': 'posture_ik'}
+    for op, d, h in zip(ops, dev, host):
+        k = op['kind']
+        assert all(c[1] != 'device' for c in h), (k, h)
+        if k in sp.Q_MUTATORS:
+            assert [c[0] for c in d] == [c[0] for c in h] == [k] and d[0][1] == h[0][1] != 'device'
+        elif k in sp.Q_OBSERVERS:
+            side = None if k in ('closest_points', 'signed_distance') else 'device'
+            assert d == [(call[k], side)], (k, d)
+            assert h == ([(call[k], side and 'host')] if op['compared'] else []), (k, h)
+    assert sd.n_rays == sh.n_rays == len([o for o in ops if o['kind'] == 'set_rays'][-1]['links'])
+    assert (sd.points[0] == [o for o in ops if o['kind'] == 'set_kinematic_points'][-1]['links']).all()
+    assert sd.max_distance == sh.max_distance == [o for o in ops if o['kind'] == 'set_distance_pairs'][-1]['max_distance']
+    # the recipe of an IK record resolves to unit quaternions at the point in force, the same on both roads
+    goals = next(o for o in ops if o['kind'] == 'posture_ik')['goals']
+    t = sd.ik_targets(goals)
+    assert t.shape == goals.shape[:2] + (7,) and t.dtype == np.float32 and np.allclose(np.linalg.norm(t[..., 3:], axis=-1), 1.0, atol=1e-6)
+    assert np.array_equal(t, sh.ik_targets(goals))
+    assert sd.margin(0.3) == (0.3 if sd.max_distance is None else sd.max_distance) and sp.Session(FakeEnv(N, nobj), 'host').margin(0.3) == 0.3
 
 
 def test_run_is_the_session_over_the_whole_programme(programmes):
