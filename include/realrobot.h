@@ -1089,6 +1089,74 @@ int rr_posture_ik_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *byt
 /* Synchronising copy of a whole RR_PIK_* buffer (its `bytes`) to host memory. */
 int rr_posture_ik_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
 
+/* ---- Joint-space dynamics at candidate joint postures on the device (additive in ABI 7) ------------------------------------------------
+ * The posture queries above answer every kinematic and geometric question about K candidate postures per env; this one answers the
+ * dynamic one: what does it cost to hold or move the arm there?  One launch on the library's stream (rr_posture_dynamics) evaluates
+ * K rows per env of the whole batch -- a posture q, a joint velocity qd and a joint acceleration qdd each -- and writes the mass
+ * matrix M(q), the gravity torques G(q), the bias G(q) + C(q, qd), the inverse dynamics M qdd + C + G and, on request, M^-1:
+ * pybullet's calculateMassMatrix and calculateInverseDynamics for every row at once.  A trajectory optimiser's effort cost and
+ * torque limits, a gravity-compensated or computed-torque controller and an operational-space controller (M^-1 beside the Jacobian
+ * of rr_posture_kinematics) read them in place.  The buffers are NOT fields of rr_get_buffer and not buffers of another query: they
+ * have this enum and rr_posture_dynamics_buffer. */
+enum {
+    RR_PD_MASS_MATRIX = 0,   /* f32 [N, K, 11, 11]  M(q) over the eleven independent joints, in the order of the state's q[11]       */
+    RR_PD_GRAVITY = 1,       /* f32 [N, K, 11]      G(q): the joint torques that hold the posture still                            */
+    RR_PD_BIAS = 2,          /* f32 [N, K, 11]      G(q) + C(q, qd): calculateInverseDynamics at zero acceleration                 */
+    RR_PD_TORQUE = 3,        /* f32 [N, K, 11]      M qdd + bias: calculateInverseDynamics                                         */
+    RR_PD_MASS_INVERSE = 4,  /* f32 [N, K, 11, 11]  M^-1; written only with RR_PD_INVERSE                                          */
+    RR_PD_COUNT = 5
+};
+enum { RR_PD_INVERSE = 1u };   /* flags */
+/* Input.  Three tensors f32 [N][K][11], C order, K = n_postures in [1, RR_PC_MAX_POSTURES], over the eleven INDEPENDENT joints in
+ * the order of the state's q[11]: postures (rad), velocities (rad/s), accelerations (rad/s^2).
+ *   velocities == NULL: qd = 0, and RR_PD_BIAS holds the same bytes as RR_PD_GRAVITY.
+ *   accelerations == NULL: qdd = 0, and RR_PD_TORQUE holds the same bytes as RR_PD_BIAS.
+ *   postures == NULL: the PRESENT-STATE form.  K = 1 (n_postures must be 1), q and qd are the joint columns of env e's RR_F_STATE
+ *     row, read and never written; velocities must then be NULL too; accelerations may be given as [N][1][11].
+ * on_device != 0: every tensor given is device memory, read IN PLACE on the library's stream under the STREAM CONTRACT of
+ * rr_posture_clearance (produced on that stream or ordered before it; not rewritten before later work on that stream); the call
+ * allocates nothing beyond the first-use buffers, checks the launch and returns without waiting.  on_device == 0: every tensor given
+ * is host memory, staged through the posture staging blocks (the handle's own, allocated by the first host-path call that needs
+ * them), and the call waits for the stream.  There is one flag for the whole set: a mixed set cannot be expressed, and the Python
+ * layer refuses one.  Values are NOT validated and NOT clamped to the joint limits: a row is evaluated as given.
+ * flags: RR_PD_INVERSE also writes RR_PD_MASS_INVERSE; without it that buffer is left as it was.  Other bits: RR_EINVAL.
+ * What is computed.  The rigid-body dynamics of the eleven moving bodies of the arm and gripper, tau = M(q) qdd + C(q, qd) + G(q):
+ * forward kinematics (the step's frames), the composite-body pass for M, one recursive Newton-Euler pass at qd = 0 for G and one at
+ * qd for the bias, M qdd added to the bias, the Cholesky factor and its inverse for M^-1 -- the arithmetic of the step's
+ * preparation, in float32 with contracted multiply-adds and 1-ulp reciprocal square roots on the Cholesky diagonal.
+ *   The link masses and inertias are the HANDLE'S OWN: the body table the step's preparation reads, so a handle created with
+ *     use_urdf_inertia answers with those inertias.
+ *   Gravity is the step's (9.81 m/s^2 along -z).
+ *   Joint damping and the motors are NOT part of any output -- as in pybullet, where joint damping (rr_set_env_actuators) is a force
+ *     the step adds.
+ *   M is computed for one triangle and mirrored: symmetric BIT FOR BIT.  An entry between joints of which neither moves the other's
+ *     body (the two finger branches: joints {7, 8} against {9, 10}) is exactly +0.0.
+ * A row is a function of its three input rows and the model ALONE.  It is independent of env e's state, of the object dynamics and
+ * of the actuators: N is the batch shape this query shares with its siblings, not an input (the present-state form reads the joint
+ * columns of the state as its input rows and nothing else of it).
+ * No effect on the simulation.  The call writes these buffers only: not the state, not the preparation record (RR_F_PREP), no error
+ * flag and no buffer of another query.  The look-ahead stays valid and the next step is bit for bit what it would have been.  The
+ * buffers hold what the LAST CALL computed.
+ * Every loop bound is a constant or the row count, and no value of the tensors ever forms an address: a non-finite row finishes like
+ * any other, its outputs are non-finite, and no other row is affected.
+ * Determinism.  No atomics: a row is identical from call to call, independent of N, of K, of the row's place and of its neighbours.
+ * Errors: RR_EINVAL with nothing allocated and nothing changed, the message naming the function and the cause, for a null env,
+ * n_postures outside [1, RR_PC_MAX_POSTURES], postures == NULL with velocities given or with n_postures != 1, and unknown flag bits.
+ * Buffers.  All five are allocated on first use -- by this call, or by rr_posture_dynamics_buffer /
+ * rr_posture_dynamics_copy_to_host --, all or nothing through the handle's memory owner, zero-filled, sized once for
+ * RR_PC_MAX_POSTURES -- N x 35 200 bytes: 144 MB at 4096 envs --, and valid until rr_destroy: no pointer ever changes.  The layout is
+ * compact for the K of the last call (0 before the first), and `bytes` reports that.  STREAM CONTRACT for readers as for the other
+ * zero-copy views: the kernel runs on the library's stream behind the work enqueued before it; readers on another stream order
+ * themselves after the call (event / rr_sync), and a later call rewrites the buffers in place.
+ * Out of scope: torque control in the step; joint damping or motor terms; the operational-space inertia itself (form
+ * (J M^-1 J^T)^-1 from this query and rr_posture_kinematics); derivatives of the dynamics. */
+int rr_posture_dynamics(rr_env *env, const float *postures /* f32 [N][K][11] or NULL */, const float *velocities /* f32 [N][K][11] or NULL */,
+                        const float *accelerations /* f32 [N][K][11] or NULL */, int32_t n_postures, int32_t on_device, uint32_t flags);
+/* Zero-copy device pointer + size in bytes of an RR_PD_* buffer (read-only for the caller); which outside [0, RR_PD_COUNT): RR_EINVAL. */
+int rr_posture_dynamics_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
+/* Synchronising copy of a whole RR_PD_* buffer (its `bytes`) to host memory. */
+int rr_posture_dynamics_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
+
 /* Batched damped-least-squares inverse kinematics for link 7 (gripper `base`), seeded with each env's current joints.
  * Replaces pybullet.calculateInverseKinematics(0, 7, pos, orn, maxNumIterations=1000, residualThreshold=0.001) in
  * step_cartesian (env.py:372-375).  targets: f32 [N, 7] (xyz + xyzw quaternion, host); q_out: f32 [N, 11] (all movable

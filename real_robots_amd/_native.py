@@ -47,7 +47,8 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_signed_gradient', 'rr_signed_gradient_buffer', 'rr_signed_gradient_copy_to_host',
            'rr_swept_clearance', 'rr_sweep_reach', 'rr_sweep_buffer', 'rr_sweep_copy_to_host',
            'rr_posture_kinematics', 'rr_posture_kinematics_buffer', 'rr_posture_kinematics_copy_to_host',
-           'rr_posture_ik', 'rr_posture_ik_buffer', 'rr_posture_ik_copy_to_host')
+           'rr_posture_ik', 'rr_posture_ik_buffer', 'rr_posture_ik_copy_to_host',
+           'rr_posture_dynamics', 'rr_posture_dynamics_buffer', 'rr_posture_dynamics_copy_to_host')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
@@ -102,6 +103,10 @@ PIK_FIELDS = ('posture', 'result', 'info')
 PIK_MAX_ITERATIONS = 256
 PIK_POSITION_ONLY, PIK_CLAMP_LIMITS = 1, 2           # flags of rr_ik_options
 PIK_CONVERGED, PIK_CAP, PIK_NOT_FINITE = 0, 1, 2     # status
+# buffers of rr_posture_dynamics_buffer (the RR_PD_* enum), per env and row of the last rr_posture_dynamics: mass_matrix f32 [11, 11],
+# gravity, bias, torque f32 [11], mass_inverse f32 [11, 11] (written only with PD_INVERSE, the flag RR_PD_INVERSE)
+PD_FIELDS = ('mass_matrix', 'gravity', 'bias', 'torque', 'mass_inverse')
+PD_INVERSE = 1
 SLOT_LIVE, MAX_SLOTS = -1, 64           # RR_SLOT_LIVE: the running envs as a slot number of rr_copy_envs; RR_MAX_SLOTS
 # `parts` of rr_write_state (the RR_W_* bits): the column groups of the 61-float state row that are written, a reset in front of them,
 # the fresh-start clean-up of rr_set_state behind them
@@ -263,6 +268,9 @@ def load_library():
     L.rr_posture_ik.argtypes = [vp, vp, vp, i32, i32, C.POINTER(IkOptions)]
     L.rr_posture_ik_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rr_posture_ik_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
+    L.rr_posture_dynamics.argtypes = [vp, vp, vp, vp, i32, i32, C.c_uint32]
+    L.rr_posture_dynamics_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rr_posture_dynamics_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]

@@ -1339,6 +1339,73 @@ class BatchedREALRobotEnv:
         return dict(posture=posture, residual=col(result, 0), position_error=col(result, 1), orientation_error=col(result, 2),
                     status=col(info, 0), iterations=col(info, 1))
 
+    # ------------------------------------------------------------------ joint-space dynamics at candidate postures
+    def posture_dynamics_buffer(self, name, host=False):
+        """One buffer of `posture_dynamics` as the LAST call left it (all zero, and K = 0, before the first), by name
+        (`_native.PD_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait.  Shapes: mass_matrix
+        and mass_inverse [N, K, 11, 11], gravity, bias and torque [N, K, 11] float32."""
+        which = nat.PD_FIELDS.index(name) if isinstance(name, str) and name in nat.PD_FIELDS else name
+        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.PD_FIELDS):
+            raise ValueError("unknown posture dynamics buffer %r (known: %s)" % (name, ', '.join(nat.PD_FIELDS)))
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(self.L.rr_posture_dynamics_buffer(self.h, int(which), C.byref(p), C.byref(n)))
+        row = (nat.N_JOINTS, nat.N_JOINTS) if nat.PD_FIELDS[int(which)] in ('mass_matrix', 'mass_inverse') else (nat.N_JOINTS,)
+        shape = (self.N, n.value // (4 * self.N * int(np.prod(row)))) + row
+        if host:
+            out = np.empty(shape, np.float32)
+            nat.check(self.L.rr_posture_dynamics_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
+            return out
+        return nat.DeviceBuffer(p.value, shape, '<f4', self)
+
+    @classmethod
+    def _dynamics_args(cls, N, postures, velocities, accelerations):
+        """The tensors of `posture_dynamics` for a handle of N envs -> (K, (address or None) x 3, on_device, keep-alive objects).
+        Every violation -- shape, dtype, contiguity, velocities without postures, tensors on different sides -- is a ValueError raised
+        here, before the native call; nothing of a handle is needed."""
+        if postures is None:
+            if velocities is not None:
+                raise ValueError("posture_dynamics: velocities without postures (the present-state form takes the state's joint velocities)")
+            K = 1
+        else:
+            K = cls._posture_arg(postures, N)
+        ptrs, sides, keep = [], [], []
+        for a, name in ((postures, 'postures'), (velocities, 'velocities'), (accelerations, 'accelerations')):
+            if a is None:
+                ptrs.append(None)
+                continue
+            ptr, dev, k = cls._state_arg(None, a, name, ('float32',), (N, K, nat.N_JOINTS))
+            ptrs.append(ptr)
+            sides.append((name, dev))
+            keep.append(k)
+        if len(set(dev for _, dev in sides)) > 1:
+            raise ValueError("posture_dynamics: the tensors must live on the same side (%s)"
+                             % ', '.join("%s on the %s" % (name, ('host', 'device')[dev]) for name, dev in sides))
+        return K, ptrs, (sides[0][1] if sides else 1), keep
+
+    def posture_dynamics(self, postures=None, velocities=None, accelerations=None, inverse=False, host=False):
+        """What it costs to hold or move the arm at K candidate rows per env (rr_posture_dynamics; pybullet's calculateMassMatrix and
+        calculateInverseDynamics for the whole batch): one launch on the library's stream evaluates row (e, k) -- a posture q, a joint
+        velocity qd, a joint acceleration qdd over the eleven independent joints -- and writes (float32)
+          mass_matrix [N, K, 11, 11] -- M(q), symmetric bit for bit, exactly +0.0 between the two finger branches;
+          gravity [N, K, 11] -- G(q), the torques that hold the posture still;
+          bias [N, K, 11] -- G(q) + C(q, qd), the inverse dynamics at zero acceleration;
+          torque [N, K, 11] -- M qdd + bias, the inverse dynamics;
+          mass_inverse [N, K, 11, 11] -- M^-1, computed and returned only with inverse=True.
+        postures, velocities, accelerations: float32 [N, K, 11], 1 <= K <= 32, C-contiguous -- all numpy arrays (staged, synchronous)
+        or all CUDA torch tensors / `__cuda_array_interface__` objects, read in place on the library's stream without waiting
+        (produce them on that stream or synchronise first); a mixed set is a ValueError.  velocities=None: qd = 0 and `bias` has the
+        bytes of `gravity`; accelerations=None: qdd = 0 and `torque` has the bytes of `bias`.  postures=None is the present-state
+        form: K = 1, q and qd are the env's own (read, never written), velocities must be None, accelerations may be [N, 1, 11].
+        Values are neither validated nor clamped to the joint limits.  The masses and inertias are the handle's (use_urdf_inertia
+        counts), gravity is the step's; joint damping and the motors are in no output.  A row depends on its three input rows and the
+        model alone.  The simulation is not touched: no state write, the next step stays prepared.  Returns device buffers (zero
+        copy, DLPack; valid after later work on the library's stream or `sync()`; they hold what the last call computed), or with
+        host=True numpy arrays after a sync."""
+        K, (qp, vp, ap), on_dev, keep = self._dynamics_args(self.N, postures, velocities, accelerations)
+        nat.check(self.L.rr_posture_dynamics(self.h, qp, vp, ap, K, on_dev, nat.PD_INVERSE if inverse else 0))
+        del keep
+        return {name: self.posture_dynamics_buffer(i, host=host) for i, name in enumerate(nat.PD_FIELDS) if inverse or name != 'mass_inverse'}
+
     def body_row_names(self):
         """The bodies of the rows of body_force / body_partners: the 17 URDF links, then this handle's objects (the rows of the
         objects it does not have, up to 20, stay zero)."""

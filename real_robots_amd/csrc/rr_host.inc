@@ -173,6 +173,11 @@ struct rr_env : ModelTables {
     void *pik_buf[RR_PIK_COUNT] = {};
     int pik_k = 0;                 // targets per env of the last call: 0 before the first
     float *pik_stage = nullptr;
+    // joint-space dynamics at candidate postures (rr_posture_dynamics): the five RR_PD_* buffers, allocated together on first use for
+    // RR_PC_MAX_POSTURES, once; a host caller's postures go through pc_stage, its velocities and accelerations through pd_stage [2][N, 32, 11]
+    float *pd_buf[RR_PD_COUNT] = {};
+    int pd_k = 0;                  // rows per env of the last call: 0 before the first
+    float *pd_stage = nullptr;
     MemOwner mem;                  // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
     bool created = false;
     bool timing = false;
@@ -2248,6 +2253,104 @@ int rr_posture_ik_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes
     HIPCHK(hipSetDevice(e->cfg.device));
     if (bytes == 0) return RR_OK;
     HIPCHK(hipMemcpyAsync(dst, e->pik_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return RR_OK;
+}
+
+// ---- joint-space dynamics at candidate postures (rr_pdyn.inc) ---------------------------------------------------------------------------
+// The five buffers of rr_posture_dynamics: allocated on first use -- by the call or by rr_posture_dynamics_buffer /
+// rr_posture_dynamics_copy_to_host -- in one list, zero-filled, for RR_PC_MAX_POSTURES rows per env.  The layout in force is
+// [N, K, ...] for the K of the last call (0 before the first).
+static size_t pd_bytes(const rr_env *e, int which, int K) {
+    const size_t row[RR_PD_COUNT] = {NB * NB, NB, NB, NB, NB * NB};
+    return (size_t)e->P.N * K * row[which] * 4;
+}
+// `stage_q` / `stage_v`: the staging blocks a host-path call still lacks come in the same list, all or nothing
+static int ensure_pdyn(rr_env *e, const char *who, bool stage_q = false, bool stage_v = false) {
+    stage_q = stage_q && !e->pc_stage;
+    stage_v = stage_v && !e->pd_stage;
+    const bool bufs = !e->pd_buf[0];
+    if (!bufs && !stage_q && !stage_v) return RR_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    float *b[RR_PD_COUNT] = {};
+    float *qs = nullptr, *vs = nullptr;
+    MemPart parts[RR_PD_COUNT + 2];
+    size_t n = 0;
+    if (bufs)
+        for (int i = 0; i < RR_PD_COUNT; i++) parts[n++] = mem_part(&b[i], pd_bytes(e, i, RR_PC_MAX_POSTURES));
+    if (stage_q) parts[n++] = mem_part(&qs, (size_t)e->P.N * RR_PC_MAX_POSTURES * 44, false);
+    if (stage_v) parts[n++] = mem_part(&vs, (size_t)2 * e->P.N * RR_PC_MAX_POSTURES * 44, false);
+    RRCHK(mem_get(e, parts, n, (std::string(who) + ": allocating the posture dynamics buffers").c_str()));
+    if (bufs)
+        for (int i = 0; i < RR_PD_COUNT; i++) e->pd_buf[i] = b[i];
+    if (stage_q) e->pc_stage = qs;
+    if (stage_v) e->pd_stage = vs;
+    return RR_OK;
+}
+
+// M, G, G + C, M qdd + C + G and on request M^-1 at K rows per env, on the device.  On the main stream like rr_posture_clearance:
+// behind every step, reset and state write enqueued before it.  Reads the tensors (without postures: the joint columns of the
+// state), the model and the handle's body table -- the one the preparation reads --; writes the five buffers and nothing else: not
+// the state, the scratch slab of the look-ahead, la_valid, an error flag or a buffer of another query.
+int rr_posture_dynamics(rr_env *e, const float *postures, const float *velocities, const float *accelerations, int32_t n_postures, int32_t on_device,
+                        uint32_t flags) {
+    if (!e) return fail(RR_EINVAL, "rr_posture_dynamics: null env");
+    if (n_postures < 1 || n_postures > RR_PC_MAX_POSTURES)
+        return fail(RR_EINVAL, "rr_posture_dynamics: n_postures " + std::to_string(n_postures) + " is not in [1, RR_PC_MAX_POSTURES = " +
+                                   std::to_string(RR_PC_MAX_POSTURES) + "]");
+    if (!postures && velocities) return fail(RR_EINVAL, "rr_posture_dynamics: velocities without postures (the present-state form takes the state's joint velocities)");
+    if (!postures && n_postures != 1) return fail(RR_EINVAL, "rr_posture_dynamics: n_postures " + std::to_string(n_postures) + " without postures (the present-state form has K = 1)");
+    if (flags & ~(uint32_t)RR_PD_INVERSE) return fail(RR_EINVAL, "rr_posture_dynamics: unknown flag bits in " + std::to_string(flags));
+    const int N = e->P.N, K = n_postures;
+    const size_t tensor = (size_t)N * K * 44;
+    RRCHK(ensure_pdyn(e, "rr_posture_dynamics", !on_device && postures, !on_device && (velocities || accelerations)));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    PdIn in = {postures, velocities, accelerations, NB, 1};
+    if (!on_device) {
+        if (postures) { HIPCHK(hipMemcpyAsync(e->pc_stage, postures, tensor, hipMemcpyHostToDevice, e->stream)); in.q = e->pc_stage; }
+        if (velocities) { HIPCHK(hipMemcpyAsync(e->pd_stage, velocities, tensor, hipMemcpyHostToDevice, e->stream)); in.qd = e->pd_stage; }
+        if (accelerations) {
+            float *dst = e->pd_stage + (size_t)N * RR_PC_MAX_POSTURES * NB;
+            HIPCHK(hipMemcpyAsync(dst, accelerations, tensor, hipMemcpyHostToDevice, e->stream));
+            in.qdd = dst;
+        }
+    }
+    if (!postures) {      // the present state: row e is env e, q and qd the columns ST_Q.. and ST_QD.. of the [61][N] state
+        in.q = (const float *)e->D.state + (size_t)ST_Q * N;
+        in.qd = (const float *)e->D.state + (size_t)ST_QD * N;
+        in.rs = 1; in.cs = (size_t)N;
+    }
+    const int rows = N * K;
+    const PdOut O = {e->pd_buf[RR_PD_MASS_MATRIX], e->pd_buf[RR_PD_GRAVITY], e->pd_buf[RR_PD_BIAS], e->pd_buf[RR_PD_TORQUE], e->pd_buf[RR_PD_MASS_INVERSE]};
+    const dim3 grid((unsigned)((rows + PD_ROWS - 1) / PD_ROWS));
+    if (flags & RR_PD_INVERSE)
+        hipLaunchKernelGGL(k_posture_dynamics<true>, grid, dim3(PD_THREADS), 0, e->stream, e->B, (const float *)e->D.body_tab, e->P.gravity, in, rows, O);
+    else
+        hipLaunchKernelGGL(k_posture_dynamics<false>, grid, dim3(PD_THREADS), 0, e->stream, e->B, (const float *)e->D.body_tab, e->P.gravity, in, rows, O);
+    HIPCHK(hipGetLastError());
+    e->pd_k = K;
+    if (!on_device) HIPCHK(hipStreamSynchronize(e->stream));   // the arguments may be host memory; one rule for the host path
+    return RR_OK;
+}
+
+int rr_posture_dynamics_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_posture_dynamics_buffer: null env");
+    if (which < 0 || which >= RR_PD_COUNT) return fail(RR_EINVAL, "rr_posture_dynamics_buffer: buffer " + std::to_string(which) + " is not in [0, RR_PD_COUNT)");
+    RRCHK(ensure_pdyn(e, "rr_posture_dynamics_buffer"));
+    if (dev_ptr) *dev_ptr = e->pd_buf[which];
+    if (bytes) *bytes = pd_bytes(e, which, e->pd_k);
+    return RR_OK;
+}
+
+int rr_posture_dynamics_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_posture_dynamics_copy_to_host: null env");
+    if (!dst) return fail(RR_EINVAL, "rr_posture_dynamics_copy_to_host: null destination");
+    if (which < 0 || which >= RR_PD_COUNT) return fail(RR_EINVAL, "rr_posture_dynamics_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_PD_COUNT)");
+    if (bytes != pd_bytes(e, which, e->pd_k)) return fail(RR_EINVAL, "rr_posture_dynamics_copy_to_host: size mismatch");
+    RRCHK(ensure_pdyn(e, "rr_posture_dynamics_copy_to_host"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    if (bytes == 0) return RR_OK;
+    HIPCHK(hipMemcpyAsync(dst, e->pd_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return RR_OK;
 }

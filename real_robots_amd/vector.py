@@ -54,6 +54,11 @@ gathered, device views or host copies by `device_obs`.  `kinematic_points=` is a
 (links, local_pos [P, 3]); the default is the one point of a fresh handle, the gripper base.  `jacobian @ _native.Q_FROM_CMD` is the
 Jacobian over the nine entries of `joint_command`.  The default leaves dict and spaces as they are.  These two arguments and the ones
 behind them (`ray_sensors`, `distance_pairs`, `distance_max`, `contact_obs`, `goals`, `goal_stride`) are keyword-only.
+Dynamics observations: `dynamics_obs=True` adds the present-state joint-space dynamics `mass_matrix` [N, 11, 11] (M(q) over the eleven
+independent joints) and `bias` [N, 11] (G(q) + C(q, qd): the joint torques that keep the present velocities, without joint damping
+and motors) to the observation dict and to the spaces (float32, unbounded; BatchedREALRobotEnv.posture_dynamics in its present-state
+form), computed where the other entries are gathered, device views or host copies by `device_obs`.  Keyword-only; the default leaves
+dict and spaces as they are.
 Ray sensors: `ray_sensors=(links, segments)` -- the arguments of BatchedREALRobotEnv.set_rays: R links (names, indices, 'world' / -1)
 and segments [R, 6] {from xyz, to xyz} in those links' COM frames -- casts the table against the collision hulls where the other
 entries are gathered (BatchedREALRobotEnv.ray_cast: pybullet's rayTestBatch) and adds `ray_distance` [N, R] (float32, metres along the
@@ -115,7 +120,8 @@ class REALRobotVectorEnv(_Base):
     def __init__(self, num_envs, objects=3, additional_obs=False, eye_width=320, eye_height=240, device=0,
                  max_episode_steps=int(15e6), render_every_step=True, device_obs=False, solver=None, dynamics_randomization=None,
                  camera_randomization=None, appearance_randomization=None, actuator_randomization=None, *, kinematic_obs=False,
-                 kinematic_points=None, ray_sensors=None, distance_pairs=None, distance_max=None, contact_obs=False, goals=None, goal_stride=1):
+                 kinematic_points=None, dynamics_obs=False, ray_sensors=None, distance_pairs=None, distance_max=None, contact_obs=False, goals=None,
+                 goal_stride=1):
         self.num_envs = int(num_envs)
         self._goals = None if goals is None else self._check_goals(goals, OBJECT_NAMES[:int(objects)], int(eye_height), int(eye_width))
         self.goal_stride = int(goal_stride)
@@ -144,6 +150,12 @@ class REALRobotVectorEnv(_Base):
                 joint_velocities=box(nat.N_JOINTS), link_poses=box(n_links, 7), link_velocities=box(n_links, 6),
                 object_velocities=box(int(objects), 6), point_positions=box(n_pts, 3), point_velocities=box(n_pts, 6),
                 jacobian=box(n_pts, 6, nat.N_JOINTS)))
+        self.dynamics_obs = bool(dynamics_obs)
+        if self.dynamics_obs:
+            self.single_observation_space = spaces.Dict(dict(
+                self.single_observation_space.spaces,
+                mass_matrix=spaces.Box(low=-np.inf, high=np.inf, shape=(nat.N_JOINTS, nat.N_JOINTS), dtype=np.float32),
+                bias=spaces.Box(low=-np.inf, high=np.inf, shape=(nat.N_JOINTS,), dtype=np.float32)))
         ray_table = None
         if ray_sensors is not None:
             if not (isinstance(ray_sensors, (tuple, list)) and len(ray_sensors) == 2):
@@ -407,6 +419,11 @@ class REALRobotVectorEnv(_Base):
             ko = be.kinematic_observations(host=not self.device_obs)
             for key, name in self.KINEMATIC_KEYS:
                 obs[key] = ko[name]
+        if self.dynamics_obs:
+            pd = be.posture_dynamics(host=not self.device_obs)
+            for key in ("mass_matrix", "bias"):       # the present-state form has K = 1: [N, 1, ...] -> [N, ...]
+                v = pd[key]
+                obs[key] = nat.DeviceBuffer(v.ptr, v.shape[:1] + v.shape[2:], v.typestr, be) if self.device_obs else v[:, 0]
         if self.ray_sensors:
             rc = be.ray_cast(host=not self.device_obs)
             obs["ray_distance"], obs["ray_uid"] = be.ray_column(rc['hit'], 1), be.ray_column(rc['id'], 0)
