@@ -1148,7 +1148,7 @@ enum { RR_PD_INVERSE = 1u };   /* flags */
  * compact for the K of the last call (0 before the first), and `bytes` reports that.  STREAM CONTRACT for readers as for the other
  * zero-copy views: the kernel runs on the library's stream behind the work enqueued before it; readers on another stream order
  * themselves after the call (event / rr_sync), and a later call rewrites the buffers in place.
- * Out of scope: torque control in the step; joint damping or motor terms; the operational-space inertia itself (form
+ * Applying such torques is rr_set_joint_torques (below).  Out of scope: joint damping or motor terms; the operational-space inertia itself (form
  * (J M^-1 J^T)^-1 from this query and rr_posture_kinematics); derivatives of the dynamics. */
 int rr_posture_dynamics(rr_env *env, const float *postures /* f32 [N][K][11] or NULL */, const float *velocities /* f32 [N][K][11] or NULL */,
                         const float *accelerations /* f32 [N][K][11] or NULL */, int32_t n_postures, int32_t on_device, uint32_t flags);
@@ -1156,6 +1156,55 @@ int rr_posture_dynamics(rr_env *env, const float *postures /* f32 [N][K][11] or 
 int rr_posture_dynamics_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
 /* Synchronising copy of a whole RR_PD_* buffer (its `bytes`) to host memory. */
 int rr_posture_dynamics_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
+
+/* ---- Joint torque inputs of the step: feed-forward and torque control (additive in ABI 7) ---------------------------------------------
+ * rr_posture_dynamics computes joint torques; this applies them: pybullet's setJointMotorControl2(TORQUE_CONTROL, force=tau), the
+ * actuation-force tensor of batched simulators.  The handle holds a table tau f32 [N][11] over the eleven INDEPENDENT joints in the
+ * order of the state's q[11] (N m), all zero on a fresh handle.  EVERY rr_step uses the table in force -- each inner step of the
+ * macro and episode entry points that call rr_step included -- and solves with
+ *     qd*' = qd* + dt M^-1 tau
+ * where qd* = qd + dt M^-1 (-bias - damping qd) and M^-1 are the values of the env's preparation record (RR_F_PREP) for this step.
+ * Motor rows, limit rows and contacts act on top, exactly as without torques.  Three uses:
+ *   max_force = 0 on a joint (rr_set_env_actuators) plus tau   torque control of that joint;
+ *   default motors plus tau                                    feed-forward under the position motor;
+ *   tau = RR_PD_BIAS of rr_posture_dynamics' present-state form  holds the arm against gravity (and the velocity terms).
+ * Joint damping is NOT compensated: it remains in qd*.  Values are NOT clamped: no torque limit, no saturation model.
+ * PERSISTENT, unlike pybullet: nothing clears the table after a step.  It holds until the next rr_set_joint_torques, like the motor
+ * targets.  A command-side setting that stays with its env: rr_reset, an episode's auto-reset, rr_write_state, rr_set_state,
+ * rr_copy_envs (forks, snapshot saves and loads) and rr_checkpoint_restore keep the table as it is, and neither a snapshot nor a
+ * checkpoint carries it.
+ * The zero-row rule.  An env whose row is all zero (either sign) is NOT TOUCHED by the step: its qd* keeps its bits, so a masked or
+ * partly zero table leaves those envs bit for bit as without the feature.  A frozen env (error flag bit 0) is not touched either.
+ * With no torque set at all -- a fresh handle, or after the clearing call below -- the step launches exactly the kernels it launched
+ * before this entry point existed.
+ * rr_set_joint_torques copies the rows of the masked envs (env_mask u8 [N], NULL: all envs) from `torques` f32 [N][11], C order, into
+ * the table with one launch on the library's stream.
+ *   torques_on_device != 0: device memory, read IN PLACE on the library's stream under the STREAM CONTRACT of rr_write_state (produced
+ *     on that stream or ordered before it; not rewritten before later work on that stream); NOT validated; the call returns without
+ *     waiting.  torques_on_device == 0: host memory; the masked rows are checked for finiteness -- a non-finite value is RR_EINVAL and
+ *     the call changes NOTHING --, then staged, and the call waits for the stream.
+ *   mask_on_device says the same of env_mask.  With both given they must live on the same side: a mixed pair is RR_EINVAL.
+ *   torques == NULL zeroes the masked rows.  torques == NULL and env_mask == NULL zeroes the table and turns the feature OFF: the
+ *     steps launch no torque kernel until the next call with a table.  (From the first successful call with a table until then every
+ *     step launches it, whatever the values: rows that happen to be zero are found by the kernel's own test.)
+ * The look-ahead stays valid: the call touches neither the state nor the preparation record, and the step applies the table BEHIND
+ * the preparation, so a controller that sets new torques every step keeps the overlap of step t with the preparation of step t + 1.
+ * For users who think in the NINE entries of a joint command (dq = Q dcmd with the [11][9] matrix of rr_kinematic_observations: entry
+ * 7 drives q[7] and q[9], entry 8 drives -q[8] and -q[10]): tau11 = Q tau9 applies entry 7 to both of its joints and minus entry 8
+ * to both of its; the generalised force on a command coordinate is Q^T tau11.
+ * Errors: RR_EINVAL for a null env, a mixed pair, a non-finite host row; RR_EDEVICE for a failed allocation (all or nothing through
+ * the handle's memory owner; the table, N x 44 bytes, zero-filled, on first use -- by this call with a table, rr_get_joint_torques or
+ * rr_joint_torque_buffer) or a device error.
+ * Out of scope: wrenches on objects; torque limits and saturation; compensation of joint damping; the table in forks, snapshots and
+ * checkpoints; a controller library. */
+int rr_set_joint_torques(rr_env *env, const float *torques /* f32 [N][11] or NULL */, int32_t torques_on_device, const uint8_t *env_mask /* u8 [N] or NULL */,
+                         int32_t mask_on_device);
+/* Synchronising copy of the table in force, f32 [N][11], to host memory. */
+int rr_get_joint_torques(rr_env *env, float *out_host);
+/* Zero-copy device pointer + size in bytes (N x 44) of the table: valid until rr_destroy, the pointer never changes.  A caller may
+ * WRITE it in stream order (on the library's stream or ordered before later work on it): the next step uses what it finds --
+ * provided the feature is on (a successful rr_set_joint_torques with a table since the last clearing call). */
+int rr_joint_torque_buffer(rr_env *env, void **dev_ptr, size_t *bytes);
 
 /* Batched damped-least-squares inverse kinematics for link 7 (gripper `base`), seeded with each env's current joints.
  * Replaces pybullet.calculateInverseKinematics(0, 7, pos, orn, maxNumIterations=1000, residualThreshold=0.001) in

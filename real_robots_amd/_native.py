@@ -48,7 +48,8 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_swept_clearance', 'rr_sweep_reach', 'rr_sweep_buffer', 'rr_sweep_copy_to_host',
            'rr_posture_kinematics', 'rr_posture_kinematics_buffer', 'rr_posture_kinematics_copy_to_host',
            'rr_posture_ik', 'rr_posture_ik_buffer', 'rr_posture_ik_copy_to_host',
-           'rr_posture_dynamics', 'rr_posture_dynamics_buffer', 'rr_posture_dynamics_copy_to_host')
+           'rr_posture_dynamics', 'rr_posture_dynamics_buffer', 'rr_posture_dynamics_copy_to_host',
+           'rr_set_joint_torques', 'rr_get_joint_torques', 'rr_joint_torque_buffer')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
@@ -271,6 +272,9 @@ def load_library():
     L.rr_posture_dynamics.argtypes = [vp, vp, vp, vp, i32, i32, C.c_uint32]
     L.rr_posture_dynamics_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rr_posture_dynamics_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
+    L.rr_set_joint_torques.argtypes = [vp, vp, i32, vp, i32]
+    L.rr_get_joint_torques.argtypes = [vp, vp]
+    L.rr_joint_torque_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]

@@ -1406,6 +1406,84 @@ class BatchedREALRobotEnv:
         del keep
         return {name: self.posture_dynamics_buffer(i, host=host) for i, name in enumerate(nat.PD_FIELDS) if inverse or name != 'mass_inverse'}
 
+    # ------------------------------------------------------------------ joint torque inputs of the step
+    @classmethod
+    def _torque_args(cls, N, torques, env_mask):
+        """The arguments of `set_joint_torques` for a handle of N envs -> (address or None, torques on the device, address or None,
+        mask on the device, keep-alive objects).  Every violation -- shape, dtype, contiguity, a non-finite host value in a masked
+        row, torques and mask on different sides -- is a ValueError raised here, before the native call; nothing of a handle is needed."""
+        tp = mp = None
+        t_dev = m_dev = 0
+        keep = []
+        if env_mask is not None:
+            if _on_device(env_mask):
+                mp, m_dev, k = cls._state_arg(None, env_mask, 'env_mask', ('uint8', 'bool'), (N,))
+            else:
+                k, mp = _env_mask(env_mask, N)
+            keep.append(k)
+        if torques is not None:
+            if _on_device(torques):
+                # the [N, 1, 11] view of posture_dynamics()'s present-state form is the same memory as [N, 11]
+                shape = tuple(torques.shape) if hasattr(torques, 'shape') else tuple(torques.__cuda_array_interface__['shape'])
+                full = (N, 1, nat.N_JOINTS) if shape == (N, 1, nat.N_JOINTS) else (N, nat.N_JOINTS)
+                tp, t_dev, k = cls._state_arg(None, torques, 'torques', ('float32',), full)
+            else:
+                if hasattr(torques, 'is_cuda') and hasattr(torques, 'numpy'):      # a CPU torch tensor
+                    torques = torques.numpy()
+                try:
+                    with np.errstate(over='ignore'):
+                        a = np.ascontiguousarray(np.broadcast_to(np.asarray(torques, dtype=np.float64).astype(np.float32), (N, nat.N_JOINTS)))
+                except (ValueError, TypeError):
+                    raise ValueError("torques: cannot broadcast an array of shape %s to %s" % (np.shape(torques), (N, nat.N_JOINTS)))
+                rows = a if env_mask is None or m_dev else a[keep[0] != 0]      # (a host mask: only its rows have to be finite)
+                if not np.isfinite(rows).all():
+                    raise ValueError("torques must be finite (in float32) in the rows of env_mask")
+                tp, t_dev, k = a.ctypes.data, 0, a
+            keep.append(k)
+            if env_mask is not None and t_dev != m_dev:
+                raise ValueError("set_joint_torques: torques and env_mask must live on the same side (torques on the %s, env_mask on the %s)"
+                                 % (('host', 'device')[t_dev], ('host', 'device')[m_dev]))
+        return tp, t_dev, mp, m_dev, keep
+
+    def set_joint_torques(self, torques=None, env_mask=None):
+        """Joint torques for the step (rr_set_joint_torques; pybullet's setJointMotorControl2(TORQUE_CONTROL, force=tau) for the whole
+        batch): a table tau float32 [N, 11] over the eleven independent joints in the order of q[11] of the state (N m), all zero on a
+        fresh handle.  Every step from now on solves with qd*' = qd* + dt M^-1 tau, the motors, joint limits and contacts on top as
+        before: `set_env_actuators(max_force=0)` on a joint plus tau is torque control of that joint, default motors plus tau is
+        feed-forward under the position motor, tau = `posture_dynamics()['bias']` holds the arm against gravity.  Joint damping is not
+        compensated, values are not clamped.  PERSISTENT, unlike pybullet: nothing clears the table after a step, and `reset`,
+        auto-resets, `write_state`, `state = ...`, `fork`, `load_snapshot` and `restore` keep it (a command-side setting that stays
+        with its env, like the motor targets; snapshots and checkpoints do not carry it).
+        torques: a numpy array that broadcasts to [N, 11] (checked for finiteness in the rows of env_mask, staged, synchronous), or a
+        CUDA torch tensor / `__cuda_array_interface__` object of the full shape [N, 11] -- or [N, 1, 11], the view `posture_dynamics()`
+        returns at the present state, taken without a copy --, float32, C-contiguous, read in place on the library's stream without
+        waiting and not validated (produce it on that stream or synchronise first).  env_mask: uint8 / bool [N] (None: all envs), on
+        the same side as the torques; the other envs keep their rows.  torques=None zeroes the rows of env_mask; torques=None without a
+        mask zeroes the table and turns the feature off: the steps then launch exactly what they launched before.  An env whose row
+        is all zero is not touched by the step -- bit for bit as without torques --, neither is a frozen env.  The look-ahead stays
+        valid: new torques every step cost one small launch.
+        For torques over the nine entries of a joint command, `torques9 @ _native.Q_FROM_CMD.T` ([N, 9] -> [N, 11]) applies entry 7 to
+        q[7] and q[9] and minus entry 8 to q[8] and q[10]; `torques11 @ _native.Q_FROM_CMD` is the generalised force on the command
+        entries."""
+        tp, t_dev, mp, m_dev, keep = self._torque_args(self.N, torques, env_mask)
+        nat.check(self.L.rr_set_joint_torques(self.h, tp, t_dev, mp, m_dev))
+        del keep
+
+    def joint_torques(self):
+        """Host copy (after a wait) of the joint torque table in force: float32 [N, 11]."""
+        out = np.empty((self.N, nat.N_JOINTS), np.float32)
+        nat.check(self.L.rr_get_joint_torques(self.h, out.ctypes.data))
+        return out
+
+    @property
+    def joint_torque_buffer(self):
+        """The joint torque table as a device view, float32 [N, 11] (zero copy, DLPack / `__cuda_array_interface__`; the pointer
+        never changes).  A write made in the library's stream order is used by the next step, provided the feature is on
+        (`set_joint_torques` with a table since the last clearing call)."""
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(self.L.rr_joint_torque_buffer(self.h, C.byref(p), C.byref(n)))
+        return nat.DeviceBuffer(p.value, (self.N, nat.N_JOINTS), '<f4', self)
+
     def body_row_names(self):
         """The bodies of the rows of body_force / body_partners: the 17 URDF links, then this handle's objects (the rows of the
         objects it does not have, up to 20, stay zero)."""

@@ -178,6 +178,11 @@ struct rr_env : ModelTables {
     float *pd_buf[RR_PD_COUNT] = {};
     int pd_k = 0;                  // rows per env of the last call: 0 before the first
     float *pd_stage = nullptr;
+    // joint torque inputs of the step (rr_set_joint_torques): the table [N][11], allocated zero-filled on first use; a host caller's rows go
+    // through jt_stage [N][11]; jt_on: rr_step launches k_joint_torque (from the first successful set with a table until the clearing call)
+    float *jt_table = nullptr;
+    float *jt_stage = nullptr;
+    bool jt_on = false;
     MemOwner mem;                  // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
     bool created = false;
     bool timing = false;
@@ -1359,6 +1364,10 @@ int rr_step(rr_env *e, const float *joint_cmd, int32_t cmd_on_device, int32_t re
     if (!e->la_valid) state_part_all(e, overlap);
     e->cur ^= 1; e->la_valid = false;           // the frame the collision pass filled is the one this step solves
     bind_frames(e);
+    // ---- joint torques (rr_torque.inc): qd* += dt M^-1 tau in this step's preparation record.  Here the main stream is behind the
+    // whole look-ahead (every step path ends with the main stream waiting for ev_join / ev_join2 or ev_dyn, or ran it on this stream;
+    // state_part_all above likewise), and every solve below is on this stream or behind ev_fork recorded on it.  Under no timer.
+    if (e->jt_on) hipLaunchKernelGGL(k_joint_torque, dim3((unsigned)((N * 16 + JT_THREADS - 1) / JT_THREADS)), dim3(JT_THREADS), 0, e->stream, e->P, e->D, (const float *)e->jt_table);
     // a device-resident command buffer is read in place by the solve kernels (stream order protects it like a copy would)
     e->D.cmd_in = (joint_cmd && cmd_on_device) ? joint_cmd : e->D.cmd;
     // ---- the plan of this step: the one reading of the lagged list lengths (behind the run-ahead wait: as fresh as it gets)
@@ -2351,6 +2360,76 @@ int rr_posture_dynamics_copy_to_host(rr_env *e, int32_t which, void *dst, size_t
     HIPCHK(hipSetDevice(e->cfg.device));
     if (bytes == 0) return RR_OK;
     HIPCHK(hipMemcpyAsync(dst, e->pd_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return RR_OK;
+}
+
+// ---- joint torque inputs of the step (rr_torque.inc) ------------------------------------------------------------------------------------
+// The table tau [N][11] and, for a host caller, its staging block: on first use, all or nothing, the table zero-filled.
+static int ensure_torques(rr_env *e, const char *who, bool stage = false) {
+    stage = stage && !e->jt_stage;
+    const bool table = !e->jt_table;
+    if (!table && !stage) return RR_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    float *t = nullptr, *st = nullptr;
+    MemPart parts[2];
+    size_t n = 0;
+    const size_t bytes = (size_t)e->P.N * NB * 4;
+    if (table) parts[n++] = mem_part(&t, bytes);
+    if (stage) parts[n++] = mem_part(&st, bytes, false);
+    RRCHK(mem_get(e, parts, n, (std::string(who) + ": allocating the joint torque table").c_str()));
+    if (table) e->jt_table = t;
+    if (stage) e->jt_stage = st;
+    return RR_OK;
+}
+
+// The rows of the masked envs into the handle's table, one launch on the main stream: behind every step enqueued before it (whose
+// k_joint_torque read the table on this stream), in front of the next one.  A command-side setting like the motor targets: the
+// state, the preparation record and la_valid are not touched -- the step applies the table behind the look-ahead, whatever it holds.
+int rr_set_joint_torques(rr_env *e, const float *torques, int32_t torques_on_device, const uint8_t *env_mask, int32_t mask_on_device) {
+    if (!e) return fail(RR_EINVAL, "rr_set_joint_torques: null env");
+    if (torques && env_mask && !torques_on_device != !mask_on_device)
+        return fail(RR_EINVAL, std::string("rr_set_joint_torques: torques and env_mask must live on the same side (torques on the ") +
+                                   (torques_on_device ? "device" : "host") + ", env_mask on the " + (mask_on_device ? "device" : "host") + ")");
+    const int N = e->P.N;
+    if (torques && !torques_on_device) {      // host rows are validated before anything changes
+        for (int i = 0; i < N; i++) {
+            if (env_mask && !env_mask[i]) continue;
+            for (int j = 0; j < NB; j++)
+                if (!std::isfinite(torques[(size_t)i * NB + j]))
+                    return fail(RR_EINVAL, "rr_set_joint_torques: env " + std::to_string(i) + ", joint " + std::to_string(j) + ": the torque is not finite");
+        }
+    }
+    if (!torques && !e->jt_table) return RR_OK;      // zeroing rows of a table that does not exist yet: it is all zero, the feature off
+    RRCHK(ensure_torques(e, "rr_set_joint_torques", torques && !torques_on_device));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const float *src = torques;
+    const unsigned char *m = env_mask;
+    if (torques && !torques_on_device) { HIPCHK(hipMemcpyAsync(e->jt_stage, torques, (size_t)N * NB * 4, hipMemcpyHostToDevice, e->stream)); src = e->jt_stage; }
+    const bool host_mask = env_mask && !mask_on_device;
+    if (host_mask) { HIPCHK(hipMemcpyAsync(e->mask_dev, env_mask, N, hipMemcpyHostToDevice, e->stream)); m = e->mask_dev; }
+    hipLaunchKernelGGL(k_joint_torque_set, dim3((unsigned)((N * NB + 255) / 256)), dim3(256), 0, e->stream, N, src, m, e->jt_table);
+    HIPCHK(hipGetLastError());
+    if (torques) e->jt_on = true;
+    else if (!env_mask) e->jt_on = false;      // the clearing call: the steps launch no torque kernel until the next table
+    if ((torques && !torques_on_device) || host_mask) HIPCHK(hipStreamSynchronize(e->stream));   // the arguments are host memory
+    return RR_OK;
+}
+
+int rr_joint_torque_buffer(rr_env *e, void **dev_ptr, size_t *bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_joint_torque_buffer: null env");
+    RRCHK(ensure_torques(e, "rr_joint_torque_buffer"));
+    if (dev_ptr) *dev_ptr = e->jt_table;
+    if (bytes) *bytes = (size_t)e->P.N * NB * 4;
+    return RR_OK;
+}
+
+int rr_get_joint_torques(rr_env *e, float *out_host) {
+    if (!e) return fail(RR_EINVAL, "rr_get_joint_torques: null env");
+    if (!out_host) return fail(RR_EINVAL, "rr_get_joint_torques: null destination");
+    RRCHK(ensure_torques(e, "rr_get_joint_torques"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    HIPCHK(hipMemcpyAsync(out_host, e->jt_table, (size_t)e->P.N * NB * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return RR_OK;
 }
