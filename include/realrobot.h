@@ -1195,7 +1195,7 @@ int rr_posture_dynamics_copy_to_host(rr_env *env, int32_t which, void *dst, size
  * Errors: RR_EINVAL for a null env, a mixed pair, a non-finite host row; RR_EDEVICE for a failed allocation (all or nothing through
  * the handle's memory owner; the table, N x 44 bytes, zero-filled, on first use -- by this call with a table, rr_get_joint_torques or
  * rr_joint_torque_buffer) or a device error.
- * Out of scope: wrenches on objects; torque limits and saturation; compensation of joint damping; the table in forks, snapshots and
+ * Wrenches on robot bodies and objects are rr_set_external_wrenches (below).  Out of scope: torque limits and saturation; compensation of joint damping; the table in forks, snapshots and
  * checkpoints; a controller library. */
 int rr_set_joint_torques(rr_env *env, const float *torques /* f32 [N][11] or NULL */, int32_t torques_on_device, const uint8_t *env_mask /* u8 [N] or NULL */,
                          int32_t mask_on_device);
@@ -1205,6 +1205,61 @@ int rr_get_joint_torques(rr_env *env, float *out_host);
  * WRITE it in stream order (on the library's stream or ordered before later work on it): the next step uses what it finds --
  * provided the feature is on (a successful rr_set_joint_torques with a table since the last clearing call). */
 int rr_joint_torque_buffer(rr_env *env, void **dev_ptr, size_t *bytes);
+
+/* ---- External wrenches on robot bodies and objects in the step (additive in ABI 7) ---------------------------------------------------
+ * pybullet's applyExternalForce / applyExternalTorque, the rigid-body force tensor of batched simulators: push an object, disturb the
+ * arm, cancel a weight, model a payload on the gripper, feed a learned residual force.  The handle holds a table w f32
+ * [N][RR_XW_BODIES][6], all zero on a fresh handle:
+ *   rows 0..10   the eleven moving robot bodies; row j is the rigid body that joint j of the state's q[11] moves (the bodies of the
+ *                preparation record, RR_F_PREP);
+ *   rows 11..13  objects 0..2.  The step never reads the rows of objects the handle does not have; they are stored and read back as
+ *                given.
+ * A row is {Fx, Fy, Fz, Tx, Ty, Tz} in the WORLD frame (N, N m).  The force acts at the body's CENTRE OF MASS, the torque is about that
+ * centre: for a robot body c_b = p_b + R_b com_b (the centre the mass matrix uses, body_com of the model), for an object the position
+ * of its state.  EVERY rr_step uses the table in force -- each inner step of the macro and episode entry points that call rr_step
+ * included -- and adds, behind the preparation and in front of the solve,
+ *     object i:  v*' = v* + dt F / m_i      w*' = w* + dt Iinv_i T
+ *     robot:     tau_k = sum over the bodies b that joint k moves of a_k . ((c_b - p_k) x F_b + T_b)      qd*' = qd* + dt M^-1 tau
+ * with m_i the ENV's own mass (rr_set_object_dynamics), Iinv_i the world inverse inertia of the pose that counts -- for an object the
+ * out-of-bounds rule sends home that is the HOME pose, and the wrench acts on it there --, a_k, p_k the world axis and origin of joint
+ * k, and M^-1, qd*, v*, w* the values of the env's preparation record (RR_F_PREP) for this step.  Contacts, motor rows and limit rows
+ * act on top, exactly as without wrenches.  Values are NOT clamped.  With joint torques (rr_set_joint_torques) also on, the torque
+ * term is added first, then the wrench term.
+ * A force at a point, or in a body frame: compose it in torch -- T += r x F for a force at c + r, F_world = R F_body with R from the
+ * link poses of rr_kinematic_observations / the object poses -- and write the buffer; the kernel knows world-frame wrenches at the
+ * centre of mass only.
+ * PERSISTENT, unlike pybullet (whose external forces last one step): nothing clears the table after a step.  It holds until the next
+ * rr_set_external_wrenches, like the joint torque table.  rr_reset, an episode's auto-reset, rr_write_state, rr_set_state, rr_copy_envs
+ * (forks, snapshot saves and loads) and rr_checkpoint_restore keep the table as it is, and neither a snapshot nor a checkpoint
+ * carries it.
+ * The zero rule, PER TARGET.  With all eleven robot rows of an env zero (either sign) its qd* keeps its bits; an object whose row is
+ * zero keeps the bits of its v* and w*: such targets are NOT TOUCHED, bit for bit as without the feature.  A frozen env (error flag
+ * bit 0) is not touched.  A NaN counts as non-zero.  With no wrench set at all -- a fresh handle, or after the clearing call below --
+ * the step launches exactly the kernels it launched before this entry point existed.
+ * rr_set_external_wrenches copies the rows of the masked envs (env_mask u8 [N], NULL: all envs) from `wrenches` f32 [N][14][6], C
+ * order, into the table with one launch on the library's stream.  The contract of rr_set_joint_torques, point for point:
+ *   wrenches_on_device != 0: device memory, read IN PLACE on the library's stream under the STREAM CONTRACT of rr_write_state; NOT
+ *     validated; the call returns without waiting.  wrenches_on_device == 0: host memory; the masked envs' rows are checked for
+ *     finiteness -- a non-finite value is RR_EINVAL naming env, row and entry, and the call changes NOTHING --, then staged, and the
+ *     call waits for the stream.
+ *   mask_on_device says the same of env_mask.  With both given they must live on the same side: a mixed pair is RR_EINVAL.
+ *   wrenches == NULL zeroes the masked rows.  wrenches == NULL and env_mask == NULL zeroes the table and turns the feature OFF.
+ *     Zeroing a table that was never allocated is RR_OK with nothing allocated.
+ * The look-ahead stays valid: the call touches neither the state nor the preparation record.
+ * Errors: RR_EINVAL for a null env, a mixed pair, a non-finite host row; RR_EDEVICE for a failed allocation (all or nothing through
+ * the handle's memory owner; the table, N x 336 bytes, zero-filled, on first use -- by this call with a table,
+ * rr_get_external_wrenches or rr_external_wrench_buffer) or a device error.
+ * Out of scope: body-frame wrenches and application points inside the kernel; timed or one-shot wrenches that clear themselves;
+ * wrenches on the static scene; force limits; the table in forks, snapshots and checkpoints. */
+#define RR_XW_BODIES 14
+int rr_set_external_wrenches(rr_env *env, const float *wrenches /* f32 [N][14][6] or NULL */, int32_t wrenches_on_device,
+                             const uint8_t *env_mask /* u8 [N] or NULL */, int32_t mask_on_device);
+/* Synchronising copy of the table in force, f32 [N][14][6], to host memory. */
+int rr_get_external_wrenches(rr_env *env, float *out_host);
+/* Zero-copy device pointer + size in bytes (N x 336) of the table: valid until rr_destroy, the pointer never changes.  A caller may
+ * WRITE it in stream order (on the library's stream or ordered before later work on it): the next step uses what it finds --
+ * provided the feature is on (a successful rr_set_external_wrenches with a table since the last clearing call). */
+int rr_external_wrench_buffer(rr_env *env, void **dev_ptr, size_t *bytes);
 
 /* Batched damped-least-squares inverse kinematics for link 7 (gripper `base`), seeded with each env's current joints.
  * Replaces pybullet.calculateInverseKinematics(0, 7, pos, orn, maxNumIterations=1000, residualThreshold=0.001) in

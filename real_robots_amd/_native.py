@@ -49,12 +49,15 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_posture_kinematics', 'rr_posture_kinematics_buffer', 'rr_posture_kinematics_copy_to_host',
            'rr_posture_ik', 'rr_posture_ik_buffer', 'rr_posture_ik_copy_to_host',
            'rr_posture_dynamics', 'rr_posture_dynamics_buffer', 'rr_posture_dynamics_copy_to_host',
-           'rr_set_joint_torques', 'rr_get_joint_torques', 'rr_joint_torque_buffer')
+           'rr_set_joint_torques', 'rr_get_joint_torques', 'rr_joint_torque_buffer',
+           'rr_set_external_wrenches', 'rr_get_external_wrenches', 'rr_external_wrench_buffer')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
 ACT_ROW = ('kp', 'kd', 'max_force', 'damping')
 N_JOINTS = 11
+# rr_set_external_wrenches: the rows of the wrench table [N, XW_BODIES, 6] -- the eleven moving robot bodies (row j: the body joint j moves), then objects 0..2
+XW_BODIES = 14
 # buffers of rr_episode_buffer (the RR_EP_* enum: goals and episodes on the device)
 (EP_SCORE, EP_REWARD, EP_DONE, EP_GOAL_INDEX, EP_EPISODE, EP_FINAL_OBS, EP_GOAL_POS, EP_GOAL_RGB) = range(8)
 EP_NAMES = ('score', 'reward', 'done', 'goal_index', 'episode', 'final_obs', 'goal_pos', 'goal_rgb')
@@ -275,6 +278,9 @@ def load_library():
     L.rr_set_joint_torques.argtypes = [vp, vp, i32, vp, i32]
     L.rr_get_joint_torques.argtypes = [vp, vp]
     L.rr_joint_torque_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rr_set_external_wrenches.argtypes = [vp, vp, i32, vp, i32]
+    L.rr_get_external_wrenches.argtypes = [vp, vp]
+    L.rr_external_wrench_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]

@@ -1484,6 +1484,117 @@ class BatchedREALRobotEnv:
         nat.check(self.L.rr_joint_torque_buffer(self.h, C.byref(p), C.byref(n)))
         return nat.DeviceBuffer(p.value, (self.N, nat.N_JOINTS), '<f4', self)
 
+    # ------------------------------------------------------------------ external wrenches of the step
+    @staticmethod
+    def _wrench_rows(n_objects=3):
+        """The names of the rows of the wrench table: robot row j is the first name of LINK_NAMES whose link_body is j (the body joint
+        j of q[11] moves), then the objects of a handle with `n_objects` objects."""
+        from .model import load_model
+        link_body = [int(b) for b in load_model()['link_body']]
+        return [nat.LINK_NAMES[link_body.index(j)] for j in range(nat.N_JOINTS)] + list(OBJECT_NAMES[:int(n_objects)])
+
+    @classmethod
+    def _wrench_args(cls, N, wrenches, env_mask, n_objects=3):
+        """The arguments of `set_external_wrenches` for a handle of N envs and `n_objects` objects -> (address or None, wrenches on the
+        device, address or None, mask on the device, keep-alive objects).  Every violation -- shape, dtype, contiguity, a non-finite
+        host value in a masked row, an unknown row name, an object the handle does not have, wrenches and mask on different sides --
+        is a ValueError raised here, before the native call; nothing of a handle is needed."""
+        wp = mp = None
+        w_dev = m_dev = 0
+        keep = []
+        full = (N, nat.XW_BODIES, 6)
+        if env_mask is not None:
+            if _on_device(env_mask):
+                mp, m_dev, k = cls._state_arg(None, env_mask, 'env_mask', ('uint8', 'bool'), (N,))
+            else:
+                k, mp = _env_mask(env_mask, N)
+            keep.append(k)
+        if wrenches is not None:
+            if _on_device(wrenches):
+                wp, w_dev, k = cls._state_arg(None, wrenches, 'wrenches', ('float32',), full)
+            else:
+                if isinstance(wrenches, dict):
+                    names = cls._wrench_rows(n_objects)
+                    table = np.zeros(full, np.float64)
+                    for key, v in wrenches.items():
+                        if isinstance(key, str):
+                            if key not in names:
+                                raise ValueError("wrenches: unknown row %r (rows of this handle: %s)" % (key, ', '.join(names)))
+                            row = names.index(key)
+                        elif isinstance(key, (int, np.integer)) and 0 <= int(key) < nat.N_JOINTS + int(n_objects):
+                            row = int(key)
+                        else:
+                            raise ValueError("wrenches: a row is a name of wrench_row_names() or an index in [0, %d), not %r" % (nat.N_JOINTS + int(n_objects), key))
+                        if hasattr(v, 'is_cuda') and hasattr(v, 'numpy'):
+                            v = v.numpy()
+                        try:
+                            table[:, row] = np.broadcast_to(np.asarray(v, dtype=np.float64), (N, 6))
+                        except (ValueError, TypeError):
+                            raise ValueError("wrenches[%r]: cannot broadcast an array of shape %s to %s" % (key, np.shape(v), (N, 6)))
+                    wrenches = table
+                if hasattr(wrenches, 'is_cuda') and hasattr(wrenches, 'numpy'):      # a CPU torch tensor
+                    wrenches = wrenches.numpy()
+                try:
+                    with np.errstate(over='ignore'):
+                        a = np.ascontiguousarray(np.broadcast_to(np.asarray(wrenches, dtype=np.float64).astype(np.float32), full))
+                except (ValueError, TypeError):
+                    raise ValueError("wrenches: cannot broadcast an array of shape %s to %s" % (np.shape(wrenches), full))
+                rows = a if env_mask is None or m_dev else a[keep[0] != 0]      # (a host mask: only its envs' rows have to be finite)
+                if not np.isfinite(rows).all():
+                    raise ValueError("wrenches must be finite (in float32) in the rows of env_mask")
+                wp, w_dev, k = a.ctypes.data, 0, a
+            keep.append(k)
+            if env_mask is not None and w_dev != m_dev:
+                raise ValueError("set_external_wrenches: wrenches and env_mask must live on the same side (wrenches on the %s, env_mask on the %s)"
+                                 % (('host', 'device')[w_dev], ('host', 'device')[m_dev]))
+        return wp, w_dev, mp, m_dev, keep
+
+    def set_external_wrenches(self, wrenches=None, env_mask=None):
+        """External wrenches on robot bodies and objects for the step (rr_set_external_wrenches; pybullet's applyExternalForce /
+        applyExternalTorque for the whole batch): a table float32 [N, 14, 6], all zero on a fresh handle.  Rows 0..10 are the eleven
+        moving robot bodies -- row j the body that joint j of q[11] moves --, rows 11..13 objects 0..2 (`wrench_row_names()`); a row
+        is {Fx, Fy, Fz, Tx, Ty, Tz} in the WORLD frame (N, N m), the force at the body's centre of mass, the torque about it.  Every
+        step from now on adds, behind the preparation and in front of the solve, v*' = v* + dt F / m and w*' = w* + dt Iinv T for an
+        object (the env's own mass and world inverse inertia) and qd*' = qd* + dt M^-1 tau for the robot, tau_k the sum over the
+        bodies b that joint k moves of a_k . ((c_b - p_k) x F_b + T_b); contacts, motors and joint limits act on top as before.
+        Values are not clamped.  With joint torques also set the torque term is added first.  PERSISTENT, unlike pybullet: nothing
+        clears the table after a step, and `reset`, auto-resets, `write_state`, `state = ...`, `fork`, `load_snapshot` and `restore`
+        keep it (snapshots and checkpoints do not carry it).
+        wrenches: a numpy array that broadcasts to [N, 14, 6]; or a dict {row name or index: array broadcasting to [N, 6]}, the
+        other rows zero (naming an object the handle does not have raises) -- both checked for finiteness in the rows of env_mask,
+        staged, synchronous --; or a CUDA torch tensor / `__cuda_array_interface__` object of the full shape, float32, C-contiguous,
+        read in place on the library's stream without waiting and not validated.  env_mask: uint8 / bool [N] (None: all envs), on
+        the same side as the wrenches; the other envs keep their rows.  wrenches=None zeroes the rows of env_mask; wrenches=None
+        without a mask zeroes the table and turns the feature off: the steps then launch exactly what they launched before.  The
+        zero rule holds per target: an env whose robot rows are all zero keeps the bits of its qd*, an object whose row is zero those
+        of its v* and w*; a frozen env is not touched.  The look-ahead stays valid: new wrenches every step cost one small launch.
+        A force at a point or in a body frame: compose T += r x F, or rotate with `link_pose` / the object poses, in torch, then
+        write `external_wrench_buffer`."""
+        wp, w_dev, mp, m_dev, keep = self._wrench_args(self.N, wrenches, env_mask, self.n_objects)
+        nat.check(self.L.rr_set_external_wrenches(self.h, wp, w_dev, mp, m_dev))
+        del keep
+
+    def external_wrenches(self):
+        """Host copy (after a wait) of the wrench table in force: float32 [N, 14, 6]."""
+        out = np.empty((self.N, nat.XW_BODIES, 6), np.float32)
+        nat.check(self.L.rr_get_external_wrenches(self.h, out.ctypes.data))
+        return out
+
+    @property
+    def external_wrench_buffer(self):
+        """The wrench table as a device view, float32 [N, 14, 6] (zero copy, DLPack / `__cuda_array_interface__`; the pointer never
+        changes).  A write made in the library's stream order is used by the next step, provided the feature is on
+        (`set_external_wrenches` with a table since the last clearing call)."""
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(self.L.rr_external_wrench_buffer(self.h, C.byref(p), C.byref(n)))
+        return nat.DeviceBuffer(p.value, (self.N, nat.XW_BODIES, 6), '<f4', self)
+
+    def wrench_row_names(self):
+        """The bodies of the rows of the wrench table that this handle's step reads: the eleven moving robot bodies, each under the
+        first name of `_native.LINK_NAMES` on it, then this handle's objects (the rows of the objects it does not have, up to 14,
+        are stored and never read)."""
+        return self._wrench_rows(self.n_objects)
+
     def body_row_names(self):
         """The bodies of the rows of body_force / body_partners: the 17 URDF links, then this handle's objects (the rows of the
         objects it does not have, up to 20, stay zero)."""

@@ -465,6 +465,7 @@ __device__ __forceinline__ void dispatch_order_class(int x, int N, int ntiles, i
 #include "rr_pik.inc"    // k_posture_ik: damped-least-squares IK for K target tool poses per env, each from its own seed (rr_posture_ik)
 #include "rr_pdyn.inc"    // k_posture_dynamics: mass matrix, gravity, bias, inverse dynamics and M^-1 at K candidate joint postures per env (rr_posture_dynamics)
 #include "rr_torque.inc"    // k_joint_torque: qd* += dt M^-1 tau in the preparation record, in front of a step's solve while torques are set (rr_set_joint_torques)
+#include "rr_wrench.inc"    // k_ext_wrench: the term of external wrenches on robot bodies and objects in the preparation record, in front of a step's solve while wrenches are set (rr_set_external_wrenches)
 #include "rr_ik.inc"    // inverse kinematics and macro plans (K8)
 #include "rr_render.inc"    // rasteriser: k_raster, k_shade, the list-walking render kernels
 #include "rr_gather.inc"    // delta image records for the observation gather (k_pack_delta, k_apply_delta)

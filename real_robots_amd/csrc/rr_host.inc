@@ -183,6 +183,11 @@ struct rr_env : ModelTables {
     float *jt_table = nullptr;
     float *jt_stage = nullptr;
     bool jt_on = false;
+    // external wrenches of the step (rr_set_external_wrenches): the table [N][14][6], allocated zero-filled on first use; a host caller's rows go
+    // through xw_stage [N][14][6]; xw_on: rr_step launches k_ext_wrench (from the first successful set with a table until the clearing call)
+    float *xw_table = nullptr;
+    float *xw_stage = nullptr;
+    bool xw_on = false;
     MemOwner mem;                  // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
     bool created = false;
     bool timing = false;
@@ -1368,6 +1373,8 @@ int rr_step(rr_env *e, const float *joint_cmd, int32_t cmd_on_device, int32_t re
     // whole look-ahead (every step path ends with the main stream waiting for ev_join / ev_join2 or ev_dyn, or ran it on this stream;
     // state_part_all above likewise), and every solve below is on this stream or behind ev_fork recorded on it.  Under no timer.
     if (e->jt_on) hipLaunchKernelGGL(k_joint_torque, dim3((unsigned)((N * 16 + JT_THREADS - 1) / JT_THREADS)), dim3(JT_THREADS), 0, e->stream, e->P, e->D, (const float *)e->jt_table);
+    // ---- external wrenches (rr_wrench.inc): their term in the same record, at the same point -- behind the torque term when both are on.
+    if (e->xw_on) hipLaunchKernelGGL(k_ext_wrench, dim3((unsigned)((N * 16 + XW_THREADS - 1) / XW_THREADS)), dim3(XW_THREADS), 0, e->stream, e->P, e->D, (const float *)e->xw_table);
     // a device-resident command buffer is read in place by the solve kernels (stream order protects it like a copy would)
     e->D.cmd_in = (joint_cmd && cmd_on_device) ? joint_cmd : e->D.cmd;
     // ---- the plan of this step: the one reading of the lagged list lengths (behind the run-ahead wait: as fresh as it gets)
@@ -2430,6 +2437,78 @@ int rr_get_joint_torques(rr_env *e, float *out_host) {
     RRCHK(ensure_torques(e, "rr_get_joint_torques"));
     HIPCHK(hipSetDevice(e->cfg.device));
     HIPCHK(hipMemcpyAsync(out_host, e->jt_table, (size_t)e->P.N * NB * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return RR_OK;
+}
+
+// ---- external wrenches of the step (rr_wrench.inc) ---------------------------------------------------------------------------------------
+// The table w [N][14][6] and, for a host caller, its staging block: on first use, all or nothing, the table zero-filled.
+static int ensure_wrenches(rr_env *e, const char *who, bool stage = false) {
+    stage = stage && !e->xw_stage;
+    const bool table = !e->xw_table;
+    if (!table && !stage) return RR_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    float *t = nullptr, *st = nullptr;
+    MemPart parts[2];
+    size_t n = 0;
+    const size_t bytes = (size_t)e->P.N * RR_XW_BODIES * 6 * 4;
+    if (table) parts[n++] = mem_part(&t, bytes);
+    if (stage) parts[n++] = mem_part(&st, bytes, false);
+    RRCHK(mem_get(e, parts, n, (std::string(who) + ": allocating the external wrench table").c_str()));
+    if (table) e->xw_table = t;
+    if (stage) e->xw_stage = st;
+    return RR_OK;
+}
+
+// The rows of the masked envs into the handle's table, one launch on the main stream: behind every step enqueued before it (whose
+// k_ext_wrench read the table on this stream), in front of the next one.  A command-side setting like the joint torques: the state,
+// the preparation record and the look-ahead's validity are not touched -- the step applies the table behind the look-ahead.
+int rr_set_external_wrenches(rr_env *e, const float *wrenches, int32_t wrenches_on_device, const uint8_t *env_mask, int32_t mask_on_device) {
+    if (!e) return fail(RR_EINVAL, "rr_set_external_wrenches: null env");
+    if (wrenches && env_mask && !wrenches_on_device != !mask_on_device)
+        return fail(RR_EINVAL, std::string("rr_set_external_wrenches: wrenches and env_mask must live on the same side (wrenches on the ") +
+                                   (wrenches_on_device ? "device" : "host") + ", env_mask on the " + (mask_on_device ? "device" : "host") + ")");
+    const int N = e->P.N;
+    const int ROW = RR_XW_BODIES * 6;
+    if (wrenches && !wrenches_on_device) {      // host rows are validated before anything changes
+        for (int i = 0; i < N; i++) {
+            if (env_mask && !env_mask[i]) continue;
+            for (int j = 0; j < ROW; j++)
+                if (!std::isfinite(wrenches[(size_t)i * ROW + j]))
+                    return fail(RR_EINVAL, "rr_set_external_wrenches: env " + std::to_string(i) + ", row " + std::to_string(j / 6) + ", entry " + std::to_string(j % 6) +
+                                               ": the wrench is not finite");
+        }
+    }
+    if (!wrenches && !e->xw_table) return RR_OK;      // zeroing rows of a table that does not exist yet: it is all zero, the feature off
+    RRCHK(ensure_wrenches(e, "rr_set_external_wrenches", wrenches && !wrenches_on_device));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const float *src = wrenches;
+    const unsigned char *m = env_mask;
+    if (wrenches && !wrenches_on_device) { HIPCHK(hipMemcpyAsync(e->xw_stage, wrenches, (size_t)N * ROW * 4, hipMemcpyHostToDevice, e->stream)); src = e->xw_stage; }
+    const bool host_mask = env_mask && !mask_on_device;
+    if (host_mask) { HIPCHK(hipMemcpyAsync(e->mask_dev, env_mask, N, hipMemcpyHostToDevice, e->stream)); m = e->mask_dev; }
+    hipLaunchKernelGGL(k_ext_wrench_set, dim3((unsigned)((N * ROW + 255) / 256)), dim3(256), 0, e->stream, N, src, m, e->xw_table);
+    HIPCHK(hipGetLastError());
+    if (wrenches) e->xw_on = true;
+    else if (!env_mask) e->xw_on = false;      // the clearing call: the steps launch no wrench kernel until the next table
+    if ((wrenches && !wrenches_on_device) || host_mask) HIPCHK(hipStreamSynchronize(e->stream));   // the arguments are host memory
+    return RR_OK;
+}
+
+int rr_external_wrench_buffer(rr_env *e, void **dev_ptr, size_t *bytes) {
+    if (!e) return fail(RR_EINVAL, "rr_external_wrench_buffer: null env");
+    RRCHK(ensure_wrenches(e, "rr_external_wrench_buffer"));
+    if (dev_ptr) *dev_ptr = e->xw_table;
+    if (bytes) *bytes = (size_t)e->P.N * RR_XW_BODIES * 6 * 4;
+    return RR_OK;
+}
+
+int rr_get_external_wrenches(rr_env *e, float *out_host) {
+    if (!e) return fail(RR_EINVAL, "rr_get_external_wrenches: null env");
+    if (!out_host) return fail(RR_EINVAL, "rr_get_external_wrenches: null destination");
+    RRCHK(ensure_wrenches(e, "rr_get_external_wrenches"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    HIPCHK(hipMemcpyAsync(out_host, e->xw_table, (size_t)e->P.N * RR_XW_BODIES * 6 * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return RR_OK;
 }

@@ -64,6 +64,11 @@ joints in the order of the state's q[11]) to the action dict and its spaces: ste
 BatchedREALRobotEnv.set_joint_torques in front of the step (a numpy array or a CUDA tensor).  The table is PERSISTENT: when the key is
 absent the torques in force are kept; nothing clears them after a step, and resets keep them.  Keyword-only; the default leaves dict
 and spaces as they are.
+External wrench actions: `external_wrench_actions=True` adds `"external_wrenches"` [N, 14, 6] (float32, unbounded; world-frame {force,
+torque} rows on the eleven moving robot bodies and objects 0..2, BatchedREALRobotEnv.wrench_row_names) to the action dict and its
+spaces: step() forwards it to BatchedREALRobotEnv.set_external_wrenches in front of the step (a numpy array or a CUDA tensor).  The
+table is PERSISTENT: when the key is absent the wrenches in force are kept; nothing clears them after a step, and resets keep them.
+Keyword-only; the default leaves dict and spaces as they are.
 Ray sensors: `ray_sensors=(links, segments)` -- the arguments of BatchedREALRobotEnv.set_rays: R links (names, indices, 'world' / -1)
 and segments [R, 6] {from xyz, to xyz} in those links' COM frames -- casts the table against the collision hulls where the other
 entries are gathered (BatchedREALRobotEnv.ray_cast: pybullet's rayTestBatch) and adds `ray_distance` [N, R] (float32, metres along the
@@ -125,14 +130,15 @@ class REALRobotVectorEnv(_Base):
     def __init__(self, num_envs, objects=3, additional_obs=False, eye_width=320, eye_height=240, device=0,
                  max_episode_steps=int(15e6), render_every_step=True, device_obs=False, solver=None, dynamics_randomization=None,
                  camera_randomization=None, appearance_randomization=None, actuator_randomization=None, *, kinematic_obs=False,
-                 kinematic_points=None, dynamics_obs=False, joint_torque_actions=False, ray_sensors=None, distance_pairs=None, distance_max=None, contact_obs=False, goals=None,
+                 kinematic_points=None, dynamics_obs=False, joint_torque_actions=False, external_wrench_actions=False, ray_sensors=None, distance_pairs=None, distance_max=None, contact_obs=False, goals=None,
                  goal_stride=1):
         self.num_envs = int(num_envs)
         self._goals = None if goals is None else self._check_goals(goals, OBJECT_NAMES[:int(objects)], int(eye_height), int(eye_width))
         self.goal_stride = int(goal_stride)
         self._robot = Kuka(additional_obs, objects, eye_width, eye_height, env=None)
         self.joint_torque_actions = bool(joint_torque_actions)
-        self.single_action_space, self.action_space = self._action_spaces(self._robot, self.num_envs, self.joint_torque_actions)
+        self.external_wrench_actions = bool(external_wrench_actions)
+        self.single_action_space, self.action_space = self._action_spaces(self._robot, self.num_envs, self.joint_torque_actions, self.external_wrench_actions)
         self.single_observation_space = self._robot.observation_space
         self.contact_obs = bool(contact_obs)
         if self.contact_obs:
@@ -470,25 +476,32 @@ class REALRobotVectorEnv(_Base):
         return self._obs(self.render_every_step), infos
 
     @staticmethod
-    def _action_spaces(robot, num_envs, joint_torque_actions=False):
+    def _action_spaces(robot, num_envs, joint_torque_actions=False, external_wrench_actions=False):
         """(single_action_space, action_space) of a vector env over `robot`'s joint command: the batched space is the single one with
-        a leading env axis (gymnasium.vector.utils.batch_space); `joint_torque_actions` adds the unbounded "joint_torques" entry."""
+        a leading env axis (gymnasium.vector.utils.batch_space); `joint_torque_actions` adds the unbounded "joint_torques" entry,
+        `external_wrench_actions` the unbounded "external_wrenches" entry."""
         single = {"joint_command": robot.action_space, "render": spaces.MultiBinary(1)}
         batched = {"joint_command": spaces.Box(low=np.tile(robot.min_joints, (num_envs, 1)), high=np.tile(robot.max_joints, (num_envs, 1)), dtype=float),
                    "render": spaces.MultiBinary(num_envs)}
         if joint_torque_actions:
             single["joint_torques"] = spaces.Box(low=-np.inf, high=np.inf, shape=(nat.N_JOINTS,), dtype=np.float32)
             batched["joint_torques"] = spaces.Box(low=-np.inf, high=np.inf, shape=(num_envs, nat.N_JOINTS), dtype=np.float32)
+        if external_wrench_actions:
+            single["external_wrenches"] = spaces.Box(low=-np.inf, high=np.inf, shape=(nat.XW_BODIES, 6), dtype=np.float32)
+            batched["external_wrenches"] = spaces.Box(low=-np.inf, high=np.inf, shape=(num_envs, nat.XW_BODIES, 6), dtype=np.float32)
         return spaces.Dict(single), spaces.Dict(batched)
 
     def step(self, actions):
         """actions: float array [N, 9] of joint commands (or a dict with "joint_command" [N, 9], optional "render" and, with
-        joint_torque_actions, optional "joint_torques" [N, 11]: absent, the torques in force are kept)."""
+        joint_torque_actions, optional "joint_torques" [N, 11]: absent, the torques in force are kept; with external_wrench_actions,
+        optional "external_wrenches" [N, 14, 6], likewise)."""
         render = self.render_every_step
         if isinstance(actions, dict):
             render = bool(np.any(actions.get("render", render)))
             if self.joint_torque_actions and actions.get("joint_torques") is not None:
                 self._be.set_joint_torques(actions["joint_torques"])
+            if self.external_wrench_actions and actions.get("external_wrenches") is not None:
+                self._be.set_external_wrenches(actions["external_wrenches"])
             actions = actions["joint_command"]
         self._be.step(np.asarray(actions, dtype=np.float32), render=render)
         self._steps += 1
