@@ -116,6 +116,52 @@ SLOT_LIVE, MAX_SLOTS = -1, 64           # RR_SLOT_LIVE: the running envs as a sl
 # the fresh-start clean-up of rr_set_state behind them
 W_JOINT_POS, W_JOINT_VEL, W_OBJ_POSE, W_OBJ_VEL, W_RESET, W_FRESH = 1, 2, 4, 8, 16, 32
 W_COLUMNS = W_JOINT_POS | W_JOINT_VEL | W_OBJ_POSE | W_OBJ_VEL
+N_LINKS = 17                            # URDF links: the rows of rr_link_poses
+
+
+class QueryFamily:
+    """One whole-batch query family of include/realrobot.h: the fields tuple (the RR_*_ enum in order), the stem of its two symbols
+    `<stem>_buffer` / `<stem>_copy_to_host`, the label of the ValueError for an unknown buffer, and per buffer (dtype, shape, free).
+    A shape is made of numbers and the dims 'N' envs, 'K' rows of the last call, 'Q' pairs, 'P' points or rays, 'O' objects; `free` is
+    the one dim that is solved from the library's byte count (None for the four kinematic buffers that have none)."""
+
+    def __init__(self, stem, label, fields, buffers):
+        self.stem, self.label, self.fields, self.buffers = stem, label, fields, buffers
+        self.buffer, self.copy_to_host = stem + '_buffer', stem + '_copy_to_host'
+
+    def shape(self, which, dims, nbytes=None):
+        """Shape of buffer `which` for `dims`; with nbytes the free dim is solved from it (0 where another dim is 0)."""
+        dt, shape, free = self.buffers[which]
+        if nbytes is not None and free is not None:
+            row = np.dtype(dt).itemsize * int(np.prod([x if isinstance(x, int) else dims[x] for x in shape if x != free]))
+            dims = dict(dims, **{free: nbytes // row if row else 0})
+        return tuple(x if isinstance(x, int) else int(dims[x]) for x in shape)
+
+    def nbytes(self, which, dims):
+        return np.dtype(self.buffers[which][0]).itemsize * int(np.prod(self.shape(which, dims)))
+
+
+_f4, _i4 = np.float32, np.int32
+_ROW12 = {'K': (_f4, ('N', 'K', 12), 'K'), 'Q': (_f4, ('N', 'Q', 12), 'Q')}      # a [12] f32 record per row / per pair
+_PAIRS = lambda dt: (dt, ('N', 'K', 'Q'), 'K')
+QUERY_FAMILIES = dict(
+    kinematic=QueryFamily('rr_kinematic', 'kinematic', KIN_FIELDS, (
+        (_f4, ('N', N_JOINTS), None), (_f4, ('N', N_LINKS, 7), None), (_f4, ('N', N_LINKS, 6), None), (_f4, ('N', 'O', 6), None),
+        (_f4, ('N', 'P', 3), 'P'), (_f4, ('N', 'P', 6), 'P'), (_f4, ('N', 'P', 6, N_JOINTS), 'P'))),
+    ray=QueryFamily('rr_ray', 'ray', RAY_FIELDS, ((_f4, ('N', 'P', 8), 'P'), (_i4, ('N', 'P', 4), 'P'))),
+    distance=QueryFamily('rr_distance', 'distance', DIST_FIELDS, (_ROW12['Q'], (_i4, ('N', 'Q', 4), 'Q'))),
+    posture=QueryFamily('rr_posture', 'posture', PC_FIELDS, (_ROW12['K'], (_i4, ('N', 'K', 4), 'K'), _PAIRS(_f4), _PAIRS(_i4))),
+    signed=QueryFamily('rr_signed', 'signed-distance', SD_FIELDS, (_ROW12['K'], (_i4, ('N', 'K', 4), 'K'), _PAIRS(_f4), _PAIRS(_i4), _ROW12['Q'])),
+    signed_gradient=QueryFamily('rr_signed_gradient', 'signed-gradient', SG_FIELDS, (_ROW12['K'], _ROW12['K'], _ROW12['Q'])),
+    sweep=QueryFamily('rr_sweep', 'sweep', SW_FIELDS, (_ROW12['K'], _ROW12['K'], (_i4, ('N', 'K', 4), 'K'), _PAIRS(_f4))),
+    posture_kinematics=QueryFamily('rr_posture_kinematics', 'posture kinematics', PK_FIELDS, (
+        (_f4, ('N', 'K', N_LINKS, 7), 'K'), (_f4, ('N', 'K', 'P', 3), 'K'), (_f4, ('N', 'K', 'P', 6, N_JOINTS), 'K'))),
+    posture_ik=QueryFamily('rr_posture_ik', 'posture IK', PIK_FIELDS, (
+        (_f4, ('N', 'K', N_JOINTS), 'K'), (_f4, ('N', 'K', 4), 'K'), (_i4, ('N', 'K', 2), 'K'))),
+    posture_dynamics=QueryFamily('rr_posture_dynamics', 'posture dynamics', PD_FIELDS, (
+        (_f4, ('N', 'K', N_JOINTS, N_JOINTS), 'K'), (_f4, ('N', 'K', N_JOINTS), 'K'), (_f4, ('N', 'K', N_JOINTS), 'K'), (_f4, ('N', 'K', N_JOINTS), 'K'),
+        (_f4, ('N', 'K', N_JOINTS, N_JOINTS), 'K'))),
+)
 
 
 class Config(C.Structure):
@@ -239,48 +285,31 @@ def load_library():
     L.rr_set_kinematic_points.argtypes = [vp, i32, vp, vp]
     L.rr_get_kinematic_points.argtypes = [vp, C.POINTER(i32), vp, vp]
     L.rr_kinematic_observations.argtypes = [vp]
-    L.rr_kinematic_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.rr_kinematic_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_write_state.argtypes = [vp, vp, vp, C.c_uint32, i32]
     L.rr_read_state.argtypes = [vp]
     L.rr_set_rays.argtypes = [vp, i32, vp, vp]
     L.rr_get_rays.argtypes = [vp, C.POINTER(i32), vp, vp]
     L.rr_ray_cast.argtypes = [vp, vp, i32]
-    L.rr_ray_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.rr_ray_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_set_distance_pairs.argtypes = [vp, i32, vp, vp, C.c_float]
     L.rr_get_distance_pairs.argtypes = [vp, C.POINTER(i32), vp, vp, C.POINTER(C.c_float)]
     L.rr_closest_points.argtypes = [vp]
-    L.rr_distance_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.rr_distance_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_posture_clearance.argtypes = [vp, vp, i32, i32]
-    L.rr_posture_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.rr_posture_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_signed_distance.argtypes = [vp, vp, i32, i32]
-    L.rr_signed_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.rr_signed_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_signed_gradient.argtypes = [vp, vp, i32, i32, C.c_float]
-    L.rr_signed_gradient_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.rr_signed_gradient_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_swept_clearance.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float]
     L.rr_sweep_reach.argtypes = [vp, vp]
-    L.rr_sweep_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.rr_sweep_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_posture_kinematics.argtypes = [vp, vp, i32, i32]
-    L.rr_posture_kinematics_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.rr_posture_kinematics_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_posture_ik.argtypes = [vp, vp, vp, i32, i32, C.POINTER(IkOptions)]
-    L.rr_posture_ik_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.rr_posture_ik_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_posture_dynamics.argtypes = [vp, vp, vp, vp, i32, i32, C.c_uint32]
-    L.rr_posture_dynamics_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.rr_posture_dynamics_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_set_joint_torques.argtypes = [vp, vp, i32, vp, i32]
     L.rr_get_joint_torques.argtypes = [vp, vp]
     L.rr_joint_torque_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rr_set_external_wrenches.argtypes = [vp, vp, i32, vp, i32]
     L.rr_get_external_wrenches.argtypes = [vp, vp]
     L.rr_external_wrench_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    for fam in QUERY_FAMILIES.values():
+        getattr(L, fam.buffer).argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        getattr(L, fam.copy_to_host).argtypes = [vp, i32, vp, C.c_size_t]
     L.rr_checkpoint_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.rr_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
     L.rr_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]

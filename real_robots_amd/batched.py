@@ -663,25 +663,32 @@ class BatchedREALRobotEnv:
         nat.check(self.L.rr_get_kinematic_points(self.h, C.byref(n), idx.ctypes.data, loc.ctypes.data))
         return idx[:n.value].copy(), loc[:n.value].copy()
 
-    def _kinematic_shape(self, which, P):
-        N = self.N
-        return ((N, 11), (N, len(nat.LINK_NAMES), 7), (N, len(nat.LINK_NAMES), 6), (N, self.n_objects, 6), (N, P, 3), (N, P, 6),
-                (N, P, 6, 11))[which]
+    def _query_buffer(self, fam, name, host):
+        """Buffer `name` (of fam.fields, or its index) of a query family (`_native.QUERY_FAMILIES`): the device view, or a host copy.
+        The shape is the family's row shape with its one free dim solved from the library's byte count."""
+        which = fam.fields.index(name) if isinstance(name, str) and name in fam.fields else name
+        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(fam.fields):
+            raise ValueError("unknown %s buffer %r (known: %s)" % (fam.label, name, ', '.join(fam.fields)))
+        which = int(which)
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(getattr(self.L, fam.buffer)(self.h, which, C.byref(p), C.byref(n)))
+        dt, row, free = fam.buffers[which]
+        dims = dict(N=self.N, O=self.n_objects)
+        if 'Q' in row and free != 'Q':
+            dims['Q'] = len(self.distance_pairs()[0])
+        if 'P' in row and free != 'P':
+            dims['P'] = len(self.kinematic_points()[0])
+        shape = fam.shape(which, dims, n.value)
+        if host:
+            out = np.empty(shape, dt)
+            nat.check(getattr(self.L, fam.copy_to_host)(self.h, which, out.ctypes.data, out.nbytes))
+            return out
+        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
 
     def kinematic_buffer(self, name, host=False):
         """One buffer of the kinematic observations as its LAST `kinematic_observations` call left it (all zero before the first),
         by name (`_native.KIN_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait."""
-        which = nat.KIN_FIELDS.index(name) if isinstance(name, str) and name in nat.KIN_FIELDS else name
-        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.KIN_FIELDS):
-            raise ValueError("unknown kinematic buffer %r (known: %s)" % (name, ', '.join(nat.KIN_FIELDS)))
-        p, n = C.c_void_p(), C.c_size_t()
-        nat.check(self.L.rr_kinematic_buffer(self.h, int(which), C.byref(p), C.byref(n)))
-        shape = self._kinematic_shape(int(which), n.value // (4 * self.N * (3, 6, 66)[int(which) - 4]) if which >= 4 else 0)
-        if host:
-            out = np.empty(shape, np.float32)
-            nat.check(self.L.rr_kinematic_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
-            return out
-        return nat.DeviceBuffer(p.value, shape, '<f4', self)
+        return self._query_buffer(nat.QUERY_FAMILIES['kinematic'], name, host)
 
     def kinematic_observations(self, host=False):
         """getJointState / getLinkState(computeLinkVelocity=1) / getBaseVelocity / calculateJacobian for the whole batch
@@ -748,18 +755,7 @@ class BatchedREALRobotEnv:
     def ray_buffer(self, name, host=False):
         """One buffer of the ray casts as the LAST `ray_cast` call left it (all zero before the first), by name
         (`_native.RAY_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait."""
-        which = nat.RAY_FIELDS.index(name) if isinstance(name, str) and name in nat.RAY_FIELDS else name
-        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.RAY_FIELDS):
-            raise ValueError("unknown ray buffer %r (known: %s)" % (name, ', '.join(nat.RAY_FIELDS)))
-        p, n = C.c_void_p(), C.c_size_t()
-        nat.check(self.L.rr_ray_buffer(self.h, int(which), C.byref(p), C.byref(n)))
-        cols, dt = ((8, np.float32), (4, np.int32))[int(which)]
-        shape = (self.N, n.value // (4 * cols * self.N), cols)
-        if host:
-            out = np.empty(shape, dt)
-            nat.check(self.L.rr_ray_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
-            return out
-        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
+        return self._query_buffer(nat.QUERY_FAMILIES['ray'], name, host)
 
     def ray_cast(self, rays=None, host=False):
         """pybullet's rayTestBatch for the whole batch (rr_ray_cast): one launch on the library's stream casts the R rays of
@@ -875,18 +871,7 @@ class BatchedREALRobotEnv:
     def distance_buffer(self, name, host=False):
         """One buffer of the closest points as the LAST `closest_points` call left it (all zero before the first), by name
         (`_native.DIST_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait."""
-        which = nat.DIST_FIELDS.index(name) if isinstance(name, str) and name in nat.DIST_FIELDS else name
-        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.DIST_FIELDS):
-            raise ValueError("unknown distance buffer %r (known: %s)" % (name, ', '.join(nat.DIST_FIELDS)))
-        p, n = C.c_void_p(), C.c_size_t()
-        nat.check(self.L.rr_distance_buffer(self.h, int(which), C.byref(p), C.byref(n)))
-        cols, dt = ((12, np.float32), (4, np.int32))[int(which)]
-        shape = (self.N, n.value // (4 * cols * self.N), cols)
-        if host:
-            out = np.empty(shape, dt)
-            nat.check(self.L.rr_distance_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
-            return out
-        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
+        return self._query_buffer(nat.QUERY_FAMILIES['distance'], name, host)
 
     @staticmethod
     def distance_columns(pts, ids):
@@ -946,19 +931,7 @@ class BatchedREALRobotEnv:
         """One buffer of `posture_clearance` as the LAST call left it (all zero, and K = 0, before the first), by name
         (`_native.PC_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait.  Shapes: nearest
         [N, K, 12] float32, id [N, K, 4] int32, distance [N, K, Q] float32, status [N, K, Q] int32."""
-        which = nat.PC_FIELDS.index(name) if isinstance(name, str) and name in nat.PC_FIELDS else name
-        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.PC_FIELDS):
-            raise ValueError("unknown posture buffer %r (known: %s)" % (name, ', '.join(nat.PC_FIELDS)))
-        p, n = C.c_void_p(), C.c_size_t()
-        nat.check(self.L.rr_posture_buffer(self.h, int(which), C.byref(p), C.byref(n)))
-        Q = len(self.distance_pairs()[0])
-        cols, dt = ((12, np.float32), (4, np.int32), (Q, np.float32), (Q, np.int32))[int(which)]
-        shape = (self.N, n.value // (4 * cols * self.N) if cols else 0, cols)
-        if host:
-            out = np.empty(shape, dt)
-            nat.check(self.L.rr_posture_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
-            return out
-        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
+        return self._query_buffer(nat.QUERY_FAMILIES['posture'], name, host)
 
     @staticmethod
     def status_bytes(status, offset=0):
@@ -1012,19 +985,7 @@ class BatchedREALRobotEnv:
         (`_native.SD_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait.  Shapes: deepest
         [N, K', 12] float32, id [N, K', 4] int32, signed [N, K', Q] float32, status [N, K', Q] int32, points [N, Q, 12] float32
         (K' = 1 after a present-state query; `points` is written by present-state queries only)."""
-        which = nat.SD_FIELDS.index(name) if isinstance(name, str) and name in nat.SD_FIELDS else name
-        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.SD_FIELDS):
-            raise ValueError("unknown signed-distance buffer %r (known: %s)" % (name, ', '.join(nat.SD_FIELDS)))
-        p, n = C.c_void_p(), C.c_size_t()
-        nat.check(self.L.rr_signed_buffer(self.h, int(which), C.byref(p), C.byref(n)))
-        Q = len(self.distance_pairs()[0])
-        cols, dt = ((12, np.float32), (4, np.int32), (Q, np.float32), (Q, np.int32), (12, np.float32))[int(which)]
-        shape = (self.N, n.value // (4 * cols * self.N) if cols else 0, cols)
-        if host:
-            out = np.empty(shape, dt)
-            nat.check(self.L.rr_signed_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
-            return out
-        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
+        return self._query_buffer(nat.QUERY_FAMILIES['signed'], name, host)
 
     def signed_distance(self, postures=None, host=False):
         """The SIGNED distance of the pairs of `set_distance_pairs` for every env (rr_signed_distance): where two hulls are apart,
@@ -1095,17 +1056,7 @@ class BatchedREALRobotEnv:
         (`_native.SG_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait.  Shapes: gradient
         [N, K', 12] float32 {d s*/dq_0..10, +0.0}, cost [N, K', 12] float32 {dC/dq_0..10, C}, pair_gradient [N, Q, 12] float32
         {d s_j/dq_0..10, +0.0} (K' = 1 after a present-state query; `pair_gradient` is written by present-state queries only)."""
-        which = nat.SG_FIELDS.index(name) if isinstance(name, str) and name in nat.SG_FIELDS else name
-        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.SG_FIELDS):
-            raise ValueError("unknown signed-gradient buffer %r (known: %s)" % (name, ', '.join(nat.SG_FIELDS)))
-        p, n = C.c_void_p(), C.c_size_t()
-        nat.check(self.L.rr_signed_gradient_buffer(self.h, int(which), C.byref(p), C.byref(n)))
-        shape = (self.N, n.value // (48 * self.N), 12)
-        if host:
-            out = np.empty(shape, np.float32)
-            nat.check(self.L.rr_signed_gradient_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
-            return out
-        return nat.DeviceBuffer(p.value, shape, np.dtype(np.float32).str, self)
+        return self._query_buffer(nat.QUERY_FAMILIES['signed_gradient'], name, host)
 
     @staticmethod
     def _gradient_views(buf, present):
@@ -1183,19 +1134,7 @@ class BatchedREALRobotEnv:
         """One buffer of `swept_clearance` as the LAST call left it (all zero, and K = 0, before the first), by name
         (`_native.SW_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait.  Shapes: stop
         [N, K, 12] float32, hit [N, K, 12] float32, id [N, K, 4] int32, free [N, K, Q] float32."""
-        which = nat.SW_FIELDS.index(name) if isinstance(name, str) and name in nat.SW_FIELDS else name
-        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.SW_FIELDS):
-            raise ValueError("unknown sweep buffer %r (known: %s)" % (name, ', '.join(nat.SW_FIELDS)))
-        p, n = C.c_void_p(), C.c_size_t()
-        nat.check(self.L.rr_sweep_buffer(self.h, int(which), C.byref(p), C.byref(n)))
-        Q = len(self.distance_pairs()[0])
-        cols, dt = ((12, np.float32), (12, np.float32), (4, np.int32), (Q, np.float32))[int(which)]
-        shape = (self.N, n.value // (4 * cols * self.N) if cols else 0, cols)
-        if host:
-            out = np.empty(shape, dt)
-            nat.check(self.L.rr_sweep_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
-            return out
-        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
+        return self._query_buffer(nat.QUERY_FAMILIES['sweep'], name, host)
 
     def sweep_reach(self):
         """The reach table of `swept_clearance` (rr_sweep_reach), float32 [11, n_shapes]: how far a point of collision shape s can be
@@ -1243,19 +1182,7 @@ class BatchedREALRobotEnv:
         """One buffer of `posture_kinematics` as the LAST call left it (all zero, and K = 0, before the first), by name
         (`_native.PK_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait.  Shapes: link_pose
         [N, K, 17, 7], point_pos [N, K, P, 3], jacobian [N, K, P, 6, 11] float32, for the P points of `set_kinematic_points`."""
-        which = nat.PK_FIELDS.index(name) if isinstance(name, str) and name in nat.PK_FIELDS else name
-        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.PK_FIELDS):
-            raise ValueError("unknown posture kinematics buffer %r (known: %s)" % (name, ', '.join(nat.PK_FIELDS)))
-        p, n = C.c_void_p(), C.c_size_t()
-        nat.check(self.L.rr_posture_kinematics_buffer(self.h, int(which), C.byref(p), C.byref(n)))
-        P = len(self.kinematic_points()[0])
-        row = ((len(nat.LINK_NAMES), 7), (P, 3), (P, 6, nat.N_JOINTS))[int(which)]
-        shape = (self.N, n.value // (4 * self.N * int(np.prod(row)))) + row
-        if host:
-            out = np.empty(shape, np.float32)
-            nat.check(self.L.rr_posture_kinematics_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
-            return out
-        return nat.DeviceBuffer(p.value, shape, '<f4', self)
+        return self._query_buffer(nat.QUERY_FAMILIES['posture_kinematics'], name, host)
 
     def posture_kinematics(self, postures, host=False):
         """Where the links and the kinematic points would be at K candidate joint postures per env, and the points' Jacobians there
@@ -1282,18 +1209,7 @@ class BatchedREALRobotEnv:
         """One buffer of `posture_ik` as the LAST call left it (all zero, and K = 0, before the first), by name (`_native.PIK_FIELDS`)
         or index: a device view (zero copy), or with host=True a numpy copy after a wait.  Shapes: posture [N, K, 11] float32, result
         [N, K, 4] float32 {residual, position error, orientation error angle, 0}, info [N, K, 2] int32 {status, iterations}."""
-        which = nat.PIK_FIELDS.index(name) if isinstance(name, str) and name in nat.PIK_FIELDS else name
-        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.PIK_FIELDS):
-            raise ValueError("unknown posture IK buffer %r (known: %s)" % (name, ', '.join(nat.PIK_FIELDS)))
-        p, n = C.c_void_p(), C.c_size_t()
-        nat.check(self.L.rr_posture_ik_buffer(self.h, int(which), C.byref(p), C.byref(n)))
-        cols, dt = ((nat.N_JOINTS, np.float32), (4, np.float32), (2, np.int32))[int(which)]
-        shape = (self.N, n.value // (4 * cols * self.N), cols)
-        if host:
-            out = np.empty(shape, dt)
-            nat.check(self.L.rr_posture_ik_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
-            return out
-        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
+        return self._query_buffer(nat.QUERY_FAMILIES['posture_ik'], name, host)
 
     def posture_ik(self, targets, seeds=None, point=0, max_iterations=32, tolerance=1e-3, damping=0.1, max_step=0.5,
                    position_only=False, clamp=True, host=False):
@@ -1344,18 +1260,7 @@ class BatchedREALRobotEnv:
         """One buffer of `posture_dynamics` as the LAST call left it (all zero, and K = 0, before the first), by name
         (`_native.PD_FIELDS`) or index: a device view (zero copy), or with host=True a numpy copy after a wait.  Shapes: mass_matrix
         and mass_inverse [N, K, 11, 11], gravity, bias and torque [N, K, 11] float32."""
-        which = nat.PD_FIELDS.index(name) if isinstance(name, str) and name in nat.PD_FIELDS else name
-        if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.PD_FIELDS):
-            raise ValueError("unknown posture dynamics buffer %r (known: %s)" % (name, ', '.join(nat.PD_FIELDS)))
-        p, n = C.c_void_p(), C.c_size_t()
-        nat.check(self.L.rr_posture_dynamics_buffer(self.h, int(which), C.byref(p), C.byref(n)))
-        row = (nat.N_JOINTS, nat.N_JOINTS) if nat.PD_FIELDS[int(which)] in ('mass_matrix', 'mass_inverse') else (nat.N_JOINTS,)
-        shape = (self.N, n.value // (4 * self.N * int(np.prod(row)))) + row
-        if host:
-            out = np.empty(shape, np.float32)
-            nat.check(self.L.rr_posture_dynamics_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
-            return out
-        return nat.DeviceBuffer(p.value, shape, '<f4', self)
+        return self._query_buffer(nat.QUERY_FAMILIES['posture_dynamics'], name, host)
 
     @classmethod
     def _dynamics_args(cls, N, postures, velocities, accelerations):

@@ -480,4 +480,5 @@ __device__ __forceinline__ void dispatch_order_class(int x, int N, int ntiles, i
 #include "rr_grad.inc"    // k_signed_gradient: k_signed_distance plus the joint gradients of the deepest pair's signed distance and of a hinge cost over all pairs (rr_signed_gradient)
 #include "rr_plan.inc"   // plan_step: the placement and launch shapes of one step from one reading of the lagged list lengths (host only, no HIP type)
 #include "rr_mem.inc"    // MemOwner: the one owner of the handle's device and pinned memory, all-or-nothing group allocation (host only, no HIP type)
+#include "rr_query.inc"    // the query families' output buffers: one layout table, one buffer / copy_to_host accessor pair (host only, no HIP type)
 #include "rr_host.inc"    // host side: model blob, rr_env, the C ABI

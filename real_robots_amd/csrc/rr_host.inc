@@ -127,57 +127,26 @@ struct rr_env : ModelTables {
     float *plan = nullptr; int *plan_step = nullptr; float *ik_in = nullptr; float *ik_out = nullptr; float *ik_err = nullptr;   // lazily allocated (macro / cartesian adapters)
     float *score_out = nullptr; unsigned char *score_mask = nullptr;            // lazily allocated (rr_evaluate_goals)
     float4 *co_contacts = nullptr; float2 *co_force = nullptr; unsigned *co_partners = nullptr;   // lazily allocated (rr_contact_observations)
-    // kinematic observations (rr_kinematic_observations): the seven RR_KIN_* buffers, allocated together on first use (the three point buffers for
-    // RR_KIN_MAX_POINTS points, once); the points are a setting of the handle: a host copy and the device copy k_kinematics reads
-    float *kin[RR_KIN_COUNT] = {};
+    // The output buffers of the ten query families (rr_query.inc): qbuf[family][which], a family's group allocated together on first use for
+    // its capacity (query_capacity), once, zero-filled; qk[family]: the rows per env (postures, segments, targets) of the family's last
+    // call, 0 before the first.  What else a family keeps on the device comes in the same list (ensure_query).
+    void *qbuf[QF_COUNT][QUERY_MAX_BUFFERS] = {};
+    int qk[QF_COUNT] = {};
+    // the kinematic points, the ray table and the pair table are settings of the handle: a host copy and the device copy the kernels read
     int kin_np = 1;                // points in force: a fresh handle has link 8 (gripper `base`) at the origin of its COM frame
     KinPoints kin_pts = {{8}, {}};
     KinPoints *kin_pts_dev = nullptr;
-    // ray casts (rr_ray_cast): the two RR_RAY_* buffers and the staging of a host caller's segments, allocated together on first use for
-    // RR_RAY_MAX rays, once; the ray table is a setting of the handle like the points: a host copy and the device copy k_ray_cast reads
-    float4 *ray_hit = nullptr; int4 *ray_id = nullptr; float *ray_stage = nullptr;
     int ray_n = 0;                 // rays in force: a fresh handle has none
     RayTable ray_tab = {};
     RayTable *ray_tab_dev = nullptr;
-    // closest points (rr_closest_points): the two RR_DIST_* buffers, allocated together on first use for RR_DIST_MAX pairs, once; the pair
-    // table is a setting of the handle like the rays: a host copy and the device copy k_closest_points reads
-    float4 *dist_pts = nullptr; int4 *dist_id = nullptr;
     int dist_n = 0;                // pairs in force: a fresh handle has none
     DistTable dist_tab = {};
     DistTable *dist_tab_dev = nullptr;
-    // clearance at candidate postures (rr_posture_clearance): the four RR_PC_* buffers, allocated together on first use for
-    // RR_PC_MAX_POSTURES x RR_DIST_MAX, once; the host path's staging buffer is a part of its own, got by the first host-path call
-    void *pc_buf[RR_PC_COUNT] = {};
-    int pc_k = 0;                  // postures per env of the last query: 0 before the first
-    float *pc_stage = nullptr;
-    // signed distance (rr_signed_distance): the five RR_SD_* buffers, allocated together on first use for RR_PC_MAX_POSTURES x RR_DIST_MAX
-    // (RR_SD_POINTS for RR_DIST_MAX), once; a host caller's postures go through pc_stage
-    void *sd_buf[RR_SD_COUNT] = {};
-    int sd_k = 0;                  // rows per env of the last query (1: the present state): 0 before the first
-    // joint gradients of the signed distance (rr_signed_gradient): the three RR_SG_* buffers, allocated together on first use for
-    // RR_PC_MAX_POSTURES rows (RR_SG_PAIR_GRADIENT for RR_DIST_MAX pairs), once; the call writes the RR_SD_* buffers too
-    void *sg_buf[RR_SG_COUNT] = {};
-    int sg_k = 0;                  // rows per env of the last gradient query: 0 before the first
-    // swept clearance (rr_swept_clearance): the four RR_SW_* buffers and the device copy of the reach table, allocated together on
-    // first use for RR_PC_MAX_POSTURES x RR_DIST_MAX, once; the host path's staging buffer is a part of its own, got by the first host-path call
-    void *sw_buf[RR_SW_COUNT] = {};
-    int sw_k = 0;                  // segments per env of the last query: 0 before the first
-    SweepReach *sw_reach_dev = nullptr;
-    float *sw_stage = nullptr;
-    // kinematics at candidate postures (rr_posture_kinematics): the three RR_PK_* buffers, allocated together on first use for
-    // RR_PC_MAX_POSTURES x RR_KIN_MAX_POINTS, once; a host caller's postures go through pc_stage; the points go to the kernel by value
-    float *pk_buf[RR_PK_COUNT] = {};
-    int pk_k = 0;                  // postures per env of the last query: 0 before the first
-    // inverse kinematics at candidate targets (rr_posture_ik): the three RR_PIK_* buffers, allocated together on first use for
-    // RR_PC_MAX_POSTURES, once; a host caller's seeds go through pc_stage, its targets through pik_stage [N, 32, 7]
-    void *pik_buf[RR_PIK_COUNT] = {};
-    int pik_k = 0;                 // targets per env of the last call: 0 before the first
-    float *pik_stage = nullptr;
-    // joint-space dynamics at candidate postures (rr_posture_dynamics): the five RR_PD_* buffers, allocated together on first use for
-    // RR_PC_MAX_POSTURES, once; a host caller's postures go through pc_stage, its velocities and accelerations through pd_stage [2][N, 32, 11]
-    float *pd_buf[RR_PD_COUNT] = {};
-    int pd_k = 0;                  // rows per env of the last call: 0 before the first
-    float *pd_stage = nullptr;
+    SweepReach *sw_reach_dev = nullptr;      // the device copy of ModelTables::sweep_reach
+    // staging of a host caller's tensors, each got with the buffers or by the first host-path call that needs it: ray_stage [N, 64, 6] the
+    // segments of rr_ray_cast; pc_stage [N, 32, 11] postures (and the seeds of rr_posture_ik); sw_stage [N, 32, 2, 11] the segments of
+    // rr_swept_clearance; pik_stage [N, 32, 7] targets; pd_stage [2][N, 32, 11] the velocities and accelerations of rr_posture_dynamics
+    float *ray_stage = nullptr, *pc_stage = nullptr, *sw_stage = nullptr, *pik_stage = nullptr, *pd_stage = nullptr;
     // joint torque inputs of the step (rr_set_joint_torques): the table [N][11], allocated zero-filled on first use; a host caller's rows go
     // through jt_stage [N][11]; jt_on: rr_step launches k_joint_torque (from the first successful set with a table until the clearing call)
     float *jt_table = nullptr;
@@ -1454,38 +1423,116 @@ int rr_contact_observations(rr_env *e) {
     return RR_OK;
 }
 
-// The seven buffers of rr_kinematic_observations and the device copy of the points: allocated on first use -- by the call or by
-// rr_kinematic_buffer / rr_kinematic_copy_to_host -- in one list, zero-filled; the points in force go up behind it.
-static size_t kin_bytes(const rr_env *e, int which, int np) {
-    const size_t row[RR_KIN_COUNT] = {NB, KIN_LINKS * 7, KIN_LINKS * 6, (size_t)6 * e->P.nobj, (size_t)3 * np, (size_t)6 * np, (size_t)6 * NB * np};
-    return (size_t)e->P.N * row[which] * 4;
-}
-static int ensure_kinematics(rr_env *e, const char *who) {
-    if (e->kin[0]) return RR_OK;
-    if (e->RM.nl != KIN_LINKS) return fail(RR_EMODEL, std::string(who) + ": the model does not have the 17 URDF links of rr_link_poses");
-    for (int l = 0; l < KIN_LINKS; l++)
-        if (e->RM.link_body[l] >= NB) return fail(RR_EMODEL, std::string(who) + ": link " + std::to_string(l) + " of the model is on a body outside the kinematic tree");
-    HIPCHK(hipSetDevice(e->cfg.device));
-    float *b[RR_KIN_COUNT] = {};
-    KinPoints *pd = nullptr;
-    MemPart parts[RR_KIN_COUNT + 1];
-    for (int i = 0; i < RR_KIN_COUNT; i++) parts[i] = mem_part(&b[i], kin_bytes(e, i, RR_KIN_MAX_POINTS));
-    parts[RR_KIN_COUNT] = mem_part(&pd, sizeof(KinPoints), false);
-    RRCHK(mem_get(e, parts, RR_KIN_COUNT + 1, (std::string(who) + ": allocating the observation buffers").c_str()));
-    hipError_t rc = hipMemcpyAsync(pd, &e->kin_pts, sizeof(KinPoints), hipMemcpyHostToDevice, e->stream);
-    if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);      // (the source is the handle's own memory)
-    if (rc != hipSuccess) {
-        (void)hipStreamSynchronize(e->stream);
-        for (int i = 0; i < RR_KIN_COUNT; i++) e->mem.release(b[i]);
-        e->mem.release(pd);
-        (void)hipGetLastError();
-        return fail(RR_EDEVICE, std::string(who) + ": uploading the points: " + hipGetErrorString(rc));
+// ---- the on-demand groups of the queries and step inputs ---------------------------------------------------------------------------------
+// One group on first use: the buffers of a query family (family >= 0, while it has none), for its capacity and zero-filled, and
+// every part of `more` whose pointer is still null (a null ptr: a part the call does not need) -- staging blocks, tables -- in ONE
+// list, all or nothing.  `up`: a host table whose device copy is a part of the list goes up behind the allocation; if that fails the
+// whole list is given back, every pointer null again.
+struct GroupUpload { void **dst; const void *src; size_t bytes; const char *name; };
+static int ensure_group(rr_env *e, int family, const char *who, const char *what, std::initializer_list<MemPart> more, const GroupUpload *up = nullptr) {
+    MemPart parts[QUERY_MAX_BUFFERS + 4];
+    size_t n = 0;
+    if (family >= 0 && !e->qbuf[family][0]) {
+        const QueryDims cap = query_capacity(family, (size_t)e->P.N, (size_t)e->P.nobj);
+        for (int i = 0; i < QUERY_FAMILIES[family].count; i++) parts[n++] = mem_part(&e->qbuf[family][i], query_bytes(family, i, cap));
     }
-    for (int i = 0; i < RR_KIN_COUNT; i++) e->kin[i] = b[i];
-    e->kin_pts_dev = pd;
+    for (const MemPart &m : more)
+        if (m.ptr && !*m.ptr) parts[n++] = m;
+    if (!n) return RR_OK;
+    const bool upload = up && !*up->dst;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    RRCHK(mem_get(e, parts, n, (std::string(who) + ": allocating " + what).c_str()));
+    if (!upload) return RR_OK;
+    hipError_t rc = hipMemcpyAsync(*up->dst, up->src, up->bytes, hipMemcpyHostToDevice, e->stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);      // (the source is the handle's own memory)
+    if (rc == hipSuccess) return RR_OK;
+    (void)hipStreamSynchronize(e->stream);
+    for (size_t i = 0; i < n; i++) e->mem.release(*parts[i].ptr);
+    (void)hipGetLastError();
+    return fail(RR_EDEVICE, std::string(who) + ": uploading " + up->name + ": " + hipGetErrorString(rc));
+}
+static inline MemPart stage_part(float **ptr, size_t bytes, bool wanted = true) { return wanted ? mem_part(ptr, bytes, false) : MemPart{}; }
+// the staging of a host caller's postures [N, RR_PC_MAX_POSTURES, 11], shared by every query that takes postures
+static inline MemPart posture_stage(rr_env *e, bool wanted) { return stage_part(&e->pc_stage, (size_t)e->P.N * RR_PC_MAX_POSTURES * 44, wanted); }
+
+// The model condition of the kernels that read the link table of rr_link_poses: 17 URDF links, every one on a body of the tree.
+// `code`: the kinematic observations and the ray casts answer RR_EMODEL, the queries at candidate postures RR_EINVAL -- an
+// inconsistency of the ABI, kept as it is.
+static int check_link_table(const rr_env *e, const char *who, int code) {
+    if (e->RM.nl != KIN_LINKS) return fail(code, std::string(who) + ": the model does not have the 17 URDF links of rr_link_poses");
+    for (int l = 0; l < KIN_LINKS; l++)
+        if (e->RM.link_body[l] >= NB) return fail(code, std::string(who) + ": link " + std::to_string(l) + " of the model is on a body outside the kinematic tree");
     return RR_OK;
 }
 
+// The group of a query family on first use -- by the query or by its buffer / copy_to_host --: its buffers, the device copy of the
+// table it reads (the table in force goes up behind the allocation), and the staging blocks of `stages` the call still lacks.
+static_assert(QRY_JOINTS == NB && QRY_LINKS == KIN_LINKS, "rr_query.inc restates the model's constants");
+static int ensure_query(rr_env *e, int family, const char *who, std::initializer_list<MemPart> stages = {}) {
+    static const char *const what[QF_COUNT] = {"the observation buffers", "the ray buffers", "the distance buffers", "the posture buffers", "the signed-distance buffers",
+                                               "the signed-gradient buffers", "the sweep buffers", "the posture kinematics buffers", "the posture IK buffers",
+                                               "the posture dynamics buffers"};
+    MemPart more[3] = {};
+    size_t n = 0;
+    for (const MemPart &m : stages) more[n++] = m;
+    GroupUpload up = {};
+    switch (family) {
+    case QF_KIN:
+        RRCHK(check_link_table(e, who, RR_EMODEL));
+        more[n] = mem_part(&e->kin_pts_dev, sizeof(KinPoints), false);
+        up = {(void **)&e->kin_pts_dev, &e->kin_pts, sizeof(KinPoints), "the points"};
+        break;
+    case QF_RAY:
+        RRCHK(check_link_table(e, who, RR_EMODEL));
+        memcpy(e->ray_tab.uid, e->shape_uid, sizeof e->ray_tab.uid);
+        more[n++] = stage_part(&e->ray_stage, (size_t)e->P.N * RR_RAY_MAX * 24);
+        more[n] = mem_part(&e->ray_tab_dev, sizeof(RayTable), false);
+        up = {(void **)&e->ray_tab_dev, &e->ray_tab, sizeof(RayTable), "the ray table"};
+        break;
+    case QF_DIST:
+        more[n] = mem_part(&e->dist_tab_dev, sizeof(DistTable), false);
+        up = {(void **)&e->dist_tab_dev, &e->dist_tab, sizeof(DistTable), "the pair table"};
+        break;
+    case QF_SW:
+        more[n] = mem_part(&e->sw_reach_dev, sizeof(SweepReach), false);
+        up = {(void **)&e->sw_reach_dev, &e->sweep_reach, sizeof(SweepReach), "the reach table"};
+        break;
+    case QF_PK: case QF_PIK:
+        RRCHK(check_link_table(e, who, RR_EINVAL));
+        break;
+    }
+    return ensure_group(e, family, who, what[family], {more[0], more[1], more[2]}, up.dst ? &up : nullptr);
+}
+
+// A host caller's tensors on their way to a kernel: each goes to the stage of its kind on the main stream, the kernel reads the
+// stage, and the call waits at its end because the arguments are host memory.  host == false: device tensors, read in place.
+struct HostStaging {
+    rr_env *e; bool host;
+    int in(const float *&tensor, float *stage, size_t bytes) const {
+        if (!host || !tensor) return RR_OK;
+        HIPCHK(hipMemcpyAsync(stage, tensor, bytes, hipMemcpyHostToDevice, e->stream));
+        tensor = stage;
+        return RR_OK;
+    }
+    int wait() const { if (host) HIPCHK(hipStreamSynchronize(e->stream)); return RR_OK; }
+};
+
+// The HIP side of the two accessors of rr_query.inc and the view of a handle they work on: the layout in force is the last call's K
+// with the table's Q and the points' -- for the ray casts the rays' -- P.
+static int hip_query_ensure(void *env, int family, const char *who) { return ensure_query((rr_env *)env, family, who); }
+static int hip_query_copy(void *env, void *dst, const void *src, size_t bytes) {
+    rr_env *e = (rr_env *)env;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return RR_OK;
+}
+static const QueryBackend HIP_QUERY = {hip_query_ensure, hip_query_copy, fail};
+static QueryView query_view(rr_env *e, int family) {
+    if (!e) return QueryView{nullptr, family, nullptr, {}};
+    return QueryView{e, family, e->qbuf[family],
+                     {{(size_t)e->P.N, (size_t)e->qk[family], (size_t)e->dist_n, (size_t)(family == QF_RAY ? e->ray_n : e->kin_np), (size_t)e->P.nobj}}};
+}
 int rr_set_kinematic_points(rr_env *e, int32_t n_points, const int32_t *link, const float *local_pos) {
     if (!e) return fail(RR_EINVAL, "rr_set_kinematic_points: null env");
     if (n_points < 1 || n_points > RR_KIN_MAX_POINTS)
@@ -1504,7 +1551,7 @@ int rr_set_kinematic_points(rr_env *e, int32_t n_points, const int32_t *link, co
             K.local[j][k] = v;
         }
     }
-    if (e->kin_pts_dev) {      // (before the buffers exist the host copy is all there is: ensure_kinematics uploads it)
+    if (e->kin_pts_dev) {      // (before the buffers exist the host copy is all there is: ensure_query uploads it)
         HIPCHK(hipSetDevice(e->cfg.device));
         HIPCHK(hipStreamSynchronize(e->stream));      // an observation call enqueued earlier still reads the earlier points
         HIPCHK(hipMemcpy(e->kin_pts_dev, &K, sizeof K, hipMemcpyHostToDevice));
@@ -1526,66 +1573,20 @@ int rr_get_kinematic_points(rr_env *e, int32_t *n_points, int32_t *link_out, flo
 // its side streams before it returns).  Reads D.state only -- never the scratch slab of the look-ahead -- and leaves la_valid alone.
 int rr_kinematic_observations(rr_env *e) {
     if (!e) return fail(RR_EINVAL, "rr_kinematic_observations: null env");
-    RRCHK(ensure_kinematics(e, "rr_kinematic_observations"));
+    RRCHK(ensure_query(e, QF_KIN, "rr_kinematic_observations"));
     HIPCHK(hipSetDevice(e->cfg.device));
-    const KinOut O = {e->kin[RR_KIN_JOINT_VEL], e->kin[RR_KIN_LINK_POSE], e->kin[RR_KIN_LINK_VEL], e->kin[RR_KIN_OBJ_VEL],
-                      e->kin[RR_KIN_POINT_POS], e->kin[RR_KIN_POINT_VEL], e->kin[RR_KIN_JACOBIAN]};
+    float *const *b = (float *const *)e->qbuf[QF_KIN];
+    const KinOut O = {b[RR_KIN_JOINT_VEL], b[RR_KIN_LINK_POSE], b[RR_KIN_LINK_VEL], b[RR_KIN_OBJ_VEL], b[RR_KIN_POINT_POS], b[RR_KIN_POINT_VEL], b[RR_KIN_JACOBIAN]};
     hipLaunchKernelGGL(k_kinematics, dim3((e->P.N + KIN_ENVS - 1) / KIN_ENVS), dim3(KIN_THREADS), 0, e->stream, e->B, e->P, e->RM_dev, e->D, O,
                        e->kin_pts_dev, e->kin_np);
     HIPCHK(hipGetLastError());
     return RR_OK;
 }
 
-int rr_kinematic_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_kinematic_buffer: null env");
-    if (which < 0 || which >= RR_KIN_COUNT) return fail(RR_EINVAL, "rr_kinematic_buffer: buffer " + std::to_string(which) + " is not in [0, RR_KIN_COUNT)");
-    RRCHK(ensure_kinematics(e, "rr_kinematic_buffer"));
-    if (dev_ptr) *dev_ptr = e->kin[which];
-    if (bytes) *bytes = kin_bytes(e, which, e->kin_np);
-    return RR_OK;
-}
-
-int rr_kinematic_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_kinematic_copy_to_host: null env");
-    if (!dst) return fail(RR_EINVAL, "rr_kinematic_copy_to_host: null destination");
-    if (which < 0 || which >= RR_KIN_COUNT) return fail(RR_EINVAL, "rr_kinematic_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_KIN_COUNT)");
-    if (bytes != kin_bytes(e, which, e->kin_np)) return fail(RR_EINVAL, "rr_kinematic_copy_to_host: size mismatch");
-    RRCHK(ensure_kinematics(e, "rr_kinematic_copy_to_host"));
-    HIPCHK(hipSetDevice(e->cfg.device));
-    HIPCHK(hipMemcpyAsync(dst, e->kin[which], bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return RR_OK;
-}
+int rr_kinematic_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) { return query_buffer(query_view(e, QF_KIN), HIP_QUERY, which, dev_ptr, bytes); }
+int rr_kinematic_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) { return query_copy_to_host(query_view(e, QF_KIN), HIP_QUERY, which, dst, bytes); }
 
 // ---- ray casts against the collision hulls (rr_ray.inc) ---------------------------------------------------------------------------------
-// The two buffers of rr_ray_cast, the staging of a host caller's segments and the device copy of the ray table: allocated on first
-// use -- by the cast or by rr_ray_buffer / rr_ray_copy_to_host -- in one list, zero-filled, for RR_RAY_MAX rays; the table in force
-// goes up behind it.
-static size_t ray_bytes(const rr_env *e, int which, int R) { return (size_t)e->P.N * R * (which == RR_RAY_HIT ? 32 : 16); }
-static int ensure_rays(rr_env *e, const char *who) {
-    if (e->ray_hit) return RR_OK;
-    if (e->RM.nl != KIN_LINKS) return fail(RR_EMODEL, std::string(who) + ": the model does not have the 17 URDF links of rr_link_poses");
-    for (int l = 0; l < KIN_LINKS; l++)
-        if (e->RM.link_body[l] >= NB) return fail(RR_EMODEL, std::string(who) + ": link " + std::to_string(l) + " of the model is on a body outside the kinematic tree");
-    HIPCHK(hipSetDevice(e->cfg.device));
-    float4 *hit = nullptr; int4 *id = nullptr; float *stage = nullptr;
-    RayTable *td = nullptr;
-    RRCHK(mem_get(e, {mem_part(&hit, ray_bytes(e, RR_RAY_HIT, RR_RAY_MAX)), mem_part(&id, ray_bytes(e, RR_RAY_ID, RR_RAY_MAX)),
-                      mem_part(&stage, (size_t)e->P.N * RR_RAY_MAX * 24), mem_part(&td, sizeof(RayTable), false)},
-                  (std::string(who) + ": allocating the ray buffers").c_str()));
-    memcpy(e->ray_tab.uid, e->shape_uid, sizeof e->ray_tab.uid);
-    hipError_t rc = hipMemcpyAsync(td, &e->ray_tab, sizeof(RayTable), hipMemcpyHostToDevice, e->stream);
-    if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);      // (the source is the handle's own memory)
-    if (rc != hipSuccess) {
-        (void)hipStreamSynchronize(e->stream);
-        e->mem.release(hit); e->mem.release(id); e->mem.release(stage); e->mem.release(td);
-        (void)hipGetLastError();
-        return fail(RR_EDEVICE, std::string(who) + ": uploading the ray table: " + hipGetErrorString(rc));
-    }
-    e->ray_hit = hit; e->ray_id = id; e->ray_stage = stage; e->ray_tab_dev = td;
-    return RR_OK;
-}
-
 int rr_set_rays(rr_env *e, int32_t n_rays, const int32_t *link, const float *from_to) {
     if (!e) return fail(RR_EINVAL, "rr_set_rays: null env");
     if (n_rays < 0 || n_rays > RR_RAY_MAX)
@@ -1606,7 +1607,7 @@ int rr_set_rays(rr_env *e, int32_t n_rays, const int32_t *link, const float *fro
         }
     }
     for (int j = n_rays; j < RR_RAY_MAX; j++) T.link[j] = -1;
-    if (e->ray_tab_dev) {      // (before the buffers exist the host copy is all there is: ensure_rays uploads it)
+    if (e->ray_tab_dev) {      // (before the buffers exist the host copy is all there is: ensure_query uploads it)
         HIPCHK(hipSetDevice(e->cfg.device));
         HIPCHK(hipStreamSynchronize(e->stream));      // a cast enqueued earlier still reads the earlier table
         HIPCHK(hipMemcpy(e->ray_tab_dev, &T, sizeof T, hipMemcpyHostToDevice));
@@ -1634,66 +1635,21 @@ int rr_ray_cast(rr_env *e, const float *rays, int32_t on_device) {
         for (size_t i = 0; i < (size_t)N * R * 6; i++)
             if (!std::isfinite(rays[i]))
                 return fail(RR_EINVAL, "rr_ray_cast: env " + std::to_string(i / ((size_t)R * 6)) + ", ray " + std::to_string(i / 6 % R) + ": the segment is not finite");
-    RRCHK(ensure_rays(e, "rr_ray_cast"));
+    RRCHK(ensure_query(e, QF_RAY, "rr_ray_cast"));
     HIPCHK(hipSetDevice(e->cfg.device));
+    const HostStaging st = {e, rays && !on_device};
     const float *seg = rays;
-    if (rays && !on_device) {
-        HIPCHK(hipMemcpyAsync(e->ray_stage, rays, (size_t)N * R * 24, hipMemcpyHostToDevice, e->stream));
-        seg = e->ray_stage;
-    }
+    RRCHK(st.in(seg, e->ray_stage, (size_t)N * R * 24));
     hipLaunchKernelGGL(k_ray_cast, dim3((N + RAY_ENVS - 1) / RAY_ENVS), dim3(RAY_THREADS), 0, e->stream, e->B, e->P, e->RM_dev, e->D, e->n_shapes,
-                       e->ray_tab_dev, seg, R, e->ray_hit, e->ray_id);
+                       e->ray_tab_dev, seg, R, (float4 *)e->qbuf[QF_RAY][RR_RAY_HIT], (int4 *)e->qbuf[QF_RAY][RR_RAY_ID]);
     HIPCHK(hipGetLastError());
-    if (rays && !on_device) HIPCHK(hipStreamSynchronize(e->stream));   // the argument is host memory
-    return RR_OK;
+    return st.wait();
 }
 
-int rr_ray_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_ray_buffer: null env");
-    if (which < 0 || which >= RR_RAY_COUNT) return fail(RR_EINVAL, "rr_ray_buffer: buffer " + std::to_string(which) + " is not in [0, RR_RAY_COUNT)");
-    RRCHK(ensure_rays(e, "rr_ray_buffer"));
-    if (dev_ptr) *dev_ptr = which == RR_RAY_HIT ? (void *)e->ray_hit : (void *)e->ray_id;
-    if (bytes) *bytes = ray_bytes(e, which, e->ray_n);
-    return RR_OK;
-}
-
-int rr_ray_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_ray_copy_to_host: null env");
-    if (!dst) return fail(RR_EINVAL, "rr_ray_copy_to_host: null destination");
-    if (which < 0 || which >= RR_RAY_COUNT) return fail(RR_EINVAL, "rr_ray_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_RAY_COUNT)");
-    if (bytes != ray_bytes(e, which, e->ray_n)) return fail(RR_EINVAL, "rr_ray_copy_to_host: size mismatch");
-    RRCHK(ensure_rays(e, "rr_ray_copy_to_host"));
-    HIPCHK(hipSetDevice(e->cfg.device));
-    if (bytes == 0) return RR_OK;
-    HIPCHK(hipMemcpyAsync(dst, which == RR_RAY_HIT ? (void *)e->ray_hit : (void *)e->ray_id, bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return RR_OK;
-}
+int rr_ray_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) { return query_buffer(query_view(e, QF_RAY), HIP_QUERY, which, dev_ptr, bytes); }
+int rr_ray_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) { return query_copy_to_host(query_view(e, QF_RAY), HIP_QUERY, which, dst, bytes); }
 
 // ---- closest points between collision hulls (rr_dist.inc) ------------------------------------------------------------------------------
-// The two buffers of rr_closest_points and the device copy of the pair table: allocated on first use -- by the query or by
-// rr_distance_buffer / rr_distance_copy_to_host -- in one list, zero-filled, for RR_DIST_MAX pairs; the table in force goes up behind it.
-static size_t dist_bytes(const rr_env *e, int which, int Q) { return (size_t)e->P.N * Q * (which == RR_DIST_POINTS ? 48 : 16); }
-static int ensure_dist(rr_env *e, const char *who) {
-    if (e->dist_pts) return RR_OK;
-    HIPCHK(hipSetDevice(e->cfg.device));
-    float4 *pts = nullptr; int4 *id = nullptr;
-    DistTable *td = nullptr;
-    RRCHK(mem_get(e, {mem_part(&pts, dist_bytes(e, RR_DIST_POINTS, RR_DIST_MAX)), mem_part(&id, dist_bytes(e, RR_DIST_ID, RR_DIST_MAX)),
-                      mem_part(&td, sizeof(DistTable), false)},
-                  (std::string(who) + ": allocating the distance buffers").c_str()));
-    hipError_t rc = hipMemcpyAsync(td, &e->dist_tab, sizeof(DistTable), hipMemcpyHostToDevice, e->stream);
-    if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);      // (the source is the handle's own memory)
-    if (rc != hipSuccess) {
-        (void)hipStreamSynchronize(e->stream);
-        e->mem.release(pts); e->mem.release(id); e->mem.release(td);
-        (void)hipGetLastError();
-        return fail(RR_EDEVICE, std::string(who) + ": uploading the pair table: " + hipGetErrorString(rc));
-    }
-    e->dist_pts = pts; e->dist_id = id; e->dist_tab_dev = td;
-    return RR_OK;
-}
-
 int rr_set_distance_pairs(rr_env *e, int32_t n_pairs, const int32_t *shape_a, const int32_t *shape_b, float max_distance) {
     if (!e) return fail(RR_EINVAL, "rr_set_distance_pairs: null env");
     if (n_pairs < -1 || n_pairs > RR_DIST_MAX)
@@ -1720,7 +1676,7 @@ int rr_set_distance_pairs(rr_env *e, int32_t n_pairs, const int32_t *shape_a, co
         if (ab[0] == ab[1]) return fail(RR_EINVAL, "rr_set_distance_pairs: pair " + std::to_string(j) + ": a == b (shape " + std::to_string(ab[0]) + ")");
         T.a[j] = ab[0]; T.b[j] = ab[1];
     }
-    if (e->dist_tab_dev) {     // (before the buffers exist the host copy is all there is: ensure_dist uploads it)
+    if (e->dist_tab_dev) {     // (before the buffers exist the host copy is all there is: ensure_query uploads it)
         HIPCHK(hipSetDevice(e->cfg.device));
         HIPCHK(hipStreamSynchronize(e->stream));      // a query enqueued earlier still reads the earlier table
         HIPCHK(hipMemcpy(e->dist_tab_dev, &T, sizeof T, hipMemcpyHostToDevice));
@@ -1745,54 +1701,18 @@ int rr_closest_points(rr_env *e) {
     if (!e) return fail(RR_EINVAL, "rr_closest_points: null env");
     const int Q = e->dist_n, N = e->P.N;
     if (Q == 0) return fail(RR_EINVAL, "rr_closest_points: the pair table is empty (rr_set_distance_pairs)");
-    RRCHK(ensure_dist(e, "rr_closest_points"));
+    RRCHK(ensure_query(e, QF_DIST, "rr_closest_points"));
     HIPCHK(hipSetDevice(e->cfg.device));
     hipLaunchKernelGGL(k_closest_points, dim3((N + DIST_ENVS - 1) / DIST_ENVS), dim3(DIST_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q,
-                       e->dist_pts, e->dist_id);
+                       (float4 *)e->qbuf[QF_DIST][RR_DIST_POINTS], (int4 *)e->qbuf[QF_DIST][RR_DIST_ID]);
     HIPCHK(hipGetLastError());
     return RR_OK;
 }
 
-int rr_distance_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_distance_buffer: null env");
-    if (which < 0 || which >= RR_DIST_COUNT) return fail(RR_EINVAL, "rr_distance_buffer: buffer " + std::to_string(which) + " is not in [0, RR_DIST_COUNT)");
-    RRCHK(ensure_dist(e, "rr_distance_buffer"));
-    if (dev_ptr) *dev_ptr = which == RR_DIST_POINTS ? (void *)e->dist_pts : (void *)e->dist_id;
-    if (bytes) *bytes = dist_bytes(e, which, e->dist_n);
-    return RR_OK;
-}
-
-int rr_distance_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_distance_copy_to_host: null env");
-    if (!dst) return fail(RR_EINVAL, "rr_distance_copy_to_host: null destination");
-    if (which < 0 || which >= RR_DIST_COUNT) return fail(RR_EINVAL, "rr_distance_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_DIST_COUNT)");
-    if (bytes != dist_bytes(e, which, e->dist_n)) return fail(RR_EINVAL, "rr_distance_copy_to_host: size mismatch");
-    RRCHK(ensure_dist(e, "rr_distance_copy_to_host"));
-    HIPCHK(hipSetDevice(e->cfg.device));
-    if (bytes == 0) return RR_OK;
-    HIPCHK(hipMemcpyAsync(dst, which == RR_DIST_POINTS ? (void *)e->dist_pts : (void *)e->dist_id, bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return RR_OK;
-}
+int rr_distance_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) { return query_buffer(query_view(e, QF_DIST), HIP_QUERY, which, dev_ptr, bytes); }
+int rr_distance_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) { return query_copy_to_host(query_view(e, QF_DIST), HIP_QUERY, which, dst, bytes); }
 
 // ---- clearance at candidate postures (rr_posture.inc) ----------------------------------------------------------------------------------
-// The four buffers of rr_posture_clearance: allocated on first use -- by the query or by rr_posture_buffer / rr_posture_copy_to_host --
-// in one list, zero-filled, for RR_PC_MAX_POSTURES postures of RR_DIST_MAX pairs.  The layout in force is [N, K, ...] for the K of the
-// last query (0 before the first) and the Q of the pair table.
-static size_t pc_bytes(const rr_env *e, int which, int K, int Q) {
-    return (size_t)e->P.N * K * (which == RR_PC_NEAREST ? 48 : which == RR_PC_ID ? 16 : (size_t)Q * 4);
-}
-static int ensure_posture(rr_env *e, const char *who) {
-    if (e->pc_buf[0]) return RR_OK;
-    HIPCHK(hipSetDevice(e->cfg.device));
-    void *b[RR_PC_COUNT] = {};
-    MemPart parts[RR_PC_COUNT];
-    for (int i = 0; i < RR_PC_COUNT; i++) parts[i] = mem_part(&b[i], pc_bytes(e, i, RR_PC_MAX_POSTURES, RR_DIST_MAX));
-    RRCHK(mem_get(e, parts, RR_PC_COUNT, (std::string(who) + ": allocating the posture buffers").c_str()));
-    for (int i = 0; i < RR_PC_COUNT; i++) e->pc_buf[i] = b[i];
-    return RR_OK;
-}
-
 // The clearance of K candidate postures per env, on the device.  On the main stream like rr_closest_points: behind every step, reset
 // and state write enqueued before it.  Reads D.state (the objects), the model, the pair table and the tensor; writes the four buffers
 // and nothing else -- not the state, the scratch slab of the look-ahead, la_valid, an error flag or an RR_DIST_* buffer.
@@ -1804,65 +1724,24 @@ int rr_posture_clearance(rr_env *e, const float *postures, int32_t n_postures, i
                                    std::to_string(RR_PC_MAX_POSTURES) + "]");
     const int Q = e->dist_n, N = e->P.N, K = n_postures;
     if (Q == 0) return fail(RR_EINVAL, "rr_posture_clearance: the pair table is empty (rr_set_distance_pairs)");
-    RRCHK(ensure_dist(e, "rr_posture_clearance"));        // (the device copy of the pair table)
-    RRCHK(ensure_posture(e, "rr_posture_clearance"));
-    if (!on_device && !e->pc_stage)
-        RRCHK(mem_get(e, {mem_part(&e->pc_stage, (size_t)N * RR_PC_MAX_POSTURES * 44, false)}, "rr_posture_clearance: allocating the staging buffer"));
+    RRCHK(ensure_query(e, QF_DIST, "rr_posture_clearance"));     // (the device copy of the pair table)
+    RRCHK(ensure_query(e, QF_PC, "rr_posture_clearance", {posture_stage(e, !on_device)}));
     HIPCHK(hipSetDevice(e->cfg.device));
+    const HostStaging st = {e, !on_device};
     const float *src = postures;
-    if (!on_device) {
-        HIPCHK(hipMemcpyAsync(e->pc_stage, postures, (size_t)N * K * 44, hipMemcpyHostToDevice, e->stream));
-        src = e->pc_stage;
-    }
+    RRCHK(st.in(src, e->pc_stage, (size_t)N * K * 44));
+    void *const *b = e->qbuf[QF_PC];
     hipLaunchKernelGGL(k_posture_clearance, dim3((unsigned)N * K), dim3(PC_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
-                       (float4 *)e->pc_buf[RR_PC_NEAREST], (int4 *)e->pc_buf[RR_PC_ID], (float *)e->pc_buf[RR_PC_DISTANCE], (int *)e->pc_buf[RR_PC_STATUS]);
+                       (float4 *)b[RR_PC_NEAREST], (int4 *)b[RR_PC_ID], (float *)b[RR_PC_DISTANCE], (int *)b[RR_PC_STATUS]);
     HIPCHK(hipGetLastError());
-    e->pc_k = K;
-    if (!on_device) HIPCHK(hipStreamSynchronize(e->stream));   // the argument is host memory
-    return RR_OK;
+    e->qk[QF_PC] = K;
+    return st.wait();
 }
 
-int rr_posture_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_posture_buffer: null env");
-    if (which < 0 || which >= RR_PC_COUNT) return fail(RR_EINVAL, "rr_posture_buffer: buffer " + std::to_string(which) + " is not in [0, RR_PC_COUNT)");
-    RRCHK(ensure_posture(e, "rr_posture_buffer"));
-    if (dev_ptr) *dev_ptr = e->pc_buf[which];
-    if (bytes) *bytes = pc_bytes(e, which, e->pc_k, e->dist_n);
-    return RR_OK;
-}
-
-int rr_posture_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_posture_copy_to_host: null env");
-    if (!dst) return fail(RR_EINVAL, "rr_posture_copy_to_host: null destination");
-    if (which < 0 || which >= RR_PC_COUNT) return fail(RR_EINVAL, "rr_posture_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_PC_COUNT)");
-    if (bytes != pc_bytes(e, which, e->pc_k, e->dist_n)) return fail(RR_EINVAL, "rr_posture_copy_to_host: size mismatch");
-    RRCHK(ensure_posture(e, "rr_posture_copy_to_host"));
-    HIPCHK(hipSetDevice(e->cfg.device));
-    if (bytes == 0) return RR_OK;
-    HIPCHK(hipMemcpyAsync(dst, e->pc_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return RR_OK;
-}
+int rr_posture_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) { return query_buffer(query_view(e, QF_PC), HIP_QUERY, which, dev_ptr, bytes); }
+int rr_posture_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) { return query_copy_to_host(query_view(e, QF_PC), HIP_QUERY, which, dst, bytes); }
 
 // ---- signed distance and penetration depth (rr_signed.inc) -----------------------------------------------------------------------------
-// The five buffers of rr_signed_distance: allocated on first use -- by the query or by rr_signed_buffer / rr_signed_copy_to_host -- in
-// one list, zero-filled, for RR_PC_MAX_POSTURES rows of RR_DIST_MAX pairs (the per-pair records of the present state for RR_DIST_MAX
-// pairs).  The layout in force is [N, K', ...] for the K' of the last query (0 before the first) and the Q of the pair table.
-static size_t sd_bytes(const rr_env *e, int which, int K, int Q) {
-    if (which == RR_SD_POINTS) return (size_t)e->P.N * Q * 48;
-    return (size_t)e->P.N * K * (which == RR_SD_DEEPEST ? 48 : which == RR_SD_ID ? 16 : (size_t)Q * 4);
-}
-static int ensure_signed(rr_env *e, const char *who) {
-    if (e->sd_buf[0]) return RR_OK;
-    HIPCHK(hipSetDevice(e->cfg.device));
-    void *b[RR_SD_COUNT] = {};
-    MemPart parts[RR_SD_COUNT];
-    for (int i = 0; i < RR_SD_COUNT; i++) parts[i] = mem_part(&b[i], sd_bytes(e, i, RR_PC_MAX_POSTURES, RR_DIST_MAX));
-    RRCHK(mem_get(e, parts, RR_SD_COUNT, (std::string(who) + ": allocating the signed-distance buffers").c_str()));
-    for (int i = 0; i < RR_SD_COUNT; i++) e->sd_buf[i] = b[i];
-    return RR_OK;
-}
-
 // The signed distance of the pair table at the present state (postures == NULL) or at K candidate postures per env.  On the main stream
 // like rr_posture_clearance: behind every step, reset and state write enqueued before it.  Reads D.state, the model, the pair table and
 // the tensor; writes the five buffers (RR_SD_POINTS at the present state only) and nothing else -- not the state, the scratch slab of
@@ -1876,66 +1755,25 @@ int rr_signed_distance(rr_env *e, const float *postures, int32_t n_postures, int
                                    std::to_string(RR_PC_MAX_POSTURES) + "]");
     const int Q = e->dist_n, N = e->P.N, K = postures ? n_postures : 1;
     if (Q == 0) return fail(RR_EINVAL, "rr_signed_distance: the pair table is empty (rr_set_distance_pairs)");
-    RRCHK(ensure_dist(e, "rr_signed_distance"));          // (the device copy of the pair table)
-    RRCHK(ensure_signed(e, "rr_signed_distance"));
-    const bool stage = postures && !on_device;
-    if (stage && !e->pc_stage)
-        RRCHK(mem_get(e, {mem_part(&e->pc_stage, (size_t)N * RR_PC_MAX_POSTURES * 44, false)}, "rr_signed_distance: allocating the staging buffer"));
+    const HostStaging st = {e, postures && !on_device};
+    RRCHK(ensure_query(e, QF_DIST, "rr_signed_distance"));       // (the device copy of the pair table)
+    RRCHK(ensure_query(e, QF_SD, "rr_signed_distance", {posture_stage(e, st.host)}));
     HIPCHK(hipSetDevice(e->cfg.device));
     const float *src = postures;
-    if (stage) {
-        HIPCHK(hipMemcpyAsync(e->pc_stage, postures, (size_t)N * K * 44, hipMemcpyHostToDevice, e->stream));
-        src = e->pc_stage;
-    }
+    RRCHK(st.in(src, e->pc_stage, (size_t)N * K * 44));
+    void *const *b = e->qbuf[QF_SD];
     hipLaunchKernelGGL(k_signed_distance, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
-                       (float4 *)e->sd_buf[RR_SD_DEEPEST], (int4 *)e->sd_buf[RR_SD_ID], (float *)e->sd_buf[RR_SD_SIGNED], (int *)e->sd_buf[RR_SD_STATUS],
-                       postures ? (float4 *)nullptr : (float4 *)e->sd_buf[RR_SD_POINTS]);
+                       (float4 *)b[RR_SD_DEEPEST], (int4 *)b[RR_SD_ID], (float *)b[RR_SD_SIGNED], (int *)b[RR_SD_STATUS],
+                       postures ? (float4 *)nullptr : (float4 *)b[RR_SD_POINTS]);
     HIPCHK(hipGetLastError());
-    e->sd_k = K;
-    if (stage) HIPCHK(hipStreamSynchronize(e->stream));        // the argument is host memory
-    return RR_OK;
+    e->qk[QF_SD] = K;
+    return st.wait();
 }
 
-int rr_signed_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_signed_buffer: null env");
-    if (which < 0 || which >= RR_SD_COUNT) return fail(RR_EINVAL, "rr_signed_buffer: buffer " + std::to_string(which) + " is not in [0, RR_SD_COUNT)");
-    RRCHK(ensure_signed(e, "rr_signed_buffer"));
-    if (dev_ptr) *dev_ptr = e->sd_buf[which];
-    if (bytes) *bytes = sd_bytes(e, which, e->sd_k, e->dist_n);
-    return RR_OK;
-}
-
-int rr_signed_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_signed_copy_to_host: null env");
-    if (!dst) return fail(RR_EINVAL, "rr_signed_copy_to_host: null destination");
-    if (which < 0 || which >= RR_SD_COUNT) return fail(RR_EINVAL, "rr_signed_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_SD_COUNT)");
-    if (bytes != sd_bytes(e, which, e->sd_k, e->dist_n)) return fail(RR_EINVAL, "rr_signed_copy_to_host: size mismatch");
-    RRCHK(ensure_signed(e, "rr_signed_copy_to_host"));
-    HIPCHK(hipSetDevice(e->cfg.device));
-    if (bytes == 0) return RR_OK;
-    HIPCHK(hipMemcpyAsync(dst, e->sd_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return RR_OK;
-}
+int rr_signed_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) { return query_buffer(query_view(e, QF_SD), HIP_QUERY, which, dev_ptr, bytes); }
+int rr_signed_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) { return query_copy_to_host(query_view(e, QF_SD), HIP_QUERY, which, dst, bytes); }
 
 // ---- joint gradients of the signed distance (rr_grad.inc) ------------------------------------------------------------------------------
-// The three buffers of rr_signed_gradient: allocated on first use -- by the query or by rr_signed_gradient_buffer /
-// rr_signed_gradient_copy_to_host -- in one list, zero-filled, for RR_PC_MAX_POSTURES rows (the pair rows of the present state for
-// RR_DIST_MAX pairs).  The layout in force is that of the last gradient query's K' (0 before the first) and the Q of the pair table.
-static size_t sg_bytes(const rr_env *e, int which, int K, int Q) {
-    return (size_t)e->P.N * (which == RR_SG_PAIR_GRADIENT ? Q : K) * 48;
-}
-static int ensure_signed_gradient(rr_env *e, const char *who) {
-    if (e->sg_buf[0]) return RR_OK;
-    HIPCHK(hipSetDevice(e->cfg.device));
-    void *b[RR_SG_COUNT] = {};
-    MemPart parts[RR_SG_COUNT];
-    for (int i = 0; i < RR_SG_COUNT; i++) parts[i] = mem_part(&b[i], sg_bytes(e, i, RR_PC_MAX_POSTURES, RR_DIST_MAX));
-    RRCHK(mem_get(e, parts, RR_SG_COUNT, (std::string(who) + ": allocating the signed-gradient buffers").c_str()));
-    for (int i = 0; i < RR_SG_COUNT; i++) e->sg_buf[i] = b[i];
-    return RR_OK;
-}
-
 // rr_signed_distance with the joint gradients: the same launch shape on the main stream, the same reads, and the five RR_SD_* buffers
 // written as that call writes them; the three RR_SG_* buffers (RR_SG_PAIR_GRADIENT at the present state only) in addition, and
 // nothing else.
@@ -1953,81 +1791,27 @@ int rr_signed_gradient(rr_env *e, const float *postures, int32_t n_postures, int
     if (maxd > 0.0f && maxd < INFINITY && margin > maxd)
         return fail(RR_EINVAL, "rr_signed_gradient: margin " + std::to_string(margin) + " is above the pair table's max_distance " + std::to_string(maxd) +
                                    " (a culled pair's sphere gap would enter the hinge as a distance)");
-    RRCHK(ensure_dist(e, "rr_signed_gradient"));          // (the device copy of the pair table)
-    RRCHK(ensure_signed(e, "rr_signed_gradient"));
-    RRCHK(ensure_signed_gradient(e, "rr_signed_gradient"));
-    const bool stage = postures && !on_device;
-    if (stage && !e->pc_stage)
-        RRCHK(mem_get(e, {mem_part(&e->pc_stage, (size_t)N * RR_PC_MAX_POSTURES * 44, false)}, "rr_signed_gradient: allocating the staging buffer"));
+    const HostStaging st = {e, postures && !on_device};
+    RRCHK(ensure_query(e, QF_DIST, "rr_signed_gradient"));       // (the device copy of the pair table)
+    RRCHK(ensure_query(e, QF_SD, "rr_signed_gradient"));
+    RRCHK(ensure_query(e, QF_SG, "rr_signed_gradient", {posture_stage(e, st.host)}));
     HIPCHK(hipSetDevice(e->cfg.device));
     const float *src = postures;
-    if (stage) {
-        HIPCHK(hipMemcpyAsync(e->pc_stage, postures, (size_t)N * K * 44, hipMemcpyHostToDevice, e->stream));
-        src = e->pc_stage;
-    }
+    RRCHK(st.in(src, e->pc_stage, (size_t)N * K * 44));
+    void *const *b = e->qbuf[QF_SD], *const *g = e->qbuf[QF_SG];
     hipLaunchKernelGGL(k_signed_gradient, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
-                       (float4 *)e->sd_buf[RR_SD_DEEPEST], (int4 *)e->sd_buf[RR_SD_ID], (float *)e->sd_buf[RR_SD_SIGNED], (int *)e->sd_buf[RR_SD_STATUS],
-                       postures ? (float4 *)nullptr : (float4 *)e->sd_buf[RR_SD_POINTS], margin,
-                       (float *)e->sg_buf[RR_SG_GRADIENT], (float *)e->sg_buf[RR_SG_COST], postures ? (float *)nullptr : (float *)e->sg_buf[RR_SG_PAIR_GRADIENT]);
+                       (float4 *)b[RR_SD_DEEPEST], (int4 *)b[RR_SD_ID], (float *)b[RR_SD_SIGNED], (int *)b[RR_SD_STATUS],
+                       postures ? (float4 *)nullptr : (float4 *)b[RR_SD_POINTS], margin,
+                       (float *)g[RR_SG_GRADIENT], (float *)g[RR_SG_COST], postures ? (float *)nullptr : (float *)g[RR_SG_PAIR_GRADIENT]);
     HIPCHK(hipGetLastError());
-    e->sd_k = K;
-    e->sg_k = K;
-    if (stage) HIPCHK(hipStreamSynchronize(e->stream));        // the argument is host memory
-    return RR_OK;
+    e->qk[QF_SD] = e->qk[QF_SG] = K;
+    return st.wait();
 }
 
-int rr_signed_gradient_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_signed_gradient_buffer: null env");
-    if (which < 0 || which >= RR_SG_COUNT) return fail(RR_EINVAL, "rr_signed_gradient_buffer: buffer " + std::to_string(which) + " is not in [0, RR_SG_COUNT)");
-    RRCHK(ensure_signed_gradient(e, "rr_signed_gradient_buffer"));
-    if (dev_ptr) *dev_ptr = e->sg_buf[which];
-    if (bytes) *bytes = sg_bytes(e, which, e->sg_k, e->dist_n);
-    return RR_OK;
-}
-
-int rr_signed_gradient_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_signed_gradient_copy_to_host: null env");
-    if (!dst) return fail(RR_EINVAL, "rr_signed_gradient_copy_to_host: null destination");
-    if (which < 0 || which >= RR_SG_COUNT) return fail(RR_EINVAL, "rr_signed_gradient_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_SG_COUNT)");
-    if (bytes != sg_bytes(e, which, e->sg_k, e->dist_n)) return fail(RR_EINVAL, "rr_signed_gradient_copy_to_host: size mismatch");
-    RRCHK(ensure_signed_gradient(e, "rr_signed_gradient_copy_to_host"));
-    HIPCHK(hipSetDevice(e->cfg.device));
-    if (bytes == 0) return RR_OK;
-    HIPCHK(hipMemcpyAsync(dst, e->sg_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return RR_OK;
-}
+int rr_signed_gradient_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) { return query_buffer(query_view(e, QF_SG), HIP_QUERY, which, dev_ptr, bytes); }
+int rr_signed_gradient_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) { return query_copy_to_host(query_view(e, QF_SG), HIP_QUERY, which, dst, bytes); }
 
 // ---- swept clearance along joint-space segments (rr_sweep.inc) -------------------------------------------------------------------------
-// The four buffers of rr_swept_clearance and the device copy of the reach table: allocated on first use -- by the query or by
-// rr_sweep_buffer / rr_sweep_copy_to_host -- in one list, zero-filled, for RR_PC_MAX_POSTURES segments of RR_DIST_MAX pairs; the table
-// goes up behind it.  The layout in force is [N, K, ...] for the K of the last query (0 before the first) and the Q of the pair table.
-static size_t sw_bytes(const rr_env *e, int which, int K, int Q) {
-    return (size_t)e->P.N * K * (which == RR_SW_STOP || which == RR_SW_HIT ? 48 : which == RR_SW_ID ? 16 : (size_t)Q * 4);
-}
-static int ensure_sweep(rr_env *e, const char *who) {
-    if (e->sw_buf[0]) return RR_OK;
-    HIPCHK(hipSetDevice(e->cfg.device));
-    void *b[RR_SW_COUNT] = {};
-    SweepReach *rd = nullptr;
-    MemPart parts[RR_SW_COUNT + 1];
-    for (int i = 0; i < RR_SW_COUNT; i++) parts[i] = mem_part(&b[i], sw_bytes(e, i, RR_PC_MAX_POSTURES, RR_DIST_MAX));
-    parts[RR_SW_COUNT] = mem_part(&rd, sizeof(SweepReach), false);
-    RRCHK(mem_get(e, parts, RR_SW_COUNT + 1, (std::string(who) + ": allocating the sweep buffers").c_str()));
-    hipError_t rc = hipMemcpyAsync(rd, &e->sweep_reach, sizeof(SweepReach), hipMemcpyHostToDevice, e->stream);
-    if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);      // (the source is the handle's own memory)
-    if (rc != hipSuccess) {
-        (void)hipStreamSynchronize(e->stream);
-        for (int i = 0; i < RR_SW_COUNT; i++) e->mem.release(b[i]);
-        e->mem.release(rd);
-        (void)hipGetLastError();
-        return fail(RR_EDEVICE, std::string(who) + ": uploading the reach table: " + hipGetErrorString(rc));
-    }
-    for (int i = 0; i < RR_SW_COUNT; i++) e->sw_buf[i] = b[i];
-    e->sw_reach_dev = rd;
-    return RR_OK;
-}
-
 // Conservative advancement along K segments per env, on the device.  On the main stream like rr_posture_clearance: behind every step,
 // reset and state write enqueued before it.  Reads D.state (the objects), the model, the pair table, the reach table and the tensor;
 // writes the four buffers and nothing else -- not the state, the scratch slab of the look-ahead, la_valid, an error flag or a buffer of
@@ -2047,22 +1831,18 @@ int rr_swept_clearance(rr_env *e, const float *segments, int32_t n_segments, int
     if (maxd > 0.0f && maxd < INFINITY && maxd < safety + tolerance)
         return fail(RR_EINVAL, "rr_swept_clearance: the cull's max_distance " + std::to_string(maxd) + " is below safety + tolerance = " +
                                    std::to_string(safety + tolerance) + ": a culled pair's sphere gap could fake a hit");
-    RRCHK(ensure_dist(e, "rr_swept_clearance"));          // (the device copy of the pair table)
-    RRCHK(ensure_sweep(e, "rr_swept_clearance"));
-    if (!on_device && !e->sw_stage)
-        RRCHK(mem_get(e, {mem_part(&e->sw_stage, (size_t)N * RR_PC_MAX_POSTURES * 88, false)}, "rr_swept_clearance: allocating the staging buffer"));
+    RRCHK(ensure_query(e, QF_DIST, "rr_swept_clearance"));       // (the device copy of the pair table)
+    RRCHK(ensure_query(e, QF_SW, "rr_swept_clearance", {stage_part(&e->sw_stage, (size_t)N * RR_PC_MAX_POSTURES * 88, !on_device)}));
     HIPCHK(hipSetDevice(e->cfg.device));
+    const HostStaging st = {e, !on_device};
     const float *src = segments;
-    if (!on_device) {
-        HIPCHK(hipMemcpyAsync(e->sw_stage, segments, (size_t)N * K * 88, hipMemcpyHostToDevice, e->stream));
-        src = e->sw_stage;
-    }
+    RRCHK(st.in(src, e->sw_stage, (size_t)N * K * 88));
+    void *const *b = e->qbuf[QF_SW];
     hipLaunchKernelGGL(k_swept_clearance, dim3((unsigned)N * K), dim3(SWEEP_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, e->sw_reach_dev, src, K,
-                       safety, tolerance, (float *)e->sw_buf[RR_SW_STOP], (float4 *)e->sw_buf[RR_SW_HIT], (int4 *)e->sw_buf[RR_SW_ID], (float *)e->sw_buf[RR_SW_FREE]);
+                       safety, tolerance, (float *)b[RR_SW_STOP], (float4 *)b[RR_SW_HIT], (int4 *)b[RR_SW_ID], (float *)b[RR_SW_FREE]);
     HIPCHK(hipGetLastError());
-    e->sw_k = K;
-    if (!on_device) HIPCHK(hipStreamSynchronize(e->stream));   // the argument is host memory
-    return RR_OK;
+    e->qk[QF_SW] = K;
+    return st.wait();
 }
 
 int rr_sweep_reach(rr_env *e, float *out) {
@@ -2072,51 +1852,10 @@ int rr_sweep_reach(rr_env *e, float *out) {
     return RR_OK;
 }
 
-int rr_sweep_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_sweep_buffer: null env");
-    if (which < 0 || which >= RR_SW_COUNT) return fail(RR_EINVAL, "rr_sweep_buffer: buffer " + std::to_string(which) + " is not in [0, RR_SW_COUNT)");
-    RRCHK(ensure_sweep(e, "rr_sweep_buffer"));
-    if (dev_ptr) *dev_ptr = e->sw_buf[which];
-    if (bytes) *bytes = sw_bytes(e, which, e->sw_k, e->dist_n);
-    return RR_OK;
-}
-
-int rr_sweep_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_sweep_copy_to_host: null env");
-    if (!dst) return fail(RR_EINVAL, "rr_sweep_copy_to_host: null destination");
-    if (which < 0 || which >= RR_SW_COUNT) return fail(RR_EINVAL, "rr_sweep_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_SW_COUNT)");
-    if (bytes != sw_bytes(e, which, e->sw_k, e->dist_n)) return fail(RR_EINVAL, "rr_sweep_copy_to_host: size mismatch");
-    RRCHK(ensure_sweep(e, "rr_sweep_copy_to_host"));
-    HIPCHK(hipSetDevice(e->cfg.device));
-    if (bytes == 0) return RR_OK;
-    HIPCHK(hipMemcpyAsync(dst, e->sw_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return RR_OK;
-}
+int rr_sweep_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) { return query_buffer(query_view(e, QF_SW), HIP_QUERY, which, dev_ptr, bytes); }
+int rr_sweep_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) { return query_copy_to_host(query_view(e, QF_SW), HIP_QUERY, which, dst, bytes); }
 
 // ---- kinematics at candidate postures (rr_pkin.inc) -------------------------------------------------------------------------------------
-// The three buffers of rr_posture_kinematics: allocated on first use -- by the query or by rr_posture_kinematics_buffer /
-// rr_posture_kinematics_copy_to_host -- in one list, zero-filled, for RR_PC_MAX_POSTURES postures of RR_KIN_MAX_POINTS points.  The
-// layout in force is [N, K, ...] for the K of the last query (0 before the first) and the P of rr_set_kinematic_points.  The model
-// condition is ensure_kinematics': the kernel's link table has the 17 rows of rr_link_poses, every one on a body of the tree.
-static size_t pk_bytes(const rr_env *e, int which, int K, int np) {
-    const size_t row[RR_PK_COUNT] = {KIN_LINKS * 7, (size_t)3 * np, (size_t)6 * NB * np};
-    return (size_t)e->P.N * K * row[which] * 4;
-}
-static int ensure_pkin(rr_env *e, const char *who) {
-    if (e->pk_buf[0]) return RR_OK;
-    if (e->RM.nl != KIN_LINKS) return fail(RR_EINVAL, std::string(who) + ": the model does not have the 17 URDF links of rr_link_poses");
-    for (int l = 0; l < KIN_LINKS; l++)
-        if (e->RM.link_body[l] >= NB) return fail(RR_EINVAL, std::string(who) + ": link " + std::to_string(l) + " of the model is on a body outside the kinematic tree");
-    HIPCHK(hipSetDevice(e->cfg.device));
-    float *b[RR_PK_COUNT] = {};
-    MemPart parts[RR_PK_COUNT];
-    for (int i = 0; i < RR_PK_COUNT; i++) parts[i] = mem_part(&b[i], pk_bytes(e, i, RR_PC_MAX_POSTURES, RR_KIN_MAX_POINTS));
-    RRCHK(mem_get(e, parts, RR_PK_COUNT, (std::string(who) + ": allocating the posture kinematics buffers").c_str()));
-    for (int i = 0; i < RR_PK_COUNT; i++) e->pk_buf[i] = b[i];
-    return RR_OK;
-}
-
 // Link poses, point positions and Jacobians at K candidate postures per env, on the device.  On the main stream like
 // rr_posture_clearance: behind every step, reset and state write enqueued before it.  Reads the tensor, the model and the points (the
 // handle's host copy goes to the kernel by value: a call enqueued earlier keeps the points it was launched with); writes the three
@@ -2128,81 +1867,25 @@ int rr_posture_kinematics(rr_env *e, const float *postures, int32_t n_postures, 
         return fail(RR_EINVAL, "rr_posture_kinematics: n_postures " + std::to_string(n_postures) + " is not in [1, RR_PC_MAX_POSTURES = " +
                                    std::to_string(RR_PC_MAX_POSTURES) + "]");
     const int N = e->P.N, K = n_postures;
-    RRCHK(ensure_pkin(e, "rr_posture_kinematics"));
-    if (!on_device && !e->pc_stage)
-        RRCHK(mem_get(e, {mem_part(&e->pc_stage, (size_t)N * RR_PC_MAX_POSTURES * 44, false)}, "rr_posture_kinematics: allocating the staging buffer"));
+    RRCHK(ensure_query(e, QF_PK, "rr_posture_kinematics", {posture_stage(e, !on_device)}));
     HIPCHK(hipSetDevice(e->cfg.device));
+    const HostStaging st = {e, !on_device};
     const float *src = postures;
-    if (!on_device) {
-        HIPCHK(hipMemcpyAsync(e->pc_stage, postures, (size_t)N * K * 44, hipMemcpyHostToDevice, e->stream));
-        src = e->pc_stage;
-    }
+    RRCHK(st.in(src, e->pc_stage, (size_t)N * K * 44));
     const int rows = N * K;
-    const PkOut O = {e->pk_buf[RR_PK_LINK_POSE], e->pk_buf[RR_PK_POINT_POS], e->pk_buf[RR_PK_JACOBIAN]};
+    float *const *b = (float *const *)e->qbuf[QF_PK];
+    const PkOut O = {b[RR_PK_LINK_POSE], b[RR_PK_POINT_POS], b[RR_PK_JACOBIAN]};
     hipLaunchKernelGGL(k_posture_kinematics, dim3((unsigned)((rows + PK_ROWS - 1) / PK_ROWS)), dim3(PK_THREADS), 0, e->stream, e->B, e->RM_dev, src, rows, O,
                        e->kin_pts, e->kin_np);
     HIPCHK(hipGetLastError());
-    e->pk_k = K;
-    if (!on_device) HIPCHK(hipStreamSynchronize(e->stream));   // the argument is host memory
-    return RR_OK;
+    e->qk[QF_PK] = K;
+    return st.wait();
 }
 
-int rr_posture_kinematics_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_posture_kinematics_buffer: null env");
-    if (which < 0 || which >= RR_PK_COUNT) return fail(RR_EINVAL, "rr_posture_kinematics_buffer: buffer " + std::to_string(which) + " is not in [0, RR_PK_COUNT)");
-    RRCHK(ensure_pkin(e, "rr_posture_kinematics_buffer"));
-    if (dev_ptr) *dev_ptr = e->pk_buf[which];
-    if (bytes) *bytes = pk_bytes(e, which, e->pk_k, e->kin_np);
-    return RR_OK;
-}
-
-int rr_posture_kinematics_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_posture_kinematics_copy_to_host: null env");
-    if (!dst) return fail(RR_EINVAL, "rr_posture_kinematics_copy_to_host: null destination");
-    if (which < 0 || which >= RR_PK_COUNT) return fail(RR_EINVAL, "rr_posture_kinematics_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_PK_COUNT)");
-    if (bytes != pk_bytes(e, which, e->pk_k, e->kin_np)) return fail(RR_EINVAL, "rr_posture_kinematics_copy_to_host: size mismatch");
-    RRCHK(ensure_pkin(e, "rr_posture_kinematics_copy_to_host"));
-    HIPCHK(hipSetDevice(e->cfg.device));
-    if (bytes == 0) return RR_OK;
-    HIPCHK(hipMemcpyAsync(dst, e->pk_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return RR_OK;
-}
+int rr_posture_kinematics_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) { return query_buffer(query_view(e, QF_PK), HIP_QUERY, which, dev_ptr, bytes); }
+int rr_posture_kinematics_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) { return query_copy_to_host(query_view(e, QF_PK), HIP_QUERY, which, dst, bytes); }
 
 // ---- inverse kinematics at candidate targets (rr_pik.inc) ------------------------------------------------------------------------------
-// The three buffers of rr_posture_ik: allocated on first use -- by the call or by rr_posture_ik_buffer / rr_posture_ik_copy_to_host --
-// in one list, zero-filled, for RR_PC_MAX_POSTURES targets per env.  The layout in force is [N, K, ...] for the K of the last call
-// (0 before the first).  The model condition is ensure_pkin's: the kernel reads the link table of rr_link_poses.
-static size_t pik_bytes(const rr_env *e, int which, int K) {
-    const size_t row[RR_PIK_COUNT] = {NB * 4, 4 * 4, 2 * 4};
-    return (size_t)e->P.N * K * row[which];
-}
-// `stage_seeds` / `stage_targets`: the staging buffers a host-path call still lacks come in the same list, all or nothing
-static int ensure_pik(rr_env *e, const char *who, bool stage_seeds = false, bool stage_targets = false) {
-    stage_seeds = stage_seeds && !e->pc_stage;
-    stage_targets = stage_targets && !e->pik_stage;
-    const bool bufs = !e->pik_buf[0];
-    if (!bufs && !stage_seeds && !stage_targets) return RR_OK;
-    if (e->RM.nl != KIN_LINKS) return fail(RR_EINVAL, std::string(who) + ": the model does not have the 17 URDF links of rr_link_poses");
-    for (int l = 0; l < KIN_LINKS; l++)
-        if (e->RM.link_body[l] >= NB) return fail(RR_EINVAL, std::string(who) + ": link " + std::to_string(l) + " of the model is on a body outside the kinematic tree");
-    HIPCHK(hipSetDevice(e->cfg.device));
-    void *b[RR_PIK_COUNT] = {};
-    float *ss = nullptr, *ts = nullptr;
-    MemPart parts[RR_PIK_COUNT + 2];
-    size_t n = 0;
-    if (bufs)
-        for (int i = 0; i < RR_PIK_COUNT; i++) parts[n++] = mem_part(&b[i], pik_bytes(e, i, RR_PC_MAX_POSTURES));
-    if (stage_seeds) parts[n++] = mem_part(&ss, (size_t)e->P.N * RR_PC_MAX_POSTURES * 44, false);
-    if (stage_targets) parts[n++] = mem_part(&ts, (size_t)e->P.N * RR_PC_MAX_POSTURES * 28, false);
-    RRCHK(mem_get(e, parts, n, (std::string(who) + ": allocating the posture IK buffers").c_str()));
-    if (bufs)
-        for (int i = 0; i < RR_PIK_COUNT; i++) e->pik_buf[i] = b[i];
-    if (stage_seeds) e->pc_stage = ss;
-    if (stage_targets) e->pik_stage = ts;
-    return RR_OK;
-}
-
 // K target tool poses per env solved on the device.  On the main stream like rr_posture_clearance: behind every step, reset and
 // state write enqueued before it.  Reads the two tensors (without seeds: the joint columns of the state), the model and the points
 // (the handle's host copy goes to the kernel by value); writes the three buffers and nothing else -- not the state, the scratch slab
@@ -2224,19 +1907,15 @@ int rr_posture_ik(rr_env *e, const float *targets, const float *seeds, int32_t n
     if (!(o.max_step > 0.0f) || !std::isfinite(o.max_step)) return fail(RR_EINVAL, "rr_posture_ik: max_step " + std::to_string(o.max_step) + " is not a finite number > 0");
     if (o.flags & ~(uint32_t)(RR_PIK_POSITION_ONLY | RR_PIK_CLAMP_LIMITS)) return fail(RR_EINVAL, "rr_posture_ik: unknown flag bits in " + std::to_string(o.flags));
     const int N = e->P.N, K = n_targets;
-    RRCHK(ensure_pik(e, "rr_posture_ik", !on_device && seeds, !on_device));
+    RRCHK(ensure_query(e, QF_PIK, "rr_posture_ik", {posture_stage(e, !on_device && seeds), stage_part(&e->pik_stage, (size_t)N * RR_PC_MAX_POSTURES * 28, !on_device)}));
     HIPCHK(hipSetDevice(e->cfg.device));
+    const HostStaging st = {e, !on_device};
     const float *tsrc = targets, *ssrc = seeds;
-    if (!on_device) {
-        HIPCHK(hipMemcpyAsync(e->pik_stage, targets, (size_t)N * K * 28, hipMemcpyHostToDevice, e->stream));
-        tsrc = e->pik_stage;
-        if (seeds) {
-            HIPCHK(hipMemcpyAsync(e->pc_stage, seeds, (size_t)N * K * 44, hipMemcpyHostToDevice, e->stream));
-            ssrc = e->pc_stage;
-        }
-    }
+    RRCHK(st.in(tsrc, e->pik_stage, (size_t)N * K * 28));
+    RRCHK(st.in(ssrc, e->pc_stage, (size_t)N * K * 44));
     const int rows = N * K;
-    const PikOut O = {(float *)e->pik_buf[RR_PIK_POSTURE], (float *)e->pik_buf[RR_PIK_RESULT], (int *)e->pik_buf[RR_PIK_INFO]};
+    void *const *b = e->qbuf[QF_PIK];
+    const PikOut O = {(float *)b[RR_PIK_POSTURE], (float *)b[RR_PIK_RESULT], (int *)b[RR_PIK_INFO]};
     const PikOpt po = {o.point, o.max_iterations, o.tolerance, o.damping * o.damping, o.max_step, o.flags};
     // (one instantiation per system size: 6 x 6 full pose, 3 x 3 position only)
     if (o.flags & RR_PIK_POSITION_ONLY)
@@ -2246,64 +1925,14 @@ int rr_posture_ik(rr_env *e, const float *targets, const float *seeds, int32_t n
         hipLaunchKernelGGL(k_posture_ik<0>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, e->stream, e->B, e->RM_dev, tsrc, ssrc, (const float *)e->D.state, N, K,
                            O, e->kin_pts, po);
     HIPCHK(hipGetLastError());
-    e->pik_k = K;
-    if (!on_device) HIPCHK(hipStreamSynchronize(e->stream));   // the arguments are host memory
-    return RR_OK;
+    e->qk[QF_PIK] = K;
+    return st.wait();
 }
 
-int rr_posture_ik_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_posture_ik_buffer: null env");
-    if (which < 0 || which >= RR_PIK_COUNT) return fail(RR_EINVAL, "rr_posture_ik_buffer: buffer " + std::to_string(which) + " is not in [0, RR_PIK_COUNT)");
-    RRCHK(ensure_pik(e, "rr_posture_ik_buffer"));
-    if (dev_ptr) *dev_ptr = e->pik_buf[which];
-    if (bytes) *bytes = pik_bytes(e, which, e->pik_k);
-    return RR_OK;
-}
-
-int rr_posture_ik_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_posture_ik_copy_to_host: null env");
-    if (!dst) return fail(RR_EINVAL, "rr_posture_ik_copy_to_host: null destination");
-    if (which < 0 || which >= RR_PIK_COUNT) return fail(RR_EINVAL, "rr_posture_ik_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_PIK_COUNT)");
-    if (bytes != pik_bytes(e, which, e->pik_k)) return fail(RR_EINVAL, "rr_posture_ik_copy_to_host: size mismatch");
-    RRCHK(ensure_pik(e, "rr_posture_ik_copy_to_host"));
-    HIPCHK(hipSetDevice(e->cfg.device));
-    if (bytes == 0) return RR_OK;
-    HIPCHK(hipMemcpyAsync(dst, e->pik_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return RR_OK;
-}
+int rr_posture_ik_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) { return query_buffer(query_view(e, QF_PIK), HIP_QUERY, which, dev_ptr, bytes); }
+int rr_posture_ik_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) { return query_copy_to_host(query_view(e, QF_PIK), HIP_QUERY, which, dst, bytes); }
 
 // ---- joint-space dynamics at candidate postures (rr_pdyn.inc) ---------------------------------------------------------------------------
-// The five buffers of rr_posture_dynamics: allocated on first use -- by the call or by rr_posture_dynamics_buffer /
-// rr_posture_dynamics_copy_to_host -- in one list, zero-filled, for RR_PC_MAX_POSTURES rows per env.  The layout in force is
-// [N, K, ...] for the K of the last call (0 before the first).
-static size_t pd_bytes(const rr_env *e, int which, int K) {
-    const size_t row[RR_PD_COUNT] = {NB * NB, NB, NB, NB, NB * NB};
-    return (size_t)e->P.N * K * row[which] * 4;
-}
-// `stage_q` / `stage_v`: the staging blocks a host-path call still lacks come in the same list, all or nothing
-static int ensure_pdyn(rr_env *e, const char *who, bool stage_q = false, bool stage_v = false) {
-    stage_q = stage_q && !e->pc_stage;
-    stage_v = stage_v && !e->pd_stage;
-    const bool bufs = !e->pd_buf[0];
-    if (!bufs && !stage_q && !stage_v) return RR_OK;
-    HIPCHK(hipSetDevice(e->cfg.device));
-    float *b[RR_PD_COUNT] = {};
-    float *qs = nullptr, *vs = nullptr;
-    MemPart parts[RR_PD_COUNT + 2];
-    size_t n = 0;
-    if (bufs)
-        for (int i = 0; i < RR_PD_COUNT; i++) parts[n++] = mem_part(&b[i], pd_bytes(e, i, RR_PC_MAX_POSTURES));
-    if (stage_q) parts[n++] = mem_part(&qs, (size_t)e->P.N * RR_PC_MAX_POSTURES * 44, false);
-    if (stage_v) parts[n++] = mem_part(&vs, (size_t)2 * e->P.N * RR_PC_MAX_POSTURES * 44, false);
-    RRCHK(mem_get(e, parts, n, (std::string(who) + ": allocating the posture dynamics buffers").c_str()));
-    if (bufs)
-        for (int i = 0; i < RR_PD_COUNT; i++) e->pd_buf[i] = b[i];
-    if (stage_q) e->pc_stage = qs;
-    if (stage_v) e->pd_stage = vs;
-    return RR_OK;
-}
-
 // M, G, G + C, M qdd + C + G and on request M^-1 at K rows per env, on the device.  On the main stream like rr_posture_clearance:
 // behind every step, reset and state write enqueued before it.  Reads the tensors (without postures: the joint columns of the
 // state), the model and the handle's body table -- the one the preparation reads --; writes the five buffers and nothing else: not
@@ -2319,75 +1948,40 @@ int rr_posture_dynamics(rr_env *e, const float *postures, const float *velocitie
     if (flags & ~(uint32_t)RR_PD_INVERSE) return fail(RR_EINVAL, "rr_posture_dynamics: unknown flag bits in " + std::to_string(flags));
     const int N = e->P.N, K = n_postures;
     const size_t tensor = (size_t)N * K * 44;
-    RRCHK(ensure_pdyn(e, "rr_posture_dynamics", !on_device && postures, !on_device && (velocities || accelerations)));
+    RRCHK(ensure_query(e, QF_PD, "rr_posture_dynamics", {posture_stage(e, !on_device && postures),
+                                                         stage_part(&e->pd_stage, (size_t)2 * N * RR_PC_MAX_POSTURES * 44, !on_device && (velocities || accelerations))}));
     HIPCHK(hipSetDevice(e->cfg.device));
+    const HostStaging st = {e, !on_device};      // (the wait also without a tensor: one rule for the host path)
     PdIn in = {postures, velocities, accelerations, NB, 1};
-    if (!on_device) {
-        if (postures) { HIPCHK(hipMemcpyAsync(e->pc_stage, postures, tensor, hipMemcpyHostToDevice, e->stream)); in.q = e->pc_stage; }
-        if (velocities) { HIPCHK(hipMemcpyAsync(e->pd_stage, velocities, tensor, hipMemcpyHostToDevice, e->stream)); in.qd = e->pd_stage; }
-        if (accelerations) {
-            float *dst = e->pd_stage + (size_t)N * RR_PC_MAX_POSTURES * NB;
-            HIPCHK(hipMemcpyAsync(dst, accelerations, tensor, hipMemcpyHostToDevice, e->stream));
-            in.qdd = dst;
-        }
-    }
+    RRCHK(st.in(in.q, e->pc_stage, tensor));
+    RRCHK(st.in(in.qd, e->pd_stage, tensor));
+    RRCHK(st.in(in.qdd, e->pd_stage + (size_t)N * RR_PC_MAX_POSTURES * NB, tensor));
     if (!postures) {      // the present state: row e is env e, q and qd the columns ST_Q.. and ST_QD.. of the [61][N] state
         in.q = (const float *)e->D.state + (size_t)ST_Q * N;
         in.qd = (const float *)e->D.state + (size_t)ST_QD * N;
         in.rs = 1; in.cs = (size_t)N;
     }
     const int rows = N * K;
-    const PdOut O = {e->pd_buf[RR_PD_MASS_MATRIX], e->pd_buf[RR_PD_GRAVITY], e->pd_buf[RR_PD_BIAS], e->pd_buf[RR_PD_TORQUE], e->pd_buf[RR_PD_MASS_INVERSE]};
+    float *const *b = (float *const *)e->qbuf[QF_PD];
+    const PdOut O = {b[RR_PD_MASS_MATRIX], b[RR_PD_GRAVITY], b[RR_PD_BIAS], b[RR_PD_TORQUE], b[RR_PD_MASS_INVERSE]};
     const dim3 grid((unsigned)((rows + PD_ROWS - 1) / PD_ROWS));
     if (flags & RR_PD_INVERSE)
         hipLaunchKernelGGL(k_posture_dynamics<true>, grid, dim3(PD_THREADS), 0, e->stream, e->B, (const float *)e->D.body_tab, e->P.gravity, in, rows, O);
     else
         hipLaunchKernelGGL(k_posture_dynamics<false>, grid, dim3(PD_THREADS), 0, e->stream, e->B, (const float *)e->D.body_tab, e->P.gravity, in, rows, O);
     HIPCHK(hipGetLastError());
-    e->pd_k = K;
-    if (!on_device) HIPCHK(hipStreamSynchronize(e->stream));   // the arguments may be host memory; one rule for the host path
-    return RR_OK;
+    e->qk[QF_PD] = K;
+    return st.wait();
 }
 
-int rr_posture_dynamics_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_posture_dynamics_buffer: null env");
-    if (which < 0 || which >= RR_PD_COUNT) return fail(RR_EINVAL, "rr_posture_dynamics_buffer: buffer " + std::to_string(which) + " is not in [0, RR_PD_COUNT)");
-    RRCHK(ensure_pdyn(e, "rr_posture_dynamics_buffer"));
-    if (dev_ptr) *dev_ptr = e->pd_buf[which];
-    if (bytes) *bytes = pd_bytes(e, which, e->pd_k);
-    return RR_OK;
-}
-
-int rr_posture_dynamics_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
-    if (!e) return fail(RR_EINVAL, "rr_posture_dynamics_copy_to_host: null env");
-    if (!dst) return fail(RR_EINVAL, "rr_posture_dynamics_copy_to_host: null destination");
-    if (which < 0 || which >= RR_PD_COUNT) return fail(RR_EINVAL, "rr_posture_dynamics_copy_to_host: buffer " + std::to_string(which) + " is not in [0, RR_PD_COUNT)");
-    if (bytes != pd_bytes(e, which, e->pd_k)) return fail(RR_EINVAL, "rr_posture_dynamics_copy_to_host: size mismatch");
-    RRCHK(ensure_pdyn(e, "rr_posture_dynamics_copy_to_host"));
-    HIPCHK(hipSetDevice(e->cfg.device));
-    if (bytes == 0) return RR_OK;
-    HIPCHK(hipMemcpyAsync(dst, e->pd_buf[which], bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return RR_OK;
-}
+int rr_posture_dynamics_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) { return query_buffer(query_view(e, QF_PD), HIP_QUERY, which, dev_ptr, bytes); }
+int rr_posture_dynamics_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) { return query_copy_to_host(query_view(e, QF_PD), HIP_QUERY, which, dst, bytes); }
 
 // ---- joint torque inputs of the step (rr_torque.inc) ------------------------------------------------------------------------------------
 // The table tau [N][11] and, for a host caller, its staging block: on first use, all or nothing, the table zero-filled.
 static int ensure_torques(rr_env *e, const char *who, bool stage = false) {
-    stage = stage && !e->jt_stage;
-    const bool table = !e->jt_table;
-    if (!table && !stage) return RR_OK;
-    HIPCHK(hipSetDevice(e->cfg.device));
-    float *t = nullptr, *st = nullptr;
-    MemPart parts[2];
-    size_t n = 0;
     const size_t bytes = (size_t)e->P.N * NB * 4;
-    if (table) parts[n++] = mem_part(&t, bytes);
-    if (stage) parts[n++] = mem_part(&st, bytes, false);
-    RRCHK(mem_get(e, parts, n, (std::string(who) + ": allocating the joint torque table").c_str()));
-    if (table) e->jt_table = t;
-    if (stage) e->jt_stage = st;
-    return RR_OK;
+    return ensure_group(e, -1, who, "the joint torque table", {mem_part(&e->jt_table, bytes), stage_part(&e->jt_stage, bytes, stage)});
 }
 
 // The rows of the masked envs into the handle's table, one launch on the main stream: behind every step enqueued before it (whose
@@ -2444,20 +2038,8 @@ int rr_get_joint_torques(rr_env *e, float *out_host) {
 // ---- external wrenches of the step (rr_wrench.inc) ---------------------------------------------------------------------------------------
 // The table w [N][14][6] and, for a host caller, its staging block: on first use, all or nothing, the table zero-filled.
 static int ensure_wrenches(rr_env *e, const char *who, bool stage = false) {
-    stage = stage && !e->xw_stage;
-    const bool table = !e->xw_table;
-    if (!table && !stage) return RR_OK;
-    HIPCHK(hipSetDevice(e->cfg.device));
-    float *t = nullptr, *st = nullptr;
-    MemPart parts[2];
-    size_t n = 0;
     const size_t bytes = (size_t)e->P.N * RR_XW_BODIES * 6 * 4;
-    if (table) parts[n++] = mem_part(&t, bytes);
-    if (stage) parts[n++] = mem_part(&st, bytes, false);
-    RRCHK(mem_get(e, parts, n, (std::string(who) + ": allocating the external wrench table").c_str()));
-    if (table) e->xw_table = t;
-    if (stage) e->xw_stage = st;
-    return RR_OK;
+    return ensure_group(e, -1, who, "the external wrench table", {mem_part(&e->xw_table, bytes), stage_part(&e->xw_stage, bytes, stage)});
 }
 
 // The rows of the masked envs into the handle's table, one launch on the main stream: behind every step enqueued before it (whose
