@@ -46,7 +46,8 @@ extern "C" {
                               rr_signed_gradient_buffer, rr_signed_gradient_copy_to_host (that query plus the joint gradients of the
                               deepest pair's signed distance and of a hinge collision cost, reduced on the device);
                               rr_swept_clearance, rr_sweep_reach, rr_sweep_buffer, rr_sweep_copy_to_host (first contact of the pair
-                              table along joint-space segments, by conservative advancement) */
+                              table along joint-space segments, by conservative advancement); rr_set_attachments,
+                              rr_get_attachments (objects attached to robot links in the posture queries) */
 
 enum {
     RR_OK = 0,
@@ -718,7 +719,8 @@ enum {
 #define RR_PC_MAX_POSTURES 32
 /* What is computed.  Posture (e, k), k in [0, K = n_postures), is evaluated as if columns 0..10 of env e's RR_F_STATE row were
  * postures[e][k][0..10]; the objects stay at env e's PRESENT pose -- whatever the last step, reset, rr_set_state, rr_write_state,
- * rr_set_object_pose(s), rr_copy_envs or restore left.  The pair table and the cull are those of rr_set_distance_pairs, and a pair
+ * rr_set_object_pose(s), rr_copy_envs or restore left (an object attached to a link, rr_set_attachments, moves with that link instead).
+ * The pair table and the cull are those of rr_set_distance_pairs, and a pair
  * means exactly what it means to rr_closest_points (the block above: the convex hulls of the vertex sets, the shapes' frames, the
  * statuses 0 to 3, the relative gap 1e-12 that ends the search, touching at 1e-6 m, the cap of 32 trips, support ties to the lowest
  * vertex index); the two kernels run the same device text for a pair.
@@ -855,7 +857,8 @@ enum {
  *     ds/dq_k = [joint k moves A's body] n . (a_k x (a - p_k)) - [joint k moves B's body] n . (a_k x (b - p_k)),
  * a_k the world axis of joint k at that row's posture and p_k its position; "moves": k is the body's own joint or an ancestor's.
  * Static shapes (table, shelf, robot_base) and the objects have no columns: the objects stay where they are, as for
- * rr_posture_clearance, and a joint that moves neither shape gets +0.0.  The columns are over the eleven independent joints of the
+ * rr_posture_clearance, and a joint that moves neither shape gets +0.0.  (An object attached to a link, rr_set_attachments, moves with that
+ * link and takes the columns of the link's body.)  The columns are over the eleven independent joints of the
  * state's q[11]; over the nine command entries the gradient is gradient @ Q_FROM_CMD of the binding.  By status of the pair:
  * 0, 1: the gradient of the signed distance; 2 (culled): the same expression on the sphere points, exactly the gradient of the
  * reported sphere gap; 3, 5: the expression on the record as reported; 4 (touching, n = +0.0): +0.0 in every column.  Where the
@@ -1260,6 +1263,52 @@ int rr_get_external_wrenches(rr_env *env, float *out_host);
  * WRITE it in stream order (on the library's stream or ordered before later work on it): the next step uses what it finds --
  * provided the feature is on (a successful rr_set_external_wrenches with a table since the last clearing call). */
 int rr_external_wrench_buffer(rr_env *env, void **dev_ptr, size_t *bytes);
+
+/* Carried objects in the posture queries: objects attached to robot links (additive in ABI 7; k_posture_clearance_carry,
+ * k_signed_distance_carry, k_signed_gradient_carry, k_attach_capture: csrc/rr_carry.inc).  What planners call an ATTACHED body: once
+ * the gripper holds the cube, a candidate posture must move the cube with the hand, or the (finger, cube) pairs report the arm's
+ * motion against a stationary cube and the (cube, shelf) / (cube, table) pairs never change.  It replaces the write-and-query loop --
+ * rr_write_state of the composed object pose per candidate, then a present-state query -- that rr_posture_clearance was added to
+ * retire.
+ * A QUERY-SIDE SETTING of the handle, like the pair table and the kinematic points: NOT a constraint of the simulation (pybullet's
+ * createConstraint is out of scope), no step reads it, and the state, the preparation record and the look-ahead are never touched.
+ * The table says, per (env, object), the URDF link the object is rigid with -- link[e][o] in [0, 17), the order of rr_link_poses and
+ * rr_set_kinematic_points, or -1: FREE -- and rel_pose[e][o], xyz + xyzw: the object's state pose expressed in that link's COM frame
+ * (the frame of RR_KIN_LINK_POSE), link_pose^-1 o object pose.  While the feature is on, rr_posture_clearance, rr_signed_distance and
+ * rr_signed_gradient place an attached object at T_link(posture) o rel -- R_o = R_b R_rel, p_o = p_b + R_b t_rel from the row's forward
+ * kinematics, not from the state -- and, in the gradient, give its shapes the joint columns of the link's body, at candidate postures
+ * and at the present state (postures == NULL) alike: RR_SG_PAIR_GRADIENT then has columns for a carried object.  A free object, and
+ * every object of an env with no attachment, is staged by the operations of the original kernels: every number that no carried shape
+ * enters has the bits it has with the feature off.  The same buffers with the same layouts are written; body_a / body_b keep reporting
+ * 16 + o for an object, attached or not.  rr_closest_points is unaffected (at the present state an object is where the state says).
+ * rr_swept_clearance REFUSES while the feature is on (RR_EINVAL, nothing written): its proof rests on a reach table that is a constant
+ * of the model and it stages the objects once per row.
+ * rr_set_attachments replaces the rows of the masked envs (env_mask u8 [N] host, NULL: every env) WHOLE:
+ *   link != NULL, rel_pose != NULL: the given poses; a quaternion is normalised on the host in float64.
+ *   link != NULL, rel_pose == NULL: CAPTURE -- one small kernel on the library's stream, behind whatever was enqueued, writes
+ *     rel = T_link(q_present)^-1 o T_object(present) for the attached objects of the masked envs with the step's forward kinematics:
+ *     "attach what the gripper holds right now" without a host round trip for the poses.
+ *   link == NULL: the masked envs' objects are detached.  link == NULL and env_mask == NULL turns the feature OFF: the three queries
+ *     launch exactly the kernels they launched before this entry point existed, as on a handle that never attached.
+ * The device table holds {moving body, rotation, translation in that body's frame}; the host converts from and to the link's COM
+ * frame in float64 through the model's link table, so rr_get_attachments returns a pose that differs from the one given by float32
+ * rounding (and possibly by the quaternion's sign).  The call waits for the stream: its arguments are host memory.
+ * PERSISTENT: rr_reset, an episode's auto-reset, rr_write_state, rr_set_state, steps and rr_set_distance_pairs keep the table;
+ * rr_copy_envs leaves it with the DESTINATION env, like every other setting; checkpoints and snapshots do not carry it.
+ * Errors: RR_EINVAL with a message naming env and object, and NOTHING changed, for a link outside [0, 17) that is not -1, a link that
+ * is rigid with the world, a non-finite rel pose or a quaternion of norm zero in a masked row; RR_EINVAL for a null env and for rel_pose
+ * without link; RR_EDEVICE for a failed allocation (all or nothing through the handle's memory owner; the table, N x 192 bytes,
+ * zero-filled, and its staging block on first use) or a device error.  Detaching on a handle that never attached is RR_OK with
+ * nothing allocated.
+ * Out of scope: swept clearance with carried objects; a device-resident table or mask and a zero-copy view of the table; carried
+ * poses as an output of rr_posture_kinematics (compose link_pose o rel in torch); gradients with respect to rel; any constraint in
+ * the step. */
+int rr_set_attachments(rr_env *env, const int32_t *link /* i32 [N][n_obj] host, or NULL: detach */,
+                       const float *rel_pose /* f32 [N][n_obj][7] host, or NULL: capture from the present state */,
+                       const uint8_t *env_mask /* u8 [N] host or NULL: every env */);
+/* The table in force: link_out i32 [N][n_obj] (-1: free), rel_pose_out f32 [N][n_obj][7] (the identity for a free object); either
+ * may be NULL.  Synchronising when rel_pose_out is given. */
+int rr_get_attachments(rr_env *env, int32_t *link_out /* [N][n_obj] */, float *rel_pose_out /* [N][n_obj][7] */);
 
 /* Batched damped-least-squares inverse kinematics for link 7 (gripper `base`), seeded with each env's current joints.
  * Replaces pybullet.calculateInverseKinematics(0, 7, pos, orn, maxNumIterations=1000, residualThreshold=0.001) in

@@ -949,7 +949,8 @@ class BatchedREALRobotEnv:
 
     def posture_clearance(self, postures, host=False):
         """The clearance of K candidate joint postures per env (rr_posture_clearance): one launch on the library's stream evaluates
-        posture (e, k) as if env e's joints q[11] were postures[e, k] -- the objects stay where they are now -- against the pairs
+        posture (e, k) as if env e's joints q[11] were postures[e, k] -- the objects stay where they are now, unless attached to a link
+        (`attach_objects`) -- against the pairs
         of `set_distance_pairs`, and reduces to the NEAREST pair on the device.  The simulation is not touched: no state write, the
         next step stays prepared.  postures: float32 [N, K, 11], 1 <= K <= 32, C-contiguous, the eleven independent joints (a
         nine-entry command maps through `_native.Q_FROM_CMD`) -- a numpy array (staged, synchronous) or a CUDA torch tensor /
@@ -1075,7 +1076,8 @@ class BatchedREALRobotEnv:
     def signed_distance_gradient(self, postures=None, margin=0.0, host=False):
         """`signed_distance` plus its derivatives over the eleven joints (rr_signed_gradient), for trajectory optimisers: one
         launch on the library's stream at the present state (postures None) or at K candidate postures per env, the objects where
-        they are now; the simulation is not touched.  The arguments are `signed_distance`'s; margin (m, finite, >= 0; with a cull in
+        they are now (an object attached to a link, `attach_objects`, moves with it and takes its joint columns); the simulation is
+        not touched.  The arguments are `signed_distance`'s; margin (m, finite, >= 0; with a cull in
         force at most the table's max_distance) is the distance below which a pair costs.  Returns `signed_distance`'s dict (the
         same bytes in the same buffers) and, with a leading [N, K] (postures) or [N] (present state),
           gradient float32 [..., 11] -- d(distance)/dq of the DEEPEST pair: n . (a_k x (a - p_k)) over the joints that move shape a's
@@ -1176,6 +1178,141 @@ class BatchedREALRobotEnv:
         col = self.ray_column
         return dict(fraction=col(stop, 0), q_stop=cut(stop, 1, 11), status=col(ids, 0), pair=col(ids, 1), steps=col(ids, 2), evaluations=col(ids, 3),
                     distance=col(hit, 0), lower=col(hit, 1), point_a=cut(hit, 2, 3), point_b=cut(hit, 5, 3), normal=cut(hit, 8, 3), pair_free_until=free)
+
+    # ------------------------------------------------------------------ carried objects: objects attached to links
+    @staticmethod
+    def _link_id(l):
+        """A link of `_native.LINK_NAMES` by name or index -> its index; -1 (free) passes through."""
+        if isinstance(l, str):
+            if l not in nat.LINK_NAMES:
+                raise ValueError("unknown link %r (known: %s)" % (l, ', '.join(nat.LINK_NAMES)))
+            return nat.LINK_NAMES.index(l)
+        if not isinstance(l, (int, np.integer)) or isinstance(l, (bool, np.bool_)):
+            raise ValueError("a link is a name of LINK_NAMES or an index, not %r" % (l,))
+        if not -1 <= int(l) < len(nat.LINK_NAMES):
+            raise ValueError("link index %d is neither -1 (free) nor in [0, %d)" % (int(l), len(nat.LINK_NAMES)))
+        return int(l)
+
+    @classmethod
+    def _attach_args(cls, N, n_objects, links, rel_pose=None):
+        """(links, rel_pose) of `attach_objects` -> (int32 [N, n_objects], float32 [N, n_objects, 7] or None); every argument error
+        that needs no handle is a ValueError raised here, before the native call."""
+        shape = (int(N), int(n_objects))
+        if isinstance(links, dict):
+            arr = np.full(shape, -1, np.int32)
+            for key, l in links.items():
+                if isinstance(key, str):
+                    if key not in OBJECT_NAMES[:shape[1]]:
+                        raise ValueError("unknown object %r (this env has: %s)" % (key, ', '.join(OBJECT_NAMES[:shape[1]])))
+                    key = OBJECT_NAMES.index(key)
+                elif not isinstance(key, (int, np.integer)) or isinstance(key, (bool, np.bool_)) or not 0 <= int(key) < shape[1]:
+                    raise ValueError("an object is a name or an index in [0, %d), not %r" % (shape[1], key))
+                arr[:, int(key)] = cls._link_id(l)
+        else:
+            a = np.asarray(links)
+            if a.dtype.kind not in 'iu':
+                raise ValueError("links is an integer array broadcastable to %s or a dict {object: link}, not dtype %s" % (shape, a.dtype))
+            try:
+                arr = np.ascontiguousarray(np.broadcast_to(a, shape)).astype(np.int32)
+            except ValueError:
+                raise ValueError("links: cannot broadcast an array of shape %s to %s" % (a.shape, shape))
+            if ((arr < -1) | (arr >= len(nat.LINK_NAMES))).any():
+                raise ValueError("links: an entry is neither -1 (free) nor in [0, %d)" % len(nat.LINK_NAMES))
+        rel = None
+        if rel_pose is not None:
+            rel = _float32_arg(rel_pose, 'rel_pose', shape + (7,))
+        return np.ascontiguousarray(arr), rel
+
+    def attach_objects(self, links, rel_pose=None, env_mask=None):
+        """Declares objects rigid with robot links for the posture queries (rr_set_attachments): what planners call attached or
+        carried bodies.  While any attachment is set, `posture_clearance`, `signed_distance` and `signed_distance_gradient` place an
+        attached object where its link's forward kinematics puts it at each candidate posture -- link_pose(posture) o rel_pose --
+        instead of where the state says, and the gradient gives its shapes the joint columns of that link; free objects, envs
+        without attachments and every pair without a carried shape keep their bits.  A query-side setting: no step reads it, and
+        it is not a constraint of the simulation.  `swept_clearance` refuses while it is on; `closest_points` is unaffected.
+        links: int [N, n_objects] (broadcastable; a link index of `_native.LINK_NAMES`, -1: free) or a dict {object name or index:
+        link name or index} applied to every env, objects not named free.  rel_pose: float32 [N, n_objects, 7] (broadcastable), xyz +
+        xyzw, the object's pose in the link's COM frame (`link_poses()`' frame: link_pose^-1 o object pose); None: CAPTURED on the
+        device from the present state -- attach what the gripper holds right now.  The rows of the masked envs (env_mask, None: all)
+        are replaced whole.  Persistent: resets, `write_state`, steps, forks and `set_distance_pairs` keep it; checkpoints and
+        snapshots do not carry it."""
+        arr, rel = self._attach_args(self.N, self.n_objects, links, rel_pose)
+        m, mp = _env_mask(env_mask, self.N)
+        nat.check(self.L.rr_set_attachments(self.h, arr.ctypes.data, None if rel is None else rel.ctypes.data, mp))
+
+    def detach_objects(self, env_mask=None):
+        """Frees every object of the masked envs (rr_set_attachments with no links).  Without a mask the feature goes off: the queries
+        launch the kernels of a handle that never attached, and `swept_clearance` works again."""
+        m, mp = _env_mask(env_mask, self.N)
+        nat.check(self.L.rr_set_attachments(self.h, None, None, mp))
+
+    def attachments(self):
+        """(links int32 [N, n_objects], rel_pose float32 [N, n_objects, 7]) in force (rr_get_attachments): -1 and the identity pose for
+        a free object.  A pose given to `attach_objects` comes back to float32 rounding (the sign of its quaternion is free); a
+        captured one is what the device composes."""
+        links = np.zeros((self.N, self.n_objects), np.int32)
+        rel = np.zeros((self.N, self.n_objects, 7), np.float32)
+        nat.check(self.L.rr_get_attachments(self.h, links.ctypes.data, rel.ctypes.data))
+        return links, rel
+
+    @classmethod
+    def carry_pairs(cls, objects, exclude_links=(), n_objects=3):
+        """A pair list for `set_distance_pairs` around carried objects (pure host code).  Each named object (name or index) is paired
+        with every static shape, every other object and every robot shape except those of `exclude_links` (names or indices of
+        `_native.LINK_NAMES`: the links that hold the object touch it by design and would own every row's minimum); behind them the
+        robot's own pairs of the step's collision table, in its order: every robot shape against table and shelf and against the
+        objects that are not named.  Returns int32 [Q, 2] shape indices, the carried object first in its pairs."""
+        shapes = cls.collision_shapes()
+        if isinstance(objects, (str, int, np.integer)):
+            objects = [objects]
+        named = []
+        for o in objects:
+            if isinstance(o, str):
+                if o not in OBJECT_NAMES[:n_objects]:
+                    raise ValueError("unknown object %r (this env has: %s)" % (o, ', '.join(OBJECT_NAMES[:n_objects])))
+                o = OBJECT_NAMES.index(o)
+            elif not isinstance(o, (int, np.integer)) or isinstance(o, (bool, np.bool_)) or not 0 <= int(o) < n_objects:
+                raise ValueError("an object is a name or an index in [0, %d), not %r" % (n_objects, o))
+            if int(o) not in named:
+                named.append(int(o))
+        if isinstance(exclude_links, (str, int, np.integer)):
+            exclude_links = [exclude_links]
+        excluded = set()
+        for l in exclude_links:
+            l = cls._link_id(l)
+            if l < 0:
+                raise ValueError("exclude_links names links, not -1")
+            excluded.add(l)
+        statics = [r['index'] for r in shapes if r['body'] < 0]
+        scenery = [r['index'] for r in shapes if r['body'] < 0 and r['link'] < 0]
+        robot = [r['index'] for r in shapes if 0 <= r['body'] < 16]
+        obj_shape = {r['body'] - 16: r['index'] for r in shapes if 16 <= r['body'] < 16 + n_objects}
+        pairs, seen = [], set()
+
+        def put(a, b):
+            if (a, b) not in seen and (b, a) not in seen:
+                seen.add((a, b))
+                pairs.append((a, b))
+        for o in named:
+            s = obj_shape[o]
+            for t in statics:
+                put(s, t)
+            for p in sorted(obj_shape):
+                if p != o:
+                    put(s, obj_shape[p])
+            for r in robot:
+                if shapes[r]['link'] not in excluded:
+                    put(s, r)
+        others = [obj_shape[p] for p in sorted(obj_shape) if p not in named]
+        for r in robot:
+            for t in scenery:
+                put(r, t)
+        for r in robot:
+            for s in others:
+                put(r, s)
+        if len(pairs) > nat.DIST_MAX:
+            raise ValueError("%d pairs: at most %d are allowed" % (len(pairs), nat.DIST_MAX))
+        return np.array(pairs, np.int32).reshape(-1, 2)
 
     # ------------------------------------------------------------------ kinematics at candidate postures
     def posture_kinematics_buffer(self, name, host=False):

@@ -157,7 +157,15 @@ struct rr_env : ModelTables {
     float *xw_table = nullptr;
     float *xw_stage = nullptr;
     bool xw_on = false;
-    MemOwner mem;                  // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
+    // objects attached to robot links in the posture queries (rr_set_attachments): the table [N][NOBJ][ATT_ROW] (rr_carry.inc), allocated
+    // zero-filled -- all free -- on first use with its staging block; att_link [N][nobj]: the host copy of the link ids, -1 free (empty until
+    // the first set); att_on: the three posture queries launch their carry variants (from the first successful set with links until the
+    // unmasked detach).  No step reads any of it.
+    float *att_table = nullptr;
+    float *att_stage = nullptr;
+    std::vector<int32_t> att_link;
+    bool att_on = false;
+    MemOwner mem;                 // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
     bool created = false;
     bool timing = false;
     int *h_hcount = nullptr;       // pinned host copy of D.hcount[0] (device-mapped: written by the first solve launch of every step, solve_body)
@@ -1731,8 +1739,12 @@ int rr_posture_clearance(rr_env *e, const float *postures, int32_t n_postures, i
     const float *src = postures;
     RRCHK(st.in(src, e->pc_stage, (size_t)N * K * 44));
     void *const *b = e->qbuf[QF_PC];
-    hipLaunchKernelGGL(k_posture_clearance, dim3((unsigned)N * K), dim3(PC_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
-                       (float4 *)b[RR_PC_NEAREST], (int4 *)b[RR_PC_ID], (float *)b[RR_PC_DISTANCE], (int *)b[RR_PC_STATUS]);
+    if (e->att_on)      // objects are attached to links (rr_set_attachments): the carry variant of rr_carry.inc, the same buffers
+        hipLaunchKernelGGL(k_posture_clearance_carry, dim3((unsigned)N * K), dim3(PC_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
+                           (float4 *)b[RR_PC_NEAREST], (int4 *)b[RR_PC_ID], (float *)b[RR_PC_DISTANCE], (int *)b[RR_PC_STATUS], (const float *)e->att_table);
+    else
+        hipLaunchKernelGGL(k_posture_clearance, dim3((unsigned)N * K), dim3(PC_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
+                           (float4 *)b[RR_PC_NEAREST], (int4 *)b[RR_PC_ID], (float *)b[RR_PC_DISTANCE], (int *)b[RR_PC_STATUS]);
     HIPCHK(hipGetLastError());
     e->qk[QF_PC] = K;
     return st.wait();
@@ -1762,9 +1774,14 @@ int rr_signed_distance(rr_env *e, const float *postures, int32_t n_postures, int
     const float *src = postures;
     RRCHK(st.in(src, e->pc_stage, (size_t)N * K * 44));
     void *const *b = e->qbuf[QF_SD];
-    hipLaunchKernelGGL(k_signed_distance, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
-                       (float4 *)b[RR_SD_DEEPEST], (int4 *)b[RR_SD_ID], (float *)b[RR_SD_SIGNED], (int *)b[RR_SD_STATUS],
-                       postures ? (float4 *)nullptr : (float4 *)b[RR_SD_POINTS]);
+    if (e->att_on)      // objects are attached to links (rr_set_attachments): the carry variant of rr_carry.inc, the same buffers
+        hipLaunchKernelGGL(k_signed_distance_carry, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
+                           (float4 *)b[RR_SD_DEEPEST], (int4 *)b[RR_SD_ID], (float *)b[RR_SD_SIGNED], (int *)b[RR_SD_STATUS],
+                           postures ? (float4 *)nullptr : (float4 *)b[RR_SD_POINTS], (const float *)e->att_table);
+    else
+        hipLaunchKernelGGL(k_signed_distance, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
+                           (float4 *)b[RR_SD_DEEPEST], (int4 *)b[RR_SD_ID], (float *)b[RR_SD_SIGNED], (int *)b[RR_SD_STATUS],
+                           postures ? (float4 *)nullptr : (float4 *)b[RR_SD_POINTS]);
     HIPCHK(hipGetLastError());
     e->qk[QF_SD] = K;
     return st.wait();
@@ -1799,10 +1816,17 @@ int rr_signed_gradient(rr_env *e, const float *postures, int32_t n_postures, int
     const float *src = postures;
     RRCHK(st.in(src, e->pc_stage, (size_t)N * K * 44));
     void *const *b = e->qbuf[QF_SD], *const *g = e->qbuf[QF_SG];
-    hipLaunchKernelGGL(k_signed_gradient, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
-                       (float4 *)b[RR_SD_DEEPEST], (int4 *)b[RR_SD_ID], (float *)b[RR_SD_SIGNED], (int *)b[RR_SD_STATUS],
-                       postures ? (float4 *)nullptr : (float4 *)b[RR_SD_POINTS], margin,
-                       (float *)g[RR_SG_GRADIENT], (float *)g[RR_SG_COST], postures ? (float *)nullptr : (float *)g[RR_SG_PAIR_GRADIENT]);
+    if (e->att_on)      // objects are attached to links (rr_set_attachments): the carry variant of rr_carry.inc, the same buffers
+        hipLaunchKernelGGL(k_signed_gradient_carry, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
+                           (float4 *)b[RR_SD_DEEPEST], (int4 *)b[RR_SD_ID], (float *)b[RR_SD_SIGNED], (int *)b[RR_SD_STATUS],
+                           postures ? (float4 *)nullptr : (float4 *)b[RR_SD_POINTS], margin,
+                           (float *)g[RR_SG_GRADIENT], (float *)g[RR_SG_COST], postures ? (float *)nullptr : (float *)g[RR_SG_PAIR_GRADIENT],
+                           (const float *)e->att_table);
+    else
+        hipLaunchKernelGGL(k_signed_gradient, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
+                           (float4 *)b[RR_SD_DEEPEST], (int4 *)b[RR_SD_ID], (float *)b[RR_SD_SIGNED], (int *)b[RR_SD_STATUS],
+                           postures ? (float4 *)nullptr : (float4 *)b[RR_SD_POINTS], margin,
+                           (float *)g[RR_SG_GRADIENT], (float *)g[RR_SG_COST], postures ? (float *)nullptr : (float *)g[RR_SG_PAIR_GRADIENT]);
     HIPCHK(hipGetLastError());
     e->qk[QF_SD] = e->qk[QF_SG] = K;
     return st.wait();
@@ -1831,6 +1855,9 @@ int rr_swept_clearance(rr_env *e, const float *segments, int32_t n_segments, int
     if (maxd > 0.0f && maxd < INFINITY && maxd < safety + tolerance)
         return fail(RR_EINVAL, "rr_swept_clearance: the cull's max_distance " + std::to_string(maxd) + " is below safety + tolerance = " +
                                    std::to_string(safety + tolerance) + ": a culled pair's sphere gap could fake a hit");
+    if (e->att_on)      // the proof's reach table is a constant of the model and the objects are staged once per row: a carried object would be swept past
+        return fail(RR_EINVAL, "rr_swept_clearance: objects are attached to links (rr_set_attachments): the sweep does not move carried objects; "
+                               "detach them (rr_set_attachments with link NULL and no mask) or use rr_posture_clearance / rr_signed_distance at sampled postures");
     RRCHK(ensure_query(e, QF_DIST, "rr_swept_clearance"));       // (the device copy of the pair table)
     RRCHK(ensure_query(e, QF_SW, "rr_swept_clearance", {stage_part(&e->sw_stage, (size_t)N * RR_PC_MAX_POSTURES * 88, !on_device)}));
     HIPCHK(hipSetDevice(e->cfg.device));
@@ -1854,6 +1881,127 @@ int rr_sweep_reach(rr_env *e, float *out) {
 
 int rr_sweep_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) { return query_buffer(query_view(e, QF_SW), HIP_QUERY, which, dev_ptr, bytes); }
 int rr_sweep_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) { return query_copy_to_host(query_view(e, QF_SW), HIP_QUERY, which, dst, bytes); }
+
+// ---- objects attached to robot links in the posture queries (rr_carry.inc) ---------------------------------------------------------------
+// The table [N][NOBJ][ATT_ROW] and its staging block: on first use, all or nothing, the table zero-filled (every object free).
+static int ensure_attachments(rr_env *e, const char *who) {
+    const size_t bytes = (size_t)e->P.N * NOBJ * ATT_ROW * 4;
+    return ensure_group(e, -1, who, "the attachment table", {mem_part(&e->att_table, bytes), stage_part(&e->att_stage, bytes)});
+}
+
+// The caller speaks of a URDF link's COM frame, the device table of the moving body b the link hangs on: with (L, l) = link_rot, link_pos
+// of the link, T_body<-object = (L, l) o rel.  Both directions in float64; the quaternion of a row read back is the largest-of-four-squares
+// root of its matrix, normalised (a captured matrix is orthonormal to float32 rounding only).
+static void att_to_body(const RenderModel &RM, int l, const double *rel7, float *row) {
+    const double x = rel7[3], y = rel7[4], z = rel7[5], w = rel7[6];
+    const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w), 2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                         2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
+    const float *L = RM.link_rot[l], *lp = RM.link_pos[l];
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) row[3 * i + j] = (float)((double)L[3 * i] * R[j] + (double)L[3 * i + 1] * R[3 + j] + (double)L[3 * i + 2] * R[6 + j]);
+        row[9 + i] = (float)((double)lp[i] + (double)L[3 * i] * rel7[0] + (double)L[3 * i + 1] * rel7[1] + (double)L[3 * i + 2] * rel7[2]);
+    }
+}
+static void att_from_body(const RenderModel &RM, int l, const float *row, float *rel7) {
+    const float *L = RM.link_rot[l], *lp = RM.link_pos[l];
+    double R[9], t[3];
+    for (int i = 0; i < 3; i++) {      // L^T R_rel, L^T (t_rel - l)
+        for (int j = 0; j < 3; j++) R[3 * i + j] = (double)L[i] * row[j] + (double)L[3 + i] * row[3 + j] + (double)L[6 + i] * row[6 + j];
+        t[i] = (double)L[i] * ((double)row[9] - lp[0]) + (double)L[3 + i] * ((double)row[10] - lp[1]) + (double)L[6 + i] * ((double)row[11] - lp[2]);
+    }
+    const double sq[4] = {1 + R[0] - R[4] - R[8], 1 - R[0] + R[4] - R[8], 1 - R[0] - R[4] + R[8], 1 + R[0] + R[4] + R[8]};    // 4 x^2, 4 y^2, 4 z^2, 4 w^2
+    int big = 0;
+    for (int a = 1; a < 4; a++) if (sq[a] > sq[big]) big = a;
+    const double r = std::sqrt(std::max(sq[big], 0.0)) * 0.5, s = 0.25 / (r > 0 ? r : 1.0);
+    double q[4];
+    if (big == 0) { q[0] = r; q[1] = (R[1] + R[3]) * s; q[2] = (R[2] + R[6]) * s; q[3] = (R[7] - R[5]) * s; }
+    else if (big == 1) { q[0] = (R[1] + R[3]) * s; q[1] = r; q[2] = (R[5] + R[7]) * s; q[3] = (R[2] - R[6]) * s; }
+    else if (big == 2) { q[0] = (R[2] + R[6]) * s; q[1] = (R[5] + R[7]) * s; q[2] = r; q[3] = (R[3] - R[1]) * s; }
+    else { q[0] = (R[7] - R[5]) * s; q[1] = (R[2] - R[6]) * s; q[2] = (R[3] - R[1]) * s; q[3] = r; }
+    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    for (int i = 0; i < 3; i++) rel7[i] = (float)t[i];
+    for (int i = 0; i < 4; i++) rel7[3 + i] = (float)(n > 0 ? q[i] / n : (i == 3 ? 1.0 : 0.0));
+}
+
+// The rows of the masked envs, replaced whole, on the main stream behind every query enqueued before (which read the table on this
+// stream).  With link and no rel_pose, k_attach_capture fills the poses from the present state behind whatever was enqueued -- no wait
+// for the poses.  Everything is validated before anything changes.  A query-side setting: the state, the preparation record and
+// la_valid are not touched, and no step reads the table.
+int rr_set_attachments(rr_env *e, const int32_t *link, const float *rel_pose, const uint8_t *env_mask) {
+    if (!e) return fail(RR_EINVAL, "rr_set_attachments: null env");
+    if (!link && rel_pose) return fail(RR_EINVAL, "rr_set_attachments: rel_pose without link (link NULL detaches)");
+    const int N = e->P.N, nobj = e->P.nobj;
+    std::vector<float> rows((size_t)N * NOBJ * ATT_ROW, 0.0f);
+    if (link) {
+        RRCHK(check_link_table(e, "rr_set_attachments", RR_EINVAL));
+        for (int i = 0; i < N; i++) {
+            if (env_mask && !env_mask[i]) continue;
+            for (int o = 0; o < nobj; o++) {
+                const int l = link[(size_t)i * nobj + o];
+                if (l == -1) continue;
+                const std::string which = "rr_set_attachments: env " + std::to_string(i) + ", object " + std::to_string(o) + ": ";
+                if (l < 0 || l >= KIN_LINKS) return fail(RR_EINVAL, which + "link " + std::to_string(l) + " is neither -1 (free) nor in [0, " + std::to_string(KIN_LINKS) + ")");
+                if (e->RM.link_body[l] < 0) return fail(RR_EINVAL, which + "link " + std::to_string(l) + " is rigid with the world: nothing carries the object");
+                float *row = &rows[((size_t)i * NOBJ + o) * ATT_ROW];
+                const int att = e->RM.link_body[l] + 1;
+                memcpy(row + ATT_BODY, &att, 4);
+                if (!rel_pose) continue;      // k_attach_capture writes the pose
+                double r[7], n2 = 0.0;
+                for (int k = 0; k < 7; k++) {
+                    r[k] = rel_pose[((size_t)i * nobj + o) * 7 + k];
+                    if (!std::isfinite(r[k])) return fail(RR_EINVAL, which + "the rel pose is not finite");
+                }
+                for (int k = 3; k < 7; k++) n2 += r[k] * r[k];
+                if (!(n2 > 0.0)) return fail(RR_EINVAL, which + "the rel pose's quaternion has norm zero");
+                for (int k = 3; k < 7; k++) r[k] /= std::sqrt(n2);
+                att_to_body(e->RM, l, r, row);
+            }
+        }
+    }
+    if (!link && !e->att_table) return RR_OK;      // detaching in a table that does not exist yet: every object is free, the feature off
+    RRCHK(ensure_attachments(e, "rr_set_attachments"));
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const unsigned char *m = nullptr;
+    HIPCHK(hipMemcpyAsync(e->att_stage, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, e->stream));
+    if (env_mask) { HIPCHK(hipMemcpyAsync(e->mask_dev, env_mask, N, hipMemcpyHostToDevice, e->stream)); m = e->mask_dev; }
+    hipLaunchKernelGGL(k_attach_set, dim3((unsigned)((N * NOBJ * ATT_ROW + 255) / 256)), dim3(256), 0, e->stream, N, (const float *)e->att_stage, m, e->att_table);
+    HIPCHK(hipGetLastError());
+    if (link && !rel_pose) {
+        hipLaunchKernelGGL(k_attach_capture, dim3((unsigned)N), dim3(64), 0, e->stream, e->B, e->P, e->D, m, e->att_table);
+        HIPCHK(hipGetLastError());
+    }
+    if (e->att_link.empty()) e->att_link.assign((size_t)N * nobj, -1);
+    for (int i = 0; i < N; i++) {
+        if (env_mask && !env_mask[i]) continue;
+        for (int o = 0; o < nobj; o++) e->att_link[(size_t)i * nobj + o] = link ? link[(size_t)i * nobj + o] : -1;
+    }
+    if (link) e->att_on = true;
+    else if (!env_mask) e->att_on = false;      // the unmasked detach: the queries launch their original kernels until the next attach
+    HIPCHK(hipStreamSynchronize(e->stream));    // the arguments and the staged rows are host memory
+    return RR_OK;
+}
+
+int rr_get_attachments(rr_env *e, int32_t *link_out, float *rel_pose_out) {
+    if (!e) return fail(RR_EINVAL, "rr_get_attachments: null env");
+    const int N = e->P.N, nobj = e->P.nobj;
+    for (size_t i = 0; link_out && i < (size_t)N * nobj; i++) link_out[i] = e->att_link.empty() ? -1 : e->att_link[i];
+    if (!rel_pose_out) return RR_OK;
+    std::vector<float> rows;
+    if (e->att_table) {
+        rows.resize((size_t)N * NOBJ * ATT_ROW);
+        HIPCHK(hipSetDevice(e->cfg.device));
+        HIPCHK(hipMemcpyAsync(rows.data(), e->att_table, rows.size() * 4, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    for (int i = 0; i < N; i++)
+        for (int o = 0; o < nobj; o++) {
+            float *out = rel_pose_out + ((size_t)i * nobj + o) * 7;
+            const int l = e->att_link.empty() ? -1 : e->att_link[(size_t)i * nobj + o];
+            if (l < 0 || rows.empty()) { for (int k = 0; k < 7; k++) out[k] = k == 6 ? 1.0f : 0.0f; continue; }      // free: the identity
+            att_from_body(e->RM, l, &rows[((size_t)i * NOBJ + o) * ATT_ROW], out);
+        }
+    return RR_OK;
+}
 
 // ---- kinematics at candidate postures (rr_pkin.inc) -------------------------------------------------------------------------------------
 // Link poses, point positions and Jacobians at K candidate postures per env, on the device.  On the main stream like
