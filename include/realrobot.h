@@ -47,7 +47,8 @@ extern "C" {
                               deepest pair's signed distance and of a hinge collision cost, reduced on the device);
                               rr_swept_clearance, rr_sweep_reach, rr_sweep_buffer, rr_sweep_copy_to_host (first contact of the pair
                               table along joint-space segments, by conservative advancement); rr_set_attachments,
-                              rr_get_attachments (objects attached to robot links in the posture queries) */
+                              rr_get_attachments (objects attached to robot links in the posture queries); rr_carried_sweep (the
+                              swept clearance with those objects moving) */
 
 enum {
     RR_OK = 0,
@@ -1282,7 +1283,7 @@ int rr_external_wrench_buffer(rr_env *env, void **dev_ptr, size_t *bytes);
  * enters has the bits it has with the feature off.  The same buffers with the same layouts are written; body_a / body_b keep reporting
  * 16 + o for an object, attached or not.  rr_closest_points is unaffected (at the present state an object is where the state says).
  * rr_swept_clearance REFUSES while the feature is on (RR_EINVAL, nothing written): its proof rests on a reach table that is a constant
- * of the model and it stages the objects once per row.
+ * of the model and it stages the objects once per row.  rr_carried_sweep, below, is the edge check that moves them.
  * rr_set_attachments replaces the rows of the masked envs (env_mask u8 [N] host, NULL: every env) WHOLE:
  *   link != NULL, rel_pose != NULL: the given poses; a quaternion is normalised on the host in float64.
  *   link != NULL, rel_pose == NULL: CAPTURE -- one small kernel on the library's stream, behind whatever was enqueued, writes
@@ -1300,7 +1301,7 @@ int rr_external_wrench_buffer(rr_env *env, void **dev_ptr, size_t *bytes);
  * without link; RR_EDEVICE for a failed allocation (all or nothing through the handle's memory owner; the table, N x 192 bytes,
  * zero-filled, and its staging block on first use) or a device error.  Detaching on a handle that never attached is RR_OK with
  * nothing allocated.
- * Out of scope: swept clearance with carried objects; a device-resident table or mask and a zero-copy view of the table; carried
+ * Out of scope: a device-resident table or mask and a zero-copy view of the table; carried
  * poses as an output of rr_posture_kinematics (compose link_pose o rel in torch); gradients with respect to rel; any constraint in
  * the step. */
 int rr_set_attachments(rr_env *env, const int32_t *link /* i32 [N][n_obj] host, or NULL: detach */,
@@ -1309,6 +1310,49 @@ int rr_set_attachments(rr_env *env, const int32_t *link /* i32 [N][n_obj] host, 
 /* The table in force: link_out i32 [N][n_obj] (-1: free), rel_pose_out f32 [N][n_obj][7] (the identity for a free object); either
  * may be NULL.  Synchronising when rel_pose_out is given. */
 int rr_get_attachments(rr_env *env, int32_t *link_out /* [N][n_obj] */, float *rel_pose_out /* [N][n_obj][7] */);
+
+/* Swept clearance with carried objects: the attached-body edge check (additive in ABI 7; k_carried_sweep: csrc/rr_csweep.inc).
+ * rr_swept_clearance proves an edge free for the empty hand; the transport half of a pick-and-place plan moves an object through the
+ * same shelf.  rr_carried_sweep is rr_swept_clearance -- its arguments, its validation and refusals (under this call's name), its host
+ * staging and STREAM CONTRACT, its four RR_SW_* buffers in the same layouts, read through rr_sweep_buffer and rr_sweep_copy_to_host:
+ * NO new buffer family -- with ONE difference: it does not refuse while attachments are on.
+ * Attachments OFF (a handle that never attached, or after the unmasked detach): the call forwards to rr_swept_clearance -- the same
+ * kernel, the same bytes.  A planner can always call this one function.
+ * Attachments ON: one launch of k_carried_sweep on the library's stream, one wave64 per (env, segment) like the original.
+ * The motion model.  q(t) = q0 + t (q1 - q0), t in [0, 1].  An ATTACHED object of env e moves with its link: at every posture the
+ * advancement evaluates it is re-staged as R_o = R_b R_rel, p_o = p_b + R_b t_rel from that posture's forward kinematics and the
+ * env's table row, by the device function rr_posture_clearance uses while attachments are on.  A FREE object stays at env e's present pose.
+ * The carried reach.  A shape s of an object attached to moving body b takes the joint mask "ancestors-or-self of b".  For a joint k
+ * of that mask its reach is chain[k][b] + rho: chain[k][b] is the sum of |body_jpos[m]| over the bodies m on the chain from b up
+ * to, but not including, k -- the term of the reach table, built once on the host in float64 and rounded UP to float32, an 11 x 11
+ * table allocated on first use through the handle's memory owner, all or nothing --, and rho = |t_rel + R_rel c_s| + ||R_rel|| r_s
+ * with (c_s, r_s) the bounding sphere of s in the object's frame.  rho is computed per row on the device from the table row (a
+ * captured row never visits the host), with ||R_rel|| MEASURED from the row (a captured rotation is orthonormal to float32 rounding
+ * only), an absolute term for a cancelling t_rel + R_rel c_s, and the factor 1 + 2^-18: float32 rounding cannot lower it
+ * (csrc/rr_csweep.inc derives the factor).  Robot shapes keep R[k][s] of rr_sweep_reach.
+ * The pair bound.  B_j as rr_swept_clearance defines it, over the joints in exactly one of the two masks, ascending k in float32,
+ * times 1 + 2^-20: the distance of pair j is B_j-Lipschitz in t with the carried objects moving.  A carried shape against a shape on
+ * its own body, and two objects carried by one body, have B_j = 0: one look, horizon +inf.  Two objects on different bodies work
+ * through the exclusive-or of their masks.  The advancement, the statuses, `steps` and `pair evaluations` are the original's.
+ * Guarantees.  Those of rr_swept_clearance with "the distance of pair j along the motion" read with the carried objects moving: for
+ * every pair j and every t < min(free_j, 1) it exceeds safety, for every t < fraction every pair's does.  The RR_SW_HIT record of a
+ * stopped row is, bit for bit, what rr_posture_clearance returns for that pair at q_stop on the same attached handle.  An env with
+ * no attachment on an attached handle gets, in every row, the bytes rr_swept_clearance writes on a handle that never attached.  No
+ * atomics and a fixed order: row (e, k) is a function of (env e's objects, env e's table rows, segment (e, k), the tables, safety,
+ * tolerance) alone.  The table's body index is clamped before it indexes anything; no other value of the table, the tensor or the
+ * state forms an address.  At most RR_SW_MAX_STEPS postures are evaluated whatever the data, a non-finite segment or table row
+ * included: such a row leaves the loop within the cap, its outputs unspecified, with status in {0, 1, 3}.
+ * Reads what rr_swept_clearance reads, and the attachment table and the chain table; writes the four RR_SW_* buffers only: not the
+ * state, the preparation record, la_valid, an error flag or a buffer of another query.  The next step stays prepared.
+ * Errors: RR_EINVAL with nothing allocated, nothing written and nothing changed for every cause of rr_swept_clearance's list -- a null
+ * env, null segments, n_segments outside [1, RR_PC_MAX_POSTURES], Q == 0, safety < 0 or NaN or infinite, tolerance < 1e-6 or NaN or
+ * infinite, a cull's max_distance below safety + tolerance --, the message naming rr_carried_sweep; RR_EDEVICE for a failed allocation
+ * or a device error.  The pair table's device copy, the four buffers with their staging block and the chain table are three groups,
+ * each all or nothing on its own: a chain table that cannot be allocated leaves the buffers allocated, zero-filled and unwritten.
+ * Out of scope: rr_swept_clearance with attachments on (it keeps refusing: its contract is "the objects stay at the present pose");
+ * a switch of the vector env; carried poses as an output of rr_posture_kinematics; objects that move on their own during the sweep;
+ * every pair's first hit; gradients of the hit time; any use by the step. */
+int rr_carried_sweep(rr_env *env, const float *segments /* f32 [N][K][2][11] */, int32_t n_segments, int32_t on_device, float safety, float tolerance);
 
 /* Batched damped-least-squares inverse kinematics for link 7 (gripper `base`), seeded with each env's current joints.
  * Replaces pybullet.calculateInverseKinematics(0, 7, pos, orn, maxNumIterations=1000, residualThreshold=0.001) in

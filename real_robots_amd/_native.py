@@ -51,7 +51,7 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_posture_dynamics', 'rr_posture_dynamics_buffer', 'rr_posture_dynamics_copy_to_host',
            'rr_set_joint_torques', 'rr_get_joint_torques', 'rr_joint_torque_buffer',
            'rr_set_external_wrenches', 'rr_get_external_wrenches', 'rr_external_wrench_buffer',
-           'rr_set_attachments', 'rr_get_attachments')
+           'rr_set_attachments', 'rr_get_attachments', 'rr_carried_sweep')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
@@ -310,6 +310,7 @@ def load_library():
     L.rr_external_wrench_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rr_set_attachments.argtypes = [vp, vp, vp, vp]
     L.rr_get_attachments.argtypes = [vp, vp, vp]
+    L.rr_carried_sweep.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float]
     for fam in QUERY_FAMILIES.values():
         getattr(L, fam.buffer).argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
         getattr(L, fam.copy_to_host).argtypes = [vp, i32, vp, C.c_size_t]

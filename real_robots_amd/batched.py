@@ -1163,13 +1163,18 @@ class BatchedREALRobotEnv:
               pair at q_stop (all +0.0 at status 0);
           pair_free_until float32 [N, K, Q] -- for every pair the t up to which it is proved further than safety (at most 1).
         Device views (zero copy, strided, DLPack; valid after later work on the library's stream or `sync()`; they hold what the last
-        call computed), or with host=True numpy views of host copies after a sync."""
+        call computed), or with host=True numpy views of host copies after a sync.  It refuses while objects are attached
+        (`attach_objects`): `carried_sweep` is the same query with the carried objects moving."""
         K = self._segment_arg(segments, self.N)
         if len(self.distance_pairs()[0]) == 0:
             raise ValueError("swept_clearance: the pair table is empty (set_distance_pairs)")
         ptr, on_dev, keep = self._state_arg(segments, 'segments', ('float32',), (self.N, K, 2, nat.N_JOINTS))
         nat.check(self.L.rr_swept_clearance(self.h, ptr, K, on_dev, float(safety), float(tolerance)))
         del keep
+        return self._sweep_columns(K, host)
+
+    def _sweep_columns(self, K, host):
+        """The columns of `swept_clearance` and `carried_sweep` cut from the four sweep buffers as the last call left them."""
         stop, hit, ids, free = (self.sweep_buffer(i, host=host) for i in range(len(nat.SW_FIELDS)))
         if isinstance(hit, np.ndarray):
             cut = lambda buf, lo, n: buf[:, :, lo:lo + n]
@@ -1178,6 +1183,22 @@ class BatchedREALRobotEnv:
         col = self.ray_column
         return dict(fraction=col(stop, 0), q_stop=cut(stop, 1, 11), status=col(ids, 0), pair=col(ids, 1), steps=col(ids, 2), evaluations=col(ids, 3),
                     distance=col(hit, 0), lower=col(hit, 1), point_a=cut(hit, 2, 3), point_b=cut(hit, 5, 3), normal=cut(hit, 8, 3), pair_free_until=free)
+
+    def carried_sweep(self, segments, safety=0.0, tolerance=1e-3, host=False):
+        """`swept_clearance` with the carried objects moving (rr_carried_sweep): the edge check of the transport half of a plan.  An
+        object attached to a link (`attach_objects`) is re-staged with that link at every posture the advancement evaluates, and a
+        pair's motion bound takes the carrying body's joints and a per-env reach for a carried shape; free objects stay where they
+        are now.  Arguments, refusals and the returned dict of columns are `swept_clearance`'s; the buffers are `sweep_buffer`'s.
+        While nothing is attached the call IS `swept_clearance` (the same kernel, the same bytes), so a planner can always call
+        this one; an env without attachments on an attached handle gets `swept_clearance`'s bytes too.  The record of a stopped row
+        is `posture_clearance(q_stop)`'s on the same handle, bit for bit."""
+        K = self._segment_arg(segments, self.N)
+        if len(self.distance_pairs()[0]) == 0:
+            raise ValueError("carried_sweep: the pair table is empty (set_distance_pairs)")
+        ptr, on_dev, keep = self._state_arg(segments, 'segments', ('float32',), (self.N, K, 2, nat.N_JOINTS))
+        nat.check(self.L.rr_carried_sweep(self.h, ptr, K, on_dev, float(safety), float(tolerance)))
+        del keep
+        return self._sweep_columns(K, host)
 
     # ------------------------------------------------------------------ carried objects: objects attached to links
     @staticmethod
@@ -1229,7 +1250,8 @@ class BatchedREALRobotEnv:
         attached object where its link's forward kinematics puts it at each candidate posture -- link_pose(posture) o rel_pose --
         instead of where the state says, and the gradient gives its shapes the joint columns of that link; free objects, envs
         without attachments and every pair without a carried shape keep their bits.  A query-side setting: no step reads it, and
-        it is not a constraint of the simulation.  `swept_clearance` refuses while it is on; `closest_points` is unaffected.
+        it is not a constraint of the simulation.  `swept_clearance` refuses while it is on (`carried_sweep` is the edge check that moves
+        the carried objects); `closest_points` is unaffected.
         links: int [N, n_objects] (broadcastable; a link index of `_native.LINK_NAMES`, -1: free) or a dict {object name or index:
         link name or index} applied to every env, objects not named free.  rel_pose: float32 [N, n_objects, 7] (broadcastable), xyz +
         xyzw, the object's pose in the link's COM frame (`link_poses()`' frame: link_pose^-1 o object pose); None: CAPTURED on the

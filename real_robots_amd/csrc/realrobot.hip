@@ -479,6 +479,7 @@ __device__ __forceinline__ void dispatch_order_class(int x, int N, int ntiles, i
 #include "rr_signed.inc"    // k_signed_distance: every pair's signed distance -- minus the penetration depth where the hulls overlap -- and the deepest pair's record, at the present state or at K postures (rr_signed_distance)
 #include "rr_grad.inc"    // k_signed_gradient: k_signed_distance plus the joint gradients of the deepest pair's signed distance and of a hinge cost over all pairs (rr_signed_gradient)
 #include "rr_carry.inc"    // k_posture_clearance_carry / k_signed_distance_carry / k_signed_gradient_carry, k_attach_capture: the posture queries with objects attached to robot links (rr_set_attachments)
+#include "rr_csweep.inc"    // k_carried_sweep: k_swept_clearance with carried objects -- the objects re-staged at every step, a carried shape's joint mask and per-env reach (rr_carried_sweep)
 #include "rr_plan.inc"   // plan_step: the placement and launch shapes of one step from one reading of the lagged list lengths (host only, no HIP type)
 #include "rr_mem.inc"    // MemOwner: the one owner of the handle's device and pinned memory, all-or-nothing group allocation (host only, no HIP type)
 #include "rr_query.inc"    // the query families' output buffers: one layout table, one buffer / copy_to_host accessor pair (host only, no HIP type)

@@ -165,6 +165,10 @@ struct rr_env : ModelTables {
     float *att_stage = nullptr;
     std::vector<int32_t> att_link;
     bool att_on = false;
+    // the swept clearance with carried objects (rr_carried_sweep): chain[k][b], the joint offsets between joint k and body b, built and
+    // uploaded by the first call that launches k_carried_sweep (rr_csweep.inc)
+    SweepChain sw_chain = {};
+    SweepChain *sw_chain_dev = nullptr;
     MemOwner mem;                 // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
     bool created = false;
     bool timing = false;
@@ -1836,28 +1840,31 @@ int rr_signed_gradient_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *
 int rr_signed_gradient_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) { return query_copy_to_host(query_view(e, QF_SG), HIP_QUERY, which, dst, bytes); }
 
 // ---- swept clearance along joint-space segments (rr_sweep.inc) -------------------------------------------------------------------------
+// the refusals rr_swept_clearance and rr_carried_sweep share, each under the name of the entry point that was called
+static int sweep_arguments(rr_env *e, const std::string &who, const float *segments, int32_t n_segments, float safety, float tolerance) {
+    if (!segments) return fail(RR_EINVAL, who + ": null segments");
+    if (n_segments < 1 || n_segments > RR_PC_MAX_POSTURES)
+        return fail(RR_EINVAL, who + ": n_segments " + std::to_string(n_segments) + " is not in [1, RR_PC_MAX_POSTURES = " + std::to_string(RR_PC_MAX_POSTURES) + "]");
+    if (e->dist_n == 0) return fail(RR_EINVAL, who + ": the pair table is empty (rr_set_distance_pairs)");
+    if (!(safety >= 0.0f) || !std::isfinite(safety)) return fail(RR_EINVAL, who + ": safety " + std::to_string(safety) + " is not a finite number >= 0");
+    if (!(tolerance >= 1e-6f) || !std::isfinite(tolerance)) return fail(RR_EINVAL, who + ": tolerance " + std::to_string(tolerance) + " is not a finite number >= 1e-6");
+    const float maxd = e->dist_tab.max_distance;
+    if (maxd > 0.0f && maxd < INFINITY && maxd < safety + tolerance)
+        return fail(RR_EINVAL, who + ": the cull's max_distance " + std::to_string(maxd) + " is below safety + tolerance = " + std::to_string(safety + tolerance) +
+                                   ": a culled pair's sphere gap could fake a hit");
+    return RR_OK;
+}
 // Conservative advancement along K segments per env, on the device.  On the main stream like rr_posture_clearance: behind every step,
 // reset and state write enqueued before it.  Reads D.state (the objects), the model, the pair table, the reach table and the tensor;
 // writes the four buffers and nothing else -- not the state, the scratch slab of the look-ahead, la_valid, an error flag or a buffer of
 // another query.
 int rr_swept_clearance(rr_env *e, const float *segments, int32_t n_segments, int32_t on_device, float safety, float tolerance) {
     if (!e) return fail(RR_EINVAL, "rr_swept_clearance: null env");
-    if (!segments) return fail(RR_EINVAL, "rr_swept_clearance: null segments");
-    if (n_segments < 1 || n_segments > RR_PC_MAX_POSTURES)
-        return fail(RR_EINVAL, "rr_swept_clearance: n_segments " + std::to_string(n_segments) + " is not in [1, RR_PC_MAX_POSTURES = " +
-                                   std::to_string(RR_PC_MAX_POSTURES) + "]");
+    RRCHK(sweep_arguments(e, "rr_swept_clearance", segments, n_segments, safety, tolerance));
     const int Q = e->dist_n, N = e->P.N, K = n_segments;
-    if (Q == 0) return fail(RR_EINVAL, "rr_swept_clearance: the pair table is empty (rr_set_distance_pairs)");
-    if (!(safety >= 0.0f) || !std::isfinite(safety)) return fail(RR_EINVAL, "rr_swept_clearance: safety " + std::to_string(safety) + " is not a finite number >= 0");
-    if (!(tolerance >= 1e-6f) || !std::isfinite(tolerance))
-        return fail(RR_EINVAL, "rr_swept_clearance: tolerance " + std::to_string(tolerance) + " is not a finite number >= 1e-6");
-    const float maxd = e->dist_tab.max_distance;
-    if (maxd > 0.0f && maxd < INFINITY && maxd < safety + tolerance)
-        return fail(RR_EINVAL, "rr_swept_clearance: the cull's max_distance " + std::to_string(maxd) + " is below safety + tolerance = " +
-                                   std::to_string(safety + tolerance) + ": a culled pair's sphere gap could fake a hit");
     if (e->att_on)      // the proof's reach table is a constant of the model and the objects are staged once per row: a carried object would be swept past
         return fail(RR_EINVAL, "rr_swept_clearance: objects are attached to links (rr_set_attachments): the sweep does not move carried objects; "
-                               "detach them (rr_set_attachments with link NULL and no mask) or use rr_posture_clearance / rr_signed_distance at sampled postures");
+                               "detach them (rr_set_attachments with link NULL and no mask) or use rr_carried_sweep, which does");
     RRCHK(ensure_query(e, QF_DIST, "rr_swept_clearance"));       // (the device copy of the pair table)
     RRCHK(ensure_query(e, QF_SW, "rr_swept_clearance", {stage_part(&e->sw_stage, (size_t)N * RR_PC_MAX_POSTURES * 88, !on_device)}));
     HIPCHK(hipSetDevice(e->cfg.device));
@@ -2001,6 +2008,53 @@ int rr_get_attachments(rr_env *e, int32_t *link_out, float *rel_pose_out) {
             att_from_body(e->RM, l, &rows[((size_t)i * NOBJ + o) * ATT_ROW], out);
         }
     return RR_OK;
+}
+
+// ---- swept clearance with carried objects (rr_csweep.inc) -------------------------------------------------------------------------------
+// The chain table of k_carried_sweep on first use, all or nothing: chain[k][b] = the sum of |jpos[m]| over the bodies m from b up to,
+// but not including, k -- the term the reach loop of the model parse adds, in its order -- in float64 and rounded up; 0 where joint k is
+// not an ancestor-or-self of body b.  A table of its own: SweepReach, which k_swept_clearance reads, keeps its size.
+static int ensure_sweep_chain(rr_env *e, const char *who) {
+    if (e->sw_chain_dev) return RR_OK;
+    e->sw_chain = {};
+    for (int b = 0; b < NB; b++) {
+        double r = 0.0;
+        for (int k = b; k >= 0; k = PARENT_HOST[k]) {
+            float f = (float)r;
+            if ((double)f < r) f = std::nextafterf(f, INFINITY);
+            e->sw_chain.c[k][b] = f;
+            const double j[3] = {e->B.jpos[k][0], e->B.jpos[k][1], e->B.jpos[k][2]};
+            r += std::sqrt(j[0] * j[0] + j[1] * j[1] + j[2] * j[2]);
+        }
+    }
+    const GroupUpload up = {(void **)&e->sw_chain_dev, &e->sw_chain, sizeof(SweepChain), "the chain table"};
+    return ensure_group(e, -1, who, "the chain table", {mem_part(&e->sw_chain_dev, sizeof(SweepChain), false)}, &up);
+}
+
+// rr_swept_clearance with the carried objects moving.  Arguments, refusals, staging, buffers and the stream contract are that call's;
+// with the attachments off it IS that call.  With them on, k_carried_sweep reads in addition the attachment table and the chain table
+// and writes the same four buffers and nothing else.
+int rr_carried_sweep(rr_env *e, const float *segments, int32_t n_segments, int32_t on_device, float safety, float tolerance) {
+    if (!e) return fail(RR_EINVAL, "rr_carried_sweep: null env");
+    RRCHK(sweep_arguments(e, "rr_carried_sweep", segments, n_segments, safety, tolerance));
+    // nothing is carried: the same kernel, the same bytes.  (rr_swept_clearance checks the arguments once more; the check above is
+    // deliberate all the same: a refusal names the entry point that was called.)
+    if (!e->att_on) return rr_swept_clearance(e, segments, n_segments, on_device, safety, tolerance);
+    const int Q = e->dist_n, N = e->P.N, K = n_segments;
+    RRCHK(ensure_query(e, QF_DIST, "rr_carried_sweep"));       // (the device copy of the pair table)
+    RRCHK(ensure_query(e, QF_SW, "rr_carried_sweep", {stage_part(&e->sw_stage, (size_t)N * RR_PC_MAX_POSTURES * 88, !on_device)}));
+    RRCHK(ensure_sweep_chain(e, "rr_carried_sweep"));       // (a group of its own, like the two above: a failure here leaves the sweep buffers allocated and zero-filled)
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const HostStaging st = {e, !on_device};
+    const float *src = segments;
+    RRCHK(st.in(src, e->sw_stage, (size_t)N * K * 88));
+    void *const *b = e->qbuf[QF_SW];
+    hipLaunchKernelGGL(k_carried_sweep, dim3((unsigned)N * K), dim3(SWEEP_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, e->sw_reach_dev, src, K,
+                       safety, tolerance, (float *)b[RR_SW_STOP], (float4 *)b[RR_SW_HIT], (int4 *)b[RR_SW_ID], (float *)b[RR_SW_FREE],
+                       (const float *)e->att_table, (const SweepChain *)e->sw_chain_dev);
+    HIPCHK(hipGetLastError());
+    e->qk[QF_SW] = K;
+    return st.wait();
 }
 
 // ---- kinematics at candidate postures (rr_pkin.inc) -------------------------------------------------------------------------------------
