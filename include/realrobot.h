@@ -1371,6 +1371,50 @@ int rr_step_plan(rr_env *env, int32_t render_mode, const uint8_t *render_flags_h
  * keep their place in the plan: step_macro with macro_action None (env.py:391-393). */
 int rr_step_plan_masked(rr_env *env, const uint8_t *idle_mask_host, int32_t render_mode, const uint8_t *render_flags_host);
 
+/* Device-resident macro actions: REALRobotEnv.step_macro (env.py:388-467) for the whole batch in ONE call per step, the re-plan
+ * decision of env.py:388-408 taken on the device.  The handle keeps, per env, a REQUEST RECORD f32 [4] {p1x, p1y, p2x, p2y} (all NaN on
+ * creation), and shares the plan [1000][9] and the plan position with rr_plan_macro / rr_step_plan.  Buffers of rr_macro_buffer: */
+enum {
+    RR_MACRO_REQUEST = 0,   /* f32 [N, 4]        the request each env's plan was made for; NaN: none, or invalidated */
+    RR_MACRO_POSITION = 1,  /* i32 [N]           the plan row the env's next step takes (rows beyond 999: the last row); rr_plan_macro's cursor */
+    RR_MACRO_REPLANNED = 2, /* u8  [N]           1 where the last rr_step_macro planned, 0 elsewhere (idle envs included) */
+    RR_MACRO_PLAN = 3,      /* f32 [N, 1000, 9]  the plans: what rr_get_plan reads, env by env */
+    RR_MACRO_COUNT = 4
+};
+/* macro: f32 [N][4]; idle: u8 [N] or NULL (none).  With macro_on_device / idle_on_device != 0 they are device memory, read in place on
+ * the library's stream WITHOUT a wait (produce them on that stream or synchronise first; keep them unchanged until later work on that
+ * stream), as rr_set_joint_torques reads its table; otherwise host arrays, staged, and the call waits at its end.  Per env:
+ *   idle[e] != 0 (the reference's `macro_action is None`, env.py:391-393): the command is zeros(9); record, plan and position untouched.
+ *   otherwise: same = all four floats == the record (IEEE ==, as np.all(a == b): -0.0 equals 0.0, a NaN equals nothing -- a NaN request
+ *   re-plans on every step); need = !same || position >= 1000 (env.py:395-403).  A needing env stores the request in its record, gets a
+ *   new plan from its PRESENT joints (rr_plan_macro's rows bit for bit, RR_SOLVER_IK_SINGLE_SEED included) and position 0.  Every
+ *   non-idle env then takes plan row min(position, 999) as its command and advances its position (env.py:404-412, 463-467).
+ * The step itself is rr_step on that command, as in rr_step_plan_masked; render_mode / render_flags_host as there.  With device
+ * arguments nothing waits and nothing is read back: the list of needing envs and its length stay on the device.
+ * Values are not validated (as in rr_plan_macro).  The record, the list and the RR_MACRO_REPLANNED bytes are allocated by the first call
+ * (with the plan buffers where the handle has none), all or nothing.
+ * Errors: RR_EINVAL with every env and every record untouched for a null env, a null macro, a bad render_mode (rr_step_plan's rule), and
+ * for an idle array on the other side than macro (a mixed pair); RR_EDEVICE for a failed allocation or a device error.
+ * Resets (rr_reset, auto-resets), rr_write_state, rr_set_state, forks / rr_copy_envs, snapshot loads and checkpoint restores KEEP the
+ * record, plan and position of the destination env: policy state, like a plan in flight.  The reference does not re-plan on reset
+ * either; a caller who wants that calls rr_macro_invalidate.  rr_plan_macro and rr_step_plan* share the plan and the position but do not
+ * know the record: mixing them with rr_step_macro on one handle is legal, and the result is defined by the three buffers alone -- after
+ * rr_plan_macro an env whose record still equals the next request keeps the plan rr_plan_macro made and goes on from its position. */
+int rr_step_macro(rr_env *env,
+                  const float *macro /* f32 [N][4] {p1x, p1y, p2x, p2y} */, int32_t macro_on_device,
+                  const uint8_t *idle /* u8 [N] or NULL */,                 int32_t idle_on_device,
+                  int32_t render_mode, const uint8_t *render_flags_host);
+/* NaN into the record rows of the envs whose mask byte is non-zero (u8 [N], host or device; NULL: all envs): the next non-idle
+ * rr_step_macro re-plans them from their present joints -- "re-plan after a reset".  Plans and positions are not touched.  A device mask
+ * is read in place without a wait; with a host mask the call waits.  A handle without a record has nothing to invalidate. */
+int rr_macro_invalidate(rr_env *env, const uint8_t *env_mask, int32_t mask_on_device);
+/* Zero-copy device pointer + size of an RR_MACRO_* buffer, valid until rr_destroy (allocates the group on first use: record NaN,
+ * positions and plans zero).  STREAM CONTRACT as for the other device buffers.  Not a family of the query table: an accessor pair of
+ * its own, like rr_episode_buffer / rr_episode_copy_to_host. */
+int rr_macro_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
+/* Synchronising copy of a whole RR_MACRO_* buffer to host memory. */
+int rr_macro_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
+
 /* Per-kernel device timing with HIP events on the library's stream (bench.py roofline leg).
  * After rr_set_timing(env, 1), each rr_step/rr_render records events; rr_get_timing returns accumulated
  * milliseconds and launch counts per kernel since the last call and resets them.

@@ -51,7 +51,8 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_posture_dynamics', 'rr_posture_dynamics_buffer', 'rr_posture_dynamics_copy_to_host',
            'rr_set_joint_torques', 'rr_get_joint_torques', 'rr_joint_torque_buffer',
            'rr_set_external_wrenches', 'rr_get_external_wrenches', 'rr_external_wrench_buffer',
-           'rr_set_attachments', 'rr_get_attachments', 'rr_carried_sweep')
+           'rr_set_attachments', 'rr_get_attachments', 'rr_carried_sweep',
+           'rr_step_macro', 'rr_macro_invalidate', 'rr_macro_buffer', 'rr_macro_copy_to_host')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
@@ -62,6 +63,11 @@ XW_BODIES = 14
 # buffers of rr_episode_buffer (the RR_EP_* enum: goals and episodes on the device)
 (EP_SCORE, EP_REWARD, EP_DONE, EP_GOAL_INDEX, EP_EPISODE, EP_FINAL_OBS, EP_GOAL_POS, EP_GOAL_RGB) = range(8)
 EP_NAMES = ('score', 'reward', 'done', 'goal_index', 'episode', 'final_obs', 'goal_pos', 'goal_rgb')
+# buffers of rr_macro_buffer (the RR_MACRO_* enum: macro actions decided on the device): request f32 [N, 4], position i32 [N], replanned u8 [N],
+# plan f32 [N, 1000, 9]
+(MACRO_REQUEST, MACRO_POSITION, MACRO_REPLANNED, MACRO_PLAN) = range(4)
+MACRO_NAMES = ('request', 'position', 'replanned', 'plan')
+PLAN_LEN = 1000
 GOAL_SCORED, GOAL_HAS_START = 1, 2      # rr_set_goals flag bits: the object counts in the score / has a start pose
 # buffers of rr_kinematic_buffer (the RR_KIN_* enum), per env: joint_vel [11], link_pose [17, 7], link_vel [17, 6], obj_vel [n_obj, 6],
 # point_pos [P, 3], point_vel [P, 6], jacobian [P, 6, 11] for the P points in force (rr_set_kinematic_points)
@@ -311,6 +317,10 @@ def load_library():
     L.rr_set_attachments.argtypes = [vp, vp, vp, vp]
     L.rr_get_attachments.argtypes = [vp, vp, vp]
     L.rr_carried_sweep.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float]
+    L.rr_step_macro.argtypes = [vp, vp, i32, vp, i32, i32, vp]
+    L.rr_macro_invalidate.argtypes = [vp, vp, i32]
+    L.rr_macro_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rr_macro_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     for fam in QUERY_FAMILIES.values():
         getattr(L, fam.buffer).argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
         getattr(L, fam.copy_to_host).argtypes = [vp, i32, vp, C.c_size_t]

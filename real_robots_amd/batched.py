@@ -1729,6 +1729,94 @@ class BatchedREALRobotEnv:
         self.step_plan(render, idle=none.astype(np.uint8) if none.any() else None)
         self._macro_step[~none] += 1
 
+    # ------------------------------------------------------------------ macro actions decided on the device
+    @classmethod
+    def _macro_args(cls, N, macro_actions, idle):
+        """The arguments of `step_macro_device` for a handle of N envs -> (address, on the device, address or None, keep-alive
+        objects).  Every violation -- shape, dtype, contiguity, requests and idle mask on different sides -- is a ValueError raised
+        here, before the native call; nothing of a handle is needed."""
+        keep = []
+        if _on_device(macro_actions):
+            shape = tuple(macro_actions.shape) if hasattr(macro_actions, 'shape') else tuple(macro_actions.__cuda_array_interface__['shape'])
+            full = (N, 2, 2) if shape == (N, 2, 2) else (N, 4)       # the same memory either way
+            mp, m_dev, k = cls._state_arg(None, macro_actions, 'macro_actions', ('float32',), full)
+        else:
+            if hasattr(macro_actions, 'is_cuda') and hasattr(macro_actions, 'numpy'):      # a CPU torch tensor
+                macro_actions = macro_actions.numpy()
+            a = np.asarray(macro_actions)
+            if a.dtype.kind not in 'fiu':
+                raise ValueError("macro_actions must be a real numeric array of shape (%d, 2, 2) or (%d, 4), not dtype %s" % (N, N, a.dtype))
+            if a.shape not in ((N, 2, 2), (N, 4)):
+                raise ValueError("macro_actions must have shape (%d, 2, 2) or (%d, 4), not %s" % (N, N, a.shape))
+            with np.errstate(over='ignore'):
+                k = np.ascontiguousarray(a, dtype=np.float32).reshape(N, 4)
+            mp, m_dev = k.ctypes.data, 0
+        keep.append(k)
+        ip = None
+        if idle is not None:
+            if hasattr(idle, 'is_cuda') and hasattr(idle, 'numpy') and not idle.is_cuda:
+                idle = idle.numpy()
+            ip, i_dev, k = cls._state_arg(None, idle, 'idle', ('uint8', 'bool'), (N,))
+            keep.append(k)
+            if i_dev != m_dev:
+                raise ValueError("step_macro_device: macro_actions and idle must live on the same side (macro_actions on the %s, idle on the %s)"
+                                 % (('host', 'device')[m_dev], ('host', 'device')[i_dev]))
+        return mp, m_dev, ip, keep
+
+    def step_macro_device(self, macro_actions, idle=None, render=False):
+        """Batched REALRobotEnv.step_macro (env.py:388-467) with the re-plan decision taken on the device (rr_step_macro): one call
+        per step, no host bookkeeping.  macro_actions: [N, 2, 2] or [N, 4] {p1x, p1y, p2x, p2y} -- a float32 CUDA torch tensor or
+        `__cuda_array_interface__` object (C-contiguous; read in place on the library's stream without waiting and without a
+        read-back: produce it on that stream or synchronise first), or a numpy array (converted to float32, staged, synchronous).
+        idle: bool / uint8 [N] on the same side, or None: a flagged env steps with zeros(9) and keeps its request record, plan and
+        position (`macro_action is None`, env.py:391-393).  Every other env re-plans from its present joints when its request
+        differs from its record (IEEE ==: -0.0 equals 0.0, NaN never equals) or its plan is exhausted (position >= 1000), then takes
+        the next row of its plan.  render as in `step_plan`.  Resets, `write_state`, forks, snapshots and checkpoints keep record,
+        plan and position (policy state): `macro_invalidate` asks for a re-plan.  `step_macro` keeps its own host bookkeeping and
+        does not know the record; the two share the plans and positions (`macro_buffer`)."""
+        flags = None
+        if isinstance(render, np.ndarray) and render.size > 1:
+            flags = np.ascontiguousarray(render, dtype=np.uint8)
+            if flags.shape != (self.N,):
+                raise ValueError("render flags must have shape (%d,)" % self.N)
+            mode = 2
+        else:
+            mode = 1 if np.any(render) else 0
+        mp, m_dev, ip, keep = self._macro_args(self.N, macro_actions, idle)
+        nat.check(self.L.rr_step_macro(self.h, mp, m_dev, ip, m_dev, mode, flags.ctypes.data if flags is not None else None))
+        del keep
+
+    def macro_invalidate(self, env_mask=None):
+        """NaN into the request record of the masked envs (bool / uint8 [N], host or device; None: all envs): the next non-idle
+        `step_macro_device` re-plans them from their present joints -- "re-plan after a reset" (rr_macro_invalidate)."""
+        if env_mask is None:
+            nat.check(self.L.rr_macro_invalidate(self.h, None, 0))
+            return
+        if hasattr(env_mask, 'is_cuda') and hasattr(env_mask, 'numpy') and not env_mask.is_cuda:
+            env_mask = env_mask.numpy()
+        mp, m_dev, keep = self._state_arg(env_mask, 'env_mask', ('uint8', 'bool'), (self.N,))
+        nat.check(self.L.rr_macro_invalidate(self.h, mp, m_dev))
+        del keep
+
+    def macro_buffer(self, name, host=False):
+        """A buffer of the device-resident macro actions (rr_macro_buffer), by name (`_native.MACRO_NAMES`: request float32 [N, 4],
+        position int32 [N], replanned uint8 [N] -- 1 where the last `step_macro_device` planned --, plan float32 [N, 1000, 9]) or
+        MACRO_* constant: a device view (DLPack / __cuda_array_interface__, zero copy; ordering as for the other device buffers),
+        or with host=True a numpy copy after a wait."""
+        which = nat.MACRO_NAMES.index(name) if isinstance(name, str) and name in nat.MACRO_NAMES else name
+        if isinstance(which, bool) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.MACRO_NAMES):
+            raise ValueError("unknown macro buffer %r (known: %s)" % (name, ', '.join(nat.MACRO_NAMES)))
+        N = self.N
+        shape, dt = {nat.MACRO_REQUEST: ((N, 4), np.float32), nat.MACRO_POSITION: ((N,), np.int32), nat.MACRO_REPLANNED: ((N,), np.uint8),
+                     nat.MACRO_PLAN: ((N, nat.PLAN_LEN, 9), np.float32)}[int(which)]
+        if host:
+            out = np.empty(shape, dt)
+            nat.check(self.L.rr_macro_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
+            return out
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(self.L.rr_macro_buffer(self.h, int(which), C.byref(p), C.byref(n)))
+        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
+
     def set_camera(self, view, proj):
         """Row-major 4x4 OpenGL view / projection matrices replacing the eye camera of this batch (None, None: the default eye)."""
         if view is None and proj is None:

@@ -125,6 +125,9 @@ struct rr_env : ModelTables {
     unsigned char *mask_dev = nullptr; // [N]
     float *link_out = nullptr;         // [N][nl][7]
     float *plan = nullptr; int *plan_step = nullptr; float *ik_in = nullptr; float *ik_out = nullptr; float *ik_err = nullptr;   // lazily allocated (macro / cartesian adapters)
+    // device-resident macro actions (rr_step_macro): the request record [N][4], the list of the envs that need a plan [N] with its length
+    // behind it, the `replanned` bytes [N] of the last call; allocated by the first call, with the plan buffers where they are missing
+    float *macro_req = nullptr; int *macro_list = nullptr; unsigned char *macro_replanned = nullptr;
     float *score_out = nullptr; unsigned char *score_mask = nullptr;            // lazily allocated (rr_evaluate_goals)
     float4 *co_contacts = nullptr; float2 *co_force = nullptr; unsigned *co_partners = nullptr;   // lazily allocated (rr_contact_observations)
     // The output buffers of the ten query families (rr_query.inc): qbuf[family][which], a family's group allocated together on first use for
@@ -2838,6 +2841,97 @@ int rr_step_plan_masked(rr_env *e, const uint8_t *idle_mask_host, int32_t render
 
 int rr_step_plan(rr_env *e, int32_t render_mode, const uint8_t *render_flags_host) {
     return rr_step_plan_masked(e, nullptr, render_mode, render_flags_host);
+}
+
+// ---- device-resident macro actions (rr_macro.inc) -----------------------------------------------------------------------------------------
+// The record, the need list and the `replanned` bytes on first use, with the plan and IK buffers where the handle has none yet: one
+// group, all or nothing.  The record starts all NaN (one launch behind the allocation): no request equals it.
+static int ensure_macro(rr_env *e, const char *who) {
+    if (e->macro_req) return RR_OK;
+    const size_t N = e->P.N;
+    RRCHK(ensure_group(e, -1, who, "the macro record and the plan buffers",
+                       {mem_part(&e->macro_req, N * 16), mem_part(&e->macro_list, (N + 1) * 4), mem_part(&e->macro_replanned, N),
+                        mem_part(&e->plan, N * PLAN_LEN * 36), mem_part(&e->plan_step, N * 4), mem_part(&e->ik_in, N * 28), mem_part(&e->ik_out, N * 44),
+                        mem_part(&e->ik_err, N * 4)}));
+    hipLaunchKernelGGL(k_macro_invalidate, dim3((unsigned)((N * 4 + 255) / 256)), dim3(256), 0, e->stream, (int)N, (const unsigned char *)nullptr, e->macro_req);
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+// One step of macro actions decided on the device.  Launch order on the main stream: staging (host arguments only), k_macro_decide,
+// k_macro_replan, k_plan_fetch, rr_step.  Device arguments are read in place and nothing waits; host arguments go through the staging
+// helper, whose wait stands at the end because they are host memory.  The grid of k_macro_replan is sized from N (up to MR_WAVES
+// listed envs a workgroup each, beyond that ceil(count / MR_WAVES) envs per workgroup, at most MR_SLOTS): the list's length stays on the
+// device.
+int rr_step_macro(rr_env *e, const float *macro, int32_t macro_on_device, const uint8_t *idle, int32_t idle_on_device, int32_t render_mode,
+                  const uint8_t *render_flags_host) {
+    if (!e) return fail(RR_EINVAL, "rr_step_macro: null env");
+    if (!macro) return fail(RR_EINVAL, "rr_step_macro: null macro");
+    // (checked here as well: the decision moves records and plan positions, which must not happen for a step rr_step then rejects)
+    if (render_mode < 0 || render_mode > 2 || (render_mode == 2 && !render_flags_host)) return fail(RR_EINVAL, "rr_step_macro: bad render_mode");
+    if (idle && !macro_on_device != !idle_on_device)
+        return fail(RR_EINVAL, std::string("rr_step_macro: macro and idle must live on the same side (macro on the ") + (macro_on_device ? "device" : "host") +
+                                   ", idle on the " + (idle_on_device ? "device" : "host") + ")");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    RRCHK(ensure_macro(e, "rr_step_macro"));
+    const int N = e->P.N;
+    const HostStaging st = {e, !macro_on_device};
+    // (a host request travels through the otherwise idle ik_out staging buffer, as in rr_plan_macro; a host idle mask through mask_dev)
+    RRCHK(st.in(macro, e->ik_out, (size_t)N * 16));
+    const unsigned char *idle_dev = idle;
+    if (idle && !idle_on_device) { HIPCHK(hipMemcpyAsync(e->mask_dev, idle, N, hipMemcpyHostToDevice, e->stream)); idle_dev = e->mask_dev; }
+    hipLaunchKernelGGL(k_macro_decide, dim3(1), dim3(MD_THREADS), 0, e->stream, N, macro, idle_dev, e->macro_req, e->plan_step, e->macro_replanned, e->macro_list);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_macro_replan, dim3((unsigned)std::min(N, std::max(MR_WAVES, (N + MR_SLOTS - 1) / MR_SLOTS))), dim3(64), 0, e->stream, e->IK, e->P, e->D, (const float *)e->macro_req, (const int *)e->macro_list, e->plan);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_plan_fetch, dim3((N + 255) / 256), dim3(256), 0, e->stream, e->P, e->D, e->plan, e->plan_step, idle_dev);
+    HIPCHK(hipGetLastError());
+    const int rc = rr_step(e, e->D.cmd, 1, render_mode, render_flags_host);
+    const int rw = st.wait();
+    return rc != RR_OK ? rc : rw;
+}
+
+int rr_macro_invalidate(rr_env *e, const uint8_t *env_mask, int32_t mask_on_device) {
+    if (!e) return fail(RR_EINVAL, "rr_macro_invalidate: null env");
+    if (!e->macro_req) return RR_OK;      // no record yet: it is created all NaN
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const int N = e->P.N;
+    const unsigned char *m = env_mask;
+    const bool host_mask = env_mask && !mask_on_device;
+    if (host_mask) { HIPCHK(hipMemcpyAsync(e->mask_dev, env_mask, N, hipMemcpyHostToDevice, e->stream)); m = e->mask_dev; }
+    hipLaunchKernelGGL(k_macro_invalidate, dim3((unsigned)((N * 4 + 255) / 256)), dim3(256), 0, e->stream, N, m, e->macro_req);
+    HIPCHK(hipGetLastError());
+    if (host_mask) HIPCHK(hipStreamSynchronize(e->stream));   // the argument is host memory
+    return RR_OK;
+}
+
+static int macro_field(rr_env *e, int32_t which, void **ptr, size_t *bytes, const char *who) {
+    if (!e || which < 0 || which >= RR_MACRO_COUNT) return fail(RR_EINVAL, std::string(who) + ": bad buffer");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    RRCHK(ensure_macro(e, who));
+    const size_t N = e->P.N;
+    void *const p[RR_MACRO_COUNT] = {e->macro_req, e->plan_step, e->macro_replanned, e->plan};
+    const size_t b[RR_MACRO_COUNT] = {N * 16, N * 4, N, N * PLAN_LEN * 36};
+    *ptr = p[which]; *bytes = b[which];
+    return RR_OK;
+}
+
+int rr_macro_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
+    void *p = nullptr; size_t b = 0;
+    RRCHK(macro_field(e, which, &p, &b, "rr_macro_buffer"));
+    if (dev_ptr) *dev_ptr = p;
+    if (bytes) *bytes = b;
+    return RR_OK;
+}
+
+int rr_macro_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
+    if (!dst) return fail(RR_EINVAL, "rr_macro_copy_to_host: null destination");
+    void *p = nullptr; size_t b = 0;
+    RRCHK(macro_field(e, which, &p, &b, "rr_macro_copy_to_host"));
+    if (bytes != b) return fail(RR_EINVAL, "rr_macro_copy_to_host: size mismatch");
+    HIPCHK(hipMemcpyAsync(dst, p, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return RR_OK;
 }
 
 // ---- per-env static layers: per-env cameras (rr_set_env_cameras) and per-env appearance (rr_set_env_appearance) -------------

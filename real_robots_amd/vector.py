@@ -94,6 +94,15 @@ device's record of the finished episode, in the layout above.  Terminations stay
 state, RR_F_ERRFLAGS & 5) is NOT reset at once: it is reset with the next truncation sweep -- the next step in which any env
 reaches `max_episode_steps` --, and is reported as truncated in that step.  Without `goals` nothing changes: zero rewards, the
 observation dict and infos as they were.
+Macro actions: `action_type='macro_action'` makes the action dict `{"macro_action": [N, 2, 2], "render": ...}` -- the reference's
+`macro_space` bounds ([[-0.25, -0.5], [-0.25, -0.5]] .. [[0.05, 0.5], [0.05, 0.5]], env.py:49-52) with a leading env axis -- and step()
+calls BatchedREALRobotEnv.step_macro_device: the re-plan decision of REALRobotEnv.step_macro is taken on the device, a numpy array or a
+float32 CUDA tensor alike (a bare array [N, 2, 2] is taken as the requests).  The optional key `"macro_idle"` (bool / uint8 [N], on the
+same side as the requests; not part of the spaces) flags envs that step with zeros(9) and keep their plan (`macro_action is None`).  As
+in the reference a reset keeps an env's plan and its place in it; with `macro_replan_on_reset=True` reset() and the same-step
+autoresets -- the device-side reset of a goal step included -- call `macro_invalidate` for the envs they reset, which then re-plan from
+their reset posture at their next step.  Both keyword-only; the default `action_type='joints'` leaves spaces, dicts and launches as they
+are.
 """
 import numpy as np
 
@@ -130,15 +139,21 @@ class REALRobotVectorEnv(_Base):
     def __init__(self, num_envs, objects=3, additional_obs=False, eye_width=320, eye_height=240, device=0,
                  max_episode_steps=int(15e6), render_every_step=True, device_obs=False, solver=None, dynamics_randomization=None,
                  camera_randomization=None, appearance_randomization=None, actuator_randomization=None, *, kinematic_obs=False,
-                 kinematic_points=None, dynamics_obs=False, joint_torque_actions=False, external_wrench_actions=False, ray_sensors=None, distance_pairs=None, distance_max=None, contact_obs=False, goals=None,
+                 kinematic_points=None, dynamics_obs=False, joint_torque_actions=False, external_wrench_actions=False, action_type='joints', macro_replan_on_reset=False, ray_sensors=None, distance_pairs=None, distance_max=None, contact_obs=False, goals=None,
                  goal_stride=1):
         self.num_envs = int(num_envs)
+        if action_type not in ('joints', 'macro_action'):
+            raise ValueError("action_type must be 'joints' or 'macro_action', not %r" % (action_type,))
+        self.action_type, self.macro_replan_on_reset = action_type, bool(macro_replan_on_reset)
+        if self.macro_replan_on_reset and action_type != 'macro_action':
+            raise ValueError("macro_replan_on_reset needs action_type='macro_action'")
         self._goals = None if goals is None else self._check_goals(goals, OBJECT_NAMES[:int(objects)], int(eye_height), int(eye_width))
         self.goal_stride = int(goal_stride)
         self._robot = Kuka(additional_obs, objects, eye_width, eye_height, env=None)
         self.joint_torque_actions = bool(joint_torque_actions)
         self.external_wrench_actions = bool(external_wrench_actions)
-        self.single_action_space, self.action_space = self._action_spaces(self._robot, self.num_envs, self.joint_torque_actions, self.external_wrench_actions)
+        self.single_action_space, self.action_space = self._action_spaces(self._robot, self.num_envs, self.joint_torque_actions, self.external_wrench_actions,
+                                                                             self.action_type)
         self.single_observation_space = self._robot.observation_space
         self.contact_obs = bool(contact_obs)
         if self.contact_obs:
@@ -461,6 +476,8 @@ class REALRobotVectorEnv(_Base):
         if self._act_rand:
             infos["actuators"] = self._draw_actuators(np.ones(self.num_envs, bool))
         self._be.reset()
+        if self.macro_replan_on_reset:
+            self._be.macro_invalidate()
         self._steps[:] = 0
         if self._goals is not None:
             # env i starts goal i mod G from its start poses (set_goal, env.py:151-166); the first reward is taken against that state
@@ -476,13 +493,18 @@ class REALRobotVectorEnv(_Base):
         return self._obs(self.render_every_step), infos
 
     @staticmethod
-    def _action_spaces(robot, num_envs, joint_torque_actions=False, external_wrench_actions=False):
+    def _action_spaces(robot, num_envs, joint_torque_actions=False, external_wrench_actions=False, action_type='joints'):
         """(single_action_space, action_space) of a vector env over `robot`'s joint command: the batched space is the single one with
         a leading env axis (gymnasium.vector.utils.batch_space); `joint_torque_actions` adds the unbounded "joint_torques" entry,
         `external_wrench_actions` the unbounded "external_wrenches" entry."""
         single = {"joint_command": robot.action_space, "render": spaces.MultiBinary(1)}
         batched = {"joint_command": spaces.Box(low=np.tile(robot.min_joints, (num_envs, 1)), high=np.tile(robot.max_joints, (num_envs, 1)), dtype=float),
                    "render": spaces.MultiBinary(num_envs)}
+        if action_type == 'macro_action':      # the reference's macro_space (env.py:49-52) in place of the joint command
+            lo, hi = np.array([[-0.25, -0.5], [-0.25, -0.5]]), np.array([[0.05, 0.5], [0.05, 0.5]])
+            single = {"macro_action": spaces.Box(low=lo, high=hi, dtype=float), "render": spaces.MultiBinary(1)}
+            batched = {"macro_action": spaces.Box(low=np.tile(lo, (num_envs, 1, 1)), high=np.tile(hi, (num_envs, 1, 1)), dtype=float),
+                       "render": spaces.MultiBinary(num_envs)}
         if joint_torque_actions:
             single["joint_torques"] = spaces.Box(low=-np.inf, high=np.inf, shape=(nat.N_JOINTS,), dtype=np.float32)
             batched["joint_torques"] = spaces.Box(low=-np.inf, high=np.inf, shape=(num_envs, nat.N_JOINTS), dtype=np.float32)
@@ -494,7 +516,8 @@ class REALRobotVectorEnv(_Base):
     def step(self, actions):
         """actions: float array [N, 9] of joint commands (or a dict with "joint_command" [N, 9], optional "render" and, with
         joint_torque_actions, optional "joint_torques" [N, 11]: absent, the torques in force are kept; with external_wrench_actions,
-        optional "external_wrenches" [N, 14, 6], likewise)."""
+        optional "external_wrenches" [N, 14, 6], likewise).  With action_type='macro_action': an array [N, 2, 2] of requests, host or
+        device (or a dict with "macro_action", optional "macro_idle" [N] and "render")."""
         render = self.render_every_step
         if isinstance(actions, dict):
             render = bool(np.any(actions.get("render", render)))
@@ -502,8 +525,14 @@ class REALRobotVectorEnv(_Base):
                 self._be.set_joint_torques(actions["joint_torques"])
             if self.external_wrench_actions and actions.get("external_wrenches") is not None:
                 self._be.set_external_wrenches(actions["external_wrenches"])
-            actions = actions["joint_command"]
-        self._be.step(np.asarray(actions, dtype=np.float32), render=render)
+            idle = actions.get("macro_idle") if self.action_type == 'macro_action' else None
+            actions = actions["macro_action" if self.action_type == 'macro_action' else "joint_command"]
+        else:
+            idle = None
+        if self.action_type == 'macro_action':
+            self._be.step_macro_device(actions, idle=idle, render=render)
+        else:
+            self._be.step(np.asarray(actions, dtype=np.float32), render=render)
         self._steps += 1
         truncated = self._steps >= self.max_episode_steps
         n = self.num_envs
@@ -524,6 +553,8 @@ class REALRobotVectorEnv(_Base):
             infos["_final_obs"] = truncated.copy()
             self._redraw(truncated, infos)
             self._be.reset(truncated.astype(np.uint8))
+            if self.macro_replan_on_reset:
+                self._be.macro_invalidate(truncated.astype(np.uint8))
             self._steps[truncated] = 0
             if render:
                 self._be.render()
@@ -551,6 +582,8 @@ class REALRobotVectorEnv(_Base):
             infos["final_obs"] = fin
             infos["_final_obs"] = truncated.copy()
             self._redraw(truncated, infos)
+            if self.macro_replan_on_reset:
+                be.macro_invalidate(truncated.astype(np.uint8))
             self._steps[truncated] = 0
             if render:
                 be.render()

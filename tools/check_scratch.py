@@ -13,7 +13,7 @@ HOT = ('k_prep_a16', 'k_prep_b16', 'k_prep_ab16', 'k_collide', 'k_solve', 'k_ras
        'k_ik', 'k_plan_macro', 'k_fork', 'k_kinematics', 'k_state_rw', 'k_ray_cast', 'k_closest_points', 'k_posture_clearance', 'k_signed_distance', 'k_signed_gradient', 'k_swept_clearance',
        'k_posture_kinematics', 'k_posture_ik', 'k_posture_dynamics', 'k_joint_torque', 'k_ext_wrench',
        'k_posture_clearance_carry', 'k_signed_distance_carry', 'k_signed_gradient_carry', 'k_attach_capture', 'k_attach_set',
-       'k_carried_sweep')
+       'k_carried_sweep', 'k_macro_decide', 'k_macro_replan')
 
 
 def main():
