@@ -33,6 +33,19 @@ two calls are compared; False -- the call is A's alone.  `check_query_conditions
 keeps the tables it has set (`points`, `max_distance`, `n_rays`) so that the arguments of later calls fit them, and `last`: which
 record wrote which result buffers last.  `probe_arguments` are the fixed query arguments of every comparison, `anchor_references`
 the float64 restatements on a state that a record itself defines (`is_anchor`).
+
+`program(..., commands=True)` draws a COMMAND programme (sessions c70 and c5; its own generator and rng stream again): the calls that
+put per-env command-side state into the handle or launch inside the step.  Ten more mutators (C_MUTATORS) -- the joint torque and
+external wrench tables (set, masked and unmasked clearing, `torques_from_dynamics`: the bias of posture_dynamics() fed straight back),
+the attachments (given poses, capture, masked detach, the unmasked detach) and macro_invalidate --, one more step kind, `step_macro`
+(rr_step_macro: requests held per env, an idle mask, a render form, now and then a NaN or a -0.0), and ten observers (C_OBSERVERS):
+posture_dynamics, carried_sweep, the four posture queries that run their `_carry` kernels while attachments are on,
+`swept_clearance_refused` and the three table read-backs, each `compared` or silent like a query record.  The Session keeps what the
+roads need -- `attached`: the feature is on -- and a pure-numpy MODEL of the macro decision rule of the header (`macro`: record,
+position, replanned), which plan_macro, step_plan, step_macro and macro_invalidate move and no state mutator does: A and B both run
+k_macro_decide, so the model is the independent reference of that rule.  `check_command_conditions` asserts what a command programme
+holds; `command_anchor_references` are the float64 restatements (tests/numpy_dynamics.py, tests/numpy_carry.py) behind the two
+anchors, a set_state and a full write_state that each stand directly behind an attach of known poses (`anchor_attach`).
 """
 import numpy as np
 
@@ -60,13 +73,31 @@ FAMILY = {'closest_points': ('dist',), 'posture_clearance': ('pc',), 'signed_dis
 READ_BEHIND = ('write_state', 'fork_dev', 'load_snapshot', 'reset_dev', 'restore', 'set_object_poses', 'episode_reset',
                'set_distance_pairs', 'set_kinematic_points')
 Q_KS, Q_PAIR_CLASSES, Q_RAY_COUNTS = (1, 3, 32), ('one', 'default', 'collision', 'full'), (1, 4, 64)
+# the command programmes (sessions c70, c5): ten more mutators, the step kind step_macro, ten observers
+C_MUTATORS = ('set_joint_torques', 'set_external_wrenches', 'clear_joint_torques', 'clear_external_wrenches', 'torques_from_dynamics',
+              'attach', 'attach_capture', 'detach', 'detach_all', 'macro_invalidate')
+C_STEP_KINDS = STEP_KINDS + ('step_macro',)
+CARRY_QUERIES = ('posture_clearance', 'signed_distance', 'signed_distance_at', 'signed_distance_gradient')     # (_carry kernels while attached)
+C_OBSERVERS = ('posture_dynamics', 'carried_sweep') + CARRY_QUERIES + ('swept_clearance_refused', 'joint_torques', 'external_wrenches',
+                                                                       'attachments')
+FAMILY.update({'posture_dynamics': ('pd',), 'torques_from_dynamics': ('pd',), 'carried_sweep': ('sw',), 'swept_clearance_refused': (),
+               'joint_torques': (), 'external_wrenches': (), 'attachments': ()})
+# the state mutators whose interplay with the tables, the attachments and the macro record the header fixes (state_kind(op))
+STATE_MUTATORS = ('reset_dev', 'fork_dev', 'load_snapshot', 'restore', 'episode_reset', 'set_state', 'write_joints', 'write_poses')
+CAPTURE_BEHIND = ('fork_dev', 'load_snapshot', 'reset_dev', 'restore', 'write_joints')     # ... and a step
+N_WRENCH_ROWS = 14                          # (RR_XW_BODIES: eleven robot bodies, three objects)
+MACRO_LO, MACRO_HI = np.array([-0.25, -0.5, -0.25, -0.5], np.float32), np.array([0.05, 0.5, 0.05, 0.5], np.float32)      # (plan_macro's draws)
+PLAN_LEN = 1000
 
 # the sessions of tests/test_gpu_session.py: name -> (seed, N, objects, width, height, ops); the seed was fixed once, for the
 # coverage the device reports (NOTEBOOK.md), and is never changed to make a comparison pass
 Q_LENGTH = 74                               # what the conditions of a query programme cost (below)
+C_LENGTH = 212                           # what the conditions of a command programme cost (the comment at C_MIN_LENGTH)
 SESSIONS = {'n70': (20261, 70, 3, 64, 64, 200), 'n5': (20262, 5, 1, 96, 64, 200), 'n1100': (20263, 1100, 3, 32, 32, 200),
-            'q70': (20264, 70, 3, 64, 64, Q_LENGTH), 'q5': (20265, 5, 1, 96, 64, Q_LENGTH)}
+            'q70': (20264, 70, 3, 64, 64, Q_LENGTH), 'q5': (20265, 5, 1, 96, 64, Q_LENGTH),
+            'c70': (20266, 70, 3, 64, 64, C_LENGTH), 'c5': (20267, 5, 1, 96, 64, C_LENGTH)}
 QUERY_SESSIONS = ('q70', 'q5')              # drawn with program(..., queries=True)
+COMMAND_SESSIONS = ('c70', 'c5')            # drawn with program(..., commands=True)
 
 # What a programme holds, whatever its size (check_conditions): M = 23 mutator kinds, O = 11 observer kinds; a pair costs 2 ops, a
 # triple 3, an observer behind a pair 1.  Every mutator 3 times in pairs, once with each render form (138); every observer behind a
@@ -84,6 +115,18 @@ MIN_LENGTH = 200
 # unit: write_state (joint positions) -- posture_ik without seeds (39).  Every query observer once more behind a pair, directly in
 # front of the next unit's mutator (9).  74 ops; a longer programme gets further steps.
 Q_MIN_LENGTH = Q_LENGTH
+# A command programme holds the conditions of check_command_conditions, and they cost more than a query programme's: a mutator needs
+# a step of its own directly behind it, so every condition of the form "X directly followed by a step" is a pair of two ops that
+# nothing else can share.  In the order of _command_program: plan_macro and four step_macro with the same requests (5); both tables,
+# the attachments, a snapshot and two checkpoints, each with its step (12); the eight state mutators with everything on, each
+# directly behind the step_macro of a new mutator and in front of a step (8 x 4, and the carry query of the attach_capture: 33), once
+# more with a step_macro behind them (16); attach_capture with its carry query behind five of them (20) and a carry query alone behind
+# the same five (15); the other render forms of the ten new mutators with torques_from_dynamics behind a fork (7 + 8 + 8), of
+# macro_invalidate with the second plan_macro, a step_plan and a step_macro (10), of detach and detach_all with the attach calls that
+# turn the feature on again and the two anchors with their attach (24); the three unmasked clearing calls and the eight state mutators
+# with everything off (22): 180 ops.  32 observers behind steps, so that each of the ten kinds is made both compared and silent, the
+# sweeps with attachments on and off: 212 ops, about three query programmes; a longer programme gets further steps.
+C_MIN_LENGTH = C_LENGTH
 # collision shapes of the model by name (BatchedREALRobotEnv.collision_shapes; tests/test_session_program.py asserts the list)
 ROBOT_SHAPES = ('lbr_iiwa_link_1', 'lbr_iiwa_link_2', 'lbr_iiwa_link_3', 'lbr_iiwa_link_4', 'lbr_iiwa_link_5', 'lbr_iiwa_link_6',
                 'lbr_iiwa_link_7', 'base', 'finger_00', 'finger_01', 'skin_01', 'skin_00', 'finger_10', 'finger_11', 'skin_11', 'skin_10')
@@ -478,6 +521,415 @@ def _query_program(seed, N, nobj, length):
     return ops
 
 
+# ------------------------------------------------------------------------------------------------------- the command programmes
+class MacroModel:
+    """The decision rule of rr_step_macro as the header states it (include/realrobot.h, "Device-resident macro actions"), in numpy:
+    the request record f32 [N, 4] (NaN on creation), the plan position i32 [N], shared with rr_plan_macro (position 0 for a planned
+    env) and rr_step_plan* (a non-idle env advances), and `replanned` u8 [N] of the last step_macro.  No state mutator moves any of
+    them.  float32 ==: -0.0 equals 0.0, a NaN equals nothing."""
+
+    def __init__(self, N):
+        self.record = np.full((N, 4), np.nan, np.float32)
+        self.position = np.zeros(N, np.int32)
+        self.replanned = np.zeros(N, np.uint8)
+
+    @staticmethod
+    def _on(mask, N):
+        return np.ones(N, bool) if mask is None else np.asarray(mask) != 0
+
+    def plan(self, mask):
+        self.position[self._on(mask, len(self.position))] = 0
+
+    def step_plan(self, idle):
+        self.position[np.ones(len(self.position), bool) if idle is None else np.asarray(idle) == 0] += 1
+
+    def invalidate(self, mask):
+        self.record[self._on(mask, len(self.position))] = np.nan
+
+    def step_macro(self, macro, idle):
+        macro = np.asarray(macro, np.float32).reshape(-1, 4)
+        act = np.ones(len(macro), bool) if idle is None else np.asarray(idle) == 0
+        same = (macro == self.record).all(axis=1)
+        need = act & (~same | (self.position >= PLAN_LEN))
+        self.record[need] = macro[need]
+        self.position[need] = 0
+        self.replanned = need.astype(np.uint8)
+        self.position[act] += 1
+        return need
+
+    def apply(self, op):
+        """the four kinds of record that move the model; every other record leaves it alone"""
+        k = op['kind']
+        if k == 'plan_macro':
+            self.plan(op['mask'])
+        elif k == 'step_plan':
+            self.step_plan(op.get('idle'))
+        elif k == 'step_macro':
+            self.step_macro(op['macro'], op['idle'])
+        elif k == 'macro_invalidate':
+            self.invalidate(op['mask'])
+
+
+def state_kind(op):
+    """the kind of a state mutator of STATE_MUTATORS ('write_joints' / 'write_poses': a masked write_state of that column group
+    alone), else None"""
+    k = op['kind']
+    if k == 'write_state':
+        return {W_JOINT_POS: 'write_joints', W_OBJ_POSE: 'write_poses'}.get(op['parts']) if op['mask'] is not None and not op['fresh'] and not op['reset'] else None
+    return k if k in STATE_MUTATORS else None
+
+
+class Situation:
+    """What a command programme has set so far, from its records alone: which envs have a non-zero row in either table, whether the
+    features are on, which envs carry something, and the macro model.  Forks, resets, writes, snapshot loads and restores leave all
+    of it with the env, as the header says, so no state mutator appears here."""
+
+    def __init__(self, N):
+        self.N = N
+        self.t_nz, self.w_nz, self.att = np.zeros(N, bool), np.zeros(N, bool), np.zeros(N, bool)
+        self.t_on = self.w_on = self.attached = False
+        self.macro = MacroModel(N)
+
+    def apply(self, op):
+        k = op['kind']
+        m = MacroModel._on(op.get('mask'), self.N)
+        if k == 'set_joint_torques':
+            self.t_nz[m], self.t_on = (op['torques'][m] != 0).any(axis=1), True
+        elif k == 'torques_from_dynamics':
+            self.t_nz[m], self.t_on = True, True          # (the gravity torques of an arm that is not folded onto its axis)
+        elif k == 'set_external_wrenches':
+            self.w_nz[m], self.w_on = (op['wrenches'][m] != 0).reshape(int(m.sum()), -1).any(axis=1), True
+        elif k == 'clear_joint_torques':
+            self.t_nz[m], self.t_on = False, self.t_on and op['mask'] is not None
+        elif k == 'clear_external_wrenches':
+            self.w_nz[m], self.w_on = False, self.w_on and op['mask'] is not None
+        elif k in ('attach', 'attach_capture'):
+            self.att[m], self.attached = (op['links'][m] >= 0).any(axis=1), True
+        elif k == 'detach':
+            self.att[m] = False
+        elif k == 'detach_all':
+            self.att[:], self.attached = False, False
+        self.macro.apply(op)
+
+    def tables(self):
+        return bool(self.t_nz.any() and self.w_nz.any())
+
+    def carrying(self):
+        return bool(self.attached and self.att.any())
+
+    def in_flight(self):
+        return bool(((self.macro.position > 0) & ~np.isnan(self.macro.record).any(axis=1)).any())
+
+    def all_off(self):
+        return not (self.t_on or self.w_on or self.attached)
+
+
+ANCHOR_SALT = 0                             # moved on the CPU until the float64 reference decides every anchor item (test_the_command_anchors_are_decided)
+
+
+def anchor_attach(N, nobj, which):
+    """the attach record in force at anchor `which` (0: the set_state, 1: the full write_state): every env, poses given.  Object o of
+    env e hangs on a finger link or on a link below joint 7, 20 to 30 cm from that link's frame; every third (env, object) is free."""
+    rng = np.random.default_rng([96, int(N), int(nobj), int(which), ANCHOR_SALT])
+    pool = np.array(FINGER_LINKS + ARM_LINKS, np.int32)
+    links = pool[rng.integers(len(pool), size=(N, nobj))].astype(np.int32)
+    links[(np.arange(N)[:, None] + np.arange(nobj)[None, :] + which) % 3 == 2] = -1
+    v = rng.normal(size=(N, nobj, 3))
+    rel = np.zeros((N, nobj, 7), np.float32)
+    rel[..., :3] = v / np.linalg.norm(v, axis=-1, keepdims=True) * rng.uniform(0.2, 0.3, (N, nobj, 1))
+    quat = rng.normal(size=(N, nobj, 4))
+    rel[..., 3:] = quat / np.linalg.norm(quat, axis=-1, keepdims=True)
+    return dict(kind='attach', links=links, rel=rel, mask=None, anchor=True)
+
+
+def is_command_anchor(op):
+    """a set_state or full write_state of a command programme that stands directly behind its `anchor_attach`"""
+    return bool(op.get('anchor')) and is_anchor(op)
+
+
+class _CDraw(_Draw):
+    """the value draws of a command programme"""
+
+    def __init__(self, rng, N, nobj, salt=0):
+        super().__init__(rng, N, nobj, salt)
+        self.req = self.requests(N)
+        self.req[0, 1] = 0.0                # (a component that is exactly 0.0, whatever the draw)
+        self.n_macro = self.n_pd = self.n_sweep = 0
+        self.n_seen = {}
+
+    def requests(self, n):
+        """n requests in the range of plan_macro's draws; about one in six has a component that is exactly 0.0"""
+        rng = self.rng
+        r = rng.uniform(MACRO_LO, MACRO_HI, (n, 4)).astype(np.float32)
+        zero = np.flatnonzero(rng.random(n) < 1 / 6)
+        r[zero, rng.integers(4, size=len(zero))] = 0.0
+        return r
+
+    def compared(self, kind):
+        n = self.n_seen[kind] = self.n_seen.get(kind, 0) + 1
+        return (n + C_OBSERVERS.index(kind) + self.salt) % 2 == 0
+
+    def step_macro(self, form, hold=False):
+        """the requests are held per env and redrawn for about a tenth of the envs per op (`hold`: for none); every fourth op gives a
+        NaN to one env, every fifth -0.0 wherever a request is 0.0 -- in the record of the call, not in the held requests"""
+        N, rng = self.N, self.rng
+        n = self.n_macro
+        self.n_macro += 1
+        if not hold:
+            new = rng.random(N) < 0.1
+            new[rng.integers(N)] = True
+            new[0] = False                  # (env 0 keeps its request, with the 0.0 in it, for the whole programme)
+            self.req[new] = self.requests(int(new.sum()))
+        m = self.req.copy()
+        if not hold and n % 4 == 3:
+            m[rng.integers(1, N), rng.integers(4)] = np.nan
+        idle = rng.random(N) < 0.15
+        idle[rng.integers(N)] = True
+        if not hold and n % 5 == 2:
+            m[m == 0.0] = np.float32(-0.0)
+            idle[0] = False                 # (... and meets the -0.0 awake)
+        if not idle.any():
+            idle[rng.integers(1, N)] = True
+        if idle.all():
+            idle[0] = False
+        op = dict(kind='step_macro', macro=m, idle=idle.astype(np.uint8), hold=bool(hold))
+        op.update(self.render(form))
+        return op
+
+    def _zeros(self, flat, mask):
+        """inside the mask: a row that is all zero, a row that is all -0.0, a -0.0 in a row that is not zero"""
+        pick = self.rng.permutation(np.flatnonzero(mask))
+        if len(pick) >= 2:
+            flat[pick[0]] = 0.0
+        if len(pick) >= 3:
+            flat[pick[1]] = np.float32(-0.0)
+        flat[pick[-1], self.rng.integers(flat.shape[1])] = np.float32(-0.0)
+        return pick
+
+    def new(self, kind, unmasked=False, inplace=False, keep=None):
+        """a record of one of C_MUTATORS.  `keep`: an env that a masked clearing call or detach must leave alone"""
+        N, nobj, rng = self.N, self.nobj, self.rng
+        op = dict(kind=kind)
+        if kind == 'set_joint_torques':     # about +-5 N m on the arm, +-0.2 on the fingers
+            t = np.concatenate([rng.uniform(-5.0, 5.0, (N, 7)), rng.uniform(-0.2, 0.2, (N, 4))], axis=1).astype(np.float32)
+            mask = self.mask()
+            self._zeros(t, mask)
+            op.update(torques=t, mask=mask, inplace=bool(inplace))
+        elif kind == 'set_external_wrenches':      # robot bodies: a few N, a few tenths of N m; objects: up to about their weight
+            w = np.empty((N, N_WRENCH_ROWS, 6), np.float32)
+            w[:, :11, :3], w[:, :11, 3:] = rng.uniform(-3.0, 3.0, (N, 11, 3)), rng.uniform(-0.3, 0.3, (N, 11, 3))
+            w[:, 11:, :3], w[:, 11:, 3:] = rng.uniform(-4.0, 4.0, (N, 3, 3)), rng.uniform(-0.02, 0.02, (N, 3, 3))
+            mask = self.mask()
+            pick = self._zeros(w.reshape(N, -1), mask)
+            if len(pick) >= 5:              # the zero rule holds per target: robot rows all zero, object rows all zero
+                w[pick[2], :11], w[pick[3], 11:] = 0.0, 0.0
+            op.update(wrenches=w, mask=mask, inplace=bool(inplace))
+        elif kind in ('clear_joint_torques', 'clear_external_wrenches', 'macro_invalidate', 'detach'):
+            mask = None if unmasked else self.mask()
+            if mask is not None and keep is not None:
+                mask[keep] = 0
+                if not mask.any():
+                    mask[(keep + 1) % N] = 1
+            op.update(mask=mask)
+        elif kind == 'torques_from_dynamics':
+            op.update(mask=self.mask(), compared=True, inverse=False)
+        elif kind in ('attach', 'attach_capture'):
+            pool = np.array(FINGER_LINKS + ARM_LINKS, np.int32)
+            links = pool[rng.integers(len(pool), size=(N, nobj))].astype(np.int32)
+            links[rng.random((N, nobj)) < 0.3] = -1            # some objects stay free inside an attached env
+            links[rng.random(N) < 0.2] = -1                    # some envs have no attachment
+            mask = self.mask()
+            e = int(np.flatnonzero(mask)[0])                   # (whatever the draw: a masked env that carries something)
+            links[e, 0] = pool[rng.integers(len(pool))]
+            if nobj > 1:
+                links[e, 1] = -1
+            op.update(links=links, mask=mask)
+            if kind == 'attach':
+                rel = np.empty((N, nobj, 7), np.float32)
+                rel[..., :3] = rng.uniform(-0.12, 0.12, (N, nobj, 3))
+                rel[..., 3:] = rng.normal(size=(N, nobj, 4)) * rng.uniform(0.5, 2.0, (N, nobj, 1))      # (the library normalises)
+                op.update(rel=rel)
+        else:
+            assert kind == 'detach_all', kind
+        return op
+
+    def dynamics(self):
+        """posture_dynamics: the present state and K in {1, 3, 32} take turns, and so do velocities, accelerations and inverse=True"""
+        N, rng = self.N, self.rng
+        n = self.n_pd
+        self.n_pd += 1
+        op = dict(kind='posture_dynamics', compared=self.compared('posture_dynamics'))
+        draw = lambda K, s: np.ascontiguousarray(rng.uniform(-s, s, (N, K, 11)).astype(np.float32))
+        if n % 4 == 0:
+            op.update(postures=None, velocities=None, accelerations=draw(1, 5.0) if n % 8 else None, inverse=True)
+        else:
+            K, turn = int(Q_KS[n % 4 - 1]), n % 3
+            op.update(postures=self.postures(K), velocities=draw(K, 1.0) if turn != 1 else None, accelerations=draw(K, 5.0) if turn != 0 else None,
+                      inverse=turn == 2)
+        return op
+
+    def sweep(self, kind):
+        """carried_sweep / swept_clearance_refused: K cycles, segments a quarter of the way between two postures"""
+        K = int(Q_KS[(self.n_sweep + self.salt) % 3])
+        self.n_sweep += 1
+        a, b = self.postures(K), self.postures(K)
+        seg = np.ascontiguousarray(np.stack([a, a + np.float32(0.25) * (b - a)], axis=2))
+        return dict(kind=kind, compared=self.compared(kind), segments=seg, safety=float(np.float32((0.0, 0.01, 0.04)[self.n_sweep % 3])))
+
+
+def _command_program(seed, N, nobj, length):
+    """a command programme (the comment at C_MIN_LENGTH): its own generator and rng stream.  The ORDER of its units is written out
+    below, phase by phase, so that every condition of check_command_conditions holds by construction; the seed decides the order of
+    the state mutators within a phase, the order of the independent groups, every mask, index and value."""
+    if length < C_MIN_LENGTH:
+        raise ValueError("a command programme needs at least %d ops" % C_MIN_LENGTH)
+    rng = np.random.default_rng([int(seed), int(N), int(nobj), int(length), 2])
+    salt = int(seed) % 7
+    d = _CDraw(rng, N, nobj, salt=int(seed) % 4)
+    sit = Situation(N)
+    ops = []
+    n = dict(form=int(rng.integers(3)), carry=salt, any=salt, on=salt, off=salt, slot=0)
+
+    def emit(*more):
+        for op in more:
+            if op is not None:
+                sit.apply(op)
+                ops.append(op)
+
+    def form():
+        n['form'] += 1
+        return n['form'] % 3
+
+    def step(f):
+        return d.step_macro(form()) if f == 'm' else d.step(f)
+
+    def state(kind):
+        if kind in ('write_joints', 'write_poses'):
+            return dict(kind='write_state', parts=W_JOINT_POS if kind == 'write_joints' else W_OBJ_POSE, reset=False, fresh=False, rows=d.rows(), mask=d.mask())
+        op = d.mutator(kind)
+        if kind == 'load_snapshot':
+            op['slot'] = n['slot']          # (a slot that has been saved)
+        return op
+
+    def order():
+        """the eight state mutators in a seeded order, the device reset in front of the auto-reset (it finds young clocks)"""
+        o = [STATE_MUTATORS[i] for i in rng.permutation(len(STATE_MUTATORS))]
+        i, j = o.index('reset_dev'), o.index('episode_reset')
+        if i > j:
+            o[i], o[j] = o[j], o[i]
+        return o
+
+    def carry():
+        n['carry'] += 1
+        k = CARRY_QUERIES[n['carry'] % 4]
+        return d.query(k, d.compared(k))
+
+    def table(kind):
+        return dict(kind=kind, compared=d.compared(kind))
+
+    def obs(which):
+        """the next observer of a rota: 'any' needs nothing, 'on' attachments on, 'off' attachments off"""
+        n[which] += 1
+        i = n[which]
+        if which == 'on':
+            assert sit.attached
+            return (lambda: d.sweep('carried_sweep'), lambda: d.sweep('swept_clearance_refused'), carry, carry)[i % 4]()
+        if which == 'off':
+            assert not sit.attached
+            return d.sweep('carried_sweep') if i % 2 else d.dynamics()
+        return (d.dynamics, lambda: table('joint_torques'), lambda: table('external_wrenches'), lambda: table('attachments'))[i % 4]()
+
+    def pair(op, f, behind=None):
+        emit(op)
+        emit(step(f))
+        if behind:
+            emit(obs(behind))
+
+    def keep(nz):
+        return int(np.flatnonzero(nz)[0]) if nz.any() else None
+
+    def clear(kind, **kw):
+        return d.new(kind, keep=keep(sit.t_nz if kind == 'clear_joint_torques' else sit.w_nz), **kw)
+
+    # 1. plans: step_macro behind plan_macro, four times in a row with the same requests
+    emit(d.mutator('plan_macro'), *[d.step_macro(form(), hold=True) for _ in range(4)])
+    # 2. both tables and the attachments on; a snapshot and two checkpoints (restore takes the one before last) while they are set
+    pair(d.new('set_joint_torques'), 0, 'any')
+    pair(d.new('set_external_wrenches'), 1, 'any')
+    pair(d.new('attach'), 2, 'on')
+    sv = d.mutator('save_snapshot')
+    n['slot'] = sv['slot']
+    pair(sv, form(), 'any')
+    pair(dict(kind='checkpoint'), form(), 'on')
+    pair(dict(kind='checkpoint'), form())
+    emit(*[d.step(form()) for _ in range(length - C_MIN_LENGTH)])
+    # 3. everything on: a new mutator, step_macro, a state mutator, a step -- the state mutator with both tables non-zero, with
+    #    attachments on and directly behind a step_macro with plans in flight; the new mutator directly behind a step
+    news = ['set_joint_torques', 'set_external_wrenches', 'clear_joint_torques', 'clear_external_wrenches', 'torques_from_dynamics', 'attach',
+            'attach_capture', 'macro_invalidate']
+    news = news[salt % 8:] + news[:salt % 8]
+    for new, s in zip(news, order()):
+        emit(clear(new) if new.startswith('clear') else d.new(new), carry() if new == 'attach_capture' else None)
+        emit(step('m'), state(s), step(form()))
+    # 4. step_macro directly behind each state mutator
+    for i, s in enumerate(order()):
+        pair(state(s), 'm', ('on', 'any')[i % 2] if i % 4 != 3 else None)
+    # 5a. attach_capture directly behind five state mutators, a carry query directly behind every attach_capture
+    for i, s in enumerate(CAPTURE_BEHIND):
+        emit(state(s), d.new('attach_capture'), carry(), step(i % 3))
+    # 5b. a carry query directly behind the same five
+    for i, s in enumerate(CAPTURE_BEHIND):
+        emit(state(s), carry(), step(form()), obs('on') if i % 2 else None)
+    # 5c. independent groups in a seeded order; every group leaves both tables and the attachments on
+    def g_dynamics():
+        emit(state('fork_dev'), d.new('torques_from_dynamics'), step(0))
+        pair(d.new('torques_from_dynamics'), 1, 'any')
+        pair(d.new('torques_from_dynamics'), 2)
+
+    def g_tables():
+        pair(d.new('set_joint_torques', inplace=True), 1, 'any')
+        pair(d.new('set_joint_torques'), 2)
+        pair(d.new('set_external_wrenches', inplace=True), 0, 'on')
+        pair(d.new('set_external_wrenches'), 2)
+
+    def g_clear():
+        pair(clear('clear_joint_torques'), 0, 'any')
+        pair(clear('clear_external_wrenches'), 0)
+        pair(clear('clear_joint_torques'), 1, 'on')
+        pair(clear('clear_external_wrenches'), 1)
+
+    def g_macro():
+        pair(d.mutator('plan_macro'), 'm')       # (the mixed use: an env whose record equals its request keeps plan_macro's plan)
+        emit(d.filler('step_plan', form()), d.step_macro(form(), hold=True))
+        pair(d.new('macro_invalidate'), 0)
+        pair(d.new('macro_invalidate', unmasked=True), 1, 'any')
+        pair(d.new('macro_invalidate'), 2)
+
+    def g_detach():
+        for f in (0, 1, 2, 'm'):
+            pair(d.new('detach', keep=keep(sit.att)), f, 'on' if f in (0, 2) else None)
+        for k, f in enumerate((0, 1, 'm')):
+            pair(d.new('detach_all'), f, 'off' if f != 'm' else None)
+            if k < 2:
+                pair(d.new('attach'), f, 'on')
+        # the two float64 anchors: a given attach of every env, then the state a record defines
+        emit(anchor_attach(N, nobj, 0), dict(d.mutator('set_state'), anchor=True), step(form()))
+        emit(anchor_attach(N, nobj, 1), dict(kind='write_state', parts=15, reset=False, fresh=True, rows=d.rows(), mask=None, anchor=True), step(form()))
+
+    groups = [g_dynamics, g_tables, g_clear, g_macro, g_detach]
+    for i in rng.permutation(len(groups)):
+        groups[i]()
+    # 6. the feature-off road: the three unmasked clearing calls, then every state mutator once more
+    pair(d.new('clear_joint_torques', unmasked=True), 2)
+    pair(d.new('clear_external_wrenches', unmasked=True), 2)
+    pair(d.new('detach_all'), 2, 'off')
+    assert sit.all_off()
+    for i, s in enumerate(order()):
+        pair(state(s), form(), ('off', 'any')[i % 2] if i % 4 != 3 else None)
+    assert len(ops) == length, (len(ops), length)
+    return ops
+
+
 def is_anchor(op):
     """behind this op the state of every env is compose_state(op['rows']), known on the CPU"""
     return op['kind'] == 'set_state' or (op['kind'] == 'write_state' and op['parts'] == 15 and op['fresh'] and op['mask'] is None)
@@ -547,10 +999,138 @@ def check_query_conditions(ops, length, nobj):
     return dict(count={m: kinds.count(m) for m in muts | set(Q_OBSERVERS)})
 
 
-def program(seed, N, nobj, length, queries=False):
+def check_command_conditions(ops, length, N, nobj):
+    """what a command programme drawn for a handle of N envs and `nobj` objects holds, asserted from the records alone.  A `step`
+    below is a step or a step_macro unless a render form is asked for; `directly` means the neighbouring record.  One exception is
+    forced by the conditions themselves: a carry query stands directly behind EVERY attach_capture, so the step that follows an
+    attach_capture follows it behind that one read-only record."""
+    assert len(ops) == length >= C_MIN_LENGTH
+    kinds = [o['kind'] for o in ops]
+    muts = set(MUTATORS) | set(C_MUTATORS)
+    assert set(kinds) <= set(C_STEP_KINDS) | muts | set(C_OBSERVERS), set(kinds) - set(C_STEP_KINDS) - muts - set(C_OBSERVERS)
+    sit = Situation(N)
+    before, after = [], []                  # the situation in front of and behind every record
+    snap = lambda: dict(tables=sit.tables(), carrying=sit.carrying(), attached=sit.attached, in_flight=sit.in_flight(), off=sit.all_off(),
+                        t_on=sit.t_on, w_on=sit.w_on)
+    for o in ops:
+        before.append(snap())
+        sit.apply(o)
+        after.append(snap())
+    nxt = lambda i: ops[i + 1] if i + 1 < len(ops) else dict(kind=None)
+    is_carry = lambda i: kinds[i] in CARRY_QUERIES and before[i]['attached']
+    # every new mutator: directly followed by a step of each render form, and by a step_macro
+    for m in C_MUTATORS:
+        forms, macro = set(), False
+        for i, k in enumerate(kinds):
+            if k != m:
+                continue
+            j = i + 2 if m == 'attach_capture' and i + 1 < len(ops) and is_carry(i + 1) else i + 1
+            if j < len(ops) and kinds[j] == 'step':
+                forms.add(ops[j]['render'])
+            macro = macro or (j < len(ops) and kinds[j] == 'step_macro')
+        assert forms == set(RENDER_FORMS) and macro, (m, forms, macro)
+    for k in ('clear_joint_torques', 'clear_external_wrenches', 'macro_invalidate'):
+        assert {o['mask'] is None for o in ops if o['kind'] == k} == {False, True}, k
+    # the state mutators, each time directly followed by a step: with both tables non-zero, with attachments on, directly behind a
+    # step_macro with plans in flight, and once more with every feature off behind the unmasked clearing calls
+    seen = {s: set() for s in STATE_MUTATORS}
+    for i, o in enumerate(ops):
+        s = state_kind(o)
+        if s is None or nxt(i)['kind'] not in ('step', 'step_macro'):
+            continue
+        b = before[i]
+        seen[s] |= {name for name, ok in (('tables', b['tables']), ('carrying', b['carrying']), ('off', b['off'] and nxt(i)['kind'] == 'step'),
+                                          ('in_flight', i > 0 and kinds[i - 1] == 'step_macro' and b['in_flight']),
+                                          ('macro_behind', nxt(i)['kind'] == 'step_macro')) if ok}
+    for s, got in seen.items():
+        assert got == {'tables', 'carrying', 'in_flight', 'off', 'macro_behind'}, (s, got)
+    assert all(any(k == c for k in kinds[:max(i for i, a in enumerate(after) if a['off'])]) for c in ('clear_joint_torques', 'clear_external_wrenches', 'detach_all'))
+    # a carry query and an attach_capture directly behind five state mutators and a step; a carry query behind every attach_capture
+    behind = {'carry': set(), 'attach_capture': set()}
+    for i in range(1, len(ops)):
+        what = 'carry' if is_carry(i) else kinds[i] if kinds[i] == 'attach_capture' else None
+        if what:
+            behind[what].add('step' if kinds[i - 1] in C_STEP_KINDS else state_kind(ops[i - 1]))
+        if kinds[i - 1] == 'attach_capture':
+            assert is_carry(i), i
+    for what, got in behind.items():
+        assert got >= set(CAPTURE_BEHIND) | {'step'}, (what, got)
+    assert {kinds[i] for i in range(len(ops)) if is_carry(i)} == set(CARRY_QUERIES)
+    # carried_sweep with attachments on and off; swept_clearance refuses only while they are on; every observer compared and silent
+    assert {before[i]['attached'] for i, k in enumerate(kinds) if k == 'carried_sweep'} == {False, True}
+    assert all(before[i]['attached'] for i, k in enumerate(kinds) if k == 'swept_clearance_refused') and 'swept_clearance' not in kinds
+    for k in C_OBSERVERS:
+        assert {o['compared'] for o in ops if o['kind'] == k} == {False, True}, k
+    pd = [o for o in ops if o['kind'] == 'posture_dynamics']
+    assert {None if o['postures'] is None else o['postures'].shape[1] for o in pd} == {None} | set(Q_KS)
+    assert any(o['velocities'] is not None for o in pd) and any(o['accelerations'] is not None for o in pd) and {o['inverse'] for o in pd} == {False, True}
+    assert all(o['velocities'] is None for o in pd if o['postures'] is None)
+    # torques_from_dynamics directly behind a step and directly behind a fork_dev
+    tfd = {kinds[i - 1] for i, k in enumerate(kinds) if k == 'torques_from_dynamics'}
+    assert 'fork_dev' in tfd and tfd & set(C_STEP_KINDS), tfd
+    # step_macro: behind plan_macro, behind macro_invalidate, directly behind each state mutator (above), three times in a row unchanged
+    sm = [i for i, k in enumerate(kinds) if k == 'step_macro']
+    assert any(kinds[i - 1] == 'plan_macro' for i in sm if i) and any(kinds[i - 1] == 'plan_macro' and before[i - 1]['in_flight'] for i in sm if i)
+    assert any(kinds[i - 1] == 'macro_invalidate' for i in sm if i) and any(kinds[i - 1] == 'step_plan' for i in sm if i)
+    same = lambda a, b: np.array_equal(a['macro'].view(np.uint32), b['macro'].view(np.uint32))
+    assert any(kinds[i + 1] == kinds[i + 2] == 'step_macro' and same(ops[i], ops[i + 1]) and same(ops[i], ops[i + 2]) for i in sm if i + 2 < len(ops))
+    assert any(np.isnan(ops[i]['macro']).any() for i in sm) and {ops[i]['render'] for i in sm} == set(RENDER_FORMS)
+    # ... a -0.0 where the record has 0.0 in an env that is not idle, and it does not re-plan
+    model, negzero = MacroModel(N), 0
+    for o in ops:
+        if o['kind'] == 'step_macro':
+            hit = (np.signbit(o['macro']) & (o['macro'] == 0) & (model.record == 0) & ~np.signbit(model.record)).any(axis=1) & (o['idle'] == 0)
+        model.apply(o)
+        if o['kind'] == 'step_macro':
+            negzero += int((hit & (model.replanned == 0)).sum())
+    assert negzero > 0
+    # snapshots and checkpoints while tables, attachments and records are set; loads and restores after those have changed
+    changed = lambda i, j: any(k in C_MUTATORS or k == 'step_macro' for k in kinds[i + 1:j])
+    for save, load in (('save_snapshot', 'load_snapshot'), ('checkpoint', 'restore')):
+        at = [i for i, k in enumerate(kinds) if k == save]
+        assert at and all(before[i]['tables'] and before[i]['carrying'] and before[i]['in_flight'] for i in at), save
+        for j, k in enumerate(kinds):
+            if k == load:
+                prev = [i for i in at if i < j and (save == 'checkpoint' or ops[i]['slot'] == ops[j]['slot'])]
+                assert prev and changed(prev[-1], j), (load, j)
+    assert kinds.count('checkpoint') >= 2 and min(i for i, k in enumerate(kinds) if k == 'restore') > sorted(i for i, k in enumerate(kinds) if k == 'checkpoint')[1]
+    for i, k in enumerate(kinds):
+        assert k != 'episode_reset' or 'reset_dev' in kinds[:i]
+    # the draws: masks are never all-clear; zero and -0.0 rows inside the mask; wrench rows for objects a smaller handle lacks; the
+    # in-place write once per table, with the feature on; links on finger and arm links, free objects, envs without attachment
+    for o in ops:
+        for key in ('mask', 'flags', 'idle'):
+            if o.get(key) is not None:
+                assert np.asarray(o[key]).any(), (o['kind'], key)
+    for kind, key, on in (('set_joint_torques', 'torques', 't_on'), ('set_external_wrenches', 'wrenches', 'w_on')):
+        recs = [(i, o) for i, o in enumerate(ops) if o['kind'] == kind]
+        assert sum(o['inplace'] for _, o in recs) == 1 and all(before[i][on] for i, o in recs if o['inplace'])
+        rows = [o[key][o['mask'] != 0].reshape(int((o['mask'] != 0).sum()), -1) for _, o in recs]
+        assert any((r == 0).all(axis=1).any() for r in rows) and any(np.signbit(r).any() for r in rows) and all(np.isfinite(r).all() for r in rows)
+        top = max(float(np.abs(o[key]).max()) for _, o in recs)
+        assert top <= 5.0, (kind, top)
+    assert all(o['wrenches'].shape == (N, N_WRENCH_ROWS, 6) and o['wrenches'][:, 11 + nobj:].any() == (nobj < 3) for o in ops if o['kind'] == 'set_external_wrenches')
+    att = [o for o in ops if o['kind'] in ('attach', 'attach_capture')]
+    pool = set(FINGER_LINKS + ARM_LINKS)
+    assert all(o['links'].shape == (N, nobj) and set(o['links'][o['links'] >= 0].tolist()) <= pool for o in att)
+    used = set().union(*[set(o['links'][o['links'] >= 0].tolist()) for o in att])
+    assert used & set(FINGER_LINKS) and used & set(ARM_LINKS)
+    assert any((o['links'] < 0).all(axis=1).any() for o in att) and (nobj == 1 or any(((o['links'] < 0).any(axis=1) & (o['links'] >= 0).any(axis=1)).any() for o in att))
+    assert all(('rel' in o) == (o['kind'] == 'attach') for o in att)
+    # the anchors: a set_state and a full write_state, each directly behind its attach of every env
+    anchors = [i for i, o in enumerate(ops) if is_command_anchor(o)]
+    assert {kinds[i] for i in anchors} == {'set_state', 'write_state'} and len(anchors) == 2
+    assert all(ops[i - 1].get('anchor') and kinds[i - 1] == 'attach' and ops[i - 1]['mask'] is None for i in anchors)
+    return dict(count={k: kinds.count(k) for k in sorted(set(kinds))})
+
+
+def program(seed, N, nobj, length, queries=False, commands=False):
     """list of `length` op records (dicts with a 'kind'); the same arguments give the same programme"""
+    assert not (queries and commands)
     if queries:
         return _query_program(seed, N, nobj, length)
+    if commands:
+        return _command_program(seed, N, nobj, length)
     if length < MIN_LENGTH:
         raise ValueError("a programme needs at least %d ops" % MIN_LENGTH)
     rng = np.random.default_rng([int(seed), int(N), int(nobj), int(length)])
@@ -586,7 +1166,7 @@ def program(seed, N, nobj, length, queries=False):
 
 
 def is_step(op):
-    return op['kind'] in STEP_KINDS
+    return op['kind'] in C_STEP_KINDS
 
 
 def render_form(op):
@@ -683,6 +1263,20 @@ def torch_device(a):
     return t
 
 
+def torch_copy_in_place(env, name, table, mask):
+    """the rows of `table` (a CUDA tensor) whose mask byte is set (None: all) into the handle's zero-copy view `name`, in the
+    library's stream order: behind everything the library has enqueued, complete before its next call"""
+    import torch
+    env.sync()
+    view = torch.from_dlpack(getattr(env, name))
+    if mask is None:
+        view.copy_(table)
+    else:
+        on = mask != 0
+        view[on] = table[on]
+    torch.cuda.synchronize()
+
+
 class Session:
     """One handle that executes op records along a road.  `to_device` turns a numpy array into device memory (a CUDA torch tensor;
     the recording fake of the CPU test passes its own marker).  Device arguments are kept alive until `release()`: the library
@@ -701,6 +1295,12 @@ class Session:
         self.points = (np.array([8], np.int32), np.zeros((1, 3), np.float32))
         self.max_distance, self.n_rays = None, 0
         self.last = {}                      # result buffers (FAMILY) -> the query record whose call wrote them last
+        # the command programmes: whether the attachments are on, the macro model (record, position, replanned) with the envs that
+        # the last op re-planned, the arrays of the compared table read-backs, the refusals met; `copy_in_place` writes rows through
+        # a zero-copy view, `strict`: the handle is a real one (a fake refuses nothing and has no buffers)
+        self.attached, self.macro, self.macro_now = False, MacroModel(self.N), np.zeros(self.N, np.uint8)
+        self.read, self.refusals, self.commands = {}, 0, False      # (`commands`: a comparison looks at the tables and the macro buffers too)
+        self.copy_in_place, self.strict = torch_copy_in_place, to_device is torch_device
 
     def setup(self):
         """what both handles get behind the warm-up: the ray table, snapshot slots, goals, the episode rule, a first checkpoint"""
@@ -735,6 +1335,7 @@ class Session:
         return int(t.data_ptr())
 
     def apply(self, op):
+        self.macro_now = np.zeros(self.N, np.uint8)      # (the envs that THIS op re-plans: a step_macro sets them)
         getattr(self, '_' + op['kind'])(op)
 
     # ---- steps
@@ -758,6 +1359,7 @@ class Session:
         nat.check(self.env.L.rr_step(self.env.h, cmd.ctypes.data, 0, int(op['render']), flags.ctypes.data if flags is not None else None))
 
     def _step_plan(self, op):
+        self.macro.apply(op)
         self.env.step_plan(self._render_arg(op), idle=op['idle'])
 
     def _render(self, op):
@@ -845,6 +1447,7 @@ class Session:
         self.env.restore(self.ckpts[-2])                 # the checkpoint before last
 
     def _plan_macro(self, op):
+        self.macro.apply(op)
         self.env.plan_macro(op['macro'], op['mask'])
 
     def _set_env_goals(self, op):
@@ -1028,6 +1631,102 @@ class Session:
 
     _posture_ik_present = _posture_ik
 
+    # ---- the command programmes: tables, attachments, macro actions decided on the device
+    def _mask_arg(self, op):
+        return None if op['mask'] is None else op['mask'] if self.road == 'host' else self._d(op['mask'])
+
+    def _set_table(self, op, key, call, buffer):
+        """A: a CUDA tensor and a device mask, or (`inplace`) the same rows written through the zero-copy view of the table, in the
+        library's stream order; B: host arrays"""
+        env = self.env
+        if self.road == 'host':
+            getattr(env, call)(op[key], op['mask'])
+        elif op['inplace']:
+            self.copy_in_place(env, buffer, self._d(op[key]), self._mask_arg(op))
+        else:
+            getattr(env, call)(self._d(op[key]), self._mask_arg(op))
+
+    def _set_joint_torques(self, op):
+        self._set_table(op, 'torques', 'set_joint_torques', 'joint_torque_buffer')
+
+    def _set_external_wrenches(self, op):
+        self._set_table(op, 'wrenches', 'set_external_wrenches', 'external_wrench_buffer')
+
+    def _clear_joint_torques(self, op):
+        self.env.set_joint_torques(None, self._mask_arg(op))
+
+    def _clear_external_wrenches(self, op):
+        self.env.set_external_wrenches(None, self._mask_arg(op))
+
+    def _torques_from_dynamics(self, op):
+        """A: the [N, 1, 11] bias view of posture_dynamics() straight into set_joint_torques -- no copy, no wait; B: the host array"""
+        self._asks(op)
+        if self.road == 'host':
+            self.env.set_joint_torques(self.env.posture_dynamics(host=True)['bias'][:, 0], op['mask'])
+        else:
+            self.env.set_joint_torques(self.env.posture_dynamics()['bias'], self._mask_arg(op))
+
+    def _attach(self, op):
+        self.env.attach_objects(op['links'], op['rel'], op['mask'])
+        self.attached = True
+
+    def _attach_capture(self, op):
+        self.env.attach_objects(op['links'], None, op['mask'])
+        self.attached = True
+
+    def _detach(self, op):
+        self.env.detach_objects(op['mask'])
+
+    def _detach_all(self, op):
+        self.env.detach_objects()
+        self.attached = False
+
+    def _macro_invalidate(self, op):
+        self.macro.apply(op)
+        self.env.macro_invalidate(self._mask_arg(op))
+
+    def _step_macro(self, op):
+        self.macro.apply(op)
+        self.macro_now = self.macro.replanned.copy()
+        if self.road == 'host':
+            self.env.step_macro_device(op['macro'], idle=op['idle'], render=self._render_arg(op))
+        else:
+            self.env.step_macro_device(self._d(op['macro']), idle=self._d(op['idle']), render=self._render_arg(op))
+
+    def _posture_dynamics(self, op):
+        if self._asks(op):
+            arg = lambda a: None if a is None else self._q(a)
+            self.env.posture_dynamics(arg(op['postures']), arg(op['velocities']), arg(op['accelerations']), inverse=op['inverse'])
+
+    def _carried_sweep(self, op):
+        if self._asks(op):
+            self.env.carried_sweep(self._q(op['segments']), safety=op['safety'])
+
+    def _sweep_bytes(self):
+        return [np.asarray(self.env.sweep_buffer(i, host=True)).tobytes() for i in range(4)] if self.strict else None
+
+    def _swept_clearance_refused(self, op):
+        """while attachments are on the call raises RR_EINVAL and changes no buffer (`strict`: on a real handle)"""
+        if not self._asks(op):
+            return
+        before = self._sweep_bytes()
+        try:
+            self.env.swept_clearance(self._q(op['segments']), safety=op['safety'])
+        except RuntimeError as e:
+            assert 'error -1' in str(e) and 'attach' in str(e), e
+            self.refusals += 1
+        else:
+            assert not self.strict, "swept_clearance did not refuse while attachments are on"
+        assert self._sweep_bytes() == before, "a refused swept_clearance changed a sweep buffer"
+
+    def _read_back(self, op):
+        """the table read-backs: a compared record's arrays are kept for the comparison (`read`)"""
+        if self._asks(op):
+            got = getattr(self.env, op['kind'])()
+            self.read[op['kind']] = (op, got if isinstance(got, tuple) else (got,))
+
+    _joint_torques = _external_wrenches = _attachments = _read_back
+
 
 ANCHOR_ENVS = 4
 
@@ -1044,6 +1743,34 @@ def anchor_references(op, nobj, probe_q):
     return st, pairs, nd.reference(st, pairs), nd.reference(npo.rows(st, probe_q['postures'][:len(st)]), pairs)
 
 
+def command_anchor_references(attach, op, nobj, probe_q, rel=None):
+    """The float64 restatements behind an anchor of a command programme (is_command_anchor), for the first ANCHOR_ENVS envs, the
+    default pair table, the attach record in force and the probe's postures.  `rel`: the poses the handle reads back (attachments();
+    None: the record's own, the quaternion normalised).  Returns the state, the pairs, the links and poses padded to three objects,
+    numpy_distance.reference on the carried rows (tests/numpy_carry.py) at the present joints and at the postures, which items have a
+    shape of an attached object, and the numpy_dynamics.reference of the present-state form."""
+    from tests import numpy_carry as nc
+    from tests import numpy_distance as nd
+    from tests import numpy_dynamics as ndy
+    names = nd.names()
+    pairs = np.array([(names[x], names[y]) for x, y in default_pairs(nobj)], np.int32)
+    st = compose_state(op['rows'], nobj)[:ANCHOR_ENVS]
+    n = len(st)
+    links = np.full((n, 3), -1, np.int32)
+    links[:, :nobj] = attach['links'][:n]
+    given = np.asarray(attach['rel'] if rel is None else rel, np.float64)[:n]
+    rel3 = np.zeros((n, 3, 7))
+    rel3[..., 6] = 1.0
+    rel3[:, :nobj] = given
+    rel3[..., 3:] /= np.linalg.norm(rel3[..., 3:], axis=-1, keepdims=True)
+    po = probe_q['postures'][:n]
+    now = np.ascontiguousarray(st[:, None, :11])
+    return dict(state=st, pairs=pairs, links=links, rel=rel3,
+                now=nd.reference(nc.carried_rows(st, now, links, rel3), pairs), po=nd.reference(nc.carried_rows(st, po, links, rel3), pairs),
+                att_now=nc.attached_items(links, pairs, 1), att_po=nc.attached_items(links, pairs, po.shape[1]),
+                dynamics=ndy.reference(now, np.ascontiguousarray(st[:, None, 11:22])))
+
+
 def probe_arguments(N, nobj):
     """the fixed arguments of the queries a comparison calls (tests/test_gpu_session.py), as host arrays: K = 2 postures, 2 segments
     and 2 IK targets per env -- the tool poses of two postures at the point of a fresh handle -- with their seeds"""
@@ -1057,7 +1784,9 @@ def probe_arguments(N, nobj):
     seeds[..., :7] += d.rng.uniform(-0.3, 0.3, seeds[..., :7].shape).astype(np.float32)
     Re, x, _ = npk.tool_frame(goals.astype(np.float64))
     targets = np.ascontiguousarray(np.concatenate([x, mat_to_quat(Re)], -1).astype(np.float32))
-    return dict(postures=po, segments=seg, targets=targets, seeds=seeds)
+    # (drawn behind everything above: the probe of the sessions from before the command programmes is what it was)
+    qd, qdd = (np.ascontiguousarray(d.rng.uniform(-s, s, po.shape).astype(np.float32)) for s in (1.0, 5.0))
+    return dict(postures=po, segments=seg, targets=targets, seeds=seeds, velocities=qd, accelerations=qdd)
 
 
 def run(env, ops, road, to_device=torch_device, setup=True):

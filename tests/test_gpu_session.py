@@ -39,7 +39,26 @@ are held against the float64 restatements of tests/numpy_distance.py, numpy_post
 the bounds of their own GPU tests (`_anchor`).  Invariants asserted on the way: the candidate queries (posture_kinematics, posture_ik
 with seeds) give the same bits at every comparison between two set_kinematic_points; posture_ik without seeds changes only in envs
 whose joints changed; the three table mutators move query and ray outputs and nothing else; a write of the object poses alone, or of
-the joints alone, moves every probe output that reads them."""
+the joints alone, moves every probe output that reads them.
+
+The command-side state.  Two more sessions, c70 and c5, run a COMMAND programme (session_program.program(..., commands=True), 212
+ops): the joint torque and external wrench tables -- set from CUDA tensors with device masks, once per table through the zero-copy
+view, cleared under a mask and without one, and `torques_from_dynamics`: the bias view of posture_dynamics() passed straight into
+set_joint_torques with no copy and no wait --, the attachments (given poses, the capture kernel, masked detach, the unmasked detach)
+and the device-resident macro actions (step_macro with device requests and idle masks, macro_invalidate) stand between the steps of
+the default handle; B gets host arrays.  Each of reset, fork, load_snapshot, restore, the auto-reset, set_state and the masked
+writes of the joints and of the object poses stands with both tables non-zero, with attachments on and directly behind a step_macro
+with plans in flight, with a step_macro behind it, and once more behind the three unmasked clearing calls (the feature-off road).  A
+comparison of a command session looks at everything above and at the three tables, the macro request record, positions and
+`replanned` bytes, the plans of the envs that the op re-planned and of four others, posture_dynamics at the present state and at the
+probe's rows, and carried_sweep; while attachments are on the probe's posture_clearance, signed_distance and gradient run their
+_carry kernels and swept_clearance, which refuses then, is left out (`swept_clearance_refused` records assert the refusal and that no
+buffer changed).  With attachments off a carried_sweep record's four buffers are compared with a swept_clearance of the same
+segments on the same handle.  A and B both run k_macro_decide, so A's record, positions and `replanned` bytes are ALSO held against
+the Session's numpy model of the header's decision rule, behind every compared op: a record that followed the source env of a fork
+would differ from it.  The float64 anchor of a command session (`_command_anchor`): behind a set_state and a full write_state, each
+directly behind an attach of known poses, posture_dynamics() against tests/numpy_dynamics.py and the carried posture_clearance and
+signed_distance against tests/numpy_carry.py, within the bounds of those modules' own GPU tests."""
 import hashlib
 import time
 
@@ -75,7 +94,7 @@ def _make(monkeypatch, env_vars, *args, **kw):
 def _program(name):
     if name not in _cache:
         seed, N, nobj, _, _, length = sp.SESSIONS[name]
-        _cache[name] = sp.program(seed, N, nobj, length, queries=name in sp.QUERY_SESSIONS)
+        _cache[name] = sp.program(seed, N, nobj, length, queries=name in sp.QUERY_SESSIONS, commands=name in sp.COMMAND_SESSIONS)
     return _cache[name]
 
 
@@ -86,7 +105,7 @@ def _took(t0):
 
 def _silent(op):
     """an observer that B does not make: no comparison behind it, the next one shows whether A's call changed anything"""
-    if op['kind'] in sp.Q_OBSERVERS:
+    if op['kind'] in sp.Q_OBSERVERS + sp.C_OBSERVERS:
         return not op['compared']
     return op['kind'] in sp.OBSERVERS and op['kind'] != 'episode_peek'
 
@@ -148,12 +167,36 @@ def _queries(env, sess, probe):
              lambda: env.signed_distance(q['postures'], host=True), grad, lambda: env.swept_clearance(q['segments'], host=True),
              lambda: env.posture_kinematics(q['postures'], host=True), lambda: env.posture_ik(q['targets'], q['seeds'], **ik),
              lambda: env.posture_ik(q['targets'], **ik))
-    return {name + '.' + k: np.array(v) for name, call in zip(QUERIES, calls) for k, v in call().items()}
+    # (a command session: swept_clearance refuses while attachments are on -- carried_sweep, below, is the edge check then -- and the
+    # three posture queries of this probe run their _carry kernels)
+    return {name + '.' + k: np.array(v) for name, call in zip(QUERIES, calls) if not (sess.attached and name == 'swept_clearance(seg)')
+            for k, v in call().items()}
+
+
+C_QUERIES = ('posture_dynamics()', 'posture_dynamics(po, qd, qdd, inverse)', 'carried_sweep(seg)')
+
+
+def _command_fields(env, sess, probe):
+    """what a comparison of a command session looks at besides: the three tables, the macro buffers -- the plans of the envs that this
+    op re-planned (the Session's model says which) and of the first ANCHOR_ENVS --, and the probe of the new queries"""
+    q = probe.q if sess.road == 'host' else probe.q_dev
+    d = {'table.joint_torques': env.joint_torques(), 'table.external_wrenches': env.external_wrenches()}
+    d['table.attach_links'], d['table.attach_rel'] = env.attachments()
+    for name in ('request', 'position', 'replanned'):
+        d['macro.' + name] = env.macro_buffer(name, host=True)
+    sel = np.union1d(np.flatnonzero(sess.macro_now), np.arange(min(sess.N, sp.ANCHOR_ENVS)))
+    d['macro.plan'] = env.macro_buffer('plan', host=True)[sel]
+    t0 = time.perf_counter()
+    calls = (lambda: env.posture_dynamics(host=True), lambda: env.posture_dynamics(q['postures'], q['velocities'], q['accelerations'], inverse=True, host=True),
+             lambda: env.carried_sweep(q['segments'], host=True))
+    d.update({name + '.' + k: np.array(v) for name, call in zip(C_QUERIES, calls) for k, v in call().items()})
+    _spent['queries'] += time.perf_counter() - t0
+    return d
 
 
 _RAW = {'dist': ('distance_buffer', nat.DIST_FIELDS), 'pc': ('posture_buffer', nat.PC_FIELDS), 'sd': ('signed_buffer', nat.SD_FIELDS),
         'sg': ('signed_gradient_buffer', nat.SG_FIELDS), 'sw': ('sweep_buffer', nat.SW_FIELDS), 'pk': ('posture_kinematics_buffer', nat.PK_FIELDS),
-        'pik': ('posture_ik_buffer', nat.PIK_FIELDS)}
+        'pik': ('posture_ik_buffer', nat.PIK_FIELDS), 'pd': ('posture_dynamics_buffer', nat.PD_FIELDS)}
 
 
 def _results(env, sess, families):
@@ -163,6 +206,8 @@ def _results(env, sess, families):
     for f in families:
         present = sess.last[f]['kind'] == 'signed_distance'
         for name in _RAW[f][1]:
+            if (f, name) == ('pd', 'mass_inverse') and not sess.last[f]['inverse']:
+                continue                    # (written with inverse=True only: else it holds an earlier call's bytes, and A makes more calls than B)
             if (f, name) not in (('sd', 'points'), ('sg', 'pair_gradient')) or (f == 'sd' and present):
                 d[f + '.' + name] = getattr(env, _RAW[f][0])(name, host=True)
     return d
@@ -186,6 +231,8 @@ def _collect(env, sess, probe, img_envs, contact_envs, images=True):
     t0 = time.perf_counter()
     d.update(_queries(env, sess, probe))
     _spent['queries'] += time.perf_counter() - t0
+    if sess.commands:
+        d.update(_command_fields(env, sess, probe))
     for k, v in env.kinematic_observations(host=True).items():
         d['kinematic.' + k] = v
     for k, v in env.contact_observations(host=True).items():
@@ -250,8 +297,10 @@ class _Twin:
         _warm_up(self.envs, N)
         self.sa = sp.Session(self.A, road_a)
         self.sb = sp.Session(self.B, 'host') if twin else None
+        self.commands = name in sp.COMMAND_SESSIONS
         for s in (self.sa, self.sb):
             if s is not None:
+                s.commands = self.commands
                 s.setup()
         self.mirror, self.img_mirror = self.A.map_observations(), self.A.map_images()
         self.probe = _Probe(N, nobj)
@@ -349,6 +398,76 @@ def _compare_results(tw, i, what):
     tw.sb.last.clear()
 
 
+def _compare_read_backs(tw, i):
+    """the arrays of a compared table read-back (joint_torques, external_wrenches, attachments), as the record's own calls returned them"""
+    for kind, (op, got) in tw.sa.read.items():
+        if kind in tw.sb.read and tw.sb.read[kind][0] is op:
+            _assert_equal({'%s[%d]' % (kind, j): x for j, x in enumerate(got)}, {'%s[%d]' % (kind, j): x for j, x in enumerate(tw.sb.read[kind][1])},
+                          i, tw.ops, "A against B, the read-back of the record")
+    tw.sa.read.clear()
+    tw.sb.read.clear()
+
+
+def _forwards_to_swept_clearance(tw, op, i):
+    """With attachments off rr_carried_sweep IS rr_swept_clearance: the four buffers of the record's call against those of a
+    swept_clearance of the same segments on the same handle, bit for bit."""
+    A = tw.A
+    mine = [A.sweep_buffer(j, host=True) for j in range(len(nat.SW_FIELDS))]
+    A.swept_clearance(tw.sa._q(op['segments']), safety=op['safety'])
+    for name, x, y in zip(nat.SW_FIELDS, mine, [A.sweep_buffer(j, host=True) for j in range(len(nat.SW_FIELDS))]):
+        bad = _differing(x, y)
+        assert bad.size == 0, "%s: carried_sweep with attachments off: buffer %s differs from swept_clearance's in envs %s" % (_where(i, tw.ops), name, bad[:16].tolist())
+
+
+def _against_the_macro_model(tw, a, i):
+    """A's request record, plan positions and `replanned` bytes against the Session's numpy model of the header's decision rule (A and
+    B both run k_macro_decide: the model is the independent reference), behind every compared op -- no state mutator may move them"""
+    m = tw.sa.macro
+    for name, want in (('request', m.record), ('position', m.position), ('replanned', m.replanned)):
+        bad = _differing(a['macro.' + name], want)
+        assert bad.size == 0, "%s: A's RR_MACRO_%s differs from the model of the decision rule in envs %s: %s against %s" % (
+            _where(i, tw.ops), name.upper(), bad[:16].tolist(), a['macro.' + name][bad[:4]].tolist(), want[bad[:4]].tolist())
+
+
+def _command_anchor(tw, attach, op, a, i, figures):
+    """Behind the set_state and the full write_state of a command programme the state is the record's and the attach record in front
+    of it is in force: for the first ANCHOR_ENVS envs, posture_dynamics() against tests/numpy_dynamics.py within that module's
+    ceilings (a ratio of at most 1), and the probe's carried posture_clearance(po), signed_distance(po) and signed_distance() against
+    tests/numpy_carry.py on the poses the handle reads back -- items with a shape of an attached object within test_gpu_carry.CEIL_D,
+    the others within the siblings' bounds, every status the reference's.  No item is set aside: the reference decides them all
+    (tests/test_session_program.py)."""
+    from tests import numpy_dynamics as ndy
+    from tests.test_gpu_carry import CEIL_D
+    from tests.test_gpu_distance import TOL as TOL_DISTANCE
+    from tests.test_gpu_posture_query import TOL as TOL_POSTURE
+    from tests.test_gpu_signed_distance import TOL_SD
+    where, n, nobj = _where(i, tw.ops), min(sp.ANCHOR_ENVS, tw.N), tw.sa.nobj
+    assert attach.get('anchor') and attach['kind'] == 'attach' and (a['table.attach_links'] == attach['links']).all(), where
+    assert (tw.A.distance_pairs()[1] == 0.0) and len(tw.A.distance_pairs()[0]) == len(sp.default_pairs(nobj)), where
+    cols = sp.part_columns(15, nobj)
+    assert (_bits(a['state'][:, cols]) == _bits(sp.compose_state(op['rows'], nobj)[:, cols])).all(), "%s: the state is not the record's" % where
+    r = sp.command_anchor_references(attach, op, nobj, tw.probe.q, rel=a['table.attach_rel'])
+    fig = {}
+    scale = ndy.scales(r['dynamics'])
+    for k in ('mass_matrix', 'gravity', 'bias', 'torque'):
+        fig['dynamics_' + k] = float(ndy.row_ratios(a['posture_dynamics().' + k][:n], r['dynamics'], scale, k).max())
+        assert fig['dynamics_' + k] <= 1.0, (where, k, fig)
+    for call, key, clip in (('posture_clearance(po)', 'po', True), ('signed_distance(po)', 'po', False), ('signed_distance()', 'now', False)):
+        ref, att = r[key], r['att_' + key]
+        assert ref['decided'].all() and att.any() and not att.all(), (where, call)
+        d = a[call + '.pair_distance'][:n].reshape(att.shape).astype(np.float64)
+        err = np.abs(d - (np.maximum(ref['d'], 0.0) if clip else ref['d']))
+        fig[call + ' attached'], fig[call + ' others'] = float(err[att].max()), float(err[~att].max())
+        wrong = int((a[call + '.pair_status'][:n].reshape(att.shape) != ref['expect']).sum())
+        print("anchor %s %s %s: attached items %d, error %.3g (bound %.3g); others %d, error %.3g (bound %.3g); status mismatches %d"
+              % (tw.name, where.split(';')[0], call, att.sum(), err[att].max(), CEIL_D, (~att).sum(), err[~att].max(), max(TOL_POSTURE, TOL_SD, TOL_DISTANCE), wrong))
+        assert err[att].max() <= CEIL_D and err[~att].max() <= max(TOL_POSTURE, TOL_SD, TOL_DISTANCE) and wrong == 0, (where, call, fig, wrong)
+    print("anchor %s %s: %s" % (tw.name, where.split(';')[0], {k: float('%.3g' % v) for k, v in fig.items()}))
+    for k, v in fig.items():
+        figures[k] = max(figures.get(k, 0.0), v)
+    figures['anchors'] = figures.get('anchors', 0) + 1
+
+
 def _run_twin(tw, counts=None, figures=None):
     """the programme on A and B with a comparison behind every op; returns the number of comparisons"""
     ops, compared = tw.ops, 0
@@ -358,10 +477,19 @@ def _run_twin(tw, counts=None, figures=None):
     for i, op in enumerate(ops):
         tw.sa.apply(op)
         tw.sb.apply(op)
+        if op['kind'] == 'carried_sweep' and not tw.sa.attached:
+            _forwards_to_swept_clearance(tw, op, i)
         if _silent(op):
             continue                        # B made no call: the next comparison shows whether A's changed anything
         _compare_results(tw, i, "A against B")
+        _compare_read_backs(tw, i)
         a = tw.collect_a()
+        if tw.commands:
+            _against_the_macro_model(tw, a, i)
+            if counts is not None and op['kind'] == 'step_macro':
+                counts['replans'] += int(a['macro.replanned'].sum())
+            if figures is not None and sp.is_command_anchor(op):
+                _command_anchor(tw, ops[i - 1], op, a, i, figures)
         stepped = sp.is_step(op)
         _assert_equal(a, tw.collect_b(stepped), i, ops, "A against B", tw.envs_of)
         if not stepped:
@@ -378,7 +506,7 @@ def _run_twin(tw, counts=None, figures=None):
                 if k.startswith('posture_ik(targets).') and same.any():
                     bad = _differing(a[k][same], before[k][same])
                     assert bad.size == 0, "%s: %s changed in envs whose joints did not: %s" % (_where(i, ops), k, np.flatnonzero(same)[bad][:16].tolist())
-        if figures is not None and sp.is_anchor(op):
+        if figures is not None and sp.is_anchor(op) and not tw.commands:
             _anchor(tw, op, a, i, figures)
         compared += 1
         before = a
@@ -489,6 +617,39 @@ def test_q5_against_the_plain_twin(monkeypatch):
     _query_session(monkeypatch, 'q5')
 
 
+def _command_session(monkeypatch, name):
+    t0 = time.perf_counter()
+    figures = {}
+    counts = dict(heavy=0, refused=0, auto_resets=0, partial_auto_resets=0, replans=0)
+    tw = _Twin(monkeypatch, name)
+    n = _run_twin(tw, counts, figures)
+    refusals = (tw.sa.refusals, tw.sb.refusals)
+    tw.close()
+    print("session %s: coverage %s; %d compared ops of %d; swept_clearance refused %d times on A, %d on B; anchors: worst figures %s; %s"
+          % (name, counts, n, len(tw.ops), refusals[0], refusals[1], {k: float('%.3g' % v) for k, v in figures.items()}, _took(t0)))
+    assert figures['anchors'] == sum(sp.is_command_anchor(o) for o in tw.ops) == 2
+    assert counts['auto_resets'] > 0 and counts['replans'] > 0 and refusals[0] > 0 and refusals[1] > 0, (counts, refusals)
+    return counts
+
+
+def test_c70_against_the_plain_twin(monkeypatch):
+    """70 envs, 3 objects, 64 x 64, the command programme: joint torques, external wrenches, attachments, the capture, macro requests
+    and macro_invalidate between the steps of the default handle -- device tables, masks, requests and idle masks, the bias view of
+    posture_dynamics() straight into set_joint_torques, once per table a write through the zero-copy view -- against host arrays on
+    the plain road.  Every state mutator stands with both tables non-zero, attachments on and plans in flight, and once more with
+    every feature off.  A's macro record, positions and `replanned` bytes are held against the numpy model of the decision rule behind
+    every compared op; behind the set_state and the full write_state: the float64 anchor of posture_dynamics() and the carried queries.
+    The device reports the coverage: envs in a heavy class, auto-resets and re-plans, all > 0."""
+    counts = _command_session(monkeypatch, 'c70')
+    assert counts['heavy'] > 0, counts
+
+
+def test_c5_against_the_plain_twin(monkeypatch):
+    """5 envs, 1 object, 96 x 64, the command programme: the one-chain placement; wrench rows for objects the handle does not have;
+    only the one object can be attached."""
+    _command_session(monkeypatch, 'c5')
+
+
 class _NullEnv:
     """takes every call and does nothing: a dry run of a Session shows which device arguments a programme needs, in order"""
 
@@ -498,6 +659,8 @@ class _NullEnv:
     def __getattr__(self, name):
         if name.startswith('_'):
             raise AttributeError(name)
+        if name == 'posture_dynamics':      # (torques_from_dynamics passes the bias on)
+            return lambda *a, **kw: {'bias': _NoMemory()}
         return lambda *a, **kw: None
 
 
@@ -506,7 +669,7 @@ class _NoMemory:
         return 0
 
 
-@pytest.mark.parametrize('name', ['n70', 'q70'])
+@pytest.mark.parametrize('name', ['n70', 'q70', 'c70'])
 def test_free_running_between_comparisons(monkeypatch, name):
     """The comparisons above wait for the device behind every op, and B's host road waits inside its calls.  Here A runs the same
     70-env programme as a training loop would: every device argument is uploaded before the first op, and A makes the ops of a chunk
@@ -519,6 +682,7 @@ def test_free_running_between_comparisons(monkeypatch, name):
     tw = _Twin(monkeypatch, name)
     staged = []
     dry = sp.Session(_NullEnv(tw.A), 'device', to_device=lambda a: staged.append(np.array(a)) or _NoMemory())
+    dry.copy_in_place = lambda *a: None
     dry.setup()
     for op in tw.ops:
         dry.apply(op)
@@ -541,7 +705,10 @@ def test_free_running_between_comparisons(monkeypatch, name):
                 tw.sb.apply(o)
             chunk = []
             _compare_results(tw, i, "A (free running) against B")
+            _compare_read_backs(tw, i)
             a = tw.collect_a()
+            if tw.commands:
+                _against_the_macro_model(tw, a, i)
             _assert_equal(a, tw.collect_b(True), i, tw.ops, "A (free running) against B", tw.envs_of)
             _check_mirrors(tw.A, tw.sa, tw.mirror, tw.img_mirror, a, tw.img_envs, i, tw.ops)
     assert not staged
@@ -564,7 +731,8 @@ def test_every_mutator_moves_the_next_step():
     select_image_mirror moves A's mapped image mirror: the deselected block keeps the old frame.
     The three table mutators (their first records of the q70 programme; for set_distance_pairs the first that is not the default
     table) are a class of their own: every field they move is a query or ray output, at least one of their own calls moves, and no
-    state or image field does.  Last, on one of the two handles: _state_writes_move_the_probe."""
+    state or image field does.  Last, on one of the two handles: _state_writes_move_the_probe; and the kinds of the command programmes
+    with the invariants the header gives them: _command_mutators_move."""
     name = 'n70'
     _, N, nobj, W, H, _ = sp.SESSIONS[name]
     ops = _program(name)
@@ -622,8 +790,103 @@ def test_every_mutator_moves_the_next_step():
         elif kind not in ('set_env_goals',):
             assert 'state' in moved or 'contacts(i)' in moved, (kind, moved)
     _state_writes_move_the_probe(X, N, nobj, probe, base)
+    _command_mutators_move(X, Y, N, nobj, W, H, probe, base, step)
     for e in (X, Y):
         e.close()
+
+
+CARRY_FIELDS = ('posture_clearance(po).', 'signed_distance().', 'signed_distance(po).', 'signed_distance_gradient(po).')
+
+
+def _command_mutators_move(X, Y, N, nobj, W, H, probe, base, step):
+    """The new kinds of the command programmes (their first records of c70), each with the invariant the header gives it.
+    * set_joint_torques, set_external_wrenches: the next step's state moves in the masked envs whose row has a non-zero entry (and
+      that are not frozen) and in NO other env -- the zero-row rule, -0.0 included.
+    * the unmasked clearing call: the next step is, bit for bit, the step of a handle that never had the feature -- a third handle
+      restored from the same checkpoint.
+    * attach: the outputs of the carry queries move in envs that carry something, and nothing else moves: no state field before the
+      step and none behind it.
+    * macro_invalidate: nothing moves before the next step_macro, and there `replanned` is set in exactly the masked envs that are
+      not idle."""
+    c = _program('c70')
+    Z = BatchedREALRobotEnv(N, objects=nobj, width=W, height=H)
+    everyone = np.arange(N)
+
+    def fresh(env):
+        env.restore(base)                   # (a restore keeps the tables, the attachments and the macro record: settings of the handle)
+        env.set_joint_torques(None)
+        env.set_external_wrenches(None)
+        env.detach_objects()
+        env.macro_invalidate()
+        env.set_kinematic_points([nat.EE_LINK])
+        s = sp.Session(env, 'device')
+        s.setup()
+        return s
+
+    def fields(env):
+        d = {'state': env.state}
+        d.update({k: env.host(f) for k, f in STATE_FIELDS.items()})
+        d['contacts(i)'] = [env.contacts(int(i)) for i in everyone]
+        return d
+    for kind, key, clear in (('set_joint_torques', 'torques', 'clear_joint_torques'), ('set_external_wrenches', 'wrenches', 'clear_external_wrenches')):
+        op = _first(c, kind, inplace=False)
+        sx, sy, sz = fresh(X), fresh(Y), fresh(Z)
+        sx.apply(op)
+        sz.apply(op)
+        sz.apply(dict(kind=clear, mask=None))
+        for s in (sx, sy, sz):
+            s.apply(step[2])
+        fx, fy, fz = fields(X), fields(Y), fields(Z)
+        rows = op[key].reshape(N, -1)[:, :11 * (1 if key == 'torques' else 6) + (0 if key == 'torques' else 6 * nobj)]
+        want = np.flatnonzero((op['mask'] != 0) & (rows != 0).any(axis=1) & ((fy['errflags'] & 5) == 0))
+        moved = _differing(fx['state'], fy['state'])
+        assert want.size and np.array_equal(moved, want), "%s moves the next step's state in envs %s, its masked non-zero rows are %s" % (kind, moved.tolist(), want.tolist())
+        for k in fx:
+            bad = _differing(fx[k], fy[k])
+            assert np.isin(bad, want).all(), "%s moves %s in envs %s outside its masked non-zero rows" % (kind, k, bad[~np.isin(bad, want)].tolist())
+            assert _differing(fz[k], fy[k]).size == 0, "behind %s the next step's %s differs from a handle that never had the feature" % (clear, k)
+        for s in (sx, sy, sz):
+            s.release()
+    # attach
+    op = next(o for o in c if o['kind'] == 'attach' and not o.get('anchor'))
+    sx, sy = fresh(X), fresh(Y)
+    sx.apply(op)
+    carrying = np.flatnonzero((op['mask'] != 0) & (op['links'] >= 0).any(axis=1))
+    dx, dy = (_collect(e, s, probe, everyone, everyone, images=False) for e, s in ((X, sx), (Y, sy)))
+    # (the episode counter and the final observation outlive a restore: X and Y have the auto-resets of earlier kinds in them)
+    moved = [k for k in dx if k in dy and k not in ('episode.episode', 'episode.final_obs') and _differing(dx[k], dy[k]).size]
+    assert moved and all(k.startswith(CARRY_FIELDS) for k in moved), ('attach', moved)
+    assert {k[:k.index('.') + 1] for k in moved} == set(CARRY_FIELDS), ('attach', moved)
+    for k in moved:
+        assert np.isin(_differing(dx[k], dy[k]), carrying).all(), ('attach', k, _differing(dx[k], dy[k]).tolist(), carrying.tolist())
+    for s in (sx, sy):
+        s.apply(step[2])
+    fx, fy = fields(X), fields(Y)
+    assert all(_differing(fx[k], fy[k]).size == 0 for k in fx), "attach moves a field of the step"
+    for s in (sx, sy):
+        s.release()
+    # macro_invalidate
+    go = dict(_first(c, 'step_macro'), render=0, flags=None)
+    op = next(o for o in c if o['kind'] == 'macro_invalidate' and o['mask'] is not None)
+    sx, sy = fresh(X), fresh(Y)
+    for s in (sx, sy):
+        s.apply(go)
+        s.apply(go)
+    macro = lambda env: {name: env.macro_buffer(name, host=True) for name in nat.MACRO_NAMES}
+    awake = go['idle'] == 0                 # (an idle env keeps the position an earlier part of this test left it)
+    assert not macro(X)['replanned'].any() and (macro(X)['position'][awake] == 2).all()
+    sx.apply(op)
+    fx, fy, mx, my = fields(X), fields(Y), macro(X), macro(Y)
+    assert all(_differing(fx[k], fy[k]).size == 0 for k in fx) and all(_differing(mx[k], my[k]).size == 0 for k in ('position', 'replanned', 'plan'))
+    assert np.array_equal(np.isnan(mx['request']).all(axis=1)[awake], (op['mask'] != 0)[awake]) and not np.isnan(my['request'][awake]).any()
+    for s in (sx, sy):
+        s.apply(go)
+    want = ((op['mask'] != 0) & (go['idle'] == 0)).astype(np.uint8)
+    assert want.any() and np.array_equal(macro(X)['replanned'], want) and not macro(Y)['replanned'].any()
+    assert np.array_equal(macro(X)['replanned'], sx.macro.replanned) and np.array_equal(macro(X)['position'][awake], sx.macro.position[awake])
+    for s in (sx, sy):
+        s.release()
+    Z.close()
 
 
 def _state_writes_move_the_probe(env, N, nobj, probe, base):

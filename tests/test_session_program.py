@@ -21,23 +21,31 @@ The query programmes of q70 and q5 (3 more mutator kinds, 9 query observer kinds
 condition; and, for the very anchor records of the GPU test, that the float64 reference decides at least 95 % of the items, so that
 the anchor cannot silently compare nothing.
 
-A recording fake of BatchedREALRobotEnv shows which calls each road issues, for the query kinds too."""
+A recording fake of BatchedREALRobotEnv shows which calls each road issues, for the query kinds too.
+
+The command programmes of c70 and c5 (10 more mutator kinds, the step kind step_macro, 10 observer kinds; 212 ops; q70 and q5 are
+pinned by digest from before they existed): the conditions of `check_command_conditions` for the very programmes the GPU test runs,
+a negative case for each kind of condition, the calls of both roads on the fake, the numpy model of the macro decision rule on a
+hand-made case, and that the float64 reference decides EVERY item of the two anchors."""
 import numpy as np
 import pytest
 
 from tests import session_program as sp
 
 
-OLD = [name for name in sp.SESSIONS if name not in sp.QUERY_SESSIONS]
+OLD = [name for name in sp.SESSIONS if name not in sp.QUERY_SESSIONS + sp.COMMAND_SESSIONS]
 assert OLD == ['n70', 'n5', 'n1100']
 # the three programmes from before the query programmes, as the parent commit's `program` drew them: blake2b-128 over every record's
 # kind and its keys in sorted order -- arrays (and the arrays of a recipe) by dtype, shape and bytes, everything else by its repr
 PINNED = {'n70': '0814dd1c46894a9a7d1660a2d276ee18', 'n5': '0fc90cd75a5fb425940149d1ff46cee7', 'n1100': '3c819adaf090f39665680cb5ccced3c7'}
+# ... and the two query programmes as the parent commit's `program` drew them, taken before the command programmes existed
+PINNED_QUERIES = {'q70': 'e07b2a5d05f54e7ed94080040d72e45c', 'q5': '34625be5378176b4b8806694589cd2fd'}
 
 
 @pytest.fixture(scope='module')
 def programmes():
-    return {name: sp.program(seed, N, nobj, length, queries=name in sp.QUERY_SESSIONS) for name, (seed, N, nobj, _, _, length) in sp.SESSIONS.items()}
+    return {name: sp.program(seed, N, nobj, length, queries=name in sp.QUERY_SESSIONS, commands=name in sp.COMMAND_SESSIONS)
+            for name, (seed, N, nobj, _, _, length) in sp.SESSIONS.items()}
 
 
 def _digest(ops):
@@ -61,6 +69,11 @@ def _digest(ops):
 @pytest.mark.parametrize('name', OLD)
 def test_the_programmes_from_before_the_queries_are_unchanged(programmes, name):
     assert _digest(programmes[name]) == PINNED[name]
+
+
+@pytest.mark.parametrize('name', sp.QUERY_SESSIONS)
+def test_the_query_programmes_are_unchanged(programmes, name):
+    assert _digest(programmes[name]) == PINNED_QUERIES[name]
 
 
 def _same(a, b):
@@ -278,13 +291,15 @@ class FakeEnv:
             raise AttributeError(name)
 
         def call(*args, **kw):
-            side = self._side(args, kw)
+            side = self._side(args, {'idle': kw.get('idle')} if name == 'step_macro_device' else kw)      # (render flags are host memory on every road)
             if name == 'step':
                 side = 'device' if kw.get('device_ptr') is not None else 'host'
             flags = tuple(k for k in ('joint_pos', 'joint_vel', 'obj_pose', 'obj_vel', 'reset', 'fresh') if kw.get(k))
             self.log.append((name, side) + ((flags,) if name == 'write_state' else ()))
             if name == 'checkpoint':
                 return np.zeros(4, np.uint8)
+            if name == 'posture_dynamics':      # (the bias is what torques_from_dynamics passes on: a device view, or a host array)
+                return {'bias': np.zeros((self.N, 1, 11), np.float32) if kw.get('host') else _Dev(None)}
             if name == 'episode_buffer':
                 return (np.arange(self.N) % 2).astype(np.uint32) if args[0] == 'done' else np.zeros(self.N, np.float32)
             if name == 'host':
@@ -307,6 +322,7 @@ class FakeEnv:
 def _run(ops, road, N, nobj):
     env = FakeEnv(N, nobj)
     s = sp.Session(env, road, to_device=_Dev)
+    s.copy_in_place = lambda e, name, table, mask: e.log.append(('in_place ' + name, e._side((table, mask), {})))
     s.setup()
     env.log.clear()
     per_op = []
@@ -411,3 +427,211 @@ def test_run_is_the_session_over_the_whole_programme(programmes):
     assert calls[-sum(len(p) for p in per_op):] == [c for p in per_op for c in p]
     assert [c[0] for c in calls[:6]] == ['set_rays', 'snapshot_slots', 'set_goals', 'set_env_goals', 'set_episode', 'checkpoint']
     assert len(s.ckpts) == 1 + sum(o['kind'] == 'checkpoint' for o in programmes['n5']) and len(s.keep) > 0
+
+
+# ---------------------------------------------------------------------------------------------------- the command programmes
+@pytest.mark.parametrize('name', sp.COMMAND_SESSIONS)
+def test_conditions_of_the_command_programmes_the_gpu_test_runs(programmes, name):
+    """c70 and c5: the conditions of `check_command_conditions` for the very programmes the GPU test runs -- every new mutator
+    directly followed by a step of each render form and by a step_macro; each of the eight state mutators directly followed by a step
+    with both tables non-zero, with attachments on, directly behind a step_macro with plans in flight, with a step_macro behind it, and
+    once more with every feature off; a carry query and an attach_capture directly behind five of them and behind a step; carried_sweep
+    with attachments on and off; snapshots while everything is set and loads after it has changed; the draws.  The same arguments
+    give the same programme, another seed another one; a shorter programme is refused, a longer one holds the conditions too."""
+    seed, N, nobj, _, _, length = sp.SESSIONS[name]
+    ops = programmes[name]
+    assert length == sp.C_LENGTH == sp.C_MIN_LENGTH
+    found = sp.check_command_conditions(ops, length, N, nobj)
+    assert all(found['count'].get(k, 0) >= 4 for k in sp.C_MUTATORS) and found['count']['step_macro'] >= 20
+    again = sp.program(seed, N, nobj, length, commands=True)
+    assert all(_same(a, b) for a, b in zip(ops, again))
+    assert not all(_same(a, b) for a, b in zip(ops, sp.program(seed + 1, N, nobj, length, commands=True)))
+    with pytest.raises(ValueError):
+        sp.program(seed, N, nobj, length - 1, commands=True)
+    sp.check_command_conditions(sp.program(seed, N, nobj, length + 5, commands=True), length + 5, N, nobj)
+    # once more, from the list of kinds alone
+    kinds = [o['kind'] for o in ops]
+    for m in sp.C_MUTATORS:
+        at = [i for i, k in enumerate(kinds) if k == m]
+        skip = lambda i: i + 2 if m == 'attach_capture' and kinds[i + 1] in sp.CARRY_QUERIES else i + 1
+        assert {ops[skip(i)]['render'] for i in at if kinds[skip(i)] == 'step'} == {0, 1, 2}, m
+        assert any(kinds[skip(i)] == 'step_macro' for i in at), m
+    assert all(kinds[i + 1] in sp.CARRY_QUERIES for i, k in enumerate(kinds) if k == 'attach_capture')
+    for s in ('fork_dev', 'load_snapshot', 'reset_dev', 'restore'):
+        assert any(kinds[i + 1] == 'attach_capture' for i, k in enumerate(kinds) if k == s), s
+        assert any(kinds[i + 1] in sp.CARRY_QUERIES for i, k in enumerate(kinds) if k == s), s
+        assert any(kinds[i + 1] == 'step_macro' for i, k in enumerate(kinds) if k == s) and any(kinds[i - 1] == 'step_macro' for i, k in enumerate(kinds) if k == s), s
+
+
+def test_a_broken_command_condition_is_noticed(programmes):
+    """each of these breaks one condition of a command programme and nothing else"""
+    _, N, nobj, _, _, length = sp.SESSIONS['c70']
+    c = programmes['c70']
+    kinds = [o['kind'] for o in c]
+    fork = next(i for i, k in enumerate(kinds) if k == 'fork_dev' and kinds[i + 1] == 'attach_capture')
+    off = max(i for i, k in enumerate(kinds) if k == 'detach_all')
+    broken = [
+        [dict(o, render=0, flags=None) if o['kind'] == 'step' and c[i - 1]['kind'] == 'detach' else o for i, o in enumerate(c)],       # detach meets one render form only
+        c[:fork] + [dict(kind='checkpoint')] + c[fork + 1:],                                            # no attach_capture directly behind a fork
+        [dict(o, compared=True) if o['kind'] == 'carried_sweep' else o for o in c],                     # a kind that is never silent
+        [dict(o, mask=np.ones(N, np.uint8)) if o['kind'] == 'clear_joint_torques' else o for o in c],   # the torque feature never goes off
+        c[:off] + [dict(c[off], kind='detach', mask=np.ones(N, np.uint8))] + c[off + 1:],               # no feature-off road: the attachments stay on
+        [dict(o, macro=np.abs(o['macro'])) if o['kind'] == 'step_macro' else o for o in c],             # no request with a -0.0
+        [dict(o, inplace=False) if o['kind'] == 'set_external_wrenches' else o for o in c],             # no in-place write of the wrench table
+        [o for o in c if not o.get('anchor') or o['kind'] != 'attach'] + [dict(kind='render')] * 2,     # an anchor without its attach
+    ]
+    for ops in broken:
+        assert len(ops) == length
+        with pytest.raises(AssertionError):
+            sp.check_command_conditions(ops, length, N, nobj)
+
+
+def test_the_macro_model_is_the_rule_of_the_header():
+    """idle: nothing moves; need = a request that differs from the record (IEEE ==) or an exhausted plan; a needing env stores the
+    request and starts at row 0; every env that is not idle advances"""
+    m = sp.MacroModel(4)
+    req = np.array([[0.0, 0.1, 0.2, 0.3]] * 4, np.float32)
+    assert m.step_macro(req, np.array([0, 0, 0, 1], np.uint8)).tolist() == [True, True, True, False]      # (the record starts NaN)
+    assert m.position.tolist() == [1, 1, 1, 0] and np.isnan(m.record[3]).all() and m.replanned.tolist() == [1, 1, 1, 0]
+    req[0, 0], req[1, 2], req[2, 3] = -0.0, np.nan, 0.31
+    assert m.step_macro(req, None).tolist() == [False, True, True, True]                                  # (-0.0 equals 0.0; a NaN equals nothing)
+    assert m.position.tolist() == [2, 1, 1, 1] and not np.signbit(m.record[0, 0]) and np.isnan(m.record[1, 2])
+    assert m.step_macro(req, None).tolist() == [False, True, False, False]                                # (... on every step)
+    m.position[2] = sp.PLAN_LEN
+    m.invalidate(np.array([0, 0, 0, 1], np.uint8))
+    m.plan(np.array([1, 0, 0, 0], np.uint8))
+    assert m.position.tolist() == [0, 1, sp.PLAN_LEN, 2] and np.isnan(m.record[3]).all()
+    assert m.step_macro(req, None).tolist() == [False, True, True, True] and m.position.tolist() == [1, 1, 1, 1]
+    m.step_plan(np.array([1, 0, 0, 0], np.uint8))
+    assert m.position.tolist() == [1, 2, 2, 2]
+
+
+@pytest.mark.parametrize('name', sp.COMMAND_SESSIONS)
+def test_both_roads_issue_the_command_calls_they_should(programmes, name):
+    """A: device tables and masks, once per table the in-place write; the bias view straight into set_joint_torques; device requests
+    and idle masks.  B: host arrays throughout.  The attachment calls take host arguments on both roads.  An observer is A's, and B's
+    only where the record is compared."""
+    _, N, nobj, _, _, _ = sp.SESSIONS[name]
+    ops = programmes[name]
+    dev, sd = _run(ops, 'device', N, nobj)
+    host, sh = _run(ops, 'host', N, nobj)
+    seen = set()
+    for op, d, h in zip(ops, dev, host):
+        k = op['kind']
+        assert all(c[1] != 'device' for c in h), (k, h)
+        if k in ('set_joint_torques', 'set_external_wrenches'):
+            buf = {'set_joint_torques': 'joint_torque_buffer', 'set_external_wrenches': 'external_wrench_buffer'}[k]
+            assert d == [('in_place ' + buf if op['inplace'] else k, 'device')] and h == [(k, 'host')], (k, d, h)
+        elif k in ('clear_joint_torques', 'clear_external_wrenches'):
+            call = k.replace('clear', 'set')
+            assert d == [(call, None if op['mask'] is None else 'device')] and h == [(call, None if op['mask'] is None else 'host')]
+        elif k == 'torques_from_dynamics':
+            assert d == [('posture_dynamics', None), ('set_joint_torques', 'device')] and h == [('posture_dynamics', None), ('set_joint_torques', 'host')]
+        elif k in ('attach', 'attach_capture'):
+            assert d == h == [('attach_objects', 'host')]
+        elif k in ('detach', 'detach_all'):
+            assert d == h == [('detach_objects', None if k == 'detach_all' else 'host')]
+        elif k == 'macro_invalidate':
+            assert d == [(k, None if op['mask'] is None else 'device')] and h == [(k, None if op['mask'] is None else 'host')]
+        elif k == 'step_macro':
+            assert d == [('step_macro_device', 'device')] and h == [('step_macro_device', 'host')]
+        elif k in sp.C_OBSERVERS:
+            call = {'signed_distance_at': 'signed_distance', 'swept_clearance_refused': 'swept_clearance'}.get(k, k)
+            assert [c[0] for c in d] == [call], (k, d)
+            assert [c[0] for c in h] == ([call] if op['compared'] else []), (k, h)
+        seen.add(k)
+    assert seen >= set(sp.C_MUTATORS) | set(sp.C_OBSERVERS) | {'step_macro'}
+    # both Sessions end with the same model, the one of the records alone
+    model = sp.MacroModel(N)
+    for op in ops:
+        model.apply(op)
+    for s in (sd, sh):
+        assert np.array_equal(s.macro.position, model.position) and np.array_equal(s.macro.record, model.record, equal_nan=True) and not s.attached
+    assert sd.read.keys() >= sh.read.keys() and set(sd.read) == {'joint_torques', 'external_wrenches', 'attachments'}
+
+
+def test_written_command_values_are_what_the_calls_get():
+    """the records' arrays reach the calls as they are: a recording env keeps the arguments"""
+    _, N, nobj, _, _, length = sp.SESSIONS['c5']
+    ops = sp.program(sp.SESSIONS['c5'][0], N, nobj, length, commands=True)
+    got = []
+
+    class Keep(FakeEnv):
+        def __getattr__(self, name):
+            inner = FakeEnv.__getattr__(self, name)
+
+            def call(*args, **kw):
+                got.append((name, args, kw))
+                return inner(*args, **kw)
+            return call
+    for road in ('host', 'device'):
+        env = Keep(N, nobj)
+        s = sp.Session(env, road, to_device=_Dev)
+        s.copy_in_place = lambda e, name, table, mask: got.append((name, (table, mask), {}))
+        s.setup()
+        val = lambda a: a.a if isinstance(a, _Dev) else a
+        for op in ops:
+            del got[:]
+            s.apply(op)
+            k = op['kind']
+            if k in ('set_joint_torques', 'set_external_wrenches'):
+                _, args, _ = got[-1]
+                assert val(args[0]) is op['torques' if k == 'set_joint_torques' else 'wrenches'] and val(args[1]) is op['mask']
+            elif k == 'attach':
+                assert got[-1][1][0] is op['links'] and got[-1][1][1] is op['rel'] and got[-1][1][2] is op['mask']
+            elif k == 'attach_capture':
+                assert got[-1][1][0] is op['links'] and got[-1][1][1] is None
+            elif k == 'step_macro':
+                _, args, kw = got[-1]
+                assert val(args[0]) is op['macro'] and val(kw['idle']) is op['idle']
+                assert (kw['render'] is op['flags']) if op['render'] == 2 else kw['render'] == bool(op['render'])
+            elif k in sp.C_OBSERVERS and not got:
+                assert road == 'host' and not op['compared']          # (a silent record is A's alone)
+            elif k == 'posture_dynamics':
+                _, args, kw = got[-1]
+                assert all(val(a) is b for a, b in zip(args, (op['postures'], op['velocities'], op['accelerations']))) and kw['inverse'] == op['inverse']
+            elif k == 'carried_sweep':
+                assert val(got[-1][1][0]) is op['segments'] and got[-1][2]['safety'] == op['safety']
+    # the ranges of the issue: the arm stays in range
+    t = np.concatenate([o['torques'] for o in ops if o['kind'] == 'set_joint_torques'])
+    w = np.concatenate([o['wrenches'] for o in ops if o['kind'] == 'set_external_wrenches'])
+    assert np.abs(t[:, :7]).max() <= 5.0 and np.abs(t[:, 7:]).max() <= 0.2 and np.abs(w[..., :3]).max() <= 4.0 and np.abs(w[:, :11, 3:]).max() <= 0.3
+    req = np.concatenate([o['macro'] for o in ops if o['kind'] == 'step_macro'])
+    assert (req[np.isfinite(req).all(axis=1)] >= sp.MACRO_LO).all() and (req[np.isfinite(req).all(axis=1)] <= sp.MACRO_HI).all()
+
+
+def test_the_module_still_imports_neither_torch_nor_the_library_for_a_command_programme():
+    import subprocess
+    import sys
+    code = ("import sys; from tests import session_program as sp; seed, N, nobj = sp.SESSIONS['c5'][:3]; "
+            "sp.check_command_conditions(sp.program(seed, N, nobj, sp.C_LENGTH, commands=True), sp.C_LENGTH, N, nobj); "
+            "assert not [m for m in sys.modules if m.split('.')[0] in ('torch', 'real_robots_amd')], sys.modules.keys()")
+    subprocess.check_call([sys.executable, '-c', code], cwd=str(__import__('pathlib').Path(__file__).resolve().parents[1]))
+
+
+@pytest.mark.parametrize('name', sp.COMMAND_SESSIONS)
+def test_the_command_anchors_are_decided(programmes, name):
+    """The float64 anchor of the GPU test sets NO item aside: for the very anchor records of c70 and c5, the first four envs, the
+    default table, the anchor's attach and the probe's postures, the reference decides every (env, pair) and (env, posture, pair) item,
+    at the present joints and at the postures; a good share of the items has a shape of an attached object, and they are more than a
+    centimetre from where the state alone would put them (a query that ignored the attachments would miss the bound)."""
+    from tests import numpy_distance as nd
+    from tests import numpy_posture as npo
+    _, N, nobj, _, _, _ = sp.SESSIONS[name]
+    ops = programmes[name]
+    at = [i for i, o in enumerate(ops) if sp.is_command_anchor(o)]
+    assert [ops[i]['kind'] for i in at] in (['set_state', 'write_state'], ['write_state', 'set_state'])
+    q = sp.probe_arguments(N, nobj)
+    n = min(N, sp.ANCHOR_ENVS)
+    for i in at:
+        attach = ops[i - 1]
+        assert attach['kind'] == 'attach' and attach['mask'] is None and (attach['links'][:n] >= 0).any(axis=1).sum() >= n - 1
+        r = sp.command_anchor_references(attach, ops[i], nobj, q)
+        for key, rows in (('now', n), ('po', n * sp.PROBE_K)):
+            ref, att = r[key], r['att_' + key]
+            assert ref['decided'].shape == att.shape == (rows, len(r['pairs'])) and ref['decided'].all(), (name, i, key, np.argwhere(~ref['decided']).tolist())
+            assert att.sum() >= 0.25 * att.size
+        left = nd.reference(npo.rows(r['state'], q['postures'][:n]), r['pairs'])
+        moved = np.abs(left['d'] - r['po']['d'])[r['att_po']]
+        assert (moved > 0.01).mean() > 0.9 and not np.abs(left['d'] - r['po']['d'])[~r['att_po']].any()
+        assert all(np.isfinite(v).all() for v in r['dynamics'].values())
