@@ -1265,8 +1265,8 @@ int rr_get_external_wrenches(rr_env *env, float *out_host);
  * provided the feature is on (a successful rr_set_external_wrenches with a table since the last clearing call). */
 int rr_external_wrench_buffer(rr_env *env, void **dev_ptr, size_t *bytes);
 
-/* Carried objects in the posture queries: objects attached to robot links (additive in ABI 7; k_posture_clearance_carry,
- * k_signed_distance_carry, k_signed_gradient_carry, k_attach_capture: csrc/rr_carry.inc).  What planners call an ATTACHED body: once
+/* Carried objects in the posture queries: objects attached to robot links (additive in ABI 7; the <true> instantiations of
+ * k_posture_clearance, k_signed_distance and k_signed_gradient; k_attach_capture: csrc/rr_carry.inc).  What planners call an ATTACHED body: once
  * the gripper holds the cube, a candidate posture must move the cube with the hand, or the (finger, cube) pairs report the arm's
  * motion against a stationary cube and the (cube, shelf) / (cube, table) pairs never change.  It replaces the write-and-query loop --
  * rr_write_state of the composed object pose per candidate, then a present-state query -- that rr_posture_clearance was added to
@@ -1279,7 +1279,7 @@ int rr_external_wrench_buffer(rr_env *env, void **dev_ptr, size_t *bytes);
  * rr_signed_gradient place an attached object at T_link(posture) o rel -- R_o = R_b R_rel, p_o = p_b + R_b t_rel from the row's forward
  * kinematics, not from the state -- and, in the gradient, give its shapes the joint columns of the link's body, at candidate postures
  * and at the present state (postures == NULL) alike: RR_SG_PAIR_GRADIENT then has columns for a carried object.  A free object, and
- * every object of an env with no attachment, is staged by the operations of the original kernels: every number that no carried shape
+ * every object of an env with no attachment, is staged by the operations of the <false> instantiations: every number that no carried shape
  * enters has the bits it has with the feature off.  The same buffers with the same layouts are written; body_a / body_b keep reporting
  * 16 + o for an object, attached or not.  rr_closest_points is unaffected (at the present state an object is where the state says).
  * rr_swept_clearance REFUSES while the feature is on (RR_EINVAL, nothing written): its proof rests on a reach table that is a constant
@@ -1290,7 +1290,7 @@ int rr_external_wrench_buffer(rr_env *env, void **dev_ptr, size_t *bytes);
  *     rel = T_link(q_present)^-1 o T_object(present) for the attached objects of the masked envs with the step's forward kinematics:
  *     "attach what the gripper holds right now" without a host round trip for the poses.
  *   link == NULL: the masked envs' objects are detached.  link == NULL and env_mask == NULL turns the feature OFF: the three queries
- *     launch exactly the kernels they launched before this entry point existed, as on a handle that never attached.
+ *     launch the <false> instantiations, the instructions they ran before this entry point existed, as on a handle that never attached.
  * The device table holds {moving body, rotation, translation in that body's frame}; the host converts from and to the link's COM
  * frame in float64 through the model's link table, so rr_get_attachments returns a pose that differs from the one given by float32
  * rounding (and possibly by the quaternion's sign).  The call waits for the stream: its arguments are host memory.
@@ -1311,14 +1311,14 @@ int rr_set_attachments(rr_env *env, const int32_t *link /* i32 [N][n_obj] host, 
  * may be NULL.  Synchronising when rel_pose_out is given. */
 int rr_get_attachments(rr_env *env, int32_t *link_out /* [N][n_obj] */, float *rel_pose_out /* [N][n_obj][7] */);
 
-/* Swept clearance with carried objects: the attached-body edge check (additive in ABI 7; k_carried_sweep: csrc/rr_csweep.inc).
+/* Swept clearance with carried objects: the attached-body edge check (additive in ABI 7; k_swept_clearance<true>: csrc/rr_sweep.inc).
  * rr_swept_clearance proves an edge free for the empty hand; the transport half of a pick-and-place plan moves an object through the
  * same shelf.  rr_carried_sweep is rr_swept_clearance -- its arguments, its validation and refusals (under this call's name), its host
  * staging and STREAM CONTRACT, its four RR_SW_* buffers in the same layouts, read through rr_sweep_buffer and rr_sweep_copy_to_host:
  * NO new buffer family -- with ONE difference: it does not refuse while attachments are on.
  * Attachments OFF (a handle that never attached, or after the unmasked detach): the call forwards to rr_swept_clearance -- the same
  * kernel, the same bytes.  A planner can always call this one function.
- * Attachments ON: one launch of k_carried_sweep on the library's stream, one wave64 per (env, segment) like the original.
+ * Attachments ON: one launch of k_swept_clearance<true> on the library's stream, one wave64 per (env, segment) like <false>.
  * The motion model.  q(t) = q0 + t (q1 - q0), t in [0, 1].  An ATTACHED object of env e moves with its link: at every posture the
  * advancement evaluates it is re-staged as R_o = R_b R_rel, p_o = p_b + R_b t_rel from that posture's forward kinematics and the
  * env's table row, by the device function rr_posture_clearance uses while attachments are on.  A FREE object stays at env e's present pose.
@@ -1329,11 +1329,11 @@ int rr_get_attachments(rr_env *env, int32_t *link_out /* [N][n_obj] */, float *r
  * with (c_s, r_s) the bounding sphere of s in the object's frame.  rho is computed per row on the device from the table row (a
  * captured row never visits the host), with ||R_rel|| MEASURED from the row (a captured rotation is orthonormal to float32 rounding
  * only), an absolute term for a cancelling t_rel + R_rel c_s, and the factor 1 + 2^-18: float32 rounding cannot lower it
- * (csrc/rr_csweep.inc derives the factor).  Robot shapes keep R[k][s] of rr_sweep_reach.
+ * (csrc/rr_sweep.inc derives the factor).  Robot shapes keep R[k][s] of rr_sweep_reach.
  * The pair bound.  B_j as rr_swept_clearance defines it, over the joints in exactly one of the two masks, ascending k in float32,
  * times 1 + 2^-20: the distance of pair j is B_j-Lipschitz in t with the carried objects moving.  A carried shape against a shape on
  * its own body, and two objects carried by one body, have B_j = 0: one look, horizon +inf.  Two objects on different bodies work
- * through the exclusive-or of their masks.  The advancement, the statuses, `steps` and `pair evaluations` are the original's.
+ * through the exclusive-or of their masks.  The advancement, the statuses, `steps` and `pair evaluations` are those of rr_swept_clearance.
  * Guarantees.  Those of rr_swept_clearance with "the distance of pair j along the motion" read with the carried objects moving: for
  * every pair j and every t < min(free_j, 1) it exceeds safety, for every t < fraction every pair's does.  The RR_SW_HIT record of a
  * stopped row is, bit for bit, what rr_posture_clearance returns for that pair at q_stop on the same attached handle.  An env with

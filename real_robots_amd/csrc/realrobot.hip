@@ -475,12 +475,11 @@ __device__ __forceinline__ void dispatch_order_class(int x, int N, int ntiles, i
 #include "rr_write.inc"    // k_state_rw: masked state writes by column groups and state reads on the device (rr_write_state, rr_read_state)
 #include "rr_ray.inc"    // k_ray_cast: segments of the whole batch against the collision hulls at the present state (rr_ray_cast)
 #include "rr_dist.inc"    // k_closest_points: distance and closest points of pairs of collision hulls of the whole batch at the present state (rr_closest_points)
+#include "rr_carry.inc"    // k_attach_set / k_attach_capture, carry_stage_object: the attachment table of objects carried by robot links, and what the CARRY instantiations of the four kernels below call to stage them (rr_set_attachments)
 #include "rr_posture.inc"    // k_posture_clearance: every pair's distance and the nearest pair's record at K candidate joint postures per env (rr_posture_clearance)
-#include "rr_sweep.inc"    // k_swept_clearance: first contact of the pair table along K joint-space segments per env, by conservative advancement (rr_swept_clearance)
+#include "rr_sweep.inc"    // k_swept_clearance: first contact of the pair table along K joint-space segments per env, by conservative advancement (rr_swept_clearance); <true>: with carried objects -- re-staged at every step, a carried shape's joint mask and per-env reach (rr_carried_sweep)
 #include "rr_signed.inc"    // k_signed_distance: every pair's signed distance -- minus the penetration depth where the hulls overlap -- and the deepest pair's record, at the present state or at K postures (rr_signed_distance)
 #include "rr_grad.inc"    // k_signed_gradient: k_signed_distance plus the joint gradients of the deepest pair's signed distance and of a hinge cost over all pairs (rr_signed_gradient)
-#include "rr_carry.inc"    // k_posture_clearance_carry / k_signed_distance_carry / k_signed_gradient_carry, k_attach_capture: the posture queries with objects attached to robot links (rr_set_attachments)
-#include "rr_csweep.inc"    // k_carried_sweep: k_swept_clearance with carried objects -- the objects re-staged at every step, a carried shape's joint mask and per-env reach (rr_carried_sweep)
 #include "rr_plan.inc"   // plan_step: the placement and launch shapes of one step from one reading of the lagged list lengths (host only, no HIP type)
 #include "rr_mem.inc"    // MemOwner: the one owner of the handle's device and pinned memory, all-or-nothing group allocation (host only, no HIP type)
 #include "rr_query.inc"    // the query families' output buffers: one layout table, one buffer / copy_to_host accessor pair (host only, no HIP type)

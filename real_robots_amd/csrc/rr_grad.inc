@@ -21,17 +21,24 @@
 // The sums run in a fixed order (a wave's pairs j = w, w + 4, ... ascending from +0.0, then the waves in order), in float32, without
 // atomics: identical from call to call and independent of N, K and the row's place; a permuted table sums in another order.
 // No value of the tensor or the state forms an address: LDS is indexed by the lane number and by the masked body indices sd_pair returns.
+// With carried objects the kernel is a template <bool CARRY> like its sibling (rr_posture.inc's header, rr_carry.inc's header): <true>
+// stages the objects behind one more barrier in phase 2 and keeps every object's b + 1 (s_att, 12 bytes of LDS that <false> does not
+// have); in phase 3 a shape of an attached object takes the joint mask of the carrying body, picked by a compare chain over the masked
+// object index and fed to the one compare chain over the body index.  <false> is the text above and nothing else: ca - 1 is the -1 of
+// "no body" there.
 #define SG_FR_AX RAY_FR              // the world axes behind an env's frames: 33 floats
 #define SG_FR (RAY_FR + 3 * NB)
 #define SG_ROW 12                    // floats of a gradient row: eleven joints and one more (+0.0, or the cost)
 
+template <bool CARRY>
 __global__ void __launch_bounds__(SD_THREADS) k_signed_gradient(BodyParams B, SimParams P, DevPtrs D, const DistTable *__restrict__ tab, int Q,
                                                                 const float *__restrict__ postures /*[N][K][11] or null: the present state, K = 1*/, int K,
                                                                 float4 *__restrict__ out_deep /*[N][K][3]*/, int4 *__restrict__ out_id /*[N][K]*/,
                                                                 float *__restrict__ out_signed /*[N][K][Q]*/, int *__restrict__ out_status /*[N][K][Q]*/,
                                                                 float4 *__restrict__ out_pts /*[N][Q][3] or null*/, float margin,
                                                                 float *__restrict__ out_grad /*[N][K][12]*/, float *__restrict__ out_cost /*[N][K][12]*/,
-                                                                float *__restrict__ out_pgrad /*[N][Q][12] or null*/) {
+                                                                float *__restrict__ out_pgrad /*[N][Q][12] or null*/,
+                                                                const float *__restrict__ att /*[N][NOBJ][ATT_ROW]; null and unread without CARRY*/) {
     static_assert(RAY_ST == 32 && NB == 11 && ST_OPOS == 2 * NB, "staged slot s is joint s (s < 11) or state slot s + 11");
     static_assert(64 * DIST_TRIPS == VMAXC && 4 + SD_TRIP_CAP <= 64, "a lane holds three vertices of a shape and one of the polytope");
     static_assert(NB + 1 == SG_ROW && SG_ROW <= 64, "a lane per column of a row");
@@ -40,6 +47,7 @@ __global__ void __launch_bounds__(SD_THREADS) k_signed_gradient(BodyParams B, Si
     __shared__ float s_ob[1][12 * NOBJ + 1];
     __shared__ float s_best[SD_WAVES][SD_PARK];
     __shared__ float s_grad[SD_WAVES][2][SG_ROW];              // per wave: its best pair's row, its accumulator
+    __shared__ int s_att[CARRY ? NOBJ : 1];                    // b + 1 of every object's body, 0: free (never named without CARRY: no LDS then)
     const ShapeData *__restrict__ S = D.shapes;
     const int N = P.N, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -73,7 +81,7 @@ __global__ void __launch_bounds__(SD_THREADS) k_signed_gradient(BodyParams B, Si
             fr[RAY_FR_P + 3 * b] = pb.x; fr[RAY_FR_P + 3 * b + 1] = pb.y; fr[RAY_FR_P + 3 * b + 2] = pb.z;
             fr[SG_FR_AX + 3 * b] = aw.x; fr[SG_FR_AX + 3 * b + 1] = aw.y; fr[SG_FR_AX + 3 * b + 2] = aw.z;
         }
-    } else if (tid < 1 + NOBJ) {
+    } else if (!CARRY && tid < 1 + NOBJ) {
         const int o = tid - 1;
         const m3 Ro = nc::quat_to_m3(s_st[20 + 4 * o][0], s_st[21 + 4 * o][0], s_st[22 + 4 * o][0], s_st[23 + 4 * o][0]);
         float *ob = s_ob[0] + 12 * o;
@@ -82,7 +90,16 @@ __global__ void __launch_bounds__(SD_THREADS) k_signed_gradient(BodyParams B, Si
         ob[9] = s_st[11 + 3 * o][0]; ob[10] = s_st[12 + 3 * o][0]; ob[11] = s_st[13 + 3 * o][0];
     }
     __syncthreads();
+    if constexpr (CARRY) {
+        if (tid >= 1 && tid < 1 + NOBJ) s_att[tid - 1] = carry_stage_object(att, env, tid - 1, s_st, s_fr[0], s_ob[0]);
+        __syncthreads();
+    }
     // 3
+    int at[NOBJ];                                                     // the objects' b + 1, wave-uniform (filled and read with CARRY only)
+    if constexpr (CARRY) {
+#pragma unroll
+        for (int o = 0; o < NOBJ; o++) at[o] = __builtin_amdgcn_readfirstlane(s_att[o]);
+    }
     const float maxd = tab->max_distance;
     const bool cull = maxd > 0.0f && maxd < INFINITY;
     float key = INFINITY;
@@ -99,7 +116,14 @@ __global__ void __launch_bounds__(SD_THREADS) k_signed_gradient(BodyParams B, Si
         }
         const float4 u0 = pc_uniform(R.o0), u1 = pc_uniform(R.o1), u2 = pc_uniform(R.o2);
         const int st = __builtin_amdgcn_readfirstlane(R.status);
-        const int boda = __builtin_amdgcn_readfirstlane(R.ota == 1 ? R.oia : -1), bodb = __builtin_amdgcn_readfirstlane(R.otb == 1 ? R.oib : -1);
+        // the body that moves each shape: its own for a robot shape, the carrying one for a shape of an attached object, none otherwise
+        int ca = 0, cb = 0;                                             // b + 1 of the carrying body
+        if constexpr (CARRY) {
+            const int oba = __builtin_amdgcn_readfirstlane(R.ota == 2 ? R.oia : -1), obb = __builtin_amdgcn_readfirstlane(R.otb == 2 ? R.oib : -1);
+#pragma unroll
+            for (int o = 0; o < NOBJ; o++) { ca = oba == o ? at[o] : ca; cb = obb == o ? at[o] : cb; }
+        }
+        const int boda = __builtin_amdgcn_readfirstlane(R.ota == 1 ? R.oia : ca - 1), bodb = __builtin_amdgcn_readfirstlane(R.otb == 1 ? R.oib : cb - 1);
         // the joints that move each shape's body: the compile-time table read by a compare chain, no mask without a match
         unsigned ma = 0u, mb = 0u;
 #pragma unroll

@@ -162,14 +162,14 @@ struct rr_env : ModelTables {
     bool xw_on = false;
     // objects attached to robot links in the posture queries (rr_set_attachments): the table [N][NOBJ][ATT_ROW] (rr_carry.inc), allocated
     // zero-filled -- all free -- on first use with its staging block; att_link [N][nobj]: the host copy of the link ids, -1 free (empty until
-    // the first set); att_on: the three posture queries launch their carry variants (from the first successful set with links until the
+    // the first set); att_on: the three posture queries launch their CARRY instantiations (from the first successful set with links until the
     // unmasked detach).  No step reads any of it.
     float *att_table = nullptr;
     float *att_stage = nullptr;
     std::vector<int32_t> att_link;
     bool att_on = false;
     // the swept clearance with carried objects (rr_carried_sweep): chain[k][b], the joint offsets between joint k and body b, built and
-    // uploaded by the first call that launches k_carried_sweep (rr_csweep.inc)
+    // uploaded by the first call that launches k_swept_clearance<true> (rr_sweep.inc)
     SweepChain sw_chain = {};
     SweepChain *sw_chain_dev = nullptr;
     MemOwner mem;                 // every device and pinned block of the handle (rr_mem.inc); `created`: rr_create is through, zero-fills go on the library's stream
@@ -1746,12 +1746,12 @@ int rr_posture_clearance(rr_env *e, const float *postures, int32_t n_postures, i
     const float *src = postures;
     RRCHK(st.in(src, e->pc_stage, (size_t)N * K * 44));
     void *const *b = e->qbuf[QF_PC];
-    if (e->att_on)      // objects are attached to links (rr_set_attachments): the carry variant of rr_carry.inc, the same buffers
-        hipLaunchKernelGGL(k_posture_clearance_carry, dim3((unsigned)N * K), dim3(PC_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
+    if (e->att_on)      // objects are attached to links (rr_set_attachments): the CARRY instantiation, the same buffers
+        hipLaunchKernelGGL(k_posture_clearance<true>, dim3((unsigned)N * K), dim3(PC_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
                            (float4 *)b[RR_PC_NEAREST], (int4 *)b[RR_PC_ID], (float *)b[RR_PC_DISTANCE], (int *)b[RR_PC_STATUS], (const float *)e->att_table);
     else
-        hipLaunchKernelGGL(k_posture_clearance, dim3((unsigned)N * K), dim3(PC_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
-                           (float4 *)b[RR_PC_NEAREST], (int4 *)b[RR_PC_ID], (float *)b[RR_PC_DISTANCE], (int *)b[RR_PC_STATUS]);
+        hipLaunchKernelGGL(k_posture_clearance<false>, dim3((unsigned)N * K), dim3(PC_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
+                           (float4 *)b[RR_PC_NEAREST], (int4 *)b[RR_PC_ID], (float *)b[RR_PC_DISTANCE], (int *)b[RR_PC_STATUS], (const float *)nullptr);
     HIPCHK(hipGetLastError());
     e->qk[QF_PC] = K;
     return st.wait();
@@ -1781,14 +1781,14 @@ int rr_signed_distance(rr_env *e, const float *postures, int32_t n_postures, int
     const float *src = postures;
     RRCHK(st.in(src, e->pc_stage, (size_t)N * K * 44));
     void *const *b = e->qbuf[QF_SD];
-    if (e->att_on)      // objects are attached to links (rr_set_attachments): the carry variant of rr_carry.inc, the same buffers
-        hipLaunchKernelGGL(k_signed_distance_carry, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
+    if (e->att_on)      // objects are attached to links (rr_set_attachments): the CARRY instantiation, the same buffers
+        hipLaunchKernelGGL(k_signed_distance<true>, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
                            (float4 *)b[RR_SD_DEEPEST], (int4 *)b[RR_SD_ID], (float *)b[RR_SD_SIGNED], (int *)b[RR_SD_STATUS],
                            postures ? (float4 *)nullptr : (float4 *)b[RR_SD_POINTS], (const float *)e->att_table);
     else
-        hipLaunchKernelGGL(k_signed_distance, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
+        hipLaunchKernelGGL(k_signed_distance<false>, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
                            (float4 *)b[RR_SD_DEEPEST], (int4 *)b[RR_SD_ID], (float *)b[RR_SD_SIGNED], (int *)b[RR_SD_STATUS],
-                           postures ? (float4 *)nullptr : (float4 *)b[RR_SD_POINTS]);
+                           postures ? (float4 *)nullptr : (float4 *)b[RR_SD_POINTS], (const float *)nullptr);
     HIPCHK(hipGetLastError());
     e->qk[QF_SD] = K;
     return st.wait();
@@ -1823,17 +1823,18 @@ int rr_signed_gradient(rr_env *e, const float *postures, int32_t n_postures, int
     const float *src = postures;
     RRCHK(st.in(src, e->pc_stage, (size_t)N * K * 44));
     void *const *b = e->qbuf[QF_SD], *const *g = e->qbuf[QF_SG];
-    if (e->att_on)      // objects are attached to links (rr_set_attachments): the carry variant of rr_carry.inc, the same buffers
-        hipLaunchKernelGGL(k_signed_gradient_carry, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
+    if (e->att_on)      // objects are attached to links (rr_set_attachments): the CARRY instantiation, the same buffers
+        hipLaunchKernelGGL(k_signed_gradient<true>, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
                            (float4 *)b[RR_SD_DEEPEST], (int4 *)b[RR_SD_ID], (float *)b[RR_SD_SIGNED], (int *)b[RR_SD_STATUS],
                            postures ? (float4 *)nullptr : (float4 *)b[RR_SD_POINTS], margin,
                            (float *)g[RR_SG_GRADIENT], (float *)g[RR_SG_COST], postures ? (float *)nullptr : (float *)g[RR_SG_PAIR_GRADIENT],
                            (const float *)e->att_table);
     else
-        hipLaunchKernelGGL(k_signed_gradient, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
+        hipLaunchKernelGGL(k_signed_gradient<false>, dim3((unsigned)N * K), dim3(SD_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, src, K,
                            (float4 *)b[RR_SD_DEEPEST], (int4 *)b[RR_SD_ID], (float *)b[RR_SD_SIGNED], (int *)b[RR_SD_STATUS],
                            postures ? (float4 *)nullptr : (float4 *)b[RR_SD_POINTS], margin,
-                           (float *)g[RR_SG_GRADIENT], (float *)g[RR_SG_COST], postures ? (float *)nullptr : (float *)g[RR_SG_PAIR_GRADIENT]);
+                           (float *)g[RR_SG_GRADIENT], (float *)g[RR_SG_COST], postures ? (float *)nullptr : (float *)g[RR_SG_PAIR_GRADIENT],
+                           (const float *)nullptr);
     HIPCHK(hipGetLastError());
     e->qk[QF_SD] = e->qk[QF_SG] = K;
     return st.wait();
@@ -1875,8 +1876,9 @@ int rr_swept_clearance(rr_env *e, const float *segments, int32_t n_segments, int
     const float *src = segments;
     RRCHK(st.in(src, e->sw_stage, (size_t)N * K * 88));
     void *const *b = e->qbuf[QF_SW];
-    hipLaunchKernelGGL(k_swept_clearance, dim3((unsigned)N * K), dim3(SWEEP_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, e->sw_reach_dev, src, K,
-                       safety, tolerance, (float *)b[RR_SW_STOP], (float4 *)b[RR_SW_HIT], (int4 *)b[RR_SW_ID], (float *)b[RR_SW_FREE]);
+    hipLaunchKernelGGL(k_swept_clearance<false>, dim3((unsigned)N * K), dim3(SWEEP_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, e->sw_reach_dev, src, K,
+                       safety, tolerance, (float *)b[RR_SW_STOP], (float4 *)b[RR_SW_HIT], (int4 *)b[RR_SW_ID], (float *)b[RR_SW_FREE],
+                       (const float *)nullptr, (const SweepChain *)nullptr);
     HIPCHK(hipGetLastError());
     e->qk[QF_SW] = K;
     return st.wait();
@@ -2013,10 +2015,10 @@ int rr_get_attachments(rr_env *e, int32_t *link_out, float *rel_pose_out) {
     return RR_OK;
 }
 
-// ---- swept clearance with carried objects (rr_csweep.inc) -------------------------------------------------------------------------------
-// The chain table of k_carried_sweep on first use, all or nothing: chain[k][b] = the sum of |jpos[m]| over the bodies m from b up to,
+// ---- swept clearance with carried objects (rr_sweep.inc, CARRY) -------------------------------------------------------------------------
+// The chain table of k_swept_clearance<true> on first use, all or nothing: chain[k][b] = the sum of |jpos[m]| over the bodies m from b up to,
 // but not including, k -- the term the reach loop of the model parse adds, in its order -- in float64 and rounded up; 0 where joint k is
-// not an ancestor-or-self of body b.  A table of its own: SweepReach, which k_swept_clearance reads, keeps its size.
+// not an ancestor-or-self of body b.  A table of its own: SweepReach, which both instantiations read, keeps its size.
 static int ensure_sweep_chain(rr_env *e, const char *who) {
     if (e->sw_chain_dev) return RR_OK;
     e->sw_chain = {};
@@ -2035,7 +2037,7 @@ static int ensure_sweep_chain(rr_env *e, const char *who) {
 }
 
 // rr_swept_clearance with the carried objects moving.  Arguments, refusals, staging, buffers and the stream contract are that call's;
-// with the attachments off it IS that call.  With them on, k_carried_sweep reads in addition the attachment table and the chain table
+// with the attachments off it IS that call.  With them on, k_swept_clearance<true> reads in addition the attachment table and the chain table
 // and writes the same four buffers and nothing else.
 int rr_carried_sweep(rr_env *e, const float *segments, int32_t n_segments, int32_t on_device, float safety, float tolerance) {
     if (!e) return fail(RR_EINVAL, "rr_carried_sweep: null env");
@@ -2052,7 +2054,7 @@ int rr_carried_sweep(rr_env *e, const float *segments, int32_t n_segments, int32
     const float *src = segments;
     RRCHK(st.in(src, e->sw_stage, (size_t)N * K * 88));
     void *const *b = e->qbuf[QF_SW];
-    hipLaunchKernelGGL(k_carried_sweep, dim3((unsigned)N * K), dim3(SWEEP_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, e->sw_reach_dev, src, K,
+    hipLaunchKernelGGL(k_swept_clearance<true>, dim3((unsigned)N * K), dim3(SWEEP_THREADS), 0, e->stream, e->B, e->P, e->D, e->dist_tab_dev, Q, e->sw_reach_dev, src, K,
                        safety, tolerance, (float *)b[RR_SW_STOP], (float4 *)b[RR_SW_HIT], (int4 *)b[RR_SW_ID], (float *)b[RR_SW_FREE],
                        (const float *)e->att_table, (const SweepChain *)e->sw_chain_dev);
     HIPCHK(hipGetLastError());

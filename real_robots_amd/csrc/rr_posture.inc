@@ -1,4 +1,4 @@
-// rr_posture.inc -- part of realrobot.hip (included there, behind rr_dist.inc; not a stand-alone translation unit).
+// rr_posture.inc -- part of realrobot.hip (included there, behind rr_dist.inc and rr_carry.inc; not a stand-alone translation unit).
 // k_posture_clearance: the clearance of K candidate joint postures per env of the whole batch (rr_posture_clearance, realrobot.h):
 // posture (e, k) is env e's present state with its eleven joint columns taken from the caller's tensor, the objects where they are;
 // per posture the distance and status of every pair of the table (rr_set_distance_pairs) and the full record of the NEAREST pair,
@@ -23,6 +23,15 @@
 //      the pair loop has no early exit.
 // No atomics, fixed order: row (e, k) is a function of (env e's objects, posture (e, k), the table) alone.  Loop bounds are
 // constants or Q; no value of the tensor or the state forms an address.
+//
+// WITH CARRIED OBJECTS (rr_set_attachments; rr_carry.inc's header).  The kernel is a template <bool CARRY>: <false> is the text above and
+// nothing else, <true> is launched in its place while the handle's attachments are on.  Phase 2 then has one more barrier: thread 0
+// rolls the forward kinematics, and behind the barrier threads 1..NOBJ stage the objects with carry_stage_object, an attached one from
+// the frames just rolled and its table row, a free one by the operations of <false>.  Everything else is the one text; the carry-only
+// statements sit under `if constexpr (CARRY)`, the staging of <false> under `!CARRY`, and the phases stay written out inside the
+// template: both instantiations then compile to the instructions of two kernels written out separately (tools/compare_kernel_asm.py
+// --map), which a phase shared through a function did not (phase 2 above, DESIGN.md).  att, the table, is the last argument, null and
+// unread without CARRY.
 #define PC_THREADS 256
 #define PC_WAVES (PC_THREADS / 64)
 #define PC_PARK 20           // floats a wave parks: the record 0..11, key 12, j 13, status 14, body A 15, body B 16
@@ -30,10 +39,12 @@
 __device__ __forceinline__ float pc_uniform(const float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
 __device__ __forceinline__ float4 pc_uniform(const float4 x) { return make_float4(pc_uniform(x.x), pc_uniform(x.y), pc_uniform(x.z), pc_uniform(x.w)); }
 
+template <bool CARRY>
 __global__ void __launch_bounds__(PC_THREADS) k_posture_clearance(BodyParams B, SimParams P, DevPtrs D, const DistTable *__restrict__ tab, int Q,
                                                                   const float *__restrict__ postures /*[N][K][11]*/, int K,
                                                                   float4 *__restrict__ out_near /*[N][K][3]*/, int4 *__restrict__ out_id /*[N][K]*/,
-                                                                  float *__restrict__ out_dist /*[N][K][Q]*/, int *__restrict__ out_status /*[N][K][Q]*/) {
+                                                                  float *__restrict__ out_dist /*[N][K][Q]*/, int *__restrict__ out_status /*[N][K][Q]*/,
+                                                                  const float *__restrict__ att /*[N][NOBJ][ATT_ROW]; null and unread without CARRY*/) {
     static_assert(RAY_ST == 32 && NB == 11 && ST_OPOS == 2 * NB, "staged slot s is the posture's column s (s < 11) or state slot s + 11");
     __shared__ float s_st[RAY_ST][1];
     __shared__ float s_fr[1][RAY_FR];
@@ -70,7 +81,7 @@ __global__ void __launch_bounds__(PC_THREADS) k_posture_clearance(BodyParams B, 
             for (int k = 0; k < 9; k++) fr[9 * b + k] = Rb.m[k];
             fr[RAY_FR_P + 3 * b] = pb.x; fr[RAY_FR_P + 3 * b + 1] = pb.y; fr[RAY_FR_P + 3 * b + 2] = pb.z;
         }
-    } else if (tid < 1 + NOBJ) {
+    } else if (!CARRY && tid < 1 + NOBJ) {
         const int o = tid - 1;
         const m3 Ro = nc::quat_to_m3(s_st[20 + 4 * o][0], s_st[21 + 4 * o][0], s_st[22 + 4 * o][0], s_st[23 + 4 * o][0]);
         float *ob = s_ob[0] + 12 * o;
@@ -79,6 +90,10 @@ __global__ void __launch_bounds__(PC_THREADS) k_posture_clearance(BodyParams B, 
         ob[9] = s_st[11 + 3 * o][0]; ob[10] = s_st[12 + 3 * o][0]; ob[11] = s_st[13 + 3 * o][0];
     }
     __syncthreads();
+    if constexpr (CARRY) {
+        if (tid >= 1 && tid < 1 + NOBJ) carry_stage_object(att, env, tid - 1, s_st, s_fr[0], s_ob[0]);
+        __syncthreads();
+    }
     // 3
     const float maxd = tab->max_distance;
     const bool cull = maxd > 0.0f && maxd < INFINITY;

@@ -38,6 +38,8 @@
 // No atomics, no LDS but the reduction's, fixed order: a row is a function of (env e's objects, its joints, the table) alone.  Loop
 // bounds are constants, Q, or counts of ballot bits (at most 64); no value of the tensor or the state forms an address, vertex and
 // slot indices come out of compares over lane numbers and are masked to the wave.
+// With carried objects the kernel is k_posture_clearance's template <bool CARRY> over again (rr_posture.inc's header): <true> stages
+// the objects behind one more barrier in phase 2 with carry_stage_object (rr_carry.inc), <false> is the text above and nothing else.
 #define SD_THREADS 256
 #define SD_WAVES (SD_THREADS / 64)
 #define SD_PARK 20           // floats a wave parks: the record 0..11, key 12, j 13, status 14, body A 15, body B 16
@@ -331,11 +333,13 @@ __device__ __forceinline__ SdItem sd_pair(const ShapeData *__restrict__ S, const
     return R;
 }
 
+template <bool CARRY>
 __global__ void __launch_bounds__(SD_THREADS) k_signed_distance(BodyParams B, SimParams P, DevPtrs D, const DistTable *__restrict__ tab, int Q,
                                                                 const float *__restrict__ postures /*[N][K][11] or null: the present state, K = 1*/, int K,
                                                                 float4 *__restrict__ out_deep /*[N][K][3]*/, int4 *__restrict__ out_id /*[N][K]*/,
                                                                 float *__restrict__ out_signed /*[N][K][Q]*/, int *__restrict__ out_status /*[N][K][Q]*/,
-                                                                float4 *__restrict__ out_pts /*[N][Q][3] or null*/) {
+                                                                float4 *__restrict__ out_pts /*[N][Q][3] or null*/,
+                                                                const float *__restrict__ att /*[N][NOBJ][ATT_ROW]; null and unread without CARRY*/) {
     static_assert(RAY_ST == 32 && NB == 11 && ST_OPOS == 2 * NB, "staged slot s is joint s (s < 11) or state slot s + 11");
     static_assert(64 * DIST_TRIPS == VMAXC && 4 + SD_TRIP_CAP <= 64, "a lane holds three vertices of a shape and one of the polytope");
     __shared__ float s_st[RAY_ST][1];
@@ -373,7 +377,7 @@ __global__ void __launch_bounds__(SD_THREADS) k_signed_distance(BodyParams B, Si
             for (int k = 0; k < 9; k++) fr[9 * b + k] = Rb.m[k];
             fr[RAY_FR_P + 3 * b] = pb.x; fr[RAY_FR_P + 3 * b + 1] = pb.y; fr[RAY_FR_P + 3 * b + 2] = pb.z;
         }
-    } else if (tid < 1 + NOBJ) {
+    } else if (!CARRY && tid < 1 + NOBJ) {
         const int o = tid - 1;
         const m3 Ro = nc::quat_to_m3(s_st[20 + 4 * o][0], s_st[21 + 4 * o][0], s_st[22 + 4 * o][0], s_st[23 + 4 * o][0]);
         float *ob = s_ob[0] + 12 * o;
@@ -382,6 +386,10 @@ __global__ void __launch_bounds__(SD_THREADS) k_signed_distance(BodyParams B, Si
         ob[9] = s_st[11 + 3 * o][0]; ob[10] = s_st[12 + 3 * o][0]; ob[11] = s_st[13 + 3 * o][0];
     }
     __syncthreads();
+    if constexpr (CARRY) {
+        if (tid >= 1 && tid < 1 + NOBJ) carry_stage_object(att, env, tid - 1, s_st, s_fr[0], s_ob[0]);
+        __syncthreads();
+    }
     // 3
     const float maxd = tab->max_distance;
     const bool cull = maxd > 0.0f && maxd < INFINITY;

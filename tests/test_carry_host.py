@@ -1,6 +1,6 @@
 """Tests of the C boundary of the carried objects (rr_set_attachments, include/realrobot.h) that need no GPU: the header, the binding,
-the refusals that need no handle, the dispatch of the three posture queries and the sweep's refusal on the source, the Python-side
-argument checks and `carry_pairs`.  The GPU side is tests/test_gpu_carry.py, the reference's own tests tests/test_numpy_carry.py."""
+the refusals that need no handle, the dispatch of the three posture queries and the sweep's refusal on the source, the shape of the
+four kernel templates (`carry_only_violations`), the Python-side argument checks and `carry_pairs`.  The GPU side is tests/test_gpu_carry.py, the reference's own tests tests/test_numpy_carry.py."""
 import ctypes as C
 import inspect
 import os
@@ -14,7 +14,9 @@ from real_robots_amd.batched import BatchedREALRobotEnv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ('rr_set_attachments', 'rr_get_attachments')
-KERNELS = ('k_posture_clearance_carry', 'k_signed_distance_carry', 'k_signed_gradient_carry', 'k_attach_capture')
+TEMPLATES = {'rr_posture.inc': 'k_posture_clearance', 'rr_signed.inc': 'k_signed_distance', 'rr_grad.inc': 'k_signed_gradient', 'rr_sweep.inc': 'k_swept_clearance'}
+TABLE_KERNELS = ('k_attach_set', 'k_attach_capture')
+CARRY_NAME = re.compile(r'\b(att|s_att|chain|cs_\w+|carry_stage_object)\b')
 
 
 def _read(*parts):
@@ -23,6 +25,46 @@ def _read(*parts):
 
 def _body(src, start, end):
     return src[src.index(start):src.index(end)]
+
+
+def _code(text):
+    """the text without its comments, line for line and column for column"""
+    text = re.sub(r'/\*.*?\*/', lambda m: re.sub(r'[^\n]', ' ', m.group(0)), text, flags=re.S)
+    return '\n'.join(l.split('//')[0] for l in text.splitlines())
+
+
+def _blocks(code, opener):
+    """the (start, end) spans of the brace blocks that `opener` opens, by counting braces"""
+    spans = []
+    for m in re.finditer(re.escape(opener) + r'\s*\{', code):
+        depth, i = 1, m.end()
+        while depth:
+            depth += {'{': 1, '}': -1}.get(code[i], 0)
+            i += 1
+        spans.append((m.start(), i))
+    return spans
+
+
+def carry_only_violations(text):
+    """What a kernel template <bool CARRY> says of carried objects outside the places for it.  The kernel is the one __global__ of the
+    part, from `template <bool CARRY>` to the end.  Every code line of it that names att, s_att, chain, cs_* or carry_stage_object has
+    to be the kernel's parameter list or lie inside an `if constexpr (CARRY) {...}` block; the one other form is the LDS array that
+    only such blocks name, declared at function scope because they share it and sized by CARRY (`__shared__ T s_att[CARRY ? n : 1];`:
+    an array no statement of the plain instantiation names takes no LDS there, which the kernel descriptors compared by
+    tools/compare_kernel_asm.py show).  Returns the offending lines."""
+    code = _code(text)
+    assert code.count('__global__') == 1 and code.count('template <bool CARRY>') == 1
+    start = code.index('template <bool CARRY>')
+    assert start < code.index('__global__')
+    params = (code.index(')', code.index('__launch_bounds__(', start)) + 1, code.index(') {', start) + 1)      # behind the launch bounds, up to the body's brace
+    inside = _blocks(code, 'if constexpr (CARRY)') + [params]
+    bad = []
+    for m in CARRY_NAME.finditer(code, start):
+        line = code[code.rfind('\n', 0, m.start()) + 1:code.find('\n', m.start())]
+        if any(a <= m.start() < b for a, b in inside) or re.fullmatch(r'\s*__shared__ (int|float) s_att\[CARRY \? [\w *]+ : 1\];\s*', line):
+            continue
+        bad.append(line.strip())
+    return bad
 
 
 def test_header_declares_the_entry_points_and_keeps_the_abi_numbers():
@@ -42,7 +84,9 @@ def test_header_declares_the_entry_points_and_keeps_the_abi_numbers():
                  'N x 192 bytes', 'Out of scope'):
         assert word in doc, word
     v = _read('real_robots_amd', 'csrc', 'realrobot.hip')
-    assert v.index('#include "rr_grad.inc"') < v.index('#include "rr_carry.inc"') < v.index('#include "rr_host.inc"')
+    # what the kernel templates name is declared in front of them
+    order = [v.index('#include "%s"' % f) for f in ('rr_dist.inc', 'rr_carry.inc', 'rr_posture.inc', 'rr_sweep.inc', 'rr_signed.inc', 'rr_grad.inc', 'rr_host.inc')]
+    assert order == sorted(order)
 
 
 def test_binding_lists_and_loads_the_symbols():
@@ -65,14 +109,20 @@ def test_the_queries_dispatch_once_and_the_sweep_refuses():
     src = _read('real_robots_amd', 'csrc', 'rr_host.inc')
     ends = {'rr_posture_clearance': 'int rr_posture_buffer(', 'rr_signed_distance': 'int rr_signed_buffer(', 'rr_signed_gradient': 'int rr_signed_gradient_buffer('}
     for fn, kern in (('rr_posture_clearance', 'k_posture_clearance'), ('rr_signed_distance', 'k_signed_distance'), ('rr_signed_gradient', 'k_signed_gradient')):
+        # one reading of the flag, in front of exactly two launches of the one kernel name, <true> first; the table once, in the <true> launch
         body = _body(src, 'int %s(' % fn, ends[fn])
-        assert body.count('e->att_on') == 1 and body.count('hipLaunchKernelGGL(') == 2, fn
+        assert body.count('e->att_on') == 1 and body.count('hipLaunchKernelGGL(') == 2 == body.count('hipLaunchKernelGGL(%s<' % kern), fn
         at = body.index('if (e->att_on)')
-        carry, plain = body.index('hipLaunchKernelGGL(%s_carry,' % kern), body.index('hipLaunchKernelGGL(%s,' % kern)
-        assert at < carry < body.index('else', carry) < plain and body.count('e->att_table') == 1, fn
+        carry, plain = body.index('hipLaunchKernelGGL(%s<true>,' % kern), body.index('hipLaunchKernelGGL(%s<false>,' % kern)
+        other = body.index('else', carry)
+        assert at < carry < other < plain and body.count('e->att_table') == 1 and carry < body.index('e->att_table') < other, fn
+        assert body[plain:body.index(';', plain)].rstrip().endswith('(const float *)nullptr)'), fn      # the plain launch: null for the added pointer
         assert body.index('ensure_query(') < at and plain < body.index('hipGetLastError')
     sweep = _body(src, 'int rr_swept_clearance(', 'int rr_sweep_reach(')
-    assert sweep.count('e->att_on') == 1 and 'k_swept_clearance_carry' not in src
+    assert sweep.count('e->att_on') == 1 and '_carry,' not in src and '_carry<' not in src
+    assert sweep.count('hipLaunchKernelGGL(') == 1 == sweep.count('hipLaunchKernelGGL(k_swept_clearance<false>,') and 'e->att_table' not in sweep
+    launch = sweep[sweep.index('hipLaunchKernelGGL('):]
+    assert launch[:launch.index(';')].rstrip().endswith('(const float *)nullptr, (const SweepChain *)nullptr)')
     refuse = sweep.index('if (e->att_on)')
     first_effect = min(sweep.index(w) for w in ('ensure_query(', 'hipLaunchKernelGGL', 'st.in('))
     assert refuse < sweep.index('RR_EINVAL', refuse) < sweep.index('rr_set_attachments', refuse) < first_effect
@@ -80,8 +130,15 @@ def test_the_queries_dispatch_once_and_the_sweep_refuses():
     for fn, end in (('rr_closest_points', 'int rr_distance_buffer('), ('rr_step', 'int rr_render(')):
         body = _body(src, 'int %s(' % fn, end)
         assert 'att_' not in body, fn
-    for f in ('rr_fork.inc', 'rr_prep.inc', 'rr_solve.inc', 'rr_collide.inc', 'rr_write.inc', 'rr_state.inc', 'rr_posture.inc', 'rr_signed.inc', 'rr_grad.inc', 'rr_sweep.inc'):
+    for f in ('rr_fork.inc', 'rr_prep.inc', 'rr_solve.inc', 'rr_collide.inc', 'rr_write.inc', 'rr_state.inc'):
         assert 'att' not in re.findall(r'\batt\w*', _read('real_robots_amd', 'csrc', f)), f
+    # the four kernel templates: one __global__ each, and all they say of carried objects is the parameter list or under if constexpr (CARRY)
+    for f, kern in TEMPLATES.items():
+        text = _read('real_robots_amd', 'csrc', f)
+        assert carry_only_violations(text) == [], f
+        code = _code(text)
+        assert re.search(r'template <bool CARRY>\s*__global__ void __launch_bounds__\(\w+\) %s\(' % kern, code), f
+        assert len(_blocks(code, 'if constexpr (CARRY)')) >= 1 and '!CARRY' in code, f      # both kinds of statement exist, each under its guard
     # the setter validates before its first allocation, copy, launch or flag: a refusal changes nothing
     body = _body(src, 'int rr_set_attachments(', 'int rr_get_attachments(')
     first_effect = min(body.index(w) for w in ('ensure_attachments(', 'hipMemcpyAsync', 'hipLaunchKernelGGL', 'e->att_on =', 'e->att_link['))
@@ -89,13 +146,20 @@ def test_the_queries_dispatch_once_and_the_sweep_refuses():
         assert body.index(msg) < first_effect, msg
     assert body.index('!link && !e->att_table') < body.index('ensure_attachments(')         # detaching a table that never was: nothing allocated
     assert 'la_valid' not in body and 'scratch' not in body and 'D.state' not in body
-    # the kernels: a part of their own, in the scratch gate, the originals' pair functions called
-    k = _read('real_robots_amd', 'csrc', 'rr_carry.inc')
-    code = '\n'.join(l.split('//')[0] for l in k.splitlines())
-    assert 'atomic' not in code and code.count('dist_pair(') == 1 and code.count('sd_pair(') == 2
+    # the carry code: no atomics; the pair functions and the staging are called, once per kernel, never written out a second time
+    k = _code(_read('real_robots_amd', 'csrc', 'rr_carry.inc'))
+    assert 'atomic' not in k and k.count('__device__ __forceinline__ int carry_stage_object(') == 1 and 'dist_pair(' not in k and 'sd_pair(' not in k
+    assert '_carry(' not in k and k.count('__global__') == len(TABLE_KERNELS)
+    calls = {f: _code(_read('real_robots_amd', 'csrc', f)) for f in TEMPLATES}
+    for f, code in calls.items():
+        kernel = code[code.index('template <bool CARRY>'):]
+        assert 'atomic' not in kernel.lower() and kernel.count('carry_stage_object(') == 1, f
+        assert kernel.count('dist_pair(') == (f in ('rr_posture.inc', 'rr_sweep.inc')) and kernel.count('sd_pair(') == (f in ('rr_signed.inc', 'rr_grad.inc')), f
     gate = _read('tools', 'check_scratch.py')
-    for name in KERNELS:
-        assert '__global__' in code and name + '(' in code and "'%s'" % name in gate, name
+    for name in TABLE_KERNELS:
+        assert name + '(' in k and "'%s'" % name in gate, name
+    for name in TEMPLATES.values():                                                      # (the gate matches by substring: both instantiations)
+        assert "'%s'" % name in gate and "'%s_carry'" % name not in gate, name
 
 
 def test_python_side_arguments_need_no_device():

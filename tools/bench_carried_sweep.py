@@ -9,9 +9,10 @@ events; the medians give the milliseconds per call:
   (a) one carried_sweep call on the attached handle;
   (b) what one does today: eight posture_clearance calls at K = 32, the 32 uniform samples of each of the eight segments, on the
       attached handle;
-  (c) the cost of the restated kernel alone: carried_sweep on an attached handle whose envs are all masked free (k_carried_sweep runs,
-      every row stages its objects from the state) against swept_clearance on a handle that never attached (k_swept_clearance), the
-      same states, table and segments; their bytes are compared as well.
+  (c) the cost of the CARRY instantiation alone: carried_sweep on an attached handle whose envs are all masked free
+      (k_swept_clearance<true> runs, every row stages its objects from the state) against swept_clearance on a handle that never
+      attached (k_swept_clearance<false>, the other instantiation of the one kernel template), the same states, table and segments;
+      their bytes are compared as well (`restated_over_original` in the output: the key keeps the name it has in the recorded profile).
 Also the statuses, the steps and the pair evaluations per segment, the share of rows at the step cap, and how many segments the
 sampling check calls free that the sweep stops.
 
@@ -23,7 +24,7 @@ import sys
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--out', default=None)
-ap.add_argument('--label', default='shipped: k_swept_clearance restated, the objects re-staged at every step from the table rows in LDS')
+ap.add_argument('--label', default='shipped: k_swept_clearance<true>, the objects re-staged at every step from the table rows in LDS')
 ap.add_argument('--reps', type=int, default=11)
 ap.add_argument('--envs', type=int, default=4096)
 args = ap.parse_args()

@@ -2,9 +2,10 @@
 """Cost of carried objects in the posture queries on the MI355X: 4096 envs, 3 objects, the states of step 170 of `synthetic_actions`,
 K = 32 candidate postures per env drawn around each env's own (sigma 0.1 rad), margin 0.05 m; on the `collision` pair table (Q = 92)
 and on `carry_pairs(['cube'], exclude_links=<the two finger tips>)`.  Per table, time per call of
-  (a) signed_distance_gradient with the feature off -- the parent's kernel (its per-item time is to be read against
+  (a) signed_distance_gradient with the feature off -- k_signed_gradient<false>, the kernel as it was before carried objects (its per-item time is to be read against
       profiles/signed_gradient_bench.json; (a) is also taken at that file's K = 8 on the collision table);
-  (b) the same call with every env's cube attached to link 8 (captured from the state);
+  (b) the same call with every env's cube attached to link 8 (captured from the state) -- k_signed_gradient<true>, the other
+      instantiation of the one kernel template;
   (c) what one did before: 32 x (write_state of the posture and the composed cube pose + a present-state signed_distance_gradient),
       the composed poses prepared beforehand on the device (link poses of posture_kinematics o rel), not timed.
 (a) and (b) ALTERNATE on the same handle -- off, on, off, on --, each turn WARMUP calls and then REPS windows of back-to-back calls on

@@ -12,8 +12,9 @@ import sys
 HOT = ('k_prep_a16', 'k_prep_b16', 'k_prep_ab16', 'k_collide', 'k_solve', 'k_raster', 'k_render_list', 'k_shade', 'k_static_copy', 'k_render_setup',
        'k_ik', 'k_plan_macro', 'k_fork', 'k_kinematics', 'k_state_rw', 'k_ray_cast', 'k_closest_points', 'k_posture_clearance', 'k_signed_distance', 'k_signed_gradient', 'k_swept_clearance',
        'k_posture_kinematics', 'k_posture_ik', 'k_posture_dynamics', 'k_joint_torque', 'k_ext_wrench',
-       'k_posture_clearance_carry', 'k_signed_distance_carry', 'k_signed_gradient_carry', 'k_attach_capture', 'k_attach_set',
-       'k_carried_sweep', 'k_macro_decide', 'k_macro_replan')
+       'k_attach_capture', 'k_attach_set', 'k_macro_decide', 'k_macro_replan')
+# (a name matches by substring: both instantiations of a kernel template -- k_posture_clearance, k_signed_distance, k_signed_gradient and
+# k_swept_clearance, <false> and <true> with carried objects -- are under their one name)
 
 
 def main():
