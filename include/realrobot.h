@@ -1415,6 +1415,59 @@ int rr_macro_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
 /* Synchronising copy of a whole RR_MACRO_* buffer to host memory. */
 int rr_macro_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
 
+/* Device-resident cartesian actions: REALRobotEnv.step_cartesian (env.py:358-386) for the whole batch in ONE call per step, the IK
+ * decision of env.py:358-386 taken on the device.  The handle keeps, per env, a REQUEST RECORD f32 [7] {x, y, z, qx, qy, qz, qw} (all NaN
+ * on creation), the SOLUTION f32 [7] of that request (the reference's last_ik) and its residual.  Buffers of rr_cartesian_buffer: */
+enum {
+    RR_CART_REQUEST = 0,    /* f32 [N, 7]        the request each env's solution was made for; NaN: none, or invalidated */
+    RR_CART_SOLUTION = 1,   /* f32 [N, 7]        the stored solution: the arm joints a non-idle env is commanded to */
+    RR_CART_RESIDUAL = 2,   /* f32 [N]           ik_solve's returned error of that solution (rr_ik's err_out) */
+    RR_CART_SOLVED = 3,     /* u8  [N]           1 where the last rr_step_cartesian solved, 0 elsewhere (idle envs included) */
+    RR_CART_COUNT = 4
+};
+/* cartesian: f32 [N][7]; gripper: f32 [N][2]; idle: u8 [N] or NULL (none).  ONE flag covers the three arrays: with on_device != 0 they
+ * are device memory, read in place on the library's stream WITHOUT a wait (produce them on that stream or synchronise first; keep them
+ * unchanged until later work on that stream), as rr_step_macro reads its request; otherwise host arrays, staged, and the call waits at
+ * its end.  Per env (env.py:358-386):
+ *   idle[e] != 0 (the reference's `cartesian_command is None`, env.py:359-361): the command is zeros(9); record and solution untouched.
+ *   otherwise: same = all seven floats == the record (IEEE ==, as np.all(a == b): -0.0 equals 0.0, a NaN equals nothing -- a NaN request
+ *   solves on every step; env.py:366-369).  When same, the arm command is the stored solution: it is NOT solved again from the new
+ *   joints, exactly as the reference reuses last_ik (env.py:370).  When not same, the env is solved from its PRESENT joints by rr_ik's rule
+ *   -- ik_solve with no predecessor, seeds {present joints, elbow-up} or one seed under RR_SOLVER_IK_SINGLE_SEED, maxNumIterations 1000
+ *   (env.py:372-375); rr_ik's joints and residual bit for bit --, the request goes into the record, the result into the solution, the
+ *   error into the residual (env.py:376-378).
+ *   The command is [solution[0..6], gripper[0], gripper[1]] (env.py:380-381): the gripper is read every step and is no part of the record.
+ * The step itself is rr_step on that command (env.py:386), as in rr_step_macro; render_mode / render_flags_host as there.  With device
+ * arguments nothing waits and nothing is read back: the list of needing envs and its length stay on the device.
+ * Values are not validated (as in rr_ik); a non-finite command is rr_step's business.  The four buffers, the list and the staging of host
+ * arguments are allocated by the first call as one group, all or nothing.
+ * Errors: RR_EINVAL with every env and every record untouched for a null env, a null cartesian or gripper, a bad render_mode
+ * (rr_step_plan's rule), and for a mixed set: an array that the runtime knows to live on the other side than on_device says (pageable
+ * host memory under on_device != 0, device memory under on_device == 0; pinned and managed memory serve either side); RR_EDEVICE for a
+ * failed allocation or a device error.
+ * Resets (rr_reset, auto-resets), rr_write_state, rr_set_state, forks / rr_copy_envs, snapshot loads and checkpoint restores KEEP the
+ * record and solution of the destination env: policy state, like rr_step_macro's record.  The reference does not solve again on reset
+ * either (env.py:358-386 know no reset); a caller who wants that calls rr_cartesian_invalidate.  rr_step, rr_step_macro and rr_ik do not
+ * know these buffers and change none of them: mixing them with rr_step_cartesian on one handle is legal.
+ * Out of scope: a cartesian action type of the vector env; targets for other links or points (rr_posture_ik has them); clamping to joint
+ * limits (the reference wraps); any change of rr_ik or the ik defaults. */
+int rr_step_cartesian(rr_env *env,
+                      const float *cartesian /* f32 [N][7] {x, y, z, qx, qy, qz, qw} */,
+                      const float *gripper /* f32 [N][2] */,
+                      const uint8_t *idle /* u8 [N] or NULL */,
+                      int32_t on_device, int32_t render_mode, const uint8_t *render_flags_host);
+/* NaN into the record rows of the envs whose mask byte is non-zero (u8 [N], host or device; NULL: all envs): the next non-idle
+ * rr_step_cartesian solves them from their present joints (env.py:358-386: "solve again after a reset").  Solutions and residuals are not
+ * touched.  A device mask is read in place without a wait; with a host mask the call waits.  A handle without a record has nothing to
+ * invalidate. */
+int rr_cartesian_invalidate(rr_env *env, const uint8_t *env_mask, int32_t mask_on_device);
+/* Zero-copy device pointer + size of an RR_CART_* buffer (the state of env.py:358-386 for the batch), valid until rr_destroy (allocates
+ * the group on first use: record NaN, the others zero).  STREAM CONTRACT as for the other device buffers.  Not a family of the query
+ * table: an accessor pair of its own, like rr_macro_buffer / rr_macro_copy_to_host. */
+int rr_cartesian_buffer(rr_env *env, int32_t which, void **dev_ptr, size_t *bytes);
+/* Synchronising copy of a whole RR_CART_* buffer (env.py:358-386's requested_coords / requested_orient / last_ik) to host memory. */
+int rr_cartesian_copy_to_host(rr_env *env, int32_t which, void *dst, size_t bytes);
+
 /* Per-kernel device timing with HIP events on the library's stream (bench.py roofline leg).
  * After rr_set_timing(env, 1), each rr_step/rr_render records events; rr_get_timing returns accumulated
  * milliseconds and launch counts per kernel since the last call and resets them.

@@ -52,7 +52,8 @@ SYMBOLS = ('rr_create', 'rr_destroy', 'rr_set_stream', 'rr_reset', 'rr_set_objec
            'rr_set_joint_torques', 'rr_get_joint_torques', 'rr_joint_torque_buffer',
            'rr_set_external_wrenches', 'rr_get_external_wrenches', 'rr_external_wrench_buffer',
            'rr_set_attachments', 'rr_get_attachments', 'rr_carried_sweep',
-           'rr_step_macro', 'rr_macro_invalidate', 'rr_macro_buffer', 'rr_macro_copy_to_host')
+           'rr_step_macro', 'rr_macro_invalidate', 'rr_macro_buffer', 'rr_macro_copy_to_host',
+           'rr_step_cartesian', 'rr_cartesian_invalidate', 'rr_cartesian_buffer', 'rr_cartesian_copy_to_host')
 # rr_set_object_dynamics / rr_get_object_dynamics: one row of f32 per (env, object)
 DYN_ROW = ('mass', 'ixx', 'iyy', 'izz', 'friction', 'restitution', 'rolling', 'spinning')
 # rr_set_env_actuators / rr_get_env_actuators: one row of f32 per (env, movable joint), the joints in the order of q[11] of RR_F_STATE
@@ -68,6 +69,10 @@ EP_NAMES = ('score', 'reward', 'done', 'goal_index', 'episode', 'final_obs', 'go
 (MACRO_REQUEST, MACRO_POSITION, MACRO_REPLANNED, MACRO_PLAN) = range(4)
 MACRO_NAMES = ('request', 'position', 'replanned', 'plan')
 PLAN_LEN = 1000
+# buffers of rr_cartesian_buffer (the RR_CART_* enum: cartesian actions decided on the device): request f32 [N, 7], solution f32 [N, 7],
+# residual f32 [N], solved u8 [N]
+(CART_REQUEST, CART_SOLUTION, CART_RESIDUAL, CART_SOLVED) = range(4)
+CARTESIAN_NAMES = ('request', 'solution', 'residual', 'solved')
 GOAL_SCORED, GOAL_HAS_START = 1, 2      # rr_set_goals flag bits: the object counts in the score / has a start pose
 # buffers of rr_kinematic_buffer (the RR_KIN_* enum), per env: joint_vel [11], link_pose [17, 7], link_vel [17, 6], obj_vel [n_obj, 6],
 # point_pos [P, 3], point_vel [P, 6], jacobian [P, 6, 11] for the P points in force (rr_set_kinematic_points)
@@ -321,6 +326,10 @@ def load_library():
     L.rr_macro_invalidate.argtypes = [vp, vp, i32]
     L.rr_macro_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rr_macro_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
+    L.rr_step_cartesian.argtypes = [vp, vp, vp, vp, i32, i32, vp]
+    L.rr_cartesian_invalidate.argtypes = [vp, vp, i32]
+    L.rr_cartesian_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rr_cartesian_copy_to_host.argtypes = [vp, i32, vp, C.c_size_t]
     for fam in QUERY_FAMILIES.values():
         getattr(L, fam.buffer).argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
         getattr(L, fam.copy_to_host).argtypes = [vp, i32, vp, C.c_size_t]

@@ -1817,6 +1817,94 @@ class BatchedREALRobotEnv:
         nat.check(self.L.rr_macro_buffer(self.h, int(which), C.byref(p), C.byref(n)))
         return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
 
+    # ------------------------------------------------------------------ cartesian actions decided on the device
+    @classmethod
+    def _cartesian_args(cls, N, cartesian_commands, gripper_commands, idle):
+        """The arguments of `step_cartesian_device` for a handle of N envs -> (address of the targets, address of the gripper
+        commands, address of the idle mask or None, on the device, keep-alive objects).  Every violation -- shape, dtype, contiguity,
+        the three arrays not on one side -- is a ValueError raised here, before the native call; nothing of a handle is needed."""
+        keep, ptrs, sides = [], [], []
+        for a, name, shape in ((cartesian_commands, 'cartesian_commands', (N, 7)), (gripper_commands, 'gripper_commands', (N, 2))):
+            if _on_device(a):
+                p, d, k = cls._state_arg(None, a, name, ('float32',), shape)
+            else:
+                if hasattr(a, 'is_cuda') and hasattr(a, 'numpy'):      # a CPU torch tensor
+                    a = a.numpy()
+                a = np.asarray(a)
+                if a.dtype.kind not in 'fiu':
+                    raise ValueError("%s must be a real numeric array of shape %s, not dtype %s" % (name, shape, a.dtype))
+                if a.shape != shape:
+                    raise ValueError("%s must have shape %s, not %s" % (name, shape, a.shape))
+                with np.errstate(over='ignore'):
+                    k = np.ascontiguousarray(a, dtype=np.float32)
+                p, d = k.ctypes.data, 0
+            keep.append(k), ptrs.append(p), sides.append((name, d))
+        ip = None
+        if idle is not None:
+            if hasattr(idle, 'is_cuda') and hasattr(idle, 'numpy') and not idle.is_cuda:
+                idle = idle.numpy()
+            ip, d, k = cls._state_arg(None, idle, 'idle', ('uint8', 'bool'), (N,))
+            keep.append(k), sides.append(('idle', d))
+        if len({d for _, d in sides}) != 1:
+            raise ValueError("step_cartesian_device: cartesian_commands, gripper_commands and idle must live on the same side (%s)"
+                             % ', '.join("%s on the %s" % (n, ('host', 'device')[d]) for n, d in sides))
+        return ptrs[0], ptrs[1], ip, sides[0][1], keep
+
+    def step_cartesian_device(self, cartesian_commands, gripper_commands, idle=None, render=False):
+        """Batched REALRobotEnv.step_cartesian (env.py:358-386) with the IK decision taken on the device (rr_step_cartesian): one
+        call per step, no host bookkeeping.  cartesian_commands: [N, 7] xyz + xyzw quaternion, gripper_commands: [N, 2] -- float32
+        CUDA torch tensors or `__cuda_array_interface__` objects (C-contiguous; read in place on the library's stream without
+        waiting and without a read-back: produce them on that stream or synchronise first), or numpy arrays / CPU tensors (converted
+        to float32, staged, synchronous); idle: bool / uint8 [N] or None.  The three live on one side.  A flagged env steps with
+        zeros(9) and keeps its request record and solution (`cartesian_command is None`, env.py:359-361).  Every other env whose
+        request differs from its record (IEEE ==: -0.0 equals 0.0, NaN never equals) is solved from its present joints by `ik()`'s
+        rule, bit for bit; an env whose request equals its record is commanded to the stored solution and NOT solved again, as the
+        reference reuses last_ik.  The command is [solution, gripper]: the gripper is read every step and is no part of the
+        record.  render as in `step_plan`.  Resets, `write_state`, forks, snapshots and checkpoints keep record and solution (policy
+        state): `cartesian_invalidate` asks for a new solve.  `ik()` and `REALRobotEnv.step_cartesian` do not know the record."""
+        flags = None
+        if isinstance(render, np.ndarray) and render.size > 1:
+            flags = np.ascontiguousarray(render, dtype=np.uint8)
+            if flags.shape != (self.N,):
+                raise ValueError("render flags must have shape (%d,)" % self.N)
+            mode = 2
+        else:
+            mode = 1 if np.any(render) else 0
+        cp, gp, ip, on_dev, keep = self._cartesian_args(self.N, cartesian_commands, gripper_commands, idle)
+        nat.check(self.L.rr_step_cartesian(self.h, cp, gp, ip, on_dev, mode, flags.ctypes.data if flags is not None else None))
+        del keep
+
+    def cartesian_invalidate(self, env_mask=None):
+        """NaN into the request record of the masked envs (bool / uint8 [N], host or device; None: all envs): the next non-idle
+        `step_cartesian_device` solves them from their present joints -- "solve again after a reset" (rr_cartesian_invalidate)."""
+        if env_mask is None:
+            nat.check(self.L.rr_cartesian_invalidate(self.h, None, 0))
+            return
+        if hasattr(env_mask, 'is_cuda') and hasattr(env_mask, 'numpy') and not env_mask.is_cuda:
+            env_mask = env_mask.numpy()
+        mp, m_dev, keep = self._state_arg(env_mask, 'env_mask', ('uint8', 'bool'), (self.N,))
+        nat.check(self.L.rr_cartesian_invalidate(self.h, mp, m_dev))
+        del keep
+
+    def cartesian_buffer(self, name, host=False):
+        """A buffer of the device-resident cartesian actions (rr_cartesian_buffer), by name (`_native.CARTESIAN_NAMES`: request
+        float32 [N, 7], solution float32 [N, 7], residual float32 [N], solved uint8 [N] -- 1 where the last `step_cartesian_device`
+        solved) or CART_* constant: a device view (DLPack / __cuda_array_interface__, zero copy; ordering as for the other device
+        buffers), or with host=True a numpy copy after a wait."""
+        which = nat.CARTESIAN_NAMES.index(name) if isinstance(name, str) and name in nat.CARTESIAN_NAMES else name
+        if isinstance(which, bool) or not isinstance(which, (int, np.integer)) or not 0 <= which < len(nat.CARTESIAN_NAMES):
+            raise ValueError("unknown cartesian buffer %r (known: %s)" % (name, ', '.join(nat.CARTESIAN_NAMES)))
+        N = self.N
+        shape, dt = {nat.CART_REQUEST: ((N, 7), np.float32), nat.CART_SOLUTION: ((N, 7), np.float32), nat.CART_RESIDUAL: ((N,), np.float32),
+                     nat.CART_SOLVED: ((N,), np.uint8)}[int(which)]
+        if host:
+            out = np.empty(shape, dt)
+            nat.check(self.L.rr_cartesian_copy_to_host(self.h, int(which), out.ctypes.data, out.nbytes))
+            return out
+        p, n = C.c_void_p(), C.c_size_t()
+        nat.check(self.L.rr_cartesian_buffer(self.h, int(which), C.byref(p), C.byref(n)))
+        return nat.DeviceBuffer(p.value, shape, np.dtype(dt).str, self)
+
     def set_camera(self, view, proj):
         """Row-major 4x4 OpenGL view / projection matrices replacing the eye camera of this batch (None, None: the default eye)."""
         if view is None and proj is None:

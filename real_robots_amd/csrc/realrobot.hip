@@ -468,6 +468,7 @@ __device__ __forceinline__ void dispatch_order_class(int x, int N, int ntiles, i
 #include "rr_wrench.inc"    // k_ext_wrench: the term of external wrenches on robot bodies and objects in the preparation record, in front of a step's solve while wrenches are set (rr_set_external_wrenches)
 #include "rr_ik.inc"    // inverse kinematics and macro plans (K8)
 #include "rr_macro.inc"    // k_macro_decide / k_macro_replan / k_macro_invalidate: the re-plan decision of step_macro on the device, and a planner over the compact list of the envs that need a plan (rr_step_macro)
+#include "rr_cart.inc"    // k_cart_decide / k_cart_solve / k_cart_fetch / k_cart_invalidate: the IK decision of step_cartesian on the device, and a solver over the compact list of the envs that need a solve, the two seeds on neighbouring lanes (rr_step_cartesian)
 #include "rr_render.inc"    // rasteriser: k_raster, k_shade, the list-walking render kernels
 #include "rr_gather.inc"    // delta image records for the observation gather (k_pack_delta, k_apply_delta)
 #include "rr_episode.inc"    // k_episode, k_goal_image: goal table and per-env episode record (score, reward, done, auto-reset into the next goal)

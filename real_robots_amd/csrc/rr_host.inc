@@ -128,6 +128,10 @@ struct rr_env : ModelTables {
     // device-resident macro actions (rr_step_macro): the request record [N][4], the list of the envs that need a plan [N] with its length
     // behind it, the `replanned` bytes [N] of the last call; allocated by the first call, with the plan buffers where they are missing
     float *macro_req = nullptr; int *macro_list = nullptr; unsigned char *macro_replanned = nullptr;
+    // device-resident cartesian actions (rr_step_cartesian): the request record [N][7], its solution [N][7] and residual [N], the `solved`
+    // bytes [N] of the last call, the list of the envs that need a solve [N] with its length behind it, and the staging of a host
+    // caller's targets [N][7] and gripper commands [N][2]; one group, allocated by the first call
+    float *cart_req = nullptr, *cart_sol = nullptr, *cart_res = nullptr, *cart_stage = nullptr; unsigned char *cart_solved = nullptr; int *cart_list = nullptr;
     float *score_out = nullptr; unsigned char *score_mask = nullptr;            // lazily allocated (rr_evaluate_goals)
     float4 *co_contacts = nullptr; float2 *co_force = nullptr; unsigned *co_partners = nullptr;   // lazily allocated (rr_contact_observations)
     // The output buffers of the ten query families (rr_query.inc): qbuf[family][which], a family's group allocated together on first use for
@@ -2931,6 +2935,109 @@ int rr_macro_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
     void *p = nullptr; size_t b = 0;
     RRCHK(macro_field(e, which, &p, &b, "rr_macro_copy_to_host"));
     if (bytes != b) return fail(RR_EINVAL, "rr_macro_copy_to_host: size mismatch");
+    HIPCHK(hipMemcpyAsync(dst, p, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return RR_OK;
+}
+
+// ---- device-resident cartesian actions (rr_cart.inc) ------------------------------------------------------------------------------------
+// The record, its solution and residual, the `solved` bytes, the need list and the staging of a host caller's targets and gripper
+// commands on first use: one group, all or nothing.  The record starts all NaN (one launch behind the allocation): no request equals it.
+static int ensure_cartesian(rr_env *e, const char *who) {
+    if (e->cart_req) return RR_OK;
+    const size_t N = e->P.N;
+    RRCHK(ensure_group(e, -1, who, "the cartesian record, solution and list",
+                       {mem_part(&e->cart_req, N * 28), mem_part(&e->cart_sol, N * 28), mem_part(&e->cart_res, N * 4), mem_part(&e->cart_solved, N),
+                        mem_part(&e->cart_list, (N + 1) * 4), stage_part(&e->cart_stage, N * 36)}));
+    hipLaunchKernelGGL(k_cart_invalidate, dim3((unsigned)((N * 7 + 255) / 256)), dim3(256), 0, e->stream, (int)N, (const unsigned char *)nullptr, e->cart_req);
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+// Whether the runtime knows `p` to live on the other side than the flag says: pageable host memory under on_device (a kernel could not
+// read it), device memory under !on_device.  Pinned and managed memory serve either side.  A host-side table lookup: no wait.
+static bool cart_other_side(const void *p, bool on_device) {
+    hipPointerAttribute_t a = {};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return on_device; }      // (unknown to the runtime: pageable host memory)
+    return on_device ? a.type == hipMemoryTypeUnregistered : a.type == hipMemoryTypeDevice;
+}
+
+// One step of cartesian actions decided on the device.  Launch order on the main stream: staging (host arguments only), k_cart_decide,
+// k_cart_solve, k_cart_fetch, rr_step.  Device arguments are read in place and nothing waits; host arguments go through the staging
+// helper, whose wait stands at the end because they are host memory.  The grid of k_cart_solve is sized from N (up to CS_WAVES listed
+// envs a workgroup each, beyond that ceil(count / CS_WAVES) envs per workgroup, at most CS_SLOTS): the list's length stays on the device.
+int rr_step_cartesian(rr_env *e, const float *cartesian, const float *gripper, const uint8_t *idle, int32_t on_device, int32_t render_mode,
+                      const uint8_t *render_flags_host) {
+    if (!e) return fail(RR_EINVAL, "rr_step_cartesian: null env");
+    if (!cartesian) return fail(RR_EINVAL, "rr_step_cartesian: null cartesian");
+    if (!gripper) return fail(RR_EINVAL, "rr_step_cartesian: null gripper");
+    // (checked here as well: the decision moves records, which must not happen for a step rr_step then rejects)
+    if (render_mode < 0 || render_mode > 2 || (render_mode == 2 && !render_flags_host)) return fail(RR_EINVAL, "rr_step_cartesian: bad render_mode");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    // one flag covers the three arrays: an array the runtime knows to live on the other side makes the set a mixed one
+    const void *const arrays[3] = {cartesian, gripper, idle};
+    static const char *const names[3] = {"cartesian", "gripper", "idle"};
+    for (int i = 0; i < 3; i++)
+        if (arrays[i] && cart_other_side(arrays[i], on_device != 0))
+            return fail(RR_EINVAL, std::string("rr_step_cartesian: cartesian, gripper and idle must live on the same side (on_device says the ") +
+                                       (on_device ? "device" : "host") + ", " + names[i] + " is on the " + (on_device ? "host" : "device") + ")");
+    RRCHK(ensure_cartesian(e, "rr_step_cartesian"));
+    const int N = e->P.N;
+    const HostStaging st = {e, !on_device};
+    // (host targets and gripper commands travel through the group's own staging block, [N][7] then [N][2]; a host idle mask through mask_dev)
+    RRCHK(st.in(cartesian, e->cart_stage, (size_t)N * 28));
+    RRCHK(st.in(gripper, e->cart_stage + (size_t)N * 7, (size_t)N * 8));
+    const unsigned char *idle_dev = idle;
+    if (idle && !on_device) { HIPCHK(hipMemcpyAsync(e->mask_dev, idle, N, hipMemcpyHostToDevice, e->stream)); idle_dev = e->mask_dev; }
+    hipLaunchKernelGGL(k_cart_decide, dim3(1), dim3(MD_THREADS), 0, e->stream, N, cartesian, idle_dev, e->cart_req, e->cart_solved, e->cart_list);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_cart_solve, dim3((unsigned)std::min(N, std::max(CS_WAVES, (N + CS_SLOTS - 1) / CS_SLOTS))), dim3(64), 0, e->stream, e->IK, e->P, e->D, (const float *)e->cart_req, (const int *)e->cart_list, e->cart_sol, e->cart_res);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_cart_fetch, dim3((N + 255) / 256), dim3(256), 0, e->stream, e->P, e->D, (const float *)e->cart_sol, gripper, idle_dev);
+    HIPCHK(hipGetLastError());
+    const int rc = rr_step(e, e->D.cmd, 1, render_mode, render_flags_host);
+    const int rw = st.wait();
+    return rc != RR_OK ? rc : rw;
+}
+
+int rr_cartesian_invalidate(rr_env *e, const uint8_t *env_mask, int32_t mask_on_device) {
+    if (!e) return fail(RR_EINVAL, "rr_cartesian_invalidate: null env");
+    if (!e->cart_req) return RR_OK;      // no record yet: it is created all NaN
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const int N = e->P.N;
+    const unsigned char *m = env_mask;
+    const bool host_mask = env_mask && !mask_on_device;
+    if (host_mask) { HIPCHK(hipMemcpyAsync(e->mask_dev, env_mask, N, hipMemcpyHostToDevice, e->stream)); m = e->mask_dev; }
+    hipLaunchKernelGGL(k_cart_invalidate, dim3((unsigned)((N * 7 + 255) / 256)), dim3(256), 0, e->stream, N, m, e->cart_req);
+    HIPCHK(hipGetLastError());
+    if (host_mask) HIPCHK(hipStreamSynchronize(e->stream));   // the argument is host memory
+    return RR_OK;
+}
+
+static int cartesian_field(rr_env *e, int32_t which, void **ptr, size_t *bytes, const char *who) {
+    if (!e || which < 0 || which >= RR_CART_COUNT) return fail(RR_EINVAL, std::string(who) + ": bad buffer");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    RRCHK(ensure_cartesian(e, who));
+    const size_t N = e->P.N;
+    void *const p[RR_CART_COUNT] = {e->cart_req, e->cart_sol, e->cart_res, e->cart_solved};
+    const size_t b[RR_CART_COUNT] = {N * 28, N * 28, N * 4, N};
+    *ptr = p[which]; *bytes = b[which];
+    return RR_OK;
+}
+
+int rr_cartesian_buffer(rr_env *e, int32_t which, void **dev_ptr, size_t *bytes) {
+    void *p = nullptr; size_t b = 0;
+    RRCHK(cartesian_field(e, which, &p, &b, "rr_cartesian_buffer"));
+    if (dev_ptr) *dev_ptr = p;
+    if (bytes) *bytes = b;
+    return RR_OK;
+}
+
+int rr_cartesian_copy_to_host(rr_env *e, int32_t which, void *dst, size_t bytes) {
+    if (!dst) return fail(RR_EINVAL, "rr_cartesian_copy_to_host: null destination");
+    void *p = nullptr; size_t b = 0;
+    RRCHK(cartesian_field(e, which, &p, &b, "rr_cartesian_copy_to_host"));
+    if (bytes != b) return fail(RR_EINVAL, "rr_cartesian_copy_to_host: size mismatch");
     HIPCHK(hipMemcpyAsync(dst, p, bytes, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return RR_OK;
